@@ -2,15 +2,20 @@
 """
 bench.py - headline measurement: filter steps/s of the batched Monte-Carlo GPQ-Kalman filter on the UNGM model
 (BASELINE.json configs[1]: GaussianProcessTransform (RBF, UT points), D = 1, N = 3, 1e4 MC trajectories per GPU,
-T = 100 time steps), plus the achieved-bandwidth figure of the batched GPQ moment transform at state-dim 6 / 1e5
-trajectories (BASELINE.json north_star target).
+T = 100 time steps), and with --full the achieved-bandwidth figure of the batched GPQ moment transform at state-dim 6 /
+1e5 trajectories (BASELINE.json north_star target).
 
 One "step" of this bench = one forward pass of the filter over the whole batch = B * T filter steps (each: two moment
 transforms + one measurement update).  Inputs (measurements, initial moments, weights) are resident in HBM before the
 timed region; filtered means / covariances of every step are written to HBM (forward_pass returns all of them).
 
-Launch:  python bench.py [--gpus N --steps K --warmup W]          (N = 1)
+Launch:  python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]          (N = 1)
          python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...   (one rank per GPU)
+A plain run sets up, warms up, times the K passes and prints the result line: the contract keys, `config` without the
+all-reduce figures, and `roofline` for the headline kernel only (no `target_*` / `saturated_*`).  --full adds everything
+else: the timing blocks, the final aggregation (RMSE / NLL, `config.allreduce_us` / `allreduce_bytes`), the CPU baselines
+and the secondary legs with the north-star transform (--no-cpu-baseline / --no-mt6 leave parts of it out).  --dump-outputs DIR writes what
+the last timed pass returned (filtered means, covariances, status; float64 .npy, at most 64 MB: dump_outputs).
 Independent MC trajectories shard across ranks with no data-path collective (weak scaling: B per GPU fixed); the only
 collective is the final all-reduce of the per-step error sums: RCCL behind the C ABI (ssmq_allreduce_sum), rendezvous
 from the launcher's environment (RANK / WORLD_SIZE / LOCAL_RANK / MASTER_PORT).  No PyTorch in this process; compute
@@ -18,8 +23,8 @@ goes python -> ctypes -> libssmq.so (HIP).  (SSMQ_BENCH_BACKEND=gloo swaps in a 
 rehearsals with several ranks on one GPU.)
 
 OUTPUT.  The LAST line of stdout is the result record: one line of strict JSON of at most 4 kB with scalars only (the
-contract keys, `roofline` with the north-star transform as `target_*`, `cpu_baseline`, one number per secondary leg under
-`legs`; benchlib/record.py).  The full record of every leg goes to bench_detail.json next to this file (--detail PATH) and
+contract keys, `roofline`; with --full also the north-star transform as `roofline.target_*`, `cpu_baseline`, one number per
+secondary leg under `legs`; benchlib/record.py).  The full record of every leg goes to bench_detail.json next to this file (--detail PATH) and
 to stderr.  The legs themselves live in benchlib/ (workloads.py, legs.py, launch.py, common.py).
 """
 import argparse
@@ -33,6 +38,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 SETTLE_S = 0.06          # continuous untimed passes before the warm-up passes (clock ramp-up after the idle set-up)
+DUMP_LIMIT = 64 << 20    # bytes of --dump-outputs in all
 
 from benchlib.common import (HBM_PEAK_GBS, CLOCK_HZ, F64_MFMA_PEAK_TF, pmc_traffic, pmc_traffic_named, pmc_traffic_source, pmc_issue,     # noqa: E402,F401
                              issue_block, settle, timed_passes, cpu_port_info, host_cores, c_port_transforms,
@@ -40,7 +46,7 @@ from benchlib.common import (HBM_PEAK_GBS, CLOCK_HZ, F64_MFMA_PEAK_TF, pmc_traff
 from benchlib.workloads import simulate_ungm, simulate_reentry, synthetic_reentry6, FilterBench                        # noqa: E402,F401
 from benchlib.legs import (Mt6Bench, Study6Bench, measure_study6, register_kernel_ms, C5GemmBench, measure_c5_unisolvent, measure_c5_degree7, measure_linearize,        # noqa: E402,F401
                            measure_theta_step, filter_leg, saturated_sweep, measure_api_rate, c5_full_record)
-from benchlib.launch import make_comm, final_aggregation, free_port, child_env, needs_launcher, launch_ranks, rank_devices  # noqa: E402,F401
+from benchlib.launch import make_comm, final_aggregation, rank_slots, free_port, child_env, needs_launcher, launch_ranks, rank_devices  # noqa: E402,F401
 from benchlib.record import compact_record, result_line, write_detail                                                  # noqa: E402,F401
 
 
@@ -60,6 +66,22 @@ def headline_blocks(wl, steps, blocks=5):
     return [float(v) for v in out], per
 
 
+def dump_outputs(wl, path, limit=DUMP_LIMIT):
+    """What the timed pass hands a caller, from its last step: filtered means (D, T, B), covariances (D, D, T, B) and the
+    per-trajectory status (B,), as float64 .npy files under `path`.  Beyond `limit` bytes in all, the same fixed, seeded
+    sample of trajectories is written for every array, and its indices as trajectory_index.npy."""
+    fm, fP, st = wl.results()
+    B = st.shape[0]
+    per_traj = 8 * (fm.size + fP.size + st.size) // B
+    os.makedirs(path, exist_ok=True)
+    if per_traj * B > limit:
+        keep = np.sort(np.random.default_rng(0).choice(B, limit // (per_traj + 8), replace=False))
+        fm, fP, st = fm[..., keep], fP[..., keep], st[keep]
+        np.save(os.path.join(path, 'trajectory_index.npy'), keep.astype(np.float64))
+    for name, a in (('filtered_mean', fm), ('filtered_cov', fP), ('status', st)):
+        np.save(os.path.join(path, name + '.npy'), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -74,8 +96,12 @@ def main():
     ap.add_argument('--workload', default='ungm', choices=['ungm', 'reentry5', 'reentry6', 'ct'],
                     help="'ungm' is the headline (BASELINE configs[1]); the others are extra measurements")
     ap.add_argument('--filter', default='gpqkf', choices=['gpqkf', 'ukf', 'tpqkf', 'bsqkf'])
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-mt6', action='store_true', help='skip the single-kernel / other-config legs of the N = 1 run')
+    ap.add_argument('--full', action='store_true',
+                    help='also the timing blocks, RMSE / NLL, the CPU baselines and the secondary legs (off: the headline only)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the outputs of the last timed pass to DIR/<name>.npy (rank 0)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baselines')
+    ap.add_argument('--no-mt6', action='store_true', help='with --full: skip the single-kernel / other-config legs of the N = 1 run')
     ap.add_argument('--detail', default=os.path.join(ROOT, 'bench_detail.json'),
                     help='where the full record of every leg goes (the stdout line keeps scalars only)')
     args = ap.parse_args()
@@ -124,14 +150,19 @@ def main():
     pass_ms_dev = ev0.elapsed_ms(ev1) / max(args.steps, 1)
     comm.barrier()                      # ... closing barrier; the job's time is the slowest rank's
     elapsed = float(comm.allreduce_max(np.array([elapsed]))[0])
-    block_ms, block_len = headline_blocks(wl, args.steps)      # outside the contract's region: stability of the figure
-
-    # final aggregation: per-time-step error sums -> RMSE / NLL (the path's only collective)
-    fa = final_aggregation(
-        comm, rank, world, mcshard.device_error_sums(wl.D, B, wl.ld, T, wl.d_x, wl.d_fm, wl.d_fP, wl.d_st),
-        lambda mse: mcshard.device_lcr_sums(wl.D, B, wl.ld, T, wl.d_x, wl.d_fm, wl.d_fP, mse, wl.d_st), pass_ms_dev, B)
-    agg, lcr, slot, allreduce_us, n_packed = fa['agg'], fa['lcr'], fa['slot'], fa['allreduce_us'], fa['n_packed']
-    rmse, nll = agg['rmse_total'], float(agg['nll_avg'].mean())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(wl, args.dump_outputs)
+    full = args.full
+    if full:
+        block_ms, block_len = headline_blocks(wl, args.steps)      # outside the contract's region: stability of the figure
+        # final aggregation: per-time-step error sums -> RMSE / NLL (the path's only collective)
+        fa = final_aggregation(
+            comm, rank, world, mcshard.device_error_sums(wl.D, B, wl.ld, T, wl.d_x, wl.d_fm, wl.d_fP, wl.d_st),
+            lambda mse: mcshard.device_lcr_sums(wl.D, B, wl.ld, T, wl.d_x, wl.d_fm, wl.d_fP, mse, wl.d_st), pass_ms_dev, B)
+        agg, lcr, slot, allreduce_us, n_packed = fa['agg'], fa['lcr'], fa['slot'], fa['allreduce_us'], fa['n_packed']
+        rmse, nll = agg['rmse_total'], float(agg['nll_avg'].mean())
+    else:
+        slot = rank_slots(comm, rank, world, pass_ms_dev, B)      # the headline needs the trajectory total only
 
     out = None
     headline = args.workload == 'ungm' and args.filter == 'gpqkf'
@@ -156,7 +187,6 @@ def main():
                        'settle_s': SETTLE_S,
                        'per_rank_kernel_ms': [float(v) for v in slot[:world]],
                        'per_rank_trajectories': [int(round(v)) for v in slot[world:]],
-                       'allreduce_us': allreduce_us, 'allreduce_bytes': 8 * n_packed,
                        'collective': type(comm).__name__ + (
                            ' (gloo fallback: ' + comm.fallback_reason + ')' if getattr(comm, 'fallback_reason', '') else ''),
                        'devices': devices['compact'], 'distinct_devices': devices['distinct'], 'per_rank_devices': devices['per_rank'],
@@ -166,23 +196,27 @@ def main():
                          'traffic_source': pmc_traffic_source(), 'kernel': wl.kernel,
                          'bytes_per_launch': bytes_pass, 'ms_per_launch': pass_ms_dev,
                          'note': 'the contract\'s HBM figure for the headline filter pass (a serial recursion per trajectory: '
-                                 'roofline_issue and DESIGN.md 3.4); the north-star transform is target_*'},
-            'ms_per_step_median': float(np.median(block_ms)), 'ms_per_step_min_block': min(block_ms),
-            'ms_per_step_max_block': max(block_ms), 'timing_blocks': '{} x {} passes, HIP events'.format(len(block_ms), block_len),
-            'ms_per_step_blocks': block_ms,
-            'rmse': rmse, 'nll': nll, 'inclination_indicator': float(np.mean(lcr)),
-            'trajectories_aggregated': int(agg['count']),
-            # what the averages above leave out (summed over ranks, worst time step): failed filters / singular covariances
-            'excluded_failed_trajectories': int(agg['excluded_failed'].max()) if T else 0,
-            'excluded_singular_covariances': int(agg['excluded_not_pd'].max()) if T else 0,
+                                 'roofline_issue and DESIGN.md 3.4); with --full the north-star transform is target_*'},
         }
+        if full:
+            out['config'].update({'allreduce_us': allreduce_us, 'allreduce_bytes': 8 * n_packed})
+            out.update({
+                'ms_per_step_median': float(np.median(block_ms)), 'ms_per_step_min_block': min(block_ms),
+                'ms_per_step_max_block': max(block_ms), 'timing_blocks': '{} x {} passes, HIP events'.format(len(block_ms), block_len),
+                'ms_per_step_blocks': block_ms,
+                'rmse': rmse, 'nll': nll, 'inclination_indicator': float(np.mean(lcr)),
+                'trajectories_aggregated': int(agg['count']),
+                # what the averages above leave out (summed over ranks, worst time step): failed filters / singular covariances
+                'excluded_failed_trajectories': int(agg['excluded_failed'].max()) if T else 0,
+                'excluded_singular_covariances': int(agg['excluded_not_pd'].max()) if T else 0,
+            })
         if world > 1 and type(comm).__name__ == 'RcclComm' and devices['distinct'] != world:
             raise SystemExit('bench.py: {} ranks over RCCL on {} distinct device(s): {}'.format(world, devices['distinct'],
                                                                                               devices['per_rank']))
         ib = issue_block(wl.kernel, T, pass_ms_dev)
         if ib:
             out['roofline_issue'] = ib
-    single = world == 1      # the single-kernel legs and the CPU baselines belong to the N = 1 run only
+    single = world == 1 and full      # the single-kernel legs and the CPU baselines belong to the N = 1 run with --full only
     with_cpu = not args.no_cpu_baseline
     if rank == 0 and single and with_cpu and headline:
         cb, cpu_fm, _, cpu_st = cpu_baseline_filter(wl, B, 8.0, 'UNGM GPQ-Kalman (configs[1])')

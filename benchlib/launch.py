@@ -43,6 +43,14 @@ def make_comm():
     return comm, rank, world, local_rank
 
 
+def rank_slots(comm, rank, world, pass_ms_dev, B):
+    """Every rank's launch time and trajectory count, gathered on all ranks by one all-reduce of a zero array in which each
+    rank fills its own two slots: [ms_0 .. ms_(world-1), B_0 .. B_(world-1)]."""
+    slot = np.zeros(2 * world)
+    slot[rank], slot[world + rank] = pass_ms_dev, B
+    return comm.allreduce_sum(slot)
+
+
 def final_aggregation(comm, rank, world, loc, lcr_sums_of, pass_ms_dev, B):
     """What every rank does after its timed passes - the path's only collectives:
     phase 1: this rank's per-time-step error sums `loc` (mcshard.device_error_sums: reduced on the device from the filter's
@@ -53,9 +61,7 @@ def final_aggregation(comm, rank, world, loc, lcr_sums_of, pass_ms_dev, B):
     from ssmtoybox_amd import mcshard
     agg = mcshard.finalize(mcshard.allreduce_sums(loc, comm))
     lcr = mcshard.finalize_lcr(mcshard.allreduce_sums(lcr_sums_of(agg['mse']), comm))
-    slot = np.zeros(2 * world)
-    slot[rank], slot[world + rank] = pass_ms_dev, B
-    slot = comm.allreduce_sum(slot)
+    slot = rank_slots(comm, rank, world, pass_ms_dev, B)
     n_packed = sum(int(np.asarray(v).size) for v in loc.values())
     lat = []
     comm.barrier()

@@ -7,6 +7,6 @@ set -e
 out=${1:-gpurun_out/pmc}
 export TMPDIR=/tmp
 mkdir -p "$out"
-rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$out/fetch" -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline > "$out/fetch.log" 2>&1
-rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$out/write" -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline > "$out/write.log" 2>&1
+rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$out/fetch" -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline > "$out/fetch.log" 2>&1
+rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$out/write" -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline > "$out/write.log" 2>&1
 find "$out" -name '*counter_collection.csv' | head

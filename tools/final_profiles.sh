@@ -7,8 +7,8 @@ out=gpurun_out/$tag
 mkdir -p $out
 # the tree these numbers belong to: tools/stamp_tree.sh writes TREE_ID before the gpurun call (there is no .git on the GPU box)
 export SSMQ_COMMIT=$(cat TREE_ID 2>/dev/null || echo unknown)
-python bench.py --detail $out/bench_detail.json > $out/bench.json 2> $out/bench.err      # bench.json: the result line (what the driver keeps)
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof -- python3 bench.py --no-cpu-baseline --detail $out/bench_prof_detail.json > $out/bench_prof.json 2> $out/bench_prof.err
+python bench.py --full --detail $out/bench_detail.json > $out/bench.json 2> $out/bench.err      # bench.json: the result line (what the driver keeps)
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof -- python3 bench.py --full --no-cpu-baseline --detail $out/bench_prof_detail.json > $out/bench_prof.json 2> $out/bench_prof.err
 bash profiles/collect_pmc.sh $out/pmc > $out/pmc.log 2>&1
 bash tools/pmc_fused.sh $out/pmc_fused > $out/pmc_fused.log 2>&1
 python profiles/pmc_summary.py $out/pmc > $out/pmc_traffic.json

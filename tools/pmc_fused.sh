@@ -6,8 +6,8 @@ set -e
 out=${1:-gpurun_out/pmc_fused}
 export TMPDIR=/tmp
 mkdir -p "$out"
-rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_SMEM SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY --output-format csv -d "$out/a" -- python3 bench.py --steps 50 --warmup 5 --no-cpu-baseline > "$out/a.log" 2>&1
-rocprofv3 --pmc SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_SCA SQ_INSTS_VMEM_WR SQ_INSTS_VMEM_RD SQ_ACTIVE_INST_VMEM GRBM_GUI_ACTIVE --output-format csv -d "$out/b" -- python3 bench.py --steps 50 --warmup 5 --no-cpu-baseline > "$out/b.log" 2>&1
+rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_SMEM SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY --output-format csv -d "$out/a" -- python3 bench.py --full --steps 50 --warmup 5 --no-cpu-baseline > "$out/a.log" 2>&1
+rocprofv3 --pmc SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_SCA SQ_INSTS_VMEM_WR SQ_INSTS_VMEM_RD SQ_ACTIVE_INST_VMEM GRBM_GUI_ACTIVE --output-format csv -d "$out/b" -- python3 bench.py --full --steps 50 --warmup 5 --no-cpu-baseline > "$out/b.log" 2>&1
 python3 - "$out" <<'PY'
 import csv, glob, sys, collections
 root = sys.argv[1]

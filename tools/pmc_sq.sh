@@ -4,8 +4,8 @@ set -e
 out=${1:-gpurun_out/pmc_sq}
 export TMPDIR=/tmp
 mkdir -p "$out"
-rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_SMEM SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY --output-format csv -d "$out/a" -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline > "$out/a.log" 2>&1
-rocprofv3 --pmc SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_SCA SQ_INST_CYCLES_VMEM SQ_WAIT_INST_LDS SQ_INSTS_VMEM_WR SQ_INSTS_VMEM_RD GRBM_GUI_ACTIVE --output-format csv -d "$out/b" -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline > "$out/b.log" 2>&1
+rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_SMEM SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY --output-format csv -d "$out/a" -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline > "$out/a.log" 2>&1
+rocprofv3 --pmc SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_SCA SQ_INST_CYCLES_VMEM SQ_WAIT_INST_LDS SQ_INSTS_VMEM_WR SQ_INSTS_VMEM_RD GRBM_GUI_ACTIVE --output-format csv -d "$out/b" -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline > "$out/b.log" 2>&1
 python3 - "$out" <<'PY'
 import csv, glob, sys, collections
 root = sys.argv[1]
