@@ -35,8 +35,10 @@
 #ifndef SSMQ_H
 #define SSMQ_H
 
+#ifndef __HIPCC_RTC__   /* the run-time compiler (csrc/ssmq_rtc.hip) supplies these itself */
 #include <stddef.h>
 #include <stdint.h>
+#endif
 
 #ifdef __cplusplus
 extern "C" {
@@ -77,6 +79,35 @@ enum ssmq_integrand_id {
                                       quadrature at D = 10 is BASELINE config 5): out[i] = sin(x[i]) + x[5+i]^2,
                                       out[5+i] = x[5+i] cos(x[i]), i = 0..4; in 10 out 10; no state index */
 };
+
+/*
+ * User-defined integrands, compiled for the device at run time (csrc/ssmq_rtc.hip, ROCm's hiprtc).  A model's function body
+ * is registered once and gets an id in [SSMQ_F_USER_FIRST, SSMQ_F_USER_FIRST + SSMQ_F_USER_SLOTS); the body is placed inside
+ *     template <int E> __device__ void eval(const double *x, double *o) const { const double t = ..; const double *p = ..; { BODY } }
+ * with x the `din` inputs, o the `dout` outputs, t the time index the built-in integrands receive and p the n_par constants of
+ * ssmq_integrand.par; it may call the helpers of csrc/ssmq_math.h / ssmq_device.h (sin_nr, sincos_nr, atan2_nr, exp_nr, div_nr,
+ * sqrt_rsqrt) and the device math functions.  At most SSMQ_USER_BODY_MAX characters, braces balanced, no preprocessor lines.
+ * Idempotent: the same (body, din, dout) returns the same id.  1 <= din, dout <= SSMQ_MAX_DIM.
+ * User ids run on: ssmq_filter_forward_dev / ssmq_student_filter_forward_dev (additive noise; the whole-pass kernel compiled for
+ * the pair of models, D <= 6, Y <= 4, ND, NO <= 2 D + 1, no state index) and ssmq_apply_batch[_dev] / ssmq_apply_kernel_name
+ * (k_apply_small, the same shape range).  Every other entry point that takes an ssmq_integrand returns SSMQ_E_UNSUPPORTED.
+ * Compiled kernels are cached in the process (key: body hashes, kernel, template arguments, device architecture).
+ */
+#define SSMQ_F_USER_FIRST 1024
+#define SSMQ_F_USER_SLOTS 64
+#define SSMQ_USER_BODY_MAX 8192
+#define SSMQ_USER_MAX_D 6
+#define SSMQ_USER_MAX_Y 4
+int ssmq_integrand_define(const char *body, int din, int dout, int uses_time, int32_t *id);
+/* Compile only (no device needed): kind SSMQ_RTC_FILTER instantiates k_filter_fused<D, E (= Y), N, N_obs, id, id_obs, form, tp,
+ * 0, opt> (id_obs: any integrand id), SSMQ_RTC_APPLY k_apply_small<D, E, N, id, form, tp, 0, opt> (id_obs, N_obs ignored), for
+ * `arch` (e.g. "gfx950").  On success `log` gets the lowered kernel name on its first line, then the compiler's resource
+ * remarks (registers, spills); on failure the compiler log.  Returns SSMQ_OK, SSMQ_E_ARG or SSMQ_E_UNSUPPORTED (compile error). */
+enum ssmq_rtc_kind { SSMQ_RTC_FILTER = 0, SSMQ_RTC_APPLY = 1 };
+int ssmq_rtc_compile_check(int32_t id, int32_t id_obs, int kind, int D, int E, int N, int N_obs, int form, int tp, int opt,
+                           const char *arch, char *log, int len);
+/* Process-wide counters of the run-time compiler: programs compiled, kernel lookups served from the cache, compile wall time. */
+int ssmq_rtc_stats(int64_t *compiles, int64_t *cache_hits, double *compile_seconds);
 
 /* One integrand = id + constants + optional sub-state selection (MeasurementModel.state_index, ssmod.py:990-991):
  * if n_idx > 0 the integrand sees x[idx[0]], x[idx[1]], ... of the D-dimensional sigma point. */

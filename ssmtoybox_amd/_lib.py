@@ -23,6 +23,9 @@ F_UNGM_DYN, F_UNGM_MEAS, F_UNGMNA_DYN, F_UNGMNA_MEAS = 1, 2, 3, 4
 F_PENDULUM_DYN, F_PENDULUM_MEAS, F_REENTRY1D_DYN, F_RANGE_MEAS = 5, 6, 7, 8
 F_REENTRY2D_DYN, F_RADAR2D_MEAS, F_CT_DYN, F_BEARING_MEAS = 9, 10, 11, 12
 F_CTRS_DYN, F_CV_DYN, F_REENTRY2D_BIAS_DYN, F_SMOOTH10D_DYN = 13, 14, 15, 16
+# user-defined integrands, compiled for the device at run time (include/ssmq.h ssmq_integrand_define)
+F_USER_FIRST, F_USER_SLOTS, USER_BODY_MAX, USER_MAX_D, USER_MAX_Y = 1024, 64, 8192, 6, 4
+RTC_FILTER, RTC_APPLY = 0, 1
 
 
 class SsmqError(RuntimeError):
@@ -225,6 +228,12 @@ _PROTOTYPES = {
     'ssmq_allreduce_max': (ctypes.c_int, [c_double_p, ctypes.c_int64]),
     'ssmq_comm_barrier': (ctypes.c_int, []),
     'ssmq_comm_destroy': (ctypes.c_int, []),
+    'ssmq_integrand_define': (ctypes.c_int, [ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_int32_p]),
+    'ssmq_rtc_compile_check': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                              ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_char_p,
+                                              ctypes.c_char_p, ctypes.c_int]),
+    'ssmq_rtc_stats': (ctypes.c_int, [ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64),
+                                      ctypes.POINTER(ctypes.c_double)]),
 }
 
 BFGS_MAXITER, BFGS_PRECISION_LOSS, BFGS_NAN, BFGS_FALLBACK, BFGS_PRIOR_NOT_PD = 1, 2, 3, 100, 101     # include/ssmq.h
@@ -264,6 +273,30 @@ def load():
 
 def last_error():
     return load().ssmq_last_error().decode('utf-8', 'replace')
+
+
+def define_integrand(body, din, dout, uses_time):
+    """Register a user integrand's device function body (include/ssmq.h ssmq_integrand_define): returns its id."""
+    fid = ctypes.c_int32()
+    check(load().ssmq_integrand_define(body.encode('utf-8'), int(din), int(dout), 1 if uses_time else 0, ctypes.byref(fid)),
+          'ssmq_integrand_define')
+    return fid.value
+
+
+def rtc_compile_check(fid, kind, D, E, N, form, tp=0, opt=0, fid_obs=0, N_obs=0, arch='gfx950'):
+    """Compile one run-time kernel for `arch` without a device: (rc, log) - the lowered name and the resource remarks on
+    success, the compiler log otherwise."""
+    buf = ctypes.create_string_buffer(1 << 16)
+    rc = load().ssmq_rtc_compile_check(int(fid), int(fid_obs), int(kind), int(D), int(E), int(N), int(N_obs), int(form), int(tp),
+                                       int(opt), arch.encode(), buf, len(buf))
+    return rc, buf.value.decode('utf-8', 'replace')
+
+
+def rtc_stats():
+    """(compiles, cache_hits, compile_seconds) of the run-time compiler in this process."""
+    c, h, s = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_double()
+    check(load().ssmq_rtc_stats(ctypes.byref(c), ctypes.byref(h), ctypes.byref(s)), 'ssmq_rtc_stats')
+    return c.value, h.value, s.value
 
 
 def check(rc, what=''):

@@ -687,6 +687,26 @@ int apply_dev_impl(ssmq_transform *h, const ssmq_integrand *f, int64_t B, int64_
     FInfo fi;
     int rc = check_integrand(h, f, &fi);
     if (rc) return rc;
+    if (is_user_integrand(f)) {
+        // a user-defined integrand: k_apply_small compiled for it at run time (ssmq_rtc.hip), nothing else
+        if (h->form == SSMQ_FORM_TAYLOR1) return refuse_user_integrand("linearisation transform (k_linearize)");
+        ApplyArgs a;
+        memset(&a, 0, sizeof(a));
+        if (!dry_run && B > 0) {
+            if (!d_mean || !d_cov || !d_mean_f || !d_cov_f || !d_cov_fx || !d_status || (fi.uses_time && !d_time) || ld < B) {
+                set_error("apply: null pointer or ld < B");
+                return SSMQ_E_ARG;
+            }
+            a.mean = d_mean; a.cov = d_cov; a.time = d_time ? d_time : d_mean; a.mean_f = d_mean_f; a.cov_f = d_cov_f;
+            a.cov_fx = d_cov_fx; a.status = d_status; a.consts = h->d_small;
+            a.cov_add = d_cov_add ? d_cov_add : h->d_small + const_layout(h->D, h->E, h->N, h->form).zero; a.B = B; a.ld = ld;
+            a.time_stride = d_time ? time_stride : 0; a.emv_mode = h->emv_mode; a.tp_nu = h->tp_nu;
+            a.cov_scale = cov_scale; a.ccov_scale = ccov_scale;
+            fill_fpar(f, &a.fp);
+        }
+        a.stream_out = stream_out ? 1 : 0;
+        return rtc_launch_apply(h, f, sel_pattern(f, fi.din), a, stream(), kernel_name, dry_run || B <= 0);
+    }
     if (h->form == SSMQ_FORM_TAYLOR1) {
         // the linearisation transform (mtran.py:49-59): no points, no weights, one launch (ssmq_linear.hip)
         if (kernel_name) *kernel_name = "k_linearize";
@@ -1577,6 +1597,9 @@ struct FilterCache {
     int T = -1, fid_dyn = -1, fid_obs = -1, D = -1, Y = -1;
     int64_t ld = -1;          // the constants sit behind the ld-sized planes: a new pitch moves them
     bool consts_ok = false;
+    void *user_ws = nullptr;          // constants of the run-time compiled filters (filter_forward_user): G Q G' | R | scale [T]
+    size_t user_bytes = 0;
+    std::vector<double> user_host;    // ... what the block holds
     void drop_graph() {
         if (exec) hipGraphExecDestroy(exec);
         if (graph) hipGraphDestroy(graph);
@@ -1610,6 +1633,10 @@ void reset_device_caches() {
     if (g_fc.ws) hipFree(g_fc.ws);
     g_fc.ws = nullptr;
     g_fc.ws_bytes = 0;
+    if (g_fc.user_ws) hipFree(g_fc.user_ws);
+    g_fc.user_ws = nullptr;
+    g_fc.user_bytes = 0;
+    g_fc.user_host.clear();
     drop_gemm_scratch();
     drop_staging_arena();
     reset_wide_attributes();
@@ -1621,6 +1648,58 @@ void reset_device_caches() {
     c.strip_bytes = 0;
 }
 }  // namespace ssmq
+
+// A pair of models of which one or both are user-defined integrands: the whole-pass kernel compiled for them at run time
+// (ssmq_rtc.hip) with the time loop's constants in a small per-context block of its own, or an error - never the launch loop.
+static int filter_forward_user(ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, ssmq_transform *h_obs, const ssmq_integrand *f_obs,
+                               int64_t B, int64_t ld, int T, const double *d_y, const double *d_m0, const double *d_P0,
+                               const double *GQG, const double *R, double *d_fm, double *d_fP, int32_t *d_status,
+                               const double *sscale, double student_dof, hipStream_t s) {
+    const int D = h_dyn->D, Y = h_obs->E;
+    FInfo fio, fid;
+    if (!integrand_info(f_obs->id, &fio) || !integrand_info(f_dyn->id, &fid)) {
+        set_error("unknown integrand id");
+        return SSMQ_E_ARG;
+    }
+    // G Q G' | R | scale [T] | time tables [T] x 2: a built-in member whose time dependence is tabulated on the host (UNGM) reads
+    // its table every step (HasTimeTable<> in ssmq_fused.h), as on the AOT route
+    const size_t nd = (size_t)D * D + (size_t)Y * Y + 3 * (size_t)T, need = sizeof(double) * nd;
+    if (g_fc.user_bytes < need) {
+        if (g_fc.user_ws) {
+            SSMQ_HIP(hipStreamSynchronize(s));
+            hipFree(g_fc.user_ws);
+        }
+        g_fc.user_ws = nullptr;
+        g_fc.user_bytes = 0;
+        g_fc.user_host.clear();
+        SSMQ_HIP(hipMalloc(&g_fc.user_ws, need));
+        g_fc.user_bytes = need;
+    }
+    std::vector<double> h(nd, 0.0);
+    if (GQG) std::copy(GQG, GQG + D * D, h.begin());
+    if (R) std::copy(R, R + Y * Y, h.begin() + D * D);
+    for (int k = 0; k < T; ++k) h[(size_t)D * D + Y * Y + k] = sscale ? sscale[k] : 1.0;
+    const size_t o_td = (size_t)D * D + Y * Y + T, o_to = o_td + T;
+    const bool has_td = time_table(f_dyn->id, T, h.data() + o_td), has_to = time_table(f_obs->id, T, h.data() + o_to);
+    double *w = (double *)g_fc.user_ws;
+    if (h != g_fc.user_host) {   // (stream order: earlier passes that read the block are done before the copy lands)
+        SSMQ_HIP(hipMemcpyAsync(w, h.data(), need, hipMemcpyHostToDevice, s));
+        SSMQ_HIP(hipStreamSynchronize(s));
+        g_fc.user_host = h;
+    }
+    FusedArgs a;
+    memset(&a, 0, sizeof(a));
+    a.y = d_y; a.m0 = d_m0; a.P0 = d_P0; a.fm = d_fm; a.fP = d_fP; a.status = d_status;
+    a.c_dyn = h_dyn->d_small; a.c_obs = h_obs->d_small; a.gqg = w; a.rr = w + D * D; a.B = B; a.ld = ld; a.T = T;
+    a.emv_dyn = h_dyn->emv_mode; a.emv_obs = h_obs->emv_mode; a.nu_dyn = h_dyn->tp_nu; a.nu_obs = h_obs->tp_nu;
+    a.sscale = sscale ? w + D * D + Y * Y : nullptr; a.student_dof = student_dof; a.lpw = 64;
+    fill_fpar(f_dyn, &a.fd);
+    fill_fpar(f_obs, &a.fo);
+    a.fd.ttab = has_td ? w + o_td : nullptr;
+    a.fo.ttab = has_to ? w + o_to : nullptr;
+    const int rc = rtc_launch_fused(h_dyn, f_dyn, h_obs, f_obs, sel_pattern(f_obs, fio.din), a, s, nullptr, false);
+    return rc < 0 ? rc : SSMQ_OK;
+}
 
 // sscale (host, [T]) / student_dof: Studentian recursion (ssinf.py:634-736); null / 0 for the Gaussian filters.
 int filter_forward_impl(ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, ssmq_transform *h_obs,
@@ -1639,6 +1718,8 @@ int filter_forward_impl(ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, ssmq
         set_error("filter_forward: additive-noise filter needs dyn (D -> D) and obs (D -> Y) transforms");
         return SSMQ_E_ARG;
     }
+    const bool user = is_user_integrand(f_dyn) || is_user_integrand(f_obs);
+    if (user && (d_pm || d_pP || d_pC)) return refuse_user_integrand("smoother (predictive moments kept)");
     int rc = ensure_device();
     if (rc) return rc;
     if (B == 0) return SSMQ_OK;
@@ -1647,6 +1728,8 @@ int filter_forward_impl(ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, ssmq
         return SSMQ_OK;
     }
     hipStream_t s = stream();
+    if (user) return filter_forward_user(h_dyn, f_dyn, h_obs, f_obs, B, ld, T, d_y, d_m0, d_P0, GQG, R, d_fm, d_fP, d_status, sscale,
+                                         student_dof, s);
     // workspace carve-up (doubles first, then the two int32 status planes)
     const size_t n_dbl = (size_t)ld * (D + 3 * D * D + Y + Y * Y + Y * D) + 4 * (size_t)T + D * D + Y * Y;
     const size_t need = sizeof(double) * n_dbl + 2 * sizeof(int32_t) * (size_t)ld;
@@ -1813,6 +1896,7 @@ static int filter_forward_aug_impl(ssmq_transform *h_dyn, const ssmq_integrand *
                                    const double *q_cov, int dq, const double *r_mean, const double *r_cov, int dr,
                                    double *d_fm, double *d_fP, int32_t *d_status, double *d_pm, double *d_pP,
                                    double *d_pC, int *c_cols) {
+    if (is_user_integrand(f_dyn) || is_user_integrand(f_obs)) return refuse_user_integrand("filter with non-additive noise (augmented moments)");
     if (!h_dyn || !h_obs || !f_dyn || !f_obs || dim_state <= 0 || dq < 0 || dr < 0 || B < 0 || ld < B || T < 0 || !d_y ||
         !d_m0 || !d_P0 || !d_fm || !d_fP || !d_status || (dq > 0 && (!q_mean || !q_cov)) ||
         (dr > 0 && (!r_mean || !r_cov))) {
@@ -1976,6 +2060,7 @@ extern "C" int ssmq_filter_smooth_aug_dev(ssmq_transform *h_dyn, const ssmq_inte
                                           const double *q_mean, const double *q_cov, int dq, const double *r_mean,
                                           const double *r_cov, int dr, double *d_fm, double *d_fP, double *d_sm,
                                           double *d_sP, int32_t *d_status) {
+    if (is_user_integrand(f_dyn) || is_user_integrand(f_obs)) return refuse_user_integrand("ssmq_filter_smooth_aug_dev");
     SSMQ_HANDLE_LOCK(h_dyn, h_obs);
     if (!h_dyn || !d_sm || !d_sP || dim_state <= 0 || dq < 0 || B < 0 || T < 0 || ld < B) {
         set_error("filter_smooth_aug: bad argument");
@@ -2026,6 +2111,7 @@ extern "C" int ssmq_filter_smooth_dev(ssmq_transform *h_dyn, const ssmq_integran
                                       const ssmq_integrand *f_obs, int64_t B, int64_t ld, int T, const double *d_y,
                                       const double *d_m0, const double *d_P0, const double *GQG, const double *R,
                                       double *d_fm, double *d_fP, double *d_sm, double *d_sP, int32_t *d_status) {
+    if (is_user_integrand(f_dyn) || is_user_integrand(f_obs)) return refuse_user_integrand("ssmq_filter_smooth_dev");
     SSMQ_HANDLE_LOCK(h_dyn, h_obs);
     if (!h_dyn || !d_sm || !d_sP || B < 0 || T < 0 || ld < B) {
         set_error("filter_smooth: bad argument");
@@ -2211,6 +2297,7 @@ extern "C" int ssmq_gp_theta_step(ssmq_transform *h_dyn, const ssmq_integrand *f
                                   double jitter, const double *mean, const double *cov, int shared_state,
                                   const double *y, int shared_y, double time, const double *GQG, const double *R,
                                   double *post_mean, double *post_cov, double *loglik, int32_t *status) {
+    if (is_user_integrand(f_dyn) || is_user_integrand(f_obs)) return refuse_user_integrand("ssmq_gp_theta_step");
     SSMQ_HANDLE_LOCK(h_dyn, h_obs);
     return gp_theta_step_impl(h_dyn, f_dyn, h_obs, f_obs, P, par_dyn, par_obs, jitter, mean, cov, shared_state, y, shared_y, time,
                               nullptr, GQG, R, post_mean, post_cov, loglik, status);
@@ -2223,6 +2310,7 @@ extern "C" int ssmq_gp_theta_step_times(ssmq_transform *h_dyn, const ssmq_integr
                                         double jitter, const double *mean, const double *cov, int shared_state,
                                         const double *y, int shared_y, const double *times, const double *GQG, const double *R,
                                         double *post_mean, double *post_cov, double *loglik, int32_t *status) {
+    if (is_user_integrand(f_dyn) || is_user_integrand(f_obs)) return refuse_user_integrand("ssmq_gp_theta_step_times");
     SSMQ_HANDLE_LOCK(h_dyn, h_obs);
     if (!times) {
         set_error("gp_theta_step_times: times is NULL");
@@ -2590,6 +2678,7 @@ extern "C" int ssmq_simulate_rv_dev(const ssmq_integrand *f_dyn, const ssmq_inte
                                     const ssmq_rv *q, const ssmq_rv *r, const double *G, int dyn_additive, int obs_additive,
                                     int64_t B, int64_t ld, int T, int continuous, double dt, uint64_t seed,
                                     uint64_t traj_offset, double *d_x, double *d_y) {
+    if (is_user_integrand(f_dyn) || is_user_integrand(f_obs)) return refuse_user_integrand("ssmq_simulate_rv_dev");
     const int mode = (f_dyn ? 1 : 0) | (f_obs ? 2 : 0);
     auto rv_ok = [](const ssmq_rv *v, int dim) {
         return v && v->dim == dim && v->chol && v->kind >= SSMQ_RV_GAUSS && v->kind <= SSMQ_RV_MIXTURE &&
@@ -2681,6 +2770,7 @@ extern "C" int ssmq_simulate_dev(const ssmq_integrand *f_dyn, const ssmq_integra
                                  const double *x0_mean, const double *x0_chol, const double *q_mean,
                                  const double *q_chol, const double *G, const double *r_mean, const double *r_chol,
                                  uint64_t seed, uint64_t traj_offset, double *d_x, double *d_y) {
+    if (is_user_integrand(f_dyn) || is_user_integrand(f_obs)) return refuse_user_integrand("ssmq_simulate_dev");
     ssmq_rv x0{SSMQ_RV_GAUSS, D, 1, 0, 0.0, x0_mean, x0_chol, nullptr};
     ssmq_rv q{SSMQ_RV_GAUSS, dq, 1, 0, 0.0, q_mean, q_chol, nullptr};
     ssmq_rv r{SSMQ_RV_GAUSS, dr, 1, 0, 0.0, r_mean, r_chol, nullptr};
@@ -2704,8 +2794,9 @@ extern "C" int ssmq_filter_kernel_name_batch(const ssmq_transform *h_dyn, const 
     FInfo fio;
     if (!integrand_info(f_obs->id, &fio)) return SSMQ_E_ARG;
     const char *name = nullptr;
-    int rc = ssmq::sw("SSMQ_NO_FUSED") ? 0
-                                     : try_launch_fused(h_dyn, f_dyn, h_obs, f_obs, sel_pattern(f_obs, fio.din), B, 0, 0,
+    int rc = ssmq::sw("SSMQ_NO_FUSED") && !is_user_integrand(f_dyn) && !is_user_integrand(f_obs)
+                 ? 0
+                 : try_launch_fused(h_dyn, f_dyn, h_obs, f_obs, sel_pattern(f_obs, fio.din), B, 0, 0,
                                                         nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
                                                         nullptr, nullptr, &name, true, nullptr, 0.0, nullptr, nullptr);
     if (rc < 0) return rc;

@@ -660,6 +660,7 @@ __global__ __launch_bounds__(kSmallBlock, 2) void k_apply_small(const ApplyArgs 
     }
 }
 
+#ifndef __HIPCC_RTC__
 template <int D, int E, int N, int F, int FORM, int TP, int SEL, int OPT>
 inline hipError_t launch_apply_small(const ApplyArgs &a, hipStream_t s) {
     const unsigned grid = (unsigned)((a.B + kSmallLpw - 1) / kSmallLpw);
@@ -672,5 +673,6 @@ inline hipError_t launch_apply_small(const ApplyArgs &a, hipStream_t s) {
     hipLaunchKernelGGL((k_apply_small<D, E, N, F, FORM, TP, SEL, OPT, false>), dim3(grid), dim3(kSmallBlock), 0, s, a);
     return hipGetLastError();
 }
+#endif
 
 }  // namespace ssmq

@@ -1,9 +1,11 @@
 // Device-side building blocks shared by every kernel of libssmq: argument blocks, the in-register Cholesky, and the
 // closed-form integrands of the reference's ssmod.py as __device__ functors.  gfx950 only.
 #pragma once
+#ifndef __HIPCC_RTC__   // (ssmq_rtc.hip: hiprtc supplies the runtime, the integer types and the math functions)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <math.h>
+#endif
 #include "../../include/ssmq.h"
 #include "ssmq_math.h"
 
@@ -517,6 +519,7 @@ __host__ __device__ inline bool integrand_has_jacobian(int id) {
 
 // Host: the time-dependent constant of integrand `id` for times 0..T-1 (what Fn<id>::init would compute), or false if the
 // integrand has none.  Evaluated with the host libm in fp64 - the reference evaluates np.cos on the host as well.
+#ifndef __HIPCC_RTC__
 __host__ inline bool time_table(int id, int T, double *out) {
     if (id == SSMQ_F_UNGM_DYN) {
         for (int k = 0; k < T; ++k) out[k] = 8.0 * cos(1.2 * (double)k);
@@ -528,12 +531,16 @@ __host__ inline bool time_table(int id, int T, double *out) {
     }
     return false;
 }
+#endif
 
 // Host-visible table: inputs read / outputs produced by each integrand (0 = "set by the transform's E").
 struct FInfo {
     int din, dout;
     bool uses_time;
 };
+#ifndef __HIPCC_RTC__
+bool user_integrand_info(int id, FInfo *o);   // ids SSMQ_F_USER_FIRST ... (ssmq_rtc.hip)
+#endif
 __host__ inline bool integrand_info(int id, FInfo *o) {
     switch (id) {
         case SSMQ_F_UNGM_DYN: *o = {1, 1, true}; return true;
@@ -552,7 +559,11 @@ __host__ inline bool integrand_info(int id, FInfo *o) {
         case SSMQ_F_CV_DYN: *o = {4, 4, false}; return true;
         case SSMQ_F_REENTRY2D_BIAS_DYN: *o = {6, 6, false}; return true;
         case SSMQ_F_SMOOTH10D_DYN: *o = {10, 10, false}; return true;
+#ifndef __HIPCC_RTC__
+        default: return user_integrand_info(id, o);
+#else
         default: return false;
+#endif
     }
 }
 

@@ -461,6 +461,14 @@ int try_launch_fused(const ssmq_transform *hd, const ssmq_integrand *fd, const s
                      const double *d_m0, const double *d_P0, const double *d_gqg, const double *d_rr, double *d_fm,
                      double *d_fP, int32_t *d_status, hipStream_t s, const char **name, bool dry_run,
                      const double *d_sscale, double student_dof, const double *d_ttab_dyn, const double *d_ttab_obs) {
+    if (is_user_integrand(fd) || is_user_integrand(fo)) {
+        // user-defined integrands: the run-time compiled whole-pass kernel (ssmq_rtc.hip; launched by the filter entry points
+        // themselves), no quad / wave-split / strip variant; here only its name
+        if (!dry_run) return refuse_user_integrand("fused filter launch");
+        FusedArgs a;
+        memset(&a, 0, sizeof(a));
+        return rtc_launch_fused(hd, fd, ho, fo, sel_obs, a, s, name, true);
+    }
     if (hd->form != ho->form || (hd->tp_nu > 0.0) != (ho->tp_nu > 0.0) || sel_obs < 0 || fd->n_idx > 0) return 0;
     if (!dry_run || B > 0) {
         // batches whose waves would each sit alone on a SIMD: one trajectory on four lanes (ssmq_filter_quad.hip) ...

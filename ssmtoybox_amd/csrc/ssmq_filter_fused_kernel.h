@@ -1,10 +1,14 @@
 // The fused filter time loop as a device function + its whole-pass kernel (ssmq_filter_fused.hip: dispatch table; the chunked,
 // self-scheduling variant of the heavy shapes: ssmq_filter_chunked.hip).
 #pragma once
+#ifndef __HIPCC_RTC__
 #include <cstdlib>
+#endif
 #include "ssmq_fused.h"
+#ifndef __HIPCC_RTC__
 #include <type_traits>
 #include "ssmq_host.h"
+#endif
 
 namespace ssmq {
 

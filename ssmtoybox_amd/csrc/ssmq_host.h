@@ -41,6 +41,21 @@ struct ssmq_transform {
 namespace ssmq {
 
 void set_error(const std::string &msg);
+
+// User-defined integrands (ssmq_rtc.hip).  Only the two routes below run them; every other entry point that takes an integrand
+// refuses a user id at its top (SSMQ_E_UNSUPPORTED) instead of reaching a generic kernel, whose eval_integrand() has no case for it.
+inline bool is_user_integrand(int id) { return id >= SSMQ_F_USER_FIRST && id < SSMQ_F_USER_FIRST + SSMQ_F_USER_SLOTS; }
+inline bool is_user_integrand(const ssmq_integrand *f) { return f && is_user_integrand(f->id); }
+int refuse_user_integrand(const char *what);   // sets the error text, returns SSMQ_E_UNSUPPORTED
+struct FusedArgs;
+struct ApplyArgs;
+// Whole-pass filter kernel k_filter_fused<> for a pair of models of which at least one is a user integrand: 1 launched (or, with
+// dry_run, the name set), < 0 error - never 0, so that no caller falls back to the launch loop.
+int rtc_launch_fused(const ssmq_transform *hd, const ssmq_integrand *fd, const ssmq_transform *ho, const ssmq_integrand *fo,
+                     int sel_obs, const FusedArgs &a, hipStream_t s, const char **name, bool dry_run);
+// k_apply_small<> for a user integrand: SSMQ_OK (launched, or with dry_run the name set) or < 0.
+int rtc_launch_apply(const ssmq_transform *h, const ssmq_integrand *f, int sel, const ApplyArgs &a, hipStream_t s,
+                     const char **name, bool dry_run);
 // Threads.  Every calling thread has its own CONTEXT: a HIP stream and the caches that belong to a stream (grow-only workspaces,
 // pinned staging blocks, captured launch graphs).  Calls of different threads on different handles run concurrently - on the
 // host and, stream by stream, on the device.  Contexts are pooled: a thread that ends hands its context (stream and caches

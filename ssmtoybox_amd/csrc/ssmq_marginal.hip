@@ -174,6 +174,7 @@ extern "C" int ssmq_gp_marginal_laplace_batch(ssmq_transform *h_dyn, const ssmq_
                                               const double *cov, const double *y, double time, const double *GQG, const double *R,
                                               const double *prior_mean, const double *prior_cov, double fd_step, double *theta,
                                               double *hess_inv, int32_t *status, int32_t *iters, int64_t *rounds_out) {
+    if (is_user_integrand(f_dyn) || is_user_integrand(f_obs)) return refuse_user_integrand("ssmq_gp_marginal_laplace_batch");
     SSMQ_HANDLE_LOCK(h_dyn, h_obs);
     if (!h_dyn || !h_obs || !f_dyn || !f_obs || B < 0 || (B > 0 && (!mean || !cov || !y || !prior_mean || !prior_cov || !theta ||
                                                                      !hess_inv || !status))) {
@@ -952,6 +953,7 @@ extern "C" int ssmq_gp_marginal_filter_batch(ssmq_transform *h_dyn, const ssmq_i
                                              const double *prior_cov, const double *upts, const double *uwts, int NP,
                                              double fd_step, double param_jitter, double *fm, double *fP, int32_t *failed,
                                              double *theta_last, double *pcov_last, int64_t *stats) {
+    if (is_user_integrand(f_dyn) || is_user_integrand(f_obs)) return refuse_user_integrand("ssmq_gp_marginal_filter_batch");
     SSMQ_HANDLE_LOCK(h_dyn, h_obs);
     if (!h_dyn || !h_obs || !f_dyn || !f_obs || B < 0 || T < 0 || (B > 0 && T > 0 && (!y || !x0_mean || !x0_cov || !prior_mean ||
         !prior_cov || !upts || !uwts || !fm || !fP || !failed))) {

@@ -15,7 +15,9 @@
 // Compiles on the host as well (tests/test_math_sequences.py builds this header with g++ and compares with libm over
 // the ranges; the reciprocal seed is emulated at the accuracy measured on gfx950, 2^-24).
 #pragma once
+#ifndef __HIPCC_RTC__
 #include <math.h>
+#endif
 
 #if defined(__HIPCC__)
 #define SSMQ_HD __host__ __device__ __forceinline__

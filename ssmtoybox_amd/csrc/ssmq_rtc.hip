@@ -1,0 +1,542 @@
+// User-defined integrands compiled for the device at run time (ROCm's hiprtc).  A model's function body is registered once
+// (ssmq_integrand_define) and becomes `template <> struct Fn<id>` next to the built-in functors of ssmq_device.h; the kernels that
+// run it are the AOT ones - k_filter_fused<> (ssmq_filter_fused_kernel.h) and k_apply_small<> (ssmq_apply_small.h) - instantiated
+// for the model in one translation unit made of:
+//   a prelude (the integer types and NAN, which hiprtc does not declare) | the device headers, embedded into the library at build
+//   time (ssmq_rtc_src.inc, made by the Makefile; their host-only parts sit behind #ifndef __HIPCC_RTC__) | the Fn<> wrapper of
+//   every user body involved | one explicit instantiation.
+// Compiled with the Makefile's -O3 -std=c++17 for the current device's architecture, found by lowered name, loaded as a module and
+// launched with the AOT launcher's grid, block and argument struct - the same code as a built-in model up to the functor.
+// Code objects are cached for the life of the process (key: the body hashes, kernel and template arguments, architecture) - failed
+// compiles too, with their message, so a broken body is compiled once - and modules per device.  Locks: the registry of bodies has
+// a mutex of its own (held for a lookup only); the cache mutex is held while a kernel is looked up, compiled or loaded, so a
+// compile (0.2 - 0.6 s) delays the lookups of other threads for that long - once per kernel and process; the launch itself runs
+// outside both.
+#include <hip/hiprtc.h>
+#include <algorithm>
+#include <chrono>
+#include <cstdio>
+#include <cstring>
+#include <map>
+#include <memory>
+#include <mutex>
+#include <string>
+#include <vector>
+#include "ssmq_host.h"
+#include "ssmq_fused.h"
+
+namespace ssmq {
+
+static const char kRtcHeaders[] =
+#include "ssmq_rtc_src.inc"
+    ;
+
+static const char kRtcPrelude[] =
+    "typedef __hip_internal::int32_t int32_t;\n"
+    "typedef __hip_internal::uint32_t uint32_t;\n"
+    "typedef __hip_internal::int64_t int64_t;\n"
+    "typedef __hip_internal::uint64_t uint64_t;\n"
+    "#define NAN __builtin_nan(\"\")\n";
+
+namespace {
+
+struct UserFn {
+    std::string body;
+    int din, dout;
+    bool uses_time;
+    uint64_t hash;
+};
+
+struct Compiled {
+    std::string error;                             // non-empty: the compile failed with this message (nothing to load)
+    std::vector<char> code;
+    std::string lowered;
+    std::map<int, std::pair<hipModule_t, hipFunction_t>> loaded;   // per device
+};
+
+std::mutex g_reg_mu;                               // g_user (taken inside g_mu, never the other way round)
+std::vector<UserFn> g_user;                        // slot = id - SSMQ_F_USER_FIRST
+std::mutex g_mu;                                   // cache, counters, names
+std::map<std::string, std::unique_ptr<Compiled>> g_cache;
+int64_t g_compiles = 0, g_hits = 0;
+double g_compile_s = 0.0;
+std::map<std::string, std::string> g_names;        // printable kernel names handed out as const char * (stable storage)
+
+uint64_t fnv1a(const std::string &s, uint64_t h = 1469598103934665603ull) {
+    for (unsigned char c : s) {
+        h ^= c;
+        h *= 1099511628211ull;
+    }
+    return h;
+}
+
+// Braces balanced, never closing more than it opened, outside comments and literals; no preprocessor lines, digraphs, raw strings
+// or line splices (a backslash before a line break joins two lines before comments are recognised: the end of a `//` comment, or a
+// `*` + `/`, would then lie elsewhere for the compiler than for this scan) - each could close the function the body is placed in
+// without a visible brace.  Empty string = accepted.
+std::string check_body(const char *body) {
+    const size_t n = strlen(body);
+    if (n == 0) return "integrand body is empty";
+    if (n > SSMQ_USER_BODY_MAX) return "integrand body is longer than SSMQ_USER_BODY_MAX (" + std::to_string(SSMQ_USER_BODY_MAX) + ") characters";
+    for (size_t i = 0; i < n; ++i) {   // (clang also splices a backslash followed by blanks and then the line break)
+        if (body[i] != '\\') continue;
+        size_t j = i + 1;
+        while (j < n && (body[j] == ' ' || body[j] == '\t' || body[j] == '\v' || body[j] == '\f')) ++j;
+        if (j < n && (body[j] == '\n' || body[j] == '\r'))
+            return "integrand body: line continuations (a backslash before a line break) are not allowed";
+    }
+    int depth = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const char c = body[i], d = i + 1 < n ? body[i + 1] : '\0';
+        if (c == '/' && d == '/') {
+            while (i < n && body[i] != '\n') ++i;
+            continue;
+        }
+        if (c == '/' && d == '*') {
+            const char *e = strstr(body + i + 2, "*/");
+            if (!e) return "integrand body: unterminated comment";
+            i = (size_t)(e - body) + 1;
+            continue;
+        }
+        if (c == '"' || c == '\'') {
+            if (i > 0 && (body[i - 1] == 'R')) return "integrand body: raw string literals are not allowed";
+            size_t j = i + 1;
+            while (j < n && body[j] != c && body[j] != '\n') j += body[j] == '\\' ? 2 : 1;
+            if (j >= n || body[j] != c) return "integrand body: unterminated literal";
+            i = j;
+            continue;
+        }
+        if (c == '#') return "integrand body: preprocessor directives are not allowed";
+        if (c == '\\') return "integrand body: backslashes are only allowed inside literals";
+        if ((c == '<' && d == '%') || (c == '%' && (d == '>' || d == ':'))) return "integrand body: digraphs are not allowed";
+        if (c == '{') ++depth;
+        if (c == '}' && --depth < 0) return "integrand body: unbalanced braces ('}' without '{')";
+    }
+    if (depth != 0) return "integrand body: unbalanced braces (" + std::to_string(depth) + " '{' not closed)";
+    return "";
+}
+
+bool user_fn(int id, UserFn *out) {
+    std::lock_guard<std::mutex> lk(g_reg_mu);
+    if (!is_user_integrand(id) || id - SSMQ_F_USER_FIRST >= (int)g_user.size()) return false;
+    *out = g_user[id - SSMQ_F_USER_FIRST];
+    return true;
+}
+
+std::string wrapper(int id, const UserFn &u) {
+    std::string s;
+    s += "namespace ssmq {\ntemplate <>\nstruct Fn<" + std::to_string(id) + "> {\n";
+    s += "    static constexpr int DIN = " + std::to_string(u.din) + ";\n";
+    s += "    double t_;\n    const FPar *fp_;\n";
+    s += "    __device__ __forceinline__ void init(double t, const FPar &par) { t_ = t; fp_ = &par; }\n";
+    s += "    template <int E>\n    __device__ __forceinline__ void eval(const double *x, double *o) const {\n";
+    s += "        const double t = t_;\n        const double *p = fp_->p;\n        (void)t; (void)p; (void)x; (void)o;\n        {\n";
+    s += "#line 1 \"user_integrand_" + std::to_string(id) + "\"\n";
+    s += u.body;
+    s += "\n        }\n    }\n};\n}  // namespace ssmq\n";
+    return s;
+}
+
+std::string first_lines(const std::string &log, int lines) {
+    size_t pos = 0;
+    for (int k = 0; k < lines && pos != std::string::npos; ++k) {
+        pos = log.find('\n', pos);
+        if (pos != std::string::npos) ++pos;
+    }
+    return pos == std::string::npos ? log : log.substr(0, pos);
+}
+
+// Compiles (or finds) the program that instantiates `expr` for the user integrands `ids`; g_mu held.  remarks: also ask the
+// compiler for its resource-usage remarks (compile check only; they do not change the code).
+int compile(const std::string &expr, const std::vector<int> &ids, const std::string &arch, Compiled **out, std::string *log,
+            bool remarks) {
+    std::string key = expr + "|" + arch;
+    std::string wrappers;
+    for (int id : ids) {
+        UserFn u;
+        if (!user_fn(id, &u)) {
+            set_error("integrand id " + std::to_string(id) + " is not a registered user integrand");
+            return SSMQ_E_ARG;
+        }
+        char hx[32];
+        snprintf(hx, sizeof(hx), "|%016llx", (unsigned long long)u.hash);
+        key += hx;
+        wrappers += wrapper(id, u);
+    }
+    if (!remarks) {
+        auto it = g_cache.find(key);
+        if (it != g_cache.end()) {
+            ++g_hits;
+            if (!it->second->error.empty()) {
+                set_error(it->second->error);
+                return SSMQ_E_UNSUPPORTED;
+            }
+            *out = it->second.get();
+            return SSMQ_OK;
+        }
+    }
+    std::string src = kRtcPrelude;
+    src += kRtcHeaders;
+    src += wrappers;
+    src += "template __global__ void " + expr + "(const " + (expr.find("k_filter_fused") != std::string::npos ? "ssmq::FusedArgs" : "ssmq::ApplyArgs") + ");\n";
+    const auto t0 = std::chrono::steady_clock::now();
+    hiprtcProgram prog;
+    if (hiprtcCreateProgram(&prog, src.c_str(), "ssmq_user.hip", 0, nullptr, nullptr) != HIPRTC_SUCCESS) {
+        set_error("hiprtcCreateProgram failed");
+        return SSMQ_E_HIP;
+    }
+    hiprtcAddNameExpression(prog, expr.c_str());
+    const std::string arch_opt = "--offload-arch=" + arch;
+    std::vector<const char *> opts = {arch_opt.c_str(), "-O3", "-std=c++17"};
+    if (remarks) opts.push_back("-Rpass-analysis=kernel-resource-usage");
+    const hiprtcResult rc = hiprtcCompileProgram(prog, (int)opts.size(), opts.data());
+    size_t ls = 0;
+    hiprtcGetProgramLogSize(prog, &ls);
+    std::string lg(ls, '\0');
+    if (ls) hiprtcGetProgramLog(prog, &lg[0]);
+    while (!lg.empty() && lg.back() == '\0') lg.pop_back();
+    if (log) *log = lg;
+    if (rc != HIPRTC_SUCCESS) {
+        hiprtcDestroyProgram(&prog);
+        const std::string msg = "run-time compilation of " + expr + " failed: " + first_lines(lg, 12);
+        set_error(msg);
+        ++g_compiles;
+        g_compile_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        if (!remarks) {
+            auto c = std::unique_ptr<Compiled>(new Compiled);
+            c->error = msg;
+            g_cache[key] = std::move(c);
+        }
+        return SSMQ_E_UNSUPPORTED;
+    }
+    const char *lowered = nullptr;
+    size_t cs = 0;
+    auto c = std::unique_ptr<Compiled>(new Compiled);
+    if (hiprtcGetLoweredName(prog, expr.c_str(), &lowered) != HIPRTC_SUCCESS || !lowered || hiprtcGetCodeSize(prog, &cs) != HIPRTC_SUCCESS ||
+        cs == 0) {
+        hiprtcDestroyProgram(&prog);
+        set_error("run-time compilation of " + expr + ": no code object / lowered name");
+        return SSMQ_E_HIP;
+    }
+    c->lowered = lowered;
+    c->code.resize(cs);
+    hiprtcGetCode(prog, c->code.data());
+    hiprtcDestroyProgram(&prog);
+    ++g_compiles;
+    g_compile_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    Compiled *p = c.get();
+    if (remarks) {
+        static std::unique_ptr<Compiled> last_check;   // (compile checks are not cached: the remarks are wanted every time)
+        last_check = std::move(c);
+    } else {
+        g_cache[key] = std::move(c);
+    }
+    *out = p;
+    return SSMQ_OK;
+}
+
+int device_arch(std::string *arch, int *dev) {
+    static thread_local std::map<int, std::string> known;      // (per thread: no lock; properties are asked once per device)
+    SSMQ_HIP(hipGetDevice(dev));
+    auto it = known.find(*dev);
+    if (it == known.end()) {
+        hipDeviceProp_t p;
+        SSMQ_HIP(hipGetDeviceProperties(&p, *dev));
+        std::string a = p.gcnArchName;      // "gfx950:sramecc+:xnack-": the Makefile builds for the processor alone
+        it = known.emplace(*dev, a.substr(0, a.find(':'))).first;
+    }
+    *arch = it->second;
+    return SSMQ_OK;
+}
+
+int function_of(Compiled *c, int dev, hipFunction_t *fn) {   // g_mu held
+    auto it = c->loaded.find(dev);
+    if (it != c->loaded.end()) {
+        *fn = it->second.second;
+        return SSMQ_OK;
+    }
+    hipModule_t m;
+    SSMQ_HIP(hipModuleLoadData(&m, c->code.data()));
+    hipFunction_t f;
+    hipError_t e = hipModuleGetFunction(&f, m, c->lowered.c_str());
+    if (e != hipSuccess) {
+        hipModuleUnload(m);
+        return hip_fail(e, "hipModuleGetFunction");
+    }
+    c->loaded[dev] = {m, f};
+    *fn = f;
+    return SSMQ_OK;
+}
+
+// The loaded kernel for `expr` on the current device: compiled, or found in the cache, under g_mu; the launch is the caller's.
+int kernel_for(const std::string &expr, const std::vector<int> &ids, hipFunction_t *fn) {
+    std::string arch;
+    int dev = 0;
+    int rc = device_arch(&arch, &dev);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(g_mu);
+    Compiled *c = nullptr;
+    if ((rc = compile(expr, ids, arch, &c, nullptr, false))) return rc;
+    return function_of(c, dev, fn);
+}
+
+const char *stable_name(const std::string &s) {   // g_mu held
+    auto it = g_names.find(s);
+    if (it == g_names.end()) it = g_names.emplace(s, s).first;
+    return it->second.c_str();
+}
+
+std::string fused_expr(int D, int Y, int ND, int NO, int FD, int FO, int form, int tp, int selo, int opt, int stu) {
+    char b[256];
+    snprintf(b, sizeof(b), "ssmq::k_filter_fused<%d, %d, %d, %d, %d, %d, %d, %d, %d, %d, %d>", D, Y, ND, NO, FD, FO, form, tp, selo,
+             opt, stu);
+    return b;
+}
+std::string apply_expr(int D, int E, int N, int F, int form, int tp, int sel, int opt, bool nts) {
+    char b[256];
+    snprintf(b, sizeof(b), "ssmq::k_apply_small<%d, %d, %d, %d, %d, %d, %d, %d, %s>", D, E, N, F, form, tp, sel, opt, nts ? "true" : "false");
+    return b;
+}
+
+// Shape range of the run-time route (the span of the AOT table kFused): D <= 6, Y <= 4, point counts up to 2 D + 1.
+bool shape_ok(int D, int E, int N, std::string *why) {
+    if (D < 1 || D > SSMQ_USER_MAX_D || E < 1 || E > std::max(D, SSMQ_USER_MAX_Y) || N < 2 || N > 2 * D + 1) {
+        *why = "user integrands run for D <= " + std::to_string(SSMQ_USER_MAX_D) + ", outputs <= max(D, " + std::to_string(SSMQ_USER_MAX_Y) +
+               ") and 2 .. 2 D + 1 points (got D = " + std::to_string(D) + ", E = " + std::to_string(E) + ", N = " + std::to_string(N) + ")";
+        return false;
+    }
+    return true;
+}
+
+// The fast-path variant: as the AOT route, which has the LDL' / unscented-point variants for the D >= 5 shapes only (kFused,
+// SSMQ_FUSED_FAST; ssmq_small_*.hip, SSMQ_SMALL_FAST) - below that the dense kernel, so a restated built-in model runs the same code.
+int pick_opt_fused(const ssmq_transform *hd, const ssmq_transform *ho, int tp) {
+    if (hd->D < 5) return 0;
+    const int both = hd->opt_mask & ho->opt_mask;
+    const int plain = !(tp || hd->form == SSMQ_FORM_SIGMA);
+    if (plain && (both & 7) == 7) return 7;
+    return both & (plain ? 3 : SSMQ_OPT_UT);
+}
+
+}  // namespace
+
+int refuse_user_integrand(const char *what) {
+    set_error(std::string(what) + ": user-defined integrands run on ssmq_filter_forward_dev / ssmq_student_filter_forward_dev "
+              "(additive noise) and ssmq_apply_batch[_dev] only");
+    return SSMQ_E_UNSUPPORTED;
+}
+
+bool user_integrand_info(int id, FInfo *o) {
+    UserFn u;
+    if (!user_fn(id, &u)) return false;
+    *o = {u.din, u.dout, u.uses_time};
+    return true;
+}
+
+static int check_user_pair(const ssmq_integrand *fd, const ssmq_integrand *fo, std::vector<int> *ids) {
+    for (const ssmq_integrand *f : {fd, fo}) {
+        if (f->n_idx != 0) {
+            set_error("user integrands take the leading state entries: no state index (n_idx = 0)");
+            return SSMQ_E_UNSUPPORTED;
+        }
+        if (f->n_par < 0 || f->n_par > SSMQ_MAX_FPAR) {
+            set_error("integrand: n_par out of range");
+            return SSMQ_E_ARG;
+        }
+        if (is_user_integrand(f->id) && (ids->empty() || ids->back() != f->id)) ids->push_back(f->id);
+    }
+    return SSMQ_OK;
+}
+
+int rtc_launch_fused(const ssmq_transform *hd, const ssmq_integrand *fd, const ssmq_transform *ho, const ssmq_integrand *fo,
+                     int sel_obs, const FusedArgs &a0, hipStream_t s, const char **name, bool dry_run) {
+    std::vector<int> ids;
+    int rc = check_user_pair(fd, fo, &ids);
+    if (rc) return rc;
+    FInfo id_, io_;
+    if (!integrand_info(fd->id, &id_) || !integrand_info(fo->id, &io_)) {
+        set_error("unknown integrand id");
+        return SSMQ_E_ARG;
+    }
+    const int D = hd->D, Y = ho->E;
+    std::string why;
+    if (!shape_ok(D, D, hd->N, &why) || !shape_ok(D, Y, ho->N, &why) || Y > SSMQ_USER_MAX_Y) {
+        if (why.empty()) why = "user integrands: at most " + std::to_string(SSMQ_USER_MAX_Y) + " measurements";
+        set_error(why);
+        return SSMQ_E_UNSUPPORTED;
+    }
+    if (hd->form != ho->form || (hd->tp_nu > 0.0) != (ho->tp_nu > 0.0) || sel_obs != 0 || hd->form == SSMQ_FORM_TAYLOR1) {
+        set_error("user integrands: both transforms of one form (sigma-point or BQ), no linearisation, no state index");
+        return SSMQ_E_UNSUPPORTED;
+    }
+    if (id_.dout != D || id_.din > D || (io_.dout ? io_.dout : Y) != Y || io_.din > D) {
+        set_error("user integrands: input / output dimensions do not match the transforms");
+        return SSMQ_E_ARG;
+    }
+    const int tp = hd->tp_nu > 0.0 ? 1 : 0, opt = pick_opt_fused(hd, ho, tp);
+    const int stu = (a0.sscale != nullptr && a0.student_dof > 0.0) ? 1 : 0;
+    // scalar state: recursion type fixed at compile time, as the AOT table does (SSMQ_FUSED_ONE_S)
+    const std::string expr = fused_expr(D, Y, hd->N, ho->N, fd->id, fo->id, hd->form, tp, 0, opt, D == 1 && Y == 1 ? stu : -1);
+    if (name) {
+        std::lock_guard<std::mutex> lk(g_mu);
+        *name = stable_name(expr.substr(6) + " (run-time compiled)");
+    }
+    if (dry_run) return 1;
+    // A built-in member with a host time table (UNGM: HasTimeTable<> in ssmq_fused.h) is read through that table at every step
+    // of the loop, unconditionally: the caller must have uploaded it (filter_forward_user does).
+    FusedArgs a = a0;
+    for (const ssmq_integrand *f : {fd, fo}) {
+        const double *tab = f == fd ? a.fd.ttab : a.fo.ttab;
+        if (!is_user_integrand(f) && time_table(f->id, 0, nullptr) && !tab) {
+            set_error("run-time compiled filter: the time table of built-in integrand " + std::to_string(f->id) + " is missing");
+            return SSMQ_E_ARG;
+        }
+    }
+    if (is_user_integrand(fd)) a.fd.ttab = nullptr;   // (user integrands evaluate their time dependence themselves)
+    if (is_user_integrand(fo)) a.fo.ttab = nullptr;
+    hipFunction_t fn;
+    if ((rc = kernel_for(expr, ids, &fn))) return rc;
+    a.lpw = 64;
+    void *args[] = {&a};
+    const unsigned grid = (unsigned)((a.B + a.lpw - 1) / a.lpw);
+    rc = hip_fail(hipModuleLaunchKernel(fn, grid, 1, 1, kSmallBlock, 1, 1, 0, s, args, nullptr), "k_filter_fused (run-time compiled)");
+    return rc ? rc : 1;
+}
+
+int rtc_launch_apply(const ssmq_transform *h, const ssmq_integrand *f, int sel, const ApplyArgs &a0, hipStream_t s, const char **name,
+                     bool dry_run) {
+    std::vector<int> ids;
+    int rc = check_user_pair(f, f, &ids);
+    if (rc) return rc;
+    std::string why;
+    if (!shape_ok(h->D, h->E, h->N, &why)) {
+        set_error(why);
+        return SSMQ_E_UNSUPPORTED;
+    }
+    if (sel != 0 || h->form == SSMQ_FORM_TAYLOR1) {
+        set_error("user integrands: sigma-point or BQ transforms only, no state index");
+        return SSMQ_E_UNSUPPORTED;
+    }
+    const int tp = h->tp_nu > 0.0 ? 1 : 0;
+    int opt = 0;
+    if (h->D >= 5) {   // the AOT selection (apply_dev_impl) over the variants SSMQ_SMALL_FAST instantiates
+        const int want[5] = {(!tp && (h->opt_mask & 7) == 7) ? 7 : -1, h->opt_mask & (tp ? SSMQ_OPT_UT : 3), h->opt_mask & SSMQ_OPT_UT,
+                             h->opt_mask & SSMQ_OPT_LDL & (tp ? 0 : 1), 0};
+        for (int k = 0; k < 5; ++k) {
+            const int w = want[k];
+            const bool have = w == 0 || (h->form == SSMQ_FORM_BQ && !tp && (w == 7 || w == 3 || w == 1)) ||
+                              (w == SSMQ_OPT_UT && (tp || h->form == SSMQ_FORM_SIGMA));
+            if (w >= 0 && have) {
+                opt = w;
+                break;
+            }
+        }
+    }
+    const bool nts = opt != 0 && a0.stream_out;
+    const std::string expr = apply_expr(h->D, h->E, h->N, f->id, h->form, tp, 0, opt, nts);
+    if (name) {
+        std::lock_guard<std::mutex> lk(g_mu);
+        *name = stable_name(expr.substr(6) + " (run-time compiled)");
+    }
+    if (dry_run) return SSMQ_OK;
+    hipFunction_t fn;
+    if ((rc = kernel_for(expr, ids, &fn))) return rc;
+    ApplyArgs a = a0;
+    a.fp.ttab = nullptr;
+    void *args[] = {&a};
+    const unsigned grid = (unsigned)((a.B + kSmallBlock - 1) / kSmallBlock);
+    return hip_fail(hipModuleLaunchKernel(fn, grid, 1, 1, kSmallBlock, 1, 1, 0, s, args, nullptr), "k_apply_small (run-time compiled)");
+}
+
+}  // namespace ssmq
+
+using namespace ssmq;
+
+extern "C" int ssmq_integrand_define(const char *body, int din, int dout, int uses_time, int32_t *id) {
+    if (!body || !id) {
+        set_error("ssmq_integrand_define: null argument");
+        return SSMQ_E_ARG;
+    }
+    if (din < 1 || din > SSMQ_MAX_DIM || dout < 1 || dout > SSMQ_MAX_DIM) {
+        set_error("ssmq_integrand_define: din and dout must be in 1 .. " + std::to_string(SSMQ_MAX_DIM));
+        return SSMQ_E_ARG;
+    }
+    const std::string why = check_body(body);
+    if (!why.empty()) {
+        set_error(why);
+        return SSMQ_E_ARG;
+    }
+    std::lock_guard<std::mutex> lk(g_reg_mu);
+    for (size_t k = 0; k < g_user.size(); ++k) {
+        UserFn &u = g_user[k];
+        if (u.body == body && u.din == din && u.dout == dout) {
+            u.uses_time = u.uses_time || uses_time != 0;
+            *id = SSMQ_F_USER_FIRST + (int32_t)k;
+            return SSMQ_OK;
+        }
+    }
+    if ((int)g_user.size() >= SSMQ_F_USER_SLOTS) {
+        set_error("ssmq_integrand_define: all " + std::to_string(SSMQ_F_USER_SLOTS) + " user integrand slots are taken");
+        return SSMQ_E_UNSUPPORTED;
+    }
+    UserFn u{body, din, dout, uses_time != 0, 0};
+    u.hash = fnv1a(u.body, fnv1a(std::to_string(din) + "," + std::to_string(dout)));
+    g_user.push_back(u);
+    *id = SSMQ_F_USER_FIRST + (int32_t)(g_user.size() - 1);
+    return SSMQ_OK;
+}
+
+extern "C" int ssmq_rtc_compile_check(int32_t id, int32_t id_obs, int kind, int D, int E, int N, int N_obs, int form, int tp, int opt,
+                                      const char *arch, char *log, int len) {
+    if (!arch || !*arch || (kind != SSMQ_RTC_FILTER && kind != SSMQ_RTC_APPLY) || (form != SSMQ_FORM_BQ && form != SSMQ_FORM_SIGMA) ||
+        tp < 0 || tp > 1 || (opt != 0 && opt != 1 && opt != 2 && opt != 3 && opt != 7)) {
+        set_error("ssmq_rtc_compile_check: bad argument");
+        return SSMQ_E_ARG;
+    }
+    std::string why;
+    if (!shape_ok(D, E, N, &why) || (kind == SSMQ_RTC_FILTER && !shape_ok(D, D, N_obs, &why))) {
+        set_error(why);
+        return SSMQ_E_UNSUPPORTED;
+    }
+    FInfo fi;
+    if (!integrand_info(id, &fi) || (kind == SSMQ_RTC_FILTER && !integrand_info(id_obs, &fi))) {
+        set_error("ssmq_rtc_compile_check: unknown integrand id");
+        return SSMQ_E_ARG;
+    }
+    std::vector<int> ids;
+    if (is_user_integrand(id)) ids.push_back(id);
+    if (kind == SSMQ_RTC_FILTER && is_user_integrand(id_obs) && id_obs != id) ids.push_back(id_obs);
+    const std::string expr = kind == SSMQ_RTC_FILTER ? fused_expr(D, E, N, N_obs, id, id_obs, form, tp, 0, opt, -1)
+                                                     : apply_expr(D, E, N, id, form, tp, 0, opt, false);
+    std::lock_guard<std::mutex> lk(g_mu);
+    Compiled *c = nullptr;
+    std::string lg;
+    const int rc = compile(expr, ids, arch, &c, &lg, true);
+    std::string text = lg;
+    if (rc == SSMQ_OK) {   // the lowered name, then the resource remarks alone ("VGPRs: 67", "ScratchSize [bytes/lane]: 0", ...)
+        text = c->lowered + "\n";
+        size_t pos = 0;
+        while (pos < lg.size()) {
+            size_t e = lg.find('\n', pos);
+            if (e == std::string::npos) e = lg.size();
+            const std::string ln = lg.substr(pos, e - pos);
+            const size_t r = ln.find("remark: ");
+            if (r != std::string::npos) text += ln.substr(r + 8, ln.find(" [-Rpass") - r - 8) + "\n";
+            pos = e + 1;
+        }
+    }
+    if (log && len > 0) {
+        const size_t n = std::min(text.size(), (size_t)len - 1);
+        memcpy(log, text.data(), n);
+        log[n] = '\0';
+    }
+    return rc;
+}
+
+extern "C" int ssmq_rtc_stats(int64_t *compiles, int64_t *cache_hits, double *compile_seconds) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    if (compiles) *compiles = g_compiles;
+    if (cache_hits) *cache_hits = g_hits;
+    if (compile_seconds) *compile_seconds = g_compile_s;
+    return SSMQ_OK;
+}

@@ -18,6 +18,7 @@ from numpy.polynomial.hermite_e import hermegauss, hermeval
 
 from . import _lib
 from ._lib import FORM_SIGMA, EMV_DIAG
+from .ssmod import check_user_points, user_unsupported
 
 
 class MomentTransform(metaclass=ABCMeta):
@@ -110,6 +111,7 @@ class _DeviceApply:
         dev = resolve_integrand(f)
         if dev is not None:
             integ, E = dev
+            self._check_user(integ, D)
             h = self._handle_for(E)
             time = np.ascontiguousarray(np.asarray(time, dtype=np.float64).reshape(-1))
             if time.size == B and B > 1:
@@ -168,14 +170,22 @@ class _DeviceApply:
         if dev is None:
             raise ValueError('apply_batch_dev needs a built-in (device) integrand')
         integ, E = dev
+        self._check_user(integ, mean.n if hasattr(mean, 'n') else None)
         h = self._handle_for(E)
         _lib.check(_lib.load().ssmq_apply_batch_dev(ctypes.c_void_p(h), ctypes.byref(integ), mean.B, mean.ld, mean.ptr,
                                                     cov.ptr, ctypes.c_void_p(time.ptr), time_stride, mean_f.ptr,
                                                     cov_f.ptr, cov_fx.ptr, ctypes.c_void_p(status.ptr)),
                    'ssmq_apply_batch_dev')
 
+    def _check_user(self, integ, D):
+        """A user-defined integrand (device_code) runs on 2 .. 2 D + 1 points only: NotImplementedError beyond, naming the range."""
+        if integ.id >= _lib.F_USER_FIRST and self._num_points():
+            pts = getattr(self, 'unit_sp', None)
+            check_user_points(D if D is not None else (pts if pts is not None else self.model.points).shape[0], self._num_points())
+
     def kernel_name(self, f):
         integ, E = resolve_integrand(f)
+        self._check_user(integ, None)
         buf = ctypes.create_string_buffer(256)
         _lib.check(_lib.load().ssmq_apply_kernel_name(ctypes.c_void_p(self._handle_for(E)), ctypes.byref(integ), buf,
                                                       256), 'ssmq_apply_kernel_name')
@@ -206,8 +216,11 @@ class LinearizationTransform(_DeviceApply, MomentTransform):
         return 0
 
     def apply_batch(self, f, mean, cov, time=0.0, fcn_pars=None, return_status=False):
-        if resolve_integrand(f) is None:
+        dev = resolve_integrand(f)
+        if dev is None:
             raise NotImplementedError('LinearizationTransform needs a built-in model (device integrand with a Jacobian)')
+        if dev[0].id >= _lib.F_USER_FIRST:
+            raise user_unsupported('the linearisation transform (model Jacobians)')
         return super().apply_batch(f, mean, cov, time=time, fcn_pars=fcn_pars, return_status=return_status)
 
     def __del__(self):

@@ -23,7 +23,7 @@ from . import _lib
 from .mtran import (MomentTransform, LinearizationTransform, UnscentedTransform, SphericalRadialTransform, GaussHermiteTransform,
                     FullySymmetricStudentTransform, resolve_integrand)
 from .bq.bqmtran import GaussianProcessTransform, BayesSardTransform, StudentTProcessTransform
-from .ssmod import TransitionModel, MeasurementModel
+from .ssmod import TransitionModel, MeasurementModel, is_user_model, user_unsupported, check_user_points
 
 
 class GaussianInference:
@@ -48,6 +48,12 @@ class GaussianInference:
         self.status = None
         self._data = None
 
+    def _check_user_points(self):
+        """Filters on user models (device_code) run the run-time compiled whole-pass kernel: 2 .. 2 D + 1 points per transform."""
+        if is_user_model(self.mod_dyn) or is_user_model(self.mod_obs):
+            for tf in (self.tf_dyn, self.tf_obs):
+                check_user_points(self.mod_dyn.dim_state, tf._num_points())
+
     @property
     def _additive(self):
         return self.mod_dyn.noise_additive and self.mod_obs.noise_additive
@@ -58,6 +64,7 @@ class GaussianInference:
         if not self._additive:
             return ('k_filter_fused_aug (one kernel for the time loop) where instantiated, else a launch loop of 5 T '
                     'launches (k_augment | apply dyn | k_augment | apply obs | k_kalman_update)')
+        self._check_user_points()
         f_dyn, e_dyn = resolve_integrand(self.mod_dyn.dyn_eval)
         f_obs, e_obs = resolve_integrand(self.mod_obs.meas_eval)
         buf = ctypes.create_string_buffer(512)
@@ -129,6 +136,8 @@ class GaussianInference:
         """RTS smoothing of the batch given to the last forward_pass_batch: (D, T, B), (D, D, T, B).  The reference's
         indexing is kept (the last two smoothed steps equal the filtered ones)."""
         assert self._data is not None, 'run forward_pass first'     # the reference asserts its 'filtered' flag
+        if is_user_model(self.mod_dyn) or is_user_model(self.mod_obs):
+            raise user_unsupported('the RTS smoother (backward_pass)')
         self.forward_pass_batch(self._data, smooth=True)
         return self.sm_mean, self.sm_cov
 
@@ -136,6 +145,7 @@ class GaussianInference:
         """Filter measurements that are already on the device (planes [T][dim_y][ld], e.g. from `ssmod.simulate_dev`)
         and leave the results there: returns DeviceBuffers (d_fm [T][D][ld], d_fP [T][D*D][ld], d_status [ld]) for
         `mcshard.device_error_sums`; the caller frees them.  Every trajectory starts from the model's initial moments."""
+        self._check_user_points()
         lib = _lib.load()
         D = self.mod_dyn.dim_state
         mrow = np.ascontiguousarray(np.repeat(np.asarray(self.x0_mean, dtype=np.float64).reshape(D, 1), 64, axis=1))
@@ -205,6 +215,9 @@ class GaussianInference:
 
     def forward_pass_batch(self, data, x0_mean=None, x0_cov=None, raise_on_failure=True, smooth=False):
         """data (dim_y, T, B).  Optional per-trajectory initial moments x0_mean (B, D), x0_cov (B, D, D)."""
+        if smooth and (is_user_model(self.mod_dyn) or is_user_model(self.mod_obs)):
+            raise user_unsupported('the RTS smoother (backward_pass)')
+        self._check_user_points()
         lib = _lib.load()
         data = np.asarray(data, dtype=np.float64)
         self._data = data
@@ -351,6 +364,8 @@ class ExtendedKalman(GaussianInference):
     the models whose Jacobians the reference implements (its own test skips the others: tests/test_ssinf.py:96-101)."""
 
     def __init__(self, dyn, obs):
+        if is_user_model(dyn) or is_user_model(obs):
+            raise user_unsupported('ExtendedKalman (model Jacobians)')
         super().__init__(dyn, obs, LinearizationTransform(dyn.dim_in), LinearizationTransform(obs.dim_in))
 
 

@@ -10,6 +10,7 @@ the device (`ssmq_simulate_rv_dev`: counter-based Philox generator, so results m
 only statistically) for Gaussian, Student-t and Gaussian-mixture random variables; Jacobians stay in the reference.
 """
 import ctypes
+import re
 
 import numpy as np
 
@@ -105,12 +106,49 @@ def _rv_desc(rv, what):
     return d, (mean, chol, alpha)
 
 
+_USER_IDS = {}       # (model class, body, din, dout) -> integrand id registered with the library
+
+
+def is_user_model(model):
+    """A model defined by its `device_code` (no built-in integrand): runs through the run-time compiled kernels."""
+    return model is not None and getattr(model, '_fid', None) is None and getattr(model, 'device_code', None) is not None
+
+
+_USER_SUPPORTED = ('user models (device_code) run in the additive-noise filters (forward_pass*, Gaussian and Studentian: UKF, CKF, '
+                   'GHKF, GPQKF, BSQKF, TPQKF, FullySymmetricStudent, StudentProcessStudent) and the moment transforms, for '
+                   'dim_state <= {} and dim_out <= {}, without state_index'.format(_lib.USER_MAX_D, _lib.USER_MAX_Y))
+
+
+def user_unsupported(what):
+    """NotImplementedError for an operation the run-time compiled route does not cover, naming what it does cover."""
+    return NotImplementedError('{} is not available for a user model (device_code); {}'.format(what, _USER_SUPPORTED))
+
+
+def check_user_points(D, N):
+    """The run-time compiled kernels cover 2 .. 2 D + 1 points (include/ssmq.h): NotImplementedError beyond."""
+    if not 2 <= N <= 2 * D + 1:
+        raise user_unsupported('a point set of {} points at D = {} (2 .. 2 D + 1 = {})'.format(N, D, 2 * D + 1))
+
+
+def _user_integrand(model, din, dout):
+    """Register model.device_code once per (class, body) and return its integrand id."""
+    body = model.device_code
+    key = (type(model), body, din, dout)
+    fid = _USER_IDS.get(key)
+    if fid is None:
+        fid = _lib.define_integrand(body, din, dout, re.search(r'\bt\b', body) is not None)
+        _USER_IDS[key] = fid
+    return fid
+
+
 def simulate_dev(dyn, obs, steps, mc_sims, seed=0, traj_offset=0, continuous_dt=None):
     """States and measurements of `mc_sims` trajectories generated on the device, left there in the filter's layout:
     returns (d_x, d_y, ld) with d_x planes [steps][D][ld], d_y [steps][Y][ld] (DeviceBuffers; caller frees).
     x[0] ~ init_rv, x[k] = dyn_fcn(x[k-1], q[k-1], k-1), y[k] = meas_fcn(x[k], r[k], k+1) (ssmod.py:168-199, 1011-1039);
     with `continuous_dt` the states are the Euler-Maruyama steps of dyn_fcn_cont instead (ssmod.py:201-244).
     Trajectory b uses the random stream of global index traj_offset + b.  obs = None: states only (d_y is None)."""
+    if is_user_model(dyn) or is_user_model(obs):
+        raise user_unsupported('the device simulator')
     lib = _lib.load()
     D = dyn.dim_state
     Y = obs.dim_out if obs is not None else 0
@@ -141,6 +179,9 @@ class TransitionModel:
     dim_noise = None
     noise_additive = True
     _fid = None
+    # A model of your own: the body of its device function as C++ (include/ssmq.h ssmq_integrand_define) - x the state
+    # (dim_state inputs), o the dim_state outputs, t the time index, p the constants _par() returns.  Additive noise only.
+    device_code = None
 
     def __init__(self, init_rv=None, noise_rv=None, noise_gain=None):
         self.dim_in = self.dim_state if self.noise_additive else self.dim_state + self.dim_noise
@@ -153,6 +194,12 @@ class TransitionModel:
 
     def device_integrand(self):
         """(ssmq_integrand, dim_out) for the C ABI."""
+        if is_user_model(self):
+            if not self.noise_additive:
+                raise user_unsupported('non-additive noise')
+            if self.dim_state > _lib.USER_MAX_D:
+                raise user_unsupported('dim_state = {}'.format(self.dim_state))
+            return Integrand.make(_user_integrand(self, self.dim_state, self.dim_state), self._par()), self.dim_state
         return Integrand.make(self._fid, self._par()), self.dim_state
 
     def dyn_fcn(self, x, q, time):
@@ -390,6 +437,9 @@ class MeasurementModel:
     dim_substate = None
     noise_additive = True
     _fid = None
+    # A model of your own: the body of its device function as C++ - x the leading dim_substate (else dim_state) state entries,
+    # o the dim_out outputs, t the time index, p the constants _par() returns.  Additive noise, no state_index.
+    device_code = None
 
     def __init__(self, noise_rv, dim_state, state_index=None):
         self.noise_rv = noise_rv
@@ -402,6 +452,15 @@ class MeasurementModel:
         return ()
 
     def device_integrand(self):
+        if is_user_model(self):
+            if not self.noise_additive:
+                raise user_unsupported('non-additive noise')
+            if self.state_index is not None:
+                raise user_unsupported('state_index')
+            din = self.dim_substate if self.dim_substate is not None else self.dim_state
+            if self.dim_state > _lib.USER_MAX_D or self.dim_out > _lib.USER_MAX_Y or din > self.dim_state:
+                raise user_unsupported('dim_state = {}, dim_out = {}'.format(self.dim_state, self.dim_out))
+            return Integrand.make(_user_integrand(self, din, self.dim_out), self._par()), self.dim_out
         idx = None
         if self.state_index is not None:
             idx = list(self.state_index)
@@ -415,6 +474,8 @@ class MeasurementModel:
     def simulate_measurements(self, x, seed=0, traj_offset=0):
         """(dim_out, steps, mc_sims) measurements of the given states x (dim_state, steps, mc_sims), y[k] taken at time
         k + 1 (ssmod.py:1011-1039), generated on the device."""
+        if is_user_model(self):
+            raise user_unsupported('the device simulator')
         lib = _lib.load()
         x = np.asarray(x, dtype=np.float64)
         D, steps, mc_sims = x.shape

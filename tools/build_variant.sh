@@ -6,5 +6,5 @@ cd "$(dirname "$0")/../ssmtoybox_amd/csrc"
 mkdir -p ../../variants
 /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 ${SSMQ_VARIANT_SCOPE--DSSMQ_FUSED_UNGM_ONLY} $2 -c ssmq_filter_fused.hip -o ../../variants/fused_$1.o
 objs=$(ls *.o | grep -v ssmq_filter_fused.o)
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../../variants/libssmq_$1.so $objs ../../variants/fused_$1.o
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../../variants/libssmq_$1.so $objs ../../variants/fused_$1.o -lhiprtc
 echo built variants/libssmq_$1.so
