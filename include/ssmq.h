@@ -207,6 +207,31 @@ int ssmq_rbf_eval(int D, int N1, const double *x1, int N2, const double *x2, con
 int ssmq_rbf_factor(int D, int N, const double *x, const double *par, int P, int scaling, double jitter,
                     const double *rhs, double *chol, double *iK, int32_t *status);
 int ssmq_rbf_exp_kxkx(int D, int N, const double *x, const double *par0, const double *par1, int scaling, double *Q);
+
+/*
+ * Type-II maximum likelihood of the RBF kernel's parameters [alpha, ell_1 .. ell_D] (P = D + 1), B independent rows in
+ * one launch, one workgroup each.
+ *   ssmq_gp_nlml_batch  GaussianProcessModel.neg_log_marginal_likelihood (bq/bqmod.py:537-596), nu = 0, and
+ *                       StudentTProcessModel.neg_log_marginal_likelihood (bq/bqmod.py:1191-1245), nu > 2, with the
+ *                       kernel derivatives of RBFGauss.der_par (bq/bqkern.py:426-436): nlml [B] and grad [B][P] at the
+ *                       log-parameters log_par [B][P].  K = eval(exp(log_par), x) + jitter; der_par uses K without the
+ *                       jitter and differentiates with respect to alpha (not log alpha) and log ell_d: grad[b][0] is the
+ *                       derivative with respect to log alpha divided by alpha, as in the reference.  status[b] = 1 (nlml and
+ *                       grad NaN) where K is not positive definite; the return value is then the first such row + 1.
+ *   ssmq_gp_ml2_batch   Model.optimize (bq/bqmod.py:250-285): scipy.optimize.minimize(nlml, log_par_0, method='BFGS',
+ *                       jac=True, options={gtol, maxiter}) per row (maxiter < 0: 200 P), the whole optimisation inside
+ *                       the launch.  x [B][P] minimisers, fun [B], jac [B][P] at them, hess_inv [B][P*P] (may be NULL),
+ *                       status[b] = scipy's warnflag (0, SSMQ_BFGS_MAXITER, _PRECISION_LOSS, _NAN), nit [B] and nfev [B]
+ *                       (may be NULL; the gradient comes with every evaluation: njev = nfev).  A point where K is not
+ *                       positive definite is a value of +inf there (the reference raises LinAlgError).
+ * x_obs [D][N] shared, or [B][D][N] with x_per_fit; fcn_obs [B][N][E]; jitter [N][N] added to K as the reference does.
+ * Supported: D <= 16, N <= 128, E <= 16 (else SSMQ_E_UNSUPPORTED).  Host arrays; synchronous.
+ */
+int ssmq_gp_nlml_batch(int D, int N, int E, int64_t B, const double *x_obs, int x_per_fit, const double *fcn_obs,
+                       const double *jitter, double nu, const double *log_par, double *nlml, double *grad, int32_t *status);
+int ssmq_gp_ml2_batch(int D, int N, int E, int64_t B, const double *x_obs, int x_per_fit, const double *fcn_obs,
+                      const double *jitter, double nu, double gtol, int maxiter, const double *log_par_0, double *x,
+                      double *fun, double *jac, double *hess_inv, int32_t *status, int32_t *nit, int32_t *nfev);
 /*
  * Student-t process model: the same weights as ssmq_weights_gp (StudentTProcessModel inherits bq_weights,
  * bq/bqmod.py:1060-1130); model_var / integral_var are the GP values, which the t-process rescales with the integrand
@@ -444,6 +469,18 @@ enum { SSMQ_BFGS_MAXITER = 1, SSMQ_BFGS_PRECISION_LOSS = 2, SSMQ_BFGS_NAN = 3, S
 typedef int (*ssmq_objective_fn)(void *ctx, int64_t n, int P, const int64_t *traj, const double *rows, double *vals);
 int ssmq_bfgs_lockstep_host(ssmq_objective_fn fn, void *ctx, int64_t B, int P, double fd_step, double *theta, double *hess_inv,
                             int32_t *status, int32_t *iters, int64_t *rounds);
+/*
+ * The analytic-gradient mode of the same optimiser (scipy.optimize.minimize(method='BFGS', jac=True), options gtol and
+ * maxiter; maxiter < 0: 200 P): fn(ctx, n, P, traj, rows, vals, grads) fills vals[i] and grads[i][P] with the objective
+ * and its gradient of run traj[i] at rows[i][P] and returns 0 (< 0: abort with that code).  theta [B][P]: start points in,
+ * minimisers out; fun [B], jac [B][P], hess_inv [B][P*P]; status[b] as scipy's warnflag (0, SSMQ_BFGS_MAXITER,
+ * _PRECISION_LOSS, _NAN); nit[b], nfev[b] (may be NULL): iterations, objective evaluations.  No device.
+ */
+typedef int (*ssmq_objective_grad_fn)(void *ctx, int64_t n, int P, const int64_t *traj, const double *rows, double *vals,
+                                      double *grads);
+int ssmq_bfgs_jac_lockstep_host(ssmq_objective_grad_fn fn, void *ctx, int64_t B, int P, double gtol, int maxiter,
+                                double *theta, double *fun, double *jac, double *hess_inv, int32_t *status, int32_t *nit,
+                                int32_t *nfev);
 int ssmq_gp_marginal_laplace_batch(ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, ssmq_transform *h_obs,
                                    const ssmq_integrand *f_obs, int64_t B, double jitter, const double *mean,
                                    const double *cov, const double *y, double time, const double *GQG, const double *R,

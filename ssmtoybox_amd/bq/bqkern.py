@@ -137,6 +137,18 @@ class RBFGauss(Kernel):
                                          int(bool(scaling)), pq), 'ssmq_rbf_exp_kxkx')
         return Q
 
+    def der_par(self, par_0, x):
+        """Derivatives of K (no jitter) with respect to the parameters, (N, N, 1 + D) (bq/bqkern.py:426-436): 2 K / alpha
+        (with respect to alpha itself, a quirk of the reference the ML-II gradient inherits), then (x_i - x_j)^2 / ell^2 K
+        (with respect to log ell).  K comes from the device (`eval`); the elementwise factors are formed here."""
+        p = np.asarray(par_0, dtype=np.float64).squeeze()
+        x = np.asarray(x, dtype=np.float64)
+        alpha, el = p[0], p[1:]
+        K = self.eval(p, x)
+        d_alpha = 2 * alpha ** -1 * K
+        d_el = (x[:, None, :] - x[:, :, None]) ** 2 * (el ** -2)[:, None, None] * K[None, :, :]
+        return np.concatenate((d_alpha[..., None], d_el.T), axis=2)
+
     def exp_x_kxx(self, par):
         """bq/bqkern.py:417-419."""
         return float(np.atleast_2d(par)[0, 0]) ** 2

@@ -5,8 +5,12 @@ The weights are computed on the device (`ssmq_weights_gp` / `ssmq_weights_bs`, s
 this module keeps the reference's attribute surface: `points`, `kernel`, `dim_in`, `num_pts`, `q`, `Q`, `R`, `iK`,
 `model_var`, `integral_var`, `nu`, `mulind` (bq/bqmod.py:85-106) and the `bq_weights(par, *args)` /
 `exp_model_variance` / `integral_variance` methods the reference's tests and research scripts call.
-Hyper-parameter optimisation, prediction, plotting and the multi-output models are out of scope.
+Type-II maximum likelihood of the kernel parameters - `neg_log_marginal_likelihood` and `optimize` (bq/bqmod.py:250-285,
+537-596, 1191-1245) - runs on the device too (`ssmq_gp_nlml_batch` / `ssmq_gp_ml2_batch`), with batched forms that fit
+many data sets in one launch.  Prediction, plotting and the multi-output models are out of scope.
 """
+import warnings
+
 import numpy as np
 
 from .. import _lib
@@ -33,6 +37,78 @@ def n_sum_k(n, k):
         tail = [tuple(a + b for a, b in zip(col, unit[n - 1])) for col in level[n - 1:]]
         level = head + tail
     return np.array(level, dtype=int).T.reshape(n, -1)
+
+
+ML2_MAX_DIM, ML2_MAX_PTS, ML2_MAX_OUT = 16, 128, 16
+_ML2_RANGE = 'ML-II on the device supports D <= 16 inputs, N <= 128 data points and E <= 16 outputs'
+# scipy.optimize._optimize._status_message for the BFGS warnflags 0 .. 3
+_BFGS_MESSAGES = ('Optimization terminated successfully.', 'Maximum number of iterations has been exceeded.',
+                  'Desired error not necessarily achieved due to precision loss.', 'NaN result encountered.')
+
+
+def _ml2_inputs(log_par, fcn_obs, x_obs, jitter=None):
+    """Shapes and range checks shared by the ML-II entry points, before any device call.  log_par (B, P); fcn_obs (B, N, E);
+    x_obs (D, N) or (B, D, N).  Returns C-contiguous float64 arrays and (D, N, E, B, x_per_fit)."""
+    lp = np.ascontiguousarray(log_par, dtype=np.float64)
+    y = np.asarray(fcn_obs, dtype=np.float64)
+    x = np.asarray(x_obs, dtype=np.float64)
+    if lp.ndim != 2 or y.ndim != 3 or x.ndim not in (2, 3):
+        raise ValueError('log_par must be (B, P), fcn_obs (B, N, E) and x_obs (D, N) or (B, D, N)')
+    B, P = lp.shape
+    D, N = x.shape[-2:]
+    E = y.shape[2]
+    if D > ML2_MAX_DIM or N > ML2_MAX_PTS or E > ML2_MAX_OUT:
+        raise NotImplementedError('{}; got D = {}, N = {}, E = {}'.format(_ML2_RANGE, D, N, E))
+    if P != D + 1:
+        raise ValueError('log_par needs 1 + dim = {} entries per row, got {}'.format(D + 1, P))
+    if y.shape[:2] != (B, N) or (x.ndim == 3 and x.shape[0] != B):
+        raise ValueError('fcn_obs must be ({0}, {1}, E) and x_obs ({2}, {1}) or ({0}, {2}, {1})'.format(B, N, D))
+    if jitter is None:
+        jitter = 1e-8 * np.eye(N)
+    jit = np.ascontiguousarray(np.broadcast_to(np.asarray(jitter, dtype=np.float64), (N, N)))
+    return lp, np.ascontiguousarray(y), np.ascontiguousarray(x), jit, (D, N, E, B, int(x.ndim == 3))
+
+
+def _nlml_batch(log_par, fcn_obs, x_obs, jitter, nu):
+    """(B,) values, (B, P) gradients and (B,) status (1: K not positive definite, value and gradient NaN)."""
+    lp, y, x, jit, (D, N, E, B, per_fit) = _ml2_inputs(log_par, fcn_obs, x_obs, jitter)
+    f, pf = _lib.out_c((B,))
+    g, pg = _lib.out_c((B, D + 1))
+    st = np.zeros(B, dtype=np.int32)
+    _lib.check(_lib.load().ssmq_gp_nlml_batch(D, N, E, B, _lib.as_c(x)[1], per_fit, _lib.as_c(y)[1], _lib.as_c(jit)[1],
+                                              float(nu), _lib.as_c(lp)[1], pf, pg, st.ctypes.data_as(_lib.c_int32_p)),
+               'ssmq_gp_nlml_batch')
+    return f, g, st
+
+
+def _ml2_options(options):
+    """gtol and maxiter of scipy's BFGS (the only options the device optimiser takes); norm must stay inf."""
+    options = dict(options or {})
+    gtol = float(options.pop('gtol', 1e-5))
+    maxiter = options.pop('maxiter', None)
+    norm = options.pop('norm', np.inf)
+    options.pop('disp', None)
+    if norm != np.inf:
+        raise NotImplementedError('ML-II on the device uses the max-norm of the gradient (norm=inf)')
+    if options:
+        raise NotImplementedError('BFGS options other than gtol, maxiter, norm=inf and disp are not supported on the device: '
+                                  '{}'.format(sorted(options)))
+    return gtol, (-1 if maxiter is None else int(maxiter))
+
+
+def _ml2_batch(log_par_0, fcn_obs, x_obs, nu, gtol, maxiter, jitter=None):
+    lp, y, x, jit, (D, N, E, B, per_fit) = _ml2_inputs(log_par_0, fcn_obs, x_obs, jitter)
+    P = D + 1
+    out = {k: _lib.out_c(sh) for k, sh in (('x', (B, P)), ('fun', (B,)), ('jac', (B, P)), ('hess_inv', (B, P, P)))}
+    st, nit, nfev = (np.zeros(B, dtype=np.int32) for _ in range(3))
+    _lib.check(_lib.load().ssmq_gp_ml2_batch(D, N, E, B, _lib.as_c(x)[1], per_fit, _lib.as_c(y)[1], _lib.as_c(jit)[1],
+                                             float(nu), float(gtol), int(maxiter), _lib.as_c(lp)[1], out['x'][1],
+                                             out['fun'][1], out['jac'][1], out['hess_inv'][1],
+                                             st.ctypes.data_as(_lib.c_int32_p), nit.ctypes.data_as(_lib.c_int32_p),
+                                             nfev.ctypes.data_as(_lib.c_int32_p)), 'ssmq_gp_ml2_batch')
+    res = {k: v[0] for k, v in out.items()}
+    res.update(status=st, success=st == 0, nit=nit, nfev=nfev, njev=nfev.copy())
+    return res
 
 
 class Model:
@@ -81,6 +157,68 @@ class Model:
             return None
         return RBFGauss(dim, par)
 
+    def neg_log_marginal_likelihood(self, log_par, fcn_obs, x_obs, jitter):
+        """Objective of `optimize` (bq/bqmod.py:214-248); the base model has none, as in the reference."""
+        pass
+
+    def _ml2_nu(self):
+        raise NotImplementedError('{} has no marginal likelihood'.format(type(self).__name__))
+
+    def optimize(self, log_par_0, fcn_obs, x_obs, method='BFGS', **kwargs):
+        """Kernel log-parameters by type-II maximum likelihood (bq/bqmod.py:250-285): scipy.optimize.minimize(
+        self.neg_log_marginal_likelihood, log_par_0, args=(fcn_obs, x_obs, 1e-8 I), method='BFGS', jac=True, **kwargs),
+        with the whole optimisation on the device (`ssmq_gp_ml2_batch`: SciPy's BFGS and line searches restated).
+        Returns a scipy.optimize.OptimizeResult.  `options` takes gtol and maxiter (and `tol` stands for gtol, as in
+        minimize); bounds and constraints are ignored with SciPy's warning; other methods are not implemented.  Where K is
+        not positive definite at a trial point, the objective is +inf there (the reference raises LinAlgError)."""
+        from scipy.optimize import OptimizeResult
+        if not isinstance(method, str) or method.lower() != 'bfgs':
+            raise NotImplementedError('ML-II on the device implements method=\'BFGS\' only, not {!r}'.format(method))
+        kwargs = dict(kwargs)
+        options = dict(kwargs.pop('options', None) or {})
+        tol = kwargs.pop('tol', None)
+        if tol is not None:
+            options.setdefault('gtol', tol)
+        for key in ('hess', 'hessp'):
+            if kwargs.pop(key, None) is not None:
+                warnings.warn('Method BFGS does not use Hessian{} information ({}).'.format(
+                    '-vector product' if key == 'hessp' else '', key), RuntimeWarning, stacklevel=2)
+        if np.any(kwargs.pop('constraints', ())):
+            warnings.warn('Method BFGS cannot handle constraints.', RuntimeWarning, stacklevel=2)
+        if kwargs.pop('bounds', None) is not None:
+            warnings.warn('Method BFGS cannot handle bounds.', RuntimeWarning, stacklevel=2)
+        if kwargs.pop('callback', None) is not None:
+            raise NotImplementedError('ML-II on the device takes no callback')
+        if kwargs:
+            raise TypeError('optimize() got unexpected keyword arguments {}'.format(sorted(kwargs)))
+        x0 = np.asarray(log_par_0, dtype=np.float64)
+        if x0.ndim != 1:
+            raise ValueError("'x0' must only have one dimension.")
+        y = np.asarray(fcn_obs, dtype=np.float64)
+        if y.ndim == 1:
+            y = y[:, None]
+        x = np.asarray(x_obs, dtype=np.float64)
+        gtol, maxiter = _ml2_options(options)
+        r = _ml2_batch(x0[None, :], y[None], x, self._ml2_nu(), gtol, maxiter)
+        st = int(r['status'][0])
+        return OptimizeResult(x=r['x'][0], fun=float(r['fun'][0]), jac=r['jac'][0], hess_inv=r['hess_inv'][0],
+                              nit=int(r['nit'][0]), nfev=int(r['nfev'][0]), njev=int(r['njev'][0]), status=st,
+                              success=st == 0, message=_BFGS_MESSAGES[st] if 0 <= st < 4 else 'status {}'.format(st))
+
+    def optimize_batch(self, log_par_0, fcn_obs, x_obs, **options):
+        """B independent `optimize` runs in one launch, one workgroup per fit: log_par_0 (B, P) or (P,) for all, fcn_obs
+        (B, N, E), x_obs (D, N) shared or (B, D, N); options gtol, maxiter.  Returns a dict of arrays with a leading B axis:
+        x, fun, jac, hess_inv, nit, nfev, njev, status (scipy's warnflag), success.  Row b equals optimize() on row b's
+        data, bit for bit."""
+        y = np.asarray(fcn_obs, dtype=np.float64)
+        if y.ndim == 2:
+            y = y[..., None]
+        x0 = np.asarray(log_par_0, dtype=np.float64)
+        if x0.ndim == 1:
+            x0 = np.broadcast_to(x0, (y.shape[0], x0.shape[0]))
+        gtol, maxiter = _ml2_options(options)
+        return _ml2_batch(x0, y, x_obs, self._ml2_nu(), gtol, maxiter)
+
 
 class GaussianProcessModel(Model):
     """GP quadrature weights (bq/bqmod.py:426-535)."""
@@ -96,6 +234,34 @@ class GaussianProcessModel(Model):
         self.model_var = float(w['model_var'][0])
         self.integral_var = float(w['integral_var'][0])
         return w['wm'][0], w['Wc'][0], w['Wcc'][0], self.model_var, self.integral_var
+
+    def _ml2_nu(self):
+        return 0.0
+
+    def neg_log_marginal_likelihood(self, log_par, fcn_obs, x_obs, jitter):
+        """Negative log marginal likelihood and its gradient at the kernel log-parameters (bq/bqmod.py:537-596), on the
+        device: (float, (P,) array).  fcn_obs (N, E), x_obs (D, N), jitter added to K (an (N, N) matrix, as `optimize`
+        passes it).  The gradient's first entry is taken with respect to alpha, not log alpha (RBFGauss.der_par)."""
+        return self._nlml_one(log_par, fcn_obs, x_obs, jitter)
+
+    def _nlml_one(self, log_par, fcn_obs, x_obs, jitter):
+        y = np.asarray(fcn_obs, dtype=np.float64)
+        if y.ndim == 1:
+            y = y[:, None]
+        f, g, st = _nlml_batch(np.atleast_1d(np.asarray(log_par, dtype=np.float64)).reshape(1, -1), y[None], x_obs, jitter,
+                               self._ml2_nu())
+        if st[0]:
+            raise np.linalg.LinAlgError('kernel matrix not positive definite')
+        return float(f[0]), g[0]
+
+    def neg_log_marginal_likelihood_batch(self, log_par, fcn_obs, x_obs, jitter=None):
+        """B objective evaluations in one launch: log_par (B, P), fcn_obs (B, N, E), x_obs (D, N) or (B, D, N), jitter
+        (N, N) (default 1e-8 I).  Returns values (B,) and gradients (B, P); rows whose K is not positive definite are NaN."""
+        y = np.asarray(fcn_obs, dtype=np.float64)
+        if y.ndim == 2:
+            y = y[..., None]
+        f, g, _ = _nlml_batch(np.atleast_2d(log_par), y, x_obs, jitter, self._ml2_nu())
+        return f, g
 
     def bq_weights_batch(self, pars):
         """theta-batched weights: pars (P, 1 + D) -> dict with a leading P axis (one workgroup per row)."""
@@ -122,6 +288,14 @@ class StudentTProcessModel(GaussianProcessModel):
     def __init__(self, dim, kern_par, kern_str, point_str, point_par=None, estimate_par=False, nu=4.0):
         super().__init__(dim, kern_par, kern_str, point_str, point_par, estimate_par)
         self.nu = 3.0 if nu < 2 else nu
+
+    def _ml2_nu(self):
+        return float(self.nu)
+
+    def neg_log_marginal_likelihood(self, log_par, fcn_obs, x_obs, jitter):
+        """Student-t process negative log marginal likelihood and its gradient (bq/bqmod.py:1191-1245), on the device; the
+        log Gamma terms of its constant as the reference forms them (the log of Gamma itself)."""
+        return self._nlml_one(log_par, fcn_obs, x_obs, jitter)
 
     def exp_model_variance(self, par, *args):
         """(nu - 2 + fx iK fx') / (nu - 2 + N) * model_var with the cached scaling=False inverse

@@ -189,18 +189,13 @@ struct RunT {            // _minimize_bfgs' locals of one trajectory; PM: compil
     double a_lo = 0, a_hi = 0, phi_lo = 0, phi_hi = 0, derphi_lo = 0, phi_rec = 0, a_rec = 0;
 };
 
-template <int PM>
-SSMQ_BFGS_HD inline __attribute__((always_inline)) void bfgs_advance(RunT<PM> &r, int P, double fd_step, const double *vals) {
-    const double gtol = 1e-5, inf = __builtin_huge_val();
-    const int maxiter = 200 * P, per = P + 1;
-    // value and gradient at xt (non-finite -> +inf as the Python objective, ssmtoybox_amd/ssinf.py)
-    double val[PM + 1], gt[PM];
-    for (int j = 0; j < per; ++j) {
-        const double v = vals[j];
-        val[j] = __builtin_isfinite(v) ? v : inf;
-    }
-    for (int i = 0; i < P; ++i) gt[i] = (val[i + 1] - val[0]) / ((r.xt[i] + fd_step) - r.xt[i]);
-    const double ft = val[0];
+// One step of the state machine: ft / gt are the objective's value and gradient at the pending point r.xt.  JAC (the
+// analytic-gradient mode, minimize(..., jac=True)): an accepted step takes x = xt itself, the point the value and gradient
+// were evaluated at (SciPy: xk + alpha pk in both places), and maxiter = 0 ends the run before the first iteration.  With
+// JAC = false, gtol = 1e-5 and maxiter = 200 P this is the forward-difference path's arithmetic, unchanged.
+template <int PM, bool JAC>
+SSMQ_BFGS_HD inline __attribute__((always_inline)) void bfgs_step(RunT<PM> &r, int P, double ft, const double *gt, double gtol,
+                                                                   int maxiter) {
     bool start_iteration = false;
     if (r.phase == PH_INIT) {
         r.old_fval = ft;
@@ -211,7 +206,7 @@ SSMQ_BFGS_HD inline __attribute__((always_inline)) void bfgs_advance(RunT<PM> &r
             gmax = (__builtin_isnan(gt[i]) || __builtin_isnan(gmax)) ? __builtin_nan("") : __builtin_fmax(gmax, __builtin_fabs(gt[i]));   // numpy's max keeps NaN
         }
         r.old_old_fval = r.old_fval + __builtin_sqrt(n2) / 2;
-        if (!(gmax > gtol)) {            // (a NaN gradient ends the loop as in SciPy: `while gnorm > gtol`)
+        if (!(gmax > gtol) || (JAC && maxiter <= 0)) {   // (a NaN gradient ends the loop as in SciPy: `while gnorm > gtol`)
             r.phase = PH_DONE;
             r.status = (__builtin_isnan(gmax) || __builtin_isnan(ft)) ? SSMQ_BFGS_NAN : 0;
             return;
@@ -321,7 +316,7 @@ SSMQ_BFGS_HD inline __attribute__((always_inline)) void bfgs_advance(RunT<PM> &r
         double sk[PM], yk[PM], pn = 0.0, gmax = 0.0;
         for (int i = 0; i < P; ++i) {
             sk[i] = alpha * r.pk[i];
-            r.x[i] = r.x[i] + sk[i];
+            r.x[i] = JAC ? r.xt[i] : r.x[i] + sk[i];
             yk[i] = gt[i] - r.g[i];
             r.g[i] = gt[i];
             pn += r.pk[i] * r.pk[i];
@@ -408,6 +403,35 @@ SSMQ_BFGS_HD inline __attribute__((always_inline)) void bfgs_advance(RunT<PM> &r
         r.stp = stp;
         for (int i = 0; i < P; ++i) r.xt[i] = r.x[i] + stp * r.pk[i];
     }
+}
+
+// Forward-difference mode: vals[0] is the objective at r.xt, vals[1 + i] at r.xt + fd_step e_i.
+template <int PM>
+SSMQ_BFGS_HD inline __attribute__((always_inline)) void bfgs_advance(RunT<PM> &r, int P, double fd_step, const double *vals) {
+    const double inf = __builtin_huge_val();
+    const int per = P + 1;
+    // value and gradient at xt (non-finite -> +inf as the Python objective, ssmtoybox_amd/ssinf.py)
+    double val[PM + 1], gt[PM];
+    for (int j = 0; j < per; ++j) {
+        const double v = vals[j];
+        val[j] = __builtin_isfinite(v) ? v : inf;
+    }
+    for (int i = 0; i < P; ++i) gt[i] = (val[i + 1] - val[0]) / ((r.xt[i] + fd_step) - r.xt[i]);
+    bfgs_step<PM, false>(r, P, val[0], gt, 1e-5, 200 * P);
+}
+
+// Analytic-gradient mode (scipy.optimize.minimize(fun, x0, method='BFGS', jac=True, options={gtol, maxiter})): f and g are
+// the objective's value and gradient at r.xt, taken as they are.  When the run ends, its status is decided as
+// _minimize_bfgs decides its warnflag: 2 if a line search failed or the value stopped being finite, else 1 if
+// k >= maxiter, else 3 if the gradient's max-norm, the value or x is NaN, else 0.
+template <int PM>
+SSMQ_BFGS_HD inline __attribute__((always_inline)) void bfgs_advance_jac(RunT<PM> &r, int P, double f, const double *g, double gtol,
+                                                                          int maxiter) {
+    bfgs_step<PM, true>(r, P, f, g, gtol, maxiter);
+    if (r.phase != PH_DONE || r.status == SSMQ_BFGS_PRECISION_LOSS) return;
+    bool nan = __builtin_isnan(r.old_fval);
+    for (int i = 0; i < P; ++i) nan = nan || __builtin_isnan(r.g[i]) || __builtin_isnan(r.x[i]);
+    r.status = r.k >= maxiter ? SSMQ_BFGS_MAXITER : (nan ? SSMQ_BFGS_NAN : 0);
 }
 
 template <int PM>

@@ -169,6 +169,52 @@ extern "C" int ssmq_bfgs_lockstep_host(ssmq_objective_fn fn, void *ctx, int64_t 
     return bfgs_lockstep(B, P, fd_step, ev, theta, hess_inv, status, iters, rounds);
 }
 
+// The analytic-gradient mode of the same state machine on a host objective: B runs in lock step, each round one call of fn
+// for the pending points of the unfinished runs (value and gradient together, as minimize(..., jac=True) takes them).
+extern "C" int ssmq_bfgs_jac_lockstep_host(ssmq_objective_grad_fn fn, void *ctx, int64_t B, int P, double gtol, int maxiter,
+                                           double *theta, double *fun, double *jac, double *hess_inv, int32_t *status,
+                                           int32_t *nit, int32_t *nfev) {
+    if (!fn || B < 0 || P < 1 || P > kMaxPar || (B > 0 && (!theta || !fun || !jac || !hess_inv || !status))) {
+        set_error("bfgs_jac_lockstep_host: bad argument");
+        return SSMQ_E_ARG;
+    }
+    if (maxiter < 0) maxiter = 200 * P;
+    std::vector<Run> run((size_t)B);
+    std::vector<int32_t> evals((size_t)B, 0);
+    for (int64_t b = 0; b < B; ++b) bfgs_start(run[b], P, theta + (size_t)b * P);
+    std::vector<int64_t> want;
+    std::vector<double> rows, vals, grads;
+    for (;;) {
+        want.clear();
+        for (int64_t b = 0; b < B; ++b)
+            if (run[b].phase != PH_DONE) want.push_back(b);
+        if (want.empty()) break;
+        const int64_t nw = (int64_t)want.size();
+        rows.resize((size_t)nw * P); vals.resize((size_t)nw); grads.resize((size_t)nw * P);
+        for (int64_t w = 0; w < nw; ++w)
+            for (int i = 0; i < P; ++i) rows[(size_t)w * P + i] = run[want[w]].xt[i];
+        const int rc = fn(ctx, nw, P, want.data(), rows.data(), vals.data(), grads.data());
+        if (rc < 0) return rc;
+        for (int64_t w = 0; w < nw; ++w) {
+            ++evals[want[w]];
+            bfgs_advance_jac(run[want[w]], P, vals[w], &grads[(size_t)w * P], gtol, maxiter);
+        }
+    }
+    for (int64_t b = 0; b < B; ++b) {
+        const Run &r = run[b];
+        for (int i = 0; i < P; ++i) {
+            theta[(size_t)b * P + i] = r.x[i];
+            jac[(size_t)b * P + i] = r.g[i];
+        }
+        std::memcpy(hess_inv + (size_t)b * P * P, r.H, sizeof(double) * P * P);
+        fun[b] = r.old_fval;
+        status[b] = r.status;
+        if (nit) nit[b] = r.k;
+        if (nfev) nfev[b] = evals[b];
+    }
+    return SSMQ_OK;
+}
+
 extern "C" int ssmq_gp_marginal_laplace_batch(ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, ssmq_transform *h_obs,
                                               const ssmq_integrand *f_obs, int64_t B, double jitter, const double *mean,
                                               const double *cov, const double *y, double time, const double *GQG, const double *R,
