@@ -224,7 +224,9 @@ int ssmq_rbf_exp_kxkx(int D, int N, const double *x, const double *par0, const d
  *                       status[b] = scipy's warnflag (0, SSMQ_BFGS_MAXITER, _PRECISION_LOSS, _NAN), nit [B] and nfev [B]
  *                       (may be NULL; the gradient comes with every evaluation: njev = nfev).  A point where K is not
  *                       positive definite is a value of +inf there (the reference raises LinAlgError).
- * x_obs [D][N] shared, or [B][D][N] with x_per_fit; fcn_obs [B][N][E]; jitter [N][N] added to K as the reference does.
+ * x_obs [D][N] shared, or [B][D][N] with x_per_fit; fcn_obs [B][N][E]; jitter [N][N] added to K, of which only the
+ * upper triangle is read (entry (i, j), j >= i, of K + jitter), as the reference's cho_factor(lower=False) reads it: a
+ * jitter that is not symmetric (a per-point nugget jitter[i][j] = v[j], a triangle) gives the reference's answer.
  * Supported: D <= 16, N <= 128, E <= 16 (else SSMQ_E_UNSUPPORTED).  Host arrays; synchronous.
  */
 int ssmq_gp_nlml_batch(int D, int N, int E, int64_t B, const double *x_obs, int x_per_fit, const double *fcn_obs,

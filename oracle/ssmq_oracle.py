@@ -18,6 +18,7 @@ It is a plain restatement, written from the reference's published algorithm, of 
     marginalised-filter theta step         ssinf.py:1117-1198
     performance metrics                    utils.py:18-148 (aggregation research/tpq/tpq_base.py:154-172)
     BS model / integral variance           bq/bqmod.py:995-1050
+    ML-II objective (NLML and gradient)    bq/bqmod.py:537-596, 1191-1245, bq/bqkern.py:426-436 (also in long double)
     simulators                             ssmod.py:168-199, 1011-1039, with THIS BUILD's counter-based generator
                                            (Philox4x32-10, pinned by the Random123 known-answer vectors)
 
@@ -1085,3 +1086,146 @@ def simulate_rv(fid_dyn, fid_obs, steps, B, x0, q, r, G=None, p_dyn=(), p_obs=()
         f = np.stack([integrand(fid_dyn, xa[:, b], k, p_dyn) for b in range(B)], axis=1)
         x = f + G.dot(qk) if dyn_additive else f
     return np.stack(xs, axis=1), (np.stack(ys, axis=1) if ys else None)
+
+
+# --------------------------------------------------------------------------------------------------------------
+# type-II maximum likelihood: the negative log marginal likelihood of the GP / TP and its gradient
+# --------------------------------------------------------------------------------------------------------------
+
+
+def _ml2_fns(dtype):
+    """exp, log, sqrt and the conversion of float64 input for the arithmetic `dtype`: np.float64, np.longdouble, or
+    object (mpmath numbers, for hosts whose long double is no wider than a double; ml2_terms works at 32 digits)."""
+    if dtype is object:
+        import mpmath
+
+        def conv(a):
+            return np.vectorize(lambda v: mpmath.mpf(float(v)), otypes=[object])(np.asarray(a, dtype=np.float64))
+        return (np.frompyfunc(mpmath.exp, 1, 1), np.frompyfunc(mpmath.log, 1, 1), np.frompyfunc(mpmath.sqrt, 1, 1),
+                conv)
+    return np.exp, np.log, np.sqrt, lambda a: np.asarray(a, dtype=np.float64).astype(dtype)
+
+
+def _ml2_chol(A, sqrt):
+    """Lower Cholesky factors of the stack A (..., N, N), column by column (vectorised over the stack and the rows).  Only
+    the upper triangle of A is read, as cho_factor(A) (lower=False) reads it.  A factor whose pivot is not positive is NaN
+    from there on (float dtypes) or raises (object)."""
+    N = A.shape[-1]
+    L = np.zeros_like(A)
+    for k in range(N):
+        # column k of the symmetric matrix below the diagonal is row k of A right of it
+        lk = L[..., k:k + 1, :k]                                           # (..., 1, k)
+        d = A[..., k, k] - (lk @ np.swapaxes(lk, -1, -2))[..., 0, 0]
+        if A.dtype == object:
+            if not all(v > 0 for v in np.ravel(d)):
+                raise np.linalg.LinAlgError('not positive definite')
+        else:
+            d = np.where(d > 0, d, np.nan)
+        lkk = sqrt(d)
+        L[..., k, k] = lkk
+        if k + 1 < N:
+            s = A[..., k, k + 1:] - (L[..., k + 1:, :k] @ np.swapaxes(lk, -1, -2))[..., 0]
+            L[..., k + 1:, k] = s / lkk[..., None]
+    return L
+
+
+def _ml2_solve(L, B):
+    """(L L')^-1 B for lower L (..., N, N) and B (..., N, M): forward, then backward substitution, row by row."""
+    N = L.shape[-1]
+    Z = np.zeros_like(B)
+    for k in range(N):
+        Z[..., k, :] = (B[..., k, :] - (L[..., k:k + 1, :k] @ Z[..., :k, :])[..., 0, :]) / L[..., k, k, None]
+    X = np.zeros_like(B)
+    for k in range(N - 1, -1, -1):
+        X[..., k, :] = (Z[..., k, :] - (L[..., None, k + 1:, k] @ X[..., k + 1:, :])[..., 0, :]) / L[..., k, k, None]
+    return X
+
+
+def ml2_tp_const(nu, N, dtype=np.float64):
+    """N / 2 log((nu - 2) pi) - log Gamma((nu + N) / 2) + log Gamma(nu / 2) as bq/bqmod.py:1229 forms it, the log of Gamma
+    itself: -inf where Gamma((nu + N) / 2) overflows a double (nu + N > ~343).  float64: the reference's float64 arithmetic;
+    wider dtypes: the exact constant (mpmath, 40 digits) wherever the reference's is finite."""
+    from scipy.special import gamma
+    c64 = (N / 2) * np.log((nu - 2) * np.pi) - np.log(gamma((nu + N) / 2)) + np.log(gamma(nu / 2))
+    if dtype is np.float64 or not np.isfinite(c64):
+        return c64
+    import mpmath
+    with mpmath.workdps(40):
+        c = (mpmath.mpf(N) / 2) * mpmath.log((mpmath.mpf(nu) - 2) * mpmath.pi) - mpmath.loggamma(
+            (mpmath.mpf(nu) + N) / 2) + mpmath.loggamma(mpmath.mpf(nu) / 2)
+        return c if dtype is object else np.longdouble(mpmath.nstr(c, 30))
+
+
+def ml2_terms(log_par, y, x, jitter, nu=0.0, dtype=np.float64):
+    """The pieces of ml2_nlml for a stack of R rows: value (R,), W (R, N, N) and dK (R, P, N, N), with the gradient
+    1/2 sum_ij W_ij dK_p,ij (W = E K^-1 - sum_e scale_e a_e a_e', a_e = K^-1 y_e; dK = RBFGauss.der_par).  Arguments as
+    ml2_nlml's, with a leading row axis on log_par (R, P), y (R, N, E) and, per row, x (R, D, N)."""
+    if dtype is object:
+        import mpmath
+        with mpmath.workdps(32):
+            return _ml2_terms(log_par, y, x, jitter, nu, dtype)
+    return _ml2_terms(log_par, y, x, jitter, nu, dtype)
+
+
+def _ml2_terms(log_par, y, x, jitter, nu, dtype):
+    exp, log, sqrt, conv = _ml2_fns(dtype)
+    lp = conv(log_par)
+    R, P = lp.shape
+    Y = conv(y)
+    N, E = Y.shape[1:]
+    X = conv(x)
+    X = X if X.ndim == 3 else np.broadcast_to(X, (R,) + X.shape)
+    J = conv(np.broadcast_to(np.asarray(jitter, dtype=np.float64), (N, N)))
+    par = exp(lp)
+    alpha, ell = par[:, 0], par[:, 1:]
+    # bq/bqkern.py:329-343 as rbf_eval forms it: exp(2 log alpha - maha / 2), maha as |a|^2 + |b|^2 - 2 a.b
+    Z = X / ell[:, :, None]                                               # (R, D, N)
+    nrm = np.sum(Z * Z, axis=1)                                           # (R, N)
+    maha = (nrm[:, :, None] + nrm[:, None, :]) - 2 * (np.swapaxes(Z, 1, 2) @ Z)
+    K = exp(2 * log(alpha)[:, None, None] - maha / 2)
+    L = _ml2_chol(K + J, sqrt)
+    S = _ml2_solve(L, np.concatenate([np.broadcast_to(np.eye(N, dtype=np.float64).astype(K.dtype), (R, N, N)), Y], axis=2))
+    iK, A = S[:, :, :N], S[:, :, N:]
+    yda = np.sum(Y * A, axis=1)                                           # (R, E)
+    hld = np.sum(log(np.diagonal(L, axis1=1, axis2=2)), axis=1)           # half log det
+    if nu:
+        const = ml2_tp_const(nu, N, dtype)
+        f = 0.5 * (nu + N) * np.sum(log(1 + yda / (nu - 2)), axis=1) + E * (hld + const)
+        scale = (nu + N) / (nu + yda - 2)
+    else:
+        f = E * hld + 0.5 * (np.sum(yda, axis=1) + E * N * log(conv(2 * np.pi)))
+        scale = np.ones_like(yda)
+    W = E * iK - (A * scale[:, None, :]) @ np.swapaxes(A, 1, 2)
+    # der_par (bq/bqkern.py:426-436): with respect to alpha (not log alpha), and log ell_d on the raw inputs
+    dK = np.empty((R, P, N, N), dtype=K.dtype)
+    dK[:, 0] = (2 / alpha)[:, None, None] * K
+    dX = X[:, :, None, :] - X[:, :, :, None]                              # (R, D, N, N)
+    dK[:, 1:] = dX ** 2 * (ell ** -2)[:, :, None, None] * K[:, None]
+    return f, W, dK
+
+
+def ml2_nlml(log_par, y, x, jitter, nu=0.0, dtype=np.float64):
+    """GaussianProcessModel (nu = 0) / StudentTProcessModel (nu > 2).neg_log_marginal_likelihood: bq/bqmod.py:537-596,
+    1191-1245 with RBFGauss.der_par (bq/bqkern.py:426-436).  log_par (P,), y (N, E), x (D, N), jitter a scalar, (N,) or
+    (N, N) added to K (broadcast as the reference adds it) -> (value, gradient (P,)); with a leading row axis on log_par
+    (R, P), y (R, N, E) and optionally x (R, D, N) -> ((R,), (R, P)).
+    K + jitter is read through its upper triangle, as cho_factor (lower=False) reads it; gradient entry 0 is taken with
+    respect to alpha, the others with respect to log ell_d (der_par); the TP constant is log(gamma(.)) as the reference
+    forms it, -inf where gamma overflows.  dtype np.longdouble (or object: mpmath) runs the same formulas in that
+    arithmetic with this module's own Cholesky and triangular solves (LAPACK has none); the results come back in it.
+    A row whose K + jitter is not positive definite gets NaN (the reference raises LinAlgError)."""
+    lp = np.asarray(log_par, dtype=np.float64)
+    one = lp.ndim == 1
+    if one:
+        lp, y = lp[None], np.asarray(y)[None]
+        x = np.asarray(x)[None] if np.asarray(x).ndim == 3 else x
+    f, W, dK = ml2_terms(lp, y, x, jitter, nu, dtype)
+    if dtype is object:
+        import mpmath
+        with mpmath.workdps(32):
+            g = 0.5 * np.sum(W[:, None] * dK, axis=(2, 3))
+    else:
+        g = 0.5 * np.sum(W[:, None] * dK, axis=(2, 3))
+    if dtype is not object:
+        g[np.isnan(f)] = np.nan
+    return (f[0], g[0]) if one else (f, g)

@@ -1899,14 +1899,16 @@ __device__ bool ml2_eval(const Ml2Args &a, int64_t b, Ml2Shared &sh, double *lds
         nrm[n] = s;
     }
     bsync();
-    // K + jitter, lower triangle (bq/bqkern.py:329-343: exp(2 log alpha - maha / 2), maha as |a|^2 + |b|^2 - 2 a.b)
+    // K + jitter, lower triangle (bq/bqkern.py:329-343: exp(2 log alpha - maha / 2), maha as |a|^2 + |b|^2 - 2 a.b).  The
+    // reference factors with cho_factor's default lower=False, which reads the upper triangle of K + jitter: entry (i, j),
+    // j <= i, takes the jitter's (j, i), so a jitter that is not symmetric (a per-point nugget, a triangle) counts as there.
     for (int idx = tid; idx < N * N; idx += kWgtBlock) {
         const int i = idx / N, j = idx % N;
         if (j > i) continue;
         double dot = 0.0;
         for (int d = 0; d < D; ++d) dot += zs[d * N + i] * zs[d * N + j];
         const double mh = (nrm[i] + nrm[j]) - 2.0 * dot;
-        Km[ML2_IDX(i, j)] = exp(la - 0.5 * mh) + a.jit[idx];
+        Km[ML2_IDX(i, j)] = exp(la - 0.5 * mh) + a.jit[(int64_t)j * N + i];
     }
     bsync();
     const bool pd = PACKED ? chol_packed_lds(Km, N, &sh.flag) : chol_block(Km, N, &sh.flag);

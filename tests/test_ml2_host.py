@@ -77,7 +77,7 @@ def make_objectives(rng, B, P):
     return fgs
 
 
-@pytest.mark.parametrize('P', [1, 2, 4, 6])
+@pytest.mark.parametrize('P', [1, 2, 4, 6, 8, 12, 17])
 def test_jac_lockstep_follows_scipy(P):
     rng = np.random.default_rng(300 + P)
     B = 12
@@ -90,6 +90,15 @@ def test_jac_lockstep_follows_scipy(P):
     for b in range(B):
         ref = minimize(fgs[b], x0[b], method='BFGS', jac=True)
         assert r['status'][b] == ref.status, (b, r['status'][b], ref.status, ref.message)
+        if P > 6 and b % 4 == 1:
+            # the Rosenbrock chains at P = 8 .. 17 (ML-II's P = D + 1 up to 17), 50 - 110 iterations: the two roundings of
+            # the updates part after tens of iterations (measured: nit +-1, x to 2.5e-7 of its largest entry, hess_inv to
+            # 0.14 of its largest entry, fun to 6e-14) - the same minimiser, not the same path
+            assert abs(r['nit'][b] - ref.nit) <= 1 and r['nfev'][b] >= ref.nfev - 1, (b, r['nit'][b], ref.nit)
+            assert np.abs(r['x'][b] - ref.x).max() <= 1e-6 * max(1.0, np.abs(ref.x).max()), b
+            assert np.abs(r['hess_inv'][b] - ref.hess_inv).max() <= 0.5 * np.abs(ref.hess_inv).max(), b
+            assert abs(r['fun'][b] - ref.fun) <= 1e-12 * max(1.0, abs(ref.fun))
+            continue
         assert r['nit'][b] == ref.nit, (b, r['nit'][b], ref.nit)
         assert r['nfev'][b] >= ref.nfev - 1
         # the same path (above); x to the last bits (measured: <= 4e-12 of its largest entry).  hess_inv: numpy's dot
@@ -97,7 +106,8 @@ def test_jac_lockstep_follows_scipy(P):
         # of near-equal gradients by yk'sk: measured up to 5e-8 of the largest entry on the Rosenbrock chains and the
         # log-sum-exp family at P >= 4, <= 2e-12 on the other families
         assert np.abs(r['x'][b] - ref.x).max() <= 2e-11 * max(1.0, np.abs(ref.x).max()), b
-        hbar = 1e-6 if b % 4 in (1, 2) else 1e-10
+        # P = 8 .. 17 (measured): <= 3.3e-8 on the log-sum-exp family, <= 3.6e-10 on the others
+        hbar = 1e-6 if b % 4 in (1, 2) else (1e-10 if P <= 6 else 2e-9)
         assert np.abs(r['hess_inv'][b] - ref.hess_inv).max() <= hbar * np.abs(ref.hess_inv).max(), b
         assert abs(r['fun'][b] - ref.fun) <= 1e-12 * max(1.0, abs(ref.fun))
 
