@@ -235,6 +235,27 @@ int ssmq_gp_ml2_batch(int D, int N, int E, int64_t B, const double *x_obs, int x
                       const double *jitter, double nu, double gtol, int maxiter, const double *log_par_0, double *x,
                       double *fun, double *jac, double *hess_inv, int32_t *status, int32_t *nit, int32_t *nfev);
 /*
+ * Prediction with the fitted models: GaussianProcessModel.predict (bq/bqmod.py:454-493), StudentTProcessModel.predict
+ * (:1090-1130) and BayesSardModel.predict (:840-891), B independent fits with M test points each.  With iK = sym((K(x_obs)
+ * + jitter I)^-1) at the NATURAL parameters par [B][1 + D] (rows [alpha, ell_1 .. ell_D]; scaling=True), kx = K(test,
+ * x_obs) and kxx = alpha^2:
+ *   GP (nu = 0, NB = 0)   mean = kx iK Y, var = kxx - diag(kx iK kx')
+ *   TP (nu > 2, E = 1)    the GP's, the variance times (nu - 2 + y'iK y) / (nu - 2 + tp_num_pts); tp_num_pts is the MODEL's
+ *                         point count, which the reference uses whatever x_obs holds
+ *   Bayes-Sard (NB > 0)   V = vandermonde(mulind, x_obs), Z = V'iK, iG = (Z V)^-1 by Cholesky, A = iG V', b = Z kx' - vx',
+ *                         mean = (kx - b'A) iK Y, var = kxx - diag(kx iK kx') + diag(b'iG b); mulind [D][NB], NB <= N
+ * Layouts (host arrays, row-major): x_obs [D][N] shared, or [B][D][N] with x_per_fit; fcn_obs [B][N][E]; test [D][M] shared,
+ * or [B][D][M] with test_per_fit; jitter: the scalar added to the diagonal of K.  Outputs: mean [B][M][E], var [B][M],
+ * status [B]: 0 ok, 1 = K + jitter I not positive definite, 2 = Z V not positive definite; the mean and variance of a row
+ * with a non-zero status are NaN, other rows are unaffected, and the return value is the first such row + 1.  Row b depends
+ * on row b's data alone: a batch and B single calls give the same bits.
+ * Supported: D <= 16, N <= 128, E <= 16, NB <= N, 1 <= M <= 2^31 - 1 (else SSMQ_E_UNSUPPORTED, outputs untouched).
+ * Synchronous; rows are processed in chunks so that the device workspace stays within 512 MiB.
+ */
+int ssmq_gp_predict_batch(int D, int N, int E, int64_t B, const double *x_obs, int x_per_fit, const double *fcn_obs,
+                          double jitter, double nu, int tp_num_pts, const double *par, const int32_t *mulind, int NB,
+                          int64_t M, const double *test, int test_per_fit, double *mean, double *var, int32_t *status);
+/*
  * Student-t process model: the same weights as ssmq_weights_gp (StudentTProcessModel inherits bq_weights,
  * bq/bqmod.py:1060-1130); model_var / integral_var are the GP values, which the t-process rescales with the integrand
  * values at transform time (bq/bqmod.py:1132-1190; tp_nu / tp_iK of ssmq_transform_create).

@@ -193,6 +193,10 @@ _PROTOTYPES = {
     'ssmq_gp_ml2_batch': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64, c_double_p, ctypes.c_int,
                                          c_double_p, c_double_p, ctypes.c_double, ctypes.c_double, ctypes.c_int, c_double_p,
                                          c_double_p, c_double_p, c_double_p, c_double_p, c_int32_p, c_int32_p, c_int32_p]),
+    'ssmq_gp_predict_batch': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64, c_double_p, ctypes.c_int,
+                                             c_double_p, ctypes.c_double, ctypes.c_double, ctypes.c_int, c_double_p, c_int32_p,
+                                             ctypes.c_int, ctypes.c_int64, c_double_p, ctypes.c_int, c_double_p, c_double_p,
+                                             c_int32_p]),
     'ssmq_points_count': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_int]),
     'ssmq_points': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_int, c_double_p, c_double_p,
                                    c_double_p]),

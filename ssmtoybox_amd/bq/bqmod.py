@@ -7,7 +7,10 @@ this module keeps the reference's attribute surface: `points`, `kernel`, `dim_in
 `exp_model_variance` / `integral_variance` methods the reference's tests and research scripts call.
 Type-II maximum likelihood of the kernel parameters - `neg_log_marginal_likelihood` and `optimize` (bq/bqmod.py:250-285,
 537-596, 1191-1245) - runs on the device too (`ssmq_gp_nlml_batch` / `ssmq_gp_ml2_batch`), with batched forms that fit
-many data sets in one launch.  Prediction, plotting and the multi-output models are out of scope.
+many data sets in one launch.  Prediction - `predict` of the three model families (bq/bqmod.py:454-493, 840-891,
+1090-1130) and `predict_batch`, which takes the layout of `optimize_batch` so that fits chain into predictions - runs on
+the device as well (`ssmq_gp_predict_batch`).  `plot_model` (matplotlib, host-only) and the multi-output models are out of
+scope.
 """
 import warnings
 
@@ -109,6 +112,72 @@ def _ml2_batch(log_par_0, fcn_obs, x_obs, nu, gtol, maxiter, jitter=None):
     res = {k: v[0] for k, v in out.items()}
     res.update(status=st, success=st == 0, nit=nit, nfev=nfev, njev=nfev.copy())
     return res
+
+
+def _predict_batch(model, test_data, fcn_obs, x_obs, par, nu=0.0, mulind=None):
+    """Shapes and range checks of `predict_batch`, before any device call, then `ssmq_gp_predict_batch`.  Returns the dict of
+    `predict_batch`."""
+    y = np.asarray(fcn_obs, dtype=np.float64)
+    if y.ndim == 2:
+        y = y[..., None]
+    x = np.asarray(model.points if x_obs is None else x_obs, dtype=np.float64)
+    t = np.asarray(test_data, dtype=np.float64)
+    p = model.kernel.get_parameters(par)
+    if y.ndim != 3 or x.ndim not in (2, 3) or t.ndim not in (2, 3) or p.ndim != 2:
+        raise ValueError('fcn_obs must be (B, N, E), x_obs (D, N) or (B, D, N), test_data (D, M) or (B, D, M) and par '
+                         '(1 + D,) or (B, 1 + D)')
+    B, N, E = y.shape
+    D, M = t.shape[-2:]
+    NB = 0
+    if mulind is not None:
+        mulind = np.asarray(mulind)
+        if mulind.ndim != 2:
+            raise ValueError('the multi-index matrix must be (dim, num_basis), got {}'.format(mulind.shape))
+        NB = mulind.shape[1]
+    if D > ML2_MAX_DIM or x.shape[-2] > ML2_MAX_DIM or x.shape[-1] > ML2_MAX_PTS or N > ML2_MAX_PTS or E > ML2_MAX_OUT:
+        raise NotImplementedError('{} (prediction has the range of ML-II); got D = {}, N = {}, E = {}'.format(
+            _ML2_RANGE.replace('ML-II', 'prediction'), max(D, x.shape[-2]), max(N, x.shape[-1]), E))
+    if M < 1 or M > 2 ** 31 - 1:
+        raise NotImplementedError('prediction on the device needs 1 <= M <= 2^31 - 1 test points, got M = {}'.format(M))
+    if NB > x.shape[-1]:
+        raise NotImplementedError('Bayes-Sard prediction on the device needs num_basis <= N; got {} basis functions on {} '
+                                  'points'.format(NB, x.shape[-1]))
+    if nu != 0.0 and E != 1:
+        # the reference's fcn_obs.T.dot(iK) fails for more than one output (bq/bqmod.py:1129)
+        raise ValueError('the Student-t process predicts one output: fcn_obs must be (N,) or (1, N), got E = {}'.format(E))
+    if x.shape[-2:] != (D, N) or (x.ndim == 3 and x.shape[0] != B) or (t.ndim == 3 and t.shape[0] != B):
+        raise ValueError('x_obs must be ({0}, {1}) or ({2}, {0}, {1}) and test_data ({0}, M) or ({2}, {0}, M)'.format(D, N, B))
+    if NB and mulind.shape[0] != D:
+        raise ValueError('the multi-index matrix must be (dim, num_basis) = ({}, .), got {}'.format(D, mulind.shape))
+    if p.shape[1] != D + 1 or p.shape[0] not in (1, B):
+        raise ValueError('par needs 1 + dim = {} entries per row and 1 or {} rows, got {}'.format(D + 1, B, p.shape))
+    if nu != 0.0 and not nu > 2.0:
+        raise ValueError('the Student-t process needs nu > 2, got {}'.format(nu))
+    p = np.ascontiguousarray(np.broadcast_to(p, (B, D + 1)), dtype=np.float64)
+    mean, pm = _lib.out_c((B, M, E))
+    var, pv = _lib.out_c((B, M))
+    st = np.zeros(B, dtype=np.int32)
+    mi = np.ascontiguousarray(mulind, dtype=np.int32) if NB else None
+    _lib.check(_lib.load().ssmq_gp_predict_batch(
+        D, N, E, B, _lib.as_c(x)[1], int(x.ndim == 3), _lib.as_c(y)[1], float(model.kernel.jitter), float(nu),
+        int(model.num_pts), _lib.as_c(p)[1], mi.ctypes.data_as(_lib.c_int32_p) if NB else None, NB, M, _lib.as_c(t)[1],
+        int(t.ndim == 3), pm, pv, st.ctypes.data_as(_lib.c_int32_p)), 'ssmq_gp_predict_batch')
+    return {'mean': mean, 'var': var, 'status': st}
+
+
+def _predict_one(model, test_data, fcn_obs, x_obs, par, **model_args):
+    """The reference's single prediction through the batch entry point: fcn_obs (E, N) or (N,), outputs first."""
+    y = np.asarray(fcn_obs, dtype=np.float64)
+    if y.ndim == 1:
+        y = y[None, :]
+    if y.ndim != 2 or np.asarray(test_data).ndim != 2:
+        raise ValueError('fcn_obs must be (E, N) or (N,) and test_data (D, M)')
+    r = _predict_batch(model, test_data, y.T[None], x_obs, par, **model_args)
+    if r['status'][0] == 1:
+        raise np.linalg.LinAlgError('Matrix is not positive definite')
+    if r['status'][0]:
+        raise np.linalg.LinAlgError('Bayes-Sard prediction: V\' iK V is not positive definite')
+    return np.squeeze(r['mean'][0]), np.squeeze(r['var'][0])
 
 
 class Model:
@@ -220,6 +289,19 @@ class Model:
         return _ml2_batch(x0, y, x_obs, self._ml2_nu(), gtol, maxiter)
 
 
+    def predict_batch(self, test_data, fcn_obs, x_obs=None, par=None, **model_args):
+        """B independent predictions in one call, in the layout of `optimize_batch`: fcn_obs (B, N, E) (or (B, N)), par
+        (B, 1 + D) natural parameters or one row for all (default: the kernel's own), x_obs (D, N) shared or (B, D, N)
+        (default: self.points), test_data (D, M) shared or (B, D, M).  Returns a dict: mean (B, M, E), var (B, M), status (B,)
+        int32 - 0 ok, 1 = K + jitter I not positive definite, 2 = the Bayes-Sard V' iK V not positive definite; rows with a
+        non-zero status are NaN, the others are unaffected.  Row b equals predict() on row b's data, bit for bit.  After a
+        fit: model.predict_batch(xt, Y, x, par=np.exp(model.optimize_batch(lp0, Y, x)['x']))."""
+        return _predict_batch(self, test_data, fcn_obs, x_obs, par, **self._predict_args(**model_args))
+
+    def _predict_args(self, **model_args):
+        raise NotImplementedError('{} has no predict'.format(type(self).__name__))
+
+
 class GaussianProcessModel(Model):
     """GP quadrature weights (bq/bqmod.py:426-535)."""
 
@@ -263,6 +345,19 @@ class GaussianProcessModel(Model):
         f, g, _ = _nlml_batch(np.atleast_2d(log_par), y, x_obs, jitter, self._ml2_nu())
         return f, g
 
+    def predict(self, test_data, fcn_obs, x_obs=None, par=None):
+        """GP posterior mean and variance at the test inputs (bq/bqmod.py:454-493), on the device.  test_data (D, M);
+        fcn_obs (E, N) or (N,) - OUTPUTS FIRST, as the reference's predict takes them, not the (N, E) of `optimize`; x_obs
+        (D, N) training inputs (default: self.points); par natural kernel parameters [alpha, ell_1 .. ell_D] (default: the
+        kernel's own).  With iK = sym((K(x_obs) + jitter I)^-1), kx = K(test, x_obs), kxx = alpha^2: mean = squeeze(kx iK
+        fcn_obs.T), (M,) for one output and (M, E) otherwise; var = squeeze(kxx - diag(kx iK kx')), (M,).  At a training
+        input the variance is a jitter-sized number that rounding may push below zero, here as in the reference.  Raises
+        numpy.linalg.LinAlgError where K + jitter I is not positive definite."""
+        return _predict_one(self, test_data, fcn_obs, x_obs, par, **self._predict_args())
+
+    def _predict_args(self):
+        return {}
+
     def bq_weights_batch(self, pars):
         """theta-batched weights: pars (P, 1 + D) -> dict with a leading P axis (one workgroup per row)."""
         return device_gp_weights(self.points, np.atleast_2d(pars), self.kernel.jitter)
@@ -296,6 +391,15 @@ class StudentTProcessModel(GaussianProcessModel):
         """Student-t process negative log marginal likelihood and its gradient (bq/bqmod.py:1191-1245), on the device; the
         log Gamma terms of its constant as the reference forms them (the log of Gamma itself)."""
         return self._nlml_one(log_par, fcn_obs, x_obs, jitter)
+
+    def predict(self, test_data, fcn_obs, x_obs=None, par=None, nu=None):
+        """Student-t process prediction (bq/bqmod.py:1090-1130): the GP's mean, and the GP's variance times (nu - 2 +
+        y' iK y) / (nu - 2 + self.num_pts).  Two quirks of the reference are kept: the denominator counts the MODEL's points,
+        not the columns of x_obs, and there is one output only - fcn_obs (N,) or (1, N); more raise ValueError."""
+        return _predict_one(self, test_data, fcn_obs, x_obs, par, **self._predict_args(nu=nu))
+
+    def _predict_args(self, nu=None):
+        return {'nu': float(self.nu if nu is None else nu)}
 
     def exp_model_variance(self, par, *args):
         """(nu - 2 + fx iK fx') / (nu - 2 + N) * model_var with the cached scaling=False inverse
@@ -358,6 +462,18 @@ class BayesSardModel(Model):
         self.model_var = float(out['mv'][0][0])
         self.integral_var = float(out['iv'][0][0])
         return out['wm'][0], out['Wc'][0], out['Wcc'][0], self.model_var, self.integral_var
+
+    def predict(self, test_data, fcn_obs, x_obs=None, par=None, mulind=None):
+        """GP prediction with the polynomial prior mean (bq/bqmod.py:840-891, term by term), on the device: V =
+        vandermonde(mulind, x_obs), Z = V' iK, iViKV = (Z V)^-1 by Cholesky, A = iViKV V', b = Z kx' - vx', mean = (kx -
+        b' A) iK fcn_obs.T, var = kxx - diag(kx iK kx') + diag(b' iViKV b).  Arguments and shapes as
+        GaussianProcessModel.predict (fcn_obs (E, N) or (N,), outputs first); mulind (dim, num_basis), default self.mulind.
+        Needs num_basis <= N (NotImplementedError otherwise) and Z V positive definite (numpy.linalg.LinAlgError, as the
+        reference)."""
+        return _predict_one(self, test_data, fcn_obs, x_obs, par, **self._predict_args(mulind=mulind))
+
+    def _predict_args(self, mulind=None):
+        return {'mulind': self.mulind if mulind is None else mulind}
 
     def _moments(self, multi_ind, x=None, par=None, want=('px',)):
         """The polynomial expectations behind the weights (`ssmq_bs_moments`), one array per name in `want`."""
