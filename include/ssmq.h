@@ -209,6 +209,37 @@ int ssmq_rbf_factor(int D, int N, const double *x, const double *par, int P, int
 int ssmq_rbf_exp_kxkx(int D, int N, const double *x, const double *par0, const double *par1, int scaling, double *Q);
 
 /*
+ * The 'rbf-student' kernel (RBFStudent, bq/bqkern.py:457-536): the RBF kernel with its expectations under a standard
+ * multivariate Student-t density with dof degrees of freedom, estimated by Monte Carlo on the device.  Sample s is x = z /
+ * sqrt(u), z ~ N(0, I_D), u ~ Gamma(dof / 2, scale 2 / dof) (utils.py:349-382), drawn by the counter-based generator of the
+ * simulator as a function of (seed, s) alone.
+ *   ssmq_rbf_student_expect  exp_x_kx, exp_x_xkx and exp_x_kxkx (scaling=False) from ONE set of num_samples samples (the
+ *                            reference draws three): q [N] = E[k0], R [D][N] = E[x k0'], Q [N][N] with Q[i][j] = E[k1_i k0_j],
+ *                            k0 / k1 the kernel at par0 / par1 [1 + D] (par1 NULL or equal to par0: one kernel; Q is then
+ *                            symmetric bit for bit).  Any output may be NULL.
+ *   ssmq_rbf_student_kxy     exp_xy_kxy as the reference estimates it (:529-536): 10 000 batches of 200 samples, per batch the
+ *                            sum of alpha^2 k(x_a, x_b) over all 200 x 200 pairs (diagonal included), the total divided by
+ *                            num_samples - about 200 E[k(x, y)] at the default 2e6 samples, a quirk kept as it is.  out [1];
+ *                            batch_sums [10000] (may be NULL): the per-batch sums.
+ *   ssmq_weights_gp_given    GaussianProcessModel.bq_weights (bq/bqmod.py:495-523) from expectations the caller supplies: iK =
+ *                            sym((K + jitter I)^-1), scaling=False, then wm = q iK, Wc = sym(iK Q iK), Wcc = R iK, model_var =
+ *                            alpha^2 (1 - tr(Q iK)), integral_var = kbar - q'iK q - the code path of ssmq_weights_gp with q, R,
+ *                            Q, kbar given instead of the Gaussian closed forms.  One parameter row; status / return value as
+ *                            ssmq_weights_gp.
+ * Samples are summed in slots of 8192 (at most 1024 slots, then multiples of 8192) in sample order and the slots in index order,
+ * without atomics: the same bits from run to run, whatever the launch grid.
+ * Supported: D <= 16, N <= 128, 1 <= num_samples < 2^31, dof > 0 (else SSMQ_E_UNSUPPORTED, outputs untouched).  Host arrays;
+ * synchronous.
+ */
+int ssmq_rbf_student_expect(int D, int N, const double *x, const double *par0, const double *par1, double dof,
+                            int64_t num_samples, uint64_t seed, double *q, double *R, double *Q);
+int ssmq_rbf_student_kxy(int D, const double *par, double dof, int64_t num_samples, uint64_t seed, double *out,
+                         double *batch_sums);
+int ssmq_weights_gp_given(int D, int N, const double *xi, const double *par, double jitter, const double *q, const double *R,
+                          const double *Q, double kbar, double *wm, double *Wc, double *Wcc, double *iK, double *model_var,
+                          double *integral_var, int32_t *status);
+
+/*
  * Type-II maximum likelihood of the RBF kernel's parameters [alpha, ell_1 .. ell_D] (P = D + 1), B independent rows in
  * one launch, one workgroup each.
  *   ssmq_gp_nlml_batch  GaussianProcessModel.neg_log_marginal_likelihood (bq/bqmod.py:537-596), nu = 0, and

@@ -225,6 +225,12 @@ _PROTOTYPES = {
                                        ctypes.c_double, c_double_p, c_double_p, c_double_p, c_int32_p]),
     'ssmq_rbf_exp_kxkx': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, c_double_p, c_double_p, c_double_p, ctypes.c_int,
                                          c_double_p]),
+    'ssmq_rbf_student_expect': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, c_double_p, c_double_p, c_double_p, ctypes.c_double,
+                                               ctypes.c_int64, ctypes.c_uint64, c_double_p, c_double_p, c_double_p]),
+    'ssmq_rbf_student_kxy': (ctypes.c_int, [ctypes.c_int, c_double_p, ctypes.c_double, ctypes.c_int64, ctypes.c_uint64,
+                                            c_double_p, c_double_p]),
+    'ssmq_weights_gp_given': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, c_double_p, c_double_p, ctypes.c_double, c_double_p,
+                                             c_double_p, c_double_p, ctypes.c_double] + [c_double_p] * 6 + [c_int32_p]),
     'ssmq_bs_moments': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, c_double_p, c_double_p, c_int32_p, ctypes.c_int,
                                        c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]),
     'ssmq_current_device': (ctypes.c_int, []),

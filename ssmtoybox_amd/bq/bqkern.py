@@ -1,12 +1,14 @@
 """
 Kernels of the integrand model: attribute carrier + device-computed expectations (reference: ssmtoybox/bq/bqkern.py).
 
-Only the RBF kernel with Gaussian expectations is on the accelerated path (`RBFGauss`, bq/bqkern.py:295-454).  The
-Monte-Carlo `RBFStudent` and the approximate `RQ` kernels of the reference are out of scope (SURVEY.md section 2, row
-3b): their weights are RNG-dependent and enter this build as injected data (assign tf.wm / tf.Wc / tf.Wcc).
+The RBF kernel with Gaussian expectations (`RBFGauss`, bq/bqkern.py:295-454) and with Monte-Carlo Student-t expectations
+(`RBFStudent`, bq/bqkern.py:457-536) are on the accelerated path.  The approximate `RQ` kernel of the reference is out of
+scope.
 
-All numbers come from one device kernel (`ssmq_weights_gp`, ssmtoybox_amd/csrc/ssmq_weights.hip), which evaluates the
-kernel matrix, its Cholesky-based inverse and the expectations q, R, Q together; the methods below select from it.
+`RBFGauss`: all numbers come from one device kernel (`ssmq_weights_gp`, ssmtoybox_amd/csrc/ssmq_weights.hip), which evaluates
+the kernel matrix, its Cholesky-based inverse and the expectations q, R, Q together; the methods below select from it.
+`RBFStudent`: the expectations come from the Monte-Carlo kernels of ssmtoybox_amd/csrc/ssmq_student_mc.hip, the weights from
+`ssmq_weights_gp_given` - the algebra of `ssmq_weights_gp` on given expectations.
 """
 import numpy as np
 
@@ -157,3 +159,130 @@ class RBFGauss(Kernel):
         """bq/bqkern.py:421-424."""
         p = np.atleast_2d(par).astype(float)[0]
         return p[0] ** 2 * np.prod(2 * p[1:] ** -2 + 1.0) ** -0.5
+
+
+STUDENT_MC_MAX_DIM, STUDENT_MC_MAX_PTS = 16, 128
+_STUDENT_MC_RANGE = ("the 'rbf-student' expectations on the device support D <= 16 inputs, N <= 128 points, "
+                     "1 <= num_samples < 2^31 and dof > 0")
+
+
+class RBFStudent(RBFGauss):
+    """RBF kernel whose expectations are taken under a standard multivariate Student-t density with `dof` degrees of freedom
+    and estimated by Monte Carlo over `num_samples` samples (bq/bqkern.py:457-536), on the device.  `eval`, `eval_chol` and
+    `eval_inv_dot` are RBFGauss's.  Constructor as in the reference plus `seed`; `num_batches` is accepted and ignored - it
+    only shaped the reference's NumPy memory use (`batch_size` is still derived from it, as an attribute).
+
+    Differences from the reference, both deliberate:
+      * the random numbers are a function of (seed, sample index) alone, so repeated calls with the same `seed` return the
+        same numbers, bit for bit; the reference advances NumPy's global stream with every call.  Change `seed` (or `dof`,
+        `num_samples`) by assigning the attribute and computing the weights again;
+      * `expectations()` - and with it the model's `bq_weights` - estimates q, R and Q from ONE sample set in one pass (the
+        reference draws three independent sets).  Every estimate is still unbiased, and Q - q q' is then a sample covariance,
+        hence positive semi-definite.  The single-quantity methods below draw the same samples, so exp_x_kxkx(p, p, x) is
+        bit-equal to the Q of expectations(p, x).
+    `exp_xy_kxy` reproduces the reference's estimator including its normalisation quirk (see there).  Parameter estimation
+    is not supported (`supports_parameter_estimation = False`, as in the reference)."""
+    supports_parameter_estimation = False
+
+    def __init__(self, dim, par, jitter=1e-8, dof=4.0, num_samples=2e6, num_batches=1000, seed=0):
+        # parameters of the standard Student's density
+        self.mean = np.zeros((dim, ))
+        self.scale_mat = np.eye(dim)
+        self.dof = dof
+        # parameters of the Monte-Carlo approximation
+        self.num_samples = int(num_samples)
+        self.num_batches = int(num_batches)
+        self.batch_size = int(num_samples // num_batches)
+        self.seed = int(seed)
+        super().__init__(dim, par, jitter)
+
+    def _check_range(self, D, N=1):
+        """Raised in Python, before the library is loaded."""
+        S = int(self.num_samples)
+        if not (1 <= D <= STUDENT_MC_MAX_DIM and 1 <= N <= STUDENT_MC_MAX_PTS and 1 <= S < 2 ** 31 and self.dof > 0
+                and np.isfinite(self.dof)):
+            raise NotImplementedError('{}; got D = {}, N = {}, num_samples = {}, dof = {}'.format(
+                _STUDENT_MC_RANGE, D, N, S, self.dof))
+        return S
+
+    def expectations(self, par_0, x, par_1=None):
+        """(q (N,), R (D, N), Q (N, N)) with scaling=False from one pass over one sample set (`ssmq_rbf_student_expect`):
+        q = E[k0], R = E[x k0'], Q[i, j] = E[k1_i k0_j] with k0 / k1 the kernel at par_0 / par_1 (default: par_0)."""
+        x = np.asarray(x, dtype=np.float64)
+        D, N = x.shape
+        S = self._check_range(D, N)
+        p0 = self._row(par_0)
+        p1 = p0 if par_1 is None else self._row(par_1)
+        if p0.shape[1] != D + 1 or p1.shape[1] != D + 1:
+            raise ValueError('kernel parameters must have 1 + dim entries per row')
+        lib = _lib.load()
+        x, px = _lib.as_c(x)
+        q, pq = _lib.out_c((N,))
+        R, pr = _lib.out_c((D, N))
+        Q, pQ = _lib.out_c((N, N))
+        _lib.check(lib.ssmq_rbf_student_expect(D, N, px, _lib.as_c(p0)[1], _lib.as_c(p1)[1], float(self.dof), S,
+                                               int(self.seed) & (2 ** 64 - 1), pq, pr, pQ), 'ssmq_rbf_student_expect')
+        return q, R, Q
+
+    def exp_x_kx(self, par, x, scaling=False):
+        """Kernel mean E[k(x, x_i)], (N,) (bq/bqkern.py:476-482)."""
+        q = self.expectations(par, x)[0]
+        return q * float(np.atleast_2d(par)[0, 0]) ** 2 if scaling else q
+
+    def exp_x_xkx(self, par, x, scaling=False):
+        """E[x k(x, x_i)], (D, N) (bq/bqkern.py:484-491)."""
+        R = self.expectations(par, x)[1]
+        return R * float(np.atleast_2d(par)[0, 0]) ** 2 if scaling else R
+
+    def exp_x_kxkx(self, par_0, par_1, x, scaling=False):
+        """Q[i, j] = E[k(x, x_i; par_1) k(x, x_j; par_0)], both kernels on the same samples (bq/bqkern.py:493-524); the two
+        parameter rows may differ."""
+        Q = self.expectations(par_0, x, par_1)[2]
+        if scaling:
+            Q = Q * (float(np.atleast_2d(par_0)[0, 0]) * float(np.atleast_2d(par_1)[0, 0])) ** 2
+        return Q
+
+    def exp_x_kxx(self, par):
+        """bq/bqkern.py:526-527."""
+        return float(np.atleast_2d(par)[0, 0]) ** 2
+
+    def exp_xy_kxy(self, par, batch_sums=False):
+        """The reference's estimator as it is (bq/bqkern.py:529-536): 10 000 batches of 200 samples (hard-coded there), per
+        batch the sum of eval(par, xs, xs) over all 200 x 200 pairs, the diagonal included, scaling=True; the total divided
+        by `num_samples`.  That is NOT the pair mean E[k(x, y)]: at the default 2e6 samples it is alpha^2 (199 E[k] + 1), about
+        200 times it - a quirk of the reference that its integral variance inherits, kept here.
+        `batch_sums=True` also returns the (10000,) per-batch sums."""
+        p = self._row(par)
+        D = p.shape[1] - 1
+        S = self._check_range(D)
+        out, po = _lib.out_c((1,))
+        sums, ps = _lib.out_c((10000,)) if batch_sums else (None, None)
+        _lib.check(_lib.load().ssmq_rbf_student_kxy(D, _lib.as_c(p)[1], float(self.dof), S, int(self.seed) & (2 ** 64 - 1), po,
+                                                    ps), 'ssmq_rbf_student_kxy')
+        return (float(out[0]), sums) if batch_sums else float(out[0])
+
+
+def device_student_weights(points, par, kernel):
+    """GP-quadrature quantities of one parameter row with the Monte-Carlo expectations of an `RBFStudent` kernel: the dict of
+    `device_gp_weights` (leading axis of length 1).  The expectations and the weights are computed on the device
+    (`ssmq_rbf_student_expect`, `ssmq_rbf_student_kxy`, `ssmq_weights_gp_given`)."""
+    par = np.atleast_2d(np.asarray(par, dtype=np.float64))[:1]
+    x, px = _lib.as_c(points)
+    D, N = x.shape
+    kernel._check_range(D, N)
+    if par.shape[1] != D + 1:
+        raise ValueError('kernel parameters must have 1 + dim entries per row')
+    q, R, Q = kernel.expectations(par, x)
+    kbar = kernel.exp_xy_kxy(par)
+    out = {k: _lib.out_c(s) for k, s in (('wm', (1, N)), ('Wc', (1, N, N)), ('Wcc', (1, D, N)), ('iK', (1, N, N)),
+                                         ('model_var', (1,)), ('integral_var', (1,)))}
+    st = np.zeros(1, dtype=np.int32)
+    rc = _lib.check(_lib.load().ssmq_weights_gp_given(
+        D, N, px, _lib.as_c(par)[1], float(kernel.jitter), _lib.as_c(q)[1], _lib.as_c(R)[1], _lib.as_c(Q)[1], float(kbar),
+        out['wm'][1], out['Wc'][1], out['Wcc'][1], out['iK'][1], out['model_var'][1], out['integral_var'][1],
+        st.ctypes.data_as(_lib.c_int32_p)), 'ssmq_weights_gp_given')
+    res = {k: v[0] for k, v in out.items()}
+    res.update(q=q[None], R=R[None], Q=Q[None], status=st, kbar=kbar)
+    if rc > 0:
+        raise np.linalg.LinAlgError('kernel matrix not positive definite for parameter row {}'.format(rc - 1))
+    return res

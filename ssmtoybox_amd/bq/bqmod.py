@@ -19,7 +19,7 @@ import numpy as np
 from .. import _lib
 from ..mtran import (SphericalRadialTransform, UnscentedTransform, GaussHermiteTransform,
                      FullySymmetricStudentTransform)
-from .bqkern import RBFGauss, device_gp_weights
+from .bqkern import RBFGauss, RBFStudent, device_gp_weights, device_student_weights
 
 
 def n_sum_k(n, k):
@@ -184,7 +184,7 @@ class Model:
     """Kernel + point set (bq/bqmod.py:15-106)."""
 
     _supported_points_ = ['sr', 'ut', 'gh', 'fs']
-    _supported_kernels_ = ['rbf']
+    _supported_kernels_ = ['rbf', 'rbf-student']
 
     def __init__(self, dim, kern_par, kern_str, point_str, point_par, estimate_par):
         self.kernel = Model.get_kernel(dim, kern_str, kern_par)
@@ -219,11 +219,15 @@ class Model:
 
     @staticmethod
     def get_kernel(dim, kernel, par):
-        """bq/bqmod.py:384-423 ('rq' and 'rbf-student' are not on this path)."""
+        """bq/bqmod.py:384-423 ('rq' is not on this path).  'rbf-student' is built with the constructor's defaults, as in the
+        reference (:420-421): dof = 4.0 whatever the noise's or the transform's nu is, 2e6 samples, seed 0; change them by
+        assigning the kernel's attributes and computing the weights again."""
         kernel = kernel.lower()
         if kernel not in Model._supported_kernels_:
             print('Kernel {} not supported. Supported kernels are {}.'.format(kernel, Model._supported_kernels_))
             return None
+        if kernel == 'rbf-student':
+            return RBFStudent(dim, par)
         return RBFGauss(dim, par)
 
     def neg_log_marginal_likelihood(self, log_par, fcn_obs, x_obs, jitter):
@@ -233,6 +237,11 @@ class Model:
     def _ml2_nu(self):
         raise NotImplementedError('{} has no marginal likelihood'.format(type(self).__name__))
 
+    def _check_estimation(self):
+        if not getattr(self.kernel, 'supports_parameter_estimation', True):
+            raise NotImplementedError('{} does not support parameter estimation (supports_parameter_estimation = False, as in '
+                                      'the reference)'.format(type(self.kernel).__name__))
+
     def optimize(self, log_par_0, fcn_obs, x_obs, method='BFGS', **kwargs):
         """Kernel log-parameters by type-II maximum likelihood (bq/bqmod.py:250-285): scipy.optimize.minimize(
         self.neg_log_marginal_likelihood, log_par_0, args=(fcn_obs, x_obs, 1e-8 I), method='BFGS', jac=True, **kwargs),
@@ -241,6 +250,7 @@ class Model:
         minimize); bounds and constraints are ignored with SciPy's warning; other methods are not implemented.  Where K is
         not positive definite at a trial point, the objective is +inf there (the reference raises LinAlgError)."""
         from scipy.optimize import OptimizeResult
+        self._check_estimation()
         if not isinstance(method, str) or method.lower() != 'bfgs':
             raise NotImplementedError('ML-II on the device implements method=\'BFGS\' only, not {!r}'.format(method))
         kwargs = dict(kwargs)
@@ -279,6 +289,7 @@ class Model:
         (B, N, E), x_obs (D, N) shared or (B, D, N); options gtol, maxiter.  Returns a dict of arrays with a leading B axis:
         x, fun, jac, hess_inv, nit, nfev, njev, status (scipy's warnflag), success.  Row b equals optimize() on row b's
         data, bit for bit."""
+        self._check_estimation()
         y = np.asarray(fcn_obs, dtype=np.float64)
         if y.ndim == 2:
             y = y[..., None]
@@ -308,10 +319,17 @@ class GaussianProcessModel(Model):
     def __init__(self, dim, kern_par, kern_str, point_str, point_par=None, estimate_par=False):
         super().__init__(dim, kern_par, kern_str, point_str, point_par, estimate_par)
 
+    def _device_weights(self, par):
+        """All quantities of one parameter row: the Gaussian closed forms, or the kernel's Monte-Carlo expectations ('rbf-student',
+        with the kernel's current dof / num_samples / seed) through the same weight algebra."""
+        if isinstance(self.kernel, RBFStudent):
+            return device_student_weights(self.points, par[:1], self.kernel)
+        return device_gp_weights(self.points, par[:1], self.kernel.jitter)
+
     def bq_weights(self, par, *args):
         """wm = q iK, Wc = iK Q iK (symmetrised), Wcc = R iK and the model / integral variances (bq/bqmod.py:495-523)."""
         par = self.kernel.get_parameters(par)
-        w = device_gp_weights(self.points, par[:1], self.kernel.jitter)
+        w = self._device_weights(par)
         self.q, self.Q, self.R, self.iK = w['q'][0], w['Q'][0], w['R'][0], w['iK'][0]
         self.model_var = float(w['model_var'][0])
         self.integral_var = float(w['integral_var'][0])
@@ -359,7 +377,10 @@ class GaussianProcessModel(Model):
         return {}
 
     def bq_weights_batch(self, pars):
-        """theta-batched weights: pars (P, 1 + D) -> dict with a leading P axis (one workgroup per row)."""
+        """theta-batched weights: pars (P, 1 + D) -> dict with a leading P axis (one workgroup per row).  Gaussian expectations
+        only."""
+        if isinstance(self.kernel, RBFStudent):
+            raise NotImplementedError("theta-batched weights are not implemented for the 'rbf-student' kernel")
         return device_gp_weights(self.points, np.atleast_2d(pars), self.kernel.jitter)
 
     def exp_model_variance(self, par, *args):
@@ -374,7 +395,7 @@ class GaussianProcessModel(Model):
     def integral_variance(self, par, *args):
         """bq/bqmod.py:530-535."""
         par = self.kernel.get_parameters(par)
-        return float(device_gp_weights(self.points, par[:1], self.kernel.jitter)['integral_var'][0])
+        return float(self._device_weights(par)['integral_var'][0])
 
 
 class StudentTProcessModel(GaussianProcessModel):

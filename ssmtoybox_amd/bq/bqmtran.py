@@ -37,6 +37,14 @@ class BQTransform(_DeviceApply, MomentTransform):
         return BayesSardModel(dim_in, kern_par, point_str=point_str, point_par=point_par, estimate_par=estimate_par,
                               **kwargs)
 
+    def _set_kernel_attributes(self, kern_attr):
+        """Attributes of the model's kernel (the 'rbf-student' kernel's dof, num_samples, seed) set before the weights are
+        first computed; afterwards assign them to `model.kernel` and call `weights()` again."""
+        for key, value in (kern_attr or {}).items():
+            if not hasattr(self.model.kernel, key):
+                raise AttributeError('{} has no attribute {!r}'.format(type(self.model.kernel).__name__, key))
+            setattr(self.model.kernel, key, value)
+
     def weights(self, par, *args):
         """bq/bqmtran.py:111-130."""
         wm, wc, wcc, emv, ivar = self.model.bq_weights(par, *args)
@@ -69,10 +77,13 @@ class BQTransform(_DeviceApply, MomentTransform):
 
 
 class GaussianProcessTransform(BQTransform):
-    """GP quadrature moment transform (bq/bqmtran.py:285-310)."""
+    """GP quadrature moment transform (bq/bqmtran.py:285-310).  kern_str 'rbf' or 'rbf-student'; kern_attr (this build's
+    addition): a dict of kernel attributes set before the weights are computed."""
 
-    def __init__(self, dim_in, dim_out, kern_par, kern_str='rbf', point_str='ut', point_par=None, estimate_par=False):
+    def __init__(self, dim_in, dim_out, kern_par, kern_str='rbf', point_str='ut', point_par=None, estimate_par=False,
+                 kern_attr=None):
         super().__init__(dim_in, dim_out, kern_par, 'gp', kern_str, point_str, point_par, estimate_par)
+        self._set_kernel_attributes(kern_attr)
         self.wm, self.Wc, self.Wcc = self.weights(kern_par)
 
 
@@ -91,11 +102,13 @@ class BayesSardTransform(BQTransform):
 
 
 class StudentTProcessTransform(BQTransform):
-    """Student-t process quadrature moment transform (bq/bqmtran.py:363-415)."""
+    """Student-t process quadrature moment transform (bq/bqmtran.py:363-415).  kern_str 'rbf' or 'rbf-student'; kern_attr
+    (this build's addition): a dict of kernel attributes set before the weights are computed."""
 
     def __init__(self, dim_in, dim_out, kern_par, kern_str='rbf', point_str='ut', point_par=None, estimate_par=False,
-                 nu=3.0):
+                 nu=3.0, kern_attr=None):
         super().__init__(dim_in, dim_out, kern_par, 'tp', kern_str, point_str, point_par, estimate_par, nu=nu)
+        self._set_kernel_attributes(kern_attr)
         self.wm, self.Wc, self.Wcc = self.weights(kern_par)
 
     def _tp(self):

@@ -40,7 +40,9 @@ struct WgtArgs {
     int32_t tiled;      // 1: the products go through LDS tiles (gemm_tiled) although K and its inverse live in global memory
     int32_t var_mode;   // 1: BayesSardModel.exp_model_variance / integral_variance semantics (bq/bqmod.py:995-1050): always
                         // the general formulas, no jitter on V' iK V; weights are still written but are not the reference's
-    double jitter;
+    int32_t given;      // 1: q, R, Q hold the caller's kernel expectations and kbar its E[k(x, y)] (ssmq_weights_gp_given): the
+                        // Gaussian closed forms are skipped, everything from the inverse onwards is the same code
+    double jitter, kbar;
     const double *xi;       // [D][N]
     const double *par;      // [P][1+D]
     const int32_t *mulind;  // [D][NB]
@@ -849,8 +851,8 @@ __device__ void weights_body(const WgtArgs &a, const WgtOut &o, int p, double *l
     }
     cq = 1.0 / sqrt(cq);   // det(Lam^-1 + I) ** -0.5
     cQ = 1.0 / sqrt(cQ);   // det(2 Lam^-1 + I) ** -0.5
-    const double kbar = alpha * alpha * (1.0 / sqrt(ck));
-    if (front) {
+    const double kbar = a.given ? a.kbar : alpha * alpha * (1.0 / sqrt(ck));
+    if (front && !a.given) {
     for (int n = tid; n < N; n += kWgtBlock) {
         double s = 0.0;
         for (int d = 0; d < D; ++d) {
@@ -1231,9 +1233,14 @@ static int launch_weights(WgtArgs &a, hipStream_t s) {
     return rc;
 }
 
+struct WgtGiven {            // kernel expectations computed elsewhere (host arrays; P = 1, NB = 0)
+    const double *q, *R, *Q;
+    double kbar;
+};
+
 static int weights_impl(int var_mode, int D, int N, const double *xi, const double *par, int P, double jitter,
                         const int32_t *mulind, int NB, double *wm, double *Wc, double *Wcc, double *iK, double *q, double *Q, double *R,
-                        double *model_var, double *integral_var, int32_t *status) {
+                        double *model_var, double *integral_var, int32_t *status, const WgtGiven *given = nullptr) {
     if (D < 1 || D > SSMQ_MAX_DIM || N < 1 || N > SSMQ_MAX_PTS || P < 1 || !xi || !par || NB < 0 || NB > N ||
         (NB > 0 && !mulind)) {
         set_error("weights: bad argument");
@@ -1293,6 +1300,13 @@ static int weights_impl(int var_mode, int D, int N, const double *xi, const doub
     a.R = dR.d(); a.mv = dmv.d(); a.iv = div.d(); a.status = (int32_t *)dst.p; a.work = dwork.d();
     a.work_stride = work_stride;
     a.lpack = npk ? dlp.d() : nullptr;
+    if (given) {
+        a.given = 1;
+        a.kbar = given->kbar;
+        SSMQ_HIP(hipMemcpyAsync(dq.p, given->q, sizeof(double) * N, hipMemcpyHostToDevice, s));
+        SSMQ_HIP(hipMemcpyAsync(dR.p, given->R, sizeof(double) * D * N, hipMemcpyHostToDevice, s));
+        SSMQ_HIP(hipMemcpyAsync(dQ.p, given->Q, sizeof(double) * nn, hipMemcpyHostToDevice, s));
+    }
     if ((rc = launch_weights(a, s))) return rc;
 #define SSMQ_D2H(host, dev, count) \
     if (host) SSMQ_HIP(hipMemcpyAsync(host, dev.p, sizeof(*host) * (count), hipMemcpyDeviceToHost, s));
@@ -1757,6 +1771,25 @@ extern "C" int ssmq_weights_gp(int D, int N, const double *xi, const double *par
                                double *integral_var, int32_t *status) {
     return ssmq::weights_impl(0, D, N, xi, par, P, jitter, nullptr, 0, wm, Wc, Wcc, iK, q, Q, R, model_var, integral_var,
                               status);
+}
+
+// GP weights from kernel expectations the caller supplies (the Monte-Carlo ones of the 'rbf-student' kernel,
+// ssmq_student_mc.hip): iK as in ssmq_weights_gp, then the same kernel forms wm = q iK, Wc = sym(iK Q iK), Wcc = R iK,
+// model_var = alpha^2 (1 - tr(Q iK)) and integral_var = kbar - q' iK q with the given q, R, Q, kbar in place of the closed forms.
+extern "C" int ssmq_weights_gp_given(int D, int N, const double *xi, const double *par, double jitter, const double *q,
+                                     const double *R, const double *Q, double kbar, double *wm, double *Wc, double *Wcc,
+                                     double *iK, double *model_var, double *integral_var, int32_t *status) {
+    if (D < 1 || D > 16 || N < 1 || N > 128) {
+        ssmq::set_error("ssmq_weights_gp_given: supported are D <= 16 and N <= 128");
+        return SSMQ_E_UNSUPPORTED;
+    }
+    if (!q || !R || !Q) {
+        ssmq::set_error("ssmq_weights_gp_given: null expectations");
+        return SSMQ_E_ARG;
+    }
+    const ssmq::WgtGiven g{q, R, Q, kbar};
+    return ssmq::weights_impl(0, D, N, xi, par, 1, jitter, nullptr, 0, wm, Wc, Wcc, iK, nullptr, nullptr, nullptr, model_var,
+                              integral_var, status, &g);
 }
 
 // The Student-t process model integrates with the SAME weights as the GP model (StudentTProcessModel inherits

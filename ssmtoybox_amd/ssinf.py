@@ -481,19 +481,28 @@ class FullySymmetricStudent(StudentianInference):
 
 
 class StudentProcessStudent(StudentianInference):
-    """Student-t process quadrature Student filter (ssinf.py:793-857).  The reference builds its weights with the
-    Monte-Carlo 'rbf-student' kernel (RNG-dependent, bq/bqkern.py:457-536), which is out of scope here: construct it with
-    the plain RBF kernel and assign the Monte-Carlo weights (tf.wm / tf.Wc / tf.Wcc / tf.model.model_var / tf.model.iK)
-    as data, exactly as research/tpq/tpq_ungm.py:109-124 does."""
+    """Student-t process quadrature Student filter, the TPQSF (ssinf.py:793-857).  kernel='rbf' (the default) builds both
+    transforms with the Gaussian-expectation RBF kernel, as this class always has; kernel='rbf-student' builds the
+    reference's filter: the weights of both transforms come from the 'rbf-student' kernel, the RBF kernel with Monte-Carlo
+    Student-t expectations (bq/bqkern.py:457-536), computed on the device.  mc: a dict of kernel attributes (`num_samples`,
+    `seed`, `dof`) set on both transforms' kernels before their weights are computed; without it the kernels have the
+    constructor's defaults, as in the reference (dof 4.0, 2e6 samples; seed 0).  The same seed gives the same filter, bit
+    for bit."""
 
-    def __init__(self, dyn, obs, kern_par_dyn, kern_par_obs, point_par=None, dof=4.0, fixed_dof=True, dof_tp=4.0):
+    def __init__(self, dyn, obs, kern_par_dyn, kern_par_obs, point_par=None, dof=4.0, fixed_dof=True, dof_tp=4.0,
+                 kernel='rbf', mc=None):
         assert kern_par_dyn.shape[1] == dyn.dim_in + 1 and kern_par_obs.shape[1] == obs.dim_in + 1
+        if kernel not in ('rbf', 'rbf-student'):
+            raise ValueError("kernel must be 'rbf' or 'rbf-student', got {!r}".format(kernel))
+        if mc and kernel != 'rbf-student':
+            raise ValueError("mc sets attributes of the 'rbf-student' kernel; the 'rbf' kernel has none")
         point_par = {} if point_par is None else point_par
         pp_dyn, pp_obs = dict(point_par), dict(point_par)
         pp_dyn.update({'dof': dyn.noise_rv.dof})
         pp_obs.update({'dof': obs.noise_rv.dof})
-        t_dyn = StudentTProcessTransform(dyn.dim_in, 1, kern_par_dyn, 'rbf', 'fs', pp_dyn, nu=dof_tp)
-        t_obs = StudentTProcessTransform(obs.dim_in, 1, kern_par_obs, 'rbf', 'fs', pp_obs, nu=dof_tp)
+        mc = dict(mc) if mc else None
+        t_dyn = StudentTProcessTransform(dyn.dim_in, 1, kern_par_dyn, kernel, 'fs', pp_dyn, nu=dof_tp, kern_attr=mc)
+        t_obs = StudentTProcessTransform(obs.dim_in, 1, kern_par_obs, kernel, 'fs', pp_obs, nu=dof_tp, kern_attr=mc)
         super().__init__(dyn, obs, t_dyn, t_obs, dof, fixed_dof)
 
 
