@@ -1,6 +1,7 @@
 // Host-side internals of libssmq shared between translation units.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <initializer_list>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -114,6 +115,15 @@ StagingArena &stage_of_ctx();
         hipError_t e__ = (call);                              \
         if (e__ != hipSuccess) return ssmq::hip_fail(e__, #call); \
     } while (0)
+
+// Raises the dynamic-LDS limit of `kernels` to `bytes` once per device binding of the calling thread; `seen` is the call
+// site's `static thread_local unsigned`, left as it is on failure so that the next call tries again.
+inline int set_max_dynamic_lds(unsigned &seen, std::initializer_list<const void *> kernels, size_t bytes) {
+    if (seen == device_epoch()) return SSMQ_OK;
+    for (const void *k : kernels) SSMQ_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    seen = device_epoch();
+    return SSMQ_OK;
+}
 
 // Device arena + pinned staging blocks of the host-buffer entry points that are called in tight loops with small batches
 // (ssmq_apply_batch: the drop-in apply(); ssmq_gp_theta_step), grow-only, dropped when the device changes.  The calls are

@@ -12,7 +12,7 @@
 // moment transform of the dynamics (bq/bqmtran.py:60-109,158-223), + G Q G', the same for the measurement model, + R, the Kalman
 // update (ssinf.py:321-323) and log N(y | y_mean, P_y) (ssinf.py:1153-1198) - with the shapes as template constants, so that
 // every loop unrolls and every array is registers.  The operations and their ORDER are those of the kernels this replaces
-// (weights_body, chol_block, chol_inverse, gemm in ssmq_weights.hip; apply_wave_body in ssmq_apply_wide.hip;
+// (weights_body in ssmq_weights.hip, chol_block, chol_inverse, gemm in ssmq_blockla.h; apply_wave_body in ssmq_apply_wide.hip;
 // kalman_update_item, gauss_logpdf_item in ssmq_update.h), so the two routes agree to rounding (tests compare them and both
 // with the reference's vectors); SSMQ_NO_THETA_ITEM=1 keeps the two-launch route.
 #include <cstdlib>

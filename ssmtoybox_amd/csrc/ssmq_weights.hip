@@ -24,15 +24,11 @@
 #include <algorithm>
 #include <cstring>
 #include <vector>
-#include "ssmq_host.h"
+#include "ssmq_weights_host.h"
 #include "ssmq_wide.h"
-#include "ssmq_bfgs.h"
+#include "ssmq_blockla.h"
 
 namespace ssmq {
-
-// workgroup size: 256 threads per parameter row, 1024 for large point sets (N > 64: one row keeps a whole CU busy with
-// L2-latency-bound loops, so it takes all the waves the CU can give); device code strides by the actual block size
-#define kWgtBlock ((int)blockDim.x)
 
 struct WgtArgs {
     int32_t D, N, P, NB, bs, use_lds;
@@ -53,8 +49,6 @@ struct WgtArgs {
     int64_t work_stride;    // doubles
     double *lpack;          // stages 1 / 2: packed Cholesky factors, N (N + 1) / 2 doubles per parameter row
 };
-
-__device__ __forceinline__ void bsync() { __syncthreads(); }
 
 // offsets (doubles) of the blocks of one parameter row's workspace; the launcher of the large-N route needs M1, M2 and T4 too
 struct WgtCarve {
@@ -82,140 +76,6 @@ struct WgtCarve {
         end = w;
     }
 };
-
-// C (M x N, ldc) = op(A) op(B); op(A) is M x K, op(B) is K x N.  Block-cooperative; ends with a barrier.
-__device__ void gemm(double *C, int ldc, const double *A, int lda, bool ta, const double *B, int ldb, bool tb, int M,
-                     int N, int K) {
-    for (int idx = threadIdx.x; idx < M * N; idx += kWgtBlock) {
-        const int i = idx / N, j = idx % N;
-        double s = 0.0;
-        for (int k = 0; k < K; ++k) {
-            const double a = ta ? A[k * lda + i] : A[i * lda + k];
-            const double b = tb ? B[j * ldb + k] : B[k * ldb + j];
-            s += a * b;
-        }
-        C[i * ldc + j] = s;
-    }
-    bsync();
-}
-
-// In-place right-looking Cholesky (lower) of the n x n matrix A; the strict upper triangle is left untouched.
-// Returns false (to every thread) at the first non-positive pivot.
-__device__ bool chol_block(double *A, int n, int *flag) {
-    if (threadIdx.x == 0) *flag = 1;
-    bsync();
-    for (int k = 0; k < n; ++k) {
-        if (threadIdx.x == 0) {
-            const double p = A[k * n + k];
-            if (!(p > 0.0)) *flag = 0;
-            A[k * n + k] = sqrt(p);
-        }
-        bsync();
-        if (*flag == 0) return false;
-        const double r = 1.0 / A[k * n + k];
-        for (int i = k + 1 + threadIdx.x; i < n; i += kWgtBlock) A[i * n + k] *= r;
-        bsync();
-        const int m = n - k - 1;
-        for (int idx = threadIdx.x; idx < m * m; idx += kWgtBlock) {
-            const int i = k + 1 + idx / m, j = k + 1 + idx % m;
-            if (j <= i) A[i * n + j] -= A[i * n + k] * A[j * n + k];
-        }
-        bsync();
-    }
-    return true;
-}
-
-// X = (L L')^-1 for the lower factor L (n x n): each thread owns columns of X; forward then backward substitution.
-__device__ void chol_inverse(const double *L, double *X, int n) {
-    for (int c = threadIdx.x; c < n; c += kWgtBlock) {
-        for (int i = 0; i < n; ++i) {
-            double s = (i == c) ? 1.0 : 0.0;
-            for (int k = c; k < i; ++k) s -= L[i * n + k] * X[k * n + c];   // X[k][c] = 0 for k < c
-            X[i * n + c] = (i < c) ? 0.0 : s / L[i * n + i];
-        }
-        for (int i = n - 1; i >= 0; --i) {
-            double s = X[i * n + c];
-            for (int k = i + 1; k < n; ++k) s -= L[k * n + i] * X[k * n + c];
-            X[i * n + c] = s / L[i * n + i];
-        }
-    }
-    bsync();
-}
-
-// X = A^-1 for a general n x n matrix by LU with partial pivoting (numpy.linalg.solve(V, I), bq/bqmod.py:954).
-// A is destroyed.  Single-thread pivot search, block-parallel elimination; n is small (<= N).
-__device__ bool lu_inverse(double *A, double *X, int n, int *piv, int *flag) {
-    for (int idx = threadIdx.x; idx < n * n; idx += kWgtBlock) X[idx] = (idx / n == idx % n) ? 1.0 : 0.0;
-    if (threadIdx.x == 0) *flag = 1;
-    bsync();
-    for (int k = 0; k < n; ++k) {
-        if (threadIdx.x == 0) {
-            int p = k;
-            double best = fabs(A[k * n + k]);
-            for (int i = k + 1; i < n; ++i)
-                if (fabs(A[i * n + k]) > best) { best = fabs(A[i * n + k]); p = i; }
-            *piv = p;
-            if (best == 0.0) *flag = 0;
-        }
-        bsync();
-        if (*flag == 0) return false;
-        const int p = *piv;
-        if (p != k) {
-            for (int j = threadIdx.x; j < n; j += kWgtBlock) {
-                double t = A[k * n + j]; A[k * n + j] = A[p * n + j]; A[p * n + j] = t;
-                t = X[k * n + j]; X[k * n + j] = X[p * n + j]; X[p * n + j] = t;
-            }
-        }
-        bsync();
-        const double r = 1.0 / A[k * n + k];
-        for (int i = k + 1 + threadIdx.x; i < n; i += kWgtBlock) A[i * n + k] *= r;
-        bsync();
-        const int m = n - k - 1;
-        for (int idx = threadIdx.x; idx < m * n; idx += kWgtBlock) {
-            const int i = k + 1 + idx / n, j = idx % n;
-            const double l = A[i * n + k];
-            if (j > k) A[i * n + j] -= l * A[k * n + j];
-            X[i * n + j] -= l * X[k * n + j];
-        }
-        bsync();
-    }
-    // back substitution U X = Y, thread per column
-    for (int c = threadIdx.x; c < n; c += kWgtBlock) {
-        for (int i = n - 1; i >= 0; --i) {
-            double s = X[i * n + c];
-            for (int k = i + 1; k < n; ++k) s -= A[i * n + k] * X[k * n + c];
-            X[i * n + c] = s / A[i * n + i];
-        }
-    }
-    bsync();
-    return true;
-}
-
-// ---- large point sets (N > 64, 1024 threads) --------------------------------------------------------------------------
-#define SSMQ_PKL(i, j) ((i) * ((i) + 1) / 2 + (j))   // packed lower triangle, j <= i
-
-// Right-looking Cholesky of a packed lower triangle held in LDS (same subtraction order as chol_block: same factor).
-// Two barriers per column: every thread forms the pivot's reciprocal root itself, and the trailing update walks rows and
-// columns without an integer division per element.
-__device__ bool chol_packed_lds(double *Lp, int n, int *flag) {
-    if (threadIdx.x == 0) *flag = 1;
-    bsync();
-    for (int k = 0; k < n; ++k) {
-        const double p = Lp[SSMQ_PKL(k, k)];
-        if (!(p > 0.0)) return false;            // uniform: every thread reads the same pivot
-        const double lkk = sqrt(p), r = 1.0 / lkk;
-        bsync();                                 // everyone has read the pivot before it is overwritten
-        if (threadIdx.x == 0) Lp[SSMQ_PKL(k, k)] = lkk;
-        for (int i = k + 1 + threadIdx.x; i < n; i += kWgtBlock) Lp[SSMQ_PKL(i, k)] *= r;
-        bsync();
-        for (int i = k + 1 + (threadIdx.x >> 4); i < n; i += kWgtBlock >> 4) {
-            const double lik = Lp[SSMQ_PKL(i, k)];
-            for (int j = k + 1 + (threadIdx.x & 15); j <= i; j += 16) Lp[SSMQ_PKL(i, j)] -= lik * Lp[SSMQ_PKL(j, k)];
-        }
-        bsync();
-    }
-    return true;
-}
 
 // X = (L L')^-1 column by column - cho_solve(cho_factor(A), I): forward substitution L y = e_c, backward substitution
 // L' x = y.  Sixteen lanes (a DPP row) own a column and keep it IN REGISTERS (lane `part` holds rows part, part + 16, ...);
@@ -308,82 +168,6 @@ __global__ __launch_bounds__(kInvBlock) void k_weights_inverse(int n, const doub
             if (k < n) X[k * n + c] = x[q];
         }
     }
-}
-
-// C (M x N, ldc) = op(A) op(B) through LDS tiles: 128 x 128 outputs per pass, 4 x 4 per thread (1024 threads), K in
-// slabs of 16 whose loads are issued one slab ahead (registers) so that the L2 latency hides behind the arithmetic of
-// the current slab; k ascends inside every output's sum exactly as in gemm(), so the result is bit-identical to it.
-// tile: 2 * 16 * 132 doubles of LDS.
-constexpr int kTileMN = 128, kTileK = 16, kTilePitch = kTileMN + 4;
-__device__ void gemm_tiled(double *tile, double *C, int ldc, const double *A, int lda, bool ta, const double *B, int ldb,
-                           bool tb, int M, int N, int K) {
-    double *sA = tile, *sB = tile + kTileK * kTilePitch;     // sA[k][i], sB[k][j]
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;  // 32 x 32 threads, each 4 x 4 outputs
-    constexpr int kPer = kTileK * kTileMN / 1024;            // elements of either slab per thread (2)
-    for (int i0 = 0; i0 < M; i0 += kTileMN)
-        for (int j0 = 0; j0 < N; j0 += kTileMN) {
-            double acc[4][4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) acc[r][q] = 0.0;
-            double ra[kPer], rb[kPer];
-            auto fetch = [&](int k0) {
-#pragma unroll
-                for (int u = 0; u < kPer; ++u) {
-                    const int idx = threadIdx.x + u * kWgtBlock;
-                    int kk, ii;                  // coalesced along the contiguous direction of each operand
-                    if (ta) { kk = idx / kTileMN; ii = idx % kTileMN; } else { ii = idx / kTileK; kk = idx % kTileK; }
-                    const int gi = i0 + ii, gk = k0 + kk;
-                    ra[u] = (gi < M && gk < K) ? (ta ? A[gk * lda + gi] : A[gi * lda + gk]) : 0.0;
-                    int kb, jj;
-                    if (tb) { jj = idx / kTileK; kb = idx % kTileK; } else { kb = idx / kTileMN; jj = idx % kTileMN; }
-                    const int gj = j0 + jj, gkb = k0 + kb;
-                    rb[u] = (gj < N && gkb < K) ? (tb ? B[gj * ldb + gkb] : B[gkb * ldb + gj]) : 0.0;
-                }
-            };
-            auto park = [&]() {
-#pragma unroll
-                for (int u = 0; u < kPer; ++u) {
-                    const int idx = threadIdx.x + u * kWgtBlock;
-                    int kk, ii;
-                    if (ta) { kk = idx / kTileMN; ii = idx % kTileMN; } else { ii = idx / kTileK; kk = idx % kTileK; }
-                    sA[kk * kTilePitch + ii] = ra[u];
-                    int kb, jj;
-                    if (tb) { jj = idx / kTileK; kb = idx % kTileK; } else { kb = idx / kTileMN; jj = idx % kTileMN; }
-                    sB[kb * kTilePitch + jj] = rb[u];
-                }
-            };
-            fetch(0);
-            for (int k0 = 0; k0 < K; k0 += kTileK) {
-                bsync();                         // the previous slab has been consumed
-                park();
-                bsync();
-                if (k0 + kTileK < K) fetch(k0 + kTileK);
-#pragma unroll
-                for (int kk = 0; kk < kTileK; ++kk) {
-                    double av[4], bv[4];
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) av[r] = sA[kk * kTilePitch + ty * 4 + r];
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) bv[q] = sB[kk * kTilePitch + tx * 4 + q];
-                    if (k0 + kk < K) {
-#pragma unroll
-                        for (int r = 0; r < 4; ++r)
-#pragma unroll
-                            for (int q = 0; q < 4; ++q) acc[r][q] += av[r] * bv[q];
-                    }
-                }
-            }
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int gi = i0 + ty * 4 + r, gj = j0 + tx * 4 + q;
-                    if (gi < M && gj < N) C[gi * ldc + gj] = acc[r][q];
-                }
-        }
-    bsync();
 }
 
 // ---- point sets beyond the CU-resident route (N > 201; the degree-7 rule at D = 10 has 1 181 points) ---------------------
@@ -722,42 +506,6 @@ __device__ double block_sum(double v, double *red) {
     return s;
 }
 
-__device__ double ipow(double x, int k) {
-    double r = 1.0;
-    for (int i = 0; i < k; ++i) r *= x;
-    return r;
-}
-
-// Entry (n, q) of the Vandermonde matrix (utils.py:478-502) and of E[k(x, x_n) p_q(x)], the closed form of
-// bq/bqmod.py:733-797; its `ell` is sqrt_inv_lam ** -2 = ell^2, reproduced as written there.  sil[d] = 1 / ell_d.
-__device__ void bs_basis_entry(int D, int N, int NB, int n, int qb, const double *__restrict__ xi,
-                               const int32_t *__restrict__ mulind, const double *sil, double &vand, double &kxpx) {
-    double v = 1.0, kprod = 1.0;
-    for (int d = 0; d < D; ++d) {
-        const int al = mulind[d * NB + qb];
-        const double x = xi[d * N + n];
-        v *= ipow(x, al);
-        const double sl = sil[d];
-        const double el = 1.0 / (sl * sl);
-        const double e1 = 1.0 + el * el;
-        const double ea = el * pow(e1, -(1.0 + al) / 2.0) * exp(-(x * x) / (2.0 * e1));
-        double eb = 0.0;
-        const double xs = x / sqrt(e1);
-        for (int m = 0; m <= al / 2; ++m) {
-            // al! / (2^m m! (al - 2m)!)
-            double num = 1.0, den = 1.0;
-            for (int t = 2; t <= al; ++t) num *= t;
-            for (int t = 0; t < m; ++t) den *= 2.0;
-            for (int t = 2; t <= m; ++t) den *= t;
-            for (int t = 2; t <= al - 2 * m; ++t) den *= t;
-            eb += (num / den) * (ipow(el, 2 * m) * ipow(xs, al - 2 * m));
-        }
-        kprod *= ea * eb;
-    }
-    vand = v;
-    kxpx = kprod;
-}
-
 // where one parameter row's workspace and results live: the global arrays of WgtArgs at row p (k_weights), or the
 // workgroup's LDS (k_theta_weights, which only keeps the packed constants of the transform kernel)
 struct WgtOut {
@@ -784,16 +532,8 @@ __device__ void weights_body(const WgtArgs &a, const WgtOut &o, int p, double *l
     double *oq = o.q, *oQ = o.Q, *oR = o.R, *oiK = o.iK, *owm = o.wm, *oWc = o.Wc, *oWcc = o.Wcc;
 
     if (tid < D) s_sil[tid] = 1.0 / par[1 + tid];   // par[1:] ** -1   (bq/bqkern.py:454)
-    bsync();
     // ---- kernel matrix, scaling=False (alpha = 1): exp(2 log(1) - maha / 2) ------------------------------------
-    for (int idx = tid; idx < D * N; idx += kWgtBlock) zs[idx] = s_sil[idx / N] * a.xi[idx];
-    bsync();
-    for (int n = tid; n < N; n += kWgtBlock) {
-        double s = 0.0;
-        for (int d = 0; d < D; ++d) s += zs[d * N + n] * zs[d * N + n];
-        nrm[n] = s;
-    }
-    bsync();
+    rbf_stage(s_sil, a.xi, zs, nrm, D, N);
     bool pd = true;
     // stages 3 / 4 (point sets beyond the CU-resident route): the factor, the inverse (in gX, transposed - symmetrised below) and
     // the two N x N x N products come from the k_wb_* launches; stage 3 runs up to the products, stage 4 from there
@@ -803,10 +543,7 @@ __device__ void weights_body(const WgtArgs &a, const WgtOut &o, int p, double *l
     for (int idx = tid; idx < N * N; idx += kWgtBlock) {
         const int i = idx / N, j = idx % N;
         if (large && j > i) continue;
-        double dot = 0.0;
-        for (int d = 0; d < D; ++d) dot += zs[d * N + i] * zs[d * N + j];
-        const double mh = (nrm[i] + nrm[j]) - 2.0 * dot;
-        const double v = exp(0.0 - 0.5 * mh) + (i == j ? a.jitter : 0.0);
+        const double v = rbf_entry(0.0, zs, nrm, N, D, i, j) + (i == j ? a.jitter : 0.0);
         if (large) lds[SSMQ_PKL(i, j)] = v;
         else A[idx] = v;
     }
@@ -1077,8 +814,7 @@ static double dfact(int n) {  // (-1)!! = 0!! = 1  
     return r;
 }
 
-static void poly_moments(int D, int NB, const int32_t *mi, std::vector<double> &px, std::vector<double> &xpx,
-                         std::vector<double> &pxpx) {
+void poly_moments(int D, int NB, const int32_t *mi, std::vector<double> &px, std::vector<double> &xpx, std::vector<double> &pxpx) {
     px.assign(NB, 0.0);
     xpx.assign((size_t)D * NB, 0.0);
     pxpx.assign((size_t)NB * NB, 0.0);
@@ -1113,15 +849,6 @@ static void poly_moments(int D, int NB, const int32_t *mi, std::vector<double> &
     }
 }
 
-namespace {
-struct DBuf {
-    void *p = nullptr;
-    ~DBuf() { if (p) hipFree(p); }
-    int alloc(size_t bytes) { return hip_fail(hipMalloc(&p, bytes ? bytes : 8), "hipMalloc"); }
-    double *d() { return (double *)p; }
-};
-}  // namespace
-
 // Launches the weights computation for a.P parameter rows.  N <= 64: one launch, dense K and inverse resident in LDS
 // (256 threads).  Larger point sets: packed factor in LDS (stage 1, 1024 threads) | inverse by column blocks on
 // ceil(N / 16) workgroups per row | stage 2 (1024 threads, LDS tiles), while the packed triangle fits the CU's LDS
@@ -1142,22 +869,15 @@ static int launch_weights(WgtArgs &a, hipStream_t s) {
         hipLaunchKernelGGL(k_weights<256>, dim3(a.P), dim3(threads), sizeof(double) * 2 * nn, s, a);
         return hip_fail(hipGetLastError(), "k_weights");
     }
-    static thread_local unsigned attr_epoch = 0;   // per-device attribute: set again after a device change
-    if (attr_epoch != ssmq::device_epoch()) {
-        SSMQ_HIP(hipFuncSetAttribute((const void *)k_weights<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_cap));
-        SSMQ_HIP(hipFuncSetAttribute((const void *)k_weights_inverse, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_cap));
-        attr_epoch = ssmq::device_epoch();
-    }
+    static thread_local unsigned attr_epoch = 0;
+    int rc = set_max_dynamic_lds(attr_epoch, {(const void *)k_weights<1024>, (const void *)k_weights_inverse}, lds_cap);
+    if (rc) return rc;
     const bool staged = packed <= lds_cap && N <= kInvLanes * kInvSlots && !ssmq::sw("SSMQ_WEIGHTS_NO_LDS");
     const bool unisolvent = a.NB == N && !a.var_mode;      // N x N LU inverse in one workgroup: not a large-N case in practice
     if (!staged && !unisolvent && !ssmq::sw("SSMQ_WEIGHTS_ONE_WG")) {
         // factor, inverse and the two N^3 products on many workgroups (k_wb_*), the rest in k_weights<1024> stages 3 and 4
         static thread_local unsigned wb_epoch = 0;
-        if (wb_epoch != ssmq::device_epoch()) {
-            SSMQ_HIP(hipFuncSetAttribute((const void *)k_wb_chol_panel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kCbLds));
-            SSMQ_HIP(hipFuncSetAttribute((const void *)k_wb_chol_update, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kCbLds));
-            wb_epoch = ssmq::device_epoch();
-        }
+        if ((rc = set_max_dynamic_lds(wb_epoch, {(const void *)k_wb_chol_panel, (const void *)k_wb_chol_update}, kCbLds))) return rc;
         a.use_lds = 0;
         a.tiled = 1;
         const int P = a.P, nblk = (N + kCb - 1) / kCb;
@@ -1176,8 +896,7 @@ static int launch_weights(WgtArgs &a, hipStream_t s) {
                 hipLaunchKernelGGL(k_wb_chol_update, dim3(m * (m + 1) / 2, P), dim3(256), kCbLds, s, N, kb, a.work, a.work_stride,
                                    a.status);
         }
-        int rc = hip_fail(hipGetLastError(), "k_wb_chol");
-        if (rc) return rc;
+        if ((rc = hip_fail(hipGetLastError(), "k_wb_chol"))) return rc;
         const int slots = (N + 63) / 64;
 #define SSMQ_WB_INV(S, CPW) \
         hipLaunchKernelGGL((k_wb_inverse<S, CPW>), dim3((N + 4 * CPW - 1) / (4 * CPW), P), dim3(256), 0, s, N, a.work, a.work_stride, \
@@ -1219,7 +938,7 @@ static int launch_weights(WgtArgs &a, hipStream_t s) {
     a.use_lds = 2;
     a.stage = 1;
     hipLaunchKernelGGL(k_weights<1024>, dim3(a.P), dim3(1024), packed, s, a);
-    int rc = hip_fail(hipGetLastError(), "k_weights(factor)");
+    rc = hip_fail(hipGetLastError(), "k_weights(factor)");
     if (!rc) {
         hipLaunchKernelGGL(k_weights_inverse, dim3((N + kInvCols - 1) / kInvCols, a.P), dim3(kInvBlock), packed, s, N, a.lpack,
                            a.status, a.work, a.work_stride);
@@ -1478,293 +1197,13 @@ int gp_theta_weights_pair(const int D[2], const int E[2], const int N[2], const 
         if (N[i] > 8 || ssmq::sw("SSMQ_WEIGHTS_WIDE_BLOCK")) threads = 256;     // as launch_weights
     }
     static thread_local unsigned attr_epoch = 0;
-    if (lds > 48 * 1024 && attr_epoch != ssmq::device_epoch()) {
-        SSMQ_HIP(hipFuncSetAttribute((const void *)k_theta_weights, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));
-        attr_epoch = ssmq::device_epoch();
-    }
+    int rc;
+    if (lds > 48 * 1024 && (rc = set_max_dynamic_lds(attr_epoch, {(const void *)k_theta_weights}, 160 * 1024 - 1024))) return rc;
     hipLaunchKernelGGL(k_theta_weights, dim3(P, 2), dim3(threads), lds, s, t);
     return hip_fail(hipGetLastError(), "k_theta_weights");
 }
 
-// ---- the kernel-level methods of the reference as entry points of their own ---------------------------------------------
-// RBFGauss.eval (bq/bqkern.py:329-343 with utils.maha, utils.py:385-409), Kernel.eval_chol / eval_inv_dot / _cho_inv
-// (:38-64, 96-142) and RBFGauss.exp_x_kxkx for two different parameter rows (:366-415).  The weights kernel above needs
-// none of them separately (it builds K, its inverse and Q in one go); they exist so that callers of those methods - the
-// reference's tests, hyper-parameter studies - get device results too.
-
-// K[p][i][j] = exp(2 log(alpha) - maha(z1_i, z2_j) / 2), z = Lam^-1/2 x, maha as |a|^2 + |b|^2 - 2 a.b; diag: only
-// i == j through the difference form of the reference's `diag=True` branch.  One thread per entry.
-__global__ void k_rbf_eval(int D, int N1, int N2, const double *__restrict__ x1, const double *__restrict__ x2,
-                           const double *__restrict__ par, int scaling, int diag, double *__restrict__ K) {
-    const int p = blockIdx.y;
-    const double *pr = par + (int64_t)p * (1 + D);
-    const double la = scaling ? 2.0 * log(pr[0]) : 2.0 * log(1.0);
-    const int64_t total = diag ? N1 : (int64_t)N1 * N2;
-    for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
-        const int i = diag ? (int)idx : (int)(idx / N2), j = diag ? (int)idx : (int)(idx % N2);
-        double na = 0.0, nb = 0.0, dot = 0.0, dd = 0.0;
-        for (int d = 0; d < D; ++d) {
-            const double sil = 1.0 / pr[1 + d];
-            const double a = sil * x1[d * N1 + i], b = sil * x2[d * N2 + j];
-            na += a * a;
-            nb += b * b;
-            dot += a * b;
-            dd += (a - b) * (a - b);
-        }
-        const double mh = diag ? dd : (na + nb) - 2.0 * dot;
-        K[(int64_t)p * total + idx] = exp(la - 0.5 * mh);
-    }
-}
-
-// X = (L L')^-1 Bm for the lower factor L (n x n) and a square right-hand side: thread per column, forward then backward
-// substitution (scipy.linalg.cho_solve)
-__device__ void chol_solve(const double *L, const double *Bm, double *X, int n) {
-    for (int c = threadIdx.x; c < n; c += kWgtBlock) {
-        for (int i = 0; i < n; ++i) {
-            double s = Bm[i * n + c];
-            for (int k = 0; k < i; ++k) s -= L[i * n + k] * X[k * n + c];
-            X[i * n + c] = s / L[i * n + i];
-        }
-        for (int i = n - 1; i >= 0; --i) {
-            double s = X[i * n + c];
-            for (int k = i + 1; k < n; ++k) s -= L[k * n + i] * X[k * n + c];
-            X[i * n + c] = s / L[i * n + i];
-        }
-    }
-    bsync();
-}
-
-// A <- K + jitter I (K as k_rbf_eval, scaling optional), factor, optional inverse / solve: one workgroup per parameter
-// row, global workspace (init-time sizes).  chol: lower factor with zeros above the diagonal (numpy.linalg.cholesky); iK
-// = sym(A^-1) (rhs null) or sym(A^-1 rhs) for a square rhs - the reference symmetrises whatever it solved for.
-template <int BLOCK>
-__global__ __launch_bounds__(BLOCK) void k_rbf_factor(int D, int N, const double *__restrict__ x, const double *__restrict__ par,
-                                                       int scaling, double jitter, double *__restrict__ work, double *chol,
-                                                       double *iK, const double *__restrict__ rhs, int32_t *status) {
-    __shared__ int s_flag;
-    const int p = blockIdx.x, tid = threadIdx.x;
-    const double *pr = par + (int64_t)p * (1 + D);
-    const double la = scaling ? 2.0 * log(pr[0]) : 2.0 * log(1.0);
-    double *A = work + (int64_t)p * 2 * N * N, *X = A + (int64_t)N * N;
-    for (int idx = tid; idx < N * N; idx += kWgtBlock) {
-        const int i = idx / N, j = idx % N;
-        double na = 0.0, nb = 0.0, dot = 0.0;
-        for (int d = 0; d < D; ++d) {
-            const double sil = 1.0 / pr[1 + d];
-            const double a = sil * x[d * N + i], b = sil * x[d * N + j];
-            na += a * a;
-            nb += b * b;
-            dot += a * b;
-        }
-        A[idx] = exp(la - 0.5 * ((na + nb) - 2.0 * dot)) + (i == j ? jitter : 0.0);
-    }
-    bsync();
-    const bool pd = chol_block(A, N, &s_flag);
-    if (tid == 0) status[p] = pd ? 0 : 1;
-    const double nan = __builtin_nan("");
-    if (chol)
-        for (int idx = tid; idx < N * N; idx += kWgtBlock) {
-            const int i = idx / N, j = idx % N;
-            chol[(int64_t)p * N * N + idx] = pd ? (j <= i ? A[idx] : 0.0) : nan;
-        }
-    if (!iK) return;
-    if (!pd) {
-        for (int idx = tid; idx < N * N; idx += kWgtBlock) iK[(int64_t)p * N * N + idx] = nan;
-        return;
-    }
-    if (rhs) chol_solve(A, rhs, X, N);
-    else chol_inverse(A, X, N);
-    for (int idx = tid; idx < N * N; idx += kWgtBlock) {
-        const int i = idx / N, j = idx % N;
-        iK[(int64_t)p * N * N + idx] = 0.5 * (X[i * N + j] + X[j * N + i]);
-    }
-}
-
-// Q[i][j] = det(R)^-1/2 exp(xi_i + xi'_j + maha(Lam0^-1 x_i, -Lam1^-1 x_j; R^-1) / 2), R = Lam0^-1 + Lam1^-1 + I,
-// xi = 2 log(alpha0) - |Lam0^-1/2 x_i|^2 / 2, xi' likewise with row 1 (all matrices diagonal)
-__global__ void k_rbf_kxkx(int D, int N, const double *__restrict__ x, const double *__restrict__ par0,
-                           const double *__restrict__ par1, int scaling, double *__restrict__ Q) {
-    const double la0 = scaling ? 2.0 * log(par0[0]) : 2.0 * log(1.0), la1 = scaling ? 2.0 * log(par1[0]) : 2.0 * log(1.0);
-    double det = 1.0;
-    for (int d = 0; d < D; ++d) {
-        const double s0 = 1.0 / par0[1 + d], s1 = 1.0 / par1[1 + d];
-        det *= (s0 * s0 + s1 * s1) + 1.0;
-    }
-    const double c = 1.0 / sqrt(det);
-    for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < N * N; idx += gridDim.x * blockDim.x) {
-        const int i = idx / N, j = idx % N;
-        double n0 = 0.0, n1 = 0.0, m2i = 0.0, m2j = 0.0, mij = 0.0;
-        for (int d = 0; d < D; ++d) {
-            const double s0 = 1.0 / par0[1 + d], s1 = 1.0 / par1[1 + d];
-            const double il0 = s0 * s0, il1 = s1 * s1;
-            const double z0 = s0 * x[d * N + i], z1 = s1 * x[d * N + j];
-            n0 += z0 * z0;
-            n1 += z1 * z1;
-            const double v = 1.0 / ((il0 + il1) + 1.0);
-            const double yi = il0 * x[d * N + i], yj = -(il1 * x[d * N + j]);
-            m2i += (yi * v) * yi;
-            m2j += (yj * v) * yj;
-            mij += (yi * v) * yj;
-        }
-        const double mh = (m2i + m2j) - 2.0 * mij;
-        Q[idx] = c * exp(((la0 - 0.5 * n0) + (la1 - 0.5 * n1)) + 0.5 * mh);
-    }
-}
-
-static bool rbf_args_ok(int D, int N, const double *x, const double *par, int P) {
-    return D >= 1 && D <= SSMQ_MAX_DIM && N >= 1 && N <= SSMQ_MAX_PTS && P >= 1 && x && par;
-}
-
 }  // namespace ssmq
-
-extern "C" int ssmq_rbf_eval(int D, int N1, const double *x1, int N2, const double *x2, const double *par, int P,
-                             int scaling, int diag, double *K) {
-    using namespace ssmq;
-    if (!x2) { x2 = x1; N2 = N1; }
-    if (!rbf_args_ok(D, N1, x1, par, P) || N2 < 1 || N2 > SSMQ_MAX_PTS || !K || (diag && N1 != N2)) {
-        set_error("rbf_eval: bad argument");
-        return SSMQ_E_ARG;
-    }
-    int rc = ensure_device();
-    if (rc) return rc;
-    hipStream_t s = stream();
-    const size_t nout = (size_t)P * (diag ? (size_t)N1 : (size_t)N1 * N2);
-    DBuf d1, d2, dp, dk;
-    if ((rc = d1.alloc(sizeof(double) * D * N1)) || (rc = d2.alloc(sizeof(double) * D * N2)) ||
-        (rc = dp.alloc(sizeof(double) * P * (1 + D))) || (rc = dk.alloc(sizeof(double) * nout)))
-        return rc;
-    SSMQ_HIP(hipMemcpyAsync(d1.p, x1, sizeof(double) * D * N1, hipMemcpyHostToDevice, s));
-    SSMQ_HIP(hipMemcpyAsync(d2.p, x2, sizeof(double) * D * N2, hipMemcpyHostToDevice, s));
-    SSMQ_HIP(hipMemcpyAsync(dp.p, par, sizeof(double) * P * (1 + D), hipMemcpyHostToDevice, s));
-    const size_t per = nout / P;
-    hipLaunchKernelGGL(k_rbf_eval, dim3((unsigned)std::min<size_t>((per + 255) / 256, 4096), P), dim3(256), 0, s, D, N1, N2, d1.d(),
-                       d2.d(), dp.d(), scaling, diag, dk.d());
-    if ((rc = hip_fail(hipGetLastError(), "k_rbf_eval"))) return rc;
-    SSMQ_HIP(hipMemcpyAsync(K, dk.p, sizeof(double) * nout, hipMemcpyDeviceToHost, s));
-    SSMQ_HIP(hipStreamSynchronize(s));
-    return SSMQ_OK;
-}
-
-extern "C" int ssmq_rbf_factor(int D, int N, const double *x, const double *par, int P, int scaling, double jitter,
-                               const double *rhs, double *chol, double *iK, int32_t *status) {
-    using namespace ssmq;
-    if (!rbf_args_ok(D, N, x, par, P) || (!chol && !iK)) {
-        set_error("rbf_factor: bad argument");
-        return SSMQ_E_ARG;
-    }
-    int rc = ensure_device();
-    if (rc) return rc;
-    hipStream_t s = stream();
-    const size_t nn = (size_t)N * N;
-    DBuf dx, dp, dw, dc, di, dst, db;
-    if ((rc = db.alloc(sizeof(double) * (rhs ? nn : 1)))) return rc;
-    if (rhs) SSMQ_HIP(hipMemcpyAsync(db.p, rhs, sizeof(double) * nn, hipMemcpyHostToDevice, s));
-    if ((rc = dx.alloc(sizeof(double) * D * N)) || (rc = dp.alloc(sizeof(double) * P * (1 + D))) ||
-        (rc = dw.alloc(sizeof(double) * 2 * nn * P)) || (rc = dc.alloc(sizeof(double) * (chol ? nn * P : 1))) ||
-        (rc = di.alloc(sizeof(double) * (iK ? nn * P : 1))) || (rc = dst.alloc(sizeof(int32_t) * P)))
-        return rc;
-    SSMQ_HIP(hipMemcpyAsync(dx.p, x, sizeof(double) * D * N, hipMemcpyHostToDevice, s));
-    SSMQ_HIP(hipMemcpyAsync(dp.p, par, sizeof(double) * P * (1 + D), hipMemcpyHostToDevice, s));
-    if (N > 64)
-        hipLaunchKernelGGL(k_rbf_factor<1024>, dim3(P), dim3(1024), 0, s, D, N, dx.d(), dp.d(), scaling, jitter, dw.d(),
-                           chol ? dc.d() : nullptr, iK ? di.d() : nullptr, rhs ? db.d() : nullptr, (int32_t *)dst.p);
-    else
-        hipLaunchKernelGGL(k_rbf_factor<256>, dim3(P), dim3(256), 0, s, D, N, dx.d(), dp.d(), scaling, jitter, dw.d(),
-                           chol ? dc.d() : nullptr, iK ? di.d() : nullptr, rhs ? db.d() : nullptr, (int32_t *)dst.p);
-    if ((rc = hip_fail(hipGetLastError(), "k_rbf_factor"))) return rc;
-    if (chol) SSMQ_HIP(hipMemcpyAsync(chol, dc.p, sizeof(double) * nn * P, hipMemcpyDeviceToHost, s));
-    if (iK) SSMQ_HIP(hipMemcpyAsync(iK, di.p, sizeof(double) * nn * P, hipMemcpyDeviceToHost, s));
-    std::vector<int32_t> st(P);
-    SSMQ_HIP(hipMemcpyAsync(st.data(), dst.p, sizeof(int32_t) * P, hipMemcpyDeviceToHost, s));
-    SSMQ_HIP(hipStreamSynchronize(s));
-    int first = 0;
-    for (int i = 0; i < P; ++i) {
-        if (status) status[i] = st[i];
-        if (st[i] && !first) first = i + 1;
-    }
-    return first;
-}
-
-extern "C" int ssmq_rbf_exp_kxkx(int D, int N, const double *x, const double *par0, const double *par1, int scaling,
-                                 double *Q) {
-    using namespace ssmq;
-    if (!rbf_args_ok(D, N, x, par0, 1) || !par1 || !Q) {
-        set_error("rbf_exp_kxkx: bad argument");
-        return SSMQ_E_ARG;
-    }
-    int rc = ensure_device();
-    if (rc) return rc;
-    hipStream_t s = stream();
-    DBuf dx, dp, dq;
-    if ((rc = dx.alloc(sizeof(double) * D * N)) || (rc = dp.alloc(sizeof(double) * 2 * (1 + D))) ||
-        (rc = dq.alloc(sizeof(double) * (size_t)N * N)))
-        return rc;
-    SSMQ_HIP(hipMemcpyAsync(dx.p, x, sizeof(double) * D * N, hipMemcpyHostToDevice, s));
-    SSMQ_HIP(hipMemcpyAsync(dp.p, par0, sizeof(double) * (1 + D), hipMemcpyHostToDevice, s));
-    SSMQ_HIP(hipMemcpyAsync(dp.d() + 1 + D, par1, sizeof(double) * (1 + D), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_rbf_kxkx, dim3((unsigned)std::min<size_t>(((size_t)N * N + 255) / 256, 4096)), dim3(256), 0, s, D, N,
-                       dx.d(), dp.d(), dp.d() + 1 + D, scaling, dq.d());
-    if ((rc = hip_fail(hipGetLastError(), "k_rbf_kxkx"))) return rc;
-    SSMQ_HIP(hipMemcpyAsync(Q, dq.p, sizeof(double) * (size_t)N * N, hipMemcpyDeviceToHost, s));
-    SSMQ_HIP(hipStreamSynchronize(s));
-    return SSMQ_OK;
-}
-
-// BayesSardModel._exp_x_kxpx and utils.vandermonde for an arbitrary point set (the weights kernel forms both inline)
-__global__ void k_bs_moments(int D, int N, int NB, const double *__restrict__ x, const double *__restrict__ par,
-                             const int32_t *__restrict__ mulind, double *__restrict__ vand, double *__restrict__ kxpx) {
-    __shared__ double sil[SSMQ_MAX_DIM];
-    if ((int)threadIdx.x < D) sil[threadIdx.x] = 1.0 / par[1 + threadIdx.x];
-    __syncthreads();
-    for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < (int64_t)N * NB; idx += (int64_t)gridDim.x * blockDim.x) {
-        double v, k;
-        ssmq::bs_basis_entry(D, N, NB, (int)(idx / NB), (int)(idx % NB), x, mulind, sil, v, k);
-        if (vand) vand[idx] = v;
-        if (kxpx) kxpx[idx] = k;
-    }
-}
-
-extern "C" int ssmq_bs_moments(int D, int N, const double *x, const double *par, const int32_t *mulind, int NB, double *px,
-                               double *xpx, double *pxpx, double *kxpx, double *vand) {
-    using namespace ssmq;
-    if (D < 1 || D > SSMQ_MAX_DIM || NB < 1 || !mulind || N < 0 || ((kxpx || vand) && (!x || N < 1)) || (kxpx && !par)) {
-        set_error("bs_moments: bad argument");
-        return SSMQ_E_ARG;
-    }
-    for (int i = 0; i < D * NB; ++i)
-        if (mulind[i] < 0) {
-            set_error("bs_moments: negative multi-index");
-            return SSMQ_E_ARG;
-        }
-    if (px || xpx || pxpx) {     // integer arithmetic on the multi-indices: host code, as the point sets are
-        std::vector<double> a, b, c;
-        poly_moments(D, NB, mulind, a, b, c);
-        if (px) std::copy(a.begin(), a.end(), px);
-        if (xpx) std::copy(b.begin(), b.end(), xpx);
-        if (pxpx) std::copy(c.begin(), c.end(), pxpx);
-    }
-    if (!kxpx && !vand) return SSMQ_OK;
-    int rc = ensure_device();
-    if (rc) return rc;
-    hipStream_t s = stream();
-    const size_t nn = (size_t)N * NB;
-    DBuf dx, dp, dm, dk, dv;
-    const double one_par[1 + SSMQ_MAX_DIM] = {1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0};
-    if ((rc = dx.alloc(sizeof(double) * D * N)) || (rc = dp.alloc(sizeof(double) * (1 + D))) ||
-        (rc = dm.alloc(sizeof(int32_t) * D * NB)) || (kxpx && (rc = dk.alloc(sizeof(double) * nn))) ||
-        (vand && (rc = dv.alloc(sizeof(double) * nn))))
-        return rc;
-    SSMQ_HIP(hipMemcpyAsync(dx.p, x, sizeof(double) * D * N, hipMemcpyHostToDevice, s));
-    SSMQ_HIP(hipMemcpyAsync(dp.p, par ? par : one_par, sizeof(double) * (1 + D), hipMemcpyHostToDevice, s));
-    SSMQ_HIP(hipMemcpyAsync(dm.p, mulind, sizeof(int32_t) * D * NB, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_bs_moments, dim3((unsigned)std::min<size_t>((nn + 255) / 256, 4096)), dim3(256), 0, s, D, N, NB, dx.d(),
-                       dp.d(), (const int32_t *)dm.p, vand ? dv.d() : nullptr, kxpx ? dk.d() : nullptr);
-    if ((rc = hip_fail(hipGetLastError(), "k_bs_moments"))) return rc;
-    if (kxpx) SSMQ_HIP(hipMemcpyAsync(kxpx, dk.p, sizeof(double) * nn, hipMemcpyDeviceToHost, s));
-    if (vand) SSMQ_HIP(hipMemcpyAsync(vand, dv.p, sizeof(double) * nn, hipMemcpyDeviceToHost, s));
-    SSMQ_HIP(hipStreamSynchronize(s));
-    return SSMQ_OK;
-}
 
 extern "C" int ssmq_weights_gp(int D, int N, const double *xi, const double *par, int P, double jitter, double *wm,
                                double *Wc, double *Wcc, double *iK, double *q, double *Q, double *R, double *model_var,
@@ -1822,738 +1261,4 @@ extern "C" int ssmq_variances_bs(int D, int N, const double *xi, const double *p
     }
     return ssmq::weights_impl(1, D, N, xi, par, P, jitter, mulind, NB, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
                               nullptr, model_var, integral_var, status);
-}
-
-// ---- type-II maximum likelihood (ML-II) of the RBF kernel's parameters ----------------------------------------------------
-//
-//   GaussianProcessModel.neg_log_marginal_likelihood     bq/bqmod.py:537-596
-//   StudentTProcessModel.neg_log_marginal_likelihood     bq/bqmod.py:1191-1245
-//   RBFGauss.der_par                                     bq/bqkern.py:426-436
-//   Model.optimize (scipy.optimize.minimize, BFGS, jac)  bq/bqmod.py:250-285
-//
-// One workgroup per row b (a parameter point, or a whole fit).  At log-parameters [log alpha, log ell_1 .. log ell_D]:
-//   K = alpha^2 exp(-maha(Lam^-1/2 x) / 2) + jitter (the N x N jitter matrix), L = chol(K), X = K^-1, A = X Y  (Y: N x E)
-//   GP value  E sum log diag L + (sum Y o A + E N log 2 pi) / 2
-//   TP value  (nu + N) / 2 sum_e log(1 + y_e'a_e / (nu - 2)) + E (sum log diag L + const)
-//   gradient  g_p = 1/2 sum_ij W_ij dK_p(i, j),  W = E X - A diag(s) A',  s_e = 1 (GP) or (nu + N) / (nu + y_e'a_e - 2) (TP)
-// dK_p is der_par's: K WITHOUT the jitter, d/d alpha = 2 K / alpha (with respect to alpha itself, not log alpha - the
-// reference's quirk, kept: the first gradient entry is the true derivative divided by alpha) and d/d log ell_d =
-// (x_di - x_dj)^2 / ell_d^2 K.  The sum runs over the lower triangle once (W and dK are symmetric), so no N x N x P array is
-// formed.  N <= 64: K / its factor and X dense in LDS (chol_block, chol_inverse as k_weights); N <= 128: packed lower
-// triangles (chol_packed_lds and its packed twin below), 2 x 66 KiB at N = 128.  Both routes read the lower triangle of X,
-// which the two inverses form with the same arithmetic.
-// ML-II: one lane of the workgroup runs the row's BFGS state machine (ssmq_bfgs.h, analytic-gradient mode) in LDS, the
-// workgroup evaluates the objective at its pending point, until the state machine ends - one launch for all fits, no
-// grid-wide synchronisation.  A point where K is not positive definite is a value of +inf with a NaN gradient there (the
-// reference raises LinAlgError out of minimize): the line search backs off from it.
-
-namespace ssmq {
-
-constexpr int kMl2MaxN = 128, kMl2MaxE = 16, kMl2PM = SSMQ_MAX_DIM + 1, kMl2Block = 256;
-
-struct Ml2Args {
-    int32_t D, N, E, x_per_fit, optimise, maxiter;
-    int64_t B;
-    double gtol, nu, tp_const;          // nu = 0: GP
-    const double *x;                    // [D][N], or [B][D][N] (x_per_fit)
-    const double *y;                    // [B][N][E]
-    const double *jit;                  // [N][N]
-    const double *lp;                   // [B][P]: evaluation points / start points (log-parameters)
-    double *fun, *jac, *xout, *hess_inv;  // [B], [B][P], [B][P] (optimise), [B][P][P] (optimise)
-    int32_t *status, *nit, *nfev;       // [B]; nit / nfev: optimise only
-};
-
-// chol_inverse for a packed lower factor, into a packed lower triangle: column c's rows i >= c need only rows k >= c, so
-// the arithmetic is chol_inverse's for the lower triangle, bit for bit.
-__device__ void chol_inverse_packed(const double *Lp, double *Xp, int n) {
-    for (int c = threadIdx.x; c < n; c += kWgtBlock) {
-        for (int i = c; i < n; ++i) {
-            double s = (i == c) ? 1.0 : 0.0;
-            for (int k = c; k < i; ++k) s -= Lp[SSMQ_PKL(i, k)] * Xp[SSMQ_PKL(k, c)];
-            Xp[SSMQ_PKL(i, c)] = s / Lp[SSMQ_PKL(i, i)];
-        }
-        for (int i = n - 1; i >= c; --i) {
-            double s = Xp[SSMQ_PKL(i, c)];
-            for (int k = i + 1; k < n; ++k) s -= Lp[SSMQ_PKL(k, i)] * Xp[SSMQ_PKL(k, c)];
-            Xp[SSMQ_PKL(i, c)] = s / Lp[SSMQ_PKL(i, i)];
-        }
-    }
-    bsync();
-}
-
-// NV per-thread values -> their block sums in out[0 .. NV) (waves added in index order); ends with a barrier
-template <int NV>
-__device__ void ml2_block_sums(const double (&v)[NV], int n, double *red, double *out) {
-    const int wave = threadIdx.x >> 6, nw = kWgtBlock >> 6;
-#pragma unroll
-    for (int p = 0; p < NV; ++p) {
-        if (p < n) {
-            double s = v[p];
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
-            if ((threadIdx.x & 63) == 0) red[wave * NV + p] = s;
-        }
-    }
-    bsync();
-    if ((int)threadIdx.x < n) {
-        double s = 0.0;
-        for (int w = 0; w < nw; ++w) s += red[w * NV + threadIdx.x];
-        out[threadIdx.x] = s;
-    }
-    bsync();
-}
-
-struct Ml2Shared {
-    double sil[SSMQ_MAX_DIM], red[(kMl2Block / 64) * kMl2PM], sums[kMl2PM], yda[kMl2MaxE], scale[kMl2MaxE];
-    double f, g[kMl2PM], lp[kMl2PM];
-    int flag, done, nfev;
-};
-
-// value and gradient at the log-parameters sh.lp -> sh.f, sh.g (every thread may read them after the call); false: K is
-// not positive definite (sh.f = NaN, sh.g = NaN).  lds: the dynamic LDS of the launch (see ml2_lds_bytes).
-template <bool PACKED>
-__device__ bool ml2_eval(const Ml2Args &a, int64_t b, Ml2Shared &sh, double *lds) {
-    const int D = a.D, N = a.N, E = a.E, P = D + 1, tid = threadIdx.x;
-    const int64_t nn = PACKED ? (int64_t)N * (N + 1) / 2 : (int64_t)N * N;
-    double *Km = lds, *Xm = lds + nn, *zs = Xm + nn, *nrm = zs + D * N;
-    double *AY = PACKED ? Km : nrm + N;      // packed: A = X Y over the factor, which is no longer needed by then
-    const double *x = a.x + (a.x_per_fit ? b * D * N : 0);
-    const double *Y = a.y + b * N * E;
-#define ML2_IDX(i, j) (PACKED ? (int64_t)SSMQ_PKL(i, j) : (int64_t)(i) * N + (j))
-    const double alpha = exp(sh.lp[0]);
-    const double la = 2.0 * log(alpha);
-    if (tid < D) sh.sil[tid] = 1.0 / exp(sh.lp[1 + tid]);
-    bsync();
-    for (int idx = tid; idx < D * N; idx += kWgtBlock) zs[idx] = sh.sil[idx / N] * x[idx];
-    bsync();
-    for (int n = tid; n < N; n += kWgtBlock) {
-        double s = 0.0;
-        for (int d = 0; d < D; ++d) s += zs[d * N + n] * zs[d * N + n];
-        nrm[n] = s;
-    }
-    bsync();
-    // K + jitter, lower triangle (bq/bqkern.py:329-343: exp(2 log alpha - maha / 2), maha as |a|^2 + |b|^2 - 2 a.b).  The
-    // reference factors with cho_factor's default lower=False, which reads the upper triangle of K + jitter: entry (i, j),
-    // j <= i, takes the jitter's (j, i), so a jitter that is not symmetric (a per-point nugget, a triangle) counts as there.
-    for (int idx = tid; idx < N * N; idx += kWgtBlock) {
-        const int i = idx / N, j = idx % N;
-        if (j > i) continue;
-        double dot = 0.0;
-        for (int d = 0; d < D; ++d) dot += zs[d * N + i] * zs[d * N + j];
-        const double mh = (nrm[i] + nrm[j]) - 2.0 * dot;
-        Km[ML2_IDX(i, j)] = exp(la - 0.5 * mh) + a.jit[(int64_t)j * N + i];
-    }
-    bsync();
-    const bool pd = PACKED ? chol_packed_lds(Km, N, &sh.flag) : chol_block(Km, N, &sh.flag);
-    if (!pd) {
-        if (tid == 0) {
-            sh.f = __builtin_nan("");
-            for (int p = 0; p < P; ++p) sh.g[p] = __builtin_nan("");
-        }
-        bsync();
-        return false;
-    }
-    // half log det: sum log diag L
-    {
-        double v[1] = {0.0};
-        for (int i = tid; i < N; i += kWgtBlock) v[0] += log(Km[ML2_IDX(i, i)]);
-        ml2_block_sums<1>(v, 1, sh.red, sh.sums);
-    }
-    const double hld = sh.sums[0];
-    if (PACKED) chol_inverse_packed(Km, Xm, N);
-    else chol_inverse(Km, Xm, N);
-#define ML2_X(i, j) ((i) >= (j) ? Xm[ML2_IDX(i, j)] : Xm[ML2_IDX(j, i)])
-    // A = X Y (N x E)
-    for (int idx = tid; idx < N * E; idx += kWgtBlock) {
-        const int i = idx / E, e = idx % E;
-        double s = 0.0;
-        for (int k = 0; k < N; ++k) s += ML2_X(i, k) * Y[k * E + e];
-        AY[idx] = s;
-    }
-    bsync();
-    const bool tp = a.nu != 0.0;
-    if (tid < E) {
-        double s = 0.0;
-        for (int i = 0; i < N; ++i) s += Y[i * E + tid] * AY[i * E + tid];
-        sh.yda[tid] = s;
-        sh.scale[tid] = tp ? (a.nu + N) / (a.nu + s - 2.0) : 1.0;
-    }
-    bsync();
-    if (tid == 0) {
-        double f;
-        if (tp) {
-            double ls = 0.0;
-            for (int e = 0; e < E; ++e) ls += log(1.0 + sh.yda[e] / (a.nu - 2.0));
-            f = 0.5 * (a.nu + N) * ls + E * (hld + a.tp_const);
-        } else {
-            double ya = 0.0;
-            for (int e = 0; e < E; ++e) ya += sh.yda[e];
-            f = E * hld + 0.5 * (ya + E * N * log(2.0 * M_PI));
-        }
-        sh.f = f;
-    }
-    // gradient: 1/2 sum_ij W_ij dK_p(i, j) over the lower triangle (off-diagonal entries twice)
-    double acc[kMl2PM];
-#pragma unroll
-    for (int p = 0; p < kMl2PM; ++p) acc[p] = 0.0;
-    const double da = 2.0 / alpha;
-    for (int idx = tid; idx < N * N; idx += kWgtBlock) {
-        const int i = idx / N, j = idx % N;
-        if (j > i) continue;
-        double w = E * Xm[ML2_IDX(i, j)];
-        for (int e = 0; e < E; ++e) w -= sh.scale[e] * AY[i * E + e] * AY[j * E + e];
-        double dot = 0.0;
-        for (int d = 0; d < D; ++d) dot += zs[d * N + i] * zs[d * N + j];
-        const double mh = (nrm[i] + nrm[j]) - 2.0 * dot;
-        const double c = (i == j ? 1.0 : 2.0) * w * exp(la - 0.5 * mh);
-        acc[0] += c * da;
-#pragma unroll
-        for (int d = 0; d < SSMQ_MAX_DIM; ++d) {
-            if (d < D) {
-                const double dz = zs[d * N + i] - zs[d * N + j];
-                acc[1 + d] += c * (dz * dz);
-            }
-        }
-    }
-    ml2_block_sums<kMl2PM>(acc, P, sh.red, sh.sums);
-    if (tid < P) sh.g[tid] = 0.5 * sh.sums[tid];
-    bsync();
-    return true;
-#undef ML2_X
-#undef ML2_IDX
-}
-
-template <bool PACKED>
-__global__ __launch_bounds__(kMl2Block) void k_ml2(const Ml2Args a) {
-    extern __shared__ __align__(16) double lds[];
-    __shared__ Ml2Shared sh;
-    __shared__ __align__(16) char run_bytes[sizeof(ssmq_bfgs::RunT<kMl2PM>)];     // (no constructor runs on __shared__)
-    ssmq_bfgs::RunT<kMl2PM> &run = *reinterpret_cast<ssmq_bfgs::RunT<kMl2PM> *>(run_bytes);
-    const int64_t b = blockIdx.x;
-    const int P = a.D + 1, tid = threadIdx.x;
-    if (tid == 0) {
-        if (a.optimise) ssmq_bfgs::bfgs_start(run, P, a.lp + b * P);
-        sh.nfev = 0;
-        sh.done = 0;
-    }
-    bsync();
-    // one call site of the objective for both modes: a fit's fun / jac are bit for bit the evaluation mode's at its x
-    while (!sh.done) {
-        if (tid < P) sh.lp[tid] = a.optimise ? run.xt[tid] : a.lp[b * P + tid];
-        bsync();
-        const bool ok = ml2_eval<PACKED>(a, b, sh, lds);
-        if (tid == 0) {
-            ++sh.nfev;
-            if (a.optimise) {
-                const double f = ok ? sh.f : __builtin_huge_val();
-                ssmq_bfgs::bfgs_advance_jac(run, P, f, sh.g, a.gtol, a.maxiter);
-                sh.done = run.phase == ssmq_bfgs::PH_DONE;
-            } else {
-                sh.done = ok ? 1 : 2;
-            }
-        }
-        bsync();
-    }
-    if (!a.optimise) {
-        if (tid == 0) {
-            a.fun[b] = sh.f;
-            a.status[b] = sh.done == 1 ? 0 : 1;
-        }
-        if (tid < P) a.jac[b * P + tid] = sh.g[tid];
-        return;
-    }
-    if (tid < P) {
-        a.xout[b * P + tid] = run.x[tid];
-        a.jac[b * P + tid] = run.g[tid];
-    }
-    for (int i = tid; i < P * P; i += kWgtBlock) a.hess_inv[b * P * P + i] = run.H[i];
-    if (tid == 0) {
-        a.fun[b] = run.old_fval;
-        a.status[b] = run.status;
-        a.nit[b] = run.k;
-        a.nfev[b] = sh.nfev;
-    }
-}
-
-static size_t ml2_lds_bytes(int D, int N, int E, bool packed) {
-    const size_t nn = packed ? (size_t)N * (N + 1) / 2 : (size_t)N * N;
-    return sizeof(double) * (2 * nn + (size_t)D * N + N + (packed ? 0 : (size_t)N * E));
-}
-
-// the TP's constant N / 2 log((nu - 2) pi) - log Gamma((nu + N) / 2) + log Gamma(nu / 2), formed as the reference forms it:
-// the log of Gamma itself (np.log(gamma(.)))
-static double ml2_tp_const(double nu, int N) {
-    return (N / 2.0) * std::log((nu - 2.0) * M_PI) - std::log(std::tgamma((nu + N) / 2.0)) + std::log(std::tgamma(nu / 2.0));
-}
-
-// Host arrays in and out; synchronous.  Returns the first row whose K is not positive definite + 1 (evaluation), else 0.
-static int ml2_impl(Ml2Args a, const double *x, const double *y, const double *jit, const double *lp, double *fun, double *jac,
-                    double *xout, double *hess_inv, int32_t *status, int32_t *nit, int32_t *nfev) {
-    const int D = a.D, N = a.N, E = a.E, P = D + 1;
-    const int64_t B = a.B;
-    int rc = ensure_device();
-    if (rc) return rc;
-    if (B == 0) return SSMQ_OK;
-    hipStream_t s = stream();
-    const bool packed = N > 64;
-    const size_t lds = ml2_lds_bytes(D, N, E, packed);
-    static thread_local unsigned attr_epoch = 0;     // per-device attribute: set again after a device change
-    if (attr_epoch != ssmq::device_epoch()) {
-        const int cap = 160 * 1024 - 8192;           // static __shared__ of k_ml2: Ml2Shared + the BFGS state, < 8 KiB
-        SSMQ_HIP(hipFuncSetAttribute((const void *)k_ml2<true>, hipFuncAttributeMaxDynamicSharedMemorySize, cap));
-        SSMQ_HIP(hipFuncSetAttribute((const void *)k_ml2<false>, hipFuncAttributeMaxDynamicSharedMemorySize, cap));
-        attr_epoch = ssmq::device_epoch();
-    }
-    const size_t nx = (size_t)D * N * (a.x_per_fit ? B : 1), ny = (size_t)B * N * E, nn = (size_t)N * N, np = (size_t)B * P;
-    DBuf dx, dy, dj, dl, dfun, djac, dxo, dh, dst, dit, dfe;
-    if ((rc = dx.alloc(sizeof(double) * nx)) || (rc = dy.alloc(sizeof(double) * ny)) || (rc = dj.alloc(sizeof(double) * nn)) ||
-        (rc = dl.alloc(sizeof(double) * np)) || (rc = dfun.alloc(sizeof(double) * B)) || (rc = djac.alloc(sizeof(double) * np)) ||
-        (rc = dst.alloc(sizeof(int32_t) * B)))
-        return rc;
-    if (a.optimise && ((rc = dxo.alloc(sizeof(double) * np)) || (rc = dh.alloc(sizeof(double) * np * P)) ||
-                       (rc = dit.alloc(sizeof(int32_t) * B)) || (rc = dfe.alloc(sizeof(int32_t) * B))))
-        return rc;
-    SSMQ_HIP(hipMemcpyAsync(dx.p, x, sizeof(double) * nx, hipMemcpyHostToDevice, s));
-    SSMQ_HIP(hipMemcpyAsync(dy.p, y, sizeof(double) * ny, hipMemcpyHostToDevice, s));
-    SSMQ_HIP(hipMemcpyAsync(dj.p, jit, sizeof(double) * nn, hipMemcpyHostToDevice, s));
-    SSMQ_HIP(hipMemcpyAsync(dl.p, lp, sizeof(double) * np, hipMemcpyHostToDevice, s));
-    a.x = dx.d(); a.y = dy.d(); a.jit = dj.d(); a.lp = dl.d();
-    a.fun = dfun.d(); a.jac = djac.d(); a.status = (int32_t *)dst.p;
-    a.xout = a.optimise ? dxo.d() : nullptr;
-    a.hess_inv = a.optimise ? dh.d() : nullptr;
-    a.nit = a.optimise ? (int32_t *)dit.p : nullptr;
-    a.nfev = a.optimise ? (int32_t *)dfe.p : nullptr;
-    if (packed) hipLaunchKernelGGL(k_ml2<true>, dim3((unsigned)B), dim3(kMl2Block), lds, s, a);
-    else hipLaunchKernelGGL(k_ml2<false>, dim3((unsigned)B), dim3(kMl2Block), lds, s, a);
-    if ((rc = hip_fail(hipGetLastError(), "k_ml2"))) return rc;
-    SSMQ_HIP(hipMemcpyAsync(fun, dfun.p, sizeof(double) * B, hipMemcpyDeviceToHost, s));
-    SSMQ_HIP(hipMemcpyAsync(jac, djac.p, sizeof(double) * np, hipMemcpyDeviceToHost, s));
-    SSMQ_HIP(hipMemcpyAsync(status, dst.p, sizeof(int32_t) * B, hipMemcpyDeviceToHost, s));
-    if (a.optimise) {
-        SSMQ_HIP(hipMemcpyAsync(xout, dxo.p, sizeof(double) * np, hipMemcpyDeviceToHost, s));
-        if (hess_inv) SSMQ_HIP(hipMemcpyAsync(hess_inv, dh.p, sizeof(double) * np * P, hipMemcpyDeviceToHost, s));
-        if (nit) SSMQ_HIP(hipMemcpyAsync(nit, dit.p, sizeof(int32_t) * B, hipMemcpyDeviceToHost, s));
-        if (nfev) SSMQ_HIP(hipMemcpyAsync(nfev, dfe.p, sizeof(int32_t) * B, hipMemcpyDeviceToHost, s));
-    }
-    SSMQ_HIP(hipStreamSynchronize(s));
-    if (a.optimise) return SSMQ_OK;
-    for (int64_t b = 0; b < B; ++b)
-        if (status[b]) return (int)std::min<int64_t>(b + 1, INT32_MAX);
-    return SSMQ_OK;
-}
-
-// the supported range (D <= 16, N <= 128, E <= 16) and the arguments both entry points share
-static int ml2_check(const char *what, int D, int N, int E, int64_t B, const double *x, const double *y, const double *jit,
-                     double nu, const double *lp) {
-    if (D < 1 || N < 1 || E < 1 || B < 0 || (B > 0 && (!x || !y || !jit || !lp)) || !(nu == 0.0 || nu > 2.0)) {
-        set_error(std::string(what) + ": bad argument");
-        return SSMQ_E_ARG;
-    }
-    if (D > SSMQ_MAX_DIM || N > kMl2MaxN || E > kMl2MaxE || B > INT32_MAX) {
-        set_error(std::string(what) + ": supported range is D <= 16, N <= 128, E <= 16");
-        return SSMQ_E_UNSUPPORTED;
-    }
-    return SSMQ_OK;
-}
-
-}  // namespace ssmq
-
-extern "C" int ssmq_gp_nlml_batch(int D, int N, int E, int64_t B, const double *x_obs, int x_per_fit, const double *fcn_obs,
-                                  const double *jitter, double nu, const double *log_par, double *nlml, double *grad,
-                                  int32_t *status) {
-    using namespace ssmq;
-    int rc = ml2_check("gp_nlml_batch", D, N, E, B, x_obs, fcn_obs, jitter, nu, log_par);
-    if (rc) return rc;
-    if (B > 0 && (!nlml || !grad || !status)) {
-        set_error("gp_nlml_batch: bad argument");
-        return SSMQ_E_ARG;
-    }
-    Ml2Args a{};
-    a.D = D; a.N = N; a.E = E; a.B = B; a.x_per_fit = x_per_fit ? 1 : 0; a.optimise = 0;
-    a.nu = nu; a.tp_const = nu != 0.0 ? ml2_tp_const(nu, N) : 0.0;
-    return ml2_impl(a, x_obs, fcn_obs, jitter, log_par, nlml, grad, nullptr, nullptr, status, nullptr, nullptr);
-}
-
-extern "C" int ssmq_gp_ml2_batch(int D, int N, int E, int64_t B, const double *x_obs, int x_per_fit, const double *fcn_obs,
-                                 const double *jitter, double nu, double gtol, int maxiter, const double *log_par_0,
-                                 double *x, double *fun, double *jac, double *hess_inv, int32_t *status, int32_t *nit,
-                                 int32_t *nfev) {
-    using namespace ssmq;
-    int rc = ml2_check("gp_ml2_batch", D, N, E, B, x_obs, fcn_obs, jitter, nu, log_par_0);
-    if (rc) return rc;
-    if (B > 0 && (!x || !fun || !jac || !status)) {
-        set_error("gp_ml2_batch: bad argument");
-        return SSMQ_E_ARG;
-    }
-    Ml2Args a{};
-    a.D = D; a.N = N; a.E = E; a.B = B; a.x_per_fit = x_per_fit ? 1 : 0; a.optimise = 1;
-    a.gtol = gtol; a.maxiter = maxiter < 0 ? 200 * (D + 1) : maxiter;
-    a.nu = nu; a.tp_const = nu != 0.0 ? ml2_tp_const(nu, N) : 0.0;
-    return ml2_impl(a, x_obs, fcn_obs, jitter, log_par_0, fun, jac, x, hess_inv, status, nit, nfev);
-}
-
-// ---- prediction: Model.predict of the GP, TP and Bayes-Sard models (bq/bqmod.py:454-493, 840-891, 1090-1130), batched ----------
-//
-// B independent fits, M test points each.  Two kernels, because the factorisation is per fit and the test points are not:
-//   k_predict_fit   one 256-thread workgroup per fit, the front half of ml2_eval: K + jitter I at the NATURAL parameters
-//                   (the arithmetic of k_rbf_factor), Cholesky, explicit inverse (N <= 64: dense in LDS, symmetrised as
-//                   _cho_inv does; N <= 128: packed lower triangles, the lower triangle taken for the symmetric matrix), then
-//                   A = iK Y, the TP scale (nu - 2 + y'iK y) / (nu - 2 + num_pts) and, for Bayes-Sard, V, Z = V'iK,
-//                   (Z V)^-1 by Cholesky (no jitter on Z V here, unlike bq_weights) and A_bs = (Z V)^-1 V'.  Everything
-//                   phase 2 needs goes to a per-fit workspace (PredCarve), the status flag too.
-//   k_predict_test  one 256-thread workgroup per (fit, tile of up to 64 test points): lane l of every wave owns test point
-//                   l of the tile, the four waves share the rows of each sum and add their parts in wave order.  The
-//                   fit's packed iK is loaded into LDS once; the kx row of every lane is parked in LDS as kx[n][lane]
-//                   (consecutive lanes, consecutive doubles: no bank conflict), iK is read as LDS broadcasts.
-// A fit's arithmetic depends on nothing but its own data and (N, NB) - not on B, M or the position in the batch - so row b
-// of a batch is bit-equal to a batch of one.
-
-namespace ssmq {
-
-constexpr int kPredBlock = 256, kPredWaves = kPredBlock / 64;
-
-struct PredCarve {      // offsets (doubles) into one fit's workspace
-    int64_t iK, A, scal, zs, nrm, V, Z, G, iG, Abs, end;
-    __host__ __device__ PredCarve(int64_t D, int64_t N, int64_t E, int64_t NB) {
-        int64_t w = 0;
-        iK = w; w += N * (N + 1) / 2;   // packed lower triangle of sym((K + jitter I)^-1)
-        A = w; w += N * E;              // iK Y
-        scal = w; w += 2;               // [0]: TP variance scale (1 for the GP)
-        zs = w; w += D * N;             // Lam^-1/2 x_obs
-        nrm = w; w += N;                // |zs_n|^2
-        V = w; w += N * NB;             // Vandermonde of x_obs (N x NB)
-        Z = w; w += NB * N;             // V' iK
-        G = w; w += NB * NB;            // Z V -> its Cholesky factor
-        iG = w; w += NB * NB;           // (Z V)^-1
-        Abs = w; w += NB * N;           // (Z V)^-1 V'
-        end = w;
-    }
-};
-
-struct PredArgs {
-    int32_t D, N, E, NB, x_per_fit, test_per_fit, tile, tp_num_pts;
-    int64_t B, M, ntiles;
-    double jitter, nu;                  // nu = 0: no TP scale
-    const double *x;                    // [D][N] or [B][D][N]
-    const double *y;                    // [B][N][E]
-    const double *par;                  // [B][1 + D], natural parameters
-    const int32_t *mulind;              // [D][NB]
-    const double *test;                 // [D][M] or [B][D][M]
-    double *work;                       // [B] x PredCarve::end
-    double *mean, *var;                 // [B][M][E], [B][M]
-    int32_t *status;                    // [B]
-};
-
-template <bool PACKED>
-__global__ __launch_bounds__(kPredBlock) void k_predict_fit(const PredArgs a) {
-    extern __shared__ __align__(16) double lds[];
-    __shared__ double s_sil[SSMQ_MAX_DIM];
-    __shared__ int s_flag;
-    const int D = a.D, N = a.N, E = a.E, NB = a.NB, tid = threadIdx.x;
-    const int64_t b = blockIdx.x;
-    const int64_t nn = PACKED ? (int64_t)N * (N + 1) / 2 : (int64_t)N * N;
-    const PredCarve cv(D, N, E, NB);
-    double *w = a.work + b * cv.end;
-    double *Km = lds, *Xm = lds + nn;
-    const double *x = a.x + (a.x_per_fit ? b * D * N : 0);
-    const double *Y = a.y + b * N * E;
-    const double *pr = a.par + b * (1 + D);
-    double *zs = w + cv.zs, *nrm = w + cv.nrm;
-#define PRED_IDX(i, j) (PACKED ? (int64_t)SSMQ_PKL(i, j) : (int64_t)(i) * N + (j))
-    const double la = 2.0 * log(pr[0]);
-    if (tid < D) s_sil[tid] = 1.0 / pr[1 + tid];
-    bsync();
-    for (int idx = tid; idx < D * N; idx += kWgtBlock) zs[idx] = s_sil[idx / N] * x[idx];
-    bsync();
-    for (int n = tid; n < N; n += kWgtBlock) {
-        double s = 0.0;
-        for (int d = 0; d < D; ++d) s += zs[d * N + n] * zs[d * N + n];
-        nrm[n] = s;
-    }
-    bsync();
-    for (int idx = tid; idx < N * N; idx += kWgtBlock) {
-        const int i = idx / N, j = idx % N;
-        if (j > i) continue;
-        double dot = 0.0;
-        for (int d = 0; d < D; ++d) dot += zs[d * N + i] * zs[d * N + j];
-        Km[PRED_IDX(i, j)] = exp(la - 0.5 * ((nrm[i] + nrm[j]) - 2.0 * dot)) + (i == j ? a.jitter : 0.0);
-    }
-    bsync();
-    const bool pd = PACKED ? chol_packed_lds(Km, N, &s_flag) : chol_block(Km, N, &s_flag);
-    if (!pd) {
-        if (tid == 0) a.status[b] = 1;
-        return;
-    }
-    if (PACKED) chol_inverse_packed(Km, Xm, N);
-    else chol_inverse(Km, Xm, N);
-    // S: the symmetric inverse as a packed lower triangle, in LDS for the products below and in the workspace for phase 2
-    double *S = PACKED ? Xm : Km;
-    if (!PACKED) {
-        for (int idx = tid; idx < N * N; idx += kWgtBlock) {
-            const int i = idx / N, j = idx % N;
-            if (j <= i) S[SSMQ_PKL(i, j)] = 0.5 * (Xm[i * N + j] + Xm[j * N + i]);     // Km: the factor is no longer needed
-        }
-        bsync();
-    }
-    for (int idx = tid; idx < N * (N + 1) / 2; idx += kWgtBlock) w[cv.iK + idx] = S[idx];
-#define PRED_S(i, j) ((i) >= (j) ? S[SSMQ_PKL(i, j)] : S[SSMQ_PKL(j, i)])
-    double *A = w + cv.A;
-    for (int idx = tid; idx < N * E; idx += kWgtBlock) {
-        const int i = idx / E, e = idx % E;
-        double s = 0.0;
-        for (int k = 0; k < N; ++k) s += PRED_S(i, k) * Y[k * E + e];
-        A[idx] = s;
-    }
-    bsync();
-    if (tid == 0) {
-        double scale = 1.0;
-        if (a.nu != 0.0) {              // E = 1 (checked by the entry point)
-            double s = 0.0;
-            for (int i = 0; i < N; ++i) s += Y[i] * A[i];
-            scale = (a.nu - 2.0 + s) / (a.nu - 2.0 + a.tp_num_pts);
-        }
-        w[cv.scal] = scale;
-    }
-    int st = 0;
-    if (NB > 0) {
-        double *V = w + cv.V, *Z = w + cv.Z, *G = w + cv.G, *iG = w + cv.iG, *Abs = w + cv.Abs;
-        for (int idx = tid; idx < N * NB; idx += kWgtBlock) {
-            const int n = idx / NB, q = idx % NB;
-            double v = 1.0;
-            for (int d = 0; d < D; ++d) v *= ipow(x[d * N + n], a.mulind[d * NB + q]);
-            V[idx] = v;
-        }
-        bsync();
-        for (int idx = tid; idx < NB * N; idx += kWgtBlock) {
-            const int q = idx / N, n = idx % N;
-            double s = 0.0;
-            for (int k = 0; k < N; ++k) s += V[k * NB + q] * PRED_S(k, n);
-            Z[idx] = s;
-        }
-        bsync();
-        // Z V; the reference factors it with cho_factor's lower=False, which reads the upper triangle: entry (i, j), j <= i,
-        // of the factor's input is (Z V)(j, i)
-        for (int idx = tid; idx < NB * NB; idx += kWgtBlock) {
-            const int i = idx / NB, j = idx % NB;
-            double s = 0.0;
-            if (j <= i)
-                for (int n = 0; n < N; ++n) s += Z[j * N + n] * V[n * NB + i];
-            G[idx] = s;
-        }
-        bsync();
-        if (chol_block(G, NB, &s_flag)) {
-            chol_inverse(G, iG, NB);
-            for (int idx = tid; idx < NB * N; idx += kWgtBlock) {
-                const int q = idx / N, n = idx % N;
-                double s = 0.0;
-                for (int r = 0; r < NB; ++r) s += iG[q * NB + r] * V[n * NB + r];
-                Abs[idx] = s;
-            }
-        } else {
-            st = 2;
-        }
-    }
-    if (tid == 0) a.status[b] = st;
-#undef PRED_S
-#undef PRED_IDX
-}
-
-// the four waves' parts of one per-lane sum, added in wave order (to every wave); red: kPredBlock doubles of LDS
-__device__ __forceinline__ double pred_tile_sum(double v, double *red) {
-    red[threadIdx.x] = v;
-    bsync();
-    const int lane = threadIdx.x & 63;
-    double s = red[lane];
-#pragma unroll
-    for (int wv = 1; wv < kPredWaves; ++wv) s += red[wv * 64 + lane];
-    bsync();
-    return s;
-}
-
-__global__ __launch_bounds__(kPredBlock) void k_predict_test(const PredArgs a) {
-    extern __shared__ __align__(16) double lds[];
-    const int D = a.D, N = a.N, E = a.E, NB = a.NB, tile = a.tile, tid = threadIdx.x;
-    const int lane = tid & 63, wave = tid >> 6;
-    const int64_t b = blockIdx.x / a.ntiles, t = blockIdx.x % a.ntiles, M = a.M;
-    const int64_t m = t * tile + lane;
-    const bool mine = wave == 0 && lane < tile && m < M;
-    double *mean = a.mean + (b * M + m) * E, *var = a.var + b * M + m;
-    if (a.status[b] != 0) {                 // uniform: the fit has no factorisation
-        if (mine) {
-            for (int e = 0; e < E; ++e) mean[e] = __builtin_nan("");
-            *var = __builtin_nan("");
-        }
-        return;
-    }
-    const PredCarve cv(D, N, E, NB);
-    const double *__restrict__ w = a.work + b * cv.end;
-    const int npk = N * (N + 1) / 2;
-    double *iK = lds, *kx = iK + npk, *bv = kx + (int64_t)N * tile, *red = bv + (int64_t)NB * tile;
-    for (int idx = tid; idx < npk; idx += kPredBlock) iK[idx] = w[cv.iK + idx];
-    // lanes past the tile or past M work on the last test point and store nothing
-    const int64_t mc = m < M ? m : M - 1;
-    const int kl = lane < tile ? lane : tile - 1;       // their LDS column: a duplicate of the tile's last
-    const double *xt = a.test + (a.test_per_fit ? b * D * M : 0);
-    const double *pr = a.par + b * (1 + D);
-    const double *zs = w + cv.zs, *nrm = w + cv.nrm;
-    const double la = 2.0 * log(pr[0]);
-    // kx as RBFGauss.eval forms it (k_rbf_eval): exp(2 log alpha - (|a|^2 + |b|^2 - 2 a.b) / 2)
-    double z[SSMQ_MAX_DIM];
-    double na = 0.0;
-#pragma unroll
-    for (int d = 0; d < SSMQ_MAX_DIM; ++d) {
-        z[d] = 0.0;
-        if (d < D) {
-            z[d] = (1.0 / pr[1 + d]) * xt[d * M + mc];
-            na += z[d] * z[d];
-        }
-    }
-    if (lane < tile) {
-        for (int n = wave; n < N; n += kPredWaves) {
-            double dot = 0.0;
-#pragma unroll
-            for (int d = 0; d < SSMQ_MAX_DIM; ++d)
-                if (d < D) dot += z[d] * zs[d * N + n];
-            kx[n * tile + lane] = exp(la - 0.5 * ((na + nrm[n]) - 2.0 * dot));
-        }
-    }
-    bsync();
-    // kx iK kx' over the packed triangle: row i gives kx_i (2 sum_{j < i} iK_ij kx_j + iK_ii kx_i)
-    double acc = 0.0;
-    for (int i = wave; i < N; i += kPredWaves) {
-        const double *row = iK + SSMQ_PKL(i, 0);
-        double s = 0.0;
-        for (int j = 0; j < i; ++j) s += row[j] * kx[j * tile + kl];
-        const double ki = kx[i * tile + kl];
-        acc += ki * (2.0 * s + row[i] * ki);
-    }
-    const double quad = pred_tile_sum(acc, red);
-    double v = exp(la) - quad;              // kxx = eval(test, test, diag=True) = exp(2 log alpha - 0)
-    if (NB > 0) {
-        // b = Z kx' - vx', var += b' (Z V)^-1 b, and kx <- kx - b' A_bs in place for the mean
-        const double *Z = w + cv.Z, *iG = w + cv.iG, *Abs = w + cv.Abs;
-        for (int q = wave; q < NB; q += kPredWaves) {
-            double s = 0.0;
-            for (int n = 0; n < N; ++n) s += Z[q * N + n] * kx[n * tile + kl];
-            double vx = 1.0;
-            for (int d = 0; d < D; ++d) vx *= ipow(xt[d * M + mc], a.mulind[d * NB + q]);
-            if (lane < tile) bv[q * tile + lane] = s - vx;
-        }
-        bsync();
-        double bq = 0.0;
-        for (int q = wave; q < NB; q += kPredWaves) {
-            double s = 0.0;
-            for (int r = 0; r < NB; ++r) s += iG[q * NB + r] * bv[r * tile + kl];
-            bq += bv[q * tile + kl] * s;
-        }
-        v += pred_tile_sum(bq, red);
-        for (int n = wave; n < N; n += kPredWaves) {
-            double s = 0.0;
-            for (int q = 0; q < NB; ++q) s += bv[q * tile + kl] * Abs[q * N + n];
-            if (lane < tile) kx[n * tile + lane] -= s;
-        }
-        bsync();
-    }
-    v *= w[cv.scal];
-    const double *A = w + cv.A;
-    double me[kMl2MaxE];
-#pragma unroll
-    for (int e = 0; e < kMl2MaxE; ++e) me[e] = 0.0;
-    for (int n = wave; n < N; n += kPredWaves) {
-        const double k = kx[n * tile + kl];
-#pragma unroll
-        for (int e = 0; e < kMl2MaxE; ++e)
-            if (e < E) me[e] += k * A[n * E + e];
-    }
-#pragma unroll
-    for (int e = 0; e < kMl2MaxE; ++e) {
-        if (e < E) {                        // uniform
-            const double s = pred_tile_sum(me[e], red);
-            if (mine) mean[e] = s;
-        }
-    }
-    if (mine) *var = v;
-}
-
-static size_t pred_test_lds(int N, int NB, int tile) {
-    return sizeof(double) * ((size_t)N * (N + 1) / 2 + (size_t)(N + NB) * tile + kPredBlock);
-}
-
-}  // namespace ssmq
-
-extern "C" int ssmq_gp_predict_batch(int D, int N, int E, int64_t B, const double *x_obs, int x_per_fit, const double *fcn_obs,
-                                     double jitter, double nu, int tp_num_pts, const double *par, const int32_t *mulind, int NB,
-                                     int64_t M, const double *test, int test_per_fit, double *mean, double *var,
-                                     int32_t *status) {
-    using namespace ssmq;
-    if (D < 1 || N < 1 || E < 1 || B < 0 || M < 1 || NB < 0 || (NB > 0 && !mulind) || !(nu == 0.0 || nu > 2.0) ||
-        (nu != 0.0 && (E != 1 || NB != 0 || tp_num_pts < 1)) || !(jitter >= 0.0) ||
-        (B > 0 && (!x_obs || !fcn_obs || !par || !test || !mean || !var || !status))) {
-        set_error("gp_predict_batch: bad argument");
-        return SSMQ_E_ARG;
-    }
-    if (D > SSMQ_MAX_DIM || N > kMl2MaxN || E > kMl2MaxE || NB > N || B > INT32_MAX || M > INT32_MAX) {
-        set_error("gp_predict_batch: supported range is D <= 16, N <= 128, E <= 16, num_basis <= N, M <= 2^31 - 1");
-        return SSMQ_E_UNSUPPORTED;
-    }
-    int rc = ensure_device();
-    if (rc) return rc;
-    if (B == 0) return SSMQ_OK;
-    hipStream_t s = stream();
-    const bool packed = N > 64;
-    const size_t cap = 160 * 1024 - 1024;
-    static thread_local unsigned attr_epoch = 0;     // per-device attribute: set again after a device change
-    if (attr_epoch != ssmq::device_epoch()) {
-        SSMQ_HIP(hipFuncSetAttribute((const void *)k_predict_fit<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cap));
-        SSMQ_HIP(hipFuncSetAttribute((const void *)k_predict_fit<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cap));
-        SSMQ_HIP(hipFuncSetAttribute((const void *)k_predict_test, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cap));
-        attr_epoch = ssmq::device_epoch();
-    }
-    // the widest tile whose LDS fits: 64 lanes but for Bayes-Sard with many basis functions on many points
-    int tile = 64;
-    while (tile > 8 && pred_test_lds(N, NB, tile) > cap) tile >>= 1;
-    const size_t fit_lds = sizeof(double) * 2 * (packed ? (size_t)N * (N + 1) / 2 : (size_t)N * N);
-    const PredCarve cv(D, N, E, NB);
-    const int64_t ntiles = (M + tile - 1) / tile;
-    // rows per chunk: workspace and results of a chunk within 512 MiB, its grid within 2^31 - 1 workgroups
-    const size_t per_fit = sizeof(double) * ((size_t)cv.end + (size_t)M * (E + 1));
-    int64_t cb = std::max<int64_t>(1, (int64_t)(((size_t)512 << 20) / per_fit));
-    cb = std::min<int64_t>(std::min<int64_t>(cb, B), std::max<int64_t>(1, (int64_t)INT32_MAX / ntiles));
-    const size_t nx = (size_t)D * N * (x_per_fit ? B : 1), ny = (size_t)B * N * E, np = (size_t)B * (1 + D);
-    const size_t nt = (size_t)D * M * (test_per_fit ? B : 1);
-    DBuf dx, dy, dp, dt, dmi, dw, dm, dv, dst;
-    if ((rc = dx.alloc(sizeof(double) * nx)) || (rc = dy.alloc(sizeof(double) * ny)) || (rc = dp.alloc(sizeof(double) * np)) ||
-        (rc = dt.alloc(sizeof(double) * nt)) || (rc = dmi.alloc(sizeof(int32_t) * (size_t)D * NB)) ||
-        (rc = dw.alloc(sizeof(double) * (size_t)cv.end * cb)) || (rc = dm.alloc(sizeof(double) * (size_t)cb * M * E)) ||
-        (rc = dv.alloc(sizeof(double) * (size_t)cb * M)) || (rc = dst.alloc(sizeof(int32_t) * cb)))
-        return rc;
-    SSMQ_HIP(hipMemcpyAsync(dx.p, x_obs, sizeof(double) * nx, hipMemcpyHostToDevice, s));
-    SSMQ_HIP(hipMemcpyAsync(dy.p, fcn_obs, sizeof(double) * ny, hipMemcpyHostToDevice, s));
-    SSMQ_HIP(hipMemcpyAsync(dp.p, par, sizeof(double) * np, hipMemcpyHostToDevice, s));
-    SSMQ_HIP(hipMemcpyAsync(dt.p, test, sizeof(double) * nt, hipMemcpyHostToDevice, s));
-    if (NB > 0) SSMQ_HIP(hipMemcpyAsync(dmi.p, mulind, sizeof(int32_t) * (size_t)D * NB, hipMemcpyHostToDevice, s));
-    PredArgs a{};
-    a.D = D; a.N = N; a.E = E; a.NB = NB; a.x_per_fit = x_per_fit ? 1 : 0; a.test_per_fit = test_per_fit ? 1 : 0;
-    a.tile = tile; a.tp_num_pts = tp_num_pts; a.M = M; a.ntiles = ntiles; a.jitter = jitter; a.nu = nu;
-    a.mulind = (const int32_t *)dmi.p; a.work = dw.d(); a.mean = dm.d(); a.var = dv.d(); a.status = (int32_t *)dst.p;
-    for (int64_t b0 = 0; b0 < B; b0 += cb) {
-        const int64_t nb = std::min<int64_t>(cb, B - b0);
-        a.B = nb;
-        a.x = dx.d() + (x_per_fit ? b0 * D * N : 0);
-        a.y = dy.d() + b0 * N * E;
-        a.par = dp.d() + b0 * (1 + D);
-        a.test = dt.d() + (test_per_fit ? b0 * D * M : 0);
-        if (packed) hipLaunchKernelGGL(k_predict_fit<true>, dim3((unsigned)nb), dim3(kPredBlock), fit_lds, s, a);
-        else hipLaunchKernelGGL(k_predict_fit<false>, dim3((unsigned)nb), dim3(kPredBlock), fit_lds, s, a);
-        if ((rc = hip_fail(hipGetLastError(), "k_predict_fit"))) return rc;
-        hipLaunchKernelGGL(k_predict_test, dim3((unsigned)(nb * ntiles)), dim3(kPredBlock), pred_test_lds(N, NB, tile), s, a);
-        if ((rc = hip_fail(hipGetLastError(), "k_predict_test"))) return rc;
-        SSMQ_HIP(hipMemcpyAsync(mean + b0 * M * E, dm.p, sizeof(double) * nb * M * E, hipMemcpyDeviceToHost, s));
-        SSMQ_HIP(hipMemcpyAsync(var + b0 * M, dv.p, sizeof(double) * nb * M, hipMemcpyDeviceToHost, s));
-        SSMQ_HIP(hipMemcpyAsync(status + b0, dst.p, sizeof(int32_t) * nb, hipMemcpyDeviceToHost, s));
-        SSMQ_HIP(hipStreamSynchronize(s));      // the next chunk reuses the workspace and the result buffers
-    }
-    for (int64_t b = 0; b < B; ++b)
-        if (status[b]) return (int)std::min<int64_t>(b + 1, INT32_MAX);
-    return SSMQ_OK;
 }

@@ -1,5 +1,5 @@
 """
-ML-II on the device (csrc/ssmq_weights.hip k_ml2: ssmq_gp_nlml_batch / ssmq_gp_ml2_batch) against the reference's
+ML-II on the device (csrc/ssmq_ml2.hip k_ml2: ssmq_gp_nlml_batch / ssmq_gp_ml2_batch) against the reference's
 neg_log_marginal_likelihood and Model.optimize recorded in tests/golden/g16_ml2.npz (make_golden_ml2.py).
 """
 import os

@@ -1,5 +1,5 @@
 """
-ML-II on the device (csrc/ssmq_weights.hip k_ml2: ssmq_gp_nlml_batch / ssmq_gp_ml2_batch) over the whole range it
+ML-II on the device (csrc/ssmq_ml2.hip k_ml2: ssmq_gp_nlml_batch / ssmq_gp_ml2_batch) over the whole range it
 supports - D <= 16, N <= 128, E <= 16, GP and TP, x shared or per fit, any jitter - against the long-double form of the
 oracle (oracle/ssmq_oracle.py: ml2_nlml), SciPy's BFGS on the float64 oracle, and the reference's values recorded in
 tests/golden/g17_ml2_range.npz (make_golden_ml2_range.py).

@@ -1,5 +1,5 @@
 """
-Model.predict / predict_batch on the device (csrc/ssmq_weights.hip k_predict_fit + k_predict_test: ssmq_gp_predict_batch)
+Model.predict / predict_batch on the device (csrc/ssmq_predict.hip k_predict_fit + k_predict_test: ssmq_gp_predict_batch)
 against the reference's predict recorded in tests/golden/g16_predict.npz (make_golden_predict.py), against the package's own
 kernel methods, and against the interpolation identities.
 
