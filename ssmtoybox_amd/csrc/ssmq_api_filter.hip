@@ -1,0 +1,786 @@
+// C ABI of libssmq (include/ssmq.h), the filters: the time loop with its per-context workspace and captured launch graph
+// (FilterCache), the filter for models that take their noise as an argument, both smoothers, the Student filter, the error sums
+// over filtered trajectories and the simulator.
+#include <algorithm>
+#include <cstring>
+#include <vector>
+#include "ssmq_host.h"
+#include "ssmq_fused.h"
+
+using namespace ssmq;
+
+namespace {
+struct DevBuf {
+    void *p = nullptr;
+    ~DevBuf() { if (p) hipFree(p); }
+    int alloc(size_t bytes) { return hip_fail(hipMalloc(&p, bytes ? bytes : 8), "hipMalloc"); }
+    double *d() { return (double *)p; }
+};
+}  // namespace
+
+// ---- filter recursion around the path ---------------------------------------------------------------------------------
+extern "C" {
+int ssmq_kalman_update_dev(int D, int Y, int64_t B, int64_t ld, const double *d_m_pr, const double *d_P_pr,
+                           const double *d_y_mean, const double *d_P_y, const double *d_P_yx, const double *d_y,
+                           double *d_m_fi, double *d_P_fi, int32_t *d_status) {
+    if (D < 1 || Y < 1 || B < 0 || ld < B || !d_m_pr || !d_P_pr || !d_y_mean || !d_P_y || !d_P_yx || !d_y || !d_m_fi ||
+        !d_P_fi || !d_status)
+        return SSMQ_E_ARG;
+    int rc = ensure_device();
+    if (rc) return rc;
+    if (B == 0) return SSMQ_OK;
+    SSMQ_HIP(hipMemsetAsync(d_status, 0, sizeof(int32_t) * B, stream()));
+    return launch_kalman_update(D, Y, B, ld, d_m_pr, d_P_pr, d_y_mean, d_P_y, d_P_yx, d_y, d_m_fi, d_P_fi, d_status,
+                                stream());
+}
+}  // extern "C"
+
+namespace {
+// Grow-only device workspace + captured launch sequence of the filter loop, kept between calls so that a repeated
+// forward pass (Monte-Carlo studies, bench.py) neither allocates nor pays 3 T kernel-launch latencies: the whole time
+// loop is replayed as one hipGraph while the argument set is unchanged.
+struct FilterCache {
+    void *ws = nullptr;
+    size_t ws_bytes = 0;
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+    std::vector<uint64_t> key;
+    std::vector<double> gqg, rr, ss;
+    int T = -1, fid_dyn = -1, fid_obs = -1, D = -1, Y = -1;
+    int64_t ld = -1;          // the constants sit behind the ld-sized planes: a new pitch moves them
+    bool consts_ok = false;
+    void *user_ws = nullptr;          // constants of the run-time compiled filters (filter_forward_user): G Q G' | R | scale [T]
+    size_t user_bytes = 0;
+    std::vector<double> user_host;    // ... what the block holds
+    void drop_graph() {
+        if (exec) hipGraphExecDestroy(exec);
+        if (graph) hipGraphDestroy(graph);
+        exec = nullptr;
+        graph = nullptr;
+        key.clear();
+    }
+};
+FilterCache &fc_of_ctx() {
+    Ctx &c = ssmq::ctx();
+    if (!c.fc) c.fc = new FilterCache;
+    return *(FilterCache *)c.fc;
+}
+#define g_fc (fc_of_ctx())
+// drops the captured loop on every exit of a scope whose temporaries the graph points into
+struct GraphDropGuard {
+    ~GraphDropGuard() { g_fc.drop_graph(); }
+};
+}  // namespace
+
+namespace ssmq {
+void drop_filter_cache() {
+    g_fc.drop_graph();
+    g_fc.consts_ok = false;
+    if (g_fc.ws) hipFree(g_fc.ws);
+    g_fc.ws = nullptr;
+    g_fc.ws_bytes = 0;
+    if (g_fc.user_ws) hipFree(g_fc.user_ws);
+    g_fc.user_ws = nullptr;
+    g_fc.user_bytes = 0;
+    g_fc.user_host.clear();
+}
+}  // namespace ssmq
+
+// A pair of models of which one or both are user-defined integrands: the whole-pass kernel compiled for them at run time
+// (ssmq_rtc.hip) with the time loop's constants in a small per-context block of its own, or an error - never the launch loop.
+static int filter_forward_user(ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, ssmq_transform *h_obs, const ssmq_integrand *f_obs,
+                               int64_t B, int64_t ld, int T, const double *d_y, const double *d_m0, const double *d_P0,
+                               const double *GQG, const double *R, double *d_fm, double *d_fP, int32_t *d_status,
+                               const double *sscale, double student_dof, hipStream_t s) {
+    const int D = h_dyn->D, Y = h_obs->E;
+    FInfo fio, fid;
+    if (!integrand_info(f_obs->id, &fio) || !integrand_info(f_dyn->id, &fid)) {
+        set_error("unknown integrand id");
+        return SSMQ_E_ARG;
+    }
+    // G Q G' | R | scale [T] | time tables [T] x 2: a built-in member whose time dependence is tabulated on the host (UNGM) reads
+    // its table every step (HasTimeTable<> in ssmq_fused.h), as on the AOT route
+    const size_t nd = (size_t)D * D + (size_t)Y * Y + 3 * (size_t)T, need = sizeof(double) * nd;
+    if (g_fc.user_bytes < need) {
+        if (g_fc.user_ws) {
+            SSMQ_HIP(hipStreamSynchronize(s));
+            hipFree(g_fc.user_ws);
+        }
+        g_fc.user_ws = nullptr;
+        g_fc.user_bytes = 0;
+        g_fc.user_host.clear();
+        SSMQ_HIP(hipMalloc(&g_fc.user_ws, need));
+        g_fc.user_bytes = need;
+    }
+    std::vector<double> h(nd, 0.0);
+    if (GQG) std::copy(GQG, GQG + D * D, h.begin());
+    if (R) std::copy(R, R + Y * Y, h.begin() + D * D);
+    for (int k = 0; k < T; ++k) h[(size_t)D * D + Y * Y + k] = sscale ? sscale[k] : 1.0;
+    const size_t o_td = (size_t)D * D + Y * Y + T, o_to = o_td + T;
+    const bool has_td = time_table(f_dyn->id, T, h.data() + o_td), has_to = time_table(f_obs->id, T, h.data() + o_to);
+    double *w = (double *)g_fc.user_ws;
+    if (h != g_fc.user_host) {   // (stream order: earlier passes that read the block are done before the copy lands)
+        SSMQ_HIP(hipMemcpyAsync(w, h.data(), need, hipMemcpyHostToDevice, s));
+        SSMQ_HIP(hipStreamSynchronize(s));
+        g_fc.user_host = h;
+    }
+    FusedArgs a;
+    memset(&a, 0, sizeof(a));
+    a.y = d_y; a.m0 = d_m0; a.P0 = d_P0; a.fm = d_fm; a.fP = d_fP; a.status = d_status;
+    a.c_dyn = h_dyn->d_small; a.c_obs = h_obs->d_small; a.gqg = w; a.rr = w + D * D; a.B = B; a.ld = ld; a.T = T;
+    a.emv_dyn = h_dyn->emv_mode; a.emv_obs = h_obs->emv_mode; a.nu_dyn = h_dyn->tp_nu; a.nu_obs = h_obs->tp_nu;
+    a.sscale = sscale ? w + D * D + Y * Y : nullptr; a.student_dof = student_dof; a.lpw = 64;
+    fill_fpar(f_dyn, &a.fd);
+    fill_fpar(f_obs, &a.fo);
+    a.fd.ttab = has_td ? w + o_td : nullptr;
+    a.fo.ttab = has_to ? w + o_to : nullptr;
+    const int rc = rtc_launch_fused(h_dyn, f_dyn, h_obs, f_obs, sel_pattern(f_obs, fio.din), a, s, nullptr, false);
+    return rc < 0 ? rc : SSMQ_OK;
+}
+
+namespace ssmq {
+// sscale (host, [T]) / student_dof: Studentian recursion (ssinf.py:634-736); null / 0 for the Gaussian filters.
+int filter_forward_impl(ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, ssmq_transform *h_obs,
+                               const ssmq_integrand *f_obs, int64_t B, int64_t ld, int T, const double *d_y,
+                               const double *d_m0, const double *d_P0, const double *GQG, const double *R,
+                               double *d_fm, double *d_fP, int32_t *d_status, const double *sscale,
+                               double student_dof, double *d_pm, double *d_pP, double *d_pC) {
+    if (!h_dyn || !h_obs || !f_dyn || !f_obs || B < 0 || ld < B || T < 0 || !d_y || !d_m0 || !d_P0 || !d_fm || !d_fP ||
+        !d_status) {
+        set_error("filter_forward: bad argument");
+        return SSMQ_E_ARG;
+    }
+    const int D = h_dyn->D, Y = h_obs->E;
+    if (h_dyn->E != D || h_obs->D != D) {
+        set_error("filter_forward: additive-noise filter needs dyn (D -> D) and obs (D -> Y) transforms");
+        return SSMQ_E_ARG;
+    }
+    const bool user = is_user_integrand(f_dyn) || is_user_integrand(f_obs);
+    if (user && (d_pm || d_pP || d_pC)) return refuse_user_integrand("smoother (predictive moments kept)");
+    int rc = ensure_device();
+    if (rc) return rc;
+    if (B == 0) return SSMQ_OK;
+    if (T == 0) {   // nothing to filter: every trajectory is trivially fine
+        SSMQ_HIP(hipMemsetAsync(d_status, 0, sizeof(int32_t) * ld, stream()));
+        return SSMQ_OK;
+    }
+    hipStream_t s = stream();
+    if (user) return filter_forward_user(h_dyn, f_dyn, h_obs, f_obs, B, ld, T, d_y, d_m0, d_P0, GQG, R, d_fm, d_fP, d_status, sscale,
+                                         student_dof, s);
+    // workspace carve-up (doubles first, then the two int32 status planes)
+    const size_t n_dbl = (size_t)ld * (D + 3 * D * D + Y + Y * Y + Y * D) + 4 * (size_t)T + D * D + Y * Y;
+    const size_t need = sizeof(double) * n_dbl + 2 * sizeof(int32_t) * (size_t)ld;
+    if (g_fc.ws_bytes < need) {
+        g_fc.drop_graph();
+        g_fc.consts_ok = false;
+        if (g_fc.ws) hipFree(g_fc.ws);
+        g_fc.ws = nullptr;
+        g_fc.ws_bytes = 0;
+        SSMQ_HIP(hipMalloc(&g_fc.ws, need));
+        g_fc.ws_bytes = need;
+    }
+    double *w = (double *)g_fc.ws;
+    double *m_pr = w; w += (size_t)ld * D;
+    double *P_pr = w; w += (size_t)ld * D * D;
+    double *C_xx = w; w += (size_t)ld * D * D;
+    double *y_mean = w; w += (size_t)ld * Y;
+    double *P_y = w; w += (size_t)ld * Y * Y;
+    double *P_yx = w; w += (size_t)ld * Y * D;
+    double *smat = w; w += (size_t)ld * D * D;   // Studentian: rescaled scale matrix fed to the next time update
+    double *tvec = w; w += T;
+    double *svec = w; w += T;
+    double *ttab_d = w; w += T;   // time tables of the two integrands (UNGM: 8 cos(1.2 k)), see time_table()
+    double *ttab_o = w; w += T;
+    double *gqg = w; w += D * D;
+    double *rr = w; w += Y * Y;
+    int32_t *st_a = (int32_t *)w, *st_b = st_a + ld;
+
+    std::vector<double> hg(D * D, 0.0), hr(Y * Y, 0.0);
+    if (GQG) hg.assign(GQG, GQG + D * D);
+    if (R) hr.assign(R, R + Y * Y);
+    std::vector<double> hs(T, 1.0);
+    if (sscale) hs.assign(sscale, sscale + T);
+    std::vector<uint64_t> key = {(uint64_t)(uintptr_t)h_dyn, (uint64_t)(uintptr_t)h_obs, (uint64_t)B, (uint64_t)ld,
+                                 (uint64_t)T, (uint64_t)(uintptr_t)d_y, (uint64_t)(uintptr_t)d_m0,
+                                 (uint64_t)(uintptr_t)d_P0, (uint64_t)(uintptr_t)d_fm, (uint64_t)(uintptr_t)d_fP,
+                                 (uint64_t)(uintptr_t)d_status, (uint64_t)(uintptr_t)h_dyn->d_small,
+                                 (uint64_t)(uintptr_t)g_fc.ws, (uint64_t)(uintptr_t)d_pm, (uint64_t)(uintptr_t)d_pP,
+                                 (uint64_t)(uintptr_t)d_pC};
+    const unsigned char *fb = (const unsigned char *)f_dyn;
+    for (size_t i = 0; i + 8 <= sizeof(ssmq_integrand); i += 8) { uint64_t v; memcpy(&v, fb + i, 8); key.push_back(v); }
+    fb = (const unsigned char *)f_obs;
+    for (size_t i = 0; i + 8 <= sizeof(ssmq_integrand); i += 8) { uint64_t v; memcpy(&v, fb + i, 8); key.push_back(v); }
+    key.push_back((uint64_t)h_dyn->emv_mode * 2 + (uint64_t)h_obs->emv_mode);
+    key.push_back(((uint64_t)D << 48) | ((uint64_t)Y << 32) | ((uint64_t)h_dyn->N << 16) | (uint64_t)h_obs->N);
+    key.push_back(((uint64_t)h_dyn->form << 2) | (uint64_t)h_obs->form);
+    key.push_back((uint64_t)(uintptr_t)h_obs->d_small);
+    // which kernel variant apply_dev_impl picks depends on the fast paths the handle's CURRENT constants qualify for:
+    // ssmq_transform_update keeps the block addresses but may withdraw SSMQ_OPT_LDL (and zero its factors)
+    key.push_back(((uint64_t)(uint32_t)h_dyn->opt_mask << 32) | (uint64_t)(uint32_t)h_obs->opt_mask);
+    key.push_back(((uint64_t)(uint32_t)h_dyn->np_pad << 32) | (uint64_t)(uint32_t)h_obs->np_pad);
+    key.push_back(((uint64_t)h_dyn->generation << 32) ^ (uint64_t)h_obs->generation);
+    { uint64_t v; memcpy(&v, &h_dyn->tp_nu, 8); key.push_back(v); memcpy(&v, &h_obs->tp_nu, 8); key.push_back(v);
+      memcpy(&v, &student_dof, 8); key.push_back(v); key.push_back(sscale ? 1 : 0); }
+
+    std::vector<double> htd(T), hto(T);
+    const bool has_td = time_table(f_dyn->id, T, htd.data()), has_to = time_table(f_obs->id, T, hto.data());
+    if (!(g_fc.consts_ok && g_fc.gqg == hg && g_fc.rr == hr && g_fc.T == T && g_fc.ss == hs &&
+          g_fc.fid_dyn == f_dyn->id && g_fc.fid_obs == f_obs->id && g_fc.ld == ld && g_fc.D == D && g_fc.Y == Y)) {
+        g_fc.drop_graph();
+        std::vector<double> tv(T);
+        for (int k = 0; k < T; ++k) tv[k] = (double)k;  // both transforms of step k + 1 use time index k (ssinf.py:104)
+        SSMQ_HIP(hipMemcpyAsync(tvec, tv.data(), sizeof(double) * T, hipMemcpyHostToDevice, s));
+        SSMQ_HIP(hipMemcpyAsync(gqg, hg.data(), sizeof(double) * D * D, hipMemcpyHostToDevice, s));
+        SSMQ_HIP(hipMemcpyAsync(rr, hr.data(), sizeof(double) * Y * Y, hipMemcpyHostToDevice, s));
+        SSMQ_HIP(hipMemcpyAsync(svec, hs.data(), sizeof(double) * T, hipMemcpyHostToDevice, s));
+        if (has_td) SSMQ_HIP(hipMemcpyAsync(ttab_d, htd.data(), sizeof(double) * T, hipMemcpyHostToDevice, s));
+        if (has_to) SSMQ_HIP(hipMemcpyAsync(ttab_o, hto.data(), sizeof(double) * T, hipMemcpyHostToDevice, s));
+        SSMQ_HIP(hipStreamSynchronize(s));
+        g_fc.fid_dyn = f_dyn->id;
+        g_fc.fid_obs = f_obs->id;
+        g_fc.ss = hs;
+        g_fc.gqg = hg;
+        g_fc.rr = hr;
+        g_fc.T = T;
+        g_fc.ld = ld;
+        g_fc.D = D;
+        g_fc.Y = Y;
+        g_fc.consts_ok = true;
+    }
+    // one fused kernel for the whole time loop when this (models, shapes, form) combination has one (it does not keep
+    // the predictive moments, so a pass that has to store them for the smoother takes the launch loop)
+    const bool keep_pred = d_pm && d_pP && d_pC;
+    if (!ssmq::sw("SSMQ_NO_FUSED") && !keep_pred) {
+        FInfo fio;
+        if (!integrand_info(f_obs->id, &fio)) {
+            set_error("unknown integrand id");
+            return SSMQ_E_ARG;
+        }
+        rc = try_launch_fused(h_dyn, f_dyn, h_obs, f_obs, sel_pattern(f_obs, fio.din), B, ld, T, d_y, d_m0, d_P0, gqg,
+                              rr, d_fm, d_fP, d_status, s, nullptr, false, sscale ? svec : nullptr, student_dof,
+                              has_td ? ttab_d : nullptr, has_to ? ttab_o : nullptr);
+        if (rc < 0) return rc;
+        if (rc == 1) return SSMQ_OK;
+    }
+    if (!ssmq::sw("SSMQ_NO_FUSED") && keep_pred && !sscale && student_dof == 0.0) {
+        // smoother: the time loop in one kernel that also leaves the predictive moments of every step in HBM
+        FInfo fio;
+        if (!integrand_info(f_obs->id, &fio)) {
+            set_error("unknown integrand id");
+            return SSMQ_E_ARG;
+        }
+        rc = try_launch_fused_aug(h_dyn, f_dyn, h_obs, f_obs, sel_pattern(f_obs, fio.din), D, 0, 0, B, ld, T, d_y, d_m0, d_P0,
+                                  gqg, rr, gqg, d_fm, d_fP, d_status, s, nullptr, false, has_td ? ttab_d : nullptr,
+                                  has_to ? ttab_o : nullptr, d_pm, d_pP, d_pC);
+        if (rc < 0) return rc;
+        if (rc == 1) return SSMQ_OK;
+    }
+    if (!(g_fc.exec && g_fc.key == key)) {
+        g_fc.drop_graph();
+        SSMQ_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+        rc = hip_fail(hipMemsetAsync(d_status, 0, sizeof(int32_t) * ld, s), "hipMemsetAsync");
+        for (int k = 0; k < T && !rc; ++k) {
+            const double *m_in = k == 0 ? d_m0 : d_fm + (int64_t)(k - 1) * D * ld;
+            const double *P_in = k == 0 ? d_P0 : (student_dof > 0.0 ? smat : d_fP + (int64_t)(k - 1) * D * D * ld);
+            if (keep_pred) {   // predictive moments of every step stay in HBM for the backward pass (ssinf.py:105-107)
+                m_pr = d_pm + (int64_t)k * D * ld;
+                P_pr = d_pP + (int64_t)k * D * D * ld;
+                C_xx = d_pC + (int64_t)k * D * D * ld;
+            }
+            rc = apply_dev_impl(h_dyn, f_dyn, B, ld, m_in, P_in, tvec + k, 0, m_pr, P_pr, C_xx, st_a, gqg, nullptr, false,
+                                hs[k], 1.0, has_td ? ttab_d : nullptr, false);
+            if (!rc)
+                rc = apply_dev_impl(h_obs, f_obs, B, ld, m_pr, P_pr, tvec + k, 0, y_mean, P_y, P_yx, st_b, rr, nullptr,
+                                    false, hs[k], hs[k], has_to ? ttab_o : nullptr, false);
+            if (!rc)
+                rc = launch_kalman_update_ex(D, Y, B, ld, m_pr, P_pr, y_mean, P_y, P_yx, d_y + (int64_t)k * Y * ld,
+                                             d_fm + (int64_t)k * D * ld, d_fP + (int64_t)k * D * D * ld, d_status,
+                                             st_a, st_b, k, s, student_dof, smat, 0);
+        }
+        hipGraph_t g = nullptr;
+        hipError_t ce = hipStreamEndCapture(s, &g);
+        if (rc) {
+            if (g) hipGraphDestroy(g);
+            return rc;
+        }
+        SSMQ_HIP(ce);
+        g_fc.graph = g;
+        SSMQ_HIP(hipGraphInstantiate(&g_fc.exec, g_fc.graph, nullptr, nullptr, 0));
+        g_fc.key = key;
+    }
+    SSMQ_HIP(hipGraphLaunch(g_fc.exec, s));
+    return SSMQ_OK;
+}
+}  // namespace ssmq
+
+extern "C" int ssmq_filter_forward_dev(ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, ssmq_transform *h_obs,
+                                       const ssmq_integrand *f_obs, int64_t B, int64_t ld, int T, const double *d_y,
+                                       const double *d_m0, const double *d_P0, const double *GQG, const double *R,
+                                       double *d_fm, double *d_fP, int32_t *d_status) {
+    SSMQ_HANDLE_LOCK(h_dyn, h_obs);
+    return filter_forward_impl(h_dyn, f_dyn, h_obs, f_obs, B, ld, T, d_y, d_m0, d_P0, GQG, R, d_fm, d_fP, d_status,
+                               nullptr, 0.0);
+}
+
+// Filters whose models take the noise as an argument (ssinf.py:271-272, 282-283, 294-295): the moments are augmented with
+// the noise statistics before each transform and the cross-covariance is cut back to the state columns. Plain launch
+// loop (augment | apply | augment | apply | update per step); no fused kernel and no graph cache for this path yet.
+// d_pm / d_pP / d_pC (all or none): predictive mean [T][D][ld], covariance [T][D*D][ld] and dynamics cross-covariance of
+// every step for the RTS pass; *c_cols returns the number of columns stored per row of d_pC (D from the fused kernel,
+// D + dq from the launch loop, whose transform writes the full E x (D + dq) block: d_pC must hold T * D * (D + dq) planes).
+static int filter_forward_aug_impl(ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, ssmq_transform *h_obs,
+                                   const ssmq_integrand *f_obs, int dim_state, int64_t B, int64_t ld, int T,
+                                   const double *d_y, const double *d_m0, const double *d_P0, const double *q_mean,
+                                   const double *q_cov, int dq, const double *r_mean, const double *r_cov, int dr,
+                                   double *d_fm, double *d_fP, int32_t *d_status, double *d_pm, double *d_pP,
+                                   double *d_pC, int *c_cols) {
+    if (is_user_integrand(f_dyn) || is_user_integrand(f_obs)) return refuse_user_integrand("filter with non-additive noise (augmented moments)");
+    if (!h_dyn || !h_obs || !f_dyn || !f_obs || dim_state <= 0 || dq < 0 || dr < 0 || B < 0 || ld < B || T < 0 || !d_y ||
+        !d_m0 || !d_P0 || !d_fm || !d_fP || !d_status || (dq > 0 && (!q_mean || !q_cov)) ||
+        (dr > 0 && (!r_mean || !r_cov))) {
+        set_error("filter_forward_aug: bad argument");
+        return SSMQ_E_ARG;
+    }
+    const int D = dim_state, Da = D + dq, Do = D + dr, Y = h_obs->E;
+    if (h_dyn->D != Da || h_dyn->E != D || h_obs->D != Do) {
+        set_error("filter_forward_aug: transforms must be (dim_state + dq -> dim_state) and (dim_state + dr -> dim_y)");
+        return SSMQ_E_ARG;
+    }
+    int rc = ensure_device();
+    if (rc) return rc;
+    if (B == 0) return SSMQ_OK;
+    hipStream_t s = stream();
+    if (T == 0) {
+        SSMQ_HIP(hipMemsetAsync(d_status, 0, sizeof(int32_t) * ld, s));
+        SSMQ_HIP(hipStreamSynchronize(s));
+        return SSMQ_OK;
+    }
+    // small constants first (time tables, noise statistics); the plane workspace only if the launch loop is needed
+    DevBuf cs;
+    const size_t n_noise = (size_t)dq + (dq ? (size_t)dq * dq : (size_t)D * D) + dr + (dr ? (size_t)dr * dr : (size_t)Y * Y);
+    if ((rc = cs.alloc(sizeof(double) * (3 * (size_t)T + n_noise)))) return rc;
+    double *w = cs.d();
+    double *tvec = w; w += T;
+    double *ttab_d = w; w += T;
+    double *ttab_o = w; w += T;
+    double *d_qm = w; w += dq;
+    double *d_qc = w; w += dq ? (size_t)dq * dq : (size_t)D * D;
+    double *d_rm = w; w += dr;
+    double *d_rc = w; w += dr ? (size_t)dr * dr : (size_t)Y * Y;
+
+    std::vector<double> tv(T), htd(T), hto(T);
+    for (int k = 0; k < T; ++k) tv[k] = (double)k;   // both transforms of step k + 1 use time index k (ssinf.py:104)
+    const bool has_td = time_table(f_dyn->id, T, htd.data()), has_to = time_table(f_obs->id, T, hto.data());
+    SSMQ_HIP(hipMemcpyAsync(tvec, tv.data(), sizeof(double) * T, hipMemcpyHostToDevice, s));
+    if (has_td) SSMQ_HIP(hipMemcpyAsync(ttab_d, htd.data(), sizeof(double) * T, hipMemcpyHostToDevice, s));
+    if (has_to) SSMQ_HIP(hipMemcpyAsync(ttab_o, hto.data(), sizeof(double) * T, hipMemcpyHostToDevice, s));
+    std::vector<double> zq((size_t)D * D, 0.0), zr((size_t)Y * Y, 0.0);
+    if (dq) SSMQ_HIP(hipMemcpyAsync(d_qm, q_mean, sizeof(double) * dq, hipMemcpyHostToDevice, s));
+    SSMQ_HIP(hipMemcpyAsync(d_qc, q_cov ? q_cov : zq.data(), sizeof(double) * (dq ? (size_t)dq * dq : (size_t)D * D),
+                            hipMemcpyHostToDevice, s));
+    if (dr) SSMQ_HIP(hipMemcpyAsync(d_rm, r_mean, sizeof(double) * dr, hipMemcpyHostToDevice, s));
+    SSMQ_HIP(hipMemcpyAsync(d_rc, r_cov ? r_cov : zr.data(), sizeof(double) * (dr ? (size_t)dr * dr : (size_t)Y * Y),
+                            hipMemcpyHostToDevice, s));
+    SSMQ_HIP(hipMemsetAsync(d_status, 0, sizeof(int32_t) * ld, s));
+    SSMQ_HIP(hipStreamSynchronize(s));   // the host staging vectors above go out of scope with this call
+
+    // one kernel for the whole time loop when this combination has an instantiation (ssmq_filter_fused.hip)
+    if (!ssmq::sw("SSMQ_NO_FUSED")) {
+        FInfo fio;
+        if (!integrand_info(f_obs->id, &fio)) {
+            set_error("unknown integrand id");
+            return SSMQ_E_ARG;
+        }
+        // noise block q_mean | q_cov | r_mean | r_cov and the additive terms (zeros for a non-additive model)
+        std::vector<double> hn, ha((size_t)D * D + (size_t)Y * Y, 0.0);
+        for (int i = 0; i < dq; ++i) hn.push_back(q_mean[i]);
+        for (int i = 0; i < dq * dq; ++i) hn.push_back(q_cov[i]);
+        for (int i = 0; i < dr; ++i) hn.push_back(r_mean[i]);
+        for (int i = 0; i < dr * dr; ++i) hn.push_back(r_cov[i]);
+        hn.push_back(0.0);
+        if (!dq && q_cov) for (int i = 0; i < D * D; ++i) ha[i] = q_cov[i];
+        if (!dr && r_cov) for (int i = 0; i < Y * Y; ++i) ha[(size_t)D * D + i] = r_cov[i];
+        DevBuf dn, da;
+        if ((rc = dn.alloc(sizeof(double) * hn.size())) || (rc = da.alloc(sizeof(double) * ha.size()))) return rc;
+        SSMQ_HIP(hipMemcpyAsync(dn.p, hn.data(), sizeof(double) * hn.size(), hipMemcpyHostToDevice, s));
+        SSMQ_HIP(hipMemcpyAsync(da.p, ha.data(), sizeof(double) * ha.size(), hipMemcpyHostToDevice, s));
+        rc = try_launch_fused_aug(h_dyn, f_dyn, h_obs, f_obs, sel_pattern(f_obs, fio.din), D, dq, dr, B, ld, T, d_y, d_m0,
+                                  d_P0, da.d(), da.d() + (size_t)D * D, dn.d(), d_fm, d_fP, d_status, s, nullptr, false,
+                                  has_td ? ttab_d : nullptr, has_to ? ttab_o : nullptr, d_pm, d_pP, d_pC);
+        hipError_t e = hipStreamSynchronize(s);
+        if (rc < 0) return rc;
+        SSMQ_HIP(e);
+        if (rc == 1) {
+            if (c_cols) *c_cols = D;
+            return SSMQ_OK;
+        }
+        rc = 0;
+    }
+
+    DevBuf ws, st;
+    const size_t n_dbl = (size_t)ld * (Da + Da * Da + D + D * D + D * Da + Do + Do * Do + Y + Y * Y + Y * Do);
+    if ((rc = ws.alloc(sizeof(double) * n_dbl)) || (rc = st.alloc(2 * sizeof(int32_t) * (size_t)ld))) return rc;
+    w = ws.d();
+    double *ma = w; w += (size_t)ld * Da;
+    double *Pa = w; w += (size_t)ld * Da * Da;
+    double *m_pr = w; w += (size_t)ld * D;
+    double *P_pr = w; w += (size_t)ld * D * D;
+    double *C_xx = w; w += (size_t)ld * D * Da;
+    double *mo = w; w += (size_t)ld * Do;
+    double *Po = w; w += (size_t)ld * Do * Do;
+    double *y_mean = w; w += (size_t)ld * Y;
+    double *P_y = w; w += (size_t)ld * Y * Y;
+    double *P_yx = w; w += (size_t)ld * Y * Do;
+    int32_t *st_a = (int32_t *)st.p, *st_b = st_a + ld;
+
+    if (c_cols) *c_cols = Da;
+    for (int k = 0; k < T && !rc; ++k) {
+        const double *m_in = k == 0 ? d_m0 : d_fm + (int64_t)(k - 1) * D * ld;
+        const double *P_in = k == 0 ? d_P0 : d_fP + (int64_t)(k - 1) * D * D * ld;
+        if (d_pm) {      // predictive moments of every step stay in HBM for the backward pass (ssinf.py:105-107)
+            m_pr = d_pm + (int64_t)k * D * ld;
+            P_pr = d_pP + (int64_t)k * D * D * ld;
+            C_xx = d_pC + (int64_t)k * D * Da * ld;
+        }
+        if (dq) {
+            rc = launch_augment(m_in, P_in, d_qm, d_qc, ma, Pa, D, dq, B, ld, s);
+            if (!rc)
+                rc = apply_dev_impl(h_dyn, f_dyn, B, ld, ma, Pa, tvec + k, 0, m_pr, P_pr, C_xx, st_a, nullptr, nullptr, false,
+                                    1.0, 1.0, has_td ? ttab_d : nullptr, false);
+        } else {
+            rc = apply_dev_impl(h_dyn, f_dyn, B, ld, m_in, P_in, tvec + k, 0, m_pr, P_pr, C_xx, st_a, d_qc, nullptr, false,
+                                1.0, 1.0, has_td ? ttab_d : nullptr, false);
+        }
+        if (rc) break;
+        if (dr) {
+            rc = launch_augment(m_pr, P_pr, d_rm, d_rc, mo, Po, D, dr, B, ld, s);
+            if (!rc)
+                rc = apply_dev_impl(h_obs, f_obs, B, ld, mo, Po, tvec + k, 0, y_mean, P_y, P_yx, st_b, nullptr, nullptr, false,
+                                    1.0, 1.0, has_to ? ttab_o : nullptr, false);
+        } else {
+            rc = apply_dev_impl(h_obs, f_obs, B, ld, m_pr, P_pr, tvec + k, 0, y_mean, P_y, P_yx, st_b, d_rc, nullptr, false,
+                                1.0, 1.0, has_to ? ttab_o : nullptr, false);
+        }
+        if (!rc)
+            rc = launch_kalman_update_ex(D, Y, B, ld, m_pr, P_pr, y_mean, P_y, P_yx, d_y + (int64_t)k * Y * ld,
+                                         d_fm + (int64_t)k * D * ld, d_fP + (int64_t)k * D * D * ld, d_status, st_a, st_b,
+                                         k, s, 0.0, nullptr, Do);
+    }
+    hipError_t se = hipStreamSynchronize(s);   // workspace is released on return
+    if (rc) return rc;
+    SSMQ_HIP(se);
+    return SSMQ_OK;
+}
+
+extern "C" int ssmq_filter_forward_aug_dev(ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, ssmq_transform *h_obs,
+                                           const ssmq_integrand *f_obs, int dim_state, int64_t B, int64_t ld, int T,
+                                           const double *d_y, const double *d_m0, const double *d_P0,
+                                           const double *q_mean, const double *q_cov, int dq, const double *r_mean,
+                                           const double *r_cov, int dr, double *d_fm, double *d_fP,
+                                           int32_t *d_status) {
+    SSMQ_HANDLE_LOCK(h_dyn, h_obs);
+    return filter_forward_aug_impl(h_dyn, f_dyn, h_obs, f_obs, dim_state, B, ld, T, d_y, d_m0, d_P0, q_mean, q_cov, dq,
+                                   r_mean, r_cov, dr, d_fm, d_fP, d_status, nullptr, nullptr, nullptr, nullptr);
+}
+
+// Forward pass + RTS smoother for models that take their noise as an argument: backward_pass of the reference is model-
+// agnostic (ssinf.py:120-147, 325-344); the cross-covariance it needs is the one _time_update cut back to the state
+// columns (:294-295).  Arguments as ssmq_filter_forward_aug_dev, outputs as ssmq_filter_smooth_dev.  Synchronous.
+extern "C" int ssmq_filter_smooth_aug_dev(ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, ssmq_transform *h_obs,
+                                          const ssmq_integrand *f_obs, int dim_state, int64_t B, int64_t ld, int T,
+                                          const double *d_y, const double *d_m0, const double *d_P0,
+                                          const double *q_mean, const double *q_cov, int dq, const double *r_mean,
+                                          const double *r_cov, int dr, double *d_fm, double *d_fP, double *d_sm,
+                                          double *d_sP, int32_t *d_status) {
+    if (is_user_integrand(f_dyn) || is_user_integrand(f_obs)) return refuse_user_integrand("ssmq_filter_smooth_aug_dev");
+    SSMQ_HANDLE_LOCK(h_dyn, h_obs);
+    if (!h_dyn || !d_sm || !d_sP || dim_state <= 0 || dq < 0 || B < 0 || T < 0 || ld < B) {
+        set_error("filter_smooth_aug: bad argument");
+        return SSMQ_E_ARG;
+    }
+    int rc = ensure_device();
+    if (rc) return rc;
+    if (B == 0) return SSMQ_OK;
+    const int D = dim_state;
+    if (T == 0)
+        return filter_forward_aug_impl(h_dyn, f_dyn, h_obs, f_obs, D, B, ld, T, d_y, d_m0, d_P0, q_mean, q_cov, dq, r_mean,
+                                       r_cov, dr, d_fm, d_fP, d_status, nullptr, nullptr, nullptr, nullptr);
+    DevBuf pm, pP, pC;
+    if ((rc = pm.alloc(sizeof(double) * (size_t)T * D * ld)) || (rc = pP.alloc(sizeof(double) * (size_t)T * D * D * ld)) ||
+        (rc = pC.alloc(sizeof(double) * (size_t)T * D * (D + dq) * ld)))
+        return rc;
+    int c_cols = D;
+    rc = filter_forward_aug_impl(h_dyn, f_dyn, h_obs, f_obs, D, B, ld, T, d_y, d_m0, d_P0, q_mean, q_cov, dq, r_mean, r_cov,
+                                 dr, d_fm, d_fP, d_status, pm.d(), pP.d(), pC.d(), &c_cols);
+    if (rc) return rc;
+    rc = launch_rts_backward(D, B, ld, T, d_fm, d_fP, pm.d(), pP.d(), pC.d(), d_sm, d_sP, d_status, stream(), c_cols);
+    hipError_t e = hipStreamSynchronize(stream());
+    if (rc) return rc;
+    SSMQ_HIP(e);
+    return SSMQ_OK;
+}
+
+// backward_pass alone (ssinf.py:120-147, 325-344) over moments a caller kept from its own forward pass - the marginalised
+// filter, whose forward pass is driven from the host (BFGS per step)
+extern "C" int ssmq_rts_backward_dev(int D, int64_t B, int64_t ld, int T, const double *d_fm, const double *d_fP,
+                                     const double *d_pm, const double *d_pP, const double *d_pC, double *d_sm, double *d_sP,
+                                     int32_t *d_status) {
+    if (D < 1 || B < 0 || T < 0 || ld < B || !d_fm || !d_fP || !d_pm || !d_pP || !d_pC || !d_sm || !d_sP || !d_status) {
+        set_error("rts_backward: bad argument");
+        return SSMQ_E_ARG;
+    }
+    int rc = ensure_device();
+    if (rc) return rc;
+    if (B == 0 || T == 0) return SSMQ_OK;
+    rc = launch_rts_backward(D, B, ld, T, d_fm, d_fP, d_pm, d_pP, d_pC, d_sm, d_sP, d_status, stream(), D);
+    hipError_t e = hipStreamSynchronize(stream());
+    if (rc) return rc;
+    SSMQ_HIP(e);
+    return SSMQ_OK;
+}
+
+extern "C" int ssmq_filter_smooth_dev(ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, ssmq_transform *h_obs,
+                                      const ssmq_integrand *f_obs, int64_t B, int64_t ld, int T, const double *d_y,
+                                      const double *d_m0, const double *d_P0, const double *GQG, const double *R,
+                                      double *d_fm, double *d_fP, double *d_sm, double *d_sP, int32_t *d_status) {
+    if (is_user_integrand(f_dyn) || is_user_integrand(f_obs)) return refuse_user_integrand("ssmq_filter_smooth_dev");
+    SSMQ_HANDLE_LOCK(h_dyn, h_obs);
+    if (!h_dyn || !d_sm || !d_sP || B < 0 || T < 0 || ld < B) {
+        set_error("filter_smooth: bad argument");
+        return SSMQ_E_ARG;
+    }
+    int rc = ensure_device();
+    if (rc) return rc;
+    if (B == 0) return SSMQ_OK;
+    if (T == 0) {
+        if (d_status) SSMQ_HIP(hipMemsetAsync(d_status, 0, sizeof(int32_t) * ld, stream()));
+        SSMQ_HIP(hipStreamSynchronize(stream()));
+        return SSMQ_OK;
+    }
+    const int D = h_dyn->D;
+    DevBuf pm, pP, pC;
+    if ((rc = pm.alloc(sizeof(double) * (size_t)T * D * ld)) || (rc = pP.alloc(sizeof(double) * (size_t)T * D * D * ld)) ||
+        (rc = pC.alloc(sizeof(double) * (size_t)T * D * D * ld)))
+        return rc;
+    // a captured launch loop points into pm / pP / pC, which are released when this call returns - on every path
+    GraphDropGuard drop_on_exit;
+    rc = filter_forward_impl(h_dyn, f_dyn, h_obs, f_obs, B, ld, T, d_y, d_m0, d_P0, GQG, R, d_fm, d_fP, d_status,
+                             nullptr, 0.0, pm.d(), pP.d(), pC.d());
+    if (rc) return rc;
+    rc = launch_rts_backward(D, B, ld, T, d_fm, d_fP, pm.d(), pP.d(), pC.d(), d_sm, d_sP, d_status, stream(), D);
+    if (rc) {
+        hipStreamSynchronize(stream());
+        return rc;
+    }
+    SSMQ_HIP(hipStreamSynchronize(stream()));
+    return SSMQ_OK;
+}
+
+extern "C" int ssmq_student_filter_forward_dev(ssmq_transform *h_dyn, const ssmq_integrand *f_dyn,
+                                               ssmq_transform *h_obs, const ssmq_integrand *f_obs, int64_t B,
+                                               int64_t ld, int T, const double *d_y, const double *d_m0,
+                                               const double *d_S0, const double *GqG, const double *r_smat,
+                                               const double *scale, double dof, double *d_fm, double *d_fP,
+                                               int32_t *d_status) {
+    SSMQ_HANDLE_LOCK(h_dyn, h_obs);
+    if (!scale || !(dof > 0.0)) {
+        set_error("student_filter_forward: scale[T] and dof > 0 are required");
+        return SSMQ_E_ARG;
+    }
+    return filter_forward_impl(h_dyn, f_dyn, h_obs, f_obs, B, ld, T, d_y, d_m0, d_S0, GqG, r_smat, d_fm, d_fP, d_status,
+                               scale, dof);
+}
+
+extern "C" int ssmq_filter_kernel_name(const ssmq_transform *h_dyn, const ssmq_integrand *f_dyn,
+                                       const ssmq_transform *h_obs, const ssmq_integrand *f_obs, char *buf, int len) {
+    return ssmq_filter_kernel_name_batch(h_dyn, f_dyn, h_obs, f_obs, 0, buf, len);
+}
+
+extern "C" int ssmq_filter_kernel_name_batch(const ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, const ssmq_transform *h_obs,
+                                             const ssmq_integrand *f_obs, int64_t B, char *buf, int len) {
+    SSMQ_HANDLE_LOCK(h_dyn, h_obs);
+    if (!h_dyn || !h_obs || !f_dyn || !f_obs || !buf || len <= 0 || B < 0) return SSMQ_E_ARG;
+    FInfo fio;
+    if (!integrand_info(f_obs->id, &fio)) return SSMQ_E_ARG;
+    const char *name = nullptr;
+    int rc = ssmq::sw("SSMQ_NO_FUSED") && !is_user_integrand(f_dyn) && !is_user_integrand(f_obs)
+                 ? 0
+                 : try_launch_fused(h_dyn, f_dyn, h_obs, f_obs, sel_pattern(f_obs, fio.din), B, 0, 0,
+                                                        nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                                        nullptr, nullptr, &name, true, nullptr, 0.0, nullptr, nullptr);
+    if (rc < 0) return rc;
+    snprintf(buf, len, "%s", rc == 1 ? name : "hipGraph of 3 T launches (apply dyn | apply obs | k_kalman_update)");
+    return SSMQ_OK;
+}
+
+static int metrics_impl(int phase, int D, int64_t B, int64_t ld, int T, const double *d_x, const double *d_fm,
+                        const double *d_fP, const int32_t *d_status, const double *mse, double *sums) {
+    if (D < 1 || D > SSMQ_MAX_DIM || B < 0 || ld < B || T < 0 || !d_x || !d_fm || !d_fP || !sums || (phase == 2 && !mse)) {
+        set_error("error_sums: bad argument");
+        return SSMQ_E_ARG;
+    }
+    int rc = ensure_device();
+    if (rc) return rc;
+    const int NV = phase == 1 ? metrics_values_per_step(D) : 2;     // values per step handed back
+    const int NI = phase == 1 ? NV : 3;                             // ... and reduced on the device
+    if (T == 0) return SSMQ_OK;
+    if (B == 0) {
+        memset(sums, 0, sizeof(double) * (size_t)T * NV);
+        return SSMQ_OK;
+    }
+    hipStream_t s = stream();
+    DevBuf partial, out, dm;
+    if ((rc = partial.alloc(sizeof(double) * (size_t)T * metrics_chunks(B) * NI)) ||
+        (rc = out.alloc(sizeof(double) * (size_t)T * NI)) || (rc = dm.alloc(sizeof(double) * (size_t)T * D * D)))
+        return rc;
+    if (phase == 2) SSMQ_HIP(hipMemcpyAsync(dm.p, mse, sizeof(double) * (size_t)T * D * D, hipMemcpyHostToDevice, s));
+    rc = launch_metrics(phase, D, B, ld, T, d_x, d_fm, d_fP, d_status, dm.d(), partial.d(), out.d(), s);
+    if (rc) {
+        hipStreamSynchronize(s);
+        return rc;
+    }
+    std::vector<double> h((size_t)T * NI);
+    SSMQ_HIP(hipMemcpyAsync(h.data(), out.p, sizeof(double) * h.size(), hipMemcpyDeviceToHost, s));
+    SSMQ_HIP(hipStreamSynchronize(s));
+    // entries whose covariance is not positive definite were left out by the streaming kernels (they factor P): the
+    // reference's formulas do not need a positive-definite P (utils.py:143-148, 426-432) - a second pass adds them
+    const int i_ok = D + 2 + D * D, i_cnt = phase == 1 ? i_ok + 1 : 1, i_sum = phase == 1 ? D + 1 : 0;
+    bool left_out = false;
+    for (int t = 0; t < T && !left_out; ++t)
+        left_out = phase == 1 ? h[(size_t)t * NI + i_ok] > h[(size_t)t * NI + i_cnt] : h[(size_t)t * NI + 2] > 0.0;
+    if (left_out) {
+        rc = launch_metrics_indef(phase, D, B, ld, T, d_x, d_fm, d_fP, d_status, dm.d(), partial.d(), out.d(), s);
+        std::vector<double> extra((size_t)T * 2);
+        if (!rc) rc = hip_fail(hipMemcpyAsync(extra.data(), out.p, sizeof(double) * extra.size(), hipMemcpyDeviceToHost, s), "hipMemcpyAsync");
+        hipError_t e = hipStreamSynchronize(s);
+        if (rc) return rc;
+        SSMQ_HIP(e);
+        for (int t = 0; t < T; ++t) {
+            h[(size_t)t * NI + i_sum] += extra[(size_t)t * 2];
+            h[(size_t)t * NI + i_cnt] += extra[(size_t)t * 2 + 1];
+        }
+    }
+    for (int t = 0; t < T; ++t)
+        for (int v = 0; v < NV; ++v) sums[(size_t)t * NV + v] = h[(size_t)t * NI + v];
+    return SSMQ_OK;
+}
+
+extern "C" int ssmq_error_sums_width(int D) { return D >= 1 && D <= SSMQ_MAX_DIM ? metrics_values_per_step(D) : SSMQ_E_ARG; }
+
+extern "C" int ssmq_error_sums_dev(int D, int64_t B, int64_t ld, int T, const double *d_x, const double *d_fm,
+                                   const double *d_fP, const int32_t *d_status, double *sums) {
+    return metrics_impl(1, D, B, ld, T, d_x, d_fm, d_fP, d_status, nullptr, sums);
+}
+
+extern "C" int ssmq_lcr_sums_dev(int D, int64_t B, int64_t ld, int T, const double *d_x, const double *d_fm,
+                                 const double *d_fP, const int32_t *d_status, const double *mse, double *sums) {
+    return metrics_impl(2, D, B, ld, T, d_x, d_fm, d_fP, d_status, mse, sums);
+}
+
+extern "C" int ssmq_simulate_rv_dev(const ssmq_integrand *f_dyn, const ssmq_integrand *f_obs, int D, int Y, const ssmq_rv *x0,
+                                    const ssmq_rv *q, const ssmq_rv *r, const double *G, int dyn_additive, int obs_additive,
+                                    int64_t B, int64_t ld, int T, int continuous, double dt, uint64_t seed,
+                                    uint64_t traj_offset, double *d_x, double *d_y) {
+    if (is_user_integrand(f_dyn) || is_user_integrand(f_obs)) return refuse_user_integrand("ssmq_simulate_rv_dev");
+    const int mode = (f_dyn ? 1 : 0) | (f_obs ? 2 : 0);
+    auto rv_ok = [](const ssmq_rv *v, int dim) {
+        return v && v->dim == dim && v->chol && v->kind >= SSMQ_RV_GAUSS && v->kind <= SSMQ_RV_MIXTURE &&
+               (v->kind != SSMQ_RV_STUDENT || v->dof > 2.0) &&
+               (v->kind == SSMQ_RV_MIXTURE ? (v->n_comp >= 1 && v->n_comp <= 8 && v->alpha) : v->n_comp <= 1);
+    };
+    int dq = (f_dyn && q) ? q->dim : 0, dr = (f_obs && r) ? r->dim : 0;
+    if (!mode || D < 1 || D > SSMQ_MAX_DIM || B < 0 || ld < B || T < 0 || !d_x ||
+        (f_dyn && (!rv_ok(x0, D) || dq < 1 || dq > SSMQ_MAX_DIM || !rv_ok(q, dq))) ||
+        (f_obs && (!d_y || Y < 1 || Y > SSMQ_MAX_DIM || dr < 1 || dr > SSMQ_MAX_DIM || !rv_ok(r, dr))) ||
+        (continuous && (!f_dyn || !(dt > 0.0)))) {
+        set_error("simulate: bad argument");
+        return SSMQ_E_ARG;
+    }
+    if (!f_obs) Y = 0;
+    FInfo fid, fio;
+    if (f_dyn) {
+        const int in_dyn = D + (dyn_additive ? 0 : dq);
+        if (!integrand_info(f_dyn->id, &fid) || fid.dout != D || f_dyn->n_idx != 0 ||
+            (!continuous && (fid.din > in_dyn || in_dyn > kMaxIntegrandIn))) {
+            set_error("simulate: transition integrand / dimension mismatch (state + noise inputs: at most 16)");
+            return SSMQ_E_ARG;
+        }
+        if (continuous && !has_continuous_dynamics(f_dyn->id)) {
+            set_error("simulate: this model has no continuous-time dynamics (dyn_fcn_cont is defined for the reentry-1D, "
+                      "reentry-2D and constant-turn-rate-and-speed models only, ssmod.py:429-432, 569-585, 779-780)");
+            return SSMQ_E_UNSUPPORTED;
+        }
+        if (continuous && dq < (f_dyn->id == SSMQ_F_CTRS_DYN ? 1 : 3)) {
+            set_error("simulate: the continuous-time dynamics read three noise components");
+            return SSMQ_E_ARG;
+        }
+    }
+    if (f_obs) {
+        const int in_obs = D + (obs_additive ? 0 : dr);
+        if (!integrand_info(f_obs->id, &fio) || (fio.dout ? fio.dout : Y) != Y || (obs_additive && dr != Y) ||
+            f_obs->n_idx > SSMQ_MAX_FIDX || f_obs->n_idx < 0 || (f_obs->n_idx == 0 && (fio.din > in_obs || in_obs > kMaxIntegrandIn))) {
+            set_error("simulate: measurement integrand / dimension mismatch");
+            return SSMQ_E_ARG;
+        }
+        for (int k = 0; k < f_obs->n_idx; ++k)
+            if (f_obs->idx[k] < 0 || f_obs->idx[k] >= in_obs) {
+                set_error("simulate: measurement state index out of range");
+                return SSMQ_E_ARG;
+            }
+    }
+    int rc = ensure_device();
+    if (rc) return rc;
+    if (B == 0 || T == 0) return SSMQ_OK;
+    SimLaunch h;
+    memset(&h, 0, sizeof(h));
+    std::vector<double> hc;
+    auto put_rv = [&](const ssmq_rv *v, SimRv *out) {
+        out->off = (int)hc.size();
+        if (!v) {
+            out->kind = SSMQ_RV_GAUSS; out->dim = 0; out->ncomp = 1; out->dof = 0.0;
+            hc.push_back(1.0);
+            return;
+        }
+        const int nc = v->kind == SSMQ_RV_MIXTURE ? v->n_comp : 1, n = v->dim;
+        out->kind = v->kind; out->dim = n; out->ncomp = nc; out->dof = v->dof;
+        for (int k = 0; k < nc; ++k) hc.push_back(v->kind == SSMQ_RV_MIXTURE ? v->alpha[k] : 1.0);
+        for (int i = 0; i < nc * n; ++i) hc.push_back(v->mean ? v->mean[i] : 0.0);
+        for (int i = 0; i < nc * n * n; ++i) hc.push_back(v->chol[i]);
+    };
+    put_rv(f_dyn ? x0 : nullptr, &h.rv[0]);
+    put_rv(f_dyn ? q : nullptr, &h.rv[1]);
+    put_rv(f_obs ? r : nullptr, &h.rv[2]);
+    h.g_off = (int)hc.size();
+    for (int i = 0; i < D * dq; ++i)        // default noise gain eye(D, dq)  (ssmod.py:52)
+        hc.push_back(G ? G[i] : ((i / dq) == (i % dq) ? 1.0 : 0.0));
+    DevBuf dc;
+    if ((rc = dc.alloc(sizeof(double) * std::max<size_t>(hc.size(), 1)))) return rc;
+    hipStream_t s = stream();
+    SSMQ_HIP(hipMemcpyAsync(dc.p, hc.data(), sizeof(double) * hc.size(), hipMemcpyHostToDevice, s));
+    h.mode = mode; h.D = D; h.Y = Y; h.dq = dq; h.dr = dr; h.dyn_additive = dyn_additive; h.obs_additive = obs_additive; h.T = T;
+    h.continuous = continuous ? 1 : 0; h.dt = dt; h.B = B; h.ld = ld; h.seed = seed; h.traj_offset = traj_offset;
+    h.f_dyn = f_dyn; h.f_obs = f_obs; h.d_consts = dc.d(); h.d_x = d_x; h.d_y = d_y;
+    rc = launch_simulate(h, s);
+    hipError_t e = hipStreamSynchronize(s);
+    if (rc) return rc;
+    SSMQ_HIP(e);
+    return SSMQ_OK;
+}
+
+// the Gaussian case with plain arrays (the round-1 entry point)
+extern "C" int ssmq_simulate_dev(const ssmq_integrand *f_dyn, const ssmq_integrand *f_obs, int D, int Y, int dq, int dr,
+                                 int dyn_additive, int obs_additive, int64_t B, int64_t ld, int T,
+                                 const double *x0_mean, const double *x0_chol, const double *q_mean,
+                                 const double *q_chol, const double *G, const double *r_mean, const double *r_chol,
+                                 uint64_t seed, uint64_t traj_offset, double *d_x, double *d_y) {
+    if (is_user_integrand(f_dyn) || is_user_integrand(f_obs)) return refuse_user_integrand("ssmq_simulate_dev");
+    ssmq_rv x0{SSMQ_RV_GAUSS, D, 1, 0, 0.0, x0_mean, x0_chol, nullptr};
+    ssmq_rv q{SSMQ_RV_GAUSS, dq, 1, 0, 0.0, q_mean, q_chol, nullptr};
+    ssmq_rv r{SSMQ_RV_GAUSS, dr, 1, 0, 0.0, r_mean, r_chol, nullptr};
+    if (f_dyn && (!x0_mean || !x0_chol || !q_chol)) {
+        set_error("simulate: bad argument");
+        return SSMQ_E_ARG;
+    }
+    return ssmq_simulate_rv_dev(f_dyn, f_obs, D, Y, &x0, &q, &r, G, dyn_additive, obs_additive, B, ld, T, 0, 0.0, seed,
+                                traj_offset, d_x, d_y);
+}

@@ -1,6 +1,6 @@
 // Study-level entry points (round 6): several filters in one launch (ssmq_filter_forward_multi_dev) and the forward pass with host
-// arrays as a pipeline of time blocks (ssmq_filter_forward_piped, with its pooled page-locked blocks).  Split from ssmq_api.hip,
-// which holds the per-transform and per-filter entry points these build on.
+// arrays as a pipeline of time blocks (ssmq_filter_forward_piped, with its pooled page-locked blocks).  They build on the
+// per-transform and per-filter entry points of ssmq_api_transform.hip and ssmq_api_filter.hip.
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -19,18 +19,6 @@
 
 using namespace ssmq;
 
-int filter_forward_impl(ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, ssmq_transform *h_obs, const ssmq_integrand *f_obs, int64_t B,
-                        int64_t ld, int T, const double *d_y, const double *d_m0, const double *d_P0, const double *GQG, const double *R,
-                        double *d_fm, double *d_fP, int32_t *d_status, const double *sscale, double student_dof, double *d_pm,
-                        double *d_pP, double *d_pC);
-namespace ssmq {
-int sel_pattern(const ssmq_integrand *f, int din);
-int try_launch_fused(const ssmq_transform *hd, const ssmq_integrand *fd, const ssmq_transform *ho,
-                     const ssmq_integrand *fo, int sel_obs, int64_t B, int64_t ld, int T, const double *d_y,
-                     const double *d_m0, const double *d_P0, const double *d_gqg, const double *d_rr, double *d_fm,
-                     double *d_fP, int32_t *d_status, hipStream_t s, const char **name, bool dry_run,
-                     const double *d_sscale, double student_dof, const double *d_ttab_dyn, const double *d_ttab_obs);
-}
 #define g_stage (ssmq::stage_of_ctx())
 
 // ---- A independent filters as ONE launch (round 6) -------------------------------------------------------------------------
@@ -40,11 +28,6 @@ int try_launch_fused(const ssmq_transform *hd, const ssmq_integrand *fd, const s
 // forks into one branch per job inside a captured graph - each branch is the job's own fused time-loop kernel, so the RESULTS ARE
 // THE BITS of ssmq_filter_forward_dev / ssmq_student_filter_forward_dev - and joins again; a repeated call with the same jobs is one
 // hipGraphLaunch.  Jobs without a fused kernel run after the graph, one by one, through the ordinary path.
-namespace ssmq {
-int multi_family_table(int n, const ssmq_transform *const *hd, const ssmq_integrand *const *fd, const ssmq_transform *const *ho,
-                       const ssmq_integrand *const *fo, const FusedArgs *args, std::vector<char> *table, int *blocks);
-int multi_family_launch(const char *d_table, int blocks, hipStream_t s);
-}
 namespace {
 struct MultiCache {
     std::vector<hipStream_t> side;
@@ -318,13 +301,6 @@ extern "C" int ssmq_filter_forward_multi_dev(int n_jobs, const ssmq_filter_job *
 // ssmtoybox_amd hands out as the returned ndarrays) are written by the copy engine in the reference's (D, T, B) layout directly -
 // strided 2-D copies, no staging and no host-side memcpy of the 16 MB; pageable outputs go through the pinned staging block and a
 // pool of copy threads.
-namespace ssmq {
-int try_launch_range(const ssmq_transform *hd, const ssmq_integrand *fd, const ssmq_transform *ho, const ssmq_integrand *fo, int sel_obs,
-                     int64_t B, int64_t ld, int T, int kb, int ke, const double *d_y, const double *d_m0, const double *d_P0,
-                     const double *d_gqg, const double *d_rr, double *d_fm, double *d_fP, int32_t *d_status, double *hand, hipStream_t s,
-                     const char **name, bool dry_run, const double *d_ttab_dyn, const double *d_ttab_obs);
-size_t range_hand_doubles(int D);
-}
 namespace {
 // page-locked host blocks, pooled per process: hipHostMalloc of 16 MB costs milliseconds, a pooled block nothing
 struct PinnedPool {

@@ -475,7 +475,7 @@ hipError_t launch_tile_ks(const WideArgs &a, int64_t B, hipStream_t s) {
 
 }  // namespace
 
-size_t tile_lds_bytes(int D, int E, int N, bool tp) {
+static size_t tile_lds_bytes(int D, int E, int N, bool tp) {
     const TileGeom tg = tile_geom(D, E, N, tp);
     return sizeof(double) * ((size_t)tg.frag_doubles + (size_t)kTileWaves * tg.wave_doubles);
 }

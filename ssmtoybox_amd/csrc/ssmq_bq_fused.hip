@@ -508,7 +508,7 @@ bool bq_fused_supported(int D, int E, int N) {
     if (ssmq::sw("SSMQ_NO_BQ_FUSED")) return false;
     const int np = gemm_mfma_padded(N);
     if (np != 128 && np != 208) return false;
-    // D <= 15: column 15 of the Wcc' tile of X carries wm (ssmq_api.hip: upload of d_wcx_pad)
+    // D <= 15: column 15 of the Wcc' tile of X carries wm (ssmq_api_transform.hip: upload of d_wcx_pad)
     // E <= 10: no built-in integrand has more outputs (10-D model: 10; bearings: SSMQ_MAX_FPAR / 2 = 8 sensors), so nothing
     // beyond that could be tested
     if (D < 1 || D > 15 || E < 6 || E > 10 || !fxwc_cov_supported(E)) return false;

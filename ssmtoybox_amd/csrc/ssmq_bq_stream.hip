@@ -365,8 +365,8 @@ constexpr size_t kStreamLds = sizeof(double) * (8 * 4 * 64 * 8 + 8 * 64 * 4 + 25
 
 }  // namespace
 
-int bq_stream_panels(int N) { return (N + kPanW - 1) / kPanW; }
-int bq_stream_kblocks(int N) { return (N + 15) / 16; }
+static int bq_stream_panels(int N) { return (N + kPanW - 1) / kPanW; }
+static int bq_stream_kblocks(int N) { return (N + 15) / 16; }
 int bq_stream_tpw(int E) { return 64 / E; }
 
 // How many blocks of a batch run whole and how many - the last, partly empty round of workgroups on `cus` compute units - are

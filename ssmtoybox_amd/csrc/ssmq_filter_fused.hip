@@ -427,21 +427,6 @@ int try_launch_fused_aug(const ssmq_transform *hd, const ssmq_integrand *fd, con
     return 0;
 }
 
-int try_launch_wsplit(const ssmq_transform *hd, const ssmq_integrand *fd, const ssmq_transform *ho, const ssmq_integrand *fo,
-                      int sel_obs, int64_t B, int64_t ld, int T, const double *d_y, const double *d_m0, const double *d_P0,
-                      const double *d_gqg, const double *d_rr, double *d_fm, double *d_fP, int32_t *d_status, hipStream_t s,
-                      const char **name, bool dry_run, const double *d_sscale, double student_dof, int cus);
-
-int try_launch_quad(const ssmq_transform *hd, const ssmq_integrand *fd, const ssmq_transform *ho, const ssmq_integrand *fo, int sel_obs,
-                    int64_t B, int64_t ld, int T, const double *d_y, const double *d_m0, const double *d_P0, const double *d_gqg,
-                    const double *d_rr, double *d_fm, double *d_fP, int32_t *d_status, hipStream_t s, const char **name, bool dry_run,
-                    const double *d_sscale, double student_dof, int cus);
-
-// ... and for batches of the heavy shapes that do not fill the chip evenly, the time loop in chunks dealt from a queue
-// (ssmq_filter_chunked.hip)
-int try_launch_chunked(const FusedArgs &a0, int fd, int fo, int D, int Y, int ND, int NO, int form, int tp, int selo, int opt, int cus,
-                       hipStream_t s, bool dry_run, const char **name);
-
 // compute units of the library's device (the wave-split kernel is chosen by how many workgroups the device can spread out)
 static int device_cus() {
     static thread_local int cus = 0;

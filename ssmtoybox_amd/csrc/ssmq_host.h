@@ -48,8 +48,9 @@ void set_error(const std::string &msg);
 inline bool is_user_integrand(int id) { return id >= SSMQ_F_USER_FIRST && id < SSMQ_F_USER_FIRST + SSMQ_F_USER_SLOTS; }
 inline bool is_user_integrand(const ssmq_integrand *f) { return f && is_user_integrand(f->id); }
 int refuse_user_integrand(const char *what);   // sets the error text, returns SSMQ_E_UNSUPPORTED
-struct FusedArgs;
-struct ApplyArgs;
+struct FusedArgs;   // ssmq_fused.h
+struct ApplyArgs;   // ssmq_apply_small.h
+struct UpdArgs;     // ssmq_update.h
 // Whole-pass filter kernel k_filter_fused<> for a pair of models of which at least one is a user integrand: 1 launched (or, with
 // dry_run, the name set), < 0 error - never 0, so that no caller falls back to the launch loop.
 int rtc_launch_fused(const ssmq_transform *hd, const ssmq_integrand *fd, const ssmq_transform *ho, const ssmq_integrand *fo,
@@ -69,9 +70,11 @@ struct Ctx {
     hipStream_t stream = nullptr;
     int dev = -1;
     unsigned epoch = 0;                      // unique per (context, device binding): per-device function attributes, cached graphs
-    void *gemm_ws = nullptr;                 // scratch of the matrix-core routes (ssmq_api.hip)
+    void *gemm_ws = nullptr;                 // scratch of the matrix-core routes (ssmq_api_transform.hip)
     size_t gemm_ws_bytes = 0;
-    void *stage = nullptr, *fc = nullptr, *theta_graphs = nullptr;      // ssmq_api.hip: StagingArena, FilterCache, theta graphs
+    void *stage = nullptr;                   // ssmq_api_host.hip: StagingArena
+    void *fc = nullptr;                      // ssmq_api_filter.hip: FilterCache
+    void *theta_graphs = nullptr;            // ssmq_api_theta.hip: captured graphs of the theta-batched step
     void *pinned_flags = nullptr;            // 64 bytes of pinned host memory the device rounds report through (ssmq_marginal.hip)
     void *strip_buf = nullptr;               // flags + hand-over buffer of the strip schedule (ssmq_filter_chunked.hip), grow-only
     size_t strip_bytes = 0;
@@ -105,8 +108,18 @@ int ensure_device();
 // attributes (hipFuncAttributeMaxDynamicSharedMemorySize) are per device and are set again when a thread sees a new value
 // (the `static thread_local unsigned attr_epoch` of the launchers).
 unsigned device_epoch();
+// What the calling thread's context caches on ONE device, each piece dropped by the unit that owns it when the context binds to
+// another device (ssmq_api_runtime.hip: reset_device_caches, in this order).
+void drop_filter_cache();        // ssmq_api_filter.hip: workspace, constants and captured launch loop of the filter time loop
+void drop_theta_step_graphs();   // ssmq_api_theta.hip
+void drop_gemm_scratch();        // ssmq_api_transform.hip
+void drop_staging_arena();       // ssmq_api_host.hip
+void reset_wide_attributes();    // ssmq_apply_wide.hip: the dynamic-LDS limits are set again on the new device
+void drop_multi_cache();         // ssmq_api_study.hip
+void drop_pipe_cache();          // ssmq_api_study.hip
 
-// Device arena + pinned staging blocks of the host-buffer entry points (ssmq_api.hip, ssmq_api_study.hip): one per context.
+// Device arena + pinned staging blocks of the host-buffer entry points (ssmq_api_host.hip, ssmq_api_theta.hip,
+// ssmq_api_study.hip): one per context.
 struct StagingArena;
 StagingArena &stage_of_ctx();
 
@@ -160,9 +173,17 @@ struct StagingArena {
     }
 };
 
+// transform handles and the route selection of one transform (ssmq_api_transform.hip)
 void fill_fpar(const ssmq_integrand *f, FPar *fp);
+int sel_pattern(const ssmq_integrand *f, int din);   // 0: the integrand reads the leading entries, 1: (0, 2, 4, ...), -1: anything else
+int check_integrand(const ssmq_transform *h, const ssmq_integrand *f, FInfo *fi);
+constexpr int64_t kGemmMinRows = 256;                // rows B E from which a batch takes the matrix-core routes
+int apply_dev_impl(ssmq_transform *h, const ssmq_integrand *f, int64_t B, int64_t ld, const double *d_mean, const double *d_cov,
+                   const double *d_time, int time_stride, double *d_mean_f, double *d_cov_f, double *d_cov_fx, int32_t *d_status,
+                   const double *d_cov_add, const char **kernel_name, bool dry_run, double cov_scale = 1.0, double ccov_scale = 1.0,
+                   const double *ttab = nullptr, bool stream_out = true);
 
-// dispatch table of the register-resident kernels (ssmq_apply_small_*.hip)
+// dispatch table of the register-resident kernels (ssmq_small_*.hip)
 typedef hipError_t (*small_launch_fn)(const ApplyArgs &, hipStream_t);
 struct SmallEntry {
     int fid, D, E, N, form, tp, sel, opt;
@@ -170,6 +191,10 @@ struct SmallEntry {
     const char *name;
 };
 const SmallEntry *find_small(int fid, int D, int E, int N, int form, int tp, int sel, int opt);
+const SmallEntry *small_table_a(int *n);
+const SmallEntry *small_table_b(int *n);
+const SmallEntry *small_table_c(int *n);
+const SmallEntry *small_table_d(int *n);
 
 // batch GEMM fx Wc on the matrix cores (ssmq_gemm_mfma.hip)
 int gemm_mfma_padded(int N);
@@ -218,7 +243,7 @@ struct BigRest {
 };
 int launch_big_rest(const BigRest &r, int64_t B, hipStream_t s);
 
-// theta-batched step on items that are already on the device, their number read from device memory (ssmq_api.hip; used by the
+// theta-batched step on items that are already on the device, their number read from device memory (ssmq_api_theta.hip; used by the
 // device-resident rounds of ssmq_gp_marginal_filter_batch, ssmq_marginal.hip)
 struct ThetaDev {
     int Din, D, Y, Nd, No;
@@ -256,9 +281,89 @@ struct SimLaunch {
 int launch_simulate(const SimLaunch &h, hipStream_t s);
 bool has_continuous_dynamics(int fid);
 
-// measurement update (ssmq_filter.hip)
+// measurement update, moment augmentation, log-density and backward pass (ssmq_filter.hip)
 int launch_kalman_update(int D, int Y, int64_t B, int64_t ld, const double *m_pr, const double *P_pr,
                          const double *y_mean, const double *P_y, const double *P_yx, const double *y, double *m_fi,
                          double *P_fi, int32_t *status, hipStream_t s);
+int launch_kalman_update_ex(int D, int Y, int64_t B, int64_t ld, const double *m_pr, const double *P_pr, const double *y_mean,
+                            const double *P_y, const double *P_yx, const double *y, double *m_fi, double *P_fi, int32_t *status,
+                            const int32_t *st_a, const int32_t *st_b, int step, hipStream_t s, double student_dof, double *smat_out,
+                            int Dx);
+int launch_augment(const double *m, const double *P, const double *nmean, const double *ncov, double *ma, double *Pa, int D, int Dn,
+                   int64_t B, int64_t ld, hipStream_t s);
+int launch_gauss_logpdf(int Y, int64_t B, int64_t ld, const double *y, const double *y_mean, const double *P_y, double *out,
+                        hipStream_t s, const int32_t *merge = nullptr, int32_t *merge_out = nullptr);
+int launch_rts_backward(int D, int64_t B, int64_t ld, int T, const double *fm, const double *fP, const double *pm, const double *pP,
+                        const double *pC, double *sm, double *sP, int32_t *status, hipStream_t s, int c_cols);
+
+// the filter time loop of the entry points (ssmq_api_filter.hip).  sscale (host, [T]) / student_dof: Studentian recursion, null / 0
+// for the Gaussian filters; d_pm / d_pP / d_pC (all or none): the predictive moments of every step are kept for a backward pass.
+int filter_forward_impl(ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, ssmq_transform *h_obs, const ssmq_integrand *f_obs,
+                        int64_t B, int64_t ld, int T, const double *d_y, const double *d_m0, const double *d_P0, const double *GQG,
+                        const double *R, double *d_fm, double *d_fP, int32_t *d_status, const double *sscale, double student_dof,
+                        double *d_pm = nullptr, double *d_pP = nullptr, double *d_pC = nullptr);
+
+// the whole time loop in one kernel: 1 launched (dry_run: a kernel exists, its name set), 0 no kernel for this combination, < 0 error
+// (ssmq_filter_fused.hip, which tries the schedules of ssmq_filter_wsplit.hip, ssmq_filter_quad.hip and ssmq_filter_chunked.hip)
+int try_launch_fused(const ssmq_transform *hd, const ssmq_integrand *fd, const ssmq_transform *ho, const ssmq_integrand *fo,
+                     int sel_obs, int64_t B, int64_t ld, int T, const double *d_y, const double *d_m0, const double *d_P0,
+                     const double *d_gqg, const double *d_rr, double *d_fm, double *d_fP, int32_t *d_status, hipStream_t s,
+                     const char **name, bool dry_run, const double *d_sscale, double student_dof, const double *d_ttab_dyn,
+                     const double *d_ttab_obs);
+int try_launch_fused_aug(const ssmq_transform *hd, const ssmq_integrand *fd, const ssmq_transform *ho, const ssmq_integrand *fo,
+                         int sel_obs, int D, int dq, int dr, int64_t B, int64_t ld, int T, const double *d_y, const double *d_m0,
+                         const double *d_P0, const double *d_add_dyn, const double *d_add_obs, const double *d_noise, double *d_fm,
+                         double *d_fP, int32_t *d_status, hipStream_t s, const char **name, bool dry_run, const double *d_ttab_dyn,
+                         const double *d_ttab_obs, double *d_pm, double *d_pP, double *d_pC);
+int try_launch_wsplit(const ssmq_transform *hd, const ssmq_integrand *fd, const ssmq_transform *ho, const ssmq_integrand *fo,
+                      int sel_obs, int64_t B, int64_t ld, int T, const double *d_y, const double *d_m0, const double *d_P0,
+                      const double *d_gqg, const double *d_rr, double *d_fm, double *d_fP, int32_t *d_status, hipStream_t s,
+                      const char **name, bool dry_run, const double *d_sscale, double student_dof, int cus);
+int try_launch_quad(const ssmq_transform *hd, const ssmq_integrand *fd, const ssmq_transform *ho, const ssmq_integrand *fo, int sel_obs,
+                    int64_t B, int64_t ld, int T, const double *d_y, const double *d_m0, const double *d_P0, const double *d_gqg,
+                    const double *d_rr, double *d_fm, double *d_fP, int32_t *d_status, hipStream_t s, const char **name, bool dry_run,
+                    const double *d_sscale, double student_dof, int cus);
+int try_launch_chunked(const FusedArgs &a0, int fd, int fo, int D, int Y, int ND, int NO, int form, int tp, int selo, int opt, int cus,
+                       hipStream_t s, bool dry_run, const char **name);
+// ... several filters of one model family as one launch (ssmq_filter_fused.hip; ssmq_filter_forward_multi_dev)
+int multi_family_table(int n, const ssmq_transform *const *hd, const ssmq_integrand *const *fd, const ssmq_transform *const *ho,
+                       const ssmq_integrand *const *fo, const FusedArgs *args, std::vector<char> *table, int *blocks);
+int multi_family_launch(const char *table, int blocks, hipStream_t s);
+// ... and the steps [kb, ke) of every trajectory (ssmq_filter_piped.hip; ssmq_filter_forward_piped)
+int try_launch_range(const ssmq_transform *hd, const ssmq_integrand *fd, const ssmq_transform *ho, const ssmq_integrand *fo, int sel_obs,
+                     int64_t B, int64_t ld, int T, int kb, int ke, const double *d_y, const double *d_m0, const double *d_P0,
+                     const double *d_gqg, const double *d_rr, double *d_fm, double *d_fP, int32_t *d_status, double *hand, hipStream_t s,
+                     const char **name, bool dry_run, const double *d_ttab_dyn, const double *d_ttab_obs);
+size_t range_hand_doubles(int D);
+
+// error sums over a batch of filtered trajectories (ssmq_metrics.hip)
+int metrics_values_per_step(int D);
+int metrics_chunks(int64_t B);
+int launch_metrics(int phase, int D, int64_t B, int64_t ld, int T, const double *x, const double *fm, const double *fP,
+                   const int32_t *status, const double *mse, double *partial, double *out, hipStream_t s);
+int launch_metrics_indef(int phase, int D, int64_t B, int64_t ld, int T, const double *x, const double *fm, const double *fP,
+                         const int32_t *status, const double *mse, double *partial, double *out, hipStream_t s);
+
+// the stages of the theta-batched step (ssmq_api_theta.hip): GP weights of every item as its own constant block
+// (ssmq_weights.hip) ...
+size_t gp_weights_wide_ws_bytes(int D, int N, int64_t P);
+int gp_weights_wide_consts(int D, int E, int N, const double *d_xi, const double *d_par, int P, double jitter, double *d_consts,
+                           int32_t *d_status, void *ws, size_t ws_bytes);
+// ... or the two-launch route: both transforms' weights (ssmq_weights.hip: k_theta_weights), then transform -> transform -> update
+// -> log-likelihood by the wave that owns the item (ssmq_apply_wide.hip: k_theta_chain) ...
+bool gp_theta_weights_fits(int D0, int N0, int D1, int N1);
+int gp_theta_weights_pair(const int D[2], const int E[2], const int N[2], const double *const d_xi[2], const double *const d_par[2],
+                          int P, double jitter, double *const d_consts[2], int32_t *const d_status[2],
+                          const int32_t *d_count = nullptr);
+bool theta_chain_supported(int Din, int D, int Y, int Nd, int No);
+hipError_t launch_theta_chain(const WideArgs &dyn, const WideArgs &obs, const UpdArgs &upd, const double *y, double *loglik,
+                              const int32_t *merge, int32_t *merge_out, int64_t B, hipStream_t s, const int32_t *d_count = nullptr);
+// ... and for the small systems one lane per item, everything in registers (ssmq_theta_item.hip)
+bool theta_item_supported(int Din, int D, int Y, int Nd, int No);
+int launch_theta_item(int Din, int D, int Y, int Nd, int No, const ssmq_integrand *f_dyn, const ssmq_integrand *f_obs, int emv_dyn,
+                      int emv_obs, const double *xid, const double *xio, const double *pard, const double *paro, const double *mean,
+                      const double *cov, int64_t bs_mean, int64_t bs_cov, const double *ysoa, const double *time, int time_stride,
+                      const double *gq, const double *rr, double jitter, double *m_fi, double *P_fi, double *ll, int32_t *st_all,
+                      int64_t ld, int64_t bound, const int32_t *d_count, hipStream_t s);
 
 }  // namespace ssmq

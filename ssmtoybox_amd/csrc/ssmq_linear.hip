@@ -93,7 +93,7 @@ __global__ __launch_bounds__(256) void k_linearize(const LinArgs a) {
     a.status[b] = 0;
 }
 
-// D, E: the transform's; din: the integrand's own input count (ssmq_api.hip: FInfo)
+// D, E: the transform's; din: the integrand's own input count (ssmq_api_transform.hip: check_integrand, FInfo)
 int launch_linearize(int D, int E, int din, const ssmq_integrand *f, const FPar &fp, int64_t B, int64_t ld, const double *d_mean,
                      const double *d_cov, const double *d_time, int time_stride, double *d_mean_f, double *d_cov_f, double *d_cov_fx,
                      int32_t *d_status, const double *d_cov_add, double cov_scale, double ccov_scale, hipStream_t s) {

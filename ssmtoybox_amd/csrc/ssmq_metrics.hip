@@ -455,7 +455,6 @@ hipError_t launch_phase(const MetArgs &a, int phase, hipStream_t s) {
 
 }  // namespace
 
-int metrics_chunks(int64_t B);
 
 // second pass over the entries whose covariance is not positive definite: d_out [T][2] = term sum | count
 int launch_metrics_indef(int phase, int D, int64_t B, int64_t ld, int T, const double *x, const double *fm, const double *fP,

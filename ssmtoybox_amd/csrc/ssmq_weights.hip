@@ -493,7 +493,7 @@ __global__ __launch_bounds__(256) void k_wb_gemm(double *__restrict__ Cb, int64_
         }
 }
 
-__device__ double block_sum(double v, double *red) {
+static __device__ double block_sum(double v, double *red) {
     // all threads of the block -> one value (to every thread); waves added in index order
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
@@ -513,7 +513,7 @@ struct WgtOut {
     int32_t *status;
 };
 
-__device__ void weights_body(const WgtArgs &a, const WgtOut &o, int p, double *lds) {
+static __device__ void weights_body(const WgtArgs &a, const WgtOut &o, int p, double *lds) {
     __shared__ double s_sil[SSMQ_MAX_DIM], s_red[16];
     __shared__ int s_flag, s_piv;
     const int D = a.D, N = a.N, NB = a.NB, tid = threadIdx.x;
