@@ -88,10 +88,11 @@ void drop_filter_cache() {
 
 // A pair of models of which one or both are user-defined integrands: the whole-pass kernel compiled for them at run time
 // (ssmq_rtc.hip) with the time loop's constants in a small per-context block of its own, or an error - never the launch loop.
-static int filter_forward_user(ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, ssmq_transform *h_obs, const ssmq_integrand *f_obs,
-                               int64_t B, int64_t ld, int T, const double *d_y, const double *d_m0, const double *d_P0,
-                               const double *GQG, const double *R, double *d_fm, double *d_fP, int32_t *d_status,
-                               const double *sscale, double student_dof, hipStream_t s) {
+static int filter_forward_user(FilterPass p, const double *GQG, const double *R, const double *sscale) {
+    const ssmq_transform *h_dyn = p.hd, *h_obs = p.ho;
+    const ssmq_integrand *f_dyn = p.fd, *f_obs = p.fo;
+    const int T = p.T;
+    hipStream_t s = p.s;
     const int D = h_dyn->D, Y = h_obs->E;
     FInfo fio, fid;
     if (!integrand_info(f_obs->id, &fio) || !integrand_info(f_dyn->id, &fid)) {
@@ -124,17 +125,11 @@ static int filter_forward_user(ssmq_transform *h_dyn, const ssmq_integrand *f_dy
         SSMQ_HIP(hipStreamSynchronize(s));
         g_fc.user_host = h;
     }
-    FusedArgs a;
-    memset(&a, 0, sizeof(a));
-    a.y = d_y; a.m0 = d_m0; a.P0 = d_P0; a.fm = d_fm; a.fP = d_fP; a.status = d_status;
-    a.c_dyn = h_dyn->d_small; a.c_obs = h_obs->d_small; a.gqg = w; a.rr = w + D * D; a.B = B; a.ld = ld; a.T = T;
-    a.emv_dyn = h_dyn->emv_mode; a.emv_obs = h_obs->emv_mode; a.nu_dyn = h_dyn->tp_nu; a.nu_obs = h_obs->tp_nu;
-    a.sscale = sscale ? w + D * D + Y * Y : nullptr; a.student_dof = student_dof; a.lpw = 64;
-    fill_fpar(f_dyn, &a.fd);
-    fill_fpar(f_obs, &a.fo);
-    a.fd.ttab = has_td ? w + o_td : nullptr;
-    a.fo.ttab = has_to ? w + o_to : nullptr;
-    const int rc = rtc_launch_fused(h_dyn, f_dyn, h_obs, f_obs, sel_pattern(f_obs, fio.din), a, s, nullptr, false);
+    p.sel_obs = sel_pattern(f_obs, fio.din);
+    p.gqg = w; p.rr = w + D * D; p.sscale = sscale ? w + D * D + Y * Y : nullptr;
+    p.ttab_dyn = has_td ? w + o_td : nullptr;
+    p.ttab_obs = has_to ? w + o_to : nullptr;
+    const int rc = rtc_launch_fused(p);
     return rc < 0 ? rc : SSMQ_OK;
 }
 
@@ -165,8 +160,12 @@ int filter_forward_impl(ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, ssmq
         return SSMQ_OK;
     }
     hipStream_t s = stream();
-    if (user) return filter_forward_user(h_dyn, f_dyn, h_obs, f_obs, B, ld, T, d_y, d_m0, d_P0, GQG, R, d_fm, d_fP, d_status, sscale,
-                                         student_dof, s);
+    // the pass as the fused launchers take it; each route below adds the constants it has uploaded
+    FilterPass pass;
+    pass.hd = h_dyn; pass.fd = f_dyn; pass.ho = h_obs; pass.fo = f_obs;
+    pass.B = B; pass.ld = ld; pass.T = T; pass.y = d_y; pass.m0 = d_m0; pass.P0 = d_P0; pass.fm = d_fm; pass.fP = d_fP;
+    pass.status = d_status; pass.student_dof = student_dof; pass.s = s;
+    if (user) return filter_forward_user(pass, GQG, R, sscale);
     // workspace carve-up (doubles first, then the two int32 status planes)
     const size_t n_dbl = (size_t)ld * (D + 3 * D * D + Y + Y * Y + Y * D) + 4 * (size_t)T + D * D + Y * Y;
     const size_t need = sizeof(double) * n_dbl + 2 * sizeof(int32_t) * (size_t)ld;
@@ -256,9 +255,10 @@ int filter_forward_impl(ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, ssmq
             set_error("unknown integrand id");
             return SSMQ_E_ARG;
         }
-        rc = try_launch_fused(h_dyn, f_dyn, h_obs, f_obs, sel_pattern(f_obs, fio.din), B, ld, T, d_y, d_m0, d_P0, gqg,
-                              rr, d_fm, d_fP, d_status, s, nullptr, false, sscale ? svec : nullptr, student_dof,
-                              has_td ? ttab_d : nullptr, has_to ? ttab_o : nullptr);
+        pass.sel_obs = sel_pattern(f_obs, fio.din);
+        pass.gqg = gqg; pass.rr = rr; pass.sscale = sscale ? svec : nullptr;
+        pass.ttab_dyn = has_td ? ttab_d : nullptr; pass.ttab_obs = has_to ? ttab_o : nullptr;
+        rc = try_launch_fused(pass);
         if (rc < 0) return rc;
         if (rc == 1) return SSMQ_OK;
     }
@@ -269,9 +269,9 @@ int filter_forward_impl(ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, ssmq
             set_error("unknown integrand id");
             return SSMQ_E_ARG;
         }
-        rc = try_launch_fused_aug(h_dyn, f_dyn, h_obs, f_obs, sel_pattern(f_obs, fio.din), D, 0, 0, B, ld, T, d_y, d_m0, d_P0,
-                                  gqg, rr, gqg, d_fm, d_fP, d_status, s, nullptr, false, has_td ? ttab_d : nullptr,
-                                  has_to ? ttab_o : nullptr, d_pm, d_pP, d_pC);
+        pass.sel_obs = sel_pattern(f_obs, fio.din);
+        pass.ttab_dyn = has_td ? ttab_d : nullptr; pass.ttab_obs = has_to ? ttab_o : nullptr;
+        rc = try_launch_fused_aug(pass, AugExtras{D, 0, 0, gqg, rr, gqg, d_pm, d_pP, d_pC});    // (no noise inputs: the block is not read)
         if (rc < 0) return rc;
         if (rc == 1) return SSMQ_OK;
     }
@@ -404,9 +404,11 @@ static int filter_forward_aug_impl(ssmq_transform *h_dyn, const ssmq_integrand *
         if ((rc = dn.alloc(sizeof(double) * hn.size())) || (rc = da.alloc(sizeof(double) * ha.size()))) return rc;
         SSMQ_HIP(hipMemcpyAsync(dn.p, hn.data(), sizeof(double) * hn.size(), hipMemcpyHostToDevice, s));
         SSMQ_HIP(hipMemcpyAsync(da.p, ha.data(), sizeof(double) * ha.size(), hipMemcpyHostToDevice, s));
-        rc = try_launch_fused_aug(h_dyn, f_dyn, h_obs, f_obs, sel_pattern(f_obs, fio.din), D, dq, dr, B, ld, T, d_y, d_m0,
-                                  d_P0, da.d(), da.d() + (size_t)D * D, dn.d(), d_fm, d_fP, d_status, s, nullptr, false,
-                                  has_td ? ttab_d : nullptr, has_to ? ttab_o : nullptr, d_pm, d_pP, d_pC);
+        FilterPass pass;
+        pass.hd = h_dyn; pass.fd = f_dyn; pass.ho = h_obs; pass.fo = f_obs; pass.sel_obs = sel_pattern(f_obs, fio.din);
+        pass.B = B; pass.ld = ld; pass.T = T; pass.y = d_y; pass.m0 = d_m0; pass.P0 = d_P0; pass.fm = d_fm; pass.fP = d_fP;
+        pass.status = d_status; pass.ttab_dyn = has_td ? ttab_d : nullptr; pass.ttab_obs = has_to ? ttab_o : nullptr; pass.s = s;
+        rc = try_launch_fused_aug(pass, AugExtras{D, dq, dr, da.d(), da.d() + (size_t)D * D, dn.d(), d_pm, d_pP, d_pC});
         hipError_t e = hipStreamSynchronize(s);
         if (rc < 0) return rc;
         SSMQ_HIP(e);
@@ -603,11 +605,10 @@ extern "C" int ssmq_filter_kernel_name_batch(const ssmq_transform *h_dyn, const 
     FInfo fio;
     if (!integrand_info(f_obs->id, &fio)) return SSMQ_E_ARG;
     const char *name = nullptr;
-    int rc = ssmq::sw("SSMQ_NO_FUSED") && !is_user_integrand(f_dyn) && !is_user_integrand(f_obs)
-                 ? 0
-                 : try_launch_fused(h_dyn, f_dyn, h_obs, f_obs, sel_pattern(f_obs, fio.din), B, 0, 0,
-                                                        nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                                        nullptr, nullptr, &name, true, nullptr, 0.0, nullptr, nullptr);
+    FilterPass query;
+    query.hd = h_dyn; query.fd = f_dyn; query.ho = h_obs; query.fo = f_obs; query.sel_obs = sel_pattern(f_obs, fio.din); query.B = B;
+    query.name = &name; query.dry_run = true;
+    int rc = ssmq::sw("SSMQ_NO_FUSED") && !is_user_integrand(f_dyn) && !is_user_integrand(f_obs) ? 0 : try_launch_fused(query);
     if (rc < 0) return rc;
     snprintf(buf, len, "%s", rc == 1 ? name : "hipGraph of 3 T launches (apply dyn | apply obs | k_kalman_update)");
     return SSMQ_OK;

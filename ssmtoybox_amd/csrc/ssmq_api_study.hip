@@ -200,7 +200,7 @@ extern "C" int ssmq_filter_forward_multi_dev(int n_jobs, const ssmq_filter_job *
     if (!mc.fork) SSMQ_HIP(hipEventCreateWithFlags(&mc.fork, hipEventDisableTiming));
     // ---- which jobs have a fused kernel (dry run), then the fork / launch / join sequence, captured unless told otherwise -------
     mc.fused.assign(n_jobs, 0);
-    std::vector<int> sel(n_jobs, -1);
+    std::vector<FilterPass> pass(n_jobs);
     const bool no_fused = ssmq::sw("SSMQ_NO_FUSED") != nullptr;
     for (int i = 0; i < n_jobs && !no_fused; ++i) {
         const ssmq_filter_job &j = jobs[i];
@@ -209,10 +209,15 @@ extern "C" int ssmq_filter_forward_multi_dev(int n_jobs, const ssmq_filter_job *
             set_error("unknown integrand id");
             return SSMQ_E_ARG;
         }
-        sel[i] = sel_pattern(j.f_obs, fio.din);
+        FilterPass &p = pass[i];
+        p.hd = j.h_dyn; p.fd = j.f_dyn; p.ho = j.h_obs; p.fo = j.f_obs; p.sel_obs = sel_pattern(j.f_obs, fio.din);
+        p.B = j.B; p.ld = j.ld; p.T = j.T; p.y = j.d_y; p.m0 = j.d_m0; p.P0 = j.d_P0; p.fm = j.d_fm; p.fP = j.d_fP; p.status = j.d_status;
+        p.gqg = jc[i].gqg; p.rr = jc[i].rr; p.sscale = jc[i].svec; p.student_dof = j.dof; p.ttab_dyn = jc[i].ttd; p.ttab_obs = jc[i].tto;
         if (j.B == 0 || j.T == 0) continue;
-        const int r = try_launch_fused(j.h_dyn, j.f_dyn, j.h_obs, j.f_obs, sel[i], 0, j.ld, j.T, j.d_y, j.d_m0, j.d_P0, jc[i].gqg, jc[i].rr, j.d_fm,
-                                       j.d_fP, j.d_status, s, nullptr, true, jc[i].svec, j.dof, jc[i].ttd, jc[i].tto);
+        FilterPass query = p;
+        query.B = 0;                 // (whatever the batch: the whole-pass kernel, not a schedule for small or uneven batches)
+        query.s = s; query.dry_run = true;
+        const int r = try_launch_fused(query);
         if (r < 0) return r;
         mc.fused[i] = r == 1;
     }
@@ -225,16 +230,7 @@ extern "C" int ssmq_filter_forward_multi_dev(int n_jobs, const ssmq_filter_job *
         std::vector<const ssmq_integrand *> vfd(n_jobs), vfo(n_jobs);
         for (int i = 0; i < n_jobs; ++i) {
             const ssmq_filter_job &j = jobs[i];
-            FusedArgs &a = fa[i];
-            memset(&a, 0, sizeof(a));
-            a.y = j.d_y; a.m0 = j.d_m0; a.P0 = j.d_P0; a.fm = j.d_fm; a.fP = j.d_fP; a.status = j.d_status;
-            a.c_dyn = j.h_dyn->d_small; a.c_obs = j.h_obs->d_small; a.gqg = jc[i].gqg; a.rr = jc[i].rr; a.B = j.B; a.ld = j.ld; a.T = j.T;
-            a.emv_dyn = j.h_dyn->emv_mode; a.emv_obs = j.h_obs->emv_mode; a.nu_dyn = j.h_dyn->tp_nu; a.nu_obs = j.h_obs->tp_nu;
-            a.sscale = jc[i].svec; a.student_dof = j.dof; a.lpw = 64;
-            fill_fpar(j.f_dyn, &a.fd);
-            fill_fpar(j.f_obs, &a.fo);
-            a.fd.ttab = jc[i].ttd;
-            a.fo.ttab = jc[i].tto;
+            fa[i] = fused_args(pass[i]);
             vhd[i] = j.h_dyn; vho[i] = j.h_obs; vfd[i] = j.f_dyn; vfo[i] = j.f_obs;
         }
         std::vector<char> table;
@@ -265,8 +261,8 @@ extern "C" int ssmq_filter_forward_multi_dev(int n_jobs, const ssmq_filter_job *
             hipStream_t bs = mc.side[b];
             rc = hip_fail(hipStreamWaitEvent(bs, mc.fork, 0), "hipStreamWaitEvent");
             if (!rc) {
-                const int r = try_launch_fused(j.h_dyn, j.f_dyn, j.h_obs, j.f_obs, sel[i], j.B, j.ld, j.T, j.d_y, j.d_m0, j.d_P0, jc[i].gqg, jc[i].rr,
-                                               j.d_fm, j.d_fP, j.d_status, bs, nullptr, false, jc[i].svec, j.dof, jc[i].ttd, jc[i].tto);
+                pass[i].s = bs;
+                const int r = try_launch_fused(pass[i]);
                 rc = r < 0 ? r : (r == 1 ? 0 : SSMQ_E_UNSUPPORTED);
             }
             if (!rc) rc = hip_fail(hipEventRecord(mc.joined[b], bs), "hipEventRecord");
@@ -501,13 +497,14 @@ extern "C" int ssmq_filter_forward_piped(ssmq_transform *h_dyn, const ssmq_integ
         set_error("unknown integrand id");
         return SSMQ_E_ARG;
     }
-    const int sel = sel_pattern(f_obs, fio.din);
-    const char *kname = nullptr;
+    FilterPass pass, query;
+    pass.hd = h_dyn; pass.fd = f_dyn; pass.ho = h_obs; pass.fo = f_obs; pass.sel_obs = sel_pattern(f_obs, fio.din); pass.B = B; pass.T = T;
+    query = pass;
+    query.dry_run = true;
     // (a forced route - wave split, quad, strips, lanes per wave - means the caller wants THAT kernel: not pipelined)
     if (ssmq::sw("SSMQ_NO_FUSED") || ssmq::sw("SSMQ_NO_PIPED") || ssmq::sw("SSMQ_FUSED_WSPLIT") || ssmq::sw("SSMQ_FUSED_QUAD") ||
         ssmq::sw("SSMQ_FUSED_CHUNKED") || ssmq::sw("SSMQ_FUSED_LPW") ||
-        try_launch_range(h_dyn, f_dyn, h_obs, f_obs, sel, B, 0, T, 0, T, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                         nullptr, &kname, true, nullptr, nullptr) != 1) {
+        try_launch_range(query, 0, T, nullptr) != 1) {
         set_error("filter_forward_piped: no time-block kernel for this (models, shapes, form) combination");
         return SSMQ_E_UNSUPPORTED;
     }
@@ -573,7 +570,9 @@ extern "C" int ssmq_filter_forward_piped(ssmq_transform *h_dyn, const ssmq_integ
         for (int i = 0; i < D * D; ++i) std::fill(h_P0 + (size_t)i * ld, h_P0 + (size_t)(i + 1) * ld, P0[i]);
     }
     SSMQ_HIP(hipMemcpyAsync(d_m0, h_m0, sizeof(double) * (n_m + n_P + n_c), hipMemcpyHostToDevice, pc.s_in));      // m0 | P0 | consts are adjacent
-    const double *dc_gqg = d_c, *dc_rr = d_c + D * D, *dc_ttd = has_td ? d_c + D * D + Y * Y : nullptr, *dc_tto = has_to ? d_c + D * D + Y * Y + T : nullptr;
+    pass.ld = ld; pass.y = d_y; pass.m0 = d_m0; pass.P0 = d_P0; pass.fm = d_fm; pass.fP = d_fP; pass.status = d_st;
+    pass.gqg = d_c; pass.rr = d_c + D * D; pass.ttab_dyn = has_td ? d_c + D * D + Y * Y : nullptr;
+    pass.ttab_obs = has_to ? d_c + D * D + Y * Y + T : nullptr; pass.s = s;
     auto drain = [&](int k) -> int {        // block k's outputs are in host memory: bring them into the caller's arrays if staged
         SSMQ_HIP(hipEventSynchronize(pc.ev_out[k]));
         if (!out_pinned) {
@@ -590,8 +589,7 @@ extern "C" int ssmq_filter_forward_piped(ssmq_transform *h_dyn, const ssmq_integ
         SSMQ_HIP(hipMemcpyAsync(d_y + (size_t)kb * Y * ld, h_y + (size_t)kb * Y * ld, sizeof(double) * (size_t)(ke - kb) * Y * ld, hipMemcpyHostToDevice, pc.s_in));
         SSMQ_HIP(hipEventRecord(pc.ev_in[k], pc.s_in));
         SSMQ_HIP(hipStreamWaitEvent(s, pc.ev_in[k], 0));
-        rc = try_launch_range(h_dyn, f_dyn, h_obs, f_obs, sel, B, ld, T, kb, ke, d_y, d_m0, d_P0, dc_gqg, dc_rr, d_fm, d_fP, d_st, d_hand, s, nullptr, false,
-                              dc_ttd, dc_tto);
+        rc = try_launch_range(pass, kb, ke, d_hand);
         if (rc != 1) return rc < 0 ? rc : SSMQ_E_UNSUPPORTED;
         SSMQ_HIP(hipEventRecord(pc.ev_run[k], s));
         SSMQ_HIP(hipStreamWaitEvent(pc.s_out, pc.ev_run[k], 0));

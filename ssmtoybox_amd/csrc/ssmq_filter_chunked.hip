@@ -36,6 +36,7 @@
 //     hundreds of hand-overs per launch, bitwise against the whole pass).
 //   * Every wait is bounded (~seconds; then the block's trajectories are marked failed at step 0) although none is ever long.
 #include "ssmq_filter_fused_kernel.h"
+#include "ssmq_filter_shapes.h"
 
 namespace ssmq {
 namespace {
@@ -105,31 +106,21 @@ __global__ __launch_bounds__(kSmallBlock, (D >= 6 ? 1 : ((D >= 5 && FORM == SSMQ
 
 typedef void (*chunked_kernel)(const FusedArgs);
 struct ChunkedEntry {
-    int fd, fo, D, Y, ND, NO, form, tp, selo, opt;
+    FilterShape shape;
     chunked_kernel k;
     const char *name;
 };
-#define SSMQ_CH_ONE(FD, FO, D, Y, N, FORM, TP, SELO, OPT)                                                  \
-    {FD, FO, D, Y, N, N, FORM, TP, SELO, OPT, &k_filter_chunked<D, Y, N, N, FD, FO, FORM, TP, SELO, OPT, (D == 1 ? 0 : -1)>, \
+#define SSMQ_CH_ONE(FD, FO, D, Y, N, FORM, TP, SELO, OPT)                                                                    \
+    {{FD, FO, D, Y, N, N, FORM, TP, SELO, OPT}, &k_filter_chunked<D, Y, N, N, FD, FO, FORM, TP, SELO, OPT, (D == 1 ? 0 : -1)>, \
      "k_filter_chunked<D=" #D ",Y=" #Y ",ND=" #N ",NO=" #N "," #FD "," #FO "," #FORM ",TP=" #TP ",SELO=" #SELO ",OPT=" #OPT ">"}
-// the shapes of ssmq_filter_fused.hip's table with five or six states (2 000+ vector instructions per step: one wave keeps a SIMD's
-// issue port busy by itself); unscented and spherical-radial point sets
-#define SSMQ_CH(FD, FO, D, Y, N, SELO)                                  \
-    SSMQ_CH_ONE(FD, FO, D, Y, N, SSMQ_FORM_BQ, 0, SELO, 0), SSMQ_CH_ONE(FD, FO, D, Y, N, SSMQ_FORM_BQ, 1, SELO, 0), \
-    SSMQ_CH_ONE(FD, FO, D, Y, N, SSMQ_FORM_SIGMA, 0, SELO, 0)
-#define SSMQ_CH_FAST(FD, FO, D, Y, N, SELO)                             \
-    SSMQ_CH(FD, FO, D, Y, N, SELO), SSMQ_CH_ONE(FD, FO, D, Y, N, SSMQ_FORM_BQ, 0, SELO, 7), SSMQ_CH_ONE(FD, FO, D, Y, N, SSMQ_FORM_BQ, 0, SELO, 3), SSMQ_CH_ONE(FD, FO, D, Y, N, SSMQ_FORM_BQ, 1, SELO, 2), \
-    SSMQ_CH_ONE(FD, FO, D, Y, N, SSMQ_FORM_SIGMA, 0, SELO, 2)
+// the shapes with five or six states (2 000+ vector instructions per step: one wave keeps a SIMD's issue port busy by itself);
+// unscented and spherical-radial point sets
 const ChunkedEntry kChunked[] = {
     // (NOT the scalar UNGM filters: a 36-register kernel with a dependent chain of 125 instructions per step lives on many waves per
     // SIMD - one strip per SIMD ran the bench headline's kernel at 0.083 ms against 0.063 at B = 1e5 and 0.25 against 0.13 at 2e5,
     // 4 096 strips break even; profiles/r05_chunked.txt)
-    SSMQ_CH_FAST(SSMQ_F_REENTRY2D_DYN, SSMQ_F_RADAR2D_MEAS, 5, 2, 11, 0),
-    SSMQ_CH_FAST(SSMQ_F_REENTRY2D_BIAS_DYN, SSMQ_F_RADAR2D_MEAS, 6, 2, 13, 0),
-    SSMQ_CH_FAST(SSMQ_F_CT_DYN, SSMQ_F_BEARING_MEAS, 5, 4, 11, 1),
-    SSMQ_CH(SSMQ_F_REENTRY2D_DYN, SSMQ_F_RADAR2D_MEAS, 5, 2, 10, 0),
-    SSMQ_CH(SSMQ_F_REENTRY2D_BIAS_DYN, SSMQ_F_RADAR2D_MEAS, 6, 2, 12, 0),
-    SSMQ_CH(SSMQ_F_CT_DYN, SSMQ_F_BEARING_MEAS, 5, 4, 10, 1),
+    SSMQ_SHAPES_HEAVY_UT(SSMQ_SHAPE_FAST, SSMQ_CH_ONE),
+    SSMQ_SHAPES_HEAVY_SR(SSMQ_SHAPE, SSMQ_CH_ONE),
 };
 
 }  // namespace
@@ -138,17 +129,14 @@ const ChunkedEntry kChunked[] = {
 // Default: taken when the batch has more blocks than the chip has SIMDs and whole passes would cost at least 5 % more wave-times
 // (ceil(x) against x, x = blocks per SIMD).  SSMQ_FUSED_CHUNKED=0 never; = n > 1: n strips (tests: any batch).
 // The results ARE the whole-pass kernel's bits (test_chunked_time_loop_is_bitwise_the_whole_pass).
-int try_launch_chunked(const FusedArgs &a0, int fd, int fo, int D, int Y, int ND, int NO, int form, int tp, int selo, int opt, int cus,
-                       hipStream_t s, bool dry_run, const char **name) {
+int try_launch_chunked(const FusedArgs &a0, const FilterShape &shape, int cus, hipStream_t s, bool dry_run, const char **name) {
     const char *ev = ssmq::sw("SSMQ_FUSED_CHUNKED");
     const int force = ev ? atoi(ev) : -1;
     if (!dry_run && ctx().no_strips) return 0;      // a job of a multi-filter launch (one hand-over buffer per context)
     if (force == 0 || a0.sscale != nullptr || a0.student_dof > 0.0 || (!dry_run && a0.T < 2)) return 0;
     const ChunkedEntry *e = nullptr;
     for (const ChunkedEntry &c : kChunked)
-        if (c.fd == fd && c.fo == fo && c.D == D && c.Y == Y && c.ND == ND && c.NO == NO && c.form == form && c.tp == tp && c.selo == selo &&
-            c.opt == opt)
-            e = &c;
+        if (c.shape == shape) e = &c;
     if (!e) return 0;
     const int64_t n_blocks = (a0.B + a0.lpw - 1) / a0.lpw, simds = 4 * (int64_t)cus;
     if (n_blocks >= (int64_t)1 << 24) return 0;
@@ -164,9 +152,8 @@ int try_launch_chunked(const FusedArgs &a0, int fd, int fo, int D, int Y, int ND
     if (dry_run) return 1;
     FusedArgs a = a0;
     a.n_blocks = (int32_t)n_blocks;
-    a.t_chunk = 0;
     // flags [n_blocks], strip counter | hand-over [n_blocks][NS + 1][64]
-    const size_t ns = (size_t)D + (size_t)D * (D + 1) / 2 + 1;
+    const size_t D = (size_t)shape.D, ns = D + D * (D + 1) / 2 + 1;
     const size_t q_bytes = (sizeof(int32_t) * ((size_t)n_blocks + 1) + 255) / 256 * 256, need = q_bytes + sizeof(double) * (size_t)n_blocks * ns * 64;
     Ctx &cx = ctx();       // the buffer belongs to the thread's context (pooled; dropped with the context's other caches on a device change)
     if (cx.strip_bytes < need) {

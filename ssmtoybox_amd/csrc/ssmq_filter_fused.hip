@@ -10,6 +10,7 @@
 #include <cstring>
 #include <vector>
 #include "ssmq_filter_fused_kernel.h"
+#include "ssmq_filter_shapes.h"
 
 namespace ssmq {
 
@@ -22,63 +23,33 @@ static hipError_t launch_fused(const FusedArgs &a, hipStream_t s) {
 
 typedef hipError_t (*fused_fn)(const FusedArgs &, hipStream_t);
 struct FusedEntry {
-    int fd, fo, D, Y, ND, NO, form, tp, selo, opt;
+    FilterShape shape;
     fused_fn fn[2];   // [Studentian]; shapes with the recursion type decided at run time fill fn[0] only
     const char *name;
 };
 
-#define SSMQ_FUSED_NAME(FD, FO, D, Y, ND, NO, FORM, TP, SELO, OPT)                                              \
-    "k_filter_fused<D=" #D ",Y=" #Y ",ND=" #ND ",NO=" #NO "," #FD "," #FO "," #FORM ",TP=" #TP ",SELO=" #SELO \
+#define SSMQ_FUSED_NAME(FD, FO, D, Y, N, FORM, TP, SELO, OPT)                                                 \
+    "k_filter_fused<D=" #D ",Y=" #Y ",ND=" #N ",NO=" #N "," #FD "," #FO "," #FORM ",TP=" #TP ",SELO=" #SELO \
     ",OPT=" #OPT ">"
-#define SSMQ_FUSED_FN(FD, FO, D, Y, ND, NO, FORM, TP, SELO, OPT, STU) \
-    &launch_fused<D, Y, ND, NO, FD, FO, FORM, TP, SELO, OPT, STU>
-#define SSMQ_FUSED_ONE(FD, FO, D, Y, ND, NO, FORM, TP, SELO, OPT)                                        \
-    {FD, FO, D, Y, ND, NO, FORM, TP, SELO, OPT,                                                         \
-     {SSMQ_FUSED_FN(FD, FO, D, Y, ND, NO, FORM, TP, SELO, OPT, -1), nullptr},                           \
-     SSMQ_FUSED_NAME(FD, FO, D, Y, ND, NO, FORM, TP, SELO, OPT)}
+#define SSMQ_FUSED_FN(FD, FO, D, Y, N, FORM, TP, SELO, OPT, STU) &launch_fused<D, Y, N, N, FD, FO, FORM, TP, SELO, OPT, STU>
+#define SSMQ_FUSED_ONE(FD, FO, D, Y, N, FORM, TP, SELO, OPT)                                           \
+    {{FD, FO, D, Y, N, N, FORM, TP, SELO, OPT},                                                        \
+     {SSMQ_FUSED_FN(FD, FO, D, Y, N, FORM, TP, SELO, OPT, -1), nullptr},                               \
+     SSMQ_FUSED_NAME(FD, FO, D, Y, N, FORM, TP, SELO, OPT)}
 // scalar state: recursion type fixed at compile time
-#define SSMQ_FUSED_ONE_S(FD, FO, D, Y, ND, NO, FORM, TP, SELO, OPT)                                      \
-    {FD, FO, D, Y, ND, NO, FORM, TP, SELO, OPT,                                                         \
-     {SSMQ_FUSED_FN(FD, FO, D, Y, ND, NO, FORM, TP, SELO, OPT, 0),                                      \
-      SSMQ_FUSED_FN(FD, FO, D, Y, ND, NO, FORM, TP, SELO, OPT, 1)},                                     \
-     SSMQ_FUSED_NAME(FD, FO, D, Y, ND, NO, FORM, TP, SELO, OPT)}
-#define SSMQ_FUSED(FD, FO, D, Y, N, SELO)                                      \
-    SSMQ_FUSED_ONE(FD, FO, D, Y, N, N, SSMQ_FORM_BQ, 0, SELO, 0),              \
-    SSMQ_FUSED_ONE(FD, FO, D, Y, N, N, SSMQ_FORM_BQ, 1, SELO, 0),              \
-    SSMQ_FUSED_ONE(FD, FO, D, Y, N, N, SSMQ_FORM_SIGMA, 0, SELO, 0)
-// scalar-state models (D = Y = 1)
-#define SSMQ_FUSED_S(FD, FO, N)                                                \
-    SSMQ_FUSED_ONE_S(FD, FO, 1, 1, N, N, SSMQ_FORM_BQ, 0, 0, 0),               \
-    SSMQ_FUSED_ONE_S(FD, FO, 1, 1, N, N, SSMQ_FORM_BQ, 1, 0, 0),               \
-    SSMQ_FUSED_ONE_S(FD, FO, 1, 1, N, N, SSMQ_FORM_SIGMA, 0, 0, 0)
-// larger shapes: also with the LDL' / unscented-point fast paths of ssmq_apply_small.h
-#define SSMQ_FUSED_FAST(FD, FO, D, Y, N, SELO)                                 \
-    SSMQ_FUSED(FD, FO, D, Y, N, SELO),                                         \
-    SSMQ_FUSED_ONE(FD, FO, D, Y, N, N, SSMQ_FORM_BQ, 0, SELO, 7),              \
-    SSMQ_FUSED_ONE(FD, FO, D, Y, N, N, SSMQ_FORM_BQ, 0, SELO, 3),              \
-    SSMQ_FUSED_ONE(FD, FO, D, Y, N, N, SSMQ_FORM_BQ, 1, SELO, 2),              \
-    SSMQ_FUSED_ONE(FD, FO, D, Y, N, N, SSMQ_FORM_SIGMA, 0, SELO, 2)
+#define SSMQ_FUSED_ONE_S(FD, FO, D, Y, N, FORM, TP, SELO, OPT)                                         \
+    {{FD, FO, D, Y, N, N, FORM, TP, SELO, OPT},                                                        \
+     {SSMQ_FUSED_FN(FD, FO, D, Y, N, FORM, TP, SELO, OPT, 0),                                          \
+      SSMQ_FUSED_FN(FD, FO, D, Y, N, FORM, TP, SELO, OPT, 1)},                                         \
+     SSMQ_FUSED_NAME(FD, FO, D, Y, N, FORM, TP, SELO, OPT)}
 
-static bool HasTimeTableRT(int fid) { return fid == SSMQ_F_UNGM_DYN || fid == SSMQ_F_UNGMNA_DYN; }
-
+// every shape of ssmq_filter_shapes.h; the fast paths for the heavy shapes with unscented points
 static const FusedEntry kFused[] = {
-    SSMQ_FUSED_S(SSMQ_F_UNGM_DYN, SSMQ_F_UNGM_MEAS, 2),
-    SSMQ_FUSED_S(SSMQ_F_UNGM_DYN, SSMQ_F_UNGM_MEAS, 3),
-    SSMQ_FUSED_S(SSMQ_F_UNGM_DYN, SSMQ_F_UNGM_MEAS, 5),
+    SSMQ_SHAPES_UNGM(SSMQ_SHAPE, SSMQ_FUSED_ONE_S),
 #ifndef SSMQ_FUSED_UNGM_ONLY   // tools/build_variant.sh: quick builds for A/B timing of the UNGM kernels
-    SSMQ_FUSED(SSMQ_F_PENDULUM_DYN, SSMQ_F_PENDULUM_MEAS, 2, 1, 5, 0),
-    SSMQ_FUSED(SSMQ_F_REENTRY1D_DYN, SSMQ_F_RANGE_MEAS, 3, 1, 7, 0),          // tests/test_ssinf.py:40-50 of the reference
-    SSMQ_FUSED(SSMQ_F_CV_DYN, SSMQ_F_RADAR2D_MEAS, 4, 2, 9, 0),               // constant velocity + radar (Student filters)
-    SSMQ_FUSED_FAST(SSMQ_F_REENTRY2D_DYN, SSMQ_F_RADAR2D_MEAS, 5, 2, 11, 0),
-    SSMQ_FUSED_FAST(SSMQ_F_REENTRY2D_BIAS_DYN, SSMQ_F_RADAR2D_MEAS, 6, 2, 13, 0),
-    SSMQ_FUSED_FAST(SSMQ_F_CT_DYN, SSMQ_F_BEARING_MEAS, 5, 4, 11, 1),
-    // spherical-radial point sets (2 D points: the cubature Kalman filter and every BQ transform built with 'sr')
-    SSMQ_FUSED(SSMQ_F_PENDULUM_DYN, SSMQ_F_PENDULUM_MEAS, 2, 1, 4, 0),
-    SSMQ_FUSED(SSMQ_F_REENTRY1D_DYN, SSMQ_F_RANGE_MEAS, 3, 1, 6, 0),
-    SSMQ_FUSED(SSMQ_F_CV_DYN, SSMQ_F_RADAR2D_MEAS, 4, 2, 8, 0),
-    SSMQ_FUSED(SSMQ_F_REENTRY2D_DYN, SSMQ_F_RADAR2D_MEAS, 5, 2, 10, 0),
-    SSMQ_FUSED(SSMQ_F_REENTRY2D_BIAS_DYN, SSMQ_F_RADAR2D_MEAS, 6, 2, 12, 0),
-    SSMQ_FUSED(SSMQ_F_CT_DYN, SSMQ_F_BEARING_MEAS, 5, 4, 10, 1),
+    SSMQ_SHAPES_MID(SSMQ_SHAPE, SSMQ_FUSED_ONE),
+    SSMQ_SHAPES_HEAVY_UT(SSMQ_SHAPE_FAST, SSMQ_FUSED_ONE),
+    SSMQ_SHAPES_HEAVY_SR(SSMQ_SHAPE, SSMQ_FUSED_ONE),
 #endif
 };
 
@@ -395,32 +366,43 @@ static const AugEntry kAug[] = {
 #endif
 };
 
-// as try_launch_fused, for filters whose models take the noise as an argument; d_noise: q_mean | q_cov | r_mean | r_cov
-int try_launch_fused_aug(const ssmq_transform *hd, const ssmq_integrand *fd, const ssmq_transform *ho,
-                         const ssmq_integrand *fo, int sel_obs, int D, int dq, int dr, int64_t B, int64_t ld, int T,
-                         const double *d_y, const double *d_m0, const double *d_P0, const double *d_add_dyn,
-                         const double *d_add_obs, const double *d_noise, double *d_fm, double *d_fP, int32_t *d_status,
-                         hipStream_t s, const char **name, bool dry_run, const double *d_ttab_dyn,
-                         const double *d_ttab_obs, double *d_pm, double *d_pP, double *d_pC) {
-    const int keep = (d_pm && d_pP && d_pC) ? 1 : 0;
-    if (hd->form != ho->form || (hd->tp_nu > 0.0) != (ho->tp_nu > 0.0) || sel_obs < 0 || fd->n_idx > 0) return 0;
-    const int tp = hd->tp_nu > 0.0 ? 1 : 0;
+// What FusedArgs and AugArgs have in common, from a pass
+template <class Args>
+static void fill_common(Args &a, const FilterPass &p) {
+    a.y = p.y; a.m0 = p.m0; a.P0 = p.P0; a.fm = p.fm; a.fP = p.fP; a.status = p.status;
+    a.c_dyn = p.hd->d_small; a.c_obs = p.ho->d_small; a.B = p.B; a.ld = p.ld; a.T = p.T;
+    a.emv_dyn = p.hd->emv_mode; a.emv_obs = p.ho->emv_mode; a.nu_dyn = p.hd->tp_nu; a.nu_obs = p.ho->tp_nu;
+    fill_fpar(p.fd, &a.fd);
+    fill_fpar(p.fo, &a.fo);
+    a.fd.ttab = p.ttab_dyn;
+    a.fo.ttab = p.ttab_obs;
+}
+
+FusedArgs fused_args(const FilterPass &p) {
+    FusedArgs a;
+    memset(&a, 0, sizeof(a));   // the strip schedule's fields (n_blocks, queue, hand) included: the route that uses them sets them
+    fill_common(a, p);
+    a.gqg = p.gqg; a.rr = p.rr; a.sscale = p.sscale; a.student_dof = p.student_dof;
+    a.lpw = 64;
+    return a;
+}
+
+// as try_launch_fused, for filters whose models take the noise as an argument
+int try_launch_fused_aug(const FilterPass &p, const AugExtras &x) {
+    const int keep = (x.pm && x.pP && x.pC) ? 1 : 0;
+    if (!same_family(p)) return 0;
+    const int tp = p.hd->tp_nu > 0.0 ? 1 : 0;
     for (const AugEntry &e : kAug) {
-        if (e.fd == fd->id && e.fo == fo->id && e.D == D && e.Y == ho->E && e.DQ == dq && e.DR == dr && e.ND == hd->N &&
-            e.NO == ho->N && e.form == hd->form && e.tp == tp && e.selo == sel_obs && e.keep == keep) {
-            if (name) *name = e.name;
-            if (dry_run) return 1;
+        if (e.fd == p.fd->id && e.fo == p.fo->id && e.D == x.D && e.Y == p.ho->E && e.DQ == x.dq && e.DR == x.dr && e.ND == p.hd->N &&
+            e.NO == p.ho->N && e.form == p.hd->form && e.tp == tp && e.selo == p.sel_obs && e.keep == keep) {
+            if (p.name) *p.name = e.name;
+            if (p.dry_run) return 1;
             AugArgs a;
-            a.pm = d_pm; a.pP = d_pP; a.pC = d_pC;
-            a.y = d_y; a.m0 = d_m0; a.P0 = d_P0; a.fm = d_fm; a.fP = d_fP; a.status = d_status;
-            a.c_dyn = hd->d_small; a.c_obs = ho->d_small; a.add_dyn = d_add_dyn; a.add_obs = d_add_obs;
-            a.noise = d_noise; a.B = B; a.ld = ld; a.T = T; a.emv_dyn = hd->emv_mode; a.emv_obs = ho->emv_mode;
-            a.nu_dyn = hd->tp_nu; a.nu_obs = ho->tp_nu;
-            fill_fpar(fd, &a.fd);
-            fill_fpar(fo, &a.fo);
-            a.fd.ttab = d_ttab_dyn;
-            a.fo.ttab = d_ttab_obs;
-            int rc = hip_fail(e.fn(a, s), e.name);
+            memset(&a, 0, sizeof(a));
+            fill_common(a, p);
+            a.add_dyn = x.add_dyn; a.add_obs = x.add_obs; a.noise = x.noise;
+            a.pm = x.pm; a.pP = x.pP; a.pC = x.pC;
+            int rc = hip_fail(e.fn(a, p.s), e.name);
             return rc ? rc : 1;
         }
     }
@@ -441,73 +423,46 @@ static int device_cus() {
 }
 
 // Returns 1 if a fused kernel was launched, 0 if none exists for this combination, < 0 on error.
-int try_launch_fused(const ssmq_transform *hd, const ssmq_integrand *fd, const ssmq_transform *ho,
-                     const ssmq_integrand *fo, int sel_obs, int64_t B, int64_t ld, int T, const double *d_y,
-                     const double *d_m0, const double *d_P0, const double *d_gqg, const double *d_rr, double *d_fm,
-                     double *d_fP, int32_t *d_status, hipStream_t s, const char **name, bool dry_run,
-                     const double *d_sscale, double student_dof, const double *d_ttab_dyn, const double *d_ttab_obs) {
-    if (is_user_integrand(fd) || is_user_integrand(fo)) {
+int try_launch_fused(const FilterPass &p) {
+    if (is_user_integrand(p.fd) || is_user_integrand(p.fo)) {
         // user-defined integrands: the run-time compiled whole-pass kernel (ssmq_rtc.hip; launched by the filter entry points
         // themselves), no quad / wave-split / strip variant; here only its name
-        if (!dry_run) return refuse_user_integrand("fused filter launch");
-        FusedArgs a;
-        memset(&a, 0, sizeof(a));
-        return rtc_launch_fused(hd, fd, ho, fo, sel_obs, a, s, name, true);
+        if (!p.dry_run) return refuse_user_integrand("fused filter launch");
+        return rtc_launch_fused(p);
     }
-    if (hd->form != ho->form || (hd->tp_nu > 0.0) != (ho->tp_nu > 0.0) || sel_obs < 0 || fd->n_idx > 0) return 0;
-    if (!dry_run || B > 0) {
+    if (!same_family(p)) return 0;
+    if (!p.dry_run || p.B > 0) {
         // batches whose waves would each sit alone on a SIMD: one trajectory on four lanes (ssmq_filter_quad.hip) ...
-        const int rq = try_launch_quad(hd, fd, ho, fo, sel_obs, B, ld, T, d_y, d_m0, d_P0, d_gqg, d_rr, d_fm, d_fP, d_status, s, name, dry_run,
-                                       d_sscale, student_dof, device_cus());
+        const int rq = try_launch_quad(p, device_cus());
         if (rq != 0) return rq;
         // ... or the sigma points shared out over the waves of a workgroup (ssmq_filter_wsplit.hip)
-        const int rw = try_launch_wsplit(hd, fd, ho, fo, sel_obs, B, ld, T, d_y, d_m0, d_P0, d_gqg, d_rr, d_fm, d_fP, d_status, s, name,
-                                         dry_run, d_sscale, student_dof, device_cus());    // (the dry run asks the same device: 256 only without one)
+        const int rw = try_launch_wsplit(p, device_cus());    // (the dry run asks the same device: 256 only without one)
         if (rw != 0) return rw;
     }
-    const int tp = hd->tp_nu > 0.0 ? 1 : 0;
-    const int both = hd->opt_mask & ho->opt_mask;
-    // best fast path BOTH handles qualify for: reflection-symmetric weights (7), LDL' + unscented points (3), the dense kernel
-    const int plain = !(tp || hd->form == SSMQ_FORM_SIGMA);
-    const int want[3] = {(plain && (both & 7) == 7) ? 7 : -1, both & (plain ? 3 : SSMQ_OPT_UT), 0};
-    for (int w = 0; w < 3; ++w)
+    for (const int opt : opt_preference(p.hd, p.ho))
     for (const FusedEntry &e : kFused) {
-        if (want[w] < 0) break;      // (no such variant for these handles: next w)
-        if (e.fd == fd->id && e.fo == fo->id && e.D == hd->D && e.Y == ho->E && e.ND == hd->N && e.NO == ho->N &&
-            e.form == hd->form && e.tp == tp && e.selo == sel_obs && e.opt == want[w]) {
-            const int stu = (d_sscale != nullptr && student_dof > 0.0) ? 1 : 0;
-            if ((d_sscale != nullptr) != (student_dof > 0.0)) return 0;   // never produced by the entry points
-            fused_fn fn = e.fn[stu] ? e.fn[stu] : e.fn[0];
-            const char *kname = e.name;
-            if (HasTimeTableRT(fd->id) && !d_ttab_dyn && !dry_run) return 0;   // the kernels read the table
-            if (name) *name = kname;
-            FusedArgs a;
-            memset(&a, 0, sizeof(a));
-            a.B = B; a.T = T; a.lpw = 64; a.sscale = d_sscale; a.student_dof = student_dof;
-            if (dry_run) {
-                if (B > 0) (void)try_launch_chunked(a, e.fd, e.fo, e.D, e.Y, e.ND, e.NO, e.form, e.tp, e.selo, e.opt, device_cus(), s, true, name);
-                return 1;
-            }
-            a.y = d_y; a.m0 = d_m0; a.P0 = d_P0; a.fm = d_fm; a.fP = d_fP; a.status = d_status;
-            a.c_dyn = hd->d_small; a.c_obs = ho->d_small; a.gqg = d_gqg; a.rr = d_rr; a.B = B; a.ld = ld; a.T = T;
-            a.emv_dyn = hd->emv_mode; a.emv_obs = ho->emv_mode; a.nu_dyn = hd->tp_nu; a.nu_obs = ho->tp_nu;
-            a.sscale = d_sscale; a.student_dof = student_dof;
-            a.lpw = 64;
-            if (const char *ev = ssmq::sw("SSMQ_FUSED_LPW")) {
-                const int v = atoi(ev);
-                if (v == 16 || v == 32 || v == 64) a.lpw = v;
-            }
-            fill_fpar(fd, &a.fd);
-            fill_fpar(fo, &a.fo);
-            a.fd.ttab = d_ttab_dyn;
-            a.fo.ttab = d_ttab_obs;
-            if (a.lpw == 64) {
-                const int rcq = try_launch_chunked(a, e.fd, e.fo, e.D, e.Y, e.ND, e.NO, e.form, e.tp, e.selo, e.opt, device_cus(), s, false, name);
-                if (rcq != 0) return rcq;
-            }
-            int rc = hip_fail(fn(a, s), kname);
-            return rc ? rc : 1;
+        if (opt < 0) break;      // (no such variant for these handles: next opt)
+        if (!(e.shape == shape_of(p, opt))) continue;
+        const int stu = (p.sscale != nullptr && p.student_dof > 0.0) ? 1 : 0;
+        if ((p.sscale != nullptr) != (p.student_dof > 0.0)) return 0;   // never produced by the entry points
+        fused_fn fn = e.fn[stu] ? e.fn[stu] : e.fn[0];
+        if (has_time_table(p.fd->id) && !p.ttab_dyn && !p.dry_run) return 0;   // the kernels read the table
+        if (p.name) *p.name = e.name;
+        FusedArgs a = fused_args(p);
+        if (p.dry_run) {
+            if (p.B > 0) (void)try_launch_chunked(a, e.shape, device_cus(), p.s, true, p.name);
+            return 1;
         }
+        if (const char *ev = ssmq::sw("SSMQ_FUSED_LPW")) {      // fewer trajectories per wave (A/B timing, tests)
+            const int v = atoi(ev);
+            if (v == 16 || v == 32 || v == 64) a.lpw = v;
+        }
+        if (a.lpw == 64) {
+            const int rcq = try_launch_chunked(a, e.shape, device_cus(), p.s, false, p.name);
+            if (rcq != 0) return rcq;
+        }
+        int rc = hip_fail(fn(a, p.s), e.name);
+        return rc ? rc : 1;
     }
     return 0;
 }

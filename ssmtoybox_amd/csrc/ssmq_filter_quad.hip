@@ -347,33 +347,26 @@ const QuadEntry kQuad[] = {
 // 1: launched (dry_run: would be); 0: this filter / batch keeps its other routes; < 0: error.
 // Taken when the batch's whole-pass waves would each have a SIMD to themselves and the quad waves still do: ceil(B / 16) <= SIMDs
 // (B <= 16 384 on 256 compute units).  SSMQ_FUSED_QUAD=0 never, =1 for any batch (tests).
-int try_launch_quad(const ssmq_transform *hd, const ssmq_integrand *fd, const ssmq_transform *ho, const ssmq_integrand *fo, int sel_obs,
-                    int64_t B, int64_t ld, int T, const double *d_y, const double *d_m0, const double *d_P0, const double *d_gqg,
-                    const double *d_rr, double *d_fm, double *d_fP, int32_t *d_status, hipStream_t s, const char **name, bool dry_run,
-                    const double *d_sscale, double student_dof, int cus) {
+int try_launch_quad(const FilterPass &p, int cus) {
+    const ssmq_transform *hd = p.hd, *ho = p.ho;
     const char *ev = ssmq::sw("SSMQ_FUSED_QUAD");
     const int force = ev ? atoi(ev) : -1;
-    if (force == 0 || d_sscale || student_dof > 0.0 || B <= 0) return 0;
-    if (!dry_run && ctx().no_strips) return 0;       // a job of a multi-filter launch shares the chip: whole-pass kernels only
+    if (force == 0 || p.sscale || p.student_dof > 0.0 || p.B <= 0) return 0;
+    if (!p.dry_run && ctx().no_strips) return 0;       // a job of a multi-filter launch shares the chip: whole-pass kernels only
     if (force != 1 && ssmq::sw("SSMQ_FUSED_WSPLIT")) return 0;          // a forced wave-split mode (0 = the register kernel) is what runs
-    if (hd->form != SSMQ_FORM_SIGMA || ho->form != SSMQ_FORM_SIGMA || hd->tp_nu > 0.0 || ho->tp_nu > 0.0 || sel_obs < 0 || fd->n_idx > 0) return 0;
+    if (!same_family(p) || hd->form != SSMQ_FORM_SIGMA || hd->tp_nu > 0.0) return 0;
     if (!(hd->opt_mask & ho->opt_mask & SSMQ_OPT_UT)) return 0;          // unscented-type points [0 | c I | -c I], verified on the host
     if (hd->N != 2 * hd->D + 1 || ho->N != hd->N || ho->D != hd->D || hd->E != hd->D) return 0;
-    if ((int64_t)hd->D * hd->D * ld * 8 >= ((int64_t)1 << 32)) return 0;        // (the kernel's 32-bit store offsets inside one step's planes)
-    const int64_t waves = (B + kQuadTraj - 1) / kQuadTraj;
+    if ((int64_t)hd->D * hd->D * p.ld * 8 >= ((int64_t)1 << 32)) return 0;      // (the kernel's 32-bit store offsets inside one step's planes)
+    const int64_t waves = (p.B + kQuadTraj - 1) / kQuadTraj;
     if (force != 1 && waves > 4 * (int64_t)cus) return 0;
     for (const QuadEntry &e : kQuad) {
-        if (!(e.fd == fd->id && e.fo == fo->id && e.D == hd->D && e.Y == ho->E && e.selo == sel_obs)) continue;
-        if (name) *name = e.name;
-        if (dry_run) return 1;
-        FusedArgs a;
-        memset(&a, 0, sizeof(a));
-        a.y = d_y; a.m0 = d_m0; a.P0 = d_P0; a.fm = d_fm; a.fP = d_fP; a.status = d_status;
-        a.c_dyn = hd->d_small; a.c_obs = ho->d_small; a.gqg = d_gqg; a.rr = d_rr; a.B = B; a.ld = ld; a.T = T;
-        a.emv_dyn = hd->emv_mode; a.emv_obs = ho->emv_mode; a.lpw = kQuadTraj;
-        fill_fpar(fd, &a.fd);
-        fill_fpar(fo, &a.fo);
-        hipLaunchKernelGGL(e.k, dim3((unsigned)waves), dim3(kSmallBlock), 0, s, a);
+        if (!(e.fd == p.fd->id && e.fo == p.fo->id && e.D == hd->D && e.Y == ho->E && e.selo == p.sel_obs)) continue;
+        if (p.name) *p.name = e.name;
+        if (p.dry_run) return 1;
+        FusedArgs a = fused_args(p);
+        a.lpw = kQuadTraj;         // a trajectory takes four lanes
+        hipLaunchKernelGGL(e.k, dim3((unsigned)waves), dim3(kSmallBlock), 0, p.s, a);
         const int rc = hip_fail(hipGetLastError(), e.name);
         return rc ? rc : 1;
     }

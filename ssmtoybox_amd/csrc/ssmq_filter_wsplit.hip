@@ -435,13 +435,14 @@ static hipError_t launch_wsplit(const FusedArgs &a, hipStream_t s) {
 
 typedef hipError_t (*wsplit_fn)(const FusedArgs &, hipStream_t);
 struct WsplitEntry {
-    int fd, fo, D, Y, ND, NO, form, tp, selo, W;
+    FilterShape shape;    // (opt = 0: the kernel has no fast-path variants)
+    int W;
     wsplit_fn fn;
     const char *name;
     size_t lds_need;      // bytes of LDS the exchange areas take
 };
 #define SSMQ_WS_ONE(FD, FO, D, Y, N, FORM, TP, SELO, W)                                                          \
-    {FD, FO, D, Y, N, N, FORM, TP, SELO, W, &launch_wsplit<D, Y, N, N, FD, FO, FORM, TP, SELO, W>,               \
+    {{FD, FO, D, Y, N, N, FORM, TP, SELO, 0}, W, &launch_wsplit<D, Y, N, N, FD, FO, FORM, TP, SELO, W>,          \
      "k_filter_wsplit<D=" #D ",Y=" #Y ",N=" #N "," #FD "," #FO "," #FORM ",TP=" #TP ",SELO=" #SELO ",W=" #W ">",                 \
      sizeof(double) * ws_lds_doubles<D, Y, N, N, FORM, TP, W>()}
 #define SSMQ_WS(FD, FO, D, Y, N, SELO, W)                    \
@@ -478,44 +479,23 @@ static bool ws_wanted(const WsplitEntry &e, int64_t B, int cus) {
     // t-process form, two N x N quadratic forms per output row: configs[3] 0.318 -> 0.272 ms with W = 2 - and loses 10-25 % on the
     // unscented and Bayes-Sard filters of the reentry model (~60 instructions per point against four barriers per step), so only
     // the former is picked by default; W = 4 of the t-process form needs more than 512 registers (spills) and is slower than W = 2.
-    if (!(e.tp && e.W == 2)) return false;
+    if (!(e.shape.tp && e.W == 2)) return false;
     return (B + 63) / 64 <= (int64_t)cus * ws_groups_per_cu(e);
 }
 
 // Returns 1 if the wave-split kernel was launched (or, dry_run, would be), 0 if not applicable, < 0 on error.
-int try_launch_wsplit(const ssmq_transform *hd, const ssmq_integrand *fd, const ssmq_transform *ho, const ssmq_integrand *fo,
-                      int sel_obs, int64_t B, int64_t ld, int T, const double *d_y, const double *d_m0, const double *d_P0,
-                      const double *d_gqg, const double *d_rr, double *d_fm, double *d_fP, int32_t *d_status, hipStream_t s,
-                      const char **name, bool dry_run, const double *d_sscale, double student_dof, int cus) {
-    if (hd->form != ho->form || (hd->tp_nu > 0.0) != (ho->tp_nu > 0.0) || sel_obs < 0 || fd->n_idx > 0 || B < 1) return 0;
-    if ((d_sscale != nullptr) != (student_dof > 0.0)) return 0;
-    const int tp = hd->tp_nu > 0.0 ? 1 : 0;
+int try_launch_wsplit(const FilterPass &p, int cus) {
+    if (!same_family(p) || p.B < 1) return 0;
+    if ((p.sscale != nullptr) != (p.student_dof > 0.0)) return 0;
     const WsplitEntry *pick = nullptr;
     for (const WsplitEntry &e : kWsplit)
-        if (e.fd == fd->id && e.fo == fo->id && e.D == hd->D && e.Y == ho->E && e.ND == hd->N && e.NO == ho->N && e.form == hd->form &&
-            e.tp == tp && e.selo == sel_obs && ws_wanted(e, B, cus) && (!pick || e.W > pick->W))
-            pick = &e;
+        if (e.shape == shape_of(p, 0) && ws_wanted(e, p.B, cus) && (!pick || e.W > pick->W)) pick = &e;
     if (!pick) return 0;
-    {
-        {
-            const WsplitEntry &e = *pick;
-            if (name) *name = e.name;
-            if (dry_run) return 1;
-            FusedArgs a;
-            a.y = d_y; a.m0 = d_m0; a.P0 = d_P0; a.fm = d_fm; a.fP = d_fP; a.status = d_status;
-            a.c_dyn = hd->d_small; a.c_obs = ho->d_small; a.gqg = d_gqg; a.rr = d_rr; a.B = B; a.ld = ld; a.T = T;
-            a.emv_dyn = hd->emv_mode; a.emv_obs = ho->emv_mode; a.nu_dyn = hd->tp_nu; a.nu_obs = ho->tp_nu;
-            a.sscale = d_sscale; a.student_dof = student_dof;
-            a.lpw = 64;
-            fill_fpar(fd, &a.fd);
-            fill_fpar(fo, &a.fo);
-            a.fd.ttab = nullptr;
-            a.fo.ttab = nullptr;
-            int rc = hip_fail(e.fn(a, s), e.name);
-            return rc ? rc : 1;
-        }
-    }
-    return 0;
+    if (p.name) *p.name = pick->name;
+    if (p.dry_run) return 1;
+    // (fused_args() as it is: the kernel builds its FPar without the time tables - load_fpar - so there is nothing to clear)
+    const int rc = hip_fail(pick->fn(fused_args(p), p.s), pick->name);
+    return rc ? rc : 1;
 }
 
 }  // namespace ssmq

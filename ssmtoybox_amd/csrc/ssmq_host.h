@@ -53,8 +53,8 @@ struct ApplyArgs;   // ssmq_apply_small.h
 struct UpdArgs;     // ssmq_update.h
 // Whole-pass filter kernel k_filter_fused<> for a pair of models of which at least one is a user integrand: 1 launched (or, with
 // dry_run, the name set), < 0 error - never 0, so that no caller falls back to the launch loop.
-int rtc_launch_fused(const ssmq_transform *hd, const ssmq_integrand *fd, const ssmq_transform *ho, const ssmq_integrand *fo,
-                     int sel_obs, const FusedArgs &a, hipStream_t s, const char **name, bool dry_run);
+struct FilterPass;   // below, with the launchers of the fused time loop
+int rtc_launch_fused(const FilterPass &p);
 // k_apply_small<> for a user integrand: SSMQ_OK (launched, or with dry_run the name set) or < 0.
 int rtc_launch_apply(const ssmq_transform *h, const ssmq_integrand *f, int sel, const ApplyArgs &a, hipStream_t s,
                      const char **name, bool dry_run);
@@ -303,37 +303,72 @@ int filter_forward_impl(ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, ssmq
                         const double *R, double *d_fm, double *d_fP, int32_t *d_status, const double *sscale, double student_dof,
                         double *d_pm = nullptr, double *d_pP = nullptr, double *d_pC = nullptr);
 
+// One pass of the additive-noise filter time loop, as every launcher of the fused time loop takes it.  Pointers are device
+// pointers.  A default-constructed pass with the handles, the integrands, sel_obs and B set is a valid dry-run query (dry_run = true).
+struct FilterPass {
+    const ssmq_transform *hd = nullptr;
+    const ssmq_integrand *fd = nullptr;
+    const ssmq_transform *ho = nullptr;
+    const ssmq_integrand *fo = nullptr;
+    int sel_obs = 0;                                              // sel_pattern() of the measurement integrand
+    int64_t B = 0, ld = 0;
+    int T = 0;
+    const double *y = nullptr, *m0 = nullptr, *P0 = nullptr;      // [T][Y][ld], [D][ld], [D*D][ld]
+    double *fm = nullptr, *fP = nullptr;                          // [T][D][ld], [T][D*D][ld]
+    int32_t *status = nullptr;                                    // [B]
+    const double *gqg = nullptr, *rr = nullptr;                   // [D*D], [Y*Y]
+    const double *sscale = nullptr;                               // Studentian recursion: scale [T] and the filter's dof (null / 0: Gaussian)
+    double student_dof = 0.0;
+    const double *ttab_dyn = nullptr, *ttab_obs = nullptr;        // time tables [T] of the integrands that have one (has_time_table)
+    hipStream_t s = nullptr;
+    const char **name = nullptr;                                  // receives the kernel's name, or null
+    bool dry_run = false;                                         // only say whether a kernel exists (and its name)
+};
+// The one place that fills the kernels' argument block from a pass: everything zero but the pass's fields, lpw = 64
+// (ssmq_filter_fused.hip).  A route states what it sets differently next to its launch.
+FusedArgs fused_args(const FilterPass &p);
+// both transforms of one form (sigma-point, BQ or t-process BQ), a measurement index pattern the kernels know, no state index list
+inline bool same_family(const FilterPass &p) {
+    return p.hd->form == p.ho->form && (p.hd->tp_nu > 0.0) == (p.ho->tp_nu > 0.0) && p.sel_obs >= 0 && p.fd->n_idx <= 0;
+}
+// Integrands whose time dependence the fused loops read from a per-step table (time_table() in ssmq_device.h fills it); the kernels'
+// HasTimeTable<> (ssmq_fused.h) is checked against this function id by id in ssmq_filter_shapes.h.
+constexpr bool has_time_table(int fid) { return fid == SSMQ_F_UNGM_DYN || fid == SSMQ_F_UNGMNA_DYN; }
+// What the tables of the time-loop kernels are keyed by (the template arguments of an instantiation)
+struct FilterShape {
+    int fd, fo, D, Y, ND, NO, form, tp, selo, opt;
+    bool operator==(const FilterShape &o) const {
+        return fd == o.fd && fo == o.fo && D == o.D && Y == o.Y && ND == o.ND && NO == o.NO && form == o.form && tp == o.tp &&
+               selo == o.selo && opt == o.opt;
+    }
+};
+// ... and the key of a pass (same_family) with fast path `opt`
+inline FilterShape shape_of(const FilterPass &p, int opt) {
+    return {p.fd->id, p.fo->id, p.hd->D, p.ho->E, p.hd->N, p.ho->N, p.hd->form, p.hd->tp_nu > 0.0 ? 1 : 0, p.sel_obs, opt};
+}
+
 // the whole time loop in one kernel: 1 launched (dry_run: a kernel exists, its name set), 0 no kernel for this combination, < 0 error
-// (ssmq_filter_fused.hip, which tries the schedules of ssmq_filter_wsplit.hip, ssmq_filter_quad.hip and ssmq_filter_chunked.hip)
-int try_launch_fused(const ssmq_transform *hd, const ssmq_integrand *fd, const ssmq_transform *ho, const ssmq_integrand *fo,
-                     int sel_obs, int64_t B, int64_t ld, int T, const double *d_y, const double *d_m0, const double *d_P0,
-                     const double *d_gqg, const double *d_rr, double *d_fm, double *d_fP, int32_t *d_status, hipStream_t s,
-                     const char **name, bool dry_run, const double *d_sscale, double student_dof, const double *d_ttab_dyn,
-                     const double *d_ttab_obs);
-int try_launch_fused_aug(const ssmq_transform *hd, const ssmq_integrand *fd, const ssmq_transform *ho, const ssmq_integrand *fo,
-                         int sel_obs, int D, int dq, int dr, int64_t B, int64_t ld, int T, const double *d_y, const double *d_m0,
-                         const double *d_P0, const double *d_add_dyn, const double *d_add_obs, const double *d_noise, double *d_fm,
-                         double *d_fP, int32_t *d_status, hipStream_t s, const char **name, bool dry_run, const double *d_ttab_dyn,
-                         const double *d_ttab_obs, double *d_pm, double *d_pP, double *d_pC);
-int try_launch_wsplit(const ssmq_transform *hd, const ssmq_integrand *fd, const ssmq_transform *ho, const ssmq_integrand *fo,
-                      int sel_obs, int64_t B, int64_t ld, int T, const double *d_y, const double *d_m0, const double *d_P0,
-                      const double *d_gqg, const double *d_rr, double *d_fm, double *d_fP, int32_t *d_status, hipStream_t s,
-                      const char **name, bool dry_run, const double *d_sscale, double student_dof, int cus);
-int try_launch_quad(const ssmq_transform *hd, const ssmq_integrand *fd, const ssmq_transform *ho, const ssmq_integrand *fo, int sel_obs,
-                    int64_t B, int64_t ld, int T, const double *d_y, const double *d_m0, const double *d_P0, const double *d_gqg,
-                    const double *d_rr, double *d_fm, double *d_fP, int32_t *d_status, hipStream_t s, const char **name, bool dry_run,
-                    const double *d_sscale, double student_dof, int cus);
-int try_launch_chunked(const FusedArgs &a0, int fd, int fo, int D, int Y, int ND, int NO, int form, int tp, int selo, int opt, int cus,
-                       hipStream_t s, bool dry_run, const char **name);
+// (ssmq_filter_fused.hip, which tries the schedules of ssmq_filter_quad.hip, ssmq_filter_wsplit.hip and ssmq_filter_chunked.hip;
+// cus: compute units of the device)
+int try_launch_fused(const FilterPass &p);
+int try_launch_quad(const FilterPass &p, int cus);
+int try_launch_wsplit(const FilterPass &p, int cus);
+int try_launch_chunked(const FusedArgs &a0, const FilterShape &shape, int cus, hipStream_t s, bool dry_run, const char **name);
+// ... for models that take their noise as an argument, and for the smoother (p.gqg / p.rr are not read)
+struct AugExtras {
+    int D, dq, dr;                            // state dimension; dimensions of the noise inputs (0: that model is additive)
+    const double *add_dyn, *add_obs;          // [D*D] / [Y*Y]: G Q G' / R for an additive model, zeros otherwise
+    const double *noise;                      // q_mean[dq] | q_cov[dq*dq] | r_mean[dr] | r_cov[dr*dr]
+    double *pm, *pP, *pC;                     // all or none: predictive moments of every step, kept for the backward pass
+};
+int try_launch_fused_aug(const FilterPass &p, const AugExtras &x);
 // ... several filters of one model family as one launch (ssmq_filter_fused.hip; ssmq_filter_forward_multi_dev)
 int multi_family_table(int n, const ssmq_transform *const *hd, const ssmq_integrand *const *fd, const ssmq_transform *const *ho,
                        const ssmq_integrand *const *fo, const FusedArgs *args, std::vector<char> *table, int *blocks);
 int multi_family_launch(const char *table, int blocks, hipStream_t s);
-// ... and the steps [kb, ke) of every trajectory (ssmq_filter_piped.hip; ssmq_filter_forward_piped)
-int try_launch_range(const ssmq_transform *hd, const ssmq_integrand *fd, const ssmq_transform *ho, const ssmq_integrand *fo, int sel_obs,
-                     int64_t B, int64_t ld, int T, int kb, int ke, const double *d_y, const double *d_m0, const double *d_P0,
-                     const double *d_gqg, const double *d_rr, double *d_fm, double *d_fP, int32_t *d_status, double *hand, hipStream_t s,
-                     const char **name, bool dry_run, const double *d_ttab_dyn, const double *d_ttab_obs);
+// ... and the steps [kb, ke) of every trajectory (ssmq_filter_piped.hip; ssmq_filter_forward_piped); hand: range_hand_doubles(D)
+// doubles per block of 64 trajectories
+int try_launch_range(const FilterPass &p, int kb, int ke, double *hand);
 size_t range_hand_doubles(int D);
 
 // error sums over a batch of filtered trajectories (ssmq_metrics.hip)

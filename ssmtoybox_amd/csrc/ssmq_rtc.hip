@@ -24,6 +24,7 @@
 #include <vector>
 #include "ssmq_host.h"
 #include "ssmq_fused.h"
+#include "ssmq_filter_shapes.h"
 
 namespace ssmq {
 
@@ -309,13 +310,11 @@ bool shape_ok(int D, int E, int N, std::string *why) {
 }
 
 // The fast-path variant: as the AOT route, which has the LDL' / unscented-point variants for the D >= 5 shapes only (kFused,
-// SSMQ_FUSED_FAST; ssmq_small_*.hip, SSMQ_SMALL_FAST) - below that the dense kernel, so a restated built-in model runs the same code.
-int pick_opt_fused(const ssmq_transform *hd, const ssmq_transform *ho, int tp) {
+// SSMQ_SHAPE_FAST in ssmq_filter_shapes.h; ssmq_small_*.hip, SSMQ_SMALL_FAST) - below that the dense kernel, so a restated built-in model runs the same code.
+int pick_opt_fused(const ssmq_transform *hd, const ssmq_transform *ho) {
     if (hd->D < 5) return 0;
-    const int both = hd->opt_mask & ho->opt_mask;
-    const int plain = !(tp || hd->form == SSMQ_FORM_SIGMA);
-    if (plain && (both & 7) == 7) return 7;
-    return both & (plain ? 3 : SSMQ_OPT_UT);
+    const auto want = opt_preference(hd, ho);     // as the AOT tables: the best fast path both handles qualify for
+    return want[0] >= 0 ? want[0] : want[1];
 }
 
 }  // namespace
@@ -348,8 +347,9 @@ static int check_user_pair(const ssmq_integrand *fd, const ssmq_integrand *fo, s
     return SSMQ_OK;
 }
 
-int rtc_launch_fused(const ssmq_transform *hd, const ssmq_integrand *fd, const ssmq_transform *ho, const ssmq_integrand *fo,
-                     int sel_obs, const FusedArgs &a0, hipStream_t s, const char **name, bool dry_run) {
+int rtc_launch_fused(const FilterPass &p) {
+    const ssmq_transform *hd = p.hd, *ho = p.ho;
+    const ssmq_integrand *fd = p.fd, *fo = p.fo;
     std::vector<int> ids;
     int rc = check_user_pair(fd, fo, &ids);
     if (rc) return rc;
@@ -365,7 +365,7 @@ int rtc_launch_fused(const ssmq_transform *hd, const ssmq_integrand *fd, const s
         set_error(why);
         return SSMQ_E_UNSUPPORTED;
     }
-    if (hd->form != ho->form || (hd->tp_nu > 0.0) != (ho->tp_nu > 0.0) || sel_obs != 0 || hd->form == SSMQ_FORM_TAYLOR1) {
+    if (hd->form != ho->form || (hd->tp_nu > 0.0) != (ho->tp_nu > 0.0) || p.sel_obs != 0 || hd->form == SSMQ_FORM_TAYLOR1) {
         set_error("user integrands: both transforms of one form (sigma-point or BQ), no linearisation, no state index");
         return SSMQ_E_UNSUPPORTED;
     }
@@ -373,21 +373,21 @@ int rtc_launch_fused(const ssmq_transform *hd, const ssmq_integrand *fd, const s
         set_error("user integrands: input / output dimensions do not match the transforms");
         return SSMQ_E_ARG;
     }
-    const int tp = hd->tp_nu > 0.0 ? 1 : 0, opt = pick_opt_fused(hd, ho, tp);
-    const int stu = (a0.sscale != nullptr && a0.student_dof > 0.0) ? 1 : 0;
+    const int tp = hd->tp_nu > 0.0 ? 1 : 0, opt = pick_opt_fused(hd, ho);
+    const int stu = (p.sscale != nullptr && p.student_dof > 0.0) ? 1 : 0;
     // scalar state: recursion type fixed at compile time, as the AOT table does (SSMQ_FUSED_ONE_S)
     const std::string expr = fused_expr(D, Y, hd->N, ho->N, fd->id, fo->id, hd->form, tp, 0, opt, D == 1 && Y == 1 ? stu : -1);
-    if (name) {
+    if (p.name) {
         std::lock_guard<std::mutex> lk(g_mu);
-        *name = stable_name(expr.substr(6) + " (run-time compiled)");
+        *p.name = stable_name(expr.substr(6) + " (run-time compiled)");
     }
-    if (dry_run) return 1;
-    // A built-in member with a host time table (UNGM: HasTimeTable<> in ssmq_fused.h) is read through that table at every step
-    // of the loop, unconditionally: the caller must have uploaded it (filter_forward_user does).
-    FusedArgs a = a0;
+    if (p.dry_run) return 1;
+    // A built-in member with a host time table (UNGM) is read through that table at every step of the loop, unconditionally: the
+    // caller must have uploaded it (filter_forward_user does).
+    FusedArgs a = fused_args(p);
     for (const ssmq_integrand *f : {fd, fo}) {
         const double *tab = f == fd ? a.fd.ttab : a.fo.ttab;
-        if (!is_user_integrand(f) && time_table(f->id, 0, nullptr) && !tab) {
+        if (!is_user_integrand(f) && has_time_table(f->id) && !tab) {
             set_error("run-time compiled filter: the time table of built-in integrand " + std::to_string(f->id) + " is missing");
             return SSMQ_E_ARG;
         }
@@ -396,10 +396,9 @@ int rtc_launch_fused(const ssmq_transform *hd, const ssmq_integrand *fd, const s
     if (is_user_integrand(fo)) a.fo.ttab = nullptr;
     hipFunction_t fn;
     if ((rc = kernel_for(expr, ids, &fn))) return rc;
-    a.lpw = 64;
     void *args[] = {&a};
     const unsigned grid = (unsigned)((a.B + a.lpw - 1) / a.lpw);
-    rc = hip_fail(hipModuleLaunchKernel(fn, grid, 1, 1, kSmallBlock, 1, 1, 0, s, args, nullptr), "k_filter_fused (run-time compiled)");
+    rc = hip_fail(hipModuleLaunchKernel(fn, grid, 1, 1, kSmallBlock, 1, 1, 0, p.s, args, nullptr), "k_filter_fused (run-time compiled)");
     return rc ? rc : 1;
 }
 
