@@ -1,5 +1,5 @@
 // C ABI of libssmq (include/ssmq.h), the theta-batched filter step: one step per kernel-parameter item, from host arrays
-// (ssmq_gp_theta_step, with its captured graphs) or on items that are already on the device (theta_dev_*, for ssmq_marginal.hip).
+// (ssmq_gp_theta_step, with its captured graphs) or on items that are already on the device (theta_dev_*, for ssmq_marginal_device.hip).
 #include <algorithm>
 #include <cstring>
 #include <vector>
@@ -309,7 +309,7 @@ static int gp_theta_step_impl(ssmq_transform *h_dyn, const ssmq_integrand *f_dyn
 }
 
 // ---- the theta-batched step with its items ALREADY on the device and their number in device memory --------------------------
-// (the device-resident rounds of the batched marginalised filter, ssmq_marginal.hip: no host copy and no synchronisation per
+// (the device-resident rounds of the batched marginalised filter, ssmq_marginal_device.hip: no host copy and no synchronisation per
 // round; the kernels are the two of gp_theta_step_impl's two-launch route, launched on an upper bound of the item count.)
 namespace ssmq {
 bool theta_dev_supported(const ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, const ssmq_transform *h_obs, const ssmq_integrand *f_obs) {

@@ -1,8 +1,8 @@
 // SciPy's BFGS (scipy.optimize._minimize_bfgs with both of its line searches) as a per-run state machine that takes the
 // objective values of its pending point a ROUND later - the numeric core of the batched Laplace step of the marginalised filter
-// (ssmq_marginal.hip has the reference citations and the drivers).  One definition for the host rounds (ssmq_bfgs_lockstep_host,
+// (ssmq_bfgs_lockstep.hip has the reference citations and the lock-step drivers).  One definition for the host rounds (ssmq_bfgs_lockstep_host,
 // ssmq_gp_marginal_laplace_batch, the host-round route of ssmq_gp_marginal_filter_batch; pinned against SciPy in
-// tests/test_bfgs_lockstep.py) and for the device-resident rounds (ssmq_marginal_dev.hip: one thread per trajectory).
+// tests/test_bfgs_lockstep.py) and for the device-resident rounds (ssmq_marginal_device.hip: one thread per trajectory).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>

@@ -75,7 +75,7 @@ struct Ctx {
     void *stage = nullptr;                   // ssmq_api_host.hip: StagingArena
     void *fc = nullptr;                      // ssmq_api_filter.hip: FilterCache
     void *theta_graphs = nullptr;            // ssmq_api_theta.hip: captured graphs of the theta-batched step
-    void *pinned_flags = nullptr;            // 64 bytes of pinned host memory the device rounds report through (ssmq_marginal.hip)
+    void *pinned_flags = nullptr;            // 64 bytes of pinned host memory the device rounds report through (ssmq_marginal_device.hip)
     void *strip_buf = nullptr;               // flags + hand-over buffer of the strip schedule (ssmq_filter_chunked.hip), grow-only
     size_t strip_bytes = 0;
     void *multi = nullptr;                   // ssmq_api_study.hip: MultiCache (side streams, events, constants and captured graph of
@@ -244,7 +244,7 @@ struct BigRest {
 int launch_big_rest(const BigRest &r, int64_t B, hipStream_t s);
 
 // theta-batched step on items that are already on the device, their number read from device memory (ssmq_api_theta.hip; used by the
-// device-resident rounds of ssmq_gp_marginal_filter_batch, ssmq_marginal.hip)
+// device-resident rounds of ssmq_gp_marginal_filter_batch, ssmq_marginal_device.hip)
 struct ThetaDev {
     int Din, D, Y, Nd, No;
     int64_t cap, ld;                                     // items the arena holds; plane pitch
@@ -262,6 +262,27 @@ int theta_dev_upload_static(const ThetaDev &t, const ssmq_transform *h_dyn, cons
                             hipStream_t s);
 int theta_dev_enqueue(const ThetaDev &t, const ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, const ssmq_transform *h_obs,
                       const ssmq_integrand *f_obs, double jitter, int64_t bound, const int32_t *d_count, hipStream_t s);
+
+// One call of ssmq_gp_marginal_filter_batch as its routes take it: the entry point's arguments under their names (include/ssmq.h).
+struct MarginalCall {
+    ssmq_transform *h_dyn;
+    const ssmq_integrand *f_dyn;
+    ssmq_transform *h_obs;
+    const ssmq_integrand *f_obs;
+    int64_t B;
+    int T;
+    double jitter;
+    const double *y, *x0_mean, *x0_cov, *q_mean, *q_cov, *GQG, *R, *prior_mean, *prior_cov, *upts, *uwts;
+    int NP;
+    double fd_step, param_jitter;
+    double *fm, *fP;
+    int32_t *failed;
+    double *theta_last, *pcov_last;
+    int64_t *stats;
+};
+// The state machines on the device (ssmq_marginal_device.hip): SSMQ_OK having produced everything, SSMQ_E_UNSUPPORTED if this shape
+// has no device-resident route (the caller, ssmq_marginal.hip, then runs the host rounds), or an error.
+int marginal_filter_batch_device(const MarginalCall &c);
 
 // trajectory / measurement simulator (ssmq_simulate.hip)
 struct SimRv {

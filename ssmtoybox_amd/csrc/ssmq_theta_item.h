@@ -1,5 +1,5 @@
 // Device functions of the per-item theta step (one parameter item per lane, everything in registers): shared by k_theta_item
-// (ssmq_theta_item.hip) and the one-launch marginalised filter (ssmq_marginal.hip: k_mg_persistent).  See ssmq_theta_item.hip.
+// (ssmq_theta_item.hip) and the one-launch marginalised filter (ssmq_marginal_device.hip: k_mg_persistent).  See ssmq_theta_item.hip.
 #pragma once
 #include "ssmq_device.h"
 

@@ -5,7 +5,7 @@
 // barrier-separated phases and LDS / global round trips for what is, on the reference's demo systems of the marginalised filter
 // (UNGM: 1 state, 2-3 points; pendulum: 2 states, 4-5 points), a few hundred to two thousand flops per item.  Its callers are
 // latency-bound on exactly that: MarginalInference.theta_step (param_dim + 1 items per BFGS evaluation) and the rounds of the
-// batched marginalised filter (csrc/ssmq_marginal.hip: most rounds serve a handful of straggler trajectories).
+// batched marginalised filter (csrc/ssmq_marginal_device.hip: most rounds serve a handful of straggler trajectories).
 //
 // Here lane = item: RBF kernel matrix on the unit points, its Cholesky factor and inverse, the Gaussian expectations q, R, Q, the
 // GP quadrature weights wm / Wc / Wcc and the model variance (bq/bqkern.py:38-64,96-120,329-424, bq/bqmod.py:495-523), the BQ

@@ -1125,7 +1125,7 @@ struct ThetaWgtArgs {
     double *consts[2];
     int32_t E[2];
     const int32_t *count;      // null, or the number of items on the device (the grid then covers an upper bound): the
-                               // device-resident rounds of the batched marginalised filter (ssmq_marginal.hip)
+                               // device-resident rounds of the batched marginalised filter (ssmq_marginal_device.hip)
 };
 
 static size_t theta_weights_lds_doubles(int D, int N) {

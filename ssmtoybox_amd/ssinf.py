@@ -754,7 +754,7 @@ class MarginalInference(GaussianInference):
 
     def laplace_batch(self, mean, cov, y, time, prior_mean, prior_cov):
         """The Laplace step (ssinf.py:1243-1273) of B trajectories at once: B BFGS runs in lock step, every round one
-        theta-batched device call (`ssmq_gp_marginal_laplace_batch`, csrc/ssmq_marginal.hip).  mean (B, D) / cov (B, D, D)
+        theta-batched device call (`ssmq_gp_marginal_laplace_batch`, csrc/ssmq_bfgs_lockstep.hip).  mean (B, D) / cov (B, D, D)
         filtered moments, y (B, Y), prior_mean (B, P) / prior_cov (B, P, P).  Returns the posterior modes (B, P), the BFGS
         inverse Hessians (B, P, P), status (B,), iterations (B,) and the number of device calls."""
         c = self._theta_static()

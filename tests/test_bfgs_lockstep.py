@@ -1,5 +1,5 @@
 """
-The lock-step BFGS of the batched marginalised filter (csrc/ssmq_marginal.hip) against scipy.optimize.minimize(method='BFGS')
+The lock-step BFGS of the batched marginalised filter (csrc/ssmq_bfgs_lockstep.hip) against scipy.optimize.minimize(method='BFGS')
 with the same forward-difference gradient: the optimiser is a restatement of SciPy's (MINPACK-2 DCSRCH line search), so on the
 same objective it must take the same path - minimiser, inverse Hessian and iteration count.  Host code only: runs without a GPU.
 """

@@ -3900,6 +3900,38 @@ def test_marginal_filter_device_rounds_match_host_rounds(amd, monkeypatch):
     assert np.median(np.abs(fna - fnh)[..., okn] / np.maximum(1.0, np.abs(fnh[..., okn]))) < 5e-3
 
 
+def test_marginal_filter_host_rounds_threads_do_not_change_results(amd, monkeypatch):
+    """The host rounds cut a round with many active trajectories into chunks for a pool of worker threads (Workers in
+    csrc/ssmq_marginal.hip; SSMQ_MARGINAL_THREADS), every thread running the shared state machine of csrc/ssmq_marginal_traj.h
+    on its own trajectories: one thread and the pool give the same bits.  B = 512 is the smallest batch at which the pool gets a
+    second thread (B / 256) and a round passes its threshold of 256 active trajectories."""
+    from ssmtoybox_amd import ssinf, ssmod as sm
+    from bench import simulate_ungm
+    dyn = sm.UNGMTransition(sm.GaussRV(1), sm.GaussRV(1, cov=np.array([[10.0]])))
+    obs = sm.UNGMMeasurement(sm.GaussRV(1), 1)
+    alg = ssinf.MarginalizedGaussianProcessKalman(dyn, obs, 'rbf', 'sr')
+    B, T = 512, 2
+    _, y = simulate_ungm(B, T, 21)
+    data = np.ascontiguousarray(y[None])
+    monkeypatch.setenv('SSMQ_MARGINAL_HOST_ROUNDS', '1')
+    res = []
+    for threads in ('1', None):
+        if threads is None:
+            monkeypatch.delenv('SSMQ_MARGINAL_THREADS', raising=False)
+        else:
+            monkeypatch.setenv('SSMQ_MARGINAL_THREADS', threads)
+        fm, fP = alg.forward_pass_batch(data)
+        res.append((fm.copy(), fP.copy(), alg.batch_failed.copy(), alg.batch_param_mean.copy(), dict(alg.batch_stats)))
+    monkeypatch.delenv('SSMQ_MARGINAL_HOST_ROUNDS')
+    one, pool = res
+    print('marginal filter host rounds, one thread %s | pool %s | failed %d / %d' % (
+        one[4], pool[4], int((one[2] != 0).sum()), int((pool[2] != 0).sum())))
+    assert np.array_equal(one[0], pool[0], equal_nan=True) and np.array_equal(one[1], pool[1], equal_nan=True)
+    assert np.array_equal(one[2], pool[2]) and np.array_equal(one[3], pool[3], equal_nan=True)
+    assert one[4] == pool[4]
+    assert (one[2] == 0).sum() >= B - 8 and (pool[2] == 0).sum() >= B - 8
+
+
 def test_marginal_filter_one_launch_matches_device_rounds(amd, monkeypatch):
     """The one-launch route of the batched marginalised filter (k_mg_persistent: a group of lanes per trajectory loops over
     evaluate | advance inside one kernel) against the device rounds (fill | k_theta_item | advance, three launches per round): the
