@@ -124,8 +124,11 @@ typedef struct ssmq_integrand {
 enum ssmq_form {
     SSMQ_FORM_BQ = 0,    /* bq/bqmtran.py:158-223: mean = fx wm; cov = fx Wc fx' - mean mean' + emv; ccov = fx Wcc' L' */
     SSMQ_FORM_SIGMA = 1, /* mtran.py:141-149: centred, diagonal Wc: cov = dfx diag(wc) dfx'; ccov = dfx diag(wc) (x-m)' */
-    SSMQ_FORM_TAYLOR1 = 2 /* mtran.py:49-59 (LinearizationTransform): mean = f(m); J = df/dx(m); ccov = J cov; cov = ccov J'.
+    SSMQ_FORM_TAYLOR1 = 2, /* mtran.py:49-59 (LinearizationTransform): mean = f(m); J = df/dx(m); ccov = J cov; cov = ccov J'.
                              Handles of this form come from ssmq_transform_create_linear only */
+    SSMQ_FORM_BQ_MO = 3  /* multi-output BQ (bq/bqmtran.py:425-602): one weight set per output and output pair -
+                            mean_i = fx_i wm_i; cov_ij = fx_i Wc_ij fx_j' - mean_i mean_j + delta_ij emv_i; ccov_i = fx_i Wcc_i' L'.
+                            Handles of this form come from ssmq_transform_create_mo only */
 };
 
 /* How the expected model variance enters the covariance (bq/bqmtran.py:198 `model_var * I_out`). */
@@ -330,6 +333,26 @@ int ssmq_bs_moments(int D, int N, const double *x, const double *par, const int3
 int ssmq_variances_bs(int D, int N, const double *xi, const double *par, int P, double jitter, const int32_t *mulind,
                       int NB, double *model_var, double *integral_var, int32_t *status);
 
+/*
+ * Multi-output GP quadrature weights: one kernel-parameter row per output of the integrand.  Replaces
+ * MultiOutputModel.bq_weights (bq/bqmod.py:1254-1315) with GaussianProcessMO.exp_model_variance / integral_variance
+ * (:1532-1548).  par [E][1+D]; for output e everything comes from row e as in ssmq_weights_gp (stage one: the same per-row
+ * code, P = E); stage two, one workgroup per pair i > j: Q_ij = exp_x_kxkx(par_i, par_j) (not symmetric), W = iK_i Q_ij iK_j,
+ * both blocks [i][j] and [j][i] of Wc get sym(W) - what the reference's `0.5 * (w_c + w_c.swapaxes(0, 1).swapaxes(2, 3))`
+ * leaves - and both blocks of Q get Q_ij untransposed, as the reference stores them.
+ * outputs (host, output-major; any may be NULL): wm [E][N], Wcc [E][D][N], iK [E][N][N], q [E][N], R [E][D][N],
+ *   Wc [E][E][N][N], Q [E][E][N][N], model_var [E] = alpha_e^2 (1 - tr(Q_ee iK_e)) with alpha_e from `par`,
+ *   integral_var [E], status [E] (1 = K_e + jitter I not positive definite; the return value is then the first such row + 1
+ *   and the pair blocks are not written).
+ * Supported: D <= SSMQ_MAX_DIM, E <= SSMQ_MO_MAX_OUT, N <= SSMQ_MO_MAX_PTS (else SSMQ_E_UNSUPPORTED, outputs untouched).
+ * Host arrays; synchronous.
+ */
+#define SSMQ_MO_MAX_OUT 8
+#define SSMQ_MO_MAX_PTS 64
+int ssmq_weights_gp_mo(int D, int N, int E, const double *xi, const double *par, double jitter, double *wm, double *Wcc,
+                       double *iK, double *q, double *R, double *Wc, double *Q, double *model_var, double *integral_var,
+                       int32_t *status);
+
 /* ---- transform handle --------------------------------------------------------------------------------------- */
 /*
  * Upload the constants of one moment transform (what BQTransform.__init__ / SigmaPointTransform.__init__ keep as
@@ -354,6 +377,23 @@ int ssmq_transform_update(ssmq_transform *h, const double *xi, const double *wm,
  * other integrand: SSMQ_E_UNSUPPORTED at apply time, where the reference's Jacobian is None).  The handle goes wherever a
  * transform handle goes (ssmq_apply_batch[_dev], the filter / smoother entry points: time loop as a launch loop). */
 ssmq_transform *ssmq_transform_create_linear(int D, int E);
+/*
+ * The multi-output BQ transform (SSMQ_FORM_BQ_MO; MultiOutputGaussianProcessTransform / MultiOutputStudentTProcessTransform,
+ * bq/bqmtran.py:425-602): xi [D*N]; wm [E][N]; Wc [E][E][N][N], of which the blocks [i][j] with i >= j are read; Wcc [E][D][N];
+ * emv [E] model variance per output, added to the DIAGONAL of the covariance (NULL = 0); tp_nu > 0 selects the t-process scale
+ * emv_i (tp_nu - 2 + fx_i iK_i fx_i') / (tp_nu - 2 + N) and needs tp_iK [E][N][N].
+ * D <= SSMQ_MAX_DIM, E <= SSMQ_MO_MAX_OUT, N <= SSMQ_MO_MAX_PTS (else NULL, ssmq_last_error() names the range).  Every point set
+ * with N >= 2 D is inside the range; with fewer points the kernel packs 64 / N trajectories into a wave, and the few shapes whose
+ * work space then exceeds the LDS of a CU (D = 16, E = 8, N = 8; D = 12, E = 8, N = 4; ...) are refused here as well.
+ * The handle runs through ssmq_apply_batch[_dev], ssmq_apply_kernel_name, ssmq_sigma_points_batch, ssmq_apply_fx_batch (one
+ * kernel, k_apply_mo; built-in integrands) and ssmq_filter_forward_dev / ssmq_filter_kernel_name[_batch] (the launch loop);
+ * every other entry point that takes a transform handle returns SSMQ_E_UNSUPPORTED for it and leaves its outputs untouched.
+ * ssmq_transform_update_mo replaces constants in place (any pointer NULL = keep; tp_nu <= 0 = keep).
+ */
+ssmq_transform *ssmq_transform_create_mo(int D, int E, int N, const double *xi, const double *wm, const double *Wc,
+                                         const double *Wcc, const double *emv, double tp_nu, const double *tp_iK);
+int ssmq_transform_update_mo(ssmq_transform *h, const double *xi, const double *wm, const double *Wc, const double *Wcc,
+                             const double *emv, double tp_nu, const double *tp_iK);
 void ssmq_transform_destroy(ssmq_transform *h);
 int ssmq_transform_dims(const ssmq_transform *h, int *D, int *E, int *N);
 

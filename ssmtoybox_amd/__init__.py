@@ -9,6 +9,7 @@ from ._lib import SsmqError, device_count, set_device, device_name  # noqa: F401
 from .mtran import (MomentTransform, SigmaPointTransform, UnscentedTransform, SphericalRadialTransform,  # noqa: F401
                     GaussHermiteTransform, FullySymmetricStudentTransform, MonteCarloTransform, LinearizationTransform)
 from .bq.bqmtran import (BQTransform, GaussianProcessTransform, BayesSardTransform,  # noqa: F401
-                         StudentTProcessTransform)
+                         StudentTProcessTransform, MultiOutputGaussianProcessTransform,
+                         MultiOutputStudentTProcessTransform)
 
 __version__ = '0.1.0'

@@ -9,8 +9,8 @@ Type-II maximum likelihood of the kernel parameters - `neg_log_marginal_likeliho
 537-596, 1191-1245) - runs on the device too (`ssmq_gp_nlml_batch` / `ssmq_gp_ml2_batch`), with batched forms that fit
 many data sets in one launch.  Prediction - `predict` of the three model families (bq/bqmod.py:454-493, 840-891,
 1090-1130) and `predict_batch`, which takes the layout of `optimize_batch` so that fits chain into predictions - runs on
-the device as well (`ssmq_gp_predict_batch`).  `plot_model` (matplotlib, host-only) and the multi-output models are out of
-scope.
+the device as well (`ssmq_gp_predict_batch`).  The multi-output models (bq/bqmod.py:1248-1560: one kernel-parameter row per
+output) get their weights from `ssmq_weights_gp_mo`.  `plot_model` (matplotlib, host-only) is out of scope.
 """
 import warnings
 
@@ -567,3 +567,133 @@ class BayesSardModel(Model):
     def integral_variance_batch(self, pars, mulind=None):
         return self._variances(pars, mulind)[1]
 
+
+
+MO_MAX_DIM, MO_MAX_OUT, MO_MAX_PTS = 16, 8, 64
+_MO_RANGE = ("the multi-output models run on the device for D <= 16 inputs, E <= 8 outputs and N <= 64 points, with the 'rbf' "
+             "kernel and the built-in models")
+
+
+def check_mo_range(D, E, N, kern_str='rbf'):
+    """NotImplementedError naming the range, before anything reaches the library."""
+    if str(kern_str).lower() != 'rbf':
+        raise NotImplementedError('{}; got kernel {!r}'.format(_MO_RANGE, kern_str))
+    if D > MO_MAX_DIM or E > MO_MAX_OUT or N > MO_MAX_PTS:
+        raise NotImplementedError('{}; got D = {}, E = {}, N = {}'.format(_MO_RANGE, D, E, N))
+
+
+class MultiOutputModel(Model):
+    """Kernel + point set with one parameter row [alpha, ell_1 .. ell_D] per output (bq/bqmod.py:1248-1478).  The reference's
+    class is unfinished; this is the finished model around the parts of it that work: `bq_weights`,
+    `exp_model_variance`, `integral_variance` and `optimize` as the reference defines them, `predict` (`pass` there) raises
+    NotImplementedError."""
+
+    def __init__(self, dim_in, dim_out, kern_par, kern_str, point_str, point_par=None, estimate_par=False):
+        kern_par = np.asarray(kern_par, dtype=np.float64)
+        if kern_par.ndim != 2 or kern_par.shape != (dim_out, dim_in + 1):
+            raise ValueError('kern_par must be (dim_out, 1 + dim_in) = ({}, {}), got {}'.format(dim_out, dim_in + 1, kern_par.shape))
+        check_mo_range(dim_in, dim_out, 0, kern_str)
+        super().__init__(dim_in, kern_par, kern_str, point_str, point_par, estimate_par)
+        self.dim_out = dim_out
+        check_mo_range(self.dim_in, dim_out, self.num_pts, kern_str)
+
+    def _rows(self, par):
+        par = self.kernel.get_parameters(par)
+        if par.shape != (self.dim_out, self.dim_in + 1):
+            raise ValueError('par must be (dim_out, 1 + dim_in) = ({}, {}), got {}'.format(self.dim_out, self.dim_in + 1, par.shape))
+        return np.ascontiguousarray(par, dtype=np.float64)
+
+    def _device_weights(self, par):
+        par = self._rows(par)
+        D, N, E = self.dim_in, self.num_pts, self.dim_out
+        out = {k: _lib.out_c(sh) for k, sh in (('wm', (E, N)), ('Wcc', (E, D, N)), ('iK', (E, N, N)), ('q', (E, N)), ('R', (E, D, N)),
+                                               ('Wc', (E, E, N, N)), ('Q', (E, E, N, N)), ('model_var', (E,)),
+                                               ('integral_var', (E,)))}
+        st = np.zeros(E, dtype=np.int32)
+        rc = _lib.check(_lib.load().ssmq_weights_gp_mo(D, N, E, _lib.as_c(self.points)[1], _lib.as_c(par)[1], float(self.kernel.jitter),
+                                                       out['wm'][1], out['Wcc'][1], out['iK'][1], out['q'][1], out['R'][1],
+                                                       out['Wc'][1], out['Q'][1], out['model_var'][1], out['integral_var'][1],
+                                                       st.ctypes.data_as(_lib.c_int32_p)), 'ssmq_weights_gp_mo')
+        if rc > 0:
+            raise np.linalg.LinAlgError('kernel matrix of output {} is not positive definite'.format(rc - 1))
+        return {k: v[0] for k, v in out.items()}
+
+    def bq_weights(self, par):
+        """(wm (N, E), Wc (N, N, E, E), Wcc (D, N, E)) in the reference's layouts (bq/bqmod.py:1254-1315); caches q (N, E), Q
+        (N, N, E, E), R (D, N, E), iK (N, N, E), model_var (E,) and integral_var (E,).  Wc[..., i, j] = Wc[..., j, i] =
+        sym(iK_i Q_ij iK_j), as the reference's symmetrisation leaves it."""
+        w = self._device_weights(par)
+        self.q, self.R = w['q'].T.copy(), w['R'].transpose(1, 2, 0).copy()
+        self.iK, self.Q = w['iK'].transpose(1, 2, 0).copy(), w['Q'].transpose(2, 3, 0, 1).copy()
+        self.model_var, self.integral_var = w['model_var'], w['integral_var']
+        return w['wm'].T.copy(), w['Wc'].transpose(2, 3, 0, 1).copy(), w['Wcc'].transpose(1, 2, 0).copy()
+
+    def optimize(self, log_par_0, fcn_obs, x_obs, method='BFGS', **kwargs):
+        """One ML-II fit per output (bq/bqmod.py:1317-1372), the E fits as ONE `optimize_batch` launch: log_par_0 (E, P), fcn_obs
+        (E, N).  Returns (par (E, P) - the stacked r.x - and the list of scipy.optimize.OptimizeResult), as the reference."""
+        from scipy.optimize import OptimizeResult
+        if not isinstance(method, str) or method.lower() != 'bfgs':
+            raise NotImplementedError('ML-II on the device implements method=\'BFGS\' only, not {!r}'.format(method))
+        kwargs = dict(kwargs)
+        options = dict(kwargs.pop('options', None) or {})
+        tol = kwargs.pop('tol', None)
+        if tol is not None:
+            options.setdefault('gtol', tol)
+        if kwargs:
+            raise TypeError('optimize() got unexpected keyword arguments {}'.format(sorted(kwargs)))
+        lp0 = np.asarray(log_par_0, dtype=np.float64)
+        y = np.asarray(fcn_obs, dtype=np.float64)
+        if lp0.ndim != 2 or y.ndim != 2 or lp0.shape[0] != self.dim_out or y.shape[0] != self.dim_out:
+            raise ValueError('log_par_0 must be (dim_out, P) and fcn_obs (dim_out, N) with dim_out = {}'.format(self.dim_out))
+        r = self.optimize_batch(lp0, y[:, :, None], x_obs, **options)
+        results = []
+        for e in range(self.dim_out):
+            st = int(r['status'][e])
+            results.append(OptimizeResult(x=r['x'][e], fun=float(r['fun'][e]), jac=r['jac'][e], hess_inv=r['hess_inv'][e],
+                                          nit=int(r['nit'][e]), nfev=int(r['nfev'][e]), njev=int(r['njev'][e]), status=st,
+                                          success=st == 0, message=_BFGS_MESSAGES[st] if 0 <= st < 4 else 'status {}'.format(st)))
+        return np.vstack([res.x for res in results]), results
+
+    def predict(self, test_data, fcn_obs, par=None):
+        raise NotImplementedError('the multi-output models have no predict (`pass` in the reference, bq/bqmod.py:1509-1530)')
+
+
+class GaussianProcessMO(MultiOutputModel):
+    """Multi-output GP model (bq/bqmod.py:1481-1560)."""
+
+    def __init__(self, dim_in, dim_out, kern_par, kern_str, point_str, point_par=None):
+        super().__init__(dim_in, dim_out, kern_par, kern_str, point_str, point_par)
+
+    def _ml2_nu(self):
+        return 0.0
+
+    def exp_model_variance(self, fcn_obs):
+        """(E,): alpha_e^2 (1 - tr(Q_ee iK_e)) of the last `bq_weights` (bq/bqmod.py:1532-1537).  alpha_e is taken from the rows
+        given to `bq_weights`; the reference reads the constructor's rows (`kernel.scale`) - the same in every use it makes."""
+        return np.array(self.model_var, dtype=np.float64)
+
+    def integral_variance(self, fcn_obs, par=None):
+        """(E,): kbar_e - q_e' iK_e q_e (bq/bqmod.py:1539-1548)."""
+        return self._device_weights(par)['integral_var']
+
+
+class StudentTProcessMO(MultiOutputModel):
+    """Multi-output Student-t process model (bq/bqmod.py:1563-1640): the GP's weights, the model variance of every output scaled
+    with that output's integrand values."""
+
+    def __init__(self, dim_in, dim_out, kern_par, kern_str, point_str, point_par=None, nu=3.0):
+        super().__init__(dim_in, dim_out, kern_par, kern_str, point_str, point_par)
+        self.nu = 3.0 if nu < 2 else nu
+
+    def _ml2_nu(self):
+        return float(self.nu)
+
+    def exp_model_variance(self, fcn_obs):
+        """(E,): (nu - 2 + fx_e iK_e fx_e') / (nu - 2 + N) * model_var_e for fcn_obs (E, N).  Host arithmetic for callers that ask
+        for the numbers; `apply()` computes them inside the device kernel."""
+        fx = np.asarray(fcn_obs, dtype=np.float64).reshape(self.dim_out, self.num_pts)
+        quad = np.array([fx[e].dot(self.iK[..., e]).dot(fx[e]) for e in range(self.dim_out)])
+        return (self.nu - 2 + quad) / (self.nu - 2 + self.num_pts) * self.model_var
+
+    def integral_variance(self, fcn_obs, par=None):
+        raise NotImplementedError('only the multi-output GP model has an integral variance (bq/bqmod.py:1539-1548)')

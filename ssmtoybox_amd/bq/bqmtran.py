@@ -5,17 +5,22 @@ Constructor signatures, the `wm` / `Wc` / `Wcc` / `I_out` / `model` attributes a
 reference (bq/bqmtran.py:55-130, 285-415) so that code written against it runs unchanged; weights and moments are
 computed by HIP kernels.  `apply_batch()` (many trajectories per launch) is this build's addition.
 """
+import ctypes
+
 import numpy as np
 
+from .. import _lib
 from ..mtran import MomentTransform, _DeviceApply, DeviceTransform
 from .._lib import FORM_BQ, EMV_DIAG, EMV_BROADCAST
-from .bqmod import GaussianProcessModel, StudentTProcessModel, BayesSardModel
+from ..ssmod import user_unsupported, is_user_model
+from .bqmod import (GaussianProcessModel, StudentTProcessModel, BayesSardModel, GaussianProcessMO, StudentTProcessMO,
+                    check_mo_range)
 
 
 class BQTransform(_DeviceApply, MomentTransform):
     """Base class (bq/bqmtran.py:11-130)."""
 
-    _supported_models_ = ['gp', 'tp', 'bs']
+    _supported_models_ = ['gp', 'tp', 'bs', 'gp-mo', 'tp-mo']
 
     def __init__(self, dim_in, dim_out, kern_par, model, kern_str, point_str, point_par, estimate_par, **kwargs):
         self.model = BQTransform._get_model(dim_in, dim_out, model, kern_str, point_str, kern_par, point_par,
@@ -34,6 +39,10 @@ class BQTransform(_DeviceApply, MomentTransform):
             return GaussianProcessModel(dim_in, kern_par, kern_str, point_str, point_par, estimate_par)
         if model == 'tp':
             return StudentTProcessModel(dim_in, kern_par, kern_str, point_str, point_par, estimate_par)
+        if model == 'gp-mo':
+            return GaussianProcessMO(dim_in, dim_out, kern_par, kern_str, point_str, point_par)
+        if model == 'tp-mo':      # unlike 'tp', `nu` is forwarded here (bq/bqmtran.py:278-279)
+            return StudentTProcessMO(dim_in, dim_out, kern_par, kern_str, point_str, point_par, **kwargs)
         return BayesSardModel(dim_in, kern_par, point_str=point_str, point_par=point_par, estimate_par=estimate_par,
                               **kwargs)
 
@@ -110,6 +119,128 @@ class StudentTProcessTransform(BQTransform):
         super().__init__(dim_in, dim_out, kern_par, 'tp', kern_str, point_str, point_par, estimate_par, nu=nu)
         self._set_kernel_attributes(kern_attr)
         self.wm, self.Wc, self.Wcc = self.weights(kern_par)
+
+    def _tp(self):
+        return float(self.model.nu), self.model.iK
+
+
+class _MoDeviceTransform:
+    """Owner of one multi-output `ssmq_transform` handle (`ssmq_transform_create_mo`); constants that were replaced on the Python
+    side go up again through `ssmq_transform_update_mo`."""
+
+    def __init__(self):
+        self._handle = None
+        self._key = None
+        self._snap = None
+
+    def get(self, D, E, N, xi, wm, Wc, Wcc, emv, tp_nu, iK):
+        lib = _lib.load()
+        arrs = [None if a is None else np.ascontiguousarray(a, dtype=np.float64) for a in (xi, wm, Wc, Wcc, emv, iK)]
+        key = (D, E, N, float(tp_nu) > 0.0)
+        snap = (float(tp_nu),) + tuple(None if a is None else a.tobytes() for a in arrs)
+        if self._handle is not None and key == self._key and snap == self._snap:
+            return self._handle
+        ptr = [None if a is None else a.ctypes.data_as(_lib.c_double_p) for a in arrs]
+        if self._handle is not None and key == self._key:
+            _lib.check(lib.ssmq_transform_update_mo(ctypes.c_void_p(self._handle), ptr[0], ptr[1], ptr[2], ptr[3], ptr[4],
+                                                    float(tp_nu), ptr[5]), 'ssmq_transform_update_mo')
+        else:
+            self.close()
+            h = lib.ssmq_transform_create_mo(D, E, N, ptr[0], ptr[1], ptr[2], ptr[3], ptr[4], float(tp_nu), ptr[5])
+            if not h:
+                raise _lib.SsmqError('ssmq_transform_create_mo failed: ' + _lib.last_error())
+            self._handle = h
+        self._key, self._snap = key, snap
+        return self._handle
+
+    def close(self):
+        if self._handle is not None:
+            _lib.load().ssmq_transform_destroy(ctypes.c_void_p(self._handle))
+            self._handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _MultiOutputTransform(BQTransform):
+    """What the two multi-output transforms share (bq/bqmtran.py:425-602).  Deliberate departures from the reference, whose
+    classes are unfinished (SURVEY.md appendix B): the constructor computes and sets wm (N, E), Wc (N, N, E, E), Wcc (D, N, E);
+    `weights(par)` returns the three arrays (the reference unpacks five values from three and raises); the model variance goes on
+    the DIAGONAL of the covariance, as the single-output `model_var * I_out` (the reference adds the (E,) vector to whole
+    columns, which leaves cov_f unsymmetric); `apply` returns fresh arrays (the reference returns its scratch buffers).
+    Moments: mean_f[i] = fx_i . wm[:, i]; cov_f[i, j] = fx_i' Wc[..., i, j] fx_j - mean_f[i] mean_f[j] + delta_ij emv_i;
+    cov_fx[i] = fx_i Wcc[..., i]' L' - one kernel, k_apply_mo.  Runs for D <= 16, E <= 8, N <= 64, the 'rbf' kernel and the
+    built-in models (NotImplementedError otherwise, before anything reaches the library)."""
+
+    def __init__(self, dim_in, dim_out, kern_par, model, kern_str, point_str, point_par, estimate_par, **kwargs):
+        kern_par = np.asarray(kern_par, dtype=np.float64)
+        if kern_par.ndim != 2 or kern_par.shape != (dim_out, dim_in + 1):
+            raise ValueError('kern_par must be (dim_out, 1 + dim_in) = ({}, {}), got {}'.format(dim_out, dim_in + 1, kern_par.shape))
+        check_mo_range(dim_in, dim_out, 0, kern_str)
+        super().__init__(dim_in, dim_out, kern_par, model, kern_str, point_str, point_par, estimate_par, **kwargs)
+        self.e = dim_out
+        self._mo = _MoDeviceTransform()
+        self.wm, self.Wc, self.Wcc = self.weights(kern_par)
+
+    def weights(self, par, *args):
+        return self.model.bq_weights(par)
+
+    def _check_user(self, integ, D):
+        if integ.id >= _lib.F_USER_FIRST:
+            raise user_unsupported('the multi-output transforms (D <= 16, E <= 8, N <= 64, built-in models)')
+
+    def _refuse_user_model(self, f):
+        """A user model (device_code) is refused before its code is registered with the library."""
+        if is_user_model(getattr(f, '__self__', None)):
+            raise user_unsupported('the multi-output transforms (D <= 16, E <= 8, N <= 64, built-in models)')
+
+    def apply_batch(self, f, mean, cov, time=0.0, fcn_pars=None, return_status=False):
+        self._refuse_user_model(f)
+        return super().apply_batch(f, mean, cov, time=time, fcn_pars=fcn_pars, return_status=return_status)
+
+    def apply_batch_dev(self, f, *args, **kwargs):
+        self._refuse_user_model(f)
+        return super().apply_batch_dev(f, *args, **kwargs)
+
+    def kernel_name(self, f):
+        self._refuse_user_model(f)
+        return super().kernel_name(f)
+
+    def _fixed_outputs(self):
+        return self.e
+
+    def _handle_for(self, E):
+        if E not in (1, self.e):      # (1: the sigma points of a Python integrand, which do not depend on E)
+            raise ValueError('the integrand has {} outputs, the transform was built for {}'.format(E, self.e))
+        D, N = self.model.points.shape
+        e = self.e
+        wm, Wc, Wcc = np.asarray(self.wm), np.asarray(self.Wc), np.asarray(self.Wcc)
+        if wm.shape != (N, e) or Wc.shape != (N, N, e, e) or Wcc.shape != (D, N, e):
+            raise ValueError('wm / Wc / Wcc must be (N, E), (N, N, E, E), (D, N, E)')
+        nu, iK = self._tp()
+        return self._mo.get(D, e, N, self.model.points, wm.T, Wc.transpose(2, 3, 0, 1), Wcc.transpose(2, 0, 1),
+                            np.broadcast_to(np.asarray(self.model.model_var, dtype=np.float64), (e,)), nu,
+                            None if iK is None else np.asarray(iK).transpose(2, 0, 1))
+
+
+class MultiOutputGaussianProcessTransform(_MultiOutputTransform):
+    """Multi-output GP quadrature moment transform (bq/bqmtran.py:425-523): one kernel-parameter row per output, kern_par
+    (dim_out, 1 + dim_in)."""
+
+    def __init__(self, dim_in, dim_out, kern_par, kern_str='rbf', point_str='ut', point_par=None, estimate_par=False):
+        super().__init__(dim_in, dim_out, kern_par, 'gp-mo', kern_str, point_str, point_par, estimate_par)
+
+
+class MultiOutputStudentTProcessTransform(_MultiOutputTransform):
+    """Multi-output Student-t process quadrature moment transform (bq/bqmtran.py:526-602): the model variance of output i is
+    scaled by (nu - 2 + fx_i iK_i fx_i') / (nu - 2 + N).  `nu` reaches the model (unlike the single-output 'tp')."""
+
+    def __init__(self, dim_in, dim_out, kern_par, kern_str='rbf', point_str='ut', point_par=None, estimate_par=False,
+                 nu=3.0):
+        super().__init__(dim_in, dim_out, kern_par, 'tp-mo', kern_str, point_str, point_par, estimate_par, nu=nu)
 
     def _tp(self):
         return float(self.model.nu), self.model.iK

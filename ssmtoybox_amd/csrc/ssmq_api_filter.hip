@@ -152,6 +152,11 @@ int filter_forward_impl(ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, ssmq
     }
     const bool user = is_user_integrand(f_dyn) || is_user_integrand(f_obs);
     if (user && (d_pm || d_pP || d_pC)) return refuse_user_integrand("smoother (predictive moments kept)");
+    // a multi-output transform: the Gaussian forward pass through the launch loop, nothing else
+    const bool mo = is_mo(h_dyn) || is_mo(h_obs);
+    if (mo && user) return refuse_user_integrand("multi-output transform (k_apply_mo)");
+    if (mo && (d_pm || d_pP || d_pC)) return refuse_mo("smoother (predictive moments kept)");
+    if (mo && (sscale || student_dof != 0.0)) return refuse_mo("Studentian filter");
     int rc = ensure_device();
     if (rc) return rc;
     if (B == 0) return SSMQ_OK;
@@ -213,6 +218,8 @@ int filter_forward_impl(ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, ssmq
     key.push_back(((uint64_t)D << 48) | ((uint64_t)Y << 32) | ((uint64_t)h_dyn->N << 16) | (uint64_t)h_obs->N);
     key.push_back(((uint64_t)h_dyn->form << 2) | (uint64_t)h_obs->form);
     key.push_back((uint64_t)(uintptr_t)h_obs->d_small);
+    key.push_back((uint64_t)(uintptr_t)h_dyn->d_mo);     // (the multi-output form's constant block: d_small is null there)
+    key.push_back((uint64_t)(uintptr_t)h_obs->d_mo);
     // which kernel variant apply_dev_impl picks depends on the fast paths the handle's CURRENT constants qualify for:
     // ssmq_transform_update keeps the block addresses but may withdraw SSMQ_OPT_LDL (and zero its factors)
     key.push_back(((uint64_t)(uint32_t)h_dyn->opt_mask << 32) | (uint64_t)(uint32_t)h_obs->opt_mask);
@@ -249,7 +256,7 @@ int filter_forward_impl(ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, ssmq
     // one fused kernel for the whole time loop when this (models, shapes, form) combination has one (it does not keep
     // the predictive moments, so a pass that has to store them for the smoother takes the launch loop)
     const bool keep_pred = d_pm && d_pP && d_pC;
-    if (!ssmq::sw("SSMQ_NO_FUSED") && !keep_pred) {
+    if (!ssmq::sw("SSMQ_NO_FUSED") && !keep_pred && !mo) {
         FInfo fio;
         if (!integrand_info(f_obs->id, &fio)) {
             set_error("unknown integrand id");
@@ -335,6 +342,7 @@ static int filter_forward_aug_impl(ssmq_transform *h_dyn, const ssmq_integrand *
                                    double *d_fm, double *d_fP, int32_t *d_status, double *d_pm, double *d_pP,
                                    double *d_pC, int *c_cols) {
     if (is_user_integrand(f_dyn) || is_user_integrand(f_obs)) return refuse_user_integrand("filter with non-additive noise (augmented moments)");
+    if (is_mo(h_dyn) || is_mo(h_obs)) return refuse_mo("filter with non-additive noise (augmented moments)");
     if (!h_dyn || !h_obs || !f_dyn || !f_obs || dim_state <= 0 || dq < 0 || dr < 0 || B < 0 || ld < B || T < 0 || !d_y ||
         !d_m0 || !d_P0 || !d_fm || !d_fP || !d_status || (dq > 0 && (!q_mean || !q_cov)) ||
         (dr > 0 && (!r_mean || !r_cov))) {
@@ -496,6 +504,7 @@ extern "C" int ssmq_filter_smooth_aug_dev(ssmq_transform *h_dyn, const ssmq_inte
                                           double *d_sP, int32_t *d_status) {
     if (is_user_integrand(f_dyn) || is_user_integrand(f_obs)) return refuse_user_integrand("ssmq_filter_smooth_aug_dev");
     SSMQ_HANDLE_LOCK(h_dyn, h_obs);
+    if (is_mo(h_dyn) || is_mo(h_obs)) return refuse_mo("ssmq_filter_smooth_aug_dev");
     if (!h_dyn || !d_sm || !d_sP || dim_state <= 0 || dq < 0 || B < 0 || T < 0 || ld < B) {
         set_error("filter_smooth_aug: bad argument");
         return SSMQ_E_ARG;
@@ -547,6 +556,7 @@ extern "C" int ssmq_filter_smooth_dev(ssmq_transform *h_dyn, const ssmq_integran
                                       double *d_fm, double *d_fP, double *d_sm, double *d_sP, int32_t *d_status) {
     if (is_user_integrand(f_dyn) || is_user_integrand(f_obs)) return refuse_user_integrand("ssmq_filter_smooth_dev");
     SSMQ_HANDLE_LOCK(h_dyn, h_obs);
+    if (is_mo(h_dyn) || is_mo(h_obs)) return refuse_mo("ssmq_filter_smooth_dev");
     if (!h_dyn || !d_sm || !d_sP || B < 0 || T < 0 || ld < B) {
         set_error("filter_smooth: bad argument");
         return SSMQ_E_ARG;
@@ -585,6 +595,7 @@ extern "C" int ssmq_student_filter_forward_dev(ssmq_transform *h_dyn, const ssmq
                                                const double *scale, double dof, double *d_fm, double *d_fP,
                                                int32_t *d_status) {
     SSMQ_HANDLE_LOCK(h_dyn, h_obs);
+    if (is_mo(h_dyn) || is_mo(h_obs)) return refuse_mo("ssmq_student_filter_forward_dev");
     if (!scale || !(dof > 0.0)) {
         set_error("student_filter_forward: scale[T] and dof > 0 are required");
         return SSMQ_E_ARG;
@@ -608,7 +619,9 @@ extern "C" int ssmq_filter_kernel_name_batch(const ssmq_transform *h_dyn, const 
     FilterPass query;
     query.hd = h_dyn; query.fd = f_dyn; query.ho = h_obs; query.fo = f_obs; query.sel_obs = sel_pattern(f_obs, fio.din); query.B = B;
     query.name = &name; query.dry_run = true;
-    int rc = ssmq::sw("SSMQ_NO_FUSED") && !is_user_integrand(f_dyn) && !is_user_integrand(f_obs) ? 0 : try_launch_fused(query);
+    const bool mo = is_mo(h_dyn) || is_mo(h_obs);       // no fused time loop takes the multi-output form
+    if (mo && (is_user_integrand(f_dyn) || is_user_integrand(f_obs))) return refuse_user_integrand("multi-output transform (k_apply_mo)");
+    int rc = mo || (ssmq::sw("SSMQ_NO_FUSED") && !is_user_integrand(f_dyn) && !is_user_integrand(f_obs)) ? 0 : try_launch_fused(query);
     if (rc < 0) return rc;
     snprintf(buf, len, "%s", rc == 1 ? name : "hipGraph of 3 T launches (apply dyn | apply obs | k_kalman_update)");
     return SSMQ_OK;

@@ -226,7 +226,7 @@ int ssmq_sigma_points_batch(ssmq_transform *h, int64_t B, const double *mean, co
     if (rc) return rc;
     if (B == 0) return SSMQ_OK;
     const int D = h->D, N = h->N;
-    if (wide_lds_bytes(D, h->E, N) > 160 * 1024 - 64) return SSMQ_E_UNSUPPORTED;
+    if (!is_mo(h) && wide_lds_bytes(D, h->E, N) > 160 * 1024 - 64) return SSMQ_E_UNSUPPORTED;
     // staging arena: [mean | cov] up, [x | chol | status] down, one transfer each way through the pinned blocks
     const size_t nb = (size_t)B, n_in = nb * ((size_t)D + (size_t)D * D), n_x = nb * D * N, n_l = nb * D * D;
     const size_t in_bytes = sizeof(double) * n_in, out_bytes = sizeof(double) * (n_x + n_l) + sizeof(int32_t) * nb;
@@ -240,13 +240,21 @@ int ssmq_sigma_points_batch(ssmq_transform *h, int64_t B, const double *mean, co
     fast_copy(hin, mean, sizeof(double) * nb * D);
     fast_copy(hin + nb * D, cov, sizeof(double) * n_l);
     SSMQ_HIP(hipMemcpyAsync(dm, hin, in_bytes, hipMemcpyHostToDevice, s));
-    WideArgs a;
-    memset(&a, 0, sizeof(a));
-    a.D = D; a.E = h->E; a.N = N; a.form = h->form; a.mode = SSMQ_WIDE_POINTS; a.consts = h->d_wide;
-    a.cov_scale = a.ccov_scale = 1.0;
-    a.mean = dm; a.cov = dc; a.es_in = 1; a.bs_mean = D; a.bs_cov = D * D; a.status = ds;
-    a.x_out = dx; a.chol_out = dl;
-    if ((rc = hip_fail(launch_apply_wide(a, B, s), "k_apply_wide(points)"))) return rc;
+    if (is_mo(h)) {
+        MoArgs m;
+        memset(&m, 0, sizeof(m));
+        m.D = D; m.E = h->E; m.N = N; m.mode = SSMQ_MO_POINTS; m.consts = h->d_mo; m.cov_scale = m.ccov_scale = 1.0;
+        m.mean = dm; m.cov = dc; m.es_in = 1; m.bs_mean = D; m.bs_cov = D * D; m.status = ds; m.x_out = dx; m.chol_out = dl;
+        if ((rc = launch_apply_mo(m, B, s))) return rc;
+    } else {
+        WideArgs a;
+        memset(&a, 0, sizeof(a));
+        a.D = D; a.E = h->E; a.N = N; a.form = h->form; a.mode = SSMQ_WIDE_POINTS; a.consts = h->d_wide;
+        a.cov_scale = a.ccov_scale = 1.0;
+        a.mean = dm; a.cov = dc; a.es_in = 1; a.bs_mean = D; a.bs_cov = D * D; a.status = ds;
+        a.x_out = dx; a.chol_out = dl;
+        if ((rc = hip_fail(launch_apply_wide(a, B, s), "k_apply_wide(points)"))) return rc;
+    }
     SSMQ_HIP(hipMemcpyAsync(g_stage.hout, dx, out_bytes, hipMemcpyDeviceToHost, s));
     SSMQ_HIP(hipStreamSynchronize(s));
     const double *ho = (const double *)g_stage.hout;
@@ -277,6 +285,31 @@ int ssmq_apply_fx_batch(ssmq_transform *h, int64_t B, const double *chol, const 
     if (rc) return rc;
     if (B == 0) return SSMQ_OK;
     const int D = h->D, E = h->E, N = h->N;
+    if (is_mo(h)) {
+        // the multi-output form: [chol | fx] up, the reductions of k_apply_mo, [mean_f | cov_f | cov_fx] down
+        const size_t nb = (size_t)B, n_l = nb * D * D, n_fx = nb * E * N, n_out = nb * ((size_t)E + (size_t)E * E + (size_t)E * D);
+        const size_t in_bytes = sizeof(double) * (n_l + n_fx), out_bytes = sizeof(double) * n_out, off_out = (in_bytes + 255) / 256 * 256;
+        if ((rc = g_stage.reserve(off_out + out_bytes, in_bytes, out_bytes))) return rc;
+        hipStream_t s = stream();
+        double *dl = (double *)g_stage.dev, *dfx = dl + n_l, *omf = (double *)((char *)g_stage.dev + off_out);
+        double *hin = (double *)g_stage.hin;
+        fast_copy(hin, chol, sizeof(double) * n_l);
+        fast_copy(hin + n_l, fx, sizeof(double) * n_fx);
+        SSMQ_HIP(hipMemcpyAsync(dl, hin, in_bytes, hipMemcpyHostToDevice, s));
+        MoArgs m;
+        memset(&m, 0, sizeof(m));
+        m.D = D; m.E = E; m.N = N; m.mode = SSMQ_MO_FX; m.tp_nu = h->tp_nu; m.cov_scale = m.ccov_scale = 1.0; m.consts = h->d_mo;
+        m.chol_in = dl; m.fx_in = dfx; m.mean_f = omf; m.cov_f = omf + nb * E; m.cov_fx = m.cov_f + nb * E * E;
+        m.es_out = 1; m.bs_mf = E; m.bs_cf = E * E; m.bs_cfx = E * D;
+        if ((rc = launch_apply_mo(m, B, s))) return rc;
+        SSMQ_HIP(hipMemcpyAsync(g_stage.hout, omf, out_bytes, hipMemcpyDeviceToHost, s));
+        SSMQ_HIP(hipStreamSynchronize(s));
+        const double *ho = (const double *)g_stage.hout;
+        fast_copy(mean_f, ho, sizeof(double) * nb * E);
+        fast_copy(cov_f, ho + nb * E, sizeof(double) * nb * E * E);
+        fast_copy(cov_fx, ho + nb * (E + (size_t)E * E), sizeof(double) * nb * E * D);
+        return SSMQ_OK;
+    }
     const bool wide_fits = wide_lds_bytes(D, E, N) <= 160 * 1024 - 64;
     const bool centred = h->form == SSMQ_FORM_SIGMA;
     // point sets beyond the wave kernels without a fused matrix-core instantiation (as apply_dev_impl): blocked GEMM + rest
@@ -374,6 +407,7 @@ int ssmq_apply_fx_batch(ssmq_transform *h, int64_t B, const double *chol, const 
 int ssmq_fxwc_batch_dev(ssmq_transform *h, int64_t M, const double *d_fx, int64_t ld_fx, double *d_t, int64_t ld_t,
                         int *n_padded) {
     SSMQ_HANDLE_LOCK(h);
+    if (is_mo(h)) return refuse_mo("ssmq_fxwc_batch_dev");
     if (h && h->form == SSMQ_FORM_TAYLOR1) {
         set_error("the linearisation transform has no sigma points");
         return SSMQ_E_UNSUPPORTED;

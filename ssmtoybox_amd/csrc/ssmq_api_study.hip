@@ -89,6 +89,8 @@ extern "C" int ssmq_filter_forward_multi_dev(int n_jobs, const ssmq_filter_job *
     if (n_jobs == 0) return SSMQ_OK;
     for (int i = 0; i < n_jobs; ++i)
         if (is_user_integrand(jobs[i].f_dyn) || is_user_integrand(jobs[i].f_obs)) return refuse_user_integrand("ssmq_filter_forward_multi_dev");
+    for (int i = 0; i < n_jobs; ++i)
+        if (is_mo(jobs[i].h_dyn) || is_mo(jobs[i].h_obs)) return refuse_mo("ssmq_filter_forward_multi_dev");
     std::vector<const ssmq_transform *> hs;
     for (int i = 0; i < n_jobs; ++i) {
         const ssmq_filter_job &j = jobs[i];
@@ -476,6 +478,7 @@ extern "C" int ssmq_filter_forward_piped(ssmq_transform *h_dyn, const ssmq_integ
                                          int64_t B, int T, const double *y, const double *m0, const double *P0, const double *GQG,
                                          const double *R, double *fm, double *fP, int32_t *status, int flags, int n_blocks) {
     if (is_user_integrand(f_dyn) || is_user_integrand(f_obs)) return refuse_user_integrand("ssmq_filter_forward_piped");
+    if (is_mo(h_dyn) || is_mo(h_obs)) return refuse_mo("ssmq_filter_forward_piped");
     SSMQ_HANDLE_LOCK(h_dyn, h_obs);
     if (!h_dyn || !h_obs || !f_dyn || !f_obs || B < 0 || T < 0 || !y || !m0 || !P0 || !fm || !fP || !status || n_blocks < 0) {
         set_error("filter_forward_piped: bad argument");

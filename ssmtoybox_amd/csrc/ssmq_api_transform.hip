@@ -438,6 +438,23 @@ int apply_dev_impl(ssmq_transform *h, const ssmq_integrand *f, int64_t B, int64_
         set_error("apply: null pointer or ld < B");
         return true;
     };
+    if (is_mo(h)) {
+        // the multi-output form: one kernel for the whole supported range (ssmq_apply_mo.hip), built-in integrands
+        if (is_user_integrand(f)) return refuse_user_integrand("multi-output transform (k_apply_mo)");
+        if (kernel_name) *kernel_name = "k_apply_mo";
+        if (dry_run || B <= 0) return SSMQ_OK;
+        if (null_args()) return SSMQ_E_ARG;
+        MoArgs m;
+        memset(&m, 0, sizeof(m));
+        m.D = h->D; m.E = h->E; m.N = h->N; m.mode = SSMQ_MO_FULL; m.fid = f->id; m.time_stride = d_time ? time_stride : 0;
+        m.tp_nu = h->tp_nu; m.cov_scale = cov_scale; m.ccov_scale = ccov_scale; m.consts = h->d_mo; m.cov_add = d_cov_add;
+        m.mean = d_mean; m.cov = d_cov; m.time = d_time; m.es_in = ld; m.bs_mean = m.bs_cov = 1;
+        m.mean_f = d_mean_f; m.cov_f = d_cov_f; m.cov_fx = d_cov_fx; m.es_out = ld; m.bs_mf = m.bs_cf = m.bs_cfx = 1;
+        m.status = d_status;
+        fill_fpar(f, &m.fp);
+        m.fp.ttab = ttab;
+        return launch_apply_mo(m, B, stream());
+    }
     // argument block of the register-resident kernels; fp.ttab stays null (the table route sets it, the user route has no table)
     auto fill_args = [&](ApplyArgs &a) {
         a.mean = d_mean; a.cov = d_cov; a.time = d_time ? d_time : d_mean; a.mean_f = d_mean_f; a.cov_f = d_cov_f;
@@ -657,6 +674,7 @@ ssmq_transform *ssmq_transform_create_linear(int D, int E) {
 int ssmq_transform_update(ssmq_transform *h, const double *xi, const double *wm, const double *Wc, const double *Wcc,
                           const double *emv, int emv_mode, double tp_nu, const double *tp_iK) {
     SSMQ_HANDLE_LOCK(h);
+    if (is_mo(h)) return refuse_mo("ssmq_transform_update (use ssmq_transform_update_mo)");
     if (h && h->form == SSMQ_FORM_TAYLOR1) {
         set_error("transform_update: the linearisation transform has no constants");
         return SSMQ_E_ARG;
@@ -686,6 +704,7 @@ void ssmq_transform_destroy(ssmq_transform *h) {
         SSMQ_HANDLE_LOCK(h);
         if (ssmq::stream()) hipStreamSynchronize(ssmq::stream());
     }   // ... and nobody may hold the handle any more: destroying it while another thread uses it is the caller's error
+    if (h->d_mo) hipFree(h->d_mo);
     if (h->d_small) hipFree(h->d_small);
     if (h->d_wide) hipFree(h->d_wide);
     if (h->d_wc_pad) hipFree(h->d_wc_pad);

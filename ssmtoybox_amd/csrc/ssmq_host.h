@@ -30,6 +30,10 @@ struct ssmq_transform {
     // kBigCols columns, each [big_kb 16][kBigCols] zero-padded (ssmq_apply_big.hip); null = not built
     double *d_wc_blk = nullptr, *d_ik_blk = nullptr;
     int big_kb = 0, big_ncb = 0;   // k blocks of 16 points; column blocks of [Wc | pad to 16 big_kb | Wcc'] (big_ncb)
+    // multi-output form (SSMQ_FORM_BQ_MO, ssmq_apply_mo.hip): the host vectors above hold wm [E][N], Wc as the blocks (i, j), i >= j,
+    // in packed order [i (i + 1) / 2 + j][N][N], Wcc [E][D][N], emv [E], iK [E][N][N]; d_mo is the one constant block (mo_layout),
+    // d_small / d_wide stay null
+    double *d_mo = nullptr;
     uint32_t generation = 0;   // bumped by every upload of constants (create / update)
     // Threads (include/ssmq.h, conventions): every entry point that takes this handle holds `mu` for its duration; `owner` /
     // `owner_epoch` name the thread context (its stream) that used the handle last - another context waits for that stream
@@ -182,6 +186,27 @@ int apply_dev_impl(ssmq_transform *h, const ssmq_integrand *f, int64_t B, int64_
                    const double *d_time, int time_stride, double *d_mean_f, double *d_cov_f, double *d_cov_fx, int32_t *d_status,
                    const double *d_cov_add, const char **kernel_name, bool dry_run, double cov_scale = 1.0, double ccov_scale = 1.0,
                    const double *ttab = nullptr, bool stream_out = true);
+
+// the multi-output form (ssmq_apply_mo.hip): one kernel for the whole transform, the sigma points alone (x_out / chol_out) or the
+// reductions alone (chol_in / fx_in); element e of trajectory b at ptr[e * es + b * bs]
+inline bool is_mo(const ssmq_transform *h) { return h && h->form == SSMQ_FORM_BQ_MO; }
+int refuse_mo(const char *what);   // sets the error text, returns SSMQ_E_UNSUPPORTED
+enum { SSMQ_MO_FULL = 0, SSMQ_MO_POINTS = 1, SSMQ_MO_FX = 2 };
+struct MoArgs {
+    int D, E, N, mode, fid, time_stride;
+    double tp_nu, cov_scale, ccov_scale;
+    const double *consts;          // mo_layout block
+    const double *cov_add;         // [E*E] or null
+    const double *mean, *cov, *time;
+    int64_t es_in, bs_mean, bs_cov;
+    double *mean_f, *cov_f, *cov_fx;
+    int64_t es_out, bs_mf, bs_cf, bs_cfx;
+    int32_t *status;               // [B] or null
+    double *x_out, *chol_out;      // SSMQ_MO_POINTS: [B][D][N], [B][D][D]
+    const double *chol_in, *fx_in; // SSMQ_MO_FX: [B][D][D], [B][E][N]
+    FPar fp;
+};
+int launch_apply_mo(const MoArgs &a, int64_t B, hipStream_t s);
 
 // dispatch table of the register-resident kernels (ssmq_small_*.hip)
 typedef hipError_t (*small_launch_fn)(const ApplyArgs &, hipStream_t);

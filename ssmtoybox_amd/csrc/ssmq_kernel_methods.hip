@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <vector>
 #include "ssmq_weights_host.h"
+#include "ssmq_rbf_kxkx.h"
 #include "ssmq_blockla.h"
 
 namespace ssmq {
@@ -80,35 +81,12 @@ __global__ __launch_bounds__(BLOCK) void k_rbf_factor(int D, int N, const double
     }
 }
 
-// Q[i][j] = det(R)^-1/2 exp(xi_i + xi'_j + maha(Lam0^-1 x_i, -Lam1^-1 x_j; R^-1) / 2), R = Lam0^-1 + Lam1^-1 + I,
-// xi = 2 log(alpha0) - |Lam0^-1/2 x_i|^2 / 2, xi' likewise with row 1 (all matrices diagonal)
+// Q = exp_x_kxkx(par0, par1): the entry arithmetic of ssmq_rbf_kxkx.h
 __global__ void k_rbf_kxkx(int D, int N, const double *__restrict__ x, const double *__restrict__ par0,
                            const double *__restrict__ par1, int scaling, double *__restrict__ Q) {
-    const double la0 = scaling ? 2.0 * log(par0[0]) : 2.0 * log(1.0), la1 = scaling ? 2.0 * log(par1[0]) : 2.0 * log(1.0);
-    double det = 1.0;
-    for (int d = 0; d < D; ++d) {
-        const double s0 = 1.0 / par0[1 + d], s1 = 1.0 / par1[1 + d];
-        det *= (s0 * s0 + s1 * s1) + 1.0;
-    }
-    const double c = 1.0 / sqrt(det);
-    for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < N * N; idx += gridDim.x * blockDim.x) {
-        const int i = idx / N, j = idx % N;
-        double n0 = 0.0, n1 = 0.0, m2i = 0.0, m2j = 0.0, mij = 0.0;
-        for (int d = 0; d < D; ++d) {
-            const double s0 = 1.0 / par0[1 + d], s1 = 1.0 / par1[1 + d];
-            const double il0 = s0 * s0, il1 = s1 * s1;
-            const double z0 = s0 * x[d * N + i], z1 = s1 * x[d * N + j];
-            n0 += z0 * z0;
-            n1 += z1 * z1;
-            const double v = 1.0 / ((il0 + il1) + 1.0);
-            const double yi = il0 * x[d * N + i], yj = -(il1 * x[d * N + j]);
-            m2i += (yi * v) * yi;
-            m2j += (yj * v) * yj;
-            mij += (yi * v) * yj;
-        }
-        const double mh = (m2i + m2j) - 2.0 * mij;
-        Q[idx] = c * exp(((la0 - 0.5 * n0) + (la1 - 0.5 * n1)) + 0.5 * mh);
-    }
+    const RbfKxkxPre pre = rbf_kxkx_pre(D, par0, par1, scaling);
+    for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < N * N; idx += gridDim.x * blockDim.x)
+        Q[idx] = rbf_kxkx_entry(D, N, x, par0, par1, pre, idx / N, idx % N);
 }
 
 static bool rbf_args_ok(int D, int N, const double *x, const double *par, int P) {

@@ -149,8 +149,8 @@ class _DeviceApply:
                 if fx0 is None:
                     fx0 = np.full((B,) + fxb.shape, np.nan)
                 fx0[b] = fxb
-            if fx0 is None:
-                fx0 = np.full((B, 1, N), np.nan)
+            if fx0 is None:            # every covariance failed: NaN values of the transform's own output count (1 unless it is fixed)
+                fx0 = np.full((B, self._fixed_outputs(), N), np.nan)
             E = fx0.shape[1]
             h = self._handle_for(E)
             fx0, pfx = _lib.as_c(fx0)
@@ -176,6 +176,10 @@ class _DeviceApply:
                                                     cov.ptr, ctypes.c_void_p(time.ptr), time_stride, mean_f.ptr,
                                                     cov_f.ptr, cov_fx.ptr, ctypes.c_void_p(status.ptr)),
                    'ssmq_apply_batch_dev')
+
+    def _fixed_outputs(self):
+        """Outputs of a Python integrand when none could be evaluated; transforms bound to one output count override it."""
+        return 1
 
     def _check_user(self, integ, D):
         """A user-defined integrand (device_code) runs on 2 .. 2 D + 1 points only: NotImplementedError beyond, naming the range."""

@@ -22,7 +22,8 @@ import numpy as np
 from . import _lib
 from .mtran import (MomentTransform, LinearizationTransform, UnscentedTransform, SphericalRadialTransform, GaussHermiteTransform,
                     FullySymmetricStudentTransform, resolve_integrand)
-from .bq.bqmtran import GaussianProcessTransform, BayesSardTransform, StudentTProcessTransform
+from .bq.bqmtran import (GaussianProcessTransform, BayesSardTransform, StudentTProcessTransform,
+                         MultiOutputGaussianProcessTransform)
 from .ssmod import TransitionModel, MeasurementModel, is_user_model, user_unsupported, check_user_points
 
 
@@ -294,6 +295,8 @@ def run_filters(algs, data, x0_mean=None, x0_cov=None, raise_on_failure=True):
     for a in algs:
         if not isinstance(a, GaussianInference) or not a._additive:
             raise NotImplementedError('run_filters: additive-noise Gaussian / Studentian filters only')
+        if isinstance(a, MultiOutputGaussianProcessKalman):
+            raise NotImplementedError('run_filters: not implemented for the multi-output filter (its forward pass is a launch loop)')
         if a.mod_obs.dim_out != Y:
             raise ValueError('run_filters: every filter must take the same measurements')
     d_y = _lib.scratch(8 * T * Y * ld)
@@ -392,6 +395,33 @@ class GaussianProcessKalman(GaussianInference):
         t_dyn = GaussianProcessTransform(dyn.dim_in, dyn.dim_state, kern_par_dyn, kernel, points, point_hyp)
         t_obs = GaussianProcessTransform(obs.dim_in, obs.dim_out, kern_par_obs, kernel, points, point_hyp)
         super().__init__(dyn, obs, t_dyn, t_obs)
+
+
+class MultiOutputGaussianProcessKalman(GaussianInference):
+    """GP quadrature Kalman filter with one kernel-parameter row per output (ssinf.py:911-961): kern_par_dyn (dim_state, 1 +
+    dim_in), kern_par_obs (dim_out, 1 + dim_in).  The forward pass runs as the launch loop (apply dyn | apply obs | update per
+    step, both transforms k_apply_mo); additive noise and the built-in models only; the smoother and `run_filters` are not
+    implemented for it."""
+
+    def __init__(self, dyn, obs, kern_par_dyn, kern_par_obs, kernel='rbf', points='ut', point_hyp=None):
+        if is_user_model(dyn) or is_user_model(obs):
+            raise user_unsupported('the multi-output transforms (D <= 16, E <= 8, N <= 64, built-in models)')
+        if not (dyn.noise_additive and obs.noise_additive):
+            raise NotImplementedError('MultiOutputGaussianProcessKalman runs for additive-noise models only')
+        t_dyn = MultiOutputGaussianProcessTransform(dyn.dim_in, dyn.dim_state, kern_par_dyn, kernel, points, point_hyp)
+        t_obs = MultiOutputGaussianProcessTransform(obs.dim_in, obs.dim_out, kern_par_obs, kernel, points, point_hyp)
+        super().__init__(dyn, obs, t_dyn, t_obs)
+
+    def backward_pass(self):
+        raise NotImplementedError('the RTS smoother is not implemented for the multi-output filter')
+
+    def backward_pass_batch(self):
+        raise NotImplementedError('the RTS smoother is not implemented for the multi-output filter')
+
+    def forward_pass_batch(self, data, x0_mean=None, x0_cov=None, raise_on_failure=True, smooth=False):
+        if smooth:
+            raise NotImplementedError('the RTS smoother is not implemented for the multi-output filter')
+        return super().forward_pass_batch(data, x0_mean=x0_mean, x0_cov=x0_cov, raise_on_failure=raise_on_failure)
 
 
 class BayesSardKalman(GaussianInference):
