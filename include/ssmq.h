@@ -699,6 +699,39 @@ int ssmq_lcr_sums_dev(int D, int64_t B, int64_t ld, int T, const double *d_x, co
                       const int32_t *d_status, const double *mse, double *sums);
 
 /*
+ * The time-averaged scores of every trajectory - what the reference's studies hand to bootstrap_var (utils.py:223-244) for their
+ * "+- 2 sqrt(var)" columns.  Inputs as for ssmq_error_sums_dev; the steps k0 .. T-1 enter (0 <= k0 < T; the studies skip step 0).
+ * d_scores: device [D + 3][ld], R = ssmq_traj_scores_rows(D) = D + 3 rows, for trajectory b:
+ *   rows 0 .. D-1  sqrt(mean_k (x - m)_d^2)   per-dimension RMSE (research/bsq/bsq_ungm.py:32)
+ *   row  D         mean_k ||x - m||           (research/tpq/tpq_base.py:154-160; the convention of the `rmse` sum above)
+ *   row  D + 1     mean_k of the negative log-likelihood
+ *   row  D + 2     mean_k of the log credibility ratio against mse [T][D*D] (host, regularisation already added); NaN if mse == NULL
+ * A P that is not positive definite takes the fallbacks of the sums (LU for the NLL, the quadratic form with |P| for the LCR); a
+ * singular P leaves NaN in row D + 1, an mse[k] that is not positive definite NaN in row D + 2.  Excluded trajectories (nonzero
+ * status) and the padding lanes B .. ld-1 are NaN in every row.  Synchronous.
+ */
+int ssmq_traj_scores_rows(int D);
+int ssmq_traj_scores_dev(int D, int64_t B, int64_t ld, int T, int k0, const double *d_x, const double *d_fm, const double *d_fP,
+                         const int32_t *d_status, const double *mse, double *d_scores);
+
+/*
+ * Bootstrap variance of the mean (utils.py:223-244 bootstrap_var) of each of the R rows of a device block d_data [R][ld], without
+ * the reference's (S, n) matrix of draws: S resamples of n entries, drawn with replacement from the n included entries d_idx [n]
+ * (device; values in 0 .. ld-1; NULL = the entries 0 .. n-1), mean_s = (1 / n) sum_i data[idx[j(s, i)]], var[r] = numpy.var
+ * (ddof 0, two-pass) of the S means of row r.  The draw (csrc/ssmq_bootstrap.hip states it in full):
+ *   (o0, o1, o2, o3) = Philox4x32-10(counter (i >> 1, 0, s, 0xB0075747), key (seed lo, seed hi));
+ *   word = o0 | o1 << 32 for even i, o2 | o3 << 32 for odd i;   j(s, i) = (word * n) >> 64.
+ * The draws are shared by the rows (row r of an R-row call is the one-row call on that row, bit for bit), and the summation order
+ * depends on n alone: the same (data, idx, S, seed) gives the same bits on every device.  A NaN among the included values
+ * propagates.  d_means: device [R][S], receives the resample means, or NULL.  var: host [R].
+ * 1 <= n < 2^31, n <= ld, 1 <= S <= 2^20, 1 <= R <= 19 (SSMQ_E_ARG otherwise, before the device is touched).  Synchronous.
+ * ssmq_bootstrap_var: one row of n entries in a host array.
+ */
+int ssmq_bootstrap_var_dev(const double *d_data, int64_t ld, int R, const int32_t *d_idx, int64_t n, int S, uint64_t seed,
+                           double *var, double *d_means);
+int ssmq_bootstrap_var(const double *data, int64_t n, int S, uint64_t seed, double *var);
+
+/*
  * Forward pass of a Studentian filter (ssinf.py:555-736: StudentianInference._time_update / _measurement_update) for B
  * trajectories.  Same loop as ssmq_filter_forward_dev with the reference's scale-matrix bookkeeping:
  *   transforms are fed the SCALE matrix; scale[k] * cov_f (+ G q_smat G') and scale[k] * (cov_f, cov_fx) (+ r_smat)

@@ -219,6 +219,12 @@ _PROTOTYPES = {
                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_double_p]),
     'ssmq_lcr_sums_dev': (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p,
                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_double_p, c_double_p]),
+    'ssmq_traj_scores_rows': (ctypes.c_int, [ctypes.c_int]),
+    'ssmq_traj_scores_dev': (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_double_p, ctypes.c_void_p]),
+    'ssmq_bootstrap_var_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64,
+                                              ctypes.c_int, ctypes.c_uint64, c_double_p, ctypes.c_void_p]),
+    'ssmq_bootstrap_var': (ctypes.c_int, [c_double_p, ctypes.c_int64, ctypes.c_int, ctypes.c_uint64, c_double_p]),
     'ssmq_filter_kernel_name': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Integrand), ctypes.c_void_p,
                                                ctypes.POINTER(Integrand), ctypes.c_char_p, ctypes.c_int]),
     'ssmq_filter_kernel_name_batch': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Integrand), ctypes.c_void_p,

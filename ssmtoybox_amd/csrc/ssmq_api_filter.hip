@@ -691,6 +691,29 @@ extern "C" int ssmq_lcr_sums_dev(int D, int64_t B, int64_t ld, int T, const doub
     return metrics_impl(2, D, B, ld, T, d_x, d_fm, d_fP, d_status, mse, sums);
 }
 
+extern "C" int ssmq_traj_scores_rows(int D) { return D >= 1 && D <= SSMQ_MAX_DIM ? D + 3 : SSMQ_E_ARG; }
+
+extern "C" int ssmq_traj_scores_dev(int D, int64_t B, int64_t ld, int T, int k0, const double *d_x, const double *d_fm,
+                                    const double *d_fP, const int32_t *d_status, const double *mse, double *d_scores) {
+    if (D < 1 || D > SSMQ_MAX_DIM || B < 0 || ld < B || ld < 1 || T < 1 || k0 < 0 || k0 >= T || !d_x || !d_fm || !d_fP || !d_scores) {
+        set_error("traj_scores: bad argument (1 <= D <= 16, 0 <= B <= ld, 0 <= k0 < T)");
+        return SSMQ_E_ARG;
+    }
+    int rc = ensure_device();
+    if (rc) return rc;
+    hipStream_t s = stream();
+    DevBuf dm;
+    if (mse) {
+        if ((rc = dm.alloc(sizeof(double) * (size_t)T * D * D))) return rc;
+        SSMQ_HIP(hipMemcpyAsync(dm.p, mse, sizeof(double) * (size_t)T * D * D, hipMemcpyHostToDevice, s));
+    }
+    rc = launch_traj_scores(D, B, ld, T, k0, d_x, d_fm, d_fP, d_status, mse ? dm.d() : nullptr, d_scores, s);
+    hipError_t e = hipStreamSynchronize(s);
+    if (rc) return rc;
+    SSMQ_HIP(e);
+    return SSMQ_OK;
+}
+
 extern "C" int ssmq_simulate_rv_dev(const ssmq_integrand *f_dyn, const ssmq_integrand *f_obs, int D, int Y, const ssmq_rv *x0,
                                     const ssmq_rv *q, const ssmq_rv *r, const double *G, int dyn_additive, int obs_additive,
                                     int64_t B, int64_t ld, int T, int continuous, double dt, uint64_t seed,

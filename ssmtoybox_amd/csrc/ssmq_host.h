@@ -425,6 +425,12 @@ int launch_metrics(int phase, int D, int64_t B, int64_t ld, int T, const double 
 int launch_metrics_indef(int phase, int D, int64_t B, int64_t ld, int T, const double *x, const double *fm, const double *fP,
                          const int32_t *status, const double *mse, double *partial, double *out, hipStream_t s);
 
+// time-averaged scores of every trajectory (ssmq_metrics.hip: k_traj_scores); mse: device [T][D*D] or null
+int launch_traj_scores(int D, int64_t B, int64_t ld, int T, int k0, const double *x, const double *fm, const double *fP,
+                       const int32_t *status, const double *mse, double *scores, hipStream_t s);
+// bootstrap variance of the mean of the rows of a [R][ld] block (ssmq_bootstrap.hip); the range the entry points accept
+bool bootstrap_range_ok(int64_t n, int S, int R);
+
 // the stages of the theta-batched step (ssmq_api_theta.hip): GP weights of every item as its own constant block
 // (ssmq_weights.hip) ...
 size_t gp_weights_wide_ws_bytes(int D, int N, int64_t P);

@@ -123,6 +123,52 @@ __device__ __forceinline__ double whitened_norm2_packed(const double (&L)[D * (D
     return q;
 }
 
+// ---- item bodies: one (trajectory, step) entry, shared by the sums over the Monte-Carlo axis (k_error_sums, k_lcr_sums, their
+// run-time-sized forms, k_indef_sums) and the per-trajectory scores (k_traj_scores) ---------------------------------------------
+// negative log-likelihood (utils.py:143-148) for positive-definite P: log det = 2 sum log L_ii.  L: lower triangle of P on entry,
+// its Cholesky factor on return.  The entry's term is added to `sum` (every item below adds in place: the sums keep the fused
+// multiply-add they have always ended in); false, `sum` untouched, if P is not positive definite
+template <int D>
+__device__ __forceinline__ bool nll_item(double (&L)[D * (D + 1) / 2], const double (&dx)[D], double &sum) {
+    if (!chol_packed<D>(L)) return false;
+    double logdet = 0.0;
+#pragma unroll
+    for (int i = 0; i < D; ++i) logdet += log(L[SSMQ_PK(i, i)]);
+    const double q = whitened_norm2_packed<D>(L, dx);
+    sum += 0.5 * (2.0 * logdet + q + D * 1.8378770664093453 /* log(2 pi) */);
+    return true;
+}
+
+// ... run-time D, P dense (lower triangle filled)
+__device__ __forceinline__ bool nll_item_dense(double *P, const double *dx, int D, double &sum) {
+    if (!chol_dense<0>(P, D)) return false;
+    double logdet = 0.0;
+    for (int i = 0; i < D; ++i) logdet += log(P[i * D + i]);
+    const double q = whitened_norm2<0>(P, dx, D);
+    sum += 0.5 * (2.0 * logdet + q + D * 1.8378770664093453);
+    return true;
+}
+
+// log credibility ratio (utils.py:113-120) from the two quadratic forms dx' P^-1 dx and dx' M^-1 dx
+__device__ __forceinline__ void lcr_add(double qa, double qb, double &sum) { sum += 10.0 * (log10(qa) - log10(qb)); }
+
+// ... for positive-definite P (L as in nll_item) against the factored MSE matrix M
+template <int D>
+__device__ __forceinline__ bool lcr_item(double (&L)[D * (D + 1) / 2], const double (&M)[D * (D + 1) / 2], const double (&dx)[D],
+                                         double &sum) {
+    if (!chol_packed<D>(L)) return false;              // the reference's SVD square root (utils.py:426-432): lcr_item_indef
+    const double qa = whitened_norm2_packed<D>(L, dx), qb = whitened_norm2_packed<D>(M, dx);
+    lcr_add(qa, qb, sum);
+    return true;
+}
+
+__device__ __forceinline__ bool lcr_item_dense(double *P, const double *M, const double *dx, int D, double &sum) {
+    if (!chol_dense<0>(P, D)) return false;
+    const double qa = whitened_norm2<0>(P, dx, D), qb = whitened_norm2<0>(M, dx, D);
+    lcr_add(qa, qb, sum);
+    return true;
+}
+
 // phase 1 values per time step (output): se[D] | rmse | nll | mse[D*D] | n_ok | n_pd.
 // Compile-time D: accumulators se[D], rmse, nll, lower triangle of the outer products, two counts - all in registers;
 // the partial row is written in the packed order and expanded by k_reduce_partials.
@@ -161,15 +207,7 @@ __global__ __launch_bounds__(kMetBlock) void k_error_sums(MetArgs a) {
 #pragma unroll
             for (int j = 0; j <= i; ++j) acc[D + 2 + SSMQ_PK(i, j)] += dx[i] * dx[j];
         acc[D + 2 + TRI] += 1.0;
-        // negative log-likelihood (utils.py:143-148) for positive-definite P: log det = 2 sum log L_ii
-        if (chol_packed<D>(L)) {
-            double logdet = 0.0;
-#pragma unroll
-            for (int i = 0; i < D; ++i) logdet += log(L[SSMQ_PK(i, i)]);
-            const double q = whitened_norm2_packed<D>(L, dx);
-            acc[D + 1] += 0.5 * (2.0 * logdet + q + D * 1.8378770664093453 /* log(2 pi) */);
-            acc[D + 3 + TRI] += 1.0;
-        }
+        if (nll_item<D>(L, dx, acc[D + 1])) acc[D + 3 + TRI] += 1.0;
     }
     block_sums_fixed<NA>(acc, sh, a.partial + ((int64_t)t * a.chunks + blockIdx.x) * NA);
 }
@@ -202,13 +240,7 @@ __global__ __launch_bounds__(kMetBlock) void k_error_sums_generic(MetArgs a) {
                 P[i * D + j] = fP[((int64_t)i * D + j) * a.ld + b];
             }
         acc[D + 2 + TRI] += 1.0;
-        if (chol_dense<0>(P, D)) {
-            double logdet = 0.0;
-            for (int i = 0; i < D; ++i) logdet += log(P[i * D + i]);
-            const double q = whitened_norm2<0>(P, dx, D);
-            acc[D + 1] += 0.5 * (2.0 * logdet + q + D * 1.8378770664093453);
-            acc[D + 3 + TRI] += 1.0;
-        }
+        if (nll_item_dense(P, dx, D, acc[D + 1])) acc[D + 3 + TRI] += 1.0;
     }
     block_sums(acc, NA, sh, a.partial + ((int64_t)t * a.chunks + blockIdx.x) * NA);
 }
@@ -241,12 +273,10 @@ __global__ __launch_bounds__(kMetBlock) void k_lcr_sums(MetArgs a) {
         for (int i = 0; i < D; ++i)
 #pragma unroll
             for (int j = 0; j <= i; ++j) L[SSMQ_PK(i, j)] = SSMQ_MLOAD(fP[((int64_t)i * D + j) * a.ld + b]);
-        if (!chol_packed<D>(L)) {              // the reference's SVD square root (utils.py:426-432): k_indef_sums
+        if (!lcr_item<D>(L, M, dx, acc[0])) {   // left to k_indef_sums
             acc[2] += 1.0;
             continue;
         }
-        const double qa = whitened_norm2_packed<D>(L, dx), qb = whitened_norm2_packed<D>(M, dx);
-        acc[0] += 10.0 * (log10(qa) - log10(qb));
         acc[1] += 1.0;
     }
     block_sums_fixed<3>(acc, sh, a.partial + ((int64_t)t * a.chunks + blockIdx.x) * 3);
@@ -271,12 +301,10 @@ __global__ __launch_bounds__(kMetBlock) void k_lcr_sums_generic(MetArgs a) {
         for (int d = 0; d < D; ++d) dx[d] = x[(int64_t)d * a.ld + b] - fm[(int64_t)d * a.ld + b];
         for (int i = 0; i < D; ++i)
             for (int j = 0; j <= i; ++j) P[i * D + j] = fP[((int64_t)i * D + j) * a.ld + b];
-        if (!chol_dense<0>(P, D)) {
+        if (!lcr_item_dense(P, M, dx, D, acc[0])) {
             acc[2] += 1.0;
             continue;
         }
-        const double qa = whitened_norm2<0>(P, dx, D), qb = whitened_norm2<0>(M, dx, D);
-        acc[0] += 10.0 * (log10(qa) - log10(qb));
         acc[1] += 1.0;
     }
     block_sums(acc, 3, sh, a.partial + ((int64_t)t * a.chunks + blockIdx.x) * 3);
@@ -369,6 +397,25 @@ __device__ double abs_quadratic_form(double *S, double *V, const double *dx, int
     return q;
 }
 
+// The two items for a P that is not positive definite.  P: the full matrix (destroyed); z, W: work space of D and D * D doubles.
+// false: P is singular (numpy.linalg.inv raises there) and the entry has no term.
+__device__ __forceinline__ bool nll_item_indef(double *P, const double *dx, double *z, int D, double &sum) {
+    double sign, logabs;
+    if (!lu_solve_logdet(P, dx, z, D, &sign, &logabs)) return false;
+    double q = 0.0;
+    for (int d = 0; d < D; ++d) q += dx[d] * z[d];
+    sum += 0.5 * (sign * logabs + q + D * 1.8378770664093453);
+    return true;
+}
+
+// qb: dx' M^-1 dx of the same entry
+__device__ __forceinline__ void lcr_item_indef(double *P, double *W, const double *dx, double qb, int D, double &sum) {
+    for (int i = 0; i < D; ++i)
+        for (int j = 0; j < D; ++j) W[i * D + j] = 0.5 * (P[i * D + j] + P[j * D + i]);
+    const double qa = abs_quadratic_form(W, P, dx, D);
+    lcr_add(qa, qb, sum);
+}
+
 __global__ __launch_bounds__(kMetBlock) void k_indef_sums(MetArgs a, int phase) {
     const int D = a.D;
     const int t = blockIdx.y;
@@ -394,21 +441,124 @@ __global__ __launch_bounds__(kMetBlock) void k_indef_sums(MetArgs a, int phase) 
         for (int d = 0; d < D; ++d) dx[d] = x[(int64_t)d * a.ld + b] - fm[(int64_t)d * a.ld + b];
         for (int i = 0; i < D * D; ++i) P[i] = fP[(int64_t)i * a.ld + b];
         if (phase == 1) {
-            double sign, logabs;
-            if (!lu_solve_logdet(P, dx, z, D, &sign, &logabs)) continue;
-            double q = 0.0;
-            for (int d = 0; d < D; ++d) q += dx[d] * z[d];
-            acc[0] += 0.5 * (sign * logabs + q + D * 1.8378770664093453);
+            if (!nll_item_indef(P, dx, z, D, acc[0])) continue;
             acc[1] += 1.0;
         } else {
-            for (int i = 0; i < D; ++i)
-                for (int j = 0; j < D; ++j) W[i * D + j] = 0.5 * (P[i * D + j] + P[j * D + i]);
-            const double qa = abs_quadratic_form(W, P, dx, D), qb = whitened_norm2<0>(M, dx, D);
-            acc[0] += 10.0 * (log10(qa) - log10(qb));
+            lcr_item_indef(P, W, dx, whitened_norm2<0>(M, dx, D), D, acc[0]);
             acc[1] += 1.0;
         }
     }
     block_sums(acc, 2, sh, a.partial + ((int64_t)t * a.chunks + blockIdx.x) * 2);
+}
+
+// ---- per-trajectory scores -----------------------------------------------------------------------------------------------------
+// What the reference's studies resample (utils.py:223-244 bootstrap_var on the time-averaged score of every trajectory): for
+// trajectory b, over the steps k0 .. T - 1,
+//   rows 0 .. D-1  sqrt(mean_k (x - m)_d^2)      (research/bsq/bsq_ungm.py:32)
+//   row  D         mean_k ||x - m||              (research/tpq/tpq_base.py:154-160)
+//   row  D + 1     mean_k negative log-likelihood
+//   row  D + 2     mean_k log credibility ratio against mse[k]; NaN without mse
+// One lane per trajectory, the same coalesced plane reads as k_error_sums, the item bodies above.  A P that is not positive
+// definite takes the fallbacks of k_indef_sums in place (traj_items_indef); a singular P, or an MSE matrix that is not positive
+// definite, leaves NaN in that row, as the sums leave such entries out.  Excluded trajectories and the lanes B .. ld-1: NaN.
+struct ScoreArgs {
+    const double *x, *fm, *fP;     // [T][D][ld], [T][D][ld], [T][D*D][ld]
+    const int32_t *status;         // [ld] or null
+    const double *mse;             // [T][D*D] (regularised), device, or null
+    double *scores;                // [D + 3][ld]
+    int64_t B, ld;
+    int32_t D, T, k0;
+};
+
+// fP: the step's covariance planes; qb: dx' M^-1 dx (read only with want_lcr)
+__device__ __noinline__ void traj_items_indef(const double *fP, int64_t ld, int64_t b, const double *dx, int D, bool want_lcr,
+                                              double qb, double *nll, double *lcr) {       // both are added to
+    double P[kMetMaxD * kMetMaxD], W[kMetMaxD * kMetMaxD], z[kMetMaxD];
+    for (int i = 0; i < D * D; ++i) P[i] = fP[(int64_t)i * ld + b];
+    double s_nll = *nll, s_lcr = *lcr;
+    if (!nll_item_indef(P, dx, z, D, s_nll)) s_nll = __builtin_nan("");
+    if (want_lcr) {
+        for (int i = 0; i < D * D; ++i) P[i] = fP[(int64_t)i * ld + b];
+        lcr_item_indef(P, W, dx, qb, D, s_lcr);
+    }
+    *nll = s_nll;
+    *lcr = s_lcr;
+}
+
+template <int DT>
+__global__ __launch_bounds__(kMetBlock) void k_traj_scores(ScoreArgs a) {
+    constexpr int DM = DT > 0 ? DT : kMetMaxD, TRI = DM * (DM + 1) / 2;
+    const int D = DT > 0 ? DT : a.D;
+    const int64_t b = (int64_t)blockIdx.x * kMetBlock + threadIdx.x;
+    if (b >= a.ld) return;
+    const double nan = __builtin_nan("");
+    if (b >= a.B || (a.status && a.status[b] != 0)) {
+        for (int r = 0; r < D + 3; ++r) a.scores[(int64_t)r * a.ld + b] = nan;
+        return;
+    }
+    double se[DM];
+#pragma unroll
+    for (int d = 0; d < DM; ++d) se[d] = 0.0;
+    double rm = 0.0, nll = 0.0, lcr = a.mse ? 0.0 : nan;
+    for (int t = a.k0; t < a.T; ++t) {
+        const double *x = a.x + (int64_t)t * D * a.ld, *fm = a.fm + (int64_t)t * D * a.ld;
+        const double *fP = a.fP + (int64_t)t * D * D * a.ld;
+        double dx[DM], n2 = 0.0, qb = 0.0;
+        bool pd, m_ok = false;
+        if constexpr (DT > 0) {
+            double L[TRI], L2[TRI], M[TRI];
+#pragma unroll
+            for (int i = 0; i < DT; ++i)
+#pragma unroll
+                for (int j = 0; j <= i; ++j) L2[SSMQ_PK(i, j)] = L[SSMQ_PK(i, j)] = SSMQ_MLOAD(fP[((int64_t)i * DT + j) * a.ld + b]);
+#pragma unroll
+            for (int d = 0; d < DT; ++d) {
+                dx[d] = SSMQ_MLOAD(x[(int64_t)d * a.ld + b]) - SSMQ_MLOAD(fm[(int64_t)d * a.ld + b]);
+                se[d] += dx[d] * dx[d];
+                n2 += dx[d] * dx[d];
+            }
+            pd = nll_item<DT>(L, dx, nll);
+            if (a.mse) {
+#pragma unroll
+                for (int i = 0; i < DT; ++i)
+#pragma unroll
+                    for (int j = 0; j <= i; ++j) M[SSMQ_PK(i, j)] = a.mse[(int64_t)t * DT * DT + i * DT + j];
+                m_ok = chol_packed<DT>(M);
+                if (m_ok && pd) lcr_item<DT>(L2, M, dx, lcr);
+                if (m_ok && !pd) qb = whitened_norm2_packed<DT>(M, dx);
+            }
+        } else {
+            double P[kMetMaxD * kMetMaxD], M[kMetMaxD * kMetMaxD];
+            for (int d = 0; d < D; ++d) {
+                dx[d] = SSMQ_MLOAD(x[(int64_t)d * a.ld + b]) - SSMQ_MLOAD(fm[(int64_t)d * a.ld + b]);
+                se[d] += dx[d] * dx[d];
+                n2 += dx[d] * dx[d];
+            }
+            for (int i = 0; i < D; ++i)
+                for (int j = 0; j <= i; ++j) P[i * D + j] = fP[((int64_t)i * D + j) * a.ld + b];
+            pd = nll_item_dense(P, dx, D, nll);
+            if (a.mse) {
+                for (int i = 0; i < D * D; ++i) M[i] = a.mse[(int64_t)t * D * D + i];
+                m_ok = chol_dense<0>(M, D);
+                if (m_ok && pd) {
+                    for (int i = 0; i < D; ++i)
+                        for (int j = 0; j <= i; ++j) P[i * D + j] = fP[((int64_t)i * D + j) * a.ld + b];
+                    lcr_item_dense(P, M, dx, D, lcr);
+                }
+                if (m_ok && !pd) qb = whitened_norm2<0>(M, dx, D);
+            }
+        }
+        rm += sqrt(n2);
+        if (!pd) traj_items_indef(fP, a.ld, b, dx, D, m_ok, qb, &nll, &lcr);
+        if (a.mse && !m_ok) lcr = nan;
+    }
+    const double steps = (double)(a.T - a.k0);
+#pragma unroll
+    for (int d = 0; d < DM; ++d)
+        if (d < D) a.scores[(int64_t)d * a.ld + b] = sqrt(se[d] / steps);
+    a.scores[(int64_t)D * a.ld + b] = rm / steps;
+    a.scores[(int64_t)(D + 1) * a.ld + b] = nll / steps;
+    a.scores[(int64_t)(D + 2) * a.ld + b] = lcr / steps;
 }
 
 // out[t][v] = sum over chunks, in chunk order.  D > 0: phase-1 rows, partials hold the outer products as a packed
@@ -466,6 +616,23 @@ int launch_metrics_indef(int phase, int D, int64_t B, int64_t ld, int T, const d
     if (e != hipSuccess) return hip_fail(e, "k_indef_sums");
     hipLaunchKernelGGL(k_reduce_partials, dim3((T * 2 + 255) / 256), dim3(256), 0, s, partial, out, a.chunks, 2, T * 2, 0);
     return hip_fail(hipGetLastError(), "k_reduce_partials");
+}
+
+// d_scores [D + 3][ld]; mse: device [T][D*D] or null
+int launch_traj_scores(int D, int64_t B, int64_t ld, int T, int k0, const double *x, const double *fm, const double *fP,
+                       const int32_t *status, const double *mse, double *scores, hipStream_t s) {
+    ScoreArgs a{x, fm, fP, status, mse, scores, B, ld, D, T, k0};
+    const dim3 grid((unsigned)((ld + kMetBlock - 1) / kMetBlock)), block(kMetBlock);
+    switch (D) {
+        case 1: hipLaunchKernelGGL(k_traj_scores<1>, grid, block, 0, s, a); break;
+        case 2: hipLaunchKernelGGL(k_traj_scores<2>, grid, block, 0, s, a); break;
+        case 3: hipLaunchKernelGGL(k_traj_scores<3>, grid, block, 0, s, a); break;
+        case 4: hipLaunchKernelGGL(k_traj_scores<4>, grid, block, 0, s, a); break;
+        case 5: hipLaunchKernelGGL(k_traj_scores<5>, grid, block, 0, s, a); break;
+        case 6: hipLaunchKernelGGL(k_traj_scores<6>, grid, block, 0, s, a); break;
+        default: hipLaunchKernelGGL(k_traj_scores<0>, grid, block, 0, s, a); break;
+    }
+    return hip_fail(hipGetLastError(), "k_traj_scores");
 }
 
 int metrics_values_per_step(int D) { return met_nv(D); }

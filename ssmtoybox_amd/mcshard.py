@@ -305,6 +305,105 @@ def device_lcr_sums(D, B, ld, T, d_x, d_fm, d_fP, mse_global, d_status=None, reg
     return dict(lcr=sums[:, 0].copy(), n=sums[:, 1].copy())
 
 
+# ---------------------------------------------------------------------------------------------------------------
+# per-trajectory scores and their bootstrap error bars (single process)
+# ---------------------------------------------------------------------------------------------------------------
+BOOT_MAX_N, BOOT_MAX_SAMPLES, BOOT_MAX_ROWS = 2 ** 31 - 1, 2 ** 20, 19      # include/ssmq.h ssmq_bootstrap_var_dev
+
+
+def score_names(D):
+    """Names of the D + 3 rows of `device_traj_scores`."""
+    return ['rmse_{}'.format(d) for d in range(D)] + ['rmse', 'nll', 'lcr']
+
+
+def _check_bootstrap_range(n, samples, rows):
+    """The range of ssmq_bootstrap_var_dev, checked before the library is touched."""
+    if not 1 <= n <= BOOT_MAX_N:
+        raise ValueError('bootstrap: the number of included entries n = {} is outside 1 <= n < 2^31'.format(n))
+    if not 1 <= samples <= BOOT_MAX_SAMPLES:
+        raise ValueError('bootstrap: samples = {} is outside 1 <= S <= 2^20'.format(samples))
+    if not 1 <= rows <= BOOT_MAX_ROWS:
+        raise ValueError('bootstrap: rows = {} is outside 1 <= R <= 19'.format(rows))
+
+
+def device_traj_scores(D, B, ld, T, d_x, d_fm, d_fP, mse_global=None, d_status=None, k0=0, reg=1e-6):
+    """Time-averaged scores of every trajectory over the steps k0 .. T-1 (`ssmq_traj_scores_dev`) - what the reference's
+    studies resample for their error bars (research/bsq/bsq_ungm.py:64-76).  Inputs as for `device_error_sums`;
+    mse_global (T, D, D) and reg as for `device_lcr_sums` (None: the lcr row is NaN).
+    Returns (d_scores, names): a DeviceBuffer [D + 3][ld] - rmse_0 .. rmse_{D-1} per-dimension RMSE, rmse mean ||x - m||,
+    nll, lcr - that the caller frees, and the row names.  Excluded trajectories and the lanes B .. ld-1 hold NaN."""
+    if not 0 <= k0 < T:
+        raise ValueError('device_traj_scores: k0 = {} is outside 0 <= k0 < T = {}'.format(k0, T))
+    lib = _lib.load()
+    R = lib.ssmq_traj_scores_rows(D)
+    if R < 0:
+        raise _lib.SsmqError('ssmq_traj_scores_rows: dimension {} out of range'.format(D))
+    pM = None
+    if mse_global is not None:
+        M, pM = _lib.as_c(np.asarray(mse_global, dtype=np.float64).reshape(T, D, D) + reg * np.eye(D))
+    d_scores = _lib.DeviceBuffer(8 * R * ld)
+    try:
+        _lib.check(lib.ssmq_traj_scores_dev(D, B, ld, T, k0, ctypes.c_void_p(d_x.ptr), ctypes.c_void_p(d_fm.ptr),
+                                            ctypes.c_void_p(d_fP.ptr), ctypes.c_void_p(d_status.ptr if d_status else None),
+                                            pM, ctypes.c_void_p(d_scores.ptr)), 'ssmq_traj_scores_dev')
+    except Exception:
+        d_scores.free()
+        raise
+    return d_scores, score_names(D)
+
+
+def bootstrap_var_dev(d_scores, ld, rows, B, status=None, samples=1000, seed=0, return_means=False):
+    """Bootstrap variance of the mean (utils.py:223-244) of each of the `rows` rows of the device block d_scores [rows][ld],
+    resampling the included trajectories among the first B: those with status == 0 (status: host array (B,) or None = all).
+    The draws are a counter-based function of (seed, resample, position, number of included entries) and are shared by the
+    rows (`ssmq_bootstrap_var_dev`).  Returns var (rows,), and the resample means (rows, samples) with return_means.
+    Single process: with several ranks the score rows have to be gathered first."""
+    if status is None:
+        n, idx = int(B), None
+    else:
+        idx = np.flatnonzero(np.asarray(status).reshape(-1)[:B] == 0).astype(np.int32)
+        n = int(idx.size)
+    _check_bootstrap_range(n, int(samples), int(rows))
+    if n > ld:
+        raise ValueError('bootstrap: {} entries in rows of {}'.format(n, ld))
+    lib = _lib.load()
+    d_idx = d_means = None
+    try:
+        if idx is not None:
+            d_idx = _lib.DeviceBuffer(idx.nbytes)
+            d_idx.upload(idx)
+        if return_means:
+            d_means = _lib.DeviceBuffer(8 * rows * samples)
+        var, pv = _lib.out_c((rows,))
+        _lib.check(lib.ssmq_bootstrap_var_dev(ctypes.c_void_p(d_scores.ptr), ld, rows, ctypes.c_void_p(d_idx.ptr if d_idx else None),
+                                              n, samples, ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), pv,
+                                              ctypes.c_void_p(d_means.ptr if d_means else None)), 'ssmq_bootstrap_var_dev')
+        return (var, d_means.download((rows, samples))) if return_means else var
+    finally:
+        for b in (d_idx, d_means):
+            if b is not None:
+                b.free()
+
+
+def device_score_bars(D, B, ld, T, d_x, d_fm, d_fP, d_status=None, samples=10000, seed=0, k0=0):
+    """The tail of a study on the device: phase-1 sums -> global MSE matrices -> per-trajectory scores -> bootstrap.
+    Returns {name: {'mean', 'var', 'bar'}} for the rows of `device_traj_scores`: mean over the included trajectories, the
+    bootstrap variance of that mean and bar = 2 sqrt(var), as the reference's tables print them.  Single process."""
+    _check_bootstrap_range(max(int(B), 1), int(samples), D + 3)
+    mse = finalize(device_error_sums(D, B, ld, T, d_x, d_fm, d_fP, d_status))['mse']
+    status = d_status.download((B,), dtype=np.int32) if d_status else None
+    d_scores, names = device_traj_scores(D, B, ld, T, d_x, d_fm, d_fP, mse, d_status, k0)
+    try:
+        var = bootstrap_var_dev(d_scores, ld, len(names), B, status, samples, seed)
+        sc = d_scores.download((len(names), ld))[:, :B]
+    finally:
+        d_scores.free()
+    if status is not None:
+        sc = sc[:, status == 0]
+    return {nm: dict(mean=float(np.mean(sc[r])), var=float(var[r]), bar=float(2.0 * np.sqrt(var[r])))
+            for r, nm in enumerate(names)}
+
+
 def _pack(sums, keys):
     return np.concatenate([np.asarray(sums[k], dtype=np.float64).reshape(-1) for k in keys])
 

@@ -1,7 +1,8 @@
 """
 The helper functions of the reference's `ssmtoybox/utils.py` that lie on the accelerated path, under their own names:
-the multi-index / Vandermonde helpers of the Bayes-Sard weights (utils.py:459-502) and the performance metrics
-(utils.py:41-148).  Everything numerical runs on the device through the C ABI; there is no NumPy fallback.
+the multi-index / Vandermonde helpers of the Bayes-Sard weights (utils.py:459-502), the performance metrics
+(utils.py:41-148) and the bootstrap variance of a score (utils.py:223-244).  Everything numerical runs on the device through
+the C ABI; there is no NumPy fallback.
 
 The metric functions keep the reference's PER-ITEM signatures (one state, one mean, one covariance) and are a thin
 convenience: a Monte-Carlo study should reduce its filter outputs where they lie with `mcshard.device_error_sums` /
@@ -9,6 +10,8 @@ convenience: a Monte-Carlo study should reduce its filter outputs where they lie
 research/tpq/tpq_base.py:154-172 does on the CPU.  `squared_error` is not restated: its aggregate over the Monte-Carlo
 axis is the `se` entry of `mcshard.device_error_sums`.
 """
+
+import ctypes
 
 import numpy as np
 
@@ -92,3 +95,21 @@ def log_cred_ratio(x, m, P, MSE):
     if s['n'][0] != B:
         raise np.linalg.LinAlgError('log_cred_ratio: covariance or MSE matrix is singular')
     return float(s['lcr'][0])
+
+
+def bootstrap_var(data, samples=1000, seed=None):
+    """utils.py:223-244: bootstrap estimate of the variance of the mean of `data` ((1, mc_sims) or (mc_sims,), squeezed as
+    the reference does), `samples` resamples drawn on the device (`ssmq_bootstrap_var`; the draws are the library's
+    counter-based ones, not numpy's, so the value agrees with the reference's statistically, not digit by digit).
+    seed=None takes the seed from numpy's global generator, so `np.random.seed` governs it as it governs the reference."""
+    data = np.ascontiguousarray(np.asarray(data, dtype=np.float64).squeeze())
+    if data.ndim != 1:
+        raise ValueError('bootstrap_var: data must squeeze to one dimension, got shape {}'.format(data.shape))
+    mcshard._check_bootstrap_range(data.shape[0], int(samples), 1)
+    if seed is None:
+        seed = int(np.random.randint(0, 2 ** 31 - 1)) << 31 | int(np.random.randint(0, 2 ** 31 - 1))
+    d, pd = _lib.as_c(data)
+    var, pv = _lib.out_c((1,))
+    _lib.check(_lib.load().ssmq_bootstrap_var(pd, data.shape[0], int(samples), ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), pv),
+               'ssmq_bootstrap_var')
+    return float(var[0])
