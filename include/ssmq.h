@@ -90,7 +90,8 @@ enum ssmq_integrand_id {
  * Idempotent: the same (body, din, dout) returns the same id.  1 <= din, dout <= SSMQ_MAX_DIM.
  * User ids run on: ssmq_filter_forward_dev / ssmq_student_filter_forward_dev (additive noise; the whole-pass kernel compiled for
  * the pair of models, D <= 6, Y <= 4, ND, NO <= 2 D + 1, no state index) and ssmq_apply_batch[_dev] / ssmq_apply_kernel_name
- * (k_apply_small, the same shape range).  Every other entry point that takes an ssmq_integrand returns SSMQ_E_UNSUPPORTED.
+ * (k_apply_small, the same shape range), and ssmq_mc_transform_dev (k_mc_moments, D <= 6, E <= 6, no state index).  Every other
+ * entry point that takes an ssmq_integrand returns SSMQ_E_UNSUPPORTED.
  * Compiled kernels are cached in the process (key: body hashes, kernel, template arguments, device architecture).
  */
 #define SSMQ_F_USER_FIRST 1024
@@ -103,7 +104,8 @@ int ssmq_integrand_define(const char *body, int din, int dout, int uses_time, in
  * 0, opt> (id_obs: any integrand id), SSMQ_RTC_APPLY k_apply_small<D, E, N, id, form, tp, 0, opt> (id_obs, N_obs ignored), for
  * `arch` (e.g. "gfx950").  On success `log` gets the lowered kernel name on its first line, then the compiler's resource
  * remarks (registers, spills); on failure the compiler log.  Returns SSMQ_OK, SSMQ_E_ARG or SSMQ_E_UNSUPPORTED (compile error). */
-enum ssmq_rtc_kind { SSMQ_RTC_FILTER = 0, SSMQ_RTC_APPLY = 1 };
+/* SSMQ_RTC_MC instantiates the streaming Monte-Carlo kernel k_mc_moments<id, D, E, 0> (N, N_obs, form, tp, opt ignored). */
+enum ssmq_rtc_kind { SSMQ_RTC_FILTER = 0, SSMQ_RTC_APPLY = 1, SSMQ_RTC_MC = 2 };
 int ssmq_rtc_compile_check(int32_t id, int32_t id_obs, int kind, int D, int E, int N, int N_obs, int form, int tp, int opt,
                            const char *arch, char *log, int len);
 /* Process-wide counters of the run-time compiler: programs compiled, kernel lookups served from the cache, compile wall time. */
@@ -730,6 +732,37 @@ int ssmq_traj_scores_dev(int D, int64_t B, int64_t ld, int T, int k0, const doub
 int ssmq_bootstrap_var_dev(const double *d_data, int64_t ld, int R, const int32_t *d_idx, int64_t n, int S, uint64_t seed,
                            double *var, double *d_means);
 int ssmq_bootstrap_var(const double *data, int64_t n, int S, uint64_t seed, double *var);
+
+/*
+ * Monte-Carlo moment transform of any sample count (mtran.py:62-94 MonteCarloTransform.apply), streamed: the n unit samples are
+ * drawn where they are used and no (D, n) point matrix exists.  For item b with moments (m_b, P_b), x_j = m_b + L_b z_j:
+ *   mean_f = sum f(x_j) / n,  cov_f = sum (f - mean_f)(f - mean_f)' / (n - 1),  cov_fx = sum (f - mean_f)(x_j - m_b)' / (n - 1).
+ * The draw (csrc/ssmq_mc_moments.h states it in full): (z_j[2 p], z_j[2 p + 1]) = Box-Muller of the two 53-bit uniforms of
+ *   Philox4x32-10(counter (j, 0, p, 0x4D435446), key (seed lo, seed hi)) - the same unit samples for every item of a batch.
+ * The sums are taken in one pass around the pivot f(m_b), in chunks of 2048 samples in a fixed order: an item's bits depend on
+ * (seed, n, its own inputs) alone, not on B or the launch (n <= 2048: a second pass around the mean of the first).
+ * Takes an integrand, not a transform handle: built-in ids in the (D, E, state index) combinations of csrc/ssmq_mc_transform.hip's table, and user ids (no state index).  Device buffers in the
+ * conventions of ssmq_apply_batch_dev: SoA planes with pitch ld, d_time [B] or [1], d_status [B] (1: covariance not positive
+ * definite, that item's outputs NaN).  1 <= D, E <= 6 and 2 <= n < 2^31, else SSMQ_E_UNSUPPORTED before an output is touched.
+ * Synchronous.
+ * ssmq_mc_unit_points: the unit samples first .. first + count - 1 as a host array z [D][count], by the same device code.
+ */
+int ssmq_mc_transform_dev(const ssmq_integrand *f, int D, int E, int64_t n, uint64_t seed, int64_t B, int64_t ld,
+                          const double *d_mean, const double *d_cov, const double *d_time, int time_stride, double *d_mean_f,
+                          double *d_cov_f, double *d_cov_fx, int32_t *d_status);
+int ssmq_mc_unit_points(int D, uint64_t seed, int64_t first, int64_t count, double *z);
+
+/*
+ * KL divergence of Gaussian pairs (utils.py:151-182 kl_divergence, as written there:
+ *   0.5 (tr(P1^-1 P0) + (m0 - m1)' P1^-1 (m0 - m1) + log(det P0 / det P1) - E) ), or with `symmetrized`
+ *   0.5 (KL(0, 1) + KL(1, 0)) (utils.py:185-220), one pair per lane, through the two Cholesky factors (in double-double arithmetic):
+ *   tr(P1^-1 P0) = |L1^-1 L0|_F^2, the quadratic term |L1^-1 (m0 - m1)|^2, log(det P0 / det P1) = 2 sum (log L0_ii - log L1_ii).
+ * SoA planes d_m1 [E][ld], d_P1 [E*E][ld] (lower triangle read); d_m0 / d_P0 likewise, or with bcast0 one pair [E], [E*E] used
+ * for every item.  d_kl [B], d_status [B]: a pair with a factor that fails gets status 1 and NaN (the reference returns NaN or a
+ * number without meaning from log(det / det) there).  1 <= E <= 6, else SSMQ_E_UNSUPPORTED.  Asynchronous on the library stream.
+ */
+int ssmq_kl_divergence_dev(int E, int64_t B, int64_t ld, const double *d_m0, const double *d_P0, int bcast0, const double *d_m1,
+                           const double *d_P1, int symmetrized, double *d_kl, int32_t *d_status);
 
 /*
  * Forward pass of a Studentian filter (ssinf.py:555-736: StudentianInference._time_update / _measurement_update) for B

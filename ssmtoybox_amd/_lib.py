@@ -26,7 +26,7 @@ F_REENTRY2D_DYN, F_RADAR2D_MEAS, F_CT_DYN, F_BEARING_MEAS = 9, 10, 11, 12
 F_CTRS_DYN, F_CV_DYN, F_REENTRY2D_BIAS_DYN, F_SMOOTH10D_DYN = 13, 14, 15, 16
 # user-defined integrands, compiled for the device at run time (include/ssmq.h ssmq_integrand_define)
 F_USER_FIRST, F_USER_SLOTS, USER_BODY_MAX, USER_MAX_D, USER_MAX_Y = 1024, 64, 8192, 6, 4
-RTC_FILTER, RTC_APPLY = 0, 1
+RTC_FILTER, RTC_APPLY, RTC_MC = 0, 1, 2
 
 
 class SsmqError(RuntimeError):
@@ -225,6 +225,13 @@ _PROTOTYPES = {
     'ssmq_bootstrap_var_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64,
                                               ctypes.c_int, ctypes.c_uint64, c_double_p, ctypes.c_void_p]),
     'ssmq_bootstrap_var': (ctypes.c_int, [c_double_p, ctypes.c_int64, ctypes.c_int, ctypes.c_uint64, c_double_p]),
+    'ssmq_mc_transform_dev': (ctypes.c_int, [ctypes.POINTER(Integrand), ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_uint64,
+                                             ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    'ssmq_mc_unit_points': (ctypes.c_int, [ctypes.c_int, ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64, c_double_p]),
+    'ssmq_kl_divergence_dev': (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+                                              ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+                                              ctypes.c_void_p]),
     'ssmq_filter_kernel_name': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Integrand), ctypes.c_void_p,
                                                ctypes.POINTER(Integrand), ctypes.c_char_p, ctypes.c_int]),
     'ssmq_filter_kernel_name_batch': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Integrand), ctypes.c_void_p,

@@ -62,6 +62,10 @@ int rtc_launch_fused(const FilterPass &p);
 // k_apply_small<> for a user integrand: SSMQ_OK (launched, or with dry_run the name set) or < 0.
 int rtc_launch_apply(const ssmq_transform *h, const ssmq_integrand *f, int sel, const ApplyArgs &a, hipStream_t s,
                      const char **name, bool dry_run);
+// k_mc_moments<> (ssmq_mc_moments.h) for a user integrand, launched with the AOT route's arguments: SSMQ_OK or < 0.
+struct McMomArgs;
+int rtc_launch_mc(const ssmq_integrand *f, int D, int E, const McMomArgs &a, unsigned grid, hipStream_t s);
+bool mc_range_ok(int D, int E, int64_t n);   // ssmq_mc_transform.hip: 1 <= D, E <= 6, 2 <= n < 2^31
 // Threads.  Every calling thread has its own CONTEXT: a HIP stream and the caches that belong to a stream (grow-only workspaces,
 // pinned staging blocks, captured launch graphs).  Calls of different threads on different handles run concurrently - on the
 // host and, stream by stream, on the device.  Contexts are pooled: a thread that ends hands its context (stream and caches

@@ -7,6 +7,8 @@
 //   every user body involved | one explicit instantiation.
 // Compiled with the Makefile's -O3 -std=c++17 for the current device's architecture, found by lowered name, loaded as a module and
 // launched with the AOT launcher's grid, block and argument struct - the same code as a built-in model up to the functor.
+// The streaming Monte-Carlo transform runs a user integrand the same way: k_mc_moments<> (ssmq_mc_moments.h), one explicit
+// instantiation per (integrand id, D, E), launched with the arguments ssmq_mc_transform_dev made for the AOT route.
 // Code objects are cached for the life of the process (key: the body hashes, kernel and template arguments, architecture) - failed
 // compiles too, with their message, so a broken body is compiled once - and modules per device.  Locks: the registry of bodies has
 // a mutex of its own (held for a lookup only); the cache mutex is held while a kernel is looked up, compiled or loaded, so a
@@ -25,6 +27,7 @@
 #include "ssmq_host.h"
 #include "ssmq_fused.h"
 #include "ssmq_filter_shapes.h"
+#include "ssmq_mc_moments.h"
 
 namespace ssmq {
 
@@ -179,7 +182,9 @@ int compile(const std::string &expr, const std::vector<int> &ids, const std::str
     std::string src = kRtcPrelude;
     src += kRtcHeaders;
     src += wrappers;
-    src += "template __global__ void " + expr + "(const " + (expr.find("k_filter_fused") != std::string::npos ? "ssmq::FusedArgs" : "ssmq::ApplyArgs") + ");\n";
+    const char *arg_type = expr.find("k_filter_fused") != std::string::npos ? "ssmq::FusedArgs"
+                           : expr.find("k_mc_moments") != std::string::npos ? "ssmq::McMomArgs" : "ssmq::ApplyArgs";
+    src += "template __global__ void " + expr + "(const " + arg_type + ");\n";
     const auto t0 = std::chrono::steady_clock::now();
     hiprtcProgram prog;
     if (hiprtcCreateProgram(&prog, src.c_str(), "ssmq_user.hip", 0, nullptr, nullptr) != HIPRTC_SUCCESS) {
@@ -447,6 +452,19 @@ int rtc_launch_apply(const ssmq_transform *h, const ssmq_integrand *f, int sel, 
     return hip_fail(hipModuleLaunchKernel(fn, grid, 1, 1, kSmallBlock, 1, 1, 0, s, args, nullptr), "k_apply_small (run-time compiled)");
 }
 
+// k_mc_moments<> for a user integrand (ssmq_mc_transform.hip has checked the range and filled `a0`): SSMQ_OK launched, or < 0
+int rtc_launch_mc(const ssmq_integrand *f, int D, int E, const McMomArgs &a0, unsigned grid, hipStream_t s) {
+    char b[128];
+    snprintf(b, sizeof(b), "ssmq::k_mc_moments<%d, %d, %d, 0>", f->id, D, E);
+    hipFunction_t fn;
+    int rc = kernel_for(b, {f->id}, &fn);
+    if (rc) return rc;
+    McMomArgs a = a0;
+    a.fp.ttab = nullptr;
+    void *args[] = {&a};
+    return hip_fail(hipModuleLaunchKernel(fn, grid, 1, 1, kMcBlock, 1, 1, 0, s, args, nullptr), "k_mc_moments (run-time compiled)");
+}
+
 }  // namespace ssmq
 
 using namespace ssmq;
@@ -487,13 +505,27 @@ extern "C" int ssmq_integrand_define(const char *body, int din, int dout, int us
 
 extern "C" int ssmq_rtc_compile_check(int32_t id, int32_t id_obs, int kind, int D, int E, int N, int N_obs, int form, int tp, int opt,
                                       const char *arch, char *log, int len) {
-    if (!arch || !*arch || (kind != SSMQ_RTC_FILTER && kind != SSMQ_RTC_APPLY) || (form != SSMQ_FORM_BQ && form != SSMQ_FORM_SIGMA) ||
+    if (kind == SSMQ_RTC_MC) {   // k_mc_moments<id, D, E, 0>: N, N_obs, form, tp and opt are not read
+        FInfo fm;
+        if (!arch || !*arch || !integrand_info(id, &fm)) {
+            set_error("ssmq_rtc_compile_check: bad argument");
+            return SSMQ_E_ARG;
+        }
+        if (!mc_range_ok(D, E, 2) || fm.din > D) {
+            set_error("ssmq_rtc_compile_check: the streaming Monte-Carlo kernel covers 1 <= D, E <= 6, integrand inputs <= D");
+            return SSMQ_E_UNSUPPORTED;
+        }
+        N = N_obs = 2;
+        form = SSMQ_FORM_SIGMA;
+        tp = opt = 0;
+    }
+    if (!arch || !*arch || (kind != SSMQ_RTC_FILTER && kind != SSMQ_RTC_APPLY && kind != SSMQ_RTC_MC) || (form != SSMQ_FORM_BQ && form != SSMQ_FORM_SIGMA) ||
         tp < 0 || tp > 1 || (opt != 0 && opt != 1 && opt != 2 && opt != 3 && opt != 7)) {
         set_error("ssmq_rtc_compile_check: bad argument");
         return SSMQ_E_ARG;
     }
     std::string why;
-    if (!shape_ok(D, E, N, &why) || (kind == SSMQ_RTC_FILTER && !shape_ok(D, D, N_obs, &why))) {
+    if (kind != SSMQ_RTC_MC && (!shape_ok(D, E, N, &why) || (kind == SSMQ_RTC_FILTER && !shape_ok(D, D, N_obs, &why)))) {
         set_error(why);
         return SSMQ_E_UNSUPPORTED;
     }
@@ -506,6 +538,7 @@ extern "C" int ssmq_rtc_compile_check(int32_t id, int32_t id_obs, int kind, int 
     if (is_user_integrand(id)) ids.push_back(id);
     if (kind == SSMQ_RTC_FILTER && is_user_integrand(id_obs) && id_obs != id) ids.push_back(id_obs);
     const std::string expr = kind == SSMQ_RTC_FILTER ? fused_expr(D, E, N, N_obs, id, id_obs, form, tp, 0, opt, -1)
+                             : kind == SSMQ_RTC_MC   ? "ssmq::k_mc_moments<" + std::to_string(id) + ", " + std::to_string(D) + ", " + std::to_string(E) + ", 0>"
                                                      : apply_expr(D, E, N, id, form, tp, 0, opt, false);
     std::lock_guard<std::mutex> lk(g_mu);
     Compiled *c = nullptr;

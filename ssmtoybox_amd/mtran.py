@@ -259,18 +259,38 @@ class SigmaPointTransform(_DeviceApply, MomentTransform):
 
 
 class MonteCarloTransform(SigmaPointTransform):
-    """Monte Carlo transform, the reference's baseline (mtran.py:62-94): n standard-normal unit points drawn once at
-    construction (np.random, as there), mean weights 1 / n, covariance weights 1 / (n - 1) - on the device it is a centred
-    sigma-point rule like the others (n <= 4096 = SSMQ_MAX_PTS; beyond 64 points the streaming route of k_apply_big).
-    The reference keeps the two weights as scalars; `wm` / `Wc` here are the expanded vector / diagonal matrix."""
+    """Monte Carlo transform, the reference's baseline (mtran.py:62-94): n standard-normal unit points, mean weight 1 / n,
+    covariance weight 1 / (n - 1).  Two routes:
 
-    def __init__(self, dim, n=100):
+    * `n <= 4096` and `seed is None`: the unit points are drawn once at construction (np.random, as there) and the transform is
+      a centred sigma-point rule like the others (beyond 64 points the route of k_apply_big); `wm` / `Wc` are the expanded
+      vector / diagonal matrix and `unit_sp` is the (dim, n) point matrix.
+    * `n > 4096`, or any `seed`: the STREAMING route (csrc/ssmq_mc_transform.hip, `k_mc_moments`).  Every unit sample is drawn
+      on the device where it is used - Philox4x32-10 keyed by `seed` (None = 0), the same samples for every item of a batch
+      and every call - so no (dim, n) matrix exists and n may be anything in 2 .. 2^31 - 1.  `wm` / `Wc` are the scalars
+      1 / n and 1 / (n - 1), as the reference keeps them; `unit_points(first, count)` returns a slice of the unit samples.
+      dim <= 6 and at most 6 outputs; `f` is the bound dyn_eval / meas_eval of a built-in model or of a model with
+      `device_code` - an arbitrary Python callable would need n calls per item and raises NotImplementedError.  The result's
+      bits depend on (seed, n, the item's own inputs) alone.  A filter cannot use it (the filter loops take transform handles)."""
+
+    STREAM_MAX_DIM = 6          # D and E of the streaming route (include/ssmq.h ssmq_mc_transform_dev)
+    STREAM_MAX_N = 2 ** 31 - 1
+    _RANGE = 'the streaming Monte-Carlo transform covers 1 <= dim <= 6, 1 <= outputs <= 6 and 2 <= n < 2^31'
+
+    def __init__(self, dim, n=100, seed=None):
         n = int(n)
-        if n < 2 or n > 4096:
-            raise ValueError('MonteCarloTransform: 2 <= n <= 4096 points on the device path')
-        wm, wc = self.weights(n)
-        self.wm, self.Wc = np.full(n, wm), np.diag(np.full(n, wc))
-        self.unit_sp = self.unit_sigma_points(dim, n)
+        self.streaming = n > 4096 or seed is not None
+        if n < 2 or n > self.STREAM_MAX_N:
+            raise ValueError('MonteCarloTransform: 2 <= n < 2^31 (got n = {})'.format(n))
+        if not self.streaming:
+            wm, wc = self.weights(n)
+            self.wm, self.Wc = np.full(n, wm), np.diag(np.full(n, wc))
+            self.unit_sp = self.unit_sigma_points(dim, n)
+            return
+        if not 1 <= int(dim) <= self.STREAM_MAX_DIM:
+            raise NotImplementedError('{} (got dim = {})'.format(self._RANGE, dim))
+        self.dim, self.n, self.seed = int(dim), n, (0 if seed is None else int(seed)) & (2 ** 64 - 1)
+        self.wm, self.Wc = self.weights(n)
 
     @staticmethod
     def weights(n):
@@ -279,6 +299,94 @@ class MonteCarloTransform(SigmaPointTransform):
     @staticmethod
     def unit_sigma_points(dim, n):
         return np.random.multivariate_normal(np.zeros(dim), np.eye(dim), size=n).T
+
+    # ---- the streaming route -------------------------------------------------------------------------------------------
+    def unit_points(self, first=0, count=None):
+        """(dim, count) unit samples first .. first + count - 1 of the streaming route, computed by the kernel's own device
+        code (`ssmq_mc_unit_points`).  The non-streaming route returns the columns of `unit_sp`."""
+        if not self.streaming:
+            return self.unit_sp[:, first:None if count is None else first + count].copy()
+        first = int(first)
+        count = self.n - first if count is None else int(count)
+        if first < 0 or count < 0 or first + count > self.n:
+            raise ValueError('unit_points: 0 <= first, first + count <= n')
+        z, pz = _lib.out_c((self.dim, count))
+        _lib.check(_lib.load().ssmq_mc_unit_points(self.dim, ctypes.c_uint64(self.seed), first, count, pz), 'ssmq_mc_unit_points')
+        return z
+
+    def _stream_integrand(self, f, D):
+        """(Integrand, E) of `f` on the streaming route; range errors are raised here, before the library is touched."""
+        dev = resolve_integrand(f)
+        if dev is None:
+            raise NotImplementedError('the streaming Monte-Carlo transform (n > 4096 or a seed) evaluates the integrand on the device: '
+                                      'f must be the dyn_eval / meas_eval of a built-in model or of a model with device_code, not '
+                                      'an arbitrary Python callable (n calls per item is not a device path)')
+        integ, E = dev
+        if D != self.dim:
+            raise ValueError('mean has {} entries, the transform was made for dim = {}'.format(D, self.dim))
+        if not 1 <= E <= self.STREAM_MAX_DIM:
+            raise NotImplementedError('{} (got {} outputs)'.format(self._RANGE, E))
+        return integ, E
+
+    def _handle_for(self, E):
+        if self.streaming:
+            raise NotImplementedError('a streaming MonteCarloTransform (n > 4096 or a seed) cannot be a filter\'s transform or go '
+                                      'through the transform handles: the filter loops take handles of point rules; use '
+                                      'apply / apply_batch / apply_batch_dev')
+        return super()._handle_for(E)
+
+    def _num_points(self):
+        return self.n if self.streaming else super()._num_points()
+
+    def kernel_name(self, f):
+        if not self.streaming:
+            return super().kernel_name(f)
+        self._stream_integrand(f, self.dim)
+        return 'k_mc_moments'
+
+    def apply_batch(self, f, mean, cov, time=0.0, fcn_pars=None, return_status=False):
+        if not self.streaming:
+            return super().apply_batch(f, mean, cov, time=time, fcn_pars=fcn_pars, return_status=return_status)
+        mean = np.ascontiguousarray(mean, dtype=np.float64)
+        cov = np.ascontiguousarray(cov, dtype=np.float64)
+        if mean.ndim != 2 or cov.shape != mean.shape + mean.shape[1:]:
+            raise ValueError('mean must have shape (B, D) and cov (B, D, D)')
+        B, D = mean.shape
+        integ, E = self._stream_integrand(f, D)
+        time = np.ascontiguousarray(np.asarray(time, dtype=np.float64).reshape(-1))
+        if time.size == B and B > 1:
+            stride = 1
+        else:
+            time, stride = (time[:1].copy() if time.size >= 1 else np.zeros(1)), 0
+        d_m, d_c = _lib.SoA.from_host(mean), _lib.SoA.from_host(cov)
+        d_t = _lib.DeviceBuffer(time.nbytes)
+        d_t.upload(time)
+        d_mf, d_cf, d_cfx = _lib.SoA(E, B), _lib.SoA(E * E, B), _lib.SoA(E * D, B)
+        d_st = _lib.DeviceBuffer(4 * max(d_m.ld, 1))
+        try:
+            self.apply_batch_dev(f, d_m, d_c, d_t, d_mf, d_cf, d_cfx, d_st, time_stride=stride)
+            mf, cf, cfx = d_mf.to_host(), d_cf.to_host((E, E)), d_cfx.to_host((E, D))
+            st = d_st.download((d_m.ld,), dtype=np.int32)[:B].copy()
+        finally:
+            for b in (d_m.buf, d_c.buf, d_t, d_mf.buf, d_cf.buf, d_cfx.buf, d_st):
+                b.free()
+        if return_status:
+            return mf, cf, cfx, st
+        bad = np.flatnonzero(st)
+        if bad.size:
+            _raise_not_pd(int(bad[0]) + 1)
+        return mf, cf, cfx
+
+    def apply_batch_dev(self, f, mean, cov, time, mean_f, cov_f, cov_fx, status, time_stride=0):
+        """Device-resident variant: `_lib.SoA` planes (time, status: DeviceBuffers).  The streaming route returns when the
+        results are complete."""
+        if not self.streaming:
+            return super().apply_batch_dev(f, mean, cov, time, mean_f, cov_f, cov_fx, status, time_stride=time_stride)
+        integ, E = self._stream_integrand(f, mean.n)
+        _lib.check(_lib.load().ssmq_mc_transform_dev(ctypes.byref(integ), self.dim, E, self.n, ctypes.c_uint64(self.seed), mean.B,
+                                                     mean.ld, mean.ptr, cov.ptr, ctypes.c_void_p(time.ptr), int(time_stride),
+                                                     mean_f.ptr, cov_f.ptr, cov_fx.ptr, ctypes.c_void_p(status.ptr)),
+                   'ssmq_mc_transform_dev')
 
 
 class SphericalRadialTransform(SigmaPointTransform):

@@ -1,7 +1,8 @@
 """
 The helper functions of the reference's `ssmtoybox/utils.py` that lie on the accelerated path, under their own names:
 the multi-index / Vandermonde helpers of the Bayes-Sard weights (utils.py:459-502), the performance metrics
-(utils.py:41-148) and the bootstrap variance of a score (utils.py:223-244).  Everything numerical runs on the device through
+(utils.py:41-148), the KL divergences of the transform accuracy studies (utils.py:151-220) and the bootstrap variance of a score
+(utils.py:223-244).  Everything numerical runs on the device through
 the C ABI; there is no NumPy fallback.
 
 The metric functions keep the reference's PER-ITEM signatures (one state, one mean, one covariance) and are a thin
@@ -113,3 +114,71 @@ def bootstrap_var(data, samples=1000, seed=None):
     _lib.check(_lib.load().ssmq_bootstrap_var(pd, data.shape[0], int(samples), ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), pv),
                'ssmq_bootstrap_var')
     return float(var[0])
+
+
+KL_MAX_DIM = 6      # include/ssmq.h ssmq_kl_divergence_dev
+
+
+def kl_divergence_batch(mean_0, cov_0, mean_1, cov_1, symmetrized=False):
+    """B KL divergences in one launch (`k_kl_divergence`, csrc/ssmq_kl.hip): mean_1 (B, E), cov_1 (B, E, E); mean_0 / cov_0
+    likewise, or one pair (E,), (E, E) that is used for every item (the Monte-Carlo ground truth against a grid of
+    approximations).  Returns (kl (B,), status (B,)).  Each item is the reference's `kl_divergence` (utils.py:151-182, as
+    written there, with log(det cov_0 / det cov_1)) or, with `symmetrized`, `symmetrized_kl_divergence` (utils.py:185-220),
+    computed through the two Cholesky factors.  A pair with a covariance that is not positive definite gets status 1 and NaN;
+    the reference returns NaN or a number without meaning from log(det / det) there.  E <= 6 (NotImplementedError beyond)."""
+    m1 = np.ascontiguousarray(mean_1, dtype=np.float64)
+    P1 = np.ascontiguousarray(cov_1, dtype=np.float64)
+    m0 = np.ascontiguousarray(mean_0, dtype=np.float64)
+    P0 = np.ascontiguousarray(cov_0, dtype=np.float64)
+    if m1.ndim != 2 or P1.shape != m1.shape + m1.shape[1:]:
+        raise ValueError('mean_1 must have shape (B, E) and cov_1 (B, E, E)')
+    B, E = m1.shape
+    bcast = m0.ndim == 1
+    if (bcast and (m0.shape != (E,) or P0.shape != (E, E))) or (not bcast and (m0.shape != (B, E) or P0.shape != (B, E, E))):
+        raise ValueError('mean_0 / cov_0 must be (B, E), (B, E, E) like mean_1 / cov_1, or one pair (E,), (E, E)')
+    if not 1 <= E <= KL_MAX_DIM:
+        raise NotImplementedError('kl_divergence on the device covers 1 <= E <= {} (got E = {})'.format(KL_MAX_DIM, E))
+    if B == 0:
+        return np.empty(0), np.empty(0, dtype=np.int32)
+    d1m, d1P = _lib.SoA.from_host(m1), _lib.SoA.from_host(P1)
+    ld = d1m.ld
+    if bcast:
+        d0m, d0P = _lib.DeviceBuffer(m0.nbytes), _lib.DeviceBuffer(P0.nbytes)
+        d0m.upload(m0)
+        d0P.upload(P0)
+        bufs = [d0m, d0P]
+    else:
+        s0m, s0P = _lib.SoA.from_host(m0), _lib.SoA.from_host(P0)
+        d0m, d0P = s0m.buf, s0P.buf
+        bufs = [d0m, d0P]
+    d_kl, d_st = _lib.DeviceBuffer(8 * ld), _lib.DeviceBuffer(4 * ld)
+    bufs += [d1m.buf, d1P.buf, d_kl, d_st]
+    try:
+        _lib.check(_lib.load().ssmq_kl_divergence_dev(E, B, ld, ctypes.c_void_p(d0m.ptr), ctypes.c_void_p(d0P.ptr), 1 if bcast else 0,
+                                                      d1m.ptr, d1P.ptr, 1 if symmetrized else 0, ctypes.c_void_p(d_kl.ptr),
+                                                      ctypes.c_void_p(d_st.ptr)), 'ssmq_kl_divergence_dev')
+        kl = d_kl.download((ld,))[:B].copy()
+        st = d_st.download((ld,), dtype=np.int32)[:B].copy()
+    finally:
+        for b in bufs:
+            b.free()
+    return kl, st
+
+
+def _kl_single(mean_0, cov_0, mean_1, cov_1, symmetrized):
+    m0, m1 = np.atleast_1d(np.asarray(mean_0, dtype=np.float64)), np.atleast_1d(np.asarray(mean_1, dtype=np.float64))
+    P0, P1 = np.atleast_2d(np.asarray(cov_0, dtype=np.float64)), np.atleast_2d(np.asarray(cov_1, dtype=np.float64))
+    kl, _ = kl_divergence_batch(m0[None], P0[None], m1[None], P1[None], symmetrized=symmetrized)
+    return float(kl[0])
+
+
+def kl_divergence(mean_0, cov_0, mean_1, cov_1):
+    """utils.py:151-182: KL divergence between the true Gaussian N(mean_0, cov_0) and the approximation N(mean_1, cov_1), with
+    the reference's signature (scalars and 1-D inputs as there) and its formula as written; a Python float - item 0 of
+    `kl_divergence_batch`, bit for bit.  NaN if a covariance is not positive definite."""
+    return _kl_single(mean_0, cov_0, mean_1, cov_1, False)
+
+
+def symmetrized_kl_divergence(mean_0, cov_0, mean_1, cov_1):
+    """utils.py:185-220: 0.5 (KL(0, 1) + KL(1, 0)); see `kl_divergence`."""
+    return _kl_single(mean_0, cov_0, mean_1, cov_1, True)
