@@ -40,18 +40,14 @@ namespace {
 // forward pass (Monte-Carlo studies, bench.py) neither allocates nor pays 3 T kernel-launch latencies: the whole time
 // loop is replayed as one hipGraph while the argument set is unchanged.
 struct FilterCache {
-    void *ws = nullptr;
+    void *ws = nullptr;               // planes of the launch loop and its two status planes
     size_t ws_bytes = 0;
+    void *consts = nullptr;           // the pass's constants (PassConsts layout, ssmq_host.h) of every single-filter route, grow-only ...
+    size_t consts_bytes = 0;
+    std::vector<double> consts_host;  // ... and what the block holds
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
     std::vector<uint64_t> key;
-    std::vector<double> gqg, rr, ss;
-    int T = -1, fid_dyn = -1, fid_obs = -1, D = -1, Y = -1;
-    int64_t ld = -1;          // the constants sit behind the ld-sized planes: a new pitch moves them
-    bool consts_ok = false;
-    void *user_ws = nullptr;          // constants of the run-time compiled filters (filter_forward_user): G Q G' | R | scale [T]
-    size_t user_bytes = 0;
-    std::vector<double> user_host;    // ... what the block holds
     void drop_graph() {
         if (exec) hipGraphExecDestroy(exec);
         if (graph) hipGraphDestroy(graph);
@@ -70,70 +66,61 @@ FilterCache &fc_of_ctx() {
 struct GraphDropGuard {
     ~GraphDropGuard() { g_fc.drop_graph(); }
 };
+
+// The constants of one pass in the context's block: filled on the host, uploaded when they differ from what the block holds.
+// The captured launch loop reads the block and has the scale baked into its kernel arguments by value, so any change drops it.
+int cached_pass_consts(const ssmq_integrand *f_dyn, const ssmq_integrand *f_obs, int D, int Y, int T, const double *GQG, const double *R,
+                       const double *sscale, hipStream_t s, PassConsts *pc) {
+    FilterCache &c = g_fc;
+    std::vector<double> h(pass_consts_doubles(D, Y, T));
+    *pc = fill_pass_consts(h.data(), f_dyn, f_obs, D, Y, T, GQG, R, sscale);
+    const size_t need = sizeof(double) * h.size();
+    if (h == c.consts_host) return SSMQ_OK;
+    c.drop_graph();
+    c.consts_host.clear();
+    if (c.consts_bytes < need) {
+        if (c.consts) {
+            SSMQ_HIP(hipStreamSynchronize(s));
+            hipFree(c.consts);
+        }
+        c.consts = nullptr;
+        c.consts_bytes = 0;
+        SSMQ_HIP(hipMalloc(&c.consts, need));
+        c.consts_bytes = need;
+    }
+    // (stream order: earlier passes that read the block are done before the copy lands)
+    SSMQ_HIP(hipMemcpyAsync(c.consts, h.data(), need, hipMemcpyHostToDevice, s));
+    SSMQ_HIP(hipStreamSynchronize(s));
+    c.consts_host.swap(h);
+    return SSMQ_OK;
+}
 }  // namespace
 
 namespace ssmq {
 void drop_filter_cache() {
     g_fc.drop_graph();
-    g_fc.consts_ok = false;
     if (g_fc.ws) hipFree(g_fc.ws);
-    g_fc.ws = nullptr;
-    g_fc.ws_bytes = 0;
-    if (g_fc.user_ws) hipFree(g_fc.user_ws);
-    g_fc.user_ws = nullptr;
-    g_fc.user_bytes = 0;
-    g_fc.user_host.clear();
+    if (g_fc.consts) hipFree(g_fc.consts);
+    g_fc.ws = g_fc.consts = nullptr;
+    g_fc.ws_bytes = g_fc.consts_bytes = 0;
+    g_fc.consts_host.clear();
 }
-}  // namespace ssmq
 
-// A pair of models of which one or both are user-defined integrands: the whole-pass kernel compiled for them at run time
-// (ssmq_rtc.hip) with the time loop's constants in a small per-context block of its own, or an error - never the launch loop.
-static int filter_forward_user(FilterPass p, const double *GQG, const double *R, const double *sscale) {
-    const ssmq_transform *h_dyn = p.hd, *h_obs = p.ho;
-    const ssmq_integrand *f_dyn = p.fd, *f_obs = p.fo;
-    const int T = p.T;
-    hipStream_t s = p.s;
-    const int D = h_dyn->D, Y = h_obs->E;
-    FInfo fio, fid;
-    if (!integrand_info(f_obs->id, &fio) || !integrand_info(f_dyn->id, &fid)) {
+int make_filter_pass(const ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, const ssmq_transform *h_obs, const ssmq_integrand *f_obs,
+                     int64_t B, int64_t ld, int T, const double *y, const double *m0, const double *P0, double *fm, double *fP,
+                     int32_t *status, hipStream_t stream, FilterPass *out) {
+    FInfo fio;
+    if (!integrand_info(f_obs->id, &fio)) {
         set_error("unknown integrand id");
         return SSMQ_E_ARG;
     }
-    // G Q G' | R | scale [T] | time tables [T] x 2: a built-in member whose time dependence is tabulated on the host (UNGM) reads
-    // its table every step (HasTimeTable<> in ssmq_fused.h), as on the AOT route
-    const size_t nd = (size_t)D * D + (size_t)Y * Y + 3 * (size_t)T, need = sizeof(double) * nd;
-    if (g_fc.user_bytes < need) {
-        if (g_fc.user_ws) {
-            SSMQ_HIP(hipStreamSynchronize(s));
-            hipFree(g_fc.user_ws);
-        }
-        g_fc.user_ws = nullptr;
-        g_fc.user_bytes = 0;
-        g_fc.user_host.clear();
-        SSMQ_HIP(hipMalloc(&g_fc.user_ws, need));
-        g_fc.user_bytes = need;
-    }
-    std::vector<double> h(nd, 0.0);
-    if (GQG) std::copy(GQG, GQG + D * D, h.begin());
-    if (R) std::copy(R, R + Y * Y, h.begin() + D * D);
-    for (int k = 0; k < T; ++k) h[(size_t)D * D + Y * Y + k] = sscale ? sscale[k] : 1.0;
-    const size_t o_td = (size_t)D * D + Y * Y + T, o_to = o_td + T;
-    const bool has_td = time_table(f_dyn->id, T, h.data() + o_td), has_to = time_table(f_obs->id, T, h.data() + o_to);
-    double *w = (double *)g_fc.user_ws;
-    if (h != g_fc.user_host) {   // (stream order: earlier passes that read the block are done before the copy lands)
-        SSMQ_HIP(hipMemcpyAsync(w, h.data(), need, hipMemcpyHostToDevice, s));
-        SSMQ_HIP(hipStreamSynchronize(s));
-        g_fc.user_host = h;
-    }
-    p.sel_obs = sel_pattern(f_obs, fio.din);
-    p.gqg = w; p.rr = w + D * D; p.sscale = sscale ? w + D * D + Y * Y : nullptr;
-    p.ttab_dyn = has_td ? w + o_td : nullptr;
-    p.ttab_obs = has_to ? w + o_to : nullptr;
-    const int rc = rtc_launch_fused(p);
-    return rc < 0 ? rc : SSMQ_OK;
+    FilterPass p;
+    p.hd = h_dyn; p.fd = f_dyn; p.ho = h_obs; p.fo = f_obs; p.sel_obs = sel_pattern(f_obs, fio.din);
+    p.B = B; p.ld = ld; p.T = T; p.y = y; p.m0 = m0; p.P0 = P0; p.fm = fm; p.fP = fP; p.status = status; p.s = stream;
+    *out = p;
+    return SSMQ_OK;
 }
 
-namespace ssmq {
 // sscale (host, [T]) / student_dof: Studentian recursion (ssinf.py:634-736); null / 0 for the Gaussian filters.
 int filter_forward_impl(ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, ssmq_transform *h_obs,
                                const ssmq_integrand *f_obs, int64_t B, int64_t ld, int T, const double *d_y,
@@ -165,18 +152,23 @@ int filter_forward_impl(ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, ssmq
         return SSMQ_OK;
     }
     hipStream_t s = stream();
-    // the pass as the fused launchers take it; each route below adds the constants it has uploaded
     FilterPass pass;
-    pass.hd = h_dyn; pass.fd = f_dyn; pass.ho = h_obs; pass.fo = f_obs;
-    pass.B = B; pass.ld = ld; pass.T = T; pass.y = d_y; pass.m0 = d_m0; pass.P0 = d_P0; pass.fm = d_fm; pass.fP = d_fP;
-    pass.status = d_status; pass.student_dof = student_dof; pass.s = s;
-    if (user) return filter_forward_user(pass, GQG, R, sscale);
+    PassConsts pc;
+    if ((rc = make_filter_pass(h_dyn, f_dyn, h_obs, f_obs, B, ld, T, d_y, d_m0, d_P0, d_fm, d_fP, d_status, s, &pass)) ||
+        (rc = cached_pass_consts(f_dyn, f_obs, D, Y, T, GQG, R, sscale, s, &pc)))
+        return rc;
+    const double *cs = (const double *)g_fc.consts, *gqg = cs, *rr = cs + pc.rr, *tvec = cs + pc.steps;
+    const double *hs = g_fc.consts_host.data() + pc.scale;      // the scale on the host: ones for a Gaussian filter
+    wire_pass_consts(pass, cs, pc);
+    pass.student_dof = student_dof;
+    // A pair of models of which one or both are user-defined integrands: the whole-pass kernel compiled for them at run time
+    // (ssmq_rtc.hip), or an error - never the launch loop.
+    if (user) return (rc = rtc_launch_fused(pass)) < 0 ? rc : SSMQ_OK;
     // workspace carve-up (doubles first, then the two int32 status planes)
-    const size_t n_dbl = (size_t)ld * (D + 3 * D * D + Y + Y * Y + Y * D) + 4 * (size_t)T + D * D + Y * Y;
+    const size_t n_dbl = (size_t)ld * (D + 3 * D * D + Y + Y * Y + Y * D);
     const size_t need = sizeof(double) * n_dbl + 2 * sizeof(int32_t) * (size_t)ld;
     if (g_fc.ws_bytes < need) {
         g_fc.drop_graph();
-        g_fc.consts_ok = false;
         if (g_fc.ws) hipFree(g_fc.ws);
         g_fc.ws = nullptr;
         g_fc.ws_bytes = 0;
@@ -191,97 +183,30 @@ int filter_forward_impl(ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, ssmq
     double *P_y = w; w += (size_t)ld * Y * Y;
     double *P_yx = w; w += (size_t)ld * Y * D;
     double *smat = w; w += (size_t)ld * D * D;   // Studentian: rescaled scale matrix fed to the next time update
-    double *tvec = w; w += T;
-    double *svec = w; w += T;
-    double *ttab_d = w; w += T;   // time tables of the two integrands (UNGM: 8 cos(1.2 k)), see time_table()
-    double *ttab_o = w; w += T;
-    double *gqg = w; w += D * D;
-    double *rr = w; w += Y * Y;
     int32_t *st_a = (int32_t *)w, *st_b = st_a + ld;
-
-    std::vector<double> hg(D * D, 0.0), hr(Y * Y, 0.0);
-    if (GQG) hg.assign(GQG, GQG + D * D);
-    if (R) hr.assign(R, R + Y * Y);
-    std::vector<double> hs(T, 1.0);
-    if (sscale) hs.assign(sscale, sscale + T);
-    std::vector<uint64_t> key = {(uint64_t)(uintptr_t)h_dyn, (uint64_t)(uintptr_t)h_obs, (uint64_t)B, (uint64_t)ld,
-                                 (uint64_t)T, (uint64_t)(uintptr_t)d_y, (uint64_t)(uintptr_t)d_m0,
-                                 (uint64_t)(uintptr_t)d_P0, (uint64_t)(uintptr_t)d_fm, (uint64_t)(uintptr_t)d_fP,
-                                 (uint64_t)(uintptr_t)d_status, (uint64_t)(uintptr_t)h_dyn->d_small,
-                                 (uint64_t)(uintptr_t)g_fc.ws, (uint64_t)(uintptr_t)d_pm, (uint64_t)(uintptr_t)d_pP,
-                                 (uint64_t)(uintptr_t)d_pC};
-    const unsigned char *fb = (const unsigned char *)f_dyn;
-    for (size_t i = 0; i + 8 <= sizeof(ssmq_integrand); i += 8) { uint64_t v; memcpy(&v, fb + i, 8); key.push_back(v); }
-    fb = (const unsigned char *)f_obs;
-    for (size_t i = 0; i + 8 <= sizeof(ssmq_integrand); i += 8) { uint64_t v; memcpy(&v, fb + i, 8); key.push_back(v); }
-    key.push_back((uint64_t)h_dyn->emv_mode * 2 + (uint64_t)h_obs->emv_mode);
-    key.push_back(((uint64_t)D << 48) | ((uint64_t)Y << 32) | ((uint64_t)h_dyn->N << 16) | (uint64_t)h_obs->N);
-    key.push_back(((uint64_t)h_dyn->form << 2) | (uint64_t)h_obs->form);
-    key.push_back((uint64_t)(uintptr_t)h_obs->d_small);
-    key.push_back((uint64_t)(uintptr_t)h_dyn->d_mo);     // (the multi-output form's constant block: d_small is null there)
-    key.push_back((uint64_t)(uintptr_t)h_obs->d_mo);
-    // which kernel variant apply_dev_impl picks depends on the fast paths the handle's CURRENT constants qualify for:
-    // ssmq_transform_update keeps the block addresses but may withdraw SSMQ_OPT_LDL (and zero its factors)
-    key.push_back(((uint64_t)(uint32_t)h_dyn->opt_mask << 32) | (uint64_t)(uint32_t)h_obs->opt_mask);
-    key.push_back(((uint64_t)(uint32_t)h_dyn->np_pad << 32) | (uint64_t)(uint32_t)h_obs->np_pad);
-    key.push_back(((uint64_t)h_dyn->generation << 32) ^ (uint64_t)h_obs->generation);
-    { uint64_t v; memcpy(&v, &h_dyn->tp_nu, 8); key.push_back(v); memcpy(&v, &h_obs->tp_nu, 8); key.push_back(v);
-      memcpy(&v, &student_dof, 8); key.push_back(v); key.push_back(sscale ? 1 : 0); }
-
-    std::vector<double> htd(T), hto(T);
-    const bool has_td = time_table(f_dyn->id, T, htd.data()), has_to = time_table(f_obs->id, T, hto.data());
-    if (!(g_fc.consts_ok && g_fc.gqg == hg && g_fc.rr == hr && g_fc.T == T && g_fc.ss == hs &&
-          g_fc.fid_dyn == f_dyn->id && g_fc.fid_obs == f_obs->id && g_fc.ld == ld && g_fc.D == D && g_fc.Y == Y)) {
-        g_fc.drop_graph();
-        std::vector<double> tv(T);
-        for (int k = 0; k < T; ++k) tv[k] = (double)k;  // both transforms of step k + 1 use time index k (ssinf.py:104)
-        SSMQ_HIP(hipMemcpyAsync(tvec, tv.data(), sizeof(double) * T, hipMemcpyHostToDevice, s));
-        SSMQ_HIP(hipMemcpyAsync(gqg, hg.data(), sizeof(double) * D * D, hipMemcpyHostToDevice, s));
-        SSMQ_HIP(hipMemcpyAsync(rr, hr.data(), sizeof(double) * Y * Y, hipMemcpyHostToDevice, s));
-        SSMQ_HIP(hipMemcpyAsync(svec, hs.data(), sizeof(double) * T, hipMemcpyHostToDevice, s));
-        if (has_td) SSMQ_HIP(hipMemcpyAsync(ttab_d, htd.data(), sizeof(double) * T, hipMemcpyHostToDevice, s));
-        if (has_to) SSMQ_HIP(hipMemcpyAsync(ttab_o, hto.data(), sizeof(double) * T, hipMemcpyHostToDevice, s));
-        SSMQ_HIP(hipStreamSynchronize(s));
-        g_fc.fid_dyn = f_dyn->id;
-        g_fc.fid_obs = f_obs->id;
-        g_fc.ss = hs;
-        g_fc.gqg = hg;
-        g_fc.rr = hr;
-        g_fc.T = T;
-        g_fc.ld = ld;
-        g_fc.D = D;
-        g_fc.Y = Y;
-        g_fc.consts_ok = true;
-    }
     // one fused kernel for the whole time loop when this (models, shapes, form) combination has one (it does not keep
     // the predictive moments, so a pass that has to store them for the smoother takes the launch loop)
     const bool keep_pred = d_pm && d_pP && d_pC;
     if (!ssmq::sw("SSMQ_NO_FUSED") && !keep_pred && !mo) {
-        FInfo fio;
-        if (!integrand_info(f_obs->id, &fio)) {
-            set_error("unknown integrand id");
-            return SSMQ_E_ARG;
-        }
-        pass.sel_obs = sel_pattern(f_obs, fio.din);
-        pass.gqg = gqg; pass.rr = rr; pass.sscale = sscale ? svec : nullptr;
-        pass.ttab_dyn = has_td ? ttab_d : nullptr; pass.ttab_obs = has_to ? ttab_o : nullptr;
         rc = try_launch_fused(pass);
         if (rc < 0) return rc;
         if (rc == 1) return SSMQ_OK;
     }
     if (!ssmq::sw("SSMQ_NO_FUSED") && keep_pred && !sscale && student_dof == 0.0) {
         // smoother: the time loop in one kernel that also leaves the predictive moments of every step in HBM
-        FInfo fio;
-        if (!integrand_info(f_obs->id, &fio)) {
-            set_error("unknown integrand id");
-            return SSMQ_E_ARG;
-        }
-        pass.sel_obs = sel_pattern(f_obs, fio.din);
-        pass.ttab_dyn = has_td ? ttab_d : nullptr; pass.ttab_obs = has_to ? ttab_o : nullptr;
         rc = try_launch_fused_aug(pass, AugExtras{D, 0, 0, gqg, rr, gqg, d_pm, d_pP, d_pC});    // (no noise inputs: the block is not read)
         if (rc < 0) return rc;
         if (rc == 1) return SSMQ_OK;
     }
+    // which kernel variant apply_dev_impl picks depends on the handles' current constants: key_of_pair carries them
+    std::vector<uint64_t> key;
+    key_of_pair(key, h_dyn, f_dyn, h_obs, f_obs);
+    for (const void *p : {(const void *)d_y, (const void *)d_m0, (const void *)d_P0, (const void *)d_fm, (const void *)d_fP,
+                          (const void *)d_status, (const void *)g_fc.ws, (const void *)cs, (const void *)d_pm, (const void *)d_pP,
+                          (const void *)d_pC})
+        key.push_back((uint64_t)(uintptr_t)p);
+    for (uint64_t v : {(uint64_t)B, (uint64_t)ld, (uint64_t)T, (uint64_t)(sscale ? 1 : 0)}) key.push_back(v);
+    key_bytes(key, &student_dof, 8);
     if (!(g_fc.exec && g_fc.key == key)) {
         g_fc.drop_graph();
         SSMQ_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
@@ -295,10 +220,10 @@ int filter_forward_impl(ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, ssmq
                 C_xx = d_pC + (int64_t)k * D * D * ld;
             }
             rc = apply_dev_impl(h_dyn, f_dyn, B, ld, m_in, P_in, tvec + k, 0, m_pr, P_pr, C_xx, st_a, gqg, nullptr, false,
-                                hs[k], 1.0, has_td ? ttab_d : nullptr, false);
+                                hs[k], 1.0, pass.ttab_dyn, false);
             if (!rc)
                 rc = apply_dev_impl(h_obs, f_obs, B, ld, m_pr, P_pr, tvec + k, 0, y_mean, P_y, P_yx, st_b, rr, nullptr,
-                                    false, hs[k], hs[k], has_to ? ttab_o : nullptr, false);
+                                    false, hs[k], hs[k], pass.ttab_obs, false);
             if (!rc)
                 rc = launch_kalman_update_ex(D, Y, B, ld, m_pr, P_pr, y_mean, P_y, P_yx, d_y + (int64_t)k * Y * ld,
                                              d_fm + (int64_t)k * D * ld, d_fP + (int64_t)k * D * D * ld, d_status,
@@ -363,25 +288,23 @@ static int filter_forward_aug_impl(ssmq_transform *h_dyn, const ssmq_integrand *
         SSMQ_HIP(hipStreamSynchronize(s));
         return SSMQ_OK;
     }
-    // small constants first (time tables, noise statistics); the plane workspace only if the launch loop is needed
+    // small constants first (the time tables and steps in the context's block, the noise statistics in a block of this call);
+    // the plane workspace only if the launch loop is needed
+    FilterPass pass;
+    PassConsts pc;
+    if ((rc = make_filter_pass(h_dyn, f_dyn, h_obs, f_obs, B, ld, T, d_y, d_m0, d_P0, d_fm, d_fP, d_status, s, &pass)) ||
+        (rc = cached_pass_consts(f_dyn, f_obs, D, Y, T, nullptr, nullptr, nullptr, s, &pc)))
+        return rc;
+    wire_pass_consts(pass, (const double *)g_fc.consts, pc);
+    const double *tvec = pass.gqg + pc.steps, *ttab_d = pass.ttab_dyn, *ttab_o = pass.ttab_obs;
     DevBuf cs;
-    const size_t n_noise = (size_t)dq + (dq ? (size_t)dq * dq : (size_t)D * D) + dr + (dr ? (size_t)dr * dr : (size_t)Y * Y);
-    if ((rc = cs.alloc(sizeof(double) * (3 * (size_t)T + n_noise)))) return rc;
+    if ((rc = cs.alloc(sizeof(double) * ((size_t)dq + (dq ? (size_t)dq * dq : (size_t)D * D) + dr + (dr ? (size_t)dr * dr : (size_t)Y * Y))))) return rc;
     double *w = cs.d();
-    double *tvec = w; w += T;
-    double *ttab_d = w; w += T;
-    double *ttab_o = w; w += T;
     double *d_qm = w; w += dq;
     double *d_qc = w; w += dq ? (size_t)dq * dq : (size_t)D * D;
     double *d_rm = w; w += dr;
     double *d_rc = w; w += dr ? (size_t)dr * dr : (size_t)Y * Y;
 
-    std::vector<double> tv(T), htd(T), hto(T);
-    for (int k = 0; k < T; ++k) tv[k] = (double)k;   // both transforms of step k + 1 use time index k (ssinf.py:104)
-    const bool has_td = time_table(f_dyn->id, T, htd.data()), has_to = time_table(f_obs->id, T, hto.data());
-    SSMQ_HIP(hipMemcpyAsync(tvec, tv.data(), sizeof(double) * T, hipMemcpyHostToDevice, s));
-    if (has_td) SSMQ_HIP(hipMemcpyAsync(ttab_d, htd.data(), sizeof(double) * T, hipMemcpyHostToDevice, s));
-    if (has_to) SSMQ_HIP(hipMemcpyAsync(ttab_o, hto.data(), sizeof(double) * T, hipMemcpyHostToDevice, s));
     std::vector<double> zq((size_t)D * D, 0.0), zr((size_t)Y * Y, 0.0);
     if (dq) SSMQ_HIP(hipMemcpyAsync(d_qm, q_mean, sizeof(double) * dq, hipMemcpyHostToDevice, s));
     SSMQ_HIP(hipMemcpyAsync(d_qc, q_cov ? q_cov : zq.data(), sizeof(double) * (dq ? (size_t)dq * dq : (size_t)D * D),
@@ -394,11 +317,6 @@ static int filter_forward_aug_impl(ssmq_transform *h_dyn, const ssmq_integrand *
 
     // one kernel for the whole time loop when this combination has an instantiation (ssmq_filter_fused.hip)
     if (!ssmq::sw("SSMQ_NO_FUSED")) {
-        FInfo fio;
-        if (!integrand_info(f_obs->id, &fio)) {
-            set_error("unknown integrand id");
-            return SSMQ_E_ARG;
-        }
         // noise block q_mean | q_cov | r_mean | r_cov and the additive terms (zeros for a non-additive model)
         std::vector<double> hn, ha((size_t)D * D + (size_t)Y * Y, 0.0);
         for (int i = 0; i < dq; ++i) hn.push_back(q_mean[i]);
@@ -412,10 +330,6 @@ static int filter_forward_aug_impl(ssmq_transform *h_dyn, const ssmq_integrand *
         if ((rc = dn.alloc(sizeof(double) * hn.size())) || (rc = da.alloc(sizeof(double) * ha.size()))) return rc;
         SSMQ_HIP(hipMemcpyAsync(dn.p, hn.data(), sizeof(double) * hn.size(), hipMemcpyHostToDevice, s));
         SSMQ_HIP(hipMemcpyAsync(da.p, ha.data(), sizeof(double) * ha.size(), hipMemcpyHostToDevice, s));
-        FilterPass pass;
-        pass.hd = h_dyn; pass.fd = f_dyn; pass.ho = h_obs; pass.fo = f_obs; pass.sel_obs = sel_pattern(f_obs, fio.din);
-        pass.B = B; pass.ld = ld; pass.T = T; pass.y = d_y; pass.m0 = d_m0; pass.P0 = d_P0; pass.fm = d_fm; pass.fP = d_fP;
-        pass.status = d_status; pass.ttab_dyn = has_td ? ttab_d : nullptr; pass.ttab_obs = has_to ? ttab_o : nullptr; pass.s = s;
         rc = try_launch_fused_aug(pass, AugExtras{D, dq, dr, da.d(), da.d() + (size_t)D * D, dn.d(), d_pm, d_pP, d_pC});
         hipError_t e = hipStreamSynchronize(s);
         if (rc < 0) return rc;
@@ -456,20 +370,20 @@ static int filter_forward_aug_impl(ssmq_transform *h_dyn, const ssmq_integrand *
             rc = launch_augment(m_in, P_in, d_qm, d_qc, ma, Pa, D, dq, B, ld, s);
             if (!rc)
                 rc = apply_dev_impl(h_dyn, f_dyn, B, ld, ma, Pa, tvec + k, 0, m_pr, P_pr, C_xx, st_a, nullptr, nullptr, false,
-                                    1.0, 1.0, has_td ? ttab_d : nullptr, false);
+                                    1.0, 1.0, ttab_d, false);
         } else {
             rc = apply_dev_impl(h_dyn, f_dyn, B, ld, m_in, P_in, tvec + k, 0, m_pr, P_pr, C_xx, st_a, d_qc, nullptr, false,
-                                1.0, 1.0, has_td ? ttab_d : nullptr, false);
+                                1.0, 1.0, ttab_d, false);
         }
         if (rc) break;
         if (dr) {
             rc = launch_augment(m_pr, P_pr, d_rm, d_rc, mo, Po, D, dr, B, ld, s);
             if (!rc)
                 rc = apply_dev_impl(h_obs, f_obs, B, ld, mo, Po, tvec + k, 0, y_mean, P_y, P_yx, st_b, nullptr, nullptr, false,
-                                    1.0, 1.0, has_to ? ttab_o : nullptr, false);
+                                    1.0, 1.0, ttab_o, false);
         } else {
             rc = apply_dev_impl(h_obs, f_obs, B, ld, m_pr, P_pr, tvec + k, 0, y_mean, P_y, P_yx, st_b, d_rc, nullptr, false,
-                                1.0, 1.0, has_to ? ttab_o : nullptr, false);
+                                1.0, 1.0, ttab_o, false);
         }
         if (!rc)
             rc = launch_kalman_update_ex(D, Y, B, ld, m_pr, P_pr, y_mean, P_y, P_yx, d_y + (int64_t)k * Y * ld,
@@ -613,15 +527,14 @@ extern "C" int ssmq_filter_kernel_name_batch(const ssmq_transform *h_dyn, const 
                                              const ssmq_integrand *f_obs, int64_t B, char *buf, int len) {
     SSMQ_HANDLE_LOCK(h_dyn, h_obs);
     if (!h_dyn || !h_obs || !f_dyn || !f_obs || !buf || len <= 0 || B < 0) return SSMQ_E_ARG;
-    FInfo fio;
-    if (!integrand_info(f_obs->id, &fio)) return SSMQ_E_ARG;
     const char *name = nullptr;
     FilterPass query;
-    query.hd = h_dyn; query.fd = f_dyn; query.ho = h_obs; query.fo = f_obs; query.sel_obs = sel_pattern(f_obs, fio.din); query.B = B;
+    int rc = make_filter_pass(h_dyn, f_dyn, h_obs, f_obs, B, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &query);
+    if (rc) return rc;
     query.name = &name; query.dry_run = true;
     const bool mo = is_mo(h_dyn) || is_mo(h_obs);       // no fused time loop takes the multi-output form
     if (mo && (is_user_integrand(f_dyn) || is_user_integrand(f_obs))) return refuse_user_integrand("multi-output transform (k_apply_mo)");
-    int rc = mo || (ssmq::sw("SSMQ_NO_FUSED") && !is_user_integrand(f_dyn) && !is_user_integrand(f_obs)) ? 0 : try_launch_fused(query);
+    rc = mo || (ssmq::sw("SSMQ_NO_FUSED") && !is_user_integrand(f_dyn) && !is_user_integrand(f_obs)) ? 0 : try_launch_fused(query);
     if (rc < 0) return rc;
     snprintf(buf, len, "%s", rc == 1 ? name : "hipGraph of 3 T launches (apply dyn | apply obs | k_kalman_update)");
     return SSMQ_OK;

@@ -67,12 +67,6 @@ MultiCache &multi_of_ctx() {
     if (!c.multi) c.multi = new MultiCache;
     return *(MultiCache *)c.multi;
 }
-void key_bytes(std::vector<uint64_t> &key, const void *p, size_t n) {
-    const unsigned char *b = (const unsigned char *)p;
-    size_t i = 0;
-    for (; i + 8 <= n; i += 8) { uint64_t v; memcpy(&v, b + i, 8); key.push_back(v); }
-    if (i < n) { uint64_t v = 0; memcpy(&v, b + i, n - i); key.push_back(v); }
-}
 }  // namespace
 namespace ssmq {
 void drop_multi_cache() {
@@ -121,17 +115,12 @@ extern "C" int ssmq_filter_forward_multi_dev(int n_jobs, const ssmq_filter_job *
     for (int i = 0; i < n_jobs; ++i) {
         const ssmq_filter_job &j = jobs[i];
         const int D = j.h_dyn->D, Y = j.h_obs->E;
-        for (const void *p : {(const void *)j.h_dyn, (const void *)j.h_obs, (const void *)j.d_y, (const void *)j.d_m0, (const void *)j.d_P0,
-                              (const void *)j.d_fm, (const void *)j.d_fP, (const void *)j.d_status, (const void *)j.h_dyn->d_small,
-                              (const void *)j.h_obs->d_small})
+        key_of_pair(key, j.h_dyn, j.f_dyn, j.h_obs, j.f_obs);
+        for (const void *p : {(const void *)j.d_y, (const void *)j.d_m0, (const void *)j.d_P0, (const void *)j.d_fm, (const void *)j.d_fP,
+                              (const void *)j.d_status})
             key.push_back((uint64_t)(uintptr_t)p);
         key.push_back((uint64_t)j.B); key.push_back((uint64_t)j.ld); key.push_back((uint64_t)j.T);
-        key_bytes(key, j.f_dyn, sizeof(ssmq_integrand));
-        key_bytes(key, j.f_obs, sizeof(ssmq_integrand));
-        key.push_back(((uint64_t)j.h_dyn->generation << 32) ^ (uint64_t)j.h_obs->generation);
-        key.push_back(((uint64_t)(uint32_t)j.h_dyn->opt_mask << 32) | (uint64_t)(uint32_t)j.h_obs->opt_mask);
-        key.push_back((uint64_t)j.h_dyn->emv_mode * 2 + (uint64_t)j.h_obs->emv_mode);
-        key_bytes(key, &j.h_dyn->tp_nu, 8); key_bytes(key, &j.h_obs->tp_nu, 8); key_bytes(key, &j.dof, 8);
+        key_bytes(key, &j.dof, 8);
         if (j.GQG) key_bytes(key, j.GQG, sizeof(double) * D * D); else key.push_back(0);
         if (j.R) key_bytes(key, j.R, sizeof(double) * Y * Y); else key.push_back(0);
         if (j.scale) key_bytes(key, j.scale, sizeof(double) * j.T); else key.push_back(0);
@@ -155,12 +144,10 @@ extern "C" int ssmq_filter_forward_multi_dev(int n_jobs, const ssmq_filter_job *
         return run_rest();
     }
     mc.drop_graph();
-    // ---- per-job constants behind one allocation: G Q G', R, scale [T], the two time tables [T] ---------------------------------
-    size_t n_dbl = 0;
-    for (int i = 0; i < n_jobs; ++i) {
-        const int D = jobs[i].h_dyn->D, Y = jobs[i].h_obs->E;
-        n_dbl += (size_t)D * D + (size_t)Y * Y + 3 * (size_t)jobs[i].T + 8;
-    }
+    // ---- per-job constants behind one allocation: one block of the PassConsts layout (ssmq_host.h) per job, side by side --------
+    std::vector<size_t> off(n_jobs + 1, 0);
+    for (int i = 0; i < n_jobs; ++i) off[i + 1] = off[i] + pass_consts_doubles(jobs[i].h_dyn->D, jobs[i].h_obs->E, jobs[i].T);
+    const size_t n_dbl = off[n_jobs];
     if (mc.ws_bytes < sizeof(double) * n_dbl) {
         SSMQ_HIP(hipStreamSynchronize(s));
         if (mc.ws) hipFree(mc.ws);
@@ -169,24 +156,11 @@ extern "C" int ssmq_filter_forward_multi_dev(int n_jobs, const ssmq_filter_job *
         SSMQ_HIP(hipMalloc(&mc.ws, sizeof(double) * n_dbl * 2));
         mc.ws_bytes = sizeof(double) * n_dbl * 2;
     }
-    std::vector<double> host(n_dbl, 0.0);
-    struct JobConsts { const double *gqg, *rr, *svec, *ttd, *tto; };
-    std::vector<JobConsts> jc(n_jobs);
-    {
-        size_t o = 0;
-        double *dev = (double *)mc.ws;
-        for (int i = 0; i < n_jobs; ++i) {
-            const ssmq_filter_job &j = jobs[i];
-            const int D = j.h_dyn->D, Y = j.h_obs->E, T = j.T;
-            jc[i].gqg = dev + o; if (j.GQG) memcpy(&host[o], j.GQG, sizeof(double) * D * D); o += (size_t)D * D;
-            jc[i].rr = dev + o; if (j.R) memcpy(&host[o], j.R, sizeof(double) * Y * Y); o += (size_t)Y * Y;
-            jc[i].svec = j.scale ? dev + o : nullptr; if (j.scale) memcpy(&host[o], j.scale, sizeof(double) * T); o += T;
-            const bool td = T > 0 && time_table(j.f_dyn->id, T, &host[o]);
-            jc[i].ttd = td ? dev + o : nullptr; o += T;
-            const bool to = T > 0 && time_table(j.f_obs->id, T, &host[o]);
-            jc[i].tto = to ? dev + o : nullptr; o += T;
-            o = (o + 7) / 8 * 8;
-        }
+    std::vector<double> host(n_dbl);
+    std::vector<PassConsts> jc(n_jobs);
+    for (int i = 0; i < n_jobs; ++i) {
+        const ssmq_filter_job &j = jobs[i];
+        jc[i] = fill_pass_consts(&host[off[i]], j.f_dyn, j.f_obs, j.h_dyn->D, j.h_obs->E, j.T, j.GQG, j.R, j.scale);
     }
     SSMQ_HIP(hipMemcpyAsync(mc.ws, host.data(), sizeof(double) * n_dbl, hipMemcpyHostToDevice, s));
     SSMQ_HIP(hipStreamSynchronize(s));          // `host` goes out of scope; only when the job list changed
@@ -206,15 +180,11 @@ extern "C" int ssmq_filter_forward_multi_dev(int n_jobs, const ssmq_filter_job *
     const bool no_fused = ssmq::sw("SSMQ_NO_FUSED") != nullptr;
     for (int i = 0; i < n_jobs && !no_fused; ++i) {
         const ssmq_filter_job &j = jobs[i];
-        FInfo fio;
-        if (!integrand_info(j.f_obs->id, &fio)) {
-            set_error("unknown integrand id");
-            return SSMQ_E_ARG;
-        }
         FilterPass &p = pass[i];
-        p.hd = j.h_dyn; p.fd = j.f_dyn; p.ho = j.h_obs; p.fo = j.f_obs; p.sel_obs = sel_pattern(j.f_obs, fio.din);
-        p.B = j.B; p.ld = j.ld; p.T = j.T; p.y = j.d_y; p.m0 = j.d_m0; p.P0 = j.d_P0; p.fm = j.d_fm; p.fP = j.d_fP; p.status = j.d_status;
-        p.gqg = jc[i].gqg; p.rr = jc[i].rr; p.sscale = jc[i].svec; p.student_dof = j.dof; p.ttab_dyn = jc[i].ttd; p.ttab_obs = jc[i].tto;
+        if ((rc = make_filter_pass(j.h_dyn, j.f_dyn, j.h_obs, j.f_obs, j.B, j.ld, j.T, j.d_y, j.d_m0, j.d_P0, j.d_fm, j.d_fP, j.d_status, nullptr, &p)))
+            return rc;
+        wire_pass_consts(p, (const double *)mc.ws + off[i], jc[i]);
+        p.student_dof = j.dof;
         if (j.B == 0 || j.T == 0) continue;
         FilterPass query = p;
         query.B = 0;                 // (whatever the batch: the whole-pass kernel, not a schedule for small or uneven batches)
@@ -495,14 +465,8 @@ extern "C" int ssmq_filter_forward_piped(ssmq_transform *h_dyn, const ssmq_integ
         for (int64_t b = 0; b < B; ++b) status[b] = 0;
         return SSMQ_OK;
     }
-    FInfo fio;
-    if (!integrand_info(f_obs->id, &fio)) {
-        set_error("unknown integrand id");
-        return SSMQ_E_ARG;
-    }
-    FilterPass pass, query;
-    pass.hd = h_dyn; pass.fd = f_dyn; pass.ho = h_obs; pass.fo = f_obs; pass.sel_obs = sel_pattern(f_obs, fio.din); pass.B = B; pass.T = T;
-    query = pass;
+    FilterPass query;
+    if ((rc = make_filter_pass(h_dyn, f_dyn, h_obs, f_obs, B, 0, T, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &query))) return rc;
     query.dry_run = true;
     // (a forced route - wave split, quad, strips, lanes per wave - means the caller wants THAT kernel: not pipelined)
     if (ssmq::sw("SSMQ_NO_FUSED") || ssmq::sw("SSMQ_NO_PIPED") || ssmq::sw("SSMQ_FUSED_WSPLIT") || ssmq::sw("SSMQ_FUSED_QUAD") ||
@@ -534,7 +498,7 @@ extern "C" int ssmq_filter_forward_piped(ssmq_transform *h_dyn, const ssmq_integ
     }
     // ---- device block and pinned staging (grow-only, per context) ---------------------------------------------------------------
     const size_t n_y = (size_t)T * Y * ld, n_m = (size_t)D * ld, n_P = (size_t)D * D * ld, n_fm = (size_t)T * D * ld, n_fP = (size_t)T * D * D * ld;
-    const size_t n_c = ((size_t)D * D + (size_t)Y * Y + 2 * (size_t)T + 7) / 8 * 8, n_hand = (size_t)nblk * range_hand_doubles(D);
+    const size_t n_c = pass_consts_doubles(D, Y, T), n_hand = (size_t)nblk * range_hand_doubles(D);
     const size_t d_dbl = n_y + n_m + n_P + n_fm + n_fP + n_c + n_hand;
     // pageable results are staged block by block through TWO slots (block k + 1 lands while block k - 1's slot is free again)
     auto t_of = [&](int k) { return (int)((int64_t)T * k / K); };
@@ -559,10 +523,7 @@ extern "C" int ssmq_filter_forward_piped(ssmq_transform *h_dyn, const ssmq_integ
     double *h_out = (double *)g_stage.hout;       // [2][slot_dbl]: a block's means, then its covariances
     int32_t *h_st = (int32_t *)((double *)g_stage.hout + hout_dbl);
     // ---- constants and initial moments, then the first block of measurements: one transfer ------------------------------------
-    double *c_gqg = h_c, *c_rr = c_gqg + D * D, *c_ttd = c_rr + Y * Y, *c_tto = c_ttd + T;
-    for (int i = 0; i < D * D; ++i) c_gqg[i] = GQG ? GQG[i] : 0.0;
-    for (int i = 0; i < Y * Y; ++i) c_rr[i] = R ? R[i] : 0.0;
-    const bool has_td = time_table(f_dyn->id, T, c_ttd), has_to = time_table(f_obs->id, T, c_tto);
+    const PassConsts pcs = fill_pass_consts(h_c, f_dyn, f_obs, D, Y, T, GQG, R, nullptr);
     if (per_traj) {
         for (int d = 0; d < D; ++d)
             for (int64_t b = 0; b < ld; ++b) h_m0[(size_t)d * ld + b] = b < B ? m0[b * D + d] : 0.0;
@@ -573,9 +534,9 @@ extern "C" int ssmq_filter_forward_piped(ssmq_transform *h_dyn, const ssmq_integ
         for (int i = 0; i < D * D; ++i) std::fill(h_P0 + (size_t)i * ld, h_P0 + (size_t)(i + 1) * ld, P0[i]);
     }
     SSMQ_HIP(hipMemcpyAsync(d_m0, h_m0, sizeof(double) * (n_m + n_P + n_c), hipMemcpyHostToDevice, pc.s_in));      // m0 | P0 | consts are adjacent
-    pass.ld = ld; pass.y = d_y; pass.m0 = d_m0; pass.P0 = d_P0; pass.fm = d_fm; pass.fP = d_fP; pass.status = d_st;
-    pass.gqg = d_c; pass.rr = d_c + D * D; pass.ttab_dyn = has_td ? d_c + D * D + Y * Y : nullptr;
-    pass.ttab_obs = has_to ? d_c + D * D + Y * Y + T : nullptr; pass.s = s;
+    FilterPass pass;
+    if ((rc = make_filter_pass(h_dyn, f_dyn, h_obs, f_obs, B, ld, T, d_y, d_m0, d_P0, d_fm, d_fP, d_st, s, &pass))) return rc;
+    wire_pass_consts(pass, d_c, pcs);
     auto drain = [&](int k) -> int {        // block k's outputs are in host memory: bring them into the caller's arrays if staged
         SSMQ_HIP(hipEventSynchronize(pc.ev_out[k]));
         if (!out_pinned) {

@@ -1,6 +1,8 @@
 // Host-side internals of libssmq shared between translation units.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <algorithm>
+#include <cstring>
 #include <initializer_list>
 #include <mutex>
 #include <string>
@@ -374,6 +376,61 @@ struct FilterPass {
     const char **name = nullptr;                                  // receives the kernel's name, or null
     bool dry_run = false;                                         // only say whether a kernel exists (and its name)
 };
+// The one place that builds a pass: looks the measurement integrand up (sel_obs; an id unknown to integrand_info() is
+// SSMQ_E_ARG - the transforms of a launch loop would refuse it all the same) and sets every field, the constants (below), the
+// Studentian dof, name and dry_run at their defaults.  ssmq_api_filter.hip.
+int make_filter_pass(const ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, const ssmq_transform *h_obs, const ssmq_integrand *f_obs,
+                     int64_t B, int64_t ld, int T, const double *y, const double *m0, const double *P0, double *fm, double *fP,
+                     int32_t *status, hipStream_t stream, FilterPass *out);
+// The small per-pass constants of the time loop, ONE layout for every route:
+//     gqg [D*D] | rr [Y*Y] | scale [T] | ttab_dyn [T] | ttab_obs [T] | steps [T]        (rounded up to 8 doubles)
+// steps holds 0 .. T-1, the time argument of the launch loops (both transforms of step k + 1 use time index k, ssinf.py:104).
+// The single-filter routes keep one block per context (ssmq_api_filter.hip: FilterCache), the multi-filter entry one per job
+// side by side (MultiCache), the piped pass sends it as the third part of its m0 | P0 | constants transfer.
+struct PassConsts {
+    size_t rr, scale, ttab_dyn, ttab_obs, steps;   // where the segments start, in doubles (gqg at 0)
+    bool has_scale, has_ttab_dyn, has_ttab_obs;    // the caller passed a scale; time_table() filled that table (T > 0)
+};
+inline size_t pass_consts_doubles(int D, int Y, int T) { return ((size_t)D * D + (size_t)Y * Y + 4 * (size_t)T + 7) / 8 * 8; }
+// ... its host image: null GQG / R are zeros, a null scale is ones, an absent table and the padding are zeros
+inline PassConsts fill_pass_consts(double *host, const ssmq_integrand *f_dyn, const ssmq_integrand *f_obs, int D, int Y, int T,
+                                   const double *GQG, const double *R, const double *sscale) {
+    PassConsts c;
+    c.rr = (size_t)D * D; c.scale = c.rr + (size_t)Y * Y; c.ttab_dyn = c.scale + T; c.ttab_obs = c.ttab_dyn + T; c.steps = c.ttab_obs + T;
+    std::fill(host, host + pass_consts_doubles(D, Y, T), 0.0);
+    if (GQG) std::copy(GQG, GQG + c.rr, host);
+    if (R) std::copy(R, R + (size_t)Y * Y, host + c.rr);
+    for (int k = 0; k < T; ++k) {
+        host[c.scale + k] = sscale ? sscale[k] : 1.0;
+        host[c.steps + k] = (double)k;
+    }
+    c.has_scale = sscale != nullptr;
+    c.has_ttab_dyn = T > 0 && time_table(f_dyn->id, T, host + c.ttab_dyn);
+    c.has_ttab_obs = T > 0 && time_table(f_obs->id, T, host + c.ttab_obs);
+    return c;
+}
+// ... and the pass's pointers into the block at `dev`; the kernels branch on a null scale / table
+inline void wire_pass_consts(FilterPass &p, const double *dev, const PassConsts &c) {
+    p.gqg = dev; p.rr = dev + c.rr; p.sscale = c.has_scale ? dev + c.scale : nullptr;
+    p.ttab_dyn = c.has_ttab_dyn ? dev + c.ttab_dyn : nullptr; p.ttab_obs = c.has_ttab_obs ? dev + c.ttab_obs : nullptr;
+}
+// What a captured launch depends on, as words of a graph key: raw bytes of a struct ...
+inline void key_bytes(std::vector<uint64_t> &key, const void *p, size_t n) {
+    const unsigned char *b = (const unsigned char *)p;
+    for (size_t i = 0; i < n; i += 8) { uint64_t v = 0; memcpy(&v, b + i, std::min<size_t>(8, n - i)); key.push_back(v); }
+}
+// ... and everything about the two handles and the two integrands of a filter.  ssmq_transform_update keeps a handle's block
+// addresses but may change the fast paths its constants qualify for (opt_mask) - and bumps `generation`.
+inline void key_of_pair(std::vector<uint64_t> &key, const ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, const ssmq_transform *h_obs,
+                        const ssmq_integrand *f_obs) {
+    for (const ssmq_transform *h : {h_dyn, h_obs}) {
+        for (const void *p : {(const void *)h, (const void *)h->d_small, (const void *)h->d_mo}) key.push_back((uint64_t)(uintptr_t)p);
+        for (int v : {h->D, h->E, h->N, h->form, h->emv_mode, h->opt_mask, h->np_pad, (int)h->generation}) key.push_back((uint64_t)(uint32_t)v);
+        key_bytes(key, &h->tp_nu, 8);
+    }
+    key_bytes(key, f_dyn, sizeof(ssmq_integrand));
+    key_bytes(key, f_obs, sizeof(ssmq_integrand));
+}
 // The one place that fills the kernels' argument block from a pass: everything zero but the pass's fields, lpw = 64
 // (ssmq_filter_fused.hip).  A route states what it sets differently next to its launch.
 FusedArgs fused_args(const FilterPass &p);

@@ -388,7 +388,7 @@ int rtc_launch_fused(const FilterPass &p) {
     }
     if (p.dry_run) return 1;
     // A built-in member with a host time table (UNGM) is read through that table at every step of the loop, unconditionally: the
-    // caller must have uploaded it (filter_forward_user does).
+    // caller must have uploaded it (filter_forward_impl does, with the pass's constants).
     FusedArgs a = fused_args(p);
     for (const ssmq_integrand *f : {fd, fo}) {
         const double *tab = f == fd ? a.fd.ttab : a.fo.ttab;

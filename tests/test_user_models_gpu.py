@@ -302,3 +302,63 @@ def test_mixed_pair_with_builtin_time_table(amd, golden, monkeypatch, name):
     assert 'run-time compiled' in out[1][2] and out[0][2].startswith('k_filter_fused<'), (out[0][2], out[1][2])
     assert np.all(np.isfinite(out[1][0]))
     assert np.array_equal(out[0][0], out[1][0]) and np.array_equal(out[0][1], out[1][1])
+
+
+@pytest.mark.parametrize('launch_loop', [False, True], ids=['default-routes', 'launch-loop'])
+def test_user_and_builtin_filters_share_one_constants_block(amd, golden, monkeypatch, launch_loop):
+    """The run-time compiled route and the built-in route keep the pass's constants in ONE cached block per context.  B = 64:
+    (a) UNGM GPQ-Kalman, T = 5 (built-in, time table), (b) the Van der Pol user pair, D = 2, its own Q and R, T = 5, (c) the
+    built-in pendulum UKF, no time table, T = 3.  Each result from its first call; then a, b, c, a, c, b, a with a changed R in
+    the second-to-last call: every repeat with the original arguments is the first call bit for bit (means, covariances,
+    status) - a shorter T or smaller D after a larger one leaves nothing stale in sight - and the changed-R call differs and
+    repeats itself bit for bit.  Once with the default routes and once with the built-in calls on the captured launch loop
+    (SSMQ_NO_FUSED=1), whose graph reads the block."""
+    from ssmtoybox_amd import ssinf, ssmod as sm
+    from bench import simulate_ungm
+    monkeypatch.setenv('SSMQ_NO_PIPED', '1')          # the device-resident entry point, not the pipelined host-array pass
+    g = golden('g15_user_models')
+    rng = np.random.default_rng(15)
+    B = 64
+    par = np.array([[1.0, 3.0]])
+    ungm = ssinf.GaussianProcessKalman(sm.UNGMTransition(sm.GaussRV(1), sm.GaussRV(1, cov=np.array([[10.0]]))),
+                                       sm.UNGMMeasurement(sm.GaussRV(1), 1), par, par, 'rbf', 'ut')
+    vdp = _filter('ukf', *_system(g, 'vdp'), 2)
+    pend = ssinf.UnscentedKalman(
+        sm.Pendulum2DTransition(sm.GaussRV(2, mean=np.array([1.5, 0.0]), cov=0.01 * np.eye(2)), sm.GaussRV(2, cov=0.01 * np.eye(2)), 0.01),
+        sm.Pendulum2DMeasurement(sm.GaussRV(1, cov=np.array([[0.1]])), 2))
+    assert 'run-time compiled' in vdp.kernel_name(B)
+    data = {'a': np.ascontiguousarray(simulate_ungm(B, 5, 15)[1][None]),
+            'b': np.tile(g['vdp_y'][:, :5], (1, 1, 8)) + 0.01 * rng.standard_normal((1, 5, B)),
+            'c': 1.0 + 0.3 * rng.standard_normal((1, 3, B))}
+    algs = {'a': ungm, 'b': vdp, 'c': pend}
+    r_b = vdp.r_cov.copy()
+
+    def run(tag, r_cov=None):
+        alg = algs[tag]
+        if launch_loop and tag != 'b':
+            monkeypatch.setenv('SSMQ_NO_FUSED', '1')
+            assert alg.kernel_name(B).startswith('hipGraph')
+        if r_cov is not None:
+            alg.r_cov = r_cov
+        try:
+            fm, fP = alg.forward_pass_batch(data[tag], raise_on_failure=False)
+        finally:
+            monkeypatch.delenv('SSMQ_NO_FUSED', raising=False)
+            if tag == 'b':
+                alg.r_cov = r_b
+        assert np.isfinite(fm).all() and np.isfinite(fP).all() and not alg.status.any(), tag
+        return fm.copy(), fP.copy(), alg.status.copy()
+
+    def same(x, y):
+        return all(np.array_equal(p, q) for p, q in zip(x, y))
+
+    first = {tag: run(tag) for tag in 'abc'}
+    assert first['a'][0].shape == (1, 5, B) and first['b'][1].shape == (2, 2, 5, B) and first['c'][0].shape == (2, 3, B)
+    for i, tag in enumerate('abcacba'):
+        if i == 5:
+            changed = run('b', 2.0 * r_b)
+            assert not np.array_equal(changed[0], first['b'][0]) and not np.array_equal(changed[1], first['b'][1])
+        else:
+            assert same(run(tag), first[tag]), (i, tag)
+    assert same(run('b', 2.0 * r_b), changed)
+    assert same(run('b'), first['b'])
