@@ -128,9 +128,13 @@ enum ssmq_form {
     SSMQ_FORM_SIGMA = 1, /* mtran.py:141-149: centred, diagonal Wc: cov = dfx diag(wc) dfx'; ccov = dfx diag(wc) (x-m)' */
     SSMQ_FORM_TAYLOR1 = 2, /* mtran.py:49-59 (LinearizationTransform): mean = f(m); J = df/dx(m); ccov = J cov; cov = ccov J'.
                              Handles of this form come from ssmq_transform_create_linear only */
-    SSMQ_FORM_BQ_MO = 3  /* multi-output BQ (bq/bqmtran.py:425-602): one weight set per output and output pair -
+    SSMQ_FORM_BQ_MO = 3, /* multi-output BQ (bq/bqmtran.py:425-602): one weight set per output and output pair -
                             mean_i = fx_i wm_i; cov_ij = fx_i Wc_ij fx_j' - mean_i mean_j + delta_ij emv_i; ccov_i = fx_i Wcc_i' L'.
                             Handles of this form come from ssmq_transform_create_mo only */
+    SSMQ_FORM_TAYLOR_GPQD = 4 /* mtran.py:668-701 (TaylorGPQDTransform): the linearisation read as single-point GP quadrature with
+                            derivative observations and an RBF kernel - mean = wm f(m); cov = wc (f f' + J Wc J') - mean mean' +
+                            model_var; ccov = J cov (Lam + cov)^-1 Lam.  Handles of this form come from
+                            ssmq_transform_create_taylor_gpqd only */
 };
 
 /* How the expected model variance enters the covariance (bq/bqmtran.py:198 `model_var * I_out`). */
@@ -379,6 +383,26 @@ int ssmq_transform_update(ssmq_transform *h, const double *xi, const double *wm,
  * other integrand: SSMQ_E_UNSUPPORTED at apply time, where the reference's Jacobian is None).  The handle goes wherever a
  * transform handle goes (ssmq_apply_batch[_dev], the filter / smoother entry points: time loop as a launch loop). */
 ssmq_transform *ssmq_transform_create_linear(int D, int E);
+/*
+ * The Taylor-GPQD transform of ExtendedKalmanGPQD (SSMQ_FORM_TAYLOR_GPQD; mtran.py:668-701, ssinf.py:1302-1319): the linearisation
+ * transform calibrated by an RBF kernel with scale alpha and length-scales ell [D], Lam = diag(ell^2).  With f = f(mean) and J the
+ * model's own Jacobian (the models of ssmq_transform_create_linear; every other integrand, and every user integrand:
+ * SSMQ_E_UNSUPPORTED at apply time):
+ *   wm = det(Lam^-1 cov + I)^-1/2, wc = det(2 Lam^-1 cov + I)^-1/2, Wc = Lam/2 (Lam/2 + cov)^-1 cov,
+ *   model_var = alpha^2 - alpha^2 wc (1 + tr(Wc Lam^-1)), integ_var = alpha^2 wc - wm^2,
+ *   mean_f = wm f, cov_f = wc (f f' + J Wc J') - mean_f mean_f' + model_var (the scalar on every entry, as the reference adds it),
+ *   cov_fx = J cov (Lam + cov)^-1 Lam - (E, D) as every transform of this library; the reference returns the transpose (D, E).
+ * One launch of k_taylor_gpqd per batch; status 1 and NaN outputs for an item whose Lam + cov or Lam/2 + cov has a pivot that is
+ * not positive (cov not positive semi-definite).  alpha, ell finite, ell > 0, D <= SSMQ_MAX_DIM (else NULL, SSMQ_E_ARG semantics:
+ * ssmq_last_error() names the argument).  The handle runs through ssmq_apply_batch[_dev], ssmq_apply_kernel_name and the filter /
+ * smoother entry points that take the linearisation transform (time loop as a launch loop); ssmq_filter_forward_multi_dev, the
+ * marginalised filter, the theta-step, the sigma-point entry points and ssmq_transform_update[_mo] return SSMQ_E_UNSUPPORTED.
+ */
+ssmq_transform *ssmq_transform_create_taylor_gpqd(int D, int E, double alpha, const double *ell);
+/* Where the following applications of a Taylor-GPQD handle (ssmq_apply_batch[_dev]) write model_var and integ_var of item b:
+ * d_model_var[b], d_integ_var[b] - device arrays of at least B doubles each that the caller keeps alive; either may be NULL
+ * (not written; the state of a new handle).  A filter pass does not need them. */
+int ssmq_taylor_gpqd_variance_planes(ssmq_transform *h, double *d_model_var, double *d_integ_var);
 /*
  * The multi-output BQ transform (SSMQ_FORM_BQ_MO; MultiOutputGaussianProcessTransform / MultiOutputStudentTProcessTransform,
  * bq/bqmtran.py:425-602): xi [D*N]; wm [E][N]; Wc [E][E][N][N], of which the blocks [i][j] with i >= j are read; Wcc [E][D][N];

@@ -467,6 +467,7 @@ int apply_dev_impl(ssmq_transform *h, const ssmq_integrand *f, int64_t B, int64_
     if (is_user_integrand(f)) {
         // a user-defined integrand: k_apply_small compiled for it at run time (ssmq_rtc.hip), nothing else
         if (h->form == SSMQ_FORM_TAYLOR1) return refuse_user_integrand("linearisation transform (k_linearize)");
+        if (is_taylor_gpqd(h)) return refuse_user_integrand("Taylor-GPQD transform (k_taylor_gpqd)");
         ApplyArgs a;
         memset(&a, 0, sizeof(a));
         if (!dry_run && B > 0) {
@@ -486,6 +487,17 @@ int apply_dev_impl(ssmq_transform *h, const ssmq_integrand *f, int64_t B, int64_
         fp.ttab = ttab;
         return launch_linearize(h->D, h->E, fi.din, f, fp, B, ld, d_mean, d_cov, d_time, d_time ? time_stride : 0, d_mean_f, d_cov_f,
                                 d_cov_fx, d_status, d_cov_add, cov_scale, ccov_scale, stream());
+    }
+    if (is_taylor_gpqd(h)) {
+        // the Taylor-GPQD transform (mtran.py:668-701): the same launch shape, the kernel parameters from the handle (ssmq_taylor_gpqd.hip)
+        if (kernel_name) *kernel_name = "k_taylor_gpqd";
+        if (dry_run || B <= 0) return SSMQ_OK;
+        if (null_args()) return SSMQ_E_ARG;
+        FPar fp;
+        fill_fpar(f, &fp);
+        fp.ttab = ttab;
+        return launch_taylor_gpqd(h, fi.din, f, fp, B, ld, d_mean, d_cov, d_time, d_time ? time_stride : 0, d_mean_f, d_cov_f, d_cov_fx,
+                                  d_status, d_cov_add, cov_scale, ccov_scale, stream());
     }
     const int tp = h->tp_nu > 0.0 ? 1 : 0;
     const int sel = sel_pattern(f, fi.din);
@@ -671,6 +683,46 @@ ssmq_transform *ssmq_transform_create_linear(int D, int E) {
     return h;
 }
 
+// The Taylor-GPQD transform likewise keeps the one-point placeholder block; its kernel parameters live in the handle and reach
+// the kernel by value.  `generation` carries a hash of them: a handle that a later allocation puts at the address of a destroyed
+// one must not find the launch loop captured for the old parameters (key_of_pair, ssmq_host.h).
+ssmq_transform *ssmq_transform_create_taylor_gpqd(int D, int E, double alpha, const double *ell) {
+    if (D < 1 || D > SSMQ_MAX_DIM || E < 1 || E > SSMQ_MAX_DIM || !ell || !std::isfinite(alpha)) {
+        set_error("transform_create_taylor_gpqd: bad argument (1 <= D, E <= 16, finite alpha, ell [D])");
+        return nullptr;
+    }
+    for (int d = 0; d < D; ++d)
+        if (!std::isfinite(ell[d]) || !(ell[d] > 0.0)) {
+            set_error("transform_create_taylor_gpqd: length-scales must be finite and positive (ell[" + std::to_string(d) + "])");
+            return nullptr;
+        }
+    ssmq_transform *h = ssmq_transform_create_linear(D, E);
+    if (!h) return nullptr;
+    h->form = SSMQ_FORM_TAYLOR_GPQD;
+    h->tg_alpha = alpha;
+    std::copy(ell, ell + D, h->tg_ell);
+    std::vector<uint64_t> words;
+    key_bytes(words, &alpha, sizeof(double));
+    key_bytes(words, ell, sizeof(double) * D);
+    uint64_t hash = 1469598103934665603ull;
+    for (uint64_t w : words) hash = (hash ^ w) * 1099511628211ull;
+    h->generation = (uint32_t)(hash ^ (hash >> 32));
+    return h;
+}
+
+int ssmq_taylor_gpqd_variance_planes(ssmq_transform *h, double *d_model_var, double *d_integ_var) {
+    SSMQ_HANDLE_LOCK(h);
+    if (!is_taylor_gpqd(h)) {
+        set_error("taylor_gpqd_variance_planes: not a Taylor-GPQD handle");
+        return SSMQ_E_ARG;
+    }
+    // (a captured launch loop holds the old pointers by value: a new generation is a new graph key)
+    h->generation += 1;
+    h->d_tg_mvar = d_model_var;
+    h->d_tg_ivar = d_integ_var;
+    return SSMQ_OK;
+}
+
 int ssmq_transform_update(ssmq_transform *h, const double *xi, const double *wm, const double *Wc, const double *Wcc,
                           const double *emv, int emv_mode, double tp_nu, const double *tp_iK) {
     SSMQ_HANDLE_LOCK(h);
@@ -679,6 +731,7 @@ int ssmq_transform_update(ssmq_transform *h, const double *xi, const double *wm,
         set_error("transform_update: the linearisation transform has no constants");
         return SSMQ_E_ARG;
     }
+    if (is_taylor_gpqd(h)) return refuse_taylor_gpqd("ssmq_transform_update (its kernel parameters are fixed at creation)");
     if (!h) return SSMQ_E_ARG;
     const int D = h->D, E = h->E, N = h->N;
     if (xi) h->xi.assign(xi, xi + D * N);

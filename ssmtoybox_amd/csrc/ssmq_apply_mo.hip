@@ -351,6 +351,7 @@ int ssmq_transform_update_mo(ssmq_transform *h, const double *xi, const double *
                              const double *emv, double tp_nu, const double *tp_iK) {
     SSMQ_HANDLE_LOCK(h);
     if (!h) return SSMQ_E_ARG;
+    if (is_taylor_gpqd(h)) return refuse_taylor_gpqd("ssmq_transform_update_mo");
     if (!is_mo(h)) {
         set_error("transform_update_mo: not a multi-output transform");
         return SSMQ_E_ARG;

@@ -36,6 +36,11 @@ struct ssmq_transform {
     // in packed order [i (i + 1) / 2 + j][N][N], Wcc [E][D][N], emv [E], iK [E][N][N]; d_mo is the one constant block (mo_layout),
     // d_small / d_wide stay null
     double *d_mo = nullptr;
+    // Taylor-GPQD form (SSMQ_FORM_TAYLOR_GPQD, ssmq_taylor_gpqd.hip): the RBF kernel's scale and length-scales, which travel to the
+    // kernel by value, and the two optional planes [B] the next applications write model_var / integ_var of every item to
+    // (ssmq_taylor_gpqd_variance_planes; null: not written)
+    double tg_alpha = 0.0, tg_ell[SSMQ_MAX_DIM] = {};
+    double *d_tg_mvar = nullptr, *d_tg_ivar = nullptr;
     uint32_t generation = 0;   // bumped by every upload of constants (create / update)
     // Threads (include/ssmq.h, conventions): every entry point that takes this handle holds `mu` for its duration; `owner` /
     // `owner_epoch` name the thread context (its stream) that used the handle last - another context waits for that stream
@@ -197,6 +202,9 @@ int apply_dev_impl(ssmq_transform *h, const ssmq_integrand *f, int64_t B, int64_
 // reductions alone (chol_in / fx_in); element e of trajectory b at ptr[e * es + b * bs]
 inline bool is_mo(const ssmq_transform *h) { return h && h->form == SSMQ_FORM_BQ_MO; }
 int refuse_mo(const char *what);   // sets the error text, returns SSMQ_E_UNSUPPORTED
+// the Taylor-GPQD form (ssmq_taylor_gpqd.hip): no points, no weights - every entry point that reads a handle's constants refuses it
+inline bool is_taylor_gpqd(const ssmq_transform *h) { return h && h->form == SSMQ_FORM_TAYLOR_GPQD; }
+int refuse_taylor_gpqd(const char *what);   // sets the error text, returns SSMQ_E_UNSUPPORTED
 enum { SSMQ_MO_FULL = 0, SSMQ_MO_POINTS = 1, SSMQ_MO_FX = 2 };
 struct MoArgs {
     int D, E, N, mode, fid, time_stride;
@@ -246,6 +254,11 @@ struct FPar;
 int launch_linearize(int D, int E, int din, const ssmq_integrand *f, const FPar &fp, int64_t B, int64_t ld, const double *d_mean,
                      const double *d_cov, const double *d_time, int time_stride, double *d_mean_f, double *d_cov_f, double *d_cov_fx,
                      int32_t *d_status, const double *d_cov_add, double cov_scale, double ccov_scale, hipStream_t s);
+// Taylor-GPQD transform (ssmq_taylor_gpqd.hip): the linearisation's moments calibrated by the RBF kernel in the handle
+int launch_taylor_gpqd(const ssmq_transform *h, int din, const ssmq_integrand *f, const FPar &fp, int64_t B, int64_t ld,
+                       const double *d_mean, const double *d_cov, const double *d_time, int time_stride, double *d_mean_f,
+                       double *d_cov_f, double *d_cov_fx, int32_t *d_status, const double *d_cov_add, double cov_scale,
+                       double ccov_scale, hipStream_t s);
 size_t bq_stream_parts_doubles(int E, int N, int64_t B, int cus);   // scratch for the panel-wise tail of a batch (0: no tail is cut)
 int launch_bq_stream(const WideArgs &a, const double *X, const double *emv, int emv_broadcast, int64_t B, const double *fx,
                      const double *chol, int64_t lda, int cus, double *parts, hipStream_t s);
@@ -434,9 +447,10 @@ inline void key_of_pair(std::vector<uint64_t> &key, const ssmq_transform *h_dyn,
 // The one place that fills the kernels' argument block from a pass: everything zero but the pass's fields, lpw = 64
 // (ssmq_filter_fused.hip).  A route states what it sets differently next to its launch.
 FusedArgs fused_args(const FilterPass &p);
-// both transforms of one form (sigma-point, BQ or t-process BQ), a measurement index pattern the kernels know, no state index list
+// both transforms of one form (sigma-point, BQ or t-process BQ), a measurement index pattern the kernels know, no state index list;
+// the Taylor-GPQD form is no family by name: no time-loop kernel (fused, strips, quad, wave split, time blocks) reads its parameters
 inline bool same_family(const FilterPass &p) {
-    return p.hd->form == p.ho->form && (p.hd->tp_nu > 0.0) == (p.ho->tp_nu > 0.0) && p.sel_obs >= 0 && p.fd->n_idx <= 0;
+    return !is_taylor_gpqd(p.hd) && !is_taylor_gpqd(p.ho) && p.hd->form == p.ho->form && (p.hd->tp_nu > 0.0) == (p.ho->tp_nu > 0.0) && p.sel_obs >= 0 && p.fd->n_idx <= 0;
 }
 // Integrands whose time dependence the fused loops read from a per-step table (time_table() in ssmq_device.h fills it); the kernels'
 // HasTimeTable<> (ssmq_fused.h) is checked against this function id by id in ssmq_filter_shapes.h.

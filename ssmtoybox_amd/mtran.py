@@ -18,7 +18,7 @@ from numpy.polynomial.hermite_e import hermegauss, hermeval
 
 from . import _lib
 from ._lib import FORM_SIGMA, EMV_DIAG
-from .ssmod import check_user_points, user_unsupported
+from .ssmod import check_user_points, is_user_model, user_unsupported
 
 
 class MomentTransform(metaclass=ABCMeta):
@@ -226,6 +226,143 @@ class LinearizationTransform(_DeviceApply, MomentTransform):
         if dev[0].id >= _lib.F_USER_FIRST:
             raise user_unsupported('the linearisation transform (model Jacobians)')
         return super().apply_batch(f, mean, cov, time=time, fcn_pars=fcn_pars, return_status=return_status)
+
+    def __del__(self):
+        try:
+            lib = _lib.load()
+            for h in self._dev.values():
+                lib.ssmq_transform_destroy(ctypes.c_void_p(h))
+            self._dev = {}
+        except Exception:
+            pass
+
+
+class TaylorGPQDTransform(_DeviceApply, MomentTransform):
+    """The linearisation transform read as Gaussian-process quadrature with derivative observations at one point and an RBF
+    kernel (mtran.py:668-701; the transform of ExtendedKalmanGPQD): `ker_par` (1, 1 + dim) = [alpha, ell_1 .. ell_dim],
+    Lam = diag(ell^2).  With f = f(mean) and J = f(mean, dx=True):
+
+        wm = det(Lam^-1 cov + I)^-1/2,  wc = det(2 Lam^-1 cov + I)^-1/2,  Wc = Lam/2 (Lam/2 + cov)^-1 cov,
+        mean_f = wm f,  cov_f = wc (f f' + J Wc J') - mean_f mean_f' + model_var,  cov_fx = J cov (Lam + cov)^-1 Lam
+
+    with model_var = alpha^2 - alpha^2 wc (1 + tr(Wc Lam^-1)) added to every entry of cov_f, as the reference adds it, and
+    integ_var = alpha^2 wc - wm^2.  For long length-scales it tends to `LinearizationTransform`.  One launch of `k_taylor_gpqd`
+    (csrc/ssmq_taylor_gpqd.hip) for a batch; `f` as for `LinearizationTransform`.
+
+    cov_fx is (E, D) as for every transform of this package - the reference returns the transpose (D, E), with which its own
+    measurement update fails unless dim_y == dim_state.  `mvar_list` / `ivar_list` get the model and
+    integral variance of every `apply()` call, as in the reference; `apply_batch(..., return_variances=True)` returns them per
+    item.  An item whose covariance is not positive semi-definite has status 1 and NaN moments (apply(): LinAlgError)."""
+
+    def __init__(self, dim, ker_par):
+        ker_par = np.asarray(ker_par, dtype=np.float64)
+        if ker_par.shape != (1, 1 + int(dim)):
+            raise ValueError('TaylorGPQDTransform: ker_par must have shape (1, 1 + dim) = (1, {}), got {}'.format(1 + int(dim), ker_par.shape))
+        if not np.all(np.isfinite(ker_par)) or np.any(ker_par[0, 1:] <= 0.0):
+            raise ValueError('TaylorGPQDTransform: kernel parameters must be finite and the length-scales positive')
+        self.dim = int(dim)
+        self.alpha = ker_par[0, 0]
+        self.ell = ker_par[0, 1:].copy()
+        self.Lam = np.diag(self.ell ** 2 * np.ones(self.dim))
+        self.iLam = np.diag(self.ell ** -2 * np.ones(self.dim))
+        self.eye_d = np.eye(self.dim)
+        # model variance and integral variance of every apply() call, as the reference logs them
+        self.mvar_list = []
+        self.ivar_list = []
+        self._dev = {}
+
+    def _handle_for(self, E):
+        h = self._dev.get(E)
+        if h is None:
+            ell, pe = _lib.as_c(self.ell)
+            h = _lib.load().ssmq_transform_create_taylor_gpqd(self.dim, int(E), float(self.alpha), pe)
+            if not h:
+                raise _lib.SsmqError('ssmq_transform_create_taylor_gpqd failed: ' + _lib.last_error())
+            self._dev[E] = h
+        return h
+
+    def _num_points(self):
+        return 0
+
+    @staticmethod
+    def _device_integrand(f):
+        """(Integrand, E) of a built-in model's dyn_eval / meas_eval; everything else is refused before the library is touched."""
+        if is_user_model(getattr(f, '__self__', None)):
+            raise user_unsupported('the Taylor-GPQD transform (model Jacobians)')
+        dev = resolve_integrand(f)
+        if dev is None:
+            raise NotImplementedError('TaylorGPQDTransform needs a built-in model (device integrand with a Jacobian)')
+        return dev
+
+    def kernel_name(self, f):
+        self._device_integrand(f)
+        return super().kernel_name(f)
+
+    def apply(self, f, mean, cov, fcn_pars, tf_pars=None):
+        mean = np.asarray(mean, dtype=np.float64)
+        cov = np.asarray(cov, dtype=np.float64)
+        t = np.atleast_1d(np.asarray(fcn_pars, dtype=np.float64)) if fcn_pars is not None else np.zeros(1)
+        mf, cf, cfx, mv, iv = self.apply_batch(f, mean[None, :], cov[None, :, :], t[:1], return_variances=True)
+        self.mvar_list.append(mv[0])
+        self.ivar_list.append(iv[0])
+        return mf[0], cf[0], cfx[0]
+
+    def apply_batch(self, f, mean, cov, time=0.0, fcn_pars=None, return_status=False, return_variances=False):
+        """B transforms in one launch: (mean_f (B, E), cov_f (B, E, E), cov_fx (B, E, D)[, status (B,)][, model_var (B,),
+        integ_var (B,)])."""
+        integ, E = self._device_integrand(f)
+        mean = np.ascontiguousarray(mean, dtype=np.float64)
+        cov = np.ascontiguousarray(cov, dtype=np.float64)
+        if mean.ndim != 2 or cov.shape != mean.shape + mean.shape[1:]:
+            raise ValueError('mean must have shape (B, D) and cov (B, D, D)')
+        B, D = mean.shape
+        if D != self.dim:
+            raise ValueError('mean has {} entries, the transform was made for dim = {}'.format(D, self.dim))
+        time = np.ascontiguousarray(np.asarray(time, dtype=np.float64).reshape(-1))
+        if time.size == B and B > 1:
+            stride = 1
+        else:
+            time, stride = (time[:1].copy() if time.size >= 1 else np.zeros(1)), 0
+        d_m, d_c = _lib.SoA.from_host(mean), _lib.SoA.from_host(cov)
+        d_t = _lib.DeviceBuffer(time.nbytes)
+        d_t.upload(time)
+        d_mf, d_cf, d_cfx = _lib.SoA(E, B), _lib.SoA(E * E, B), _lib.SoA(E * D, B)
+        ld = max(d_m.ld, 1)
+        d_st, d_mv, d_iv = _lib.DeviceBuffer(4 * ld), _lib.DeviceBuffer(8 * ld), _lib.DeviceBuffer(8 * ld)
+        try:
+            self.apply_batch_dev(f, d_m, d_c, d_t, d_mf, d_cf, d_cfx, d_st, time_stride=stride, model_var=d_mv, integ_var=d_iv)
+            _lib.sync()
+            mf, cf, cfx = d_mf.to_host(), d_cf.to_host((E, E)), d_cfx.to_host((E, D))
+            st = d_st.download((ld,), dtype=np.int32)[:B].copy()
+            mv, iv = d_mv.download((ld,))[:B].copy(), d_iv.download((ld,))[:B].copy()
+        finally:
+            for b in (d_m.buf, d_c.buf, d_t, d_mf.buf, d_cf.buf, d_cfx.buf, d_st, d_mv, d_iv):
+                b.free()
+        out = (mf, cf, cfx) + ((st,) if return_status else ()) + ((mv, iv) if return_variances else ())
+        if not return_status:
+            bad = np.flatnonzero(st)
+            if bad.size:
+                _raise_not_pd(int(bad[0]) + 1)
+        return out
+
+    def apply_batch_dev(self, f, mean, cov, time, mean_f, cov_f, cov_fx, status, time_stride=0, model_var=None, integ_var=None):
+        """Device-resident variant: `_lib.SoA` planes (time, status: DeviceBuffers); model_var / integ_var: optional DeviceBuffers
+        of mean.B doubles that receive the two variances of every item.  Asynchronous."""
+        integ, E = self._device_integrand(f)
+        lib = _lib.load()
+        h = ctypes.c_void_p(self._handle_for(E))
+        planes = model_var is not None or integ_var is not None
+        if planes:
+            _lib.check(lib.ssmq_taylor_gpqd_variance_planes(h, ctypes.c_void_p(model_var.ptr if model_var is not None else None),
+                                                            ctypes.c_void_p(integ_var.ptr if integ_var is not None else None)),
+                       'ssmq_taylor_gpqd_variance_planes')
+        try:
+            _lib.check(lib.ssmq_apply_batch_dev(h, ctypes.byref(integ), mean.B, mean.ld, mean.ptr, cov.ptr, ctypes.c_void_p(time.ptr),
+                                                time_stride, mean_f.ptr, cov_f.ptr, cov_fx.ptr, ctypes.c_void_p(status.ptr)),
+                       'ssmq_apply_batch_dev')
+        finally:
+            if planes:
+                lib.ssmq_taylor_gpqd_variance_planes(h, None, None)
 
     def __del__(self):
         try:

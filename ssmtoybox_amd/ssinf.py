@@ -20,7 +20,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from .mtran import (MomentTransform, LinearizationTransform, UnscentedTransform, SphericalRadialTransform, GaussHermiteTransform,
+from .mtran import (MomentTransform, LinearizationTransform, TaylorGPQDTransform, UnscentedTransform, SphericalRadialTransform, GaussHermiteTransform,
                     FullySymmetricStudentTransform, resolve_integrand)
 from .bq.bqmtran import (GaussianProcessTransform, BayesSardTransform, StudentTProcessTransform,
                          MultiOutputGaussianProcessTransform)
@@ -297,6 +297,9 @@ def run_filters(algs, data, x0_mean=None, x0_cov=None, raise_on_failure=True):
             raise NotImplementedError('run_filters: additive-noise Gaussian / Studentian filters only')
         if isinstance(a, MultiOutputGaussianProcessKalman):
             raise NotImplementedError('run_filters: not implemented for the multi-output filter (its forward pass is a launch loop)')
+        if isinstance(a, ExtendedKalmanGPQD):
+            raise NotImplementedError('run_filters: not implemented for ExtendedKalmanGPQD (its forward pass is a launch loop that '
+                                      'ssmq_filter_forward_multi_dev refuses by name)')
         if a.mod_obs.dim_out != Y:
             raise ValueError('run_filters: every filter must take the same measurements')
     d_y = _lib.scratch(8 * T * Y * ld)
@@ -370,6 +373,21 @@ class ExtendedKalman(GaussianInference):
         if is_user_model(dyn) or is_user_model(obs):
             raise user_unsupported('ExtendedKalman (model Jacobians)')
         super().__init__(dyn, obs, LinearizationTransform(dyn.dim_in), LinearizationTransform(obs.dim_in))
+
+
+class ExtendedKalmanGPQD(GaussianInference):
+    """Extended Kalman filter and smoother whose linearisations are calibrated by single-point Gaussian-process quadrature with
+    derivative observations and an RBF kernel (ssinf.py:1302-1319): rbf_par_dyn (1, 1 + dim_in), rbf_par_obs (1, 1 + dim_state) =
+    [alpha, ell_1 ..].  Runs where `ExtendedKalman` runs (the models with a Jacobian), on the same launch loop (k_taylor_gpqd |
+    k_taylor_gpqd | k_kalman_update per step); additive-noise built-in models only.  With this package's (E, D) cross-covariance it
+    also runs for dim_y != dim_state, where the reference's own filter stops."""
+
+    def __init__(self, dyn, obs, rbf_par_dyn, rbf_par_obs):
+        if is_user_model(dyn) or is_user_model(obs):
+            raise user_unsupported('ExtendedKalmanGPQD (model Jacobians)')
+        if not (dyn.noise_additive and obs.noise_additive):
+            raise NotImplementedError('ExtendedKalmanGPQD runs for additive-noise models only')
+        super().__init__(dyn, obs, TaylorGPQDTransform(dyn.dim_in, rbf_par_dyn), TaylorGPQDTransform(obs.dim_state, rbf_par_obs))
 
 
 class UnscentedKalman(GaussianInference):
