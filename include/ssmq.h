@@ -100,12 +100,27 @@ enum ssmq_integrand_id {
 #define SSMQ_USER_MAX_D 6
 #define SSMQ_USER_MAX_Y 4
 int ssmq_integrand_define(const char *body, int din, int dout, int uses_time, int32_t *id);
+/* The same with the model's Jacobian: `jac_body` is placed inside
+ *     __device__ void jac(const double *x, double *J, const int ldj) const { const double t = ..; const double *p = ..; { JAC_BODY } }
+ * and sets J[e * ldj + k] = d o_e / d x_k for the `din` inputs; all dout x din entries are zero on entry, so a sparse Jacobian
+ * writes its non-zeros only.  The same rules as `body`.  Idempotent on (body, jac_body, din, dout); the ids differ from the id
+ * ssmq_integrand_define gives the same body, and between two Jacobians of one body.  Pass uses_time != 0 if either body reads t.
+ * Such an id runs everywhere a user id runs and, in addition, on linearisation (ssmq_transform_create_linear) and Taylor-GPQD
+ * handles: ssmq_apply_batch[_dev] (k_linearize_fn / k_taylor_gpqd_fn, compiled for (id, D, E, din), D <= 6, E <= max(D, 4), no
+ * state index; ssmq_taylor_gpqd_variance_planes applies) and ssmq_filter_forward_dev with both handles of these forms (the
+ * launch loop; the other member may be a built-in integrand that has a Jacobian).  The Jacobian lands in the `din` leading
+ * columns of the E x D matrix, the other columns are zero - the broadcast of a one-column Jacobian into every column that the
+ * built-in pendulum measurement inherits from the reference is not applied to user integrands.  A user id without a Jacobian
+ * is SSMQ_E_UNSUPPORTED on these handles. */
+int ssmq_integrand_define_dx(const char *body, const char *jac_body, int din, int dout, int uses_time, int32_t *id);
 /* Compile only (no device needed): kind SSMQ_RTC_FILTER instantiates k_filter_fused<D, E (= Y), N, N_obs, id, id_obs, form, tp,
  * 0, opt> (id_obs: any integrand id), SSMQ_RTC_APPLY k_apply_small<D, E, N, id, form, tp, 0, opt> (id_obs, N_obs ignored), for
  * `arch` (e.g. "gfx950").  On success `log` gets the lowered kernel name on its first line, then the compiler's resource
  * remarks (registers, spills); on failure the compiler log.  Returns SSMQ_OK, SSMQ_E_ARG or SSMQ_E_UNSUPPORTED (compile error). */
 /* SSMQ_RTC_MC instantiates the streaming Monte-Carlo kernel k_mc_moments<id, D, E, 0> (N, N_obs, form, tp, opt ignored). */
-enum ssmq_rtc_kind { SSMQ_RTC_FILTER = 0, SSMQ_RTC_APPLY = 1, SSMQ_RTC_MC = 2 };
+/* SSMQ_RTC_LINEAR / SSMQ_RTC_TAYLOR_GPQD instantiate k_linearize_fn / k_taylor_gpqd_fn<id, D, E, din> for an id that has a
+ * Jacobian (N, N_obs, form, tp, opt ignored); an id without one is SSMQ_E_UNSUPPORTED. */
+enum ssmq_rtc_kind { SSMQ_RTC_FILTER = 0, SSMQ_RTC_APPLY = 1, SSMQ_RTC_MC = 2, SSMQ_RTC_LINEAR = 3, SSMQ_RTC_TAYLOR_GPQD = 4 };
 int ssmq_rtc_compile_check(int32_t id, int32_t id_obs, int kind, int D, int E, int N, int N_obs, int form, int tp, int opt,
                            const char *arch, char *log, int len);
 /* Process-wide counters of the run-time compiler: programs compiled, kernel lookups served from the cache, compile wall time. */

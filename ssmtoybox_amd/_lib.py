@@ -27,7 +27,7 @@ F_REENTRY2D_DYN, F_RADAR2D_MEAS, F_CT_DYN, F_BEARING_MEAS = 9, 10, 11, 12
 F_CTRS_DYN, F_CV_DYN, F_REENTRY2D_BIAS_DYN, F_SMOOTH10D_DYN = 13, 14, 15, 16
 # user-defined integrands, compiled for the device at run time (include/ssmq.h ssmq_integrand_define)
 F_USER_FIRST, F_USER_SLOTS, USER_BODY_MAX, USER_MAX_D, USER_MAX_Y = 1024, 64, 8192, 6, 4
-RTC_FILTER, RTC_APPLY, RTC_MC = 0, 1, 2
+RTC_FILTER, RTC_APPLY, RTC_MC, RTC_LINEAR, RTC_TAYLOR_GPQD = 0, 1, 2, 3, 4
 
 
 class SsmqError(RuntimeError):
@@ -268,6 +268,7 @@ _PROTOTYPES = {
     'ssmq_comm_barrier': (ctypes.c_int, []),
     'ssmq_comm_destroy': (ctypes.c_int, []),
     'ssmq_integrand_define': (ctypes.c_int, [ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_int32_p]),
+    'ssmq_integrand_define_dx': (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_int32_p]),
     'ssmq_rtc_compile_check': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                               ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_char_p,
                                               ctypes.c_char_p, ctypes.c_int]),
@@ -319,6 +320,15 @@ def define_integrand(body, din, dout, uses_time):
     fid = ctypes.c_int32()
     check(load().ssmq_integrand_define(body.encode('utf-8'), int(din), int(dout), 1 if uses_time else 0, ctypes.byref(fid)),
           'ssmq_integrand_define')
+    return fid.value
+
+
+def define_integrand_dx(body, jac_body, din, dout, uses_time):
+    """Register a user integrand's device function body together with its Jacobian body (include/ssmq.h
+    ssmq_integrand_define_dx): returns its id - another one than `define_integrand(body, ...)` returns."""
+    fid = ctypes.c_int32()
+    check(load().ssmq_integrand_define_dx(body.encode('utf-8'), jac_body.encode('utf-8'), int(din), int(dout), 1 if uses_time else 0,
+                                          ctypes.byref(fid)), 'ssmq_integrand_define_dx')
     return fid.value
 
 

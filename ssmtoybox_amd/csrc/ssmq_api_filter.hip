@@ -162,8 +162,27 @@ int filter_forward_impl(ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, ssmq
     wire_pass_consts(pass, cs, pc);
     pass.student_dof = student_dof;
     // A pair of models of which one or both are user-defined integrands: the whole-pass kernel compiled for them at run time
-    // (ssmq_rtc.hip), or an error - never the launch loop.
-    if (user) return (rc = rtc_launch_fused(pass)) < 0 ? rc : SSMQ_OK;
+    // (ssmq_rtc.hip), or an error - and the launch loop for the extended Kalman filters alone (both transforms a linearisation or
+    // Taylor-GPQD: no time-loop kernel reads a Jacobian), each transform of a user member a launch of the kernel compiled for it.
+    // Those kernels are compiled and loaded here, before the loop is captured, and a member without a Jacobian is refused here.
+    auto jac_form = [](const ssmq_transform *h) { return h->form == SSMQ_FORM_TAYLOR1 || is_taylor_gpqd(h); };
+    const bool user_ekf = user && jac_form(h_dyn) && jac_form(h_obs);
+    if (user && !user_ekf) return (rc = rtc_launch_fused(pass)) < 0 ? rc : SSMQ_OK;
+    if (user_ekf) {
+        const ssmq_transform *hs2[2] = {h_dyn, h_obs};
+        const ssmq_integrand *fs2[2] = {f_dyn, f_obs};
+        for (int i = 0; i < 2; ++i) {
+            FInfo fi;
+            if ((rc = check_integrand(hs2[i], fs2[i], &fi))) return rc;
+            if (is_user_integrand(fs2[i])) {
+                if ((rc = rtc_prepare_jacobian(hs2[i], fs2[i]))) return rc;
+            } else if (!integrand_has_jacobian(fs2[i]->id)) {
+                set_error("filter_forward: built-in integrand " + std::to_string(fs2[i]->id) + " has no Jacobian (its dyn_fcn_dx / meas_fcn_dx "
+                          "returns None in the reference too)");
+                return SSMQ_E_UNSUPPORTED;
+            }
+        }
+    }
     // workspace carve-up (doubles first, then the two int32 status planes)
     const size_t n_dbl = (size_t)ld * (D + 3 * D * D + Y + Y * Y + Y * D);
     const size_t need = sizeof(double) * n_dbl + 2 * sizeof(int32_t) * (size_t)ld;
@@ -187,7 +206,7 @@ int filter_forward_impl(ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, ssmq
     // one fused kernel for the whole time loop when this (models, shapes, form) combination has one (it does not keep
     // the predictive moments, so a pass that has to store them for the smoother takes the launch loop)
     const bool keep_pred = d_pm && d_pP && d_pC;
-    if (!ssmq::sw("SSMQ_NO_FUSED") && !keep_pred && !mo) {
+    if (!ssmq::sw("SSMQ_NO_FUSED") && !keep_pred && !mo && !user_ekf) {
         rc = try_launch_fused(pass);
         if (rc < 0) return rc;
         if (rc == 1) return SSMQ_OK;
@@ -534,7 +553,10 @@ extern "C" int ssmq_filter_kernel_name_batch(const ssmq_transform *h_dyn, const 
     query.name = &name; query.dry_run = true;
     const bool mo = is_mo(h_dyn) || is_mo(h_obs);       // no fused time loop takes the multi-output form
     if (mo && (is_user_integrand(f_dyn) || is_user_integrand(f_obs))) return refuse_user_integrand("multi-output transform (k_apply_mo)");
-    rc = mo || (ssmq::sw("SSMQ_NO_FUSED") && !is_user_integrand(f_dyn) && !is_user_integrand(f_obs)) ? 0 : try_launch_fused(query);
+    // (the extended Kalman filters of a user model run the launch loop: filter_forward_impl)
+    const bool ekf = (h_dyn->form == SSMQ_FORM_TAYLOR1 || is_taylor_gpqd(h_dyn)) && (h_obs->form == SSMQ_FORM_TAYLOR1 || is_taylor_gpqd(h_obs));
+    const bool user = is_user_integrand(f_dyn) || is_user_integrand(f_obs);
+    rc = mo || (user && ekf) || (ssmq::sw("SSMQ_NO_FUSED") && !user) ? 0 : try_launch_fused(query);
     if (rc < 0) return rc;
     snprintf(buf, len, "%s", rc == 1 ? name : "hipGraph of 3 T launches (apply dyn | apply obs | k_kalman_update)");
     return SSMQ_OK;

@@ -465,9 +465,23 @@ int apply_dev_impl(ssmq_transform *h, const ssmq_integrand *f, int64_t B, int64_
         fill_fpar(f, &a.fp);
     };
     if (is_user_integrand(f)) {
-        // a user-defined integrand: k_apply_small compiled for it at run time (ssmq_rtc.hip), nothing else
-        if (h->form == SSMQ_FORM_TAYLOR1) return refuse_user_integrand("linearisation transform (k_linearize)");
-        if (is_taylor_gpqd(h)) return refuse_user_integrand("Taylor-GPQD transform (k_taylor_gpqd)");
+        // a user-defined integrand: a kernel compiled for it at run time (ssmq_rtc.hip), nothing else - the two Jacobian forms
+        // for an integrand that was registered with its Jacobian (k_linearize_fn / k_taylor_gpqd_fn), k_apply_small otherwise
+        if (h->form == SSMQ_FORM_TAYLOR1 || is_taylor_gpqd(h)) {
+            const bool lin = h->form == SSMQ_FORM_TAYLOR1;
+            if (!user_integrand_has_jacobian(f->id))
+                return refuse_user_integrand(lin ? "linearisation transform (k_linearize)" : "Taylor-GPQD transform (k_taylor_gpqd)");
+            const bool dry = dry_run || B <= 0;
+            if (!dry && null_args()) return SSMQ_E_ARG;
+            FPar fp;
+            fill_fpar(f, &fp);      // (no time table: a user integrand evaluates its time dependence itself)
+            const int ts = d_time ? time_stride : 0;
+            if (lin)
+                return launch_linearize(h->D, h->E, fi.din, f, fp, B, ld, d_mean, d_cov, d_time, ts, d_mean_f, d_cov_f, d_cov_fx, d_status,
+                                        d_cov_add, cov_scale, ccov_scale, stream(), kernel_name, dry);
+            return launch_taylor_gpqd(h, fi.din, f, fp, B, ld, d_mean, d_cov, d_time, ts, d_mean_f, d_cov_f, d_cov_fx, d_status, d_cov_add,
+                                      cov_scale, ccov_scale, stream(), kernel_name, dry);
+        }
         ApplyArgs a;
         memset(&a, 0, sizeof(a));
         if (!dry_run && B > 0) {

@@ -253,12 +253,24 @@ void bq_stream_pack(int D, int N, const double *Wc, const double *Wcc, const dou
 struct FPar;
 int launch_linearize(int D, int E, int din, const ssmq_integrand *f, const FPar &fp, int64_t B, int64_t ld, const double *d_mean,
                      const double *d_cov, const double *d_time, int time_stride, double *d_mean_f, double *d_cov_f, double *d_cov_fx,
-                     int32_t *d_status, const double *d_cov_add, double cov_scale, double ccov_scale, hipStream_t s);
+                     int32_t *d_status, const double *d_cov_add, double cov_scale, double ccov_scale, hipStream_t s,
+                     const char **name = nullptr, bool dry_run = false);
 // Taylor-GPQD transform (ssmq_taylor_gpqd.hip): the linearisation's moments calibrated by the RBF kernel in the handle
 int launch_taylor_gpqd(const ssmq_transform *h, int din, const ssmq_integrand *f, const FPar &fp, int64_t B, int64_t ld,
                        const double *d_mean, const double *d_cov, const double *d_time, int time_stride, double *d_mean_f,
                        double *d_cov_f, double *d_cov_fx, int32_t *d_status, const double *d_cov_add, double cov_scale,
-                       double ccov_scale, hipStream_t s);
+                       double ccov_scale, hipStream_t s, const char **name = nullptr, bool dry_run = false);
+// ... both for a user integrand that was registered with a Jacobian (ssmq_integrand_define_dx): k_linearize_fn<> / k_taylor_gpqd_fn<>
+// compiled for the model and its shape at run time (ssmq_rtc.hip), launched with the argument block, grid and block of the two
+// launchers above, which hand a user integrand over.  SSMQ_OK (launched, or with dry_run the name set) or < 0; an integrand
+// without a Jacobian is SSMQ_E_UNSUPPORTED.  rtc_prepare_jacobian compiles and loads the kernel of (h, f) without launching it:
+// a stream that is being captured must not meet a compile or a module load.
+struct LinArgs;          // ssmq_linear_kernel.h
+struct TaylorGpqdArgs;   // ssmq_taylor_gpqd_kernel.h
+bool user_integrand_has_jacobian(int id);
+int rtc_launch_linearize(const ssmq_integrand *f, const LinArgs &a, hipStream_t s, const char **name, bool dry_run);
+int rtc_launch_taylor_gpqd(const ssmq_integrand *f, const TaylorGpqdArgs &a, hipStream_t s, const char **name, bool dry_run);
+int rtc_prepare_jacobian(const ssmq_transform *h, const ssmq_integrand *f);
 size_t bq_stream_parts_doubles(int E, int N, int64_t B, int cus);   // scratch for the panel-wise tail of a batch (0: no tail is cut)
 int launch_bq_stream(const WideArgs &a, const double *X, const double *emv, int emv_broadcast, int64_t B, const double *fx,
                      const double *chol, int64_t lda, int cus, double *parts, hipStream_t s);

@@ -9,18 +9,9 @@
 #include "ssmq_device.h"
 #include "ssmq_host.h"
 #include "ssmq_math.h"
+#include "ssmq_linear_kernel.h"   // LinArgs; the user models' kernel k_linearize_fn<> (run-time compiled)
 
 namespace ssmq {
-
-struct LinArgs {
-    int32_t D, E, din, fid, time_stride, bcast;      // bcast: no state index and din == 1 < D
-    const double *mean, *cov, *time, *cov_add;       // planes [D][ld], [D*D][ld]; time [B] or [1]; cov_add [E*E] or null
-    double *mean_f, *cov_f, *cov_fx;                 // planes [E][ld], [E*E][ld], [E*D][ld]
-    int32_t *status;
-    int64_t B, ld;
-    double cov_scale, ccov_scale;
-    FPar fp;
-};
 
 // DT, ET > 0: the transform's dimensions at compile time (everything in registers: the shapes of the seven models that have a
 // Jacobian); 0: run-time sizes, private arrays of the maximal size (scratch memory - a fallback, 0.13-0.21 of HBM where the
@@ -96,12 +87,14 @@ __global__ __launch_bounds__(256) void k_linearize(const LinArgs a) {
 // D, E: the transform's; din: the integrand's own input count (ssmq_api_transform.hip: check_integrand, FInfo)
 int launch_linearize(int D, int E, int din, const ssmq_integrand *f, const FPar &fp, int64_t B, int64_t ld, const double *d_mean,
                      const double *d_cov, const double *d_time, int time_stride, double *d_mean_f, double *d_cov_f, double *d_cov_fx,
-                     int32_t *d_status, const double *d_cov_add, double cov_scale, double ccov_scale, hipStream_t s) {
-    if (!integrand_has_jacobian(f->id)) {
+                     int32_t *d_status, const double *d_cov_add, double cov_scale, double ccov_scale, hipStream_t s, const char **name,
+                     bool dry_run) {
+    const bool user = is_user_integrand(f);      // its kernel is compiled for it (rtc_launch_linearize makes the checks of that route)
+    if (!user && !integrand_has_jacobian(f->id)) {
         set_error("linearisation: this model has no Jacobian (its dyn_fcn_dx / meas_fcn_dx returns None in the reference too)");
         return SSMQ_E_UNSUPPORTED;
     }
-    if (f->n_idx == 0 && din != D && din != 1) {
+    if (!user && f->n_idx == 0 && din != D && din != 1) {
         set_error("linearisation: a Jacobian of 1 < din < D columns without a state index has no placement (numpy raises there)");
         return SSMQ_E_UNSUPPORTED;
     }
@@ -110,6 +103,9 @@ int launch_linearize(int D, int E, int din, const ssmq_integrand *f, const FPar 
     a.mean = d_mean; a.cov = d_cov; a.time = d_time; a.cov_add = d_cov_add;
     a.mean_f = d_mean_f; a.cov_f = d_cov_f; a.cov_fx = d_cov_fx; a.status = d_status; a.B = B; a.ld = ld;
     a.cov_scale = cov_scale; a.ccov_scale = ccov_scale; a.fp = fp;
+    if (user) return rtc_launch_linearize(f, a, s, name, dry_run);
+    if (name) *name = "k_linearize";
+    if (dry_run) return SSMQ_OK;
     const dim3 grid((unsigned)((B + 255) / 256)), block(256);
     const bool generic = ssmq::sw("SSMQ_LINEAR_GENERIC") != nullptr;      // tools/alt_paths.sh: the run-time-size body for every shape
     if (generic) hipLaunchKernelGGL((k_linearize<0, 0>), grid, block, 0, s, a);

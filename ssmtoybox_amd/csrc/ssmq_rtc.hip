@@ -9,6 +9,9 @@
 // launched with the AOT launcher's grid, block and argument struct - the same code as a built-in model up to the functor.
 // The streaming Monte-Carlo transform runs a user integrand the same way: k_mc_moments<> (ssmq_mc_moments.h), one explicit
 // instantiation per (integrand id, D, E), launched with the arguments ssmq_mc_transform_dev made for the AOT route.
+// A body registered with its Jacobian (ssmq_integrand_define_dx) also runs the linearisation and the Taylor-GPQD transform: its
+// Fn<> has jac() next to eval(), and k_linearize_fn<> / k_taylor_gpqd_fn<> (ssmq_linear_kernel.h, ssmq_taylor_gpqd_kernel.h) are
+// instantiated per (integrand id, D, E, DIN) - the built-in models' kernels reach the model through a run-time switch instead.
 // Code objects are cached for the life of the process (key: the body hashes, kernel and template arguments, architecture) - failed
 // compiles too, with their message, so a broken body is compiled once - and modules per device.  Locks: the registry of bodies has
 // a mutex of its own (held for a lookup only); the cache mutex is held while a kernel is looked up, compiled or loaded, so a
@@ -28,6 +31,8 @@
 #include "ssmq_fused.h"
 #include "ssmq_filter_shapes.h"
 #include "ssmq_mc_moments.h"
+#include "ssmq_linear_kernel.h"
+#include "ssmq_taylor_gpqd_kernel.h"
 
 namespace ssmq {
 
@@ -45,7 +50,7 @@ static const char kRtcPrelude[] =
 namespace {
 
 struct UserFn {
-    std::string body;
+    std::string body, jac;                         // jac empty: registered without a Jacobian (ssmq_integrand_define)
     int din, dout;
     bool uses_time;
     uint64_t hash;
@@ -78,7 +83,14 @@ uint64_t fnv1a(const std::string &s, uint64_t h = 1469598103934665603ull) {
 // or line splices (a backslash before a line break joins two lines before comments are recognised: the end of a `//` comment, or a
 // `*` + `/`, would then lie elsewhere for the compiler than for this scan) - each could close the function the body is placed in
 // without a visible brace.  Empty string = accepted.
-std::string check_body(const char *body) {
+std::string check_body_text(const char *body);
+// ... `what` names the body in the message ("integrand body" / "Jacobian body")
+std::string check_body(const char *body, const char *what = "integrand body") {
+    std::string why = check_body_text(body);
+    if (!why.empty() && strcmp(what, "integrand body") != 0) why.replace(0, strlen("integrand body"), what);
+    return why;
+}
+std::string check_body_text(const char *body) {
     const size_t n = strlen(body);
     if (n == 0) return "integrand body is empty";
     if (n > SSMQ_USER_BODY_MAX) return "integrand body is longer than SSMQ_USER_BODY_MAX (" + std::to_string(SSMQ_USER_BODY_MAX) + ") characters";
@@ -131,13 +143,23 @@ std::string wrapper(int id, const UserFn &u) {
     std::string s;
     s += "namespace ssmq {\ntemplate <>\nstruct Fn<" + std::to_string(id) + "> {\n";
     s += "    static constexpr int DIN = " + std::to_string(u.din) + ";\n";
+    s += std::string("    static constexpr bool HAS_JAC = ") + (u.jac.empty() ? "false" : "true") + ";\n";
     s += "    double t_;\n    const FPar *fp_;\n";
     s += "    __device__ __forceinline__ void init(double t, const FPar &par) { t_ = t; fp_ = &par; }\n";
     s += "    template <int E>\n    __device__ __forceinline__ void eval(const double *x, double *o) const {\n";
     s += "        const double t = t_;\n        const double *p = fp_->p;\n        (void)t; (void)p; (void)x; (void)o;\n        {\n";
     s += "#line 1 \"user_integrand_" + std::to_string(id) + "\"\n";
     s += u.body;
-    s += "\n        }\n    }\n};\n}  // namespace ssmq\n";
+    s += "\n        }\n    }\n";
+    if (!u.jac.empty()) {
+        // J: dout x DIN entries at pitch ldj, all zero on entry
+        s += "    __device__ __forceinline__ void jac(const double *x, double *J, const int ldj) const {\n";
+        s += "        const double t = t_;\n        const double *p = fp_->p;\n        (void)t; (void)p; (void)x; (void)J; (void)ldj;\n        {\n";
+        s += "#line 1 \"user_jacobian_" + std::to_string(id) + "\"\n";
+        s += u.jac;
+        s += "\n        }\n    }\n";
+    }
+    s += "};\n}  // namespace ssmq\n";
     return s;
 }
 
@@ -182,8 +204,11 @@ int compile(const std::string &expr, const std::vector<int> &ids, const std::str
     std::string src = kRtcPrelude;
     src += kRtcHeaders;
     src += wrappers;
-    const char *arg_type = expr.find("k_filter_fused") != std::string::npos ? "ssmq::FusedArgs"
-                           : expr.find("k_mc_moments") != std::string::npos ? "ssmq::McMomArgs" : "ssmq::ApplyArgs";
+    const char *arg_type = expr.find("k_filter_fused") != std::string::npos    ? "ssmq::FusedArgs"
+                           : expr.find("k_mc_moments") != std::string::npos     ? "ssmq::McMomArgs"
+                           : expr.find("k_linearize_fn") != std::string::npos   ? "ssmq::LinArgs"
+                           : expr.find("k_taylor_gpqd_fn") != std::string::npos ? "ssmq::TaylorGpqdArgs"
+                                                                                : "ssmq::ApplyArgs";
     src += "template __global__ void " + expr + "(const " + arg_type + ");\n";
     const auto t0 = std::chrono::steady_clock::now();
     hiprtcProgram prog;
@@ -453,6 +478,79 @@ int rtc_launch_apply(const ssmq_transform *h, const ssmq_integrand *f, int sel, 
     return hip_fail(hipModuleLaunchKernel(fn, grid, 1, 1, kSmallBlock, 1, 1, 0, s, args, nullptr), "k_apply_small (run-time compiled)");
 }
 
+bool user_integrand_has_jacobian(int id) {
+    UserFn u;
+    return user_fn(id, &u) && !u.jac.empty();
+}
+
+// The two Jacobian kernels of a user integrand: the checks of the route and the instantiation k_<kernel>_fn<id, D, E, DIN>
+static int jac_expr(const char *kernel, const char *what, int D, int E, const ssmq_integrand *f, std::string *expr, std::vector<int> *ids) {
+    int rc = check_user_pair(f, f, ids);
+    if (rc) return rc;
+    UserFn u;
+    if (!user_fn(f->id, &u)) {
+        set_error("integrand id " + std::to_string(f->id) + " is not a registered user integrand");
+        return SSMQ_E_ARG;
+    }
+    if (u.jac.empty()) {
+        set_error(std::string(what) + ": this model has no Jacobian (a user integrand gets one through ssmq_integrand_define_dx)");
+        return SSMQ_E_UNSUPPORTED;
+    }
+    std::string why;
+    if (!shape_ok(D, E, 2, &why)) {      // (no points: the count is not part of the range)
+        set_error(std::string(what) + ": user integrands run for D <= " + std::to_string(SSMQ_USER_MAX_D) + " and outputs <= max(D, " +
+                  std::to_string(SSMQ_USER_MAX_Y) + ") (got D = " + std::to_string(D) + ", E = " + std::to_string(E) + ")");
+        return SSMQ_E_UNSUPPORTED;
+    }
+    if (u.dout != E || u.din > D) {
+        set_error(std::string(what) + ": the user integrand's input / output dimensions do not match the transform");
+        return SSMQ_E_ARG;
+    }
+    char b[160];
+    snprintf(b, sizeof(b), "ssmq::%s<%d, %d, %d, %d>", kernel, f->id, D, E, u.din);
+    *expr = b;
+    return SSMQ_OK;
+}
+template <class Args>
+static int launch_jac(const char *kernel, const char *what, const ssmq_integrand *f, const Args &a0, hipStream_t s, const char **name,
+                      bool dry_run) {
+    std::string expr;
+    std::vector<int> ids;
+    int rc = jac_expr(kernel, what, a0.D, a0.E, f, &expr, &ids);
+    if (rc) return rc;
+    if (name) {
+        std::lock_guard<std::mutex> lk(g_mu);
+        *name = stable_name(expr.substr(6) + " (run-time compiled)");
+    }
+    if (dry_run) return SSMQ_OK;
+    hipFunction_t fn;
+    if ((rc = kernel_for(expr, ids, &fn))) return rc;
+    Args a = a0;
+    a.fp.ttab = nullptr;
+    void *args[] = {&a};
+    const unsigned grid = (unsigned)((a.B + 255) / 256);      // as launch_linearize / launch_taylor_gpqd
+    return hip_fail(hipModuleLaunchKernel(fn, grid, 1, 1, 256, 1, 1, 0, s, args, nullptr), kernel);
+}
+int rtc_launch_linearize(const ssmq_integrand *f, const LinArgs &a, hipStream_t s, const char **name, bool dry_run) {
+    return launch_jac("k_linearize_fn", "linearisation", f, a, s, name, dry_run);
+}
+int rtc_launch_taylor_gpqd(const ssmq_integrand *f, const TaylorGpqdArgs &a, hipStream_t s, const char **name, bool dry_run) {
+    return launch_jac("k_taylor_gpqd_fn", "Taylor-GPQD", f, a, s, name, dry_run);
+}
+int rtc_prepare_jacobian(const ssmq_transform *h, const ssmq_integrand *f) {
+    const bool lin = h->form == SSMQ_FORM_TAYLOR1;
+    if (!lin && !is_taylor_gpqd(h)) {
+        set_error("rtc_prepare_jacobian: neither a linearisation nor a Taylor-GPQD handle");
+        return SSMQ_E_ARG;
+    }
+    std::string expr;
+    std::vector<int> ids;
+    int rc = jac_expr(lin ? "k_linearize_fn" : "k_taylor_gpqd_fn", lin ? "linearisation" : "Taylor-GPQD", h->D, h->E, f, &expr, &ids);
+    if (rc) return rc;
+    hipFunction_t fn;
+    return kernel_for(expr, ids, &fn);
+}
+
 // k_mc_moments<> for a user integrand (ssmq_mc_transform.hip has checked the range and filled `a0`): SSMQ_OK launched, or < 0
 int rtc_launch_mc(const ssmq_integrand *f, int D, int E, const McMomArgs &a0, unsigned grid, hipStream_t s) {
     char b[128];
@@ -470,42 +568,102 @@ int rtc_launch_mc(const ssmq_integrand *f, int D, int E, const McMomArgs &a0, un
 
 using namespace ssmq;
 
-extern "C" int ssmq_integrand_define(const char *body, int din, int dout, int uses_time, int32_t *id) {
+// jac: null for ssmq_integrand_define (an entry without a Jacobian), the Jacobian body for ssmq_integrand_define_dx.  An entry is
+// found again by (body, Jacobian body, din, dout): the same body with and without a Jacobian, or with two Jacobians, are
+// different integrands with different kernels.
+static int define_impl(const char *fn, const char *body, const char *jac, int din, int dout, int uses_time, int32_t *id) {
     if (!body || !id) {
-        set_error("ssmq_integrand_define: null argument");
+        set_error(std::string(fn) + ": null argument");
         return SSMQ_E_ARG;
     }
     if (din < 1 || din > SSMQ_MAX_DIM || dout < 1 || dout > SSMQ_MAX_DIM) {
-        set_error("ssmq_integrand_define: din and dout must be in 1 .. " + std::to_string(SSMQ_MAX_DIM));
+        set_error(std::string(fn) + ": din and dout must be in 1 .. " + std::to_string(SSMQ_MAX_DIM));
         return SSMQ_E_ARG;
     }
-    const std::string why = check_body(body);
+    std::string why = check_body(body);
+    if (why.empty() && jac) why = check_body(jac, "Jacobian body");
     if (!why.empty()) {
         set_error(why);
         return SSMQ_E_ARG;
     }
+    const std::string jb = jac ? jac : "";
     std::lock_guard<std::mutex> lk(g_reg_mu);
     for (size_t k = 0; k < g_user.size(); ++k) {
         UserFn &u = g_user[k];
-        if (u.body == body && u.din == din && u.dout == dout) {
+        if (u.body == body && u.jac == jb && u.din == din && u.dout == dout) {
             u.uses_time = u.uses_time || uses_time != 0;
             *id = SSMQ_F_USER_FIRST + (int32_t)k;
             return SSMQ_OK;
         }
     }
     if ((int)g_user.size() >= SSMQ_F_USER_SLOTS) {
-        set_error("ssmq_integrand_define: all " + std::to_string(SSMQ_F_USER_SLOTS) + " user integrand slots are taken");
+        set_error(std::string(fn) + ": all " + std::to_string(SSMQ_F_USER_SLOTS) + " user integrand slots are taken");
         return SSMQ_E_UNSUPPORTED;
     }
-    UserFn u{body, din, dout, uses_time != 0, 0};
+    UserFn u{body, jb, din, dout, uses_time != 0, 0};
     u.hash = fnv1a(u.body, fnv1a(std::to_string(din) + "," + std::to_string(dout)));
+    if (jac) u.hash = fnv1a(u.jac, fnv1a("|dx|", u.hash));
     g_user.push_back(u);
     *id = SSMQ_F_USER_FIRST + (int32_t)(g_user.size() - 1);
     return SSMQ_OK;
 }
 
+extern "C" int ssmq_integrand_define(const char *body, int din, int dout, int uses_time, int32_t *id) {
+    return define_impl("ssmq_integrand_define", body, nullptr, din, dout, uses_time, id);
+}
+
+extern "C" int ssmq_integrand_define_dx(const char *body, const char *jac_body, int din, int dout, int uses_time, int32_t *id) {
+    if (!jac_body) {
+        set_error("ssmq_integrand_define_dx: null argument");
+        return SSMQ_E_ARG;
+    }
+    return define_impl("ssmq_integrand_define_dx", body, jac_body, din, dout, uses_time, id);
+}
+
+// Compiles `expr` for `arch` with the resource remarks on and writes the text of a compile check to `log`
+static int compile_check_text(const std::string &expr, const std::vector<int> &ids, const char *arch, char *log, int len) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    Compiled *c = nullptr;
+    std::string lg;
+    const int rc = compile(expr, ids, arch, &c, &lg, true);
+    std::string text = lg;
+    if (rc == SSMQ_OK) {   // the lowered name, then the resource remarks alone ("VGPRs: 67", "ScratchSize [bytes/lane]: 0", ...)
+        text = c->lowered + "\n";
+        size_t pos = 0;
+        while (pos < lg.size()) {
+            size_t e = lg.find('\n', pos);
+            if (e == std::string::npos) e = lg.size();
+            const std::string ln = lg.substr(pos, e - pos);
+            const size_t r = ln.find("remark: ");
+            if (r != std::string::npos) text += ln.substr(r + 8, ln.find(" [-Rpass") - r - 8) + "\n";
+            pos = e + 1;
+        }
+    }
+    if (log && len > 0) {
+        const size_t n = std::min(text.size(), (size_t)len - 1);
+        memcpy(log, text.data(), n);
+        log[n] = '\0';
+    }
+    return rc;
+}
+
 extern "C" int ssmq_rtc_compile_check(int32_t id, int32_t id_obs, int kind, int D, int E, int N, int N_obs, int form, int tp, int opt,
                                       const char *arch, char *log, int len) {
+    if (kind == SSMQ_RTC_LINEAR || kind == SSMQ_RTC_TAYLOR_GPQD) {   // k_<kernel>_fn<id, D, E, DIN>: N, N_obs, form, tp and opt are not read
+        if (!arch || !*arch) {
+            set_error("ssmq_rtc_compile_check: bad argument");
+            return SSMQ_E_ARG;
+        }
+        const bool lin = kind == SSMQ_RTC_LINEAR;
+        ssmq_integrand f;
+        memset(&f, 0, sizeof(f));
+        f.id = id;
+        std::string expr;
+        std::vector<int> ids;
+        int rc = jac_expr(lin ? "k_linearize_fn" : "k_taylor_gpqd_fn", lin ? "linearisation" : "Taylor-GPQD", D, E, &f, &expr, &ids);
+        if (rc) return rc;
+        return compile_check_text(expr, ids, arch, log, len);
+    }
     if (kind == SSMQ_RTC_MC) {   // k_mc_moments<id, D, E, 0>: N, N_obs, form, tp and opt are not read
         FInfo fm;
         if (!arch || !*arch || !integrand_info(id, &fm)) {
@@ -541,29 +699,7 @@ extern "C" int ssmq_rtc_compile_check(int32_t id, int32_t id_obs, int kind, int 
     const std::string expr = kind == SSMQ_RTC_FILTER ? fused_expr(D, E, N, N_obs, id, id_obs, form, tp, 0, opt, -1)
                              : kind == SSMQ_RTC_MC   ? "ssmq::k_mc_moments<" + std::to_string(id) + ", " + std::to_string(D) + ", " + std::to_string(E) + ", 0>"
                                                      : apply_expr(D, E, N, id, form, tp, 0, opt, false);
-    std::lock_guard<std::mutex> lk(g_mu);
-    Compiled *c = nullptr;
-    std::string lg;
-    const int rc = compile(expr, ids, arch, &c, &lg, true);
-    std::string text = lg;
-    if (rc == SSMQ_OK) {   // the lowered name, then the resource remarks alone ("VGPRs: 67", "ScratchSize [bytes/lane]: 0", ...)
-        text = c->lowered + "\n";
-        size_t pos = 0;
-        while (pos < lg.size()) {
-            size_t e = lg.find('\n', pos);
-            if (e == std::string::npos) e = lg.size();
-            const std::string ln = lg.substr(pos, e - pos);
-            const size_t r = ln.find("remark: ");
-            if (r != std::string::npos) text += ln.substr(r + 8, ln.find(" [-Rpass") - r - 8) + "\n";
-            pos = e + 1;
-        }
-    }
-    if (log && len > 0) {
-        const size_t n = std::min(text.size(), (size_t)len - 1);
-        memcpy(log, text.data(), n);
-        log[n] = '\0';
-    }
-    return rc;
+    return compile_check_text(expr, ids, arch, log, len);
 }
 
 extern "C" int ssmq_rtc_stats(int64_t *compiles, int64_t *cache_hits, double *compile_seconds) {

@@ -15,66 +15,12 @@
 #include "ssmq_device.h"
 #include "ssmq_host.h"
 #include "ssmq_math.h"
+#include "ssmq_taylor_gpqd_kernel.h"   // TaylorGpqdArgs, chol_lower, chol_solve_vec; the user models' kernel k_taylor_gpqd_fn<>
 
 // (the run-time-size instantiation <0, 0> cannot unroll the triangular loops of the factorisation: no warning for that)
 #pragma clang diagnostic ignored "-Wpass-failed"
 
 namespace ssmq {
-
-struct TaylorGpqdArgs {
-    int32_t D, E, din, fid, time_stride, bcast;      // bcast: no state index and din == 1 < D
-    const double *mean, *cov, *time, *cov_add;       // planes [D][ld], [D*D][ld]; time [B] or [1]; cov_add [E*E] or null
-    double *mean_f, *cov_f, *cov_fx;                 // planes [E][ld], [E*E][ld], [E*D][ld]
-    double *model_var, *integ_var;                   // [B] each, or null
-    int32_t *status;
-    int64_t B, ld;
-    double cov_scale, ccov_scale, alpha;
-    double ell[SSMQ_MAX_DIM];
-    FPar fp;
-};
-
-// lower Cholesky factor of the n x n matrix A (row-major, pitch n; the lower triangle is read and overwritten), ri = 1 / diagonal;
-// returns the product of the diagonal of the factor (= sqrt(det A)), ok = every pivot positive
-__device__ __forceinline__ double chol_lower(double *A, double *ri, int n, bool &ok) {
-    double prod = 1.0;
-#pragma unroll
-    for (int j = 0; j < n; ++j) {
-        double ajj = A[j * n + j];
-#pragma unroll
-        for (int k = 0; k < j; ++k) ajj -= A[j * n + k] * A[j * n + k];
-        ok = ok && (ajj > 0.0);
-        double s, r;
-        sqrt_rsqrt(ajj, s, r);
-        A[j * n + j] = s;
-        ri[j] = r;
-        prod *= s;
-#pragma unroll
-        for (int i = j + 1; i < n; ++i) {
-            double v = A[i * n + j];
-#pragma unroll
-            for (int k = 0; k < j; ++k) v -= A[i * n + k] * A[j * n + k];
-            A[i * n + j] = v * r;
-        }
-    }
-    return prod;
-}
-// x <- (L L')^-1 x
-__device__ __forceinline__ void chol_solve_vec(const double *L, const double *ri, double *x, int n) {
-#pragma unroll
-    for (int i = 0; i < n; ++i) {
-        double v = x[i];
-#pragma unroll
-        for (int k = 0; k < i; ++k) v -= L[i * n + k] * x[k];
-        x[i] = v * ri[i];
-    }
-#pragma unroll
-    for (int i = n - 1; i >= 0; --i) {
-        double v = x[i];
-#pragma unroll
-        for (int k = i + 1; k < n; ++k) v -= L[k * n + i] * x[k];
-        x[i] = v * ri[i];
-    }
-}
 
 // DT, ET > 0: the transform's dimensions at compile time (everything in registers: the shapes of the models that have a
 // Jacobian); 0: run-time sizes, private arrays of the maximal size (scratch memory - the fallback, as k_linearize<0, 0>)
@@ -231,13 +177,14 @@ int refuse_taylor_gpqd(const char *what) {
 int launch_taylor_gpqd(const ssmq_transform *h, int din, const ssmq_integrand *f, const FPar &fp, int64_t B, int64_t ld,
                        const double *d_mean, const double *d_cov, const double *d_time, int time_stride, double *d_mean_f,
                        double *d_cov_f, double *d_cov_fx, int32_t *d_status, const double *d_cov_add, double cov_scale,
-                       double ccov_scale, hipStream_t s) {
+                       double ccov_scale, hipStream_t s, const char **name, bool dry_run) {
     const int D = h->D, E = h->E;
-    if (!integrand_has_jacobian(f->id)) {
+    const bool user = is_user_integrand(f);      // its kernel is compiled for it (rtc_launch_taylor_gpqd makes the checks of that route)
+    if (!user && !integrand_has_jacobian(f->id)) {
         set_error("Taylor-GPQD: this model has no Jacobian (its dyn_fcn_dx / meas_fcn_dx returns None in the reference too)");
         return SSMQ_E_UNSUPPORTED;
     }
-    if (f->n_idx == 0 && din != D && din != 1) {
+    if (!user && f->n_idx == 0 && din != D && din != 1) {
         set_error("Taylor-GPQD: a Jacobian of 1 < din < D columns without a state index has no placement (numpy raises there)");
         return SSMQ_E_UNSUPPORTED;
     }
@@ -249,6 +196,9 @@ int launch_taylor_gpqd(const ssmq_transform *h, int din, const ssmq_integrand *f
     a.cov_scale = cov_scale; a.ccov_scale = ccov_scale; a.alpha = h->tg_alpha;
     for (int d = 0; d < SSMQ_MAX_DIM; ++d) a.ell[d] = d < D ? h->tg_ell[d] : 1.0;
     a.fp = fp;
+    if (user) return rtc_launch_taylor_gpqd(f, a, s, name, dry_run);
+    if (name) *name = "k_taylor_gpqd";
+    if (dry_run) return SSMQ_OK;
     const dim3 grid((unsigned)((B + 255) / 256)), block(256);
     const bool generic = ssmq::sw("SSMQ_TAYLOR_GPQD_GENERIC") != nullptr;      // the run-time-size body for every shape (tests)
     if (generic) hipLaunchKernelGGL((k_taylor_gpqd<0, 0>), grid, block, 0, s, a);

@@ -18,7 +18,7 @@ from numpy.polynomial.hermite_e import hermegauss, hermeval
 
 from . import _lib
 from ._lib import FORM_SIGMA, EMV_DIAG
-from .ssmod import check_user_points, is_user_model, user_unsupported
+from .ssmod import check_user_points, has_device_jacobian, is_user_model, user_unsupported
 
 
 class MomentTransform(metaclass=ABCMeta):
@@ -201,7 +201,9 @@ class LinearizationTransform(_DeviceApply, MomentTransform):
     mean_f = f(mean), J = f(mean, dx=True), cov_fx = J cov, cov_f = cov_fx J' - one launch of `k_linearize`
     (csrc/ssmq_linear.hip) for a batch.  `f` must be the bound dyn_eval / meas_eval of a model whose Jacobian the reference
     implements (UNGM, UNGM with non-additive noise, pendulum, constant velocity: ssmod.py dyn_fcn_dx / meas_fcn_dx); for the
-    others the reference's Jacobian is None and its apply() raises - here `SsmqError` (SSMQ_E_UNSUPPORTED)."""
+    others the reference's Jacobian is None and its apply() raises - here `SsmqError` (SSMQ_E_UNSUPPORTED).  A model of your own
+    (`device_code`) runs if it also has a `device_jacobian`: `k_linearize_fn`, compiled for the model and its shape at run time
+    (dim <= 6), its Jacobian in the leading columns of the (E, dim) matrix."""
 
     def __init__(self, dim):
         self.dim = dim
@@ -223,8 +225,8 @@ class LinearizationTransform(_DeviceApply, MomentTransform):
         dev = resolve_integrand(f)
         if dev is None:
             raise NotImplementedError('LinearizationTransform needs a built-in model (device integrand with a Jacobian)')
-        if dev[0].id >= _lib.F_USER_FIRST:
-            raise user_unsupported('the linearisation transform (model Jacobians)')
+        if dev[0].id >= _lib.F_USER_FIRST and not has_device_jacobian(getattr(f, '__self__', None)):
+            raise user_unsupported('the linearisation transform (model Jacobians: give the model a device_jacobian)')
         return super().apply_batch(f, mean, cov, time=time, fcn_pars=fcn_pars, return_status=return_status)
 
     def __del__(self):
@@ -247,7 +249,8 @@ class TaylorGPQDTransform(_DeviceApply, MomentTransform):
 
     with model_var = alpha^2 - alpha^2 wc (1 + tr(Wc Lam^-1)) added to every entry of cov_f, as the reference adds it, and
     integ_var = alpha^2 wc - wm^2.  For long length-scales it tends to `LinearizationTransform`.  One launch of `k_taylor_gpqd`
-    (csrc/ssmq_taylor_gpqd.hip) for a batch; `f` as for `LinearizationTransform`.
+    (csrc/ssmq_taylor_gpqd.hip) for a batch; `f` as for `LinearizationTransform` (a user model with a `device_jacobian` runs
+    `k_taylor_gpqd_fn`, compiled for it at run time).
 
     cov_fx is (E, D) as for every transform of this package - the reference returns the transpose (D, E), with which its own
     measurement update fails unless dim_y == dim_state.  `mvar_list` / `ivar_list` get the model and
@@ -286,9 +289,11 @@ class TaylorGPQDTransform(_DeviceApply, MomentTransform):
 
     @staticmethod
     def _device_integrand(f):
-        """(Integrand, E) of a built-in model's dyn_eval / meas_eval; everything else is refused before the library is touched."""
-        if is_user_model(getattr(f, '__self__', None)):
-            raise user_unsupported('the Taylor-GPQD transform (model Jacobians)')
+        """(Integrand, E) of the dyn_eval / meas_eval of a built-in model or of a user model with a device_jacobian; everything else
+        is refused before the library is touched."""
+        owner = getattr(f, '__self__', None)
+        if is_user_model(owner) and not has_device_jacobian(owner):
+            raise user_unsupported('the Taylor-GPQD transform (model Jacobians: give the model a device_jacobian)')
         dev = resolve_integrand(f)
         if dev is None:
             raise NotImplementedError('TaylorGPQDTransform needs a built-in model (device integrand with a Jacobian)')

@@ -24,7 +24,7 @@ from .mtran import (MomentTransform, LinearizationTransform, TaylorGPQDTransform
                     FullySymmetricStudentTransform, resolve_integrand)
 from .bq.bqmtran import (GaussianProcessTransform, BayesSardTransform, StudentTProcessTransform,
                          MultiOutputGaussianProcessTransform)
-from .ssmod import TransitionModel, MeasurementModel, is_user_model, user_unsupported, check_user_points
+from .ssmod import TransitionModel, MeasurementModel, is_user_model, has_device_jacobian, user_unsupported, check_user_points
 
 
 class GaussianInference:
@@ -53,7 +53,8 @@ class GaussianInference:
         """Filters on user models (device_code) run the run-time compiled whole-pass kernel: 2 .. 2 D + 1 points per transform."""
         if is_user_model(self.mod_dyn) or is_user_model(self.mod_obs):
             for tf in (self.tf_dyn, self.tf_obs):
-                check_user_points(self.mod_dyn.dim_state, tf._num_points())
+                if tf._num_points():                  # (the linearisation and Taylor-GPQD transforms have no points)
+                    check_user_points(self.mod_dyn.dim_state, tf._num_points())
 
     @property
     def _additive(self):
@@ -365,13 +366,22 @@ class CubatureKalman(GaussianInference):
         super().__init__(dyn, obs, SphericalRadialTransform(dyn.dim_in), SphericalRadialTransform(obs.dim_in))
 
 
+def _need_device_jacobians(what, dyn, obs):
+    """The extended Kalman filters take a user model (device_code) that states its Jacobian (device_jacobian), no other."""
+    for m in (dyn, obs):
+        if is_user_model(m) and not has_device_jacobian(m):
+            raise user_unsupported('{} (model Jacobians: {} has no device_jacobian)'.format(what, type(m).__name__))
+
+
 class ExtendedKalman(GaussianInference):
     """Extended Kalman filter and smoother (ssinf.py:347-357): both transforms are linearisations around the mean.  Runs for
-    the models whose Jacobians the reference implements (its own test skips the others: tests/test_ssinf.py:96-101)."""
+    the models whose Jacobians the reference implements (its own test skips the others: tests/test_ssinf.py:96-101) and for
+    models of your own that have a `device_jacobian` next to their `device_code` (forward pass; a user model may be paired with
+    a built-in one): the launch loop k_linearize | k_linearize | k_kalman_update per step, a user member's transform being the
+    kernel compiled for it at run time (k_linearize_fn)."""
 
     def __init__(self, dyn, obs):
-        if is_user_model(dyn) or is_user_model(obs):
-            raise user_unsupported('ExtendedKalman (model Jacobians)')
+        _need_device_jacobians('ExtendedKalman', dyn, obs)
         super().__init__(dyn, obs, LinearizationTransform(dyn.dim_in), LinearizationTransform(obs.dim_in))
 
 
@@ -379,12 +389,12 @@ class ExtendedKalmanGPQD(GaussianInference):
     """Extended Kalman filter and smoother whose linearisations are calibrated by single-point Gaussian-process quadrature with
     derivative observations and an RBF kernel (ssinf.py:1302-1319): rbf_par_dyn (1, 1 + dim_in), rbf_par_obs (1, 1 + dim_state) =
     [alpha, ell_1 ..].  Runs where `ExtendedKalman` runs (the models with a Jacobian), on the same launch loop (k_taylor_gpqd |
-    k_taylor_gpqd | k_kalman_update per step); additive-noise built-in models only.  With this package's (E, D) cross-covariance it
+    k_taylor_gpqd | k_kalman_update per step); additive-noise models only, built-in ones and models of your own that have a
+    `device_jacobian` (their transforms run k_taylor_gpqd_fn, compiled at run time).  With this package's (E, D) cross-covariance it
     also runs for dim_y != dim_state, where the reference's own filter stops."""
 
     def __init__(self, dyn, obs, rbf_par_dyn, rbf_par_obs):
-        if is_user_model(dyn) or is_user_model(obs):
-            raise user_unsupported('ExtendedKalmanGPQD (model Jacobians)')
+        _need_device_jacobians('ExtendedKalmanGPQD', dyn, obs)
         if not (dyn.noise_additive and obs.noise_additive):
             raise NotImplementedError('ExtendedKalmanGPQD runs for additive-noise models only')
         super().__init__(dyn, obs, TaylorGPQDTransform(dyn.dim_in, rbf_par_dyn), TaylorGPQDTransform(obs.dim_state, rbf_par_obs))

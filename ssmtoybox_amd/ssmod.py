@@ -116,7 +116,9 @@ def is_user_model(model):
 
 _USER_SUPPORTED = ('user models (device_code) run in the additive-noise filters (forward_pass*, Gaussian and Studentian: UKF, CKF, '
                    'GHKF, GPQKF, BSQKF, TPQKF, FullySymmetricStudent, StudentProcessStudent) and the moment transforms, for '
-                   'dim_state <= {} and dim_out <= {}, without state_index'.format(_lib.USER_MAX_D, _lib.USER_MAX_Y))
+                   'dim_state <= {} and dim_out <= {}, without state_index; ExtendedKalman, ExtendedKalmanGPQD, '
+                   'LinearizationTransform and TaylorGPQDTransform run for a user model that also has a device_jacobian'
+                   .format(_lib.USER_MAX_D, _lib.USER_MAX_Y))
 
 
 def user_unsupported(what):
@@ -130,15 +132,49 @@ def check_user_points(D, N):
         raise user_unsupported('a point set of {} points at D = {} (2 .. 2 D + 1 = {})'.format(N, D, 2 * D + 1))
 
 
+def _check_device_jacobian(model):
+    """`device_jacobian` belongs to a `device_code`: ValueError for a model that has the first without the second."""
+    if getattr(model, 'device_jacobian', None) is not None and getattr(model, 'device_code', None) is None:
+        raise ValueError('{}: device_jacobian without device_code (the Jacobian body belongs to a device function body)'.format(
+            type(model).__name__))
+
+
+def has_device_jacobian(model):
+    """A user model (device_code) that also states its Jacobian as device code."""
+    return is_user_model(model) and getattr(model, 'device_jacobian', None) is not None
+
+
 def _user_integrand(model, din, dout):
-    """Register model.device_code once per (class, body) and return its integrand id."""
-    body = model.device_code
-    key = (type(model), body, din, dout)
+    """Register model.device_code (with model.device_jacobian, if it has one) once per (class, bodies) and return its integrand id."""
+    body, jac = model.device_code, model.device_jacobian
+    key = (type(model), body, jac, din, dout)
     fid = _USER_IDS.get(key)
     if fid is None:
-        fid = _lib.define_integrand(body, din, dout, re.search(r'\bt\b', body) is not None)
+        uses_time = any(re.search(r'\bt\b', b) is not None for b in (body, jac) if b is not None)
+        fid = _lib.define_integrand(body, din, dout, uses_time) if jac is None else _lib.define_integrand_dx(body, jac, din, dout, uses_time)
         _USER_IDS[key] = fid
     return fid
+
+
+def _check_jacobian(model, f, points, time, rel_step):
+    """max |device Jacobian - central differences of the device function| per point, both from the linearisation transform."""
+    from .mtran import LinearizationTransform
+    points = np.atleast_2d(np.asarray(points, dtype=np.float64))
+    B, D = points.shape
+    if D != model.dim_in:
+        raise ValueError('check_jacobian: points must have shape (B, {}), got {}'.format(model.dim_in, points.shape))
+    tf = LinearizationTransform(D)
+    eye = np.broadcast_to(np.eye(D), (B, D, D))
+    jac = tf.apply_batch(f, points, eye, time)[2]                       # cov = I: cov_fx = J, (B, E, D)
+    h = rel_step * np.maximum(1.0, np.abs(points))                      # (B, D)
+    shifted = np.repeat(points[:, None, :], 2 * D, axis=1)              # (B, 2 D, D): x + h e_k, then x - h e_k
+    for k in range(D):
+        shifted[:, k, k] += h[:, k]
+        shifted[:, D + k, k] -= h[:, k]
+    fx = tf.apply_batch(f, shifted.reshape(2 * B * D, D), np.broadcast_to(np.eye(D), (2 * B * D, D, D)), time)[0]
+    fx = fx.reshape(B, 2 * D, -1)
+    diff = (fx[:, :D] - fx[:, D:]) / (2.0 * h[:, :, None])              # (B, D, E)
+    return np.max(np.abs(jac - diff.transpose(0, 2, 1)), axis=(1, 2))
 
 
 def simulate_dev(dyn, obs, steps, mc_sims, seed=0, traj_offset=0, continuous_dt=None):
@@ -182,8 +218,13 @@ class TransitionModel:
     # A model of your own: the body of its device function as C++ (include/ssmq.h ssmq_integrand_define) - x the state
     # (dim_state inputs), o the dim_state outputs, t the time index, p the constants _par() returns.  Additive noise only.
     device_code = None
+    # ... and, optionally, the body of its Jacobian: x, t, p as above, J[e * ldj + k] = d o_e / d x_k (double *J, const int ldj),
+    # every entry zero on entry.  With it the model runs in ExtendedKalman, ExtendedKalmanGPQD and their two transforms.
+    # dyn_fcn_dx stays the optional NumPy twin.
+    device_jacobian = None
 
     def __init__(self, init_rv=None, noise_rv=None, noise_gain=None):
+        _check_device_jacobian(self)
         self.dim_in = self.dim_state if self.noise_additive else self.dim_state + self.dim_noise
         self.init_rv, self.noise_rv = init_rv, noise_rv
         self.zero_q = np.zeros(self.dim_noise)
@@ -194,6 +235,7 @@ class TransitionModel:
 
     def device_integrand(self):
         """(ssmq_integrand, dim_out) for the C ABI."""
+        _check_device_jacobian(self)
         if is_user_model(self):
             if not self.noise_additive:
                 raise user_unsupported('non-additive noise')
@@ -240,6 +282,13 @@ class TransitionModel:
     def dyn_fcn_dx(self, x, q, time):
         """Jacobian of the dynamics (ssmod.py:105-127): implemented by UNGM, UNGM-NA, pendulum and constant velocity only."""
         return None
+
+    def check_jacobian(self, points, time=0, rel_step=1e-5):
+        """A wrong Jacobian is the usual extended-Kalman bug: for `points` (B, dim_in) returns the (B,) largest absolute deviation
+        between the device Jacobian and central differences of the device function with step rel_step * max(1, |x_k|).  Both come
+        from `LinearizationTransform` (with cov = I its cov_fx is J, its mean_f the function value).  For a model with
+        `device_jacobian` and for the built-in models that have a Jacobian."""
+        return _check_jacobian(self, self.dyn_eval, points, time, rel_step)
 
 
 class UNGMTransition(TransitionModel):
@@ -430,7 +479,12 @@ class ConstantVelocity(TransitionModel):
 
 
 class MeasurementModel:
-    """y_k = h(x_k, r_k, k)   (ssmod.py:863-1039)."""
+    """y_k = h(x_k, r_k, k)   (ssmod.py:863-1039).
+
+    A model of your own states `device_code` and, for the extended Kalman filters, `device_jacobian` (below).  Its Jacobian fills
+    the leading columns of the (dim_out, dim_state) matrix - the inputs `device_code` reads - and the other columns are zero.  The
+    built-in `Pendulum2DMeasurement` repeats its one column in every state column, because the reference's `meas_eval` assigns
+    `out[:, None] = jac`; that is reference behaviour of that model only and is not extended to user models."""
     dim_in = None
     dim_out = None
     dim_noise = None
@@ -440,8 +494,15 @@ class MeasurementModel:
     # A model of your own: the body of its device function as C++ - x the leading dim_substate (else dim_state) state entries,
     # o the dim_out outputs, t the time index, p the constants _par() returns.  Additive noise, no state_index.
     device_code = None
+    # ... and, optionally, the body of its Jacobian: J[e * ldj + k] = d o_e / d x_k for the inputs device_code reads (double *J, const
+    # int ldj), every entry zero on entry.  It fills the leading columns of the (dim_out, dim_state) Jacobian, the others are zero:
+    # the broadcast of a one-column Jacobian into every state column that the built-in Pendulum2DMeasurement inherits from the
+    # reference's meas_eval (out[:, None] = jac) is that model's behaviour alone and is not applied to a user model.
+    # meas_fcn_dx stays the optional NumPy twin.
+    device_jacobian = None
 
     def __init__(self, noise_rv, dim_state, state_index=None):
+        _check_device_jacobian(self)
         self.noise_rv = noise_rv
         self.zero_r = np.zeros(self.dim_noise)
         self.state_index = state_index
@@ -452,6 +513,7 @@ class MeasurementModel:
         return ()
 
     def device_integrand(self):
+        _check_device_jacobian(self)
         if is_user_model(self):
             if not self.noise_additive:
                 raise user_unsupported('non-additive noise')
@@ -524,6 +586,12 @@ class MeasurementModel:
     def meas_fcn_dx(self, x, r, time):
         """Jacobian of the measurement function (ssmod.py:937-958): UNGM, UNGM-NA and pendulum only."""
         return None
+
+    def check_jacobian(self, points, time=0, rel_step=1e-5):
+        """As `TransitionModel.check_jacobian`, for `points` (B, dim_in): the (B,) largest absolute deviation between the device
+        Jacobian, placed into the (dim_out, dim_in) matrix as the transforms place it, and central differences of the device
+        function."""
+        return _check_jacobian(self, self.meas_eval, points, time, rel_step)
 
 
 class UNGMMeasurement(MeasurementModel):
