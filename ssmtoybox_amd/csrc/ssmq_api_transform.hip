@@ -6,6 +6,7 @@
 #include <vector>
 #include "ssmq_host.h"
 #include "ssmq_apply_small.h"
+#include "ssmq_jacobian_kernel.h"   // LinArgs
 
 namespace ssmq {
 
@@ -464,24 +465,27 @@ int apply_dev_impl(ssmq_transform *h, const ssmq_integrand *f, int64_t B, int64_
         a.cov_scale = cov_scale; a.ccov_scale = ccov_scale;
         fill_fpar(f, &a.fp);
     };
-    if (is_user_integrand(f)) {
-        // a user-defined integrand: a kernel compiled for it at run time (ssmq_rtc.hip), nothing else - the two Jacobian forms
-        // for an integrand that was registered with its Jacobian (k_linearize_fn / k_taylor_gpqd_fn), k_apply_small otherwise
-        if (h->form == SSMQ_FORM_TAYLOR1 || is_taylor_gpqd(h)) {
-            const bool lin = h->form == SSMQ_FORM_TAYLOR1;
-            if (!user_integrand_has_jacobian(f->id))
-                return refuse_user_integrand(lin ? "linearisation transform (k_linearize)" : "Taylor-GPQD transform (k_taylor_gpqd)");
-            const bool dry = dry_run || B <= 0;
-            if (!dry && null_args()) return SSMQ_E_ARG;
-            FPar fp;
-            fill_fpar(f, &fp);      // (no time table: a user integrand evaluates its time dependence itself)
-            const int ts = d_time ? time_stride : 0;
-            if (lin)
-                return launch_linearize(h->D, h->E, fi.din, f, fp, B, ld, d_mean, d_cov, d_time, ts, d_mean_f, d_cov_f, d_cov_fx, d_status,
-                                        d_cov_add, cov_scale, ccov_scale, stream(), kernel_name, dry);
-            return launch_taylor_gpqd(h, fi.din, f, fp, B, ld, d_mean, d_cov, d_time, ts, d_mean_f, d_cov_f, d_cov_fx, d_status, d_cov_add,
-                                      cov_scale, ccov_scale, stream(), kernel_name, dry);
+    if (h->form == SSMQ_FORM_TAYLOR1 || is_taylor_gpqd(h)) {
+        // the two Jacobian forms (mtran.py:49-59, 668-701): no points, no weights, one launch (ssmq_linear.hip) - for a user
+        // integrand, which must have been registered with its Jacobian, of a kernel compiled for it at run time
+        const bool user = is_user_integrand(f);
+        if (user && !user_integrand_has_jacobian(f->id))
+            return refuse_user_integrand(is_taylor_gpqd(h) ? "Taylor-GPQD transform (k_taylor_gpqd)" : "linearisation transform (k_linearize)");
+        const bool dry = dry_run || B <= 0;
+        LinArgs a;
+        memset(&a, 0, sizeof(a));
+        if (!dry) {
+            if (null_args()) return SSMQ_E_ARG;
+            a.mean = d_mean; a.cov = d_cov; a.time = d_time; a.time_stride = d_time ? time_stride : 0; a.cov_add = d_cov_add;
+            a.mean_f = d_mean_f; a.cov_f = d_cov_f; a.cov_fx = d_cov_fx; a.status = d_status; a.B = B; a.ld = ld;
+            a.cov_scale = cov_scale; a.ccov_scale = ccov_scale;
+            fill_fpar(f, &a.fp);
+            if (!user) a.fp.ttab = ttab;      // (a user integrand evaluates its time dependence itself)
         }
+        return launch_jacobian(h, fi.din, f, a, stream(), kernel_name, dry);
+    }
+    if (is_user_integrand(f)) {
+        // a user-defined integrand: k_apply_small compiled for it at run time (ssmq_rtc.hip), nothing else
         ApplyArgs a;
         memset(&a, 0, sizeof(a));
         if (!dry_run && B > 0) {
@@ -490,28 +494,6 @@ int apply_dev_impl(ssmq_transform *h, const ssmq_integrand *f, int64_t B, int64_
         }
         a.stream_out = stream_out ? 1 : 0;
         return rtc_launch_apply(h, f, sel_pattern(f, fi.din), a, stream(), kernel_name, dry_run || B <= 0);
-    }
-    if (h->form == SSMQ_FORM_TAYLOR1) {
-        // the linearisation transform (mtran.py:49-59): no points, no weights, one launch (ssmq_linear.hip)
-        if (kernel_name) *kernel_name = "k_linearize";
-        if (dry_run || B <= 0) return SSMQ_OK;
-        if (null_args()) return SSMQ_E_ARG;
-        FPar fp;
-        fill_fpar(f, &fp);
-        fp.ttab = ttab;
-        return launch_linearize(h->D, h->E, fi.din, f, fp, B, ld, d_mean, d_cov, d_time, d_time ? time_stride : 0, d_mean_f, d_cov_f,
-                                d_cov_fx, d_status, d_cov_add, cov_scale, ccov_scale, stream());
-    }
-    if (is_taylor_gpqd(h)) {
-        // the Taylor-GPQD transform (mtran.py:668-701): the same launch shape, the kernel parameters from the handle (ssmq_taylor_gpqd.hip)
-        if (kernel_name) *kernel_name = "k_taylor_gpqd";
-        if (dry_run || B <= 0) return SSMQ_OK;
-        if (null_args()) return SSMQ_E_ARG;
-        FPar fp;
-        fill_fpar(f, &fp);
-        fp.ttab = ttab;
-        return launch_taylor_gpqd(h, fi.din, f, fp, B, ld, d_mean, d_cov, d_time, d_time ? time_stride : 0, d_mean_f, d_cov_f, d_cov_fx,
-                                  d_status, d_cov_add, cov_scale, ccov_scale, stream());
     }
     const int tp = h->tp_nu > 0.0 ? 1 : 0;
     const int sel = sel_pattern(f, fi.din);

@@ -36,7 +36,7 @@ struct ssmq_transform {
     // in packed order [i (i + 1) / 2 + j][N][N], Wcc [E][D][N], emv [E], iK [E][N][N]; d_mo is the one constant block (mo_layout),
     // d_small / d_wide stay null
     double *d_mo = nullptr;
-    // Taylor-GPQD form (SSMQ_FORM_TAYLOR_GPQD, ssmq_taylor_gpqd.hip): the RBF kernel's scale and length-scales, which travel to the
+    // Taylor-GPQD form (SSMQ_FORM_TAYLOR_GPQD, ssmq_jacobian_kernel.h): the RBF kernel's scale and length-scales, which travel to the
     // kernel by value, and the two optional planes [B] the next applications write model_var / integ_var of every item to
     // (ssmq_taylor_gpqd_variance_planes; null: not written)
     double tg_alpha = 0.0, tg_ell[SSMQ_MAX_DIM] = {};
@@ -202,7 +202,7 @@ int apply_dev_impl(ssmq_transform *h, const ssmq_integrand *f, int64_t B, int64_
 // reductions alone (chol_in / fx_in); element e of trajectory b at ptr[e * es + b * bs]
 inline bool is_mo(const ssmq_transform *h) { return h && h->form == SSMQ_FORM_BQ_MO; }
 int refuse_mo(const char *what);   // sets the error text, returns SSMQ_E_UNSUPPORTED
-// the Taylor-GPQD form (ssmq_taylor_gpqd.hip): no points, no weights - every entry point that reads a handle's constants refuses it
+// the Taylor-GPQD form (ssmq_jacobian_kernel.h): no points, no weights - every entry point that reads a handle's constants refuses it
 inline bool is_taylor_gpqd(const ssmq_transform *h) { return h && h->form == SSMQ_FORM_TAYLOR_GPQD; }
 int refuse_taylor_gpqd(const char *what);   // sets the error text, returns SSMQ_E_UNSUPPORTED
 enum { SSMQ_MO_FULL = 0, SSMQ_MO_POINTS = 1, SSMQ_MO_FX = 2 };
@@ -249,27 +249,21 @@ bool bq_stream_supported(int D, int E, int N);
 int bq_stream_tpw(int E);          // trajectories per 64-row block of FX (fragment order, WideArgs::fx_frag)
 size_t bq_stream_x_doubles(int N);
 void bq_stream_pack(int D, int N, const double *Wc, const double *Wcc, const double *wm, double *X);
-// linearisation transform (ssmq_linear.hip): mean_f = f(mean), cov_fx = J cov, cov_f = cov_fx J' with the model's own Jacobian
-struct FPar;
-int launch_linearize(int D, int E, int din, const ssmq_integrand *f, const FPar &fp, int64_t B, int64_t ld, const double *d_mean,
-                     const double *d_cov, const double *d_time, int time_stride, double *d_mean_f, double *d_cov_f, double *d_cov_fx,
-                     int32_t *d_status, const double *d_cov_add, double cov_scale, double ccov_scale, hipStream_t s,
-                     const char **name = nullptr, bool dry_run = false);
-// Taylor-GPQD transform (ssmq_taylor_gpqd.hip): the linearisation's moments calibrated by the RBF kernel in the handle
-int launch_taylor_gpqd(const ssmq_transform *h, int din, const ssmq_integrand *f, const FPar &fp, int64_t B, int64_t ld,
-                       const double *d_mean, const double *d_cov, const double *d_time, int time_stride, double *d_mean_f,
-                       double *d_cov_f, double *d_cov_fx, int32_t *d_status, const double *d_cov_add, double cov_scale,
-                       double ccov_scale, hipStream_t s, const char **name = nullptr, bool dry_run = false);
-// ... both for a user integrand that was registered with a Jacobian (ssmq_integrand_define_dx): k_linearize_fn<> / k_taylor_gpqd_fn<>
-// compiled for the model and its shape at run time (ssmq_rtc.hip), launched with the argument block, grid and block of the two
-// launchers above, which hand a user integrand over.  SSMQ_OK (launched, or with dry_run the name set) or < 0; an integrand
-// without a Jacobian is SSMQ_E_UNSUPPORTED.  rtc_prepare_jacobian compiles and loads the kernel of (h, f) without launching it:
-// a stream that is being captured must not meet a compile or a module load.
-struct LinArgs;          // ssmq_linear_kernel.h
-struct TaylorGpqdArgs;   // ssmq_taylor_gpqd_kernel.h
+// linearisation transform (mean_f = f(mean), cov_fx = J cov, cov_f = cov_fx J' with the model's own Jacobian) and Taylor-GPQD
+// transform (its moments calibrated by the RBF kernel in the handle) - ssmq_jacobian_kernel.h; one launcher for both forms and
+// both kinds of model (ssmq_linear.hip): `planes` holds the planes, the time argument, B, ld and the hooks, the rest of the
+// argument block comes from the handle and the integrand.  A built-in model runs k_linearize<> / k_taylor_gpqd<>; a user
+// integrand that was registered with a Jacobian (ssmq_integrand_define_dx) is handed to rtc_launch_jacobian: k_linearize_fn<> /
+// k_taylor_gpqd_fn<> compiled for the model and its shape at run time (ssmq_rtc.hip), launched with the same argument block, grid
+// and block.  SSMQ_OK (launched, or with dry_run the name set) or < 0; an integrand without a Jacobian is SSMQ_E_UNSUPPORTED.
+// rtc_prepare_jacobian compiles and loads the kernel of (h, f) without launching it: a stream that is being captured must not
+// meet a compile or a module load.
+struct LinArgs;          // ssmq_jacobian_kernel.h
+struct TaylorGpqdArgs;
+int launch_jacobian(const ssmq_transform *h, int din, const ssmq_integrand *f, const LinArgs &planes, hipStream_t s,
+                    const char **name = nullptr, bool dry_run = false);
 bool user_integrand_has_jacobian(int id);
-int rtc_launch_linearize(const ssmq_integrand *f, const LinArgs &a, hipStream_t s, const char **name, bool dry_run);
-int rtc_launch_taylor_gpqd(const ssmq_integrand *f, const TaylorGpqdArgs &a, hipStream_t s, const char **name, bool dry_run);
+int rtc_launch_jacobian(int form, const ssmq_integrand *f, const TaylorGpqdArgs &a, hipStream_t s, const char **name, bool dry_run);
 int rtc_prepare_jacobian(const ssmq_transform *h, const ssmq_integrand *f);
 size_t bq_stream_parts_doubles(int E, int N, int64_t B, int cus);   // scratch for the panel-wise tail of a batch (0: no tail is cut)
 int launch_bq_stream(const WideArgs &a, const double *X, const double *emv, int emv_broadcast, int64_t B, const double *fx,

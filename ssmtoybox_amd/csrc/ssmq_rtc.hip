@@ -10,8 +10,8 @@
 // The streaming Monte-Carlo transform runs a user integrand the same way: k_mc_moments<> (ssmq_mc_moments.h), one explicit
 // instantiation per (integrand id, D, E), launched with the arguments ssmq_mc_transform_dev made for the AOT route.
 // A body registered with its Jacobian (ssmq_integrand_define_dx) also runs the linearisation and the Taylor-GPQD transform: its
-// Fn<> has jac() next to eval(), and k_linearize_fn<> / k_taylor_gpqd_fn<> (ssmq_linear_kernel.h, ssmq_taylor_gpqd_kernel.h) are
-// instantiated per (integrand id, D, E, DIN) - the built-in models' kernels reach the model through a run-time switch instead.
+// Fn<> has jac() next to eval(), and k_linearize_fn<> / k_taylor_gpqd_fn<> (ssmq_jacobian_kernel.h) are instantiated per
+// (integrand id, D, E, DIN) - the built-in models' kernels reach the model through a run-time switch instead.
 // Code objects are cached for the life of the process (key: the body hashes, kernel and template arguments, architecture) - failed
 // compiles too, with their message, so a broken body is compiled once - and modules per device.  Locks: the registry of bodies has
 // a mutex of its own (held for a lookup only); the cache mutex is held while a kernel is looked up, compiled or loaded, so a
@@ -31,8 +31,7 @@
 #include "ssmq_fused.h"
 #include "ssmq_filter_shapes.h"
 #include "ssmq_mc_moments.h"
-#include "ssmq_linear_kernel.h"
-#include "ssmq_taylor_gpqd_kernel.h"
+#include "ssmq_jacobian_kernel.h"
 
 namespace ssmq {
 
@@ -172,10 +171,11 @@ std::string first_lines(const std::string &log, int lines) {
     return pos == std::string::npos ? log : log.substr(0, pos);
 }
 
-// Compiles (or finds) the program that instantiates `expr` for the user integrands `ids`; g_mu held.  remarks: also ask the
-// compiler for its resource-usage remarks (compile check only; they do not change the code).
-int compile(const std::string &expr, const std::vector<int> &ids, const std::string &arch, Compiled **out, std::string *log,
-            bool remarks) {
+// Compiles (or finds) the program that instantiates the kernel `expr`, whose one parameter is a `const arg_type`, for the user
+// integrands `ids`; g_mu held.  remarks: also ask the compiler for its resource-usage remarks (compile check only; they do not
+// change the code).
+int compile(const std::string &expr, const char *arg_type, const std::vector<int> &ids, const std::string &arch, Compiled **out,
+            std::string *log, bool remarks) {
     std::string key = expr + "|" + arch;
     std::string wrappers;
     for (int id : ids) {
@@ -204,11 +204,6 @@ int compile(const std::string &expr, const std::vector<int> &ids, const std::str
     std::string src = kRtcPrelude;
     src += kRtcHeaders;
     src += wrappers;
-    const char *arg_type = expr.find("k_filter_fused") != std::string::npos    ? "ssmq::FusedArgs"
-                           : expr.find("k_mc_moments") != std::string::npos     ? "ssmq::McMomArgs"
-                           : expr.find("k_linearize_fn") != std::string::npos   ? "ssmq::LinArgs"
-                           : expr.find("k_taylor_gpqd_fn") != std::string::npos ? "ssmq::TaylorGpqdArgs"
-                                                                                : "ssmq::ApplyArgs";
     src += "template __global__ void " + expr + "(const " + arg_type + ");\n";
     const auto t0 = std::chrono::steady_clock::now();
     hiprtcProgram prog;
@@ -300,14 +295,14 @@ int function_of(Compiled *c, int dev, hipFunction_t *fn) {   // g_mu held
 }
 
 // The loaded kernel for `expr` on the current device: compiled, or found in the cache, under g_mu; the launch is the caller's.
-int kernel_for(const std::string &expr, const std::vector<int> &ids, hipFunction_t *fn) {
+int kernel_for(const std::string &expr, const char *arg_type, const std::vector<int> &ids, hipFunction_t *fn) {
     std::string arch;
     int dev = 0;
     int rc = device_arch(&arch, &dev);
     if (rc) return rc;
     std::lock_guard<std::mutex> lk(g_mu);
     Compiled *c = nullptr;
-    if ((rc = compile(expr, ids, arch, &c, nullptr, false))) return rc;
+    if ((rc = compile(expr, arg_type, ids, arch, &c, nullptr, false))) return rc;
     return function_of(c, dev, fn);
 }
 
@@ -315,6 +310,22 @@ const char *stable_name(const std::string &s) {   // g_mu held
     auto it = g_names.find(s);
     if (it == g_names.end()) it = g_names.emplace(s, s).first;
     return it->second.c_str();
+}
+
+// The tail of every launcher: the printable name, the dry run (SSMQ_OK, nothing compiled), the kernel, its launch with the one
+// argument block `arg`; `what` names the launch in an error
+int launch_compiled(const std::string &expr, const char *arg_type, const std::vector<int> &ids, void *arg, unsigned grid, unsigned block,
+                    hipStream_t s, const char **name, bool dry_run, const char *what) {
+    if (name) {
+        std::lock_guard<std::mutex> lk(g_mu);
+        *name = stable_name(expr.substr(6) + " (run-time compiled)");
+    }
+    if (dry_run) return SSMQ_OK;
+    hipFunction_t fn;
+    const int rc = kernel_for(expr, arg_type, ids, &fn);
+    if (rc) return rc;
+    void *args[] = {arg};
+    return hip_fail(hipModuleLaunchKernel(fn, grid, 1, 1, block, 1, 1, 0, s, args, nullptr), what);
 }
 
 std::string fused_expr(int D, int Y, int ND, int NO, int FD, int FO, int form, int tp, int selo, int opt, int stu) {
@@ -408,11 +419,11 @@ int rtc_launch_fused(const FilterPass &p) {
     const int stu = (p.sscale != nullptr && p.student_dof > 0.0) ? 1 : 0;
     // scalar state: recursion type fixed at compile time, as the AOT table does (SSMQ_FUSED_ONE_S)
     const std::string expr = fused_expr(D, Y, hd->N, ho->N, fd->id, fo->id, hd->form, tp, 0, opt, D == 1 && Y == 1 ? stu : -1);
-    if (p.name) {
-        std::lock_guard<std::mutex> lk(g_mu);
-        *p.name = stable_name(expr.substr(6) + " (run-time compiled)");
+    const char *what = "k_filter_fused (run-time compiled)";
+    if (p.dry_run) {
+        rc = launch_compiled(expr, "ssmq::FusedArgs", ids, nullptr, 0, kSmallBlock, p.s, p.name, true, what);
+        return rc ? rc : 1;
     }
-    if (p.dry_run) return 1;
     // A built-in member with a host time table (UNGM) is read through that table at every step of the loop, unconditionally: the
     // caller must have uploaded it (filter_forward_impl does, with the pass's constants).
     FusedArgs a = fused_args(p);
@@ -425,11 +436,7 @@ int rtc_launch_fused(const FilterPass &p) {
     }
     if (is_user_integrand(fd)) a.fd.ttab = nullptr;   // (user integrands evaluate their time dependence themselves)
     if (is_user_integrand(fo)) a.fo.ttab = nullptr;
-    hipFunction_t fn;
-    if ((rc = kernel_for(expr, ids, &fn))) return rc;
-    void *args[] = {&a};
-    const unsigned grid = (unsigned)((a.B + a.lpw - 1) / a.lpw);
-    rc = hip_fail(hipModuleLaunchKernel(fn, grid, 1, 1, kSmallBlock, 1, 1, 0, p.s, args, nullptr), "k_filter_fused (run-time compiled)");
+    rc = launch_compiled(expr, "ssmq::FusedArgs", ids, &a, (unsigned)((a.B + a.lpw - 1) / a.lpw), kSmallBlock, p.s, p.name, false, what);
     return rc ? rc : 1;
 }
 
@@ -464,18 +471,10 @@ int rtc_launch_apply(const ssmq_transform *h, const ssmq_integrand *f, int sel, 
     }
     const bool nts = opt != 0 && a0.stream_out;
     const std::string expr = apply_expr(h->D, h->E, h->N, f->id, h->form, tp, 0, opt, nts);
-    if (name) {
-        std::lock_guard<std::mutex> lk(g_mu);
-        *name = stable_name(expr.substr(6) + " (run-time compiled)");
-    }
-    if (dry_run) return SSMQ_OK;
-    hipFunction_t fn;
-    if ((rc = kernel_for(expr, ids, &fn))) return rc;
     ApplyArgs a = a0;
     a.fp.ttab = nullptr;
-    void *args[] = {&a};
-    const unsigned grid = (unsigned)((a.B + kSmallBlock - 1) / kSmallBlock);
-    return hip_fail(hipModuleLaunchKernel(fn, grid, 1, 1, kSmallBlock, 1, 1, 0, s, args, nullptr), "k_apply_small (run-time compiled)");
+    return launch_compiled(expr, "ssmq::ApplyArgs", ids, &a, (unsigned)((a.B + kSmallBlock - 1) / kSmallBlock), kSmallBlock, s, name, dry_run,
+                           "k_apply_small (run-time compiled)");
 }
 
 bool user_integrand_has_jacobian(int id) {
@@ -483,8 +482,17 @@ bool user_integrand_has_jacobian(int id) {
     return user_fn(id, &u) && !u.jac.empty();
 }
 
-// The two Jacobian kernels of a user integrand: the checks of the route and the instantiation k_<kernel>_fn<id, D, E, DIN>
-static int jac_expr(const char *kernel, const char *what, int D, int E, const ssmq_integrand *f, std::string *expr, std::vector<int> *ids) {
+// The two Jacobian kernels of a user integrand (form: SSMQ_FORM_TAYLOR1 or SSMQ_FORM_TAYLOR_GPQD): the checks of the route, the
+// instantiation k_<kernel>_fn<id, D, E, DIN> and the type of its argument block
+struct JacKernel {
+    const char *kernel, *what, *arg_type;
+};
+static JacKernel jac_kernel(int form) {
+    return form == SSMQ_FORM_TAYLOR1 ? JacKernel{"k_linearize_fn", "linearisation", "ssmq::LinArgs"}
+                                     : JacKernel{"k_taylor_gpqd_fn", "Taylor-GPQD", "ssmq::TaylorGpqdArgs"};
+}
+static int jac_expr(int form, int D, int E, const ssmq_integrand *f, std::string *expr, std::vector<int> *ids) {
+    const char *kernel = jac_kernel(form).kernel, *what = jac_kernel(form).what;
     int rc = check_user_pair(f, f, ids);
     if (rc) return rc;
     UserFn u;
@@ -511,57 +519,36 @@ static int jac_expr(const char *kernel, const char *what, int D, int E, const ss
     *expr = b;
     return SSMQ_OK;
 }
-template <class Args>
-static int launch_jac(const char *kernel, const char *what, const ssmq_integrand *f, const Args &a0, hipStream_t s, const char **name,
-                      bool dry_run) {
+int rtc_launch_jacobian(int form, const ssmq_integrand *f, const TaylorGpqdArgs &a0, hipStream_t s, const char **name, bool dry_run) {
     std::string expr;
     std::vector<int> ids;
-    int rc = jac_expr(kernel, what, a0.D, a0.E, f, &expr, &ids);
+    const int rc = jac_expr(form, a0.D, a0.E, f, &expr, &ids);
     if (rc) return rc;
-    if (name) {
-        std::lock_guard<std::mutex> lk(g_mu);
-        *name = stable_name(expr.substr(6) + " (run-time compiled)");
-    }
-    if (dry_run) return SSMQ_OK;
-    hipFunction_t fn;
-    if ((rc = kernel_for(expr, ids, &fn))) return rc;
-    Args a = a0;
+    TaylorGpqdArgs a = a0;      // (k_linearize_fn takes the LinArgs it begins with)
     a.fp.ttab = nullptr;
-    void *args[] = {&a};
-    const unsigned grid = (unsigned)((a.B + 255) / 256);      // as launch_linearize / launch_taylor_gpqd
-    return hip_fail(hipModuleLaunchKernel(fn, grid, 1, 1, 256, 1, 1, 0, s, args, nullptr), kernel);
-}
-int rtc_launch_linearize(const ssmq_integrand *f, const LinArgs &a, hipStream_t s, const char **name, bool dry_run) {
-    return launch_jac("k_linearize_fn", "linearisation", f, a, s, name, dry_run);
-}
-int rtc_launch_taylor_gpqd(const ssmq_integrand *f, const TaylorGpqdArgs &a, hipStream_t s, const char **name, bool dry_run) {
-    return launch_jac("k_taylor_gpqd_fn", "Taylor-GPQD", f, a, s, name, dry_run);
+    return launch_compiled(expr, jac_kernel(form).arg_type, ids, static_cast<LinArgs *>(&a), (unsigned)((a.B + 255) / 256), 256, s, name,
+                           dry_run, jac_kernel(form).kernel);      // grid and block as launch_jacobian
 }
 int rtc_prepare_jacobian(const ssmq_transform *h, const ssmq_integrand *f) {
-    const bool lin = h->form == SSMQ_FORM_TAYLOR1;
-    if (!lin && !is_taylor_gpqd(h)) {
+    if (h->form != SSMQ_FORM_TAYLOR1 && !is_taylor_gpqd(h)) {
         set_error("rtc_prepare_jacobian: neither a linearisation nor a Taylor-GPQD handle");
         return SSMQ_E_ARG;
     }
     std::string expr;
     std::vector<int> ids;
-    int rc = jac_expr(lin ? "k_linearize_fn" : "k_taylor_gpqd_fn", lin ? "linearisation" : "Taylor-GPQD", h->D, h->E, f, &expr, &ids);
+    const int rc = jac_expr(h->form, h->D, h->E, f, &expr, &ids);
     if (rc) return rc;
     hipFunction_t fn;
-    return kernel_for(expr, ids, &fn);
+    return kernel_for(expr, jac_kernel(h->form).arg_type, ids, &fn);
 }
 
 // k_mc_moments<> for a user integrand (ssmq_mc_transform.hip has checked the range and filled `a0`): SSMQ_OK launched, or < 0
 int rtc_launch_mc(const ssmq_integrand *f, int D, int E, const McMomArgs &a0, unsigned grid, hipStream_t s) {
     char b[128];
     snprintf(b, sizeof(b), "ssmq::k_mc_moments<%d, %d, %d, 0>", f->id, D, E);
-    hipFunction_t fn;
-    int rc = kernel_for(b, {f->id}, &fn);
-    if (rc) return rc;
     McMomArgs a = a0;
     a.fp.ttab = nullptr;
-    void *args[] = {&a};
-    return hip_fail(hipModuleLaunchKernel(fn, grid, 1, 1, kMcBlock, 1, 1, 0, s, args, nullptr), "k_mc_moments (run-time compiled)");
+    return launch_compiled(b, "ssmq::McMomArgs", {f->id}, &a, grid, kMcBlock, s, nullptr, false, "k_mc_moments (run-time compiled)");
 }
 
 }  // namespace ssmq
@@ -621,11 +608,12 @@ extern "C" int ssmq_integrand_define_dx(const char *body, const char *jac_body, 
 }
 
 // Compiles `expr` for `arch` with the resource remarks on and writes the text of a compile check to `log`
-static int compile_check_text(const std::string &expr, const std::vector<int> &ids, const char *arch, char *log, int len) {
+static int compile_check_text(const std::string &expr, const char *arg_type, const std::vector<int> &ids, const char *arch, char *log,
+                              int len) {
     std::lock_guard<std::mutex> lk(g_mu);
     Compiled *c = nullptr;
     std::string lg;
-    const int rc = compile(expr, ids, arch, &c, &lg, true);
+    const int rc = compile(expr, arg_type, ids, arch, &c, &lg, true);
     std::string text = lg;
     if (rc == SSMQ_OK) {   // the lowered name, then the resource remarks alone ("VGPRs: 67", "ScratchSize [bytes/lane]: 0", ...)
         text = c->lowered + "\n";
@@ -654,15 +642,15 @@ extern "C" int ssmq_rtc_compile_check(int32_t id, int32_t id_obs, int kind, int 
             set_error("ssmq_rtc_compile_check: bad argument");
             return SSMQ_E_ARG;
         }
-        const bool lin = kind == SSMQ_RTC_LINEAR;
+        const int jform = kind == SSMQ_RTC_LINEAR ? SSMQ_FORM_TAYLOR1 : SSMQ_FORM_TAYLOR_GPQD;
         ssmq_integrand f;
         memset(&f, 0, sizeof(f));
         f.id = id;
         std::string expr;
         std::vector<int> ids;
-        int rc = jac_expr(lin ? "k_linearize_fn" : "k_taylor_gpqd_fn", lin ? "linearisation" : "Taylor-GPQD", D, E, &f, &expr, &ids);
+        int rc = jac_expr(jform, D, E, &f, &expr, &ids);
         if (rc) return rc;
-        return compile_check_text(expr, ids, arch, log, len);
+        return compile_check_text(expr, jac_kernel(jform).arg_type, ids, arch, log, len);
     }
     if (kind == SSMQ_RTC_MC) {   // k_mc_moments<id, D, E, 0>: N, N_obs, form, tp and opt are not read
         FInfo fm;
@@ -699,7 +687,8 @@ extern "C" int ssmq_rtc_compile_check(int32_t id, int32_t id_obs, int kind, int 
     const std::string expr = kind == SSMQ_RTC_FILTER ? fused_expr(D, E, N, N_obs, id, id_obs, form, tp, 0, opt, -1)
                              : kind == SSMQ_RTC_MC   ? "ssmq::k_mc_moments<" + std::to_string(id) + ", " + std::to_string(D) + ", " + std::to_string(E) + ", 0>"
                                                      : apply_expr(D, E, N, id, form, tp, 0, opt, false);
-    return compile_check_text(expr, ids, arch, log, len);
+    return compile_check_text(expr, kind == SSMQ_RTC_FILTER ? "ssmq::FusedArgs" : kind == SSMQ_RTC_MC ? "ssmq::McMomArgs" : "ssmq::ApplyArgs", ids,
+                              arch, log, len);
 }
 
 extern "C" int ssmq_rtc_stats(int64_t *compiles, int64_t *cache_hits, double *compile_seconds) {

@@ -249,7 +249,7 @@ class TaylorGPQDTransform(_DeviceApply, MomentTransform):
 
     with model_var = alpha^2 - alpha^2 wc (1 + tr(Wc Lam^-1)) added to every entry of cov_f, as the reference adds it, and
     integ_var = alpha^2 wc - wm^2.  For long length-scales it tends to `LinearizationTransform`.  One launch of `k_taylor_gpqd`
-    (csrc/ssmq_taylor_gpqd.hip) for a batch; `f` as for `LinearizationTransform` (a user model with a `device_jacobian` runs
+    (csrc/ssmq_jacobian_kernel.h) for a batch; `f` as for `LinearizationTransform` (a user model with a `device_jacobian` runs
     `k_taylor_gpqd_fn`, compiled for it at run time).
 
     cov_fx is (E, D) as for every transform of this package - the reference returns the transpose (D, E), with which its own

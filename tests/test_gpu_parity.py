@@ -16,6 +16,7 @@ import pytest
 from oracle import ssmq_oracle as orc
 from tests._cases import MODELS, SIGMA_TF, BQ_TF, SENSORS, assert_moments_close, rel_err, RTOL, cov_err, mean_err, mean_err_sigma, within, capped
 from tests.golden.make_golden_cases import GP_CASES, BS_CASES, gp_par
+from tests._jacobian_cases import linear_models
 
 pytestmark = pytest.mark.gpu
 
@@ -3275,24 +3276,6 @@ def test_config4_tpq_ct_bearing_1e4(amd):
 # ---------------------------------------------------------------------------------------------------------------
 # linearisation transform and the extended Kalman filter (mtran.py:49-59, ssinf.py:347-357; golden g13)
 # ---------------------------------------------------------------------------------------------------------------
-def _linear_models():
-    from ssmtoybox_amd import ssmod as sm
-    dt = 0.01
-    q2 = sm.GaussRV(2, cov=0.01 * np.array([[(dt ** 3) / 3, (dt ** 2) / 2], [(dt ** 2) / 2, dt]]))
-    return {
-        'ungm_dyn': (sm.UNGMTransition(sm.GaussRV(1), sm.GaussRV(1, cov=np.array([[10.0]]))), 'dyn', orc.F_UNGM_DYN, (), None),
-        'ungmna_dyn': (sm.UNGMNATransition(sm.GaussRV(1), sm.GaussRV(1, cov=np.array([[10.0]]))), 'dyn', orc.F_UNGMNA_DYN, (), None),
-        'pend_dyn': (sm.Pendulum2DTransition(sm.GaussRV(2, mean=np.array([1.5, 0]), cov=0.01 * np.eye(2)), q2, dt=dt), 'dyn',
-                     orc.F_PENDULUM_DYN, (dt,), None),
-        'cv_dyn': (sm.ConstantVelocity(sm.GaussRV(4), sm.GaussRV(2), dt=0.5), 'dyn', orc.F_CV_DYN, (0.5,), None),
-        'ungm_meas': (sm.UNGMMeasurement(sm.GaussRV(1), 1), 'meas', orc.F_UNGM_MEAS, (), None),
-        'ungmna_meas': (sm.UNGMNAMeasurement(sm.GaussRV(1), 1), 'meas', orc.F_UNGMNA_MEAS, (), None),
-        'pend_meas': (sm.Pendulum2DMeasurement(sm.GaussRV(1, cov=np.array([[0.1]])), 2), 'meas', orc.F_PENDULUM_MEAS, (), None),
-        'pend_meas_idx': (sm.Pendulum2DMeasurement(sm.GaussRV(1, cov=np.array([[0.1]])), 2, state_index=[0]), 'meas',
-                          orc.F_PENDULUM_MEAS, (), [0]),
-    }
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize('tag', ['ungm_dyn', 'ungmna_dyn', 'pend_dyn', 'cv_dyn', 'ungm_meas', 'ungmna_meas', 'pend_meas', 'pend_meas_idx'])
 def test_linearization_transform_golden(amd, golden, tag):
@@ -3300,7 +3283,7 @@ def test_linearization_transform_golden(amd, golden, tag):
     input at a time, then one batch of 3000 inputs against the oracle; the host mirror of the model's Jacobian
     (dyn_eval / meas_eval with dx=True) against the oracle's."""
     g = golden('g13_linear')
-    mod, kind, fid, p, idx = _linear_models()[tag]
+    mod, kind, fid, p, idx = linear_models()[tag]
     f = mod.dyn_eval if kind == 'dyn' else mod.meas_eval
     D = mod.dim_in
     tf = amd.LinearizationTransform(D)

@@ -8,6 +8,7 @@ import pytest
 
 from tests._cases import assert_moments_close, rel_err, mean_err, cov_err, within
 from tests import _taylor_oracle as to
+from tests._jacobian_cases import package_models, index_cases
 
 pytestmark = pytest.mark.gpu
 
@@ -18,20 +19,6 @@ VAR_BAR = 1e-12
 @pytest.fixture(scope='module')
 def g21(golden):
     return golden('g21_taylor_gpqd')
-
-
-def package_models():
-    from ssmtoybox_amd import ssmod as sm
-    dt = 0.01
-    q2 = sm.GaussRV(2, cov=0.01 * np.array([[(dt ** 3) / 3, (dt ** 2) / 2], [(dt ** 2) / 2, dt]]))
-    return {
-        'ungm_dyn': sm.UNGMTransition(sm.GaussRV(1), sm.GaussRV(1, cov=np.array([[10.0]]))).dyn_eval,
-        'ungm_meas': sm.UNGMMeasurement(sm.GaussRV(1), 1).meas_eval,
-        'pend_dyn': sm.Pendulum2DTransition(sm.GaussRV(2, mean=np.array([1.5, 0]), cov=0.01 * np.eye(2)), q2, dt=dt).dyn_eval,
-        'pend_meas': sm.Pendulum2DMeasurement(sm.GaussRV(1, cov=np.array([[0.1]])), 2).meas_eval,
-        'cv_dyn': sm.ConstantVelocity(sm.GaussRV(4), sm.GaussRV(2), dt=0.5).dyn_eval,
-        'ungmna_dyn': sm.UNGMNATransition(sm.GaussRV(1), sm.GaussRV(1, cov=np.array([[10.0]]))).dyn_eval,
-    }
 
 
 _TF = {}
@@ -118,6 +105,67 @@ def test_plane_addressing_and_padding(g21, tag):
         assert np.all(p[:, B:] == sent), 'padding lanes untouched'
         assert np.array_equal(p[:, :B], p[:, idx]), 'item b is item b mod 8'
         assert np.array_equal(p[:, :n], f8), 'the batch of 8 through apply_batch'
+
+
+@pytest.mark.parametrize('tag', ['pend_meas_idx1', 'ungmna_meas_idx20'])
+def test_state_index_against_the_oracle(monkeypatch, tag):
+    """The model reached through a state index: inputs gathered by it, the Jacobian placed by it.  B = 193 at ld = 256 (four
+    blocks' worth of lanes in one, a ragged tail), inputs as g21's (cov = A A' + 0.2 I, ell in [0.5, 5], alpha 1 and 2.5), as
+    routed and through the run-time-size body, against tests/_taylor_oracle.taylor_gpqd with J placed by the index; the bars of
+    test_apply_batch_against_the_reference.  The padding lanes of every output plane keep their sentinel."""
+    import ssmtoybox_amd as amd
+    from ssmtoybox_amd import _lib
+    from oracle import ssmq_oracle as orc
+    mod, fid, D, idx = index_cases()[tag]
+    f, E = mod.meas_eval, 1
+    B, ld, sent = 193, 256, 7.25
+    rng = np.random.default_rng(22)
+    mean = rng.standard_normal((B, D))
+    a = rng.standard_normal((B, D, D))
+    cov = np.einsum('bij,bkj->bik', a, a) + 0.2 * np.eye(D)
+    d_m, d_c = _lib.SoA.from_host(mean, ld=ld), _lib.SoA.from_host(cov, ld=ld)
+    d_t = _lib.DeviceBuffer(8)
+    d_t.upload(np.zeros(1))
+    outs = [_lib.SoA(k, B, ld=ld) for k in (E, E * E, E * D)]
+    d_mv, d_iv, d_st = _lib.DeviceBuffer(8 * ld), _lib.DeviceBuffer(8 * ld), _lib.DeviceBuffer(4 * ld)
+    try:
+        for alpha in (1.0, 2.5):
+            ell = rng.uniform(0.5, 5.0, D)
+            tf = amd.TaylorGPQDTransform(D, np.hstack(([alpha], ell))[None, :])
+            assert tf.kernel_name(f) == 'k_taylor_gpqd'
+            ref = [np.zeros((B, E)), np.zeros((B, E, E)), np.zeros((B, E, D)), np.zeros(B), np.zeros(B)]
+            for i in range(B):
+                xs = mean[i][idx]
+                J = np.zeros((E, D))
+                J[:, idx] = orc.jacobian(fid, xs, 0.0)
+                for r, v in zip(ref, to.taylor_gpqd(np.atleast_1d(orc.integrand(fid, xs, 0.0)), J, cov[i], alpha, ell)):
+                    r[i] = v
+            for route in ('shape', 'generic'):
+                if route == 'generic':
+                    monkeypatch.setenv('SSMQ_TAYLOR_GPQD_GENERIC', '1')
+                else:
+                    monkeypatch.delenv('SSMQ_TAYLOR_GPQD_GENERIC', raising=False)
+                for o in outs:
+                    o.buf.upload(np.full(o.n * ld, sent))
+                d_mv.upload(np.full(ld, sent))
+                d_iv.upload(np.full(ld, sent))
+                d_st.upload(np.full(ld, 77, dtype=np.int32))
+                tf.apply_batch_dev(f, d_m, d_c, d_t, outs[0], outs[1], outs[2], d_st, time_stride=0, model_var=d_mv, integ_var=d_iv)
+                _lib.sync()
+                planes = [o.buf.download((o.n, ld)) for o in outs] + [d_mv.download((1, ld)), d_iv.download((1, ld))]
+                st = d_st.download((ld,), dtype=np.int32)
+                assert np.all(st[:B] == 0) and np.all(st[B:] == 77)
+                for p in planes:
+                    assert np.all(p[:, B:] == sent), 'padding lanes untouched'
+                mf, cf, cfx = planes[0][:, :B].T, planes[1][:, :B].T.reshape(B, E, E), planes[2][:, :B].T.reshape(B, E, D)
+                what = (tag, alpha, route)
+                e = assert_moments_close((mf, cf, cfx), ref[:3], cov, rtol=LINEAR_BAR, what=what)
+                print('{} alpha {} {}: {:.3g}'.format(tag, alpha, route, e))
+                var_close(planes[3][0, :B], ref[3], alpha, '{} model_var'.format(what))
+                var_close(planes[4][0, :B], ref[4], alpha, '{} integ_var'.format(what))
+    finally:
+        for buf in [d_m.buf, d_c.buf, d_t, d_mv, d_iv, d_st] + [o.buf for o in outs]:
+            buf.free()
 
 
 @pytest.mark.parametrize('tag', ['pend_dyn', 'cv_dyn'])

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""k_taylor_gpqd (TaylorGPQDTransform, csrc/ssmq_taylor_gpqd.hip) against k_linearize (LinearizationTransform) on device-resident
+"""k_taylor_gpqd (TaylorGPQDTransform, csrc/ssmq_jacobian_kernel.h) against k_linearize (LinearizationTransform) on device-resident
 planes: time per launch, the HBM rate on the algorithmic bytes 8 (D + D^2 + E + E^2 + E D) per trajectory and the ratio of the
 two, for the pendulum dynamics (D = E = 2) and the constant-velocity model (D = E = 4) at B = 1e6.
 

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""The run-time compiled Jacobian kernels of user models (k_linearize_fn / k_taylor_gpqd_fn, csrc/ssmq_linear_kernel.h and
-ssmq_taylor_gpqd_kernel.h) against the built-in kernels on device-resident planes, B = 1e6:
+"""The run-time compiled Jacobian kernels of user models (k_linearize_fn / k_taylor_gpqd_fn, csrc/ssmq_jacobian_kernel.h)
+against the built-in kernels on device-resident planes, B = 1e6:
 
   pendulum 2-D          the built-in model restated as device_code + device_jacobian against k_linearize<2, 2> / k_taylor_gpqd<2, 2>
   constant velocity 4-D restated likewise, against k_linearize<4, 4> / k_taylor_gpqd<4, 4> and against the run-time-size bodies
