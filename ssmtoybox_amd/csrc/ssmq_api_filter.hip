@@ -212,7 +212,13 @@ int filter_forward_impl(ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, ssmq
         if (rc == 1) return SSMQ_OK;
     }
     if (!ssmq::sw("SSMQ_NO_FUSED") && keep_pred && !sscale && student_dof == 0.0) {
-        // smoother: the time loop in one kernel that also leaves the predictive moments of every step in HBM
+        // smoother: the time loop in one kernel that also leaves the predictive moments of every step in HBM (the extended Kalman
+        // filter's k_ekf_loop, or the sigma-point / BQ kernel)
+        if (!mo && !user_ekf) {
+            rc = try_launch_ekf_loop(pass, d_pm, d_pP, d_pC);
+            if (rc < 0) return rc;
+            if (rc == 1) return SSMQ_OK;
+        }
         rc = try_launch_fused_aug(pass, AugExtras{D, 0, 0, gqg, rr, gqg, d_pm, d_pP, d_pC});    // (no noise inputs: the block is not read)
         if (rc < 0) return rc;
         if (rc == 1) return SSMQ_OK;

@@ -128,6 +128,7 @@ extern "C" int ssmq_filter_forward_multi_dev(int n_jobs, const ssmq_filter_job *
         if (j.scale) key_bytes(key, j.scale, sizeof(double) * j.T); else key.push_back(0);
     }
     key.push_back(ssmq::sw("SSMQ_NO_FUSED") ? 1 : 0);
+    key.push_back(ssmq::sw("SSMQ_NO_EKF_LOOP") ? 1 : 0);
     key.push_back(ssmq::sw("SSMQ_MULTI_NO_GRAPH") ? 1 : 0);
     key.push_back(ssmq::sw("SSMQ_MULTI_NO_FAMILY") ? 1 : 0);
     auto run_rest = [&]() -> int {       // the jobs that are not in the graph, through the ordinary path, one by one

@@ -430,6 +430,8 @@ int try_launch_fused(const FilterPass &p) {
         if (!p.dry_run) return refuse_user_integrand("fused filter launch");
         return rtc_launch_fused(p);
     }
+    // the extended Kalman filter of built-in models: its own time-loop kernel, none of the schedules below (ssmq_filter_ekf.hip)
+    if (const int re = try_launch_ekf_loop(p, nullptr, nullptr, nullptr)) return re;
     if (!same_family(p)) return 0;
     if (!p.dry_run || p.B > 0) {
         // batches whose waves would each sit alone on a SIMD: one trajectory on four lanes (ssmq_filter_quad.hip) ...

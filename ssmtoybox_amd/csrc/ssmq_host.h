@@ -489,6 +489,9 @@ struct AugExtras {
     double *pm, *pP, *pC;                     // all or none: predictive moments of every step, kept for the backward pass
 };
 int try_launch_fused_aug(const FilterPass &p, const AugExtras &x);
+// ... and for the extended Kalman filter of a pair of built-in models (both handles a linearisation; ssmq_filter_ekf.hip: k_ekf_loop),
+// which try_launch_fused asks first; pm / pP / pC (all or none): the predictive moments of every step are kept for the smoother
+int try_launch_ekf_loop(const FilterPass &p, double *pm, double *pP, double *pC);
 // ... several filters of one model family as one launch (ssmq_filter_fused.hip; ssmq_filter_forward_multi_dev)
 int multi_family_table(int n, const ssmq_transform *const *hd, const ssmq_integrand *const *fd, const ssmq_transform *const *ho,
                        const ssmq_integrand *const *fo, const FusedArgs *args, std::vector<char> *table, int *blocks);

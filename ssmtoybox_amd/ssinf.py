@@ -61,7 +61,8 @@ class GaussianInference:
         return self.mod_dyn.noise_additive and self.mod_obs.noise_additive
 
     def kernel_name(self, batch=0):
-        """Which kernel(s) the device filter loop runs for this filter (one fused kernel, or a replayed hipGraph) on a batch of
+        """Which kernel(s) the device filter loop runs for this filter (one fused kernel - k_filter_fused<..> and its schedules,
+        k_ekf_loop<D=..,Y=..> for ExtendedKalman on built-in models - or a replayed hipGraph of 3 T launches) on a batch of
         `batch` trajectories (0: a batch that fills the device; small batches of some systems run k_filter_wsplit)."""
         if not self._additive:
             return ('k_filter_fused_aug (one kernel for the time loop) where instantiated, else a launch loop of 5 T '
@@ -377,8 +378,10 @@ class ExtendedKalman(GaussianInference):
     """Extended Kalman filter and smoother (ssinf.py:347-357): both transforms are linearisations around the mean.  Runs for
     the models whose Jacobians the reference implements (its own test skips the others: tests/test_ssinf.py:96-101) and for
     models of your own that have a `device_jacobian` next to their `device_code` (forward pass; a user model may be paired with
-    a built-in one): the launch loop k_linearize | k_linearize | k_kalman_update per step, a user member's transform being the
-    kernel compiled for it at run time (k_linearize_fn)."""
+    a built-in one).  On a pair of built-in additive-noise models the whole time loop is one kernel (k_ekf_loop: forward pass,
+    smoother, and as a member of `run_filters`; SSMQ_NO_EKF_LOOP=1 or SSMQ_NO_FUSED=1 switch it off).  Everything else - a pair with a
+    user member, models that take their noise as an argument - runs the launch loop k_linearize | k_linearize | k_kalman_update per
+    step, a user member's transform being the kernel compiled for it at run time (k_linearize_fn)."""
 
     def __init__(self, dyn, obs):
         _need_device_jacobians('ExtendedKalman', dyn, obs)
