@@ -146,10 +146,13 @@ enum ssmq_form {
     SSMQ_FORM_BQ_MO = 3, /* multi-output BQ (bq/bqmtran.py:425-602): one weight set per output and output pair -
                             mean_i = fx_i wm_i; cov_ij = fx_i Wc_ij fx_j' - mean_i mean_j + delta_ij emv_i; ccov_i = fx_i Wcc_i' L'.
                             Handles of this form come from ssmq_transform_create_mo only */
-    SSMQ_FORM_TAYLOR_GPQD = 4 /* mtran.py:668-701 (TaylorGPQDTransform): the linearisation read as single-point GP quadrature with
+    SSMQ_FORM_TAYLOR_GPQD = 4, /* mtran.py:668-701 (TaylorGPQDTransform): the linearisation read as single-point GP quadrature with
                             derivative observations and an RBF kernel - mean = wm f(m); cov = wc (f f' + J Wc J') - mean mean' +
                             model_var; ccov = J cov (Lam + cov)^-1 Lam.  Handles of this form come from
                             ssmq_transform_create_taylor_gpqd only */
+    SSMQ_FORM_TRUNC_SIGMA = 5 /* mtran.py:588-658 (TruncatedSigmaPointTransform): mean and cov from a sigma-point rule of the effective
+                            dimension on the leading block of the input moments, ccov from the rule of the full dimension.  Handles
+                            of this form come from ssmq_transform_create_truncated only */
 };
 
 /* How the expected model variance enters the covariance (bq/bqmtran.py:198 `model_var * I_out`). */
@@ -418,6 +421,25 @@ ssmq_transform *ssmq_transform_create_taylor_gpqd(int D, int E, double alpha, co
  * d_model_var[b], d_integ_var[b] - device arrays of at least B doubles each that the caller keeps alive; either may be NULL
  * (not written; the state of a new handle).  A filter pass does not need them. */
 int ssmq_taylor_gpqd_variance_planes(ssmq_transform *h, double *d_model_var, double *d_integ_var);
+/*
+ * The truncated sigma-point transform (SSMQ_FORM_TRUNC_SIGMA; mtran.py:588-658, the measurement transform of the Truncated*Kalman
+ * filters, ssinf.py:844-901) for an integrand that reads the D_eff leading of its D inputs: xi_eff [D_eff*N_eff], wm [N_eff],
+ * wc [N_eff] - points (element d of point n at xi_eff[d * N_eff + n], as xi of ssmq_transform_create) and mean / covariance weights
+ * of the rule of the effective dimension; xi [D*N], wcc [N] - points and cross-covariance weights of the rule of the full dimension.
+ * With L = chol(cov) (lower; its leading D_eff x D_eff block L_e is the factor of the leading block of cov), m_e = mean[:D_eff]:
+ *   x_eff_i = m_e + L_e xi_eff_i,  x_j = mean + L xi_j,
+ *   mean_f = sum_i wm_i f(x_eff_i),  cov_f = sum_i wc_i (f(x_eff_i) - mean_f)(..)',  cov_fx = sum_j wcc_j (f(x_j) - mean_f)(x_j - mean)'.
+ * mean_f and cov_f are functions of mean[:D_eff] and cov[:D_eff, :D_eff] alone, bit for bit.  One launch of k_apply_trunc per
+ * batch; an item whose cov is not positive definite has status 1 and NaN outputs.  1 <= D_eff <= D <= 6, 1 <= E <= 4,
+ * 1 <= N_eff, N <= 729, finite constants (else NULL, ssmq_last_error() names the range).  Built-in integrands that read at most
+ * D_eff inputs, every state-index entry < D_eff (else SSMQ_E_UNSUPPORTED at apply time).  The handle runs through
+ * ssmq_apply_batch[_dev], ssmq_apply_kernel_name and, as the MEASUREMENT handle next to an SSMQ_FORM_SIGMA dynamics handle, through
+ * ssmq_filter_forward_dev, ssmq_filter_smooth_dev and ssmq_filter_kernel_name[_batch] (the launch loop apply dyn | k_apply_trunc |
+ * k_kalman_update); every other entry point that takes a transform handle - and these as the dynamics handle - returns
+ * SSMQ_E_UNSUPPORTED for it before it writes to an output.  There is no update: recreate the handle when its constants change.
+ */
+ssmq_transform *ssmq_transform_create_truncated(int D, int D_eff, int E, int N_eff, const double *xi_eff, const double *wm,
+                                                const double *wc, int N, const double *xi, const double *wcc);
 /*
  * The multi-output BQ transform (SSMQ_FORM_BQ_MO; MultiOutputGaussianProcessTransform / MultiOutputStudentTProcessTransform,
  * bq/bqmtran.py:425-602): xi [D*N]; wm [E][N]; Wc [E][E][N][N], of which the blocks [i][j] with i >= j are read; Wcc [E][D][N];

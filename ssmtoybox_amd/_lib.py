@@ -18,6 +18,7 @@ SSMQ_MAX_FIDX = 16
 FORM_BQ, FORM_SIGMA = 0, 1
 FORM_BQ_MO = 3
 FORM_TAYLOR_GPQD = 4
+FORM_TRUNC_SIGMA = 5
 EMV_DIAG, EMV_BROADCAST = 0, 1
 
 # integrand ids (include/ssmq.h enum ssmq_integrand_id)
@@ -110,6 +111,8 @@ _PROTOTYPES = {
     'ssmq_transform_create_linear': (ctypes.c_void_p, [ctypes.c_int, ctypes.c_int]),
     'ssmq_transform_create_taylor_gpqd': (ctypes.c_void_p, [ctypes.c_int, ctypes.c_int, ctypes.c_double, c_double_p]),
     'ssmq_taylor_gpqd_variance_planes': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    'ssmq_transform_create_truncated': (ctypes.c_void_p, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_double_p, c_double_p,
+                                                          c_double_p, ctypes.c_int, c_double_p, c_double_p]),
     'ssmq_transform_create_mo': (ctypes.c_void_p, [ctypes.c_int] * 3 + [c_double_p] * 5 + [ctypes.c_double, c_double_p]),
     'ssmq_transform_update_mo': (ctypes.c_int, [ctypes.c_void_p] + [c_double_p] * 5 + [ctypes.c_double, c_double_p]),
     'ssmq_weights_gp_mo': (ctypes.c_int, [ctypes.c_int] * 3 + [c_double_p] * 2 + [ctypes.c_double] + [c_double_p] * 9 + [c_int32_p]),

@@ -132,6 +132,7 @@ int filter_forward_impl(ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, ssmq
         set_error("filter_forward: bad argument");
         return SSMQ_E_ARG;
     }
+    if (is_trunc(h_dyn)) return refuse_trunc("filter with a truncated DYNAMICS transform");
     const int D = h_dyn->D, Y = h_obs->E;
     if (h_dyn->E != D || h_obs->D != D) {
         set_error("filter_forward: additive-noise filter needs dyn (D -> D) and obs (D -> Y) transforms");
@@ -144,6 +145,12 @@ int filter_forward_impl(ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, ssmq
     if (mo && user) return refuse_user_integrand("multi-output transform (k_apply_mo)");
     if (mo && (d_pm || d_pP || d_pC)) return refuse_mo("smoother (predictive moments kept)");
     if (mo && (sscale || student_dof != 0.0)) return refuse_mo("Studentian filter");
+    // a truncated sigma-point transform: the measurement transform of the Gaussian launch loop (forward pass and smoother) next to
+    // a sigma-point dynamics transform, nothing else
+    const bool trunc = is_trunc(h_obs);
+    if (trunc && h_dyn->form != SSMQ_FORM_SIGMA) return refuse_trunc("filter whose dynamics transform is not a sigma-point rule");
+    if (trunc && user) return refuse_user_integrand("truncated sigma-point transform (k_apply_trunc)");
+    if (trunc && (sscale || student_dof != 0.0)) return refuse_trunc("Studentian filter");
     int rc = ensure_device();
     if (rc) return rc;
     if (B == 0) return SSMQ_OK;
@@ -206,12 +213,12 @@ int filter_forward_impl(ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, ssmq
     // one fused kernel for the whole time loop when this (models, shapes, form) combination has one (it does not keep
     // the predictive moments, so a pass that has to store them for the smoother takes the launch loop)
     const bool keep_pred = d_pm && d_pP && d_pC;
-    if (!ssmq::sw("SSMQ_NO_FUSED") && !keep_pred && !mo && !user_ekf) {
+    if (!ssmq::sw("SSMQ_NO_FUSED") && !keep_pred && !mo && !user_ekf && !trunc) {
         rc = try_launch_fused(pass);
         if (rc < 0) return rc;
         if (rc == 1) return SSMQ_OK;
     }
-    if (!ssmq::sw("SSMQ_NO_FUSED") && keep_pred && !sscale && student_dof == 0.0) {
+    if (!ssmq::sw("SSMQ_NO_FUSED") && keep_pred && !sscale && student_dof == 0.0 && !trunc) {
         // smoother: the time loop in one kernel that also leaves the predictive moments of every step in HBM (the extended Kalman
         // filter's k_ekf_loop, or the sigma-point / BQ kernel)
         if (!mo && !user_ekf) {
@@ -293,6 +300,7 @@ static int filter_forward_aug_impl(ssmq_transform *h_dyn, const ssmq_integrand *
                                    double *d_pC, int *c_cols) {
     if (is_user_integrand(f_dyn) || is_user_integrand(f_obs)) return refuse_user_integrand("filter with non-additive noise (augmented moments)");
     if (is_mo(h_dyn) || is_mo(h_obs)) return refuse_mo("filter with non-additive noise (augmented moments)");
+    if (is_trunc(h_dyn) || is_trunc(h_obs)) return refuse_trunc("filter with non-additive noise (augmented moments)");
     if (!h_dyn || !h_obs || !f_dyn || !f_obs || dim_state <= 0 || dq < 0 || dr < 0 || B < 0 || ld < B || T < 0 || !d_y ||
         !d_m0 || !d_P0 || !d_fm || !d_fP || !d_status || (dq > 0 && (!q_mean || !q_cov)) ||
         (dr > 0 && (!r_mean || !r_cov))) {
@@ -444,6 +452,7 @@ extern "C" int ssmq_filter_smooth_aug_dev(ssmq_transform *h_dyn, const ssmq_inte
     if (is_user_integrand(f_dyn) || is_user_integrand(f_obs)) return refuse_user_integrand("ssmq_filter_smooth_aug_dev");
     SSMQ_HANDLE_LOCK(h_dyn, h_obs);
     if (is_mo(h_dyn) || is_mo(h_obs)) return refuse_mo("ssmq_filter_smooth_aug_dev");
+    if (is_trunc(h_dyn) || is_trunc(h_obs)) return refuse_trunc("ssmq_filter_smooth_aug_dev");
     if (!h_dyn || !d_sm || !d_sP || dim_state <= 0 || dq < 0 || B < 0 || T < 0 || ld < B) {
         set_error("filter_smooth_aug: bad argument");
         return SSMQ_E_ARG;
@@ -496,6 +505,7 @@ extern "C" int ssmq_filter_smooth_dev(ssmq_transform *h_dyn, const ssmq_integran
     if (is_user_integrand(f_dyn) || is_user_integrand(f_obs)) return refuse_user_integrand("ssmq_filter_smooth_dev");
     SSMQ_HANDLE_LOCK(h_dyn, h_obs);
     if (is_mo(h_dyn) || is_mo(h_obs)) return refuse_mo("ssmq_filter_smooth_dev");
+    if (is_trunc(h_dyn)) return refuse_trunc("ssmq_filter_smooth_dev with a truncated DYNAMICS transform");
     if (!h_dyn || !d_sm || !d_sP || B < 0 || T < 0 || ld < B) {
         set_error("filter_smooth: bad argument");
         return SSMQ_E_ARG;
@@ -535,6 +545,7 @@ extern "C" int ssmq_student_filter_forward_dev(ssmq_transform *h_dyn, const ssmq
                                                int32_t *d_status) {
     SSMQ_HANDLE_LOCK(h_dyn, h_obs);
     if (is_mo(h_dyn) || is_mo(h_obs)) return refuse_mo("ssmq_student_filter_forward_dev");
+    if (is_trunc(h_dyn) || is_trunc(h_obs)) return refuse_trunc("ssmq_student_filter_forward_dev");
     if (!scale || !(dof > 0.0)) {
         set_error("student_filter_forward: scale[T] and dof > 0 are required");
         return SSMQ_E_ARG;
@@ -562,7 +573,11 @@ extern "C" int ssmq_filter_kernel_name_batch(const ssmq_transform *h_dyn, const 
     // (the extended Kalman filters of a user model run the launch loop: filter_forward_impl)
     const bool ekf = (h_dyn->form == SSMQ_FORM_TAYLOR1 || is_taylor_gpqd(h_dyn)) && (h_obs->form == SSMQ_FORM_TAYLOR1 || is_taylor_gpqd(h_obs));
     const bool user = is_user_integrand(f_dyn) || is_user_integrand(f_obs);
-    rc = mo || (user && ekf) || (ssmq::sw("SSMQ_NO_FUSED") && !user) ? 0 : try_launch_fused(query);
+    // (a truncated measurement transform runs the launch loop: filter_forward_impl, which also makes the refusals)
+    if (is_trunc(h_dyn)) return refuse_trunc("filter with a truncated DYNAMICS transform");
+    if (is_trunc(h_obs) && h_dyn->form != SSMQ_FORM_SIGMA) return refuse_trunc("filter whose dynamics transform is not a sigma-point rule");
+    if (is_trunc(h_obs) && user) return refuse_user_integrand("truncated sigma-point transform (k_apply_trunc)");
+    rc = mo || is_trunc(h_obs) || (user && ekf) || (ssmq::sw("SSMQ_NO_FUSED") && !user) ? 0 : try_launch_fused(query);
     if (rc < 0) return rc;
     snprintf(buf, len, "%s", rc == 1 ? name : "hipGraph of 3 T launches (apply dyn | apply obs | k_kalman_update)");
     return SSMQ_OK;

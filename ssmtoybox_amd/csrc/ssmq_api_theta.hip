@@ -49,6 +49,7 @@ extern "C" int ssmq_gp_theta_step(ssmq_transform *h_dyn, const ssmq_integrand *f
                                   double *post_mean, double *post_cov, double *loglik, int32_t *status) {
     if (is_user_integrand(f_dyn) || is_user_integrand(f_obs)) return refuse_user_integrand("ssmq_gp_theta_step");
     if (is_mo(h_dyn) || is_mo(h_obs)) return refuse_mo("ssmq_gp_theta_step");
+    if (is_trunc(h_dyn) || is_trunc(h_obs)) return refuse_trunc("ssmq_gp_theta_step");
     if (is_taylor_gpqd(h_dyn) || is_taylor_gpqd(h_obs)) return refuse_taylor_gpqd("ssmq_gp_theta_step");
     SSMQ_HANDLE_LOCK(h_dyn, h_obs);
     return gp_theta_step_impl(h_dyn, f_dyn, h_obs, f_obs, P, par_dyn, par_obs, jitter, mean, cov, shared_state, y, shared_y, time,
@@ -64,6 +65,7 @@ extern "C" int ssmq_gp_theta_step_times(ssmq_transform *h_dyn, const ssmq_integr
                                         double *post_mean, double *post_cov, double *loglik, int32_t *status) {
     if (is_user_integrand(f_dyn) || is_user_integrand(f_obs)) return refuse_user_integrand("ssmq_gp_theta_step_times");
     if (is_mo(h_dyn) || is_mo(h_obs)) return refuse_mo("ssmq_gp_theta_step_times");
+    if (is_trunc(h_dyn) || is_trunc(h_obs)) return refuse_trunc("ssmq_gp_theta_step_times");
     if (is_taylor_gpqd(h_dyn) || is_taylor_gpqd(h_obs)) return refuse_taylor_gpqd("ssmq_gp_theta_step_times");
     SSMQ_HANDLE_LOCK(h_dyn, h_obs);
     if (!times) {

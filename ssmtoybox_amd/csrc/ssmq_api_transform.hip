@@ -456,6 +456,21 @@ int apply_dev_impl(ssmq_transform *h, const ssmq_integrand *f, int64_t B, int64_
         m.fp.ttab = ttab;
         return launch_apply_mo(m, B, stream());
     }
+    if (is_trunc(h)) {
+        // the truncated sigma-point form: one kernel for the whole supported range (ssmq_apply_trunc.hip), built-in integrands
+        if (is_user_integrand(f)) return refuse_user_integrand("truncated sigma-point transform (k_apply_trunc)");
+        if (kernel_name) *kernel_name = "k_apply_trunc";
+        if (dry_run || B <= 0) return SSMQ_OK;
+        if (null_args()) return SSMQ_E_ARG;
+        LinArgs a;
+        memset(&a, 0, sizeof(a));
+        a.mean = d_mean; a.cov = d_cov; a.time = d_time; a.time_stride = d_time ? time_stride : 0; a.cov_add = d_cov_add;
+        a.mean_f = d_mean_f; a.cov_f = d_cov_f; a.cov_fx = d_cov_fx; a.status = d_status; a.B = B; a.ld = ld;
+        a.cov_scale = cov_scale; a.ccov_scale = ccov_scale;
+        fill_fpar(f, &a.fp);
+        a.fp.ttab = ttab;
+        return launch_apply_trunc(h, f, a, stream());
+    }
     // argument block of the register-resident kernels; fp.ttab stays null (the table route sets it, the user route has no table)
     auto fill_args = [&](ApplyArgs &a) {
         a.mean = d_mean; a.cov = d_cov; a.time = d_time ? d_time : d_mean; a.mean_f = d_mean_f; a.cov_f = d_cov_f;
@@ -723,6 +738,7 @@ int ssmq_transform_update(ssmq_transform *h, const double *xi, const double *wm,
                           const double *emv, int emv_mode, double tp_nu, const double *tp_iK) {
     SSMQ_HANDLE_LOCK(h);
     if (is_mo(h)) return refuse_mo("ssmq_transform_update (use ssmq_transform_update_mo)");
+    if (is_trunc(h)) return refuse_trunc("ssmq_transform_update (recreate the handle)");
     if (h && h->form == SSMQ_FORM_TAYLOR1) {
         set_error("transform_update: the linearisation transform has no constants");
         return SSMQ_E_ARG;
@@ -754,6 +770,7 @@ void ssmq_transform_destroy(ssmq_transform *h) {
         if (ssmq::stream()) hipStreamSynchronize(ssmq::stream());
     }   // ... and nobody may hold the handle any more: destroying it while another thread uses it is the caller's error
     if (h->d_mo) hipFree(h->d_mo);
+    if (h->d_trunc) hipFree(h->d_trunc);
     if (h->d_small) hipFree(h->d_small);
     if (h->d_wide) hipFree(h->d_wide);
     if (h->d_wc_pad) hipFree(h->d_wc_pad);

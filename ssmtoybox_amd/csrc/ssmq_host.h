@@ -41,6 +41,11 @@ struct ssmq_transform {
     // (ssmq_taylor_gpqd_variance_planes; null: not written)
     double tg_alpha = 0.0, tg_ell[SSMQ_MAX_DIM] = {};
     double *d_tg_mvar = nullptr, *d_tg_ivar = nullptr;
+    // truncated sigma-point form (SSMQ_FORM_TRUNC_SIGMA, ssmq_apply_trunc.hip): D inputs of which the integrand reads the tr_deff
+    // leading ones, N points of the full-dimension rule, tr_neff of the effective one; d_trunc is the one constant block
+    // (trunc_layout), d_small / d_wide stay null and no host copies are kept (the handle is recreated when its constants change)
+    int tr_deff = 0, tr_neff = 0;
+    double *d_trunc = nullptr;
     uint32_t generation = 0;   // bumped by every upload of constants (create / update)
     // Threads (include/ssmq.h, conventions): every entry point that takes this handle holds `mu` for its duration; `owner` /
     // `owner_epoch` name the thread context (its stream) that used the handle last - another context waits for that stream
@@ -205,6 +210,16 @@ int refuse_mo(const char *what);   // sets the error text, returns SSMQ_E_UNSUPP
 // the Taylor-GPQD form (ssmq_jacobian_kernel.h): no points, no weights - every entry point that reads a handle's constants refuses it
 inline bool is_taylor_gpqd(const ssmq_transform *h) { return h && h->form == SSMQ_FORM_TAYLOR_GPQD; }
 int refuse_taylor_gpqd(const char *what);   // sets the error text, returns SSMQ_E_UNSUPPORTED
+// the truncated sigma-point form (ssmq_apply_trunc.hip): two point sets in a block of its own - it runs through ssmq_apply_batch[_dev]
+// and as the measurement transform of the launch-loop filter and smoother, every other entry point refuses it
+inline bool is_trunc(const ssmq_transform *h) { return h && h->form == SSMQ_FORM_TRUNC_SIGMA; }
+int refuse_trunc(const char *what);   // sets the error text, returns SSMQ_E_UNSUPPORTED
+bool trunc_range_ok(int D, int D_eff, int E, int N_eff, int N);   // 1 <= D_eff <= D <= 6, 1 <= E <= 4, 1 <= N_eff, N <= 729
+struct TruncArgs;                     // ssmq_apply_trunc.hip
+// `planes`: the planes, the time argument, cov_add, B, ld and the hooks of one application (a LinArgs, as for launch_jacobian); the
+// rest of the argument block comes from the handle and the integrand.  SSMQ_OK or < 0.
+struct LinArgs;
+int launch_apply_trunc(const ssmq_transform *h, const ssmq_integrand *f, const LinArgs &planes, hipStream_t s);
 enum { SSMQ_MO_FULL = 0, SSMQ_MO_POINTS = 1, SSMQ_MO_FX = 2 };
 struct MoArgs {
     int D, E, N, mode, fid, time_stride;
@@ -443,7 +458,7 @@ inline void key_bytes(std::vector<uint64_t> &key, const void *p, size_t n) {
 inline void key_of_pair(std::vector<uint64_t> &key, const ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, const ssmq_transform *h_obs,
                         const ssmq_integrand *f_obs) {
     for (const ssmq_transform *h : {h_dyn, h_obs}) {
-        for (const void *p : {(const void *)h, (const void *)h->d_small, (const void *)h->d_mo}) key.push_back((uint64_t)(uintptr_t)p);
+        for (const void *p : {(const void *)h, (const void *)h->d_small, (const void *)h->d_mo, (const void *)h->d_trunc}) key.push_back((uint64_t)(uintptr_t)p);
         for (int v : {h->D, h->E, h->N, h->form, h->emv_mode, h->opt_mask, h->np_pad, (int)h->generation}) key.push_back((uint64_t)(uint32_t)v);
         key_bytes(key, &h->tp_nu, 8);
     }
@@ -454,9 +469,10 @@ inline void key_of_pair(std::vector<uint64_t> &key, const ssmq_transform *h_dyn,
 // (ssmq_filter_fused.hip).  A route states what it sets differently next to its launch.
 FusedArgs fused_args(const FilterPass &p);
 // both transforms of one form (sigma-point, BQ or t-process BQ), a measurement index pattern the kernels know, no state index list;
-// the Taylor-GPQD form is no family by name: no time-loop kernel (fused, strips, quad, wave split, time blocks) reads its parameters
+// the Taylor-GPQD and the truncated sigma-point form are no family by name: no time-loop kernel (fused, strips, quad, wave split,
+// time blocks) reads their parameters
 inline bool same_family(const FilterPass &p) {
-    return !is_taylor_gpqd(p.hd) && !is_taylor_gpqd(p.ho) && p.hd->form == p.ho->form && (p.hd->tp_nu > 0.0) == (p.ho->tp_nu > 0.0) && p.sel_obs >= 0 && p.fd->n_idx <= 0;
+    return !is_taylor_gpqd(p.hd) && !is_taylor_gpqd(p.ho) && !is_trunc(p.hd) && !is_trunc(p.ho) && p.hd->form == p.ho->form && (p.hd->tp_nu > 0.0) == (p.ho->tp_nu > 0.0) && p.sel_obs >= 0 && p.fd->n_idx <= 0;
 }
 // Integrands whose time dependence the fused loops read from a per-step table (time_table() in ssmq_device.h fills it); the kernels'
 // HasTimeTable<> (ssmq_fused.h) is checked against this function id by id in ssmq_filter_shapes.h.

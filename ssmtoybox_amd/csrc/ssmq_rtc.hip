@@ -407,7 +407,7 @@ int rtc_launch_fused(const FilterPass &p) {
         return SSMQ_E_UNSUPPORTED;
     }
     if (hd->form != ho->form || (hd->tp_nu > 0.0) != (ho->tp_nu > 0.0) || p.sel_obs != 0 || hd->form == SSMQ_FORM_TAYLOR1 ||
-        is_taylor_gpqd(hd)) {
+        is_taylor_gpqd(hd) || is_trunc(hd) || is_trunc(ho)) {
         set_error("user integrands: both transforms of one form (sigma-point or BQ), no linearisation, no state index");
         return SSMQ_E_UNSUPPORTED;
     }
@@ -450,7 +450,7 @@ int rtc_launch_apply(const ssmq_transform *h, const ssmq_integrand *f, int sel, 
         set_error(why);
         return SSMQ_E_UNSUPPORTED;
     }
-    if (sel != 0 || h->form == SSMQ_FORM_TAYLOR1 || is_taylor_gpqd(h)) {
+    if (sel != 0 || h->form == SSMQ_FORM_TAYLOR1 || is_taylor_gpqd(h) || is_trunc(h)) {
         set_error("user integrands: sigma-point or BQ transforms only, no state index");
         return SSMQ_E_UNSUPPORTED;
     }

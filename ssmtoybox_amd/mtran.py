@@ -605,6 +605,152 @@ class GaussHermiteTransform(SigmaPointTransform):
         return _product_grid(x, dim).T
 
 
+class TruncatedSigmaPointTransform(_DeviceApply, MomentTransform):
+    """Sigma-point transform that respects the effective input dimension of `f` (mtran.py:588-622; the reference calls it
+    experimental): a function that reads only the `dim_eff` leading of its `dim` inputs has its mean and covariance integrated by
+    the rule of dimension `dim_eff` on the leading block of the input moments, and only the input-output covariance by the rule
+    of the full dimension.  With L = chol(cov), m_e = mean[:dim_eff], L_e = L[:dim_eff, :dim_eff] (= chol(cov[:dim_eff, :dim_eff])):
+
+        x_eff_i = m_e + L_e unit_sp_eff[:, i],   x_j = mean + L unit_sp[:, j]
+        mean_f = sum_i wm_i f(x_eff_i),  cov_f = sum_i Wc_ii (f(x_eff_i) - mean_f)(..)',  cov_fx = sum_j Wcc_jj (f(x_j) - mean_f)(x_j - mean)'
+
+    mean_f and cov_f depend on mean[:dim_eff] and cov[:dim_eff, :dim_eff] alone, bit for bit.  Subclasses set `dim`, `dim_eff`,
+    `wm`, `Wc`, `unit_sp_eff` (rule of dim_eff) and `Wcc`, `unit_sp` (rule of dim), as the reference does; replacing any of them
+    after construction is picked up by the next call.  One launch of `k_apply_trunc` (csrc/ssmq_apply_trunc.hip) for a batch.
+
+    Supported `f`: the bound dyn_eval / meas_eval of a built-in model with additive noise that reads at most `dim_eff` leading
+    inputs (a measurement model: dim_substate <= dim_eff and every state_index entry < dim_eff; a transition model:
+    dim_state <= dim_eff), for 1 <= dim_eff <= dim <= 6, at most 4 outputs and at most 729 points per rule; everything else
+    raises NotImplementedError before the library is touched.  An item whose covariance is not positive definite has status 1 and
+    NaN moments (apply(): LinAlgError)."""
+
+    MAX_DIM, MAX_OUT, MAX_POINTS = 6, 4, 729
+    _RANGE = 'the truncated sigma-point transforms cover 1 <= dim_eff <= dim <= 6, 1 <= outputs <= 4 and at most 729 points per rule'
+    _SUPPORTED = ('the truncated sigma-point transforms take the bound dyn_eval / meas_eval of a built-in model with additive noise that '
+                  'reads at most dim_eff leading inputs (dim_substate <= dim_eff, every state_index entry < dim_eff; a transition '
+                  'model: dim_state <= dim_eff)')
+
+    def _num_points(self):
+        return self.unit_sp.shape[1]
+
+    def _check_range(self, E=1):
+        if not (1 <= int(self.dim_eff) <= int(self.dim) <= self.MAX_DIM and 1 <= int(E) <= self.MAX_OUT
+                and 1 <= self.unit_sp_eff.shape[1] <= self.MAX_POINTS and 1 <= self.unit_sp.shape[1] <= self.MAX_POINTS):
+            raise NotImplementedError('{} (got dim = {}, dim_eff = {}, {} outputs, {} and {} points)'.format(
+                self._RANGE, self.dim, self.dim_eff, E, self.unit_sp_eff.shape[1], self.unit_sp.shape[1]))
+
+    def _device_integrand(self, f):
+        """(Integrand, E) of a supported `f`; every refusal is raised here, before the library is touched."""
+        owner = getattr(f, '__self__', None)
+        name = getattr(f, '__name__', '')
+        if is_user_model(owner):
+            raise user_unsupported('the truncated sigma-point transforms (built-in models)')
+        if owner is None or name not in ('dyn_eval', 'meas_eval') or not hasattr(owner, 'device_integrand'):
+            raise NotImplementedError('not an arbitrary Python callable: ' + self._SUPPORTED)
+        if not owner.noise_additive:
+            raise NotImplementedError('not a model with non-additive noise: ' + self._SUPPORTED)
+        de = int(self.dim_eff)
+        if name == 'meas_eval':
+            idx = owner.state_index
+            din = owner.dim_substate if owner.dim_substate is not None else owner.dim_state
+            reads_ok = din <= de if idx is None else (len(idx) >= din and all(0 <= int(i) < de for i in idx))
+        else:
+            reads_ok = owner.dim_state <= de
+        if not reads_ok:
+            raise NotImplementedError('{} reads inputs beyond dim_eff = {}: {}'.format(type(owner).__name__, de, self._SUPPORTED))
+        integ, E = owner.device_integrand()
+        self._check_range(E)
+        return integ, E
+
+    def _handle_for(self, E):
+        self._check_range(E)
+        D, de = int(self.dim), int(self.dim_eff)
+        vec = lambda w: np.diag(w) if np.ndim(w) == 2 else np.asarray(w)      # noqa: E731
+        arrs = [np.ascontiguousarray(a, dtype=np.float64) for a in (self.unit_sp_eff, self.wm, vec(self.Wc), self.unit_sp, vec(self.Wcc))]
+        NE, N = arrs[0].shape[1], arrs[3].shape[1]
+        if arrs[0].shape != (de, NE) or arrs[1].shape != (NE,) or arrs[2].shape != (NE,) or arrs[3].shape != (D, N) or arrs[4].shape != (N,):
+            raise ValueError('truncated transform: unit_sp_eff (dim_eff, N_eff), wm / Wc of N_eff, unit_sp (dim, N), Wcc of N expected')
+        if not all(np.all(np.isfinite(a)) for a in arrs):
+            raise ValueError('truncated transform: points and weights must be finite')
+        if not hasattr(self, '_dev'):
+            self._dev = {}
+        snap = (D, de) + tuple(a.tobytes() for a in arrs)
+        have = self._dev.get(E)
+        if have is not None and have[1] == snap:
+            return have[0]
+        lib = _lib.load()
+        if have is not None:                 # constants were replaced: ssmq_transform_update does not take this form
+            lib.ssmq_transform_destroy(ctypes.c_void_p(have[0]))
+            del self._dev[E]
+        ptr = [a.ctypes.data_as(_lib.c_double_p) for a in arrs]
+        h = lib.ssmq_transform_create_truncated(D, de, int(E), NE, ptr[0], ptr[1], ptr[2], N, ptr[3], ptr[4])
+        if not h:
+            raise _lib.SsmqError('ssmq_transform_create_truncated failed: ' + _lib.last_error())
+        self._dev[E] = (h, snap)
+        return h
+
+    def kernel_name(self, f):
+        self._device_integrand(f)
+        return super().kernel_name(f)
+
+    def apply_batch(self, f, mean, cov, time=0.0, fcn_pars=None, return_status=False):
+        self._device_integrand(f)
+        if np.ndim(mean) != 2 or np.shape(mean)[1] != int(self.dim):
+            raise ValueError('mean must have shape (B, dim) with dim = {}'.format(self.dim))
+        return super().apply_batch(f, mean, cov, time=time, fcn_pars=fcn_pars, return_status=return_status)
+
+    def apply_batch_dev(self, f, mean, cov, time, mean_f, cov_f, cov_fx, status, time_stride=0):
+        self._device_integrand(f)
+        return super().apply_batch_dev(f, mean, cov, time, mean_f, cov_f, cov_fx, status, time_stride=time_stride)
+
+    def __del__(self):
+        try:
+            lib = _lib.load()
+            for h, _ in getattr(self, '_dev', {}).values():
+                lib.ssmq_transform_destroy(ctypes.c_void_p(h))
+            self._dev = {}
+        except Exception:
+            pass
+
+
+class TruncatedSphericalRadialTransform(TruncatedSigmaPointTransform):
+    """Truncated spherical-radial rule (mtran.py:625-634)."""
+
+    def __init__(self, dim, dim_eff):
+        self.dim, self.dim_eff = dim, dim_eff
+        # weights & points for the transformed mean and covariance
+        self.wm = SphericalRadialTransform.weights(dim_eff)
+        self.Wc = np.diag(self.wm)
+        self.unit_sp_eff = SphericalRadialTransform.unit_sigma_points(dim_eff)
+        # weights & points for the input-output covariance
+        self.Wcc = np.diag(SphericalRadialTransform.weights(dim))
+        self.unit_sp = SphericalRadialTransform.unit_sigma_points(dim)
+
+
+class TruncatedUnscentedTransform(TruncatedSigmaPointTransform):
+    """Truncated unscented rule (mtran.py:637-646)."""
+
+    def __init__(self, dim, dim_eff, kappa=None, alpha=1.0, beta=2.0):
+        self.dim, self.dim_eff = dim, dim_eff
+        self.wm, wc = UnscentedTransform.weights(dim_eff, kappa, alpha, beta)
+        self.Wc = np.diag(wc)
+        self.unit_sp_eff = UnscentedTransform.unit_sigma_points(dim_eff, kappa, alpha)
+        self.Wcc = np.diag(UnscentedTransform.weights(dim, kappa, alpha, beta)[1])
+        self.unit_sp = UnscentedTransform.unit_sigma_points(dim, kappa, alpha)
+
+
+class TruncatedGaussHermiteTransform(TruncatedSigmaPointTransform):
+    """Truncated Gauss-Hermite rule (mtran.py:649-658)."""
+
+    def __init__(self, dim, dim_eff, degree=3):
+        self.dim, self.dim_eff = dim, dim_eff
+        self.wm = GaussHermiteTransform.weights(dim_eff, degree)
+        self.Wc = np.diag(self.wm)
+        self.unit_sp_eff = GaussHermiteTransform.unit_sigma_points(dim_eff, degree)
+        self.Wcc = np.diag(GaussHermiteTransform.weights(dim, degree))
+        self.unit_sp = GaussHermiteTransform.unit_sigma_points(dim, degree)
+
+
 class FullySymmetricStudentTransform(SigmaPointTransform):
     """Fully symmetric rule for Student-t densities, degree 3 or 5 (mtran.py:363-578), and - NOT in the reference, whose
     rules stop at degree 5 (mtran.py:392) - a degree-7 rule of this build for BASELINE configs[4] ("fully-symmetric

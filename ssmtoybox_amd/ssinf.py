@@ -21,7 +21,8 @@ import numpy as np
 
 from . import _lib
 from .mtran import (MomentTransform, LinearizationTransform, TaylorGPQDTransform, UnscentedTransform, SphericalRadialTransform, GaussHermiteTransform,
-                    FullySymmetricStudentTransform, resolve_integrand)
+                    FullySymmetricStudentTransform, TruncatedUnscentedTransform, TruncatedSphericalRadialTransform,
+                    TruncatedGaussHermiteTransform, resolve_integrand)
 from .bq.bqmtran import (GaussianProcessTransform, BayesSardTransform, StudentTProcessTransform,
                          MultiOutputGaussianProcessTransform)
 from .ssmod import TransitionModel, MeasurementModel, is_user_model, has_device_jacobian, user_unsupported, check_user_points
@@ -299,6 +300,9 @@ def run_filters(algs, data, x0_mean=None, x0_cov=None, raise_on_failure=True):
             raise NotImplementedError('run_filters: additive-noise Gaussian / Studentian filters only')
         if isinstance(a, MultiOutputGaussianProcessKalman):
             raise NotImplementedError('run_filters: not implemented for the multi-output filter (its forward pass is a launch loop)')
+        if isinstance(a, TruncatedInference):
+            raise NotImplementedError('run_filters: not implemented for the truncated filters (their forward pass is a launch loop that '
+                                      'ssmq_filter_forward_multi_dev refuses by name)')
         if isinstance(a, ExtendedKalmanGPQD):
             raise NotImplementedError('run_filters: not implemented for ExtendedKalmanGPQD (its forward pass is a launch loop that '
                                       'ssmq_filter_forward_multi_dev refuses by name)')
@@ -409,6 +413,54 @@ class UnscentedKalman(GaussianInference):
     def __init__(self, dyn, obs, kappa=None, alpha=1.0, beta=2.0):
         super().__init__(dyn, obs, UnscentedTransform(dyn.dim_in, kappa=kappa, alpha=alpha, beta=beta),
                          UnscentedTransform(obs.dim_in, kappa=kappa, alpha=alpha, beta=beta))
+
+
+class TruncatedInference(GaussianInference):
+    """Base of the filters whose measurement update is aware of the effective dimension of the measurement model (ssinf.py:836-901;
+    the reference calls them experimental): the time update is the plain transform of the rule, the measurement update the
+    truncated one (`mtran.TruncatedSigmaPointTransform`) - measurement mean and covariance from the rule of dimension `dim_eff`,
+    the state-measurement covariance from the rule of the full state dimension.
+
+    `dim_eff` is this package's one deliberate departure from the reference: None (the default) means `obs.dim_substate`, the
+    number of leading state entries the measurement model reads, which is what these classes promise.  The reference passes
+    `obs.dim_in`, which equals `dim_state` for every additive-noise model there, so its three filters coincide with the UKF / CKF /
+    GHKF (ssinf.py:859, 878, 900); `dim_eff=obs.dim_state` gives that behaviour.
+
+    forward_pass / forward_pass_batch / forward_pass_dev and backward_pass / backward_pass_batch run as the captured launch loop
+    (apply dyn | k_apply_trunc | k_kalman_update per step; the smoother's variant keeps the predictive moments).  Built-in models
+    with additive noise; `run_filters` raises NotImplementedError for these classes."""
+
+    def __init__(self, dyn, obs, tf_dyn_cls, tf_obs_cls, dim_eff, *rule_args):
+        if is_user_model(dyn) or is_user_model(obs):
+            raise user_unsupported('the truncated filters (built-in models)')
+        if not (dyn.noise_additive and obs.noise_additive):
+            raise NotImplementedError('{} runs for additive-noise models only'.format(type(self).__name__))
+        self.dim_eff = int(obs.dim_substate if dim_eff is None else dim_eff)
+        tf_obs = tf_obs_cls(obs.dim_state, self.dim_eff, *rule_args)
+        tf_obs._device_integrand(obs.meas_eval)          # range and what the model reads: refused here, before the library is touched
+        super().__init__(dyn, obs, tf_dyn_cls(dyn.dim_in, *rule_args), tf_obs)
+
+
+class TruncatedUnscentedKalman(TruncatedInference):
+    """Truncated unscented Kalman filter and smoother (ssinf.py:844-860); dim_eff=None: obs.dim_substate, see `TruncatedInference`."""
+
+    def __init__(self, dyn, obs, kappa=None, alpha=1.0, beta=2.0, dim_eff=None):
+        super().__init__(dyn, obs, UnscentedTransform, TruncatedUnscentedTransform, dim_eff, kappa, alpha, beta)
+
+
+class TruncatedCubatureKalman(TruncatedInference):
+    """Truncated cubature Kalman filter and smoother (ssinf.py:863-879); dim_eff=None: obs.dim_substate, see `TruncatedInference`."""
+
+    def __init__(self, dyn, obs, dim_eff=None):
+        super().__init__(dyn, obs, SphericalRadialTransform, TruncatedSphericalRadialTransform, dim_eff)
+
+
+class TruncatedGaussHermiteKalman(TruncatedInference):
+    """Truncated Gauss-Hermite Kalman filter and smoother (ssinf.py:882-901); dim_eff=None: obs.dim_substate, see
+    `TruncatedInference`."""
+
+    def __init__(self, dyn, obs, degree, dim_eff=None):
+        super().__init__(dyn, obs, GaussHermiteTransform, TruncatedGaussHermiteTransform, dim_eff, degree)
 
 
 class GaussHermiteKalman(GaussianInference):
