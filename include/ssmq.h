@@ -120,7 +120,9 @@ int ssmq_integrand_define_dx(const char *body, const char *jac_body, int din, in
 /* SSMQ_RTC_MC instantiates the streaming Monte-Carlo kernel k_mc_moments<id, D, E, 0> (N, N_obs, form, tp, opt ignored). */
 /* SSMQ_RTC_LINEAR / SSMQ_RTC_TAYLOR_GPQD instantiate k_linearize_fn / k_taylor_gpqd_fn<id, D, E, din> for an id that has a
  * Jacobian (N, N_obs, form, tp, opt ignored); an id without one is SSMQ_E_UNSUPPORTED. */
-enum ssmq_rtc_kind { SSMQ_RTC_FILTER = 0, SSMQ_RTC_APPLY = 1, SSMQ_RTC_MC = 2, SSMQ_RTC_LINEAR = 3, SSMQ_RTC_TAYLOR_GPQD = 4 };
+/* SSMQ_RTC_GPQD instantiates the GPQ+D kernel of a user id that has a Jacobian: k_apply_gpqd<id, D, E, din> for D <= 2,
+ * k_apply_gpqd_lds<id, D, E, din> beyond (D <= 6, E <= max(D, 4); N, N_obs, form, tp, opt ignored). */
+enum ssmq_rtc_kind { SSMQ_RTC_FILTER = 0, SSMQ_RTC_APPLY = 1, SSMQ_RTC_MC = 2, SSMQ_RTC_LINEAR = 3, SSMQ_RTC_TAYLOR_GPQD = 4, SSMQ_RTC_GPQD = 5 };
 int ssmq_rtc_compile_check(int32_t id, int32_t id_obs, int kind, int D, int E, int N, int N_obs, int form, int tp, int opt,
                            const char *arch, char *log, int len);
 /* Process-wide counters of the run-time compiler: programs compiled, kernel lookups served from the cache, compile wall time. */
@@ -150,9 +152,12 @@ enum ssmq_form {
                             derivative observations and an RBF kernel - mean = wm f(m); cov = wc (f f' + J Wc J') - mean mean' +
                             model_var; ccov = J cov (Lam + cov)^-1 Lam.  Handles of this form come from
                             ssmq_transform_create_taylor_gpqd only */
-    SSMQ_FORM_TRUNC_SIGMA = 5 /* mtran.py:588-658 (TruncatedSigmaPointTransform): mean and cov from a sigma-point rule of the effective
+    SSMQ_FORM_TRUNC_SIGMA = 5, /* mtran.py:588-658 (TruncatedSigmaPointTransform): mean and cov from a sigma-point rule of the effective
                             dimension on the leading block of the input moments, ccov from the rule of the full dimension.  Handles
                             of this form come from ssmq_transform_create_truncated only */
+    SSMQ_FORM_GPQD = 6 /* research/gpqd/gpqd_base.py (GaussianProcessDerTransform): the BQ moment equations on the integrand's values
+                            at all sigma points and the rows of J(x_n) L at a subset of them.  Handles of this form come from
+                            ssmq_transform_create_gpqd only */
 };
 
 /* How the expected model variance enters the covariance (bq/bqmtran.py:198 `model_var * I_out`). */
@@ -440,6 +445,37 @@ int ssmq_taylor_gpqd_variance_planes(ssmq_transform *h, double *d_model_var, dou
  */
 ssmq_transform *ssmq_transform_create_truncated(int D, int D_eff, int E, int N_eff, const double *xi_eff, const double *wm,
                                                 const double *wc, int N, const double *xi, const double *wcc);
+/*
+ * GP quadrature with derivative observations at the sigma points (SSMQ_FORM_GPQD; research/gpqd/gpqd_base.py:
+ * GaussianProcessDerTransform): xi [D*N] as for ssmq_transform_create; which_der [Nd], strictly increasing indices into the points
+ * (Nd = 0: none); the weights in the compact layout of M = N + Nd D observations per output,
+ *     [f(x_0) .. f(x_N-1) | (J L)[e, :] at which_der[0] | (J L)[e, :] at which_der[1] | ..],   L = chol(cov), x_n = mean + L xi_n:
+ * wm [M], Wc [M*M], Wcc [D*M], and the scalar model variance, added to the diagonal of the covariance.
+ *   mean_f = obs wm,  cov_f = obs Wc obs' - mean_f mean_f' + model_var I,  cov_fx = (obs Wcc') L'      - (E, D).
+ * 1 <= D <= 6, 1 <= E <= max(D, 4), 2 <= N <= 2 D + 1, finite constants (else NULL, ssmq_last_error() names the range).  Integrands:
+ * the built-in models that have a Jacobian and additive noise (UNGM, pendulum, constant velocity and their measurement models; the
+ * Jacobian placed as for ssmq_transform_create_linear) and user ids registered with ssmq_integrand_define_dx; everything else is
+ * SSMQ_E_UNSUPPORTED at apply time.  One launch per batch: k_apply_gpqd (D <= 2, observations in registers) or k_apply_gpqd_lds
+ * (observations in LDS); an item whose cov is not positive definite has status 1 and NaN outputs.  The handle runs through
+ * ssmq_apply_batch[_dev], ssmq_apply_kernel_name and, both handles of this form, the launch loop of ssmq_filter_forward_dev and
+ * ssmq_filter_smooth_dev (built-in models; the forward pass also for user ids); every other entry point that takes a transform
+ * handle returns SSMQ_E_UNSUPPORTED for it before it writes to an output.  ssmq_transform_gpqd_set replaces the subset, the weights
+ * and the model variance of a handle (same D, E, N and points).
+ * ssmq_weights_gpqd computes the weights on the device (ssmq_weights_gpqd.hip, one workgroup, the joint kernel matrix in LDS): the
+ * RBF kernel par = [alpha, ell_1 .. ell_D], jitter on the whole diagonal of the M x M joint kernel matrix of values and derivatives;
+ * `scaling` != 0 evaluates the joint kernel matrix with alpha^2 (K_out, L_out, iK_out: what eval / eval_chol / eval_inv_dot of the
+ * reference return by default); the weights and variances are the reference's bq_weights for scaling = 0 only.  Outputs (host, each may be NULL): wm [M], Wc [M*M] symmetrised, Wcc [D*M], model_var, integral_var, the joint
+ * kernel matrix without jitter K_out [M*M], its lower Cholesky factor with jitter L_out [M*M], the symmetrised inverse iK_out [M*M],
+ * and the joint kernel expectations q_out [M], Q_out [M*M], R_out [D*M].  Returns 1 if the matrix is not positive definite (NaN
+ * outputs), SSMQ_OK otherwise.
+ */
+ssmq_transform *ssmq_transform_create_gpqd(int D, int E, int N, const double *xi, int Nd, const int32_t *which_der, const double *wm,
+                                           const double *Wc, const double *Wcc, double model_var);
+int ssmq_transform_gpqd_set(ssmq_transform *h, int Nd, const int32_t *which_der, const double *wm, const double *Wc, const double *Wcc,
+                            double model_var);
+int ssmq_weights_gpqd(int D, int N, const double *xi, const double *par, int Nd, const int32_t *which_der, double jitter, int scaling,
+                      double *wm, double *Wc, double *Wcc, double *model_var, double *integral_var, double *K_out, double *L_out,
+                      double *iK_out, double *q_out, double *Q_out, double *R_out);
 /*
  * The multi-output BQ transform (SSMQ_FORM_BQ_MO; MultiOutputGaussianProcessTransform / MultiOutputStudentTProcessTransform,
  * bq/bqmtran.py:425-602): xi [D*N]; wm [E][N]; Wc [E][E][N][N], of which the blocks [i][j] with i >= j are read; Wcc [E][D][N];

@@ -10,7 +10,7 @@ from .mtran import (MomentTransform, SigmaPointTransform, UnscentedTransform, Sp
                     GaussHermiteTransform, FullySymmetricStudentTransform, MonteCarloTransform, LinearizationTransform,
                     TaylorGPQDTransform, TruncatedSigmaPointTransform, TruncatedSphericalRadialTransform,
                     TruncatedUnscentedTransform, TruncatedGaussHermiteTransform)
-from .bq.bqmtran import (BQTransform, GaussianProcessTransform, BayesSardTransform,  # noqa: F401
+from .bq.bqmtran import (BQTransform, GaussianProcessTransform, GaussianProcessDerTransform, BayesSardTransform,  # noqa: F401
                          StudentTProcessTransform, MultiOutputGaussianProcessTransform,
                          MultiOutputStudentTProcessTransform)
 

@@ -19,6 +19,7 @@ FORM_BQ, FORM_SIGMA = 0, 1
 FORM_BQ_MO = 3
 FORM_TAYLOR_GPQD = 4
 FORM_TRUNC_SIGMA = 5
+FORM_GPQD = 6
 EMV_DIAG, EMV_BROADCAST = 0, 1
 
 # integrand ids (include/ssmq.h enum ssmq_integrand_id)
@@ -28,7 +29,7 @@ F_REENTRY2D_DYN, F_RADAR2D_MEAS, F_CT_DYN, F_BEARING_MEAS = 9, 10, 11, 12
 F_CTRS_DYN, F_CV_DYN, F_REENTRY2D_BIAS_DYN, F_SMOOTH10D_DYN = 13, 14, 15, 16
 # user-defined integrands, compiled for the device at run time (include/ssmq.h ssmq_integrand_define)
 F_USER_FIRST, F_USER_SLOTS, USER_BODY_MAX, USER_MAX_D, USER_MAX_Y = 1024, 64, 8192, 6, 4
-RTC_FILTER, RTC_APPLY, RTC_MC, RTC_LINEAR, RTC_TAYLOR_GPQD = 0, 1, 2, 3, 4
+RTC_FILTER, RTC_APPLY, RTC_MC, RTC_LINEAR, RTC_TAYLOR_GPQD, RTC_GPQD = 0, 1, 2, 3, 4, 5
 
 
 class SsmqError(RuntimeError):
@@ -111,6 +112,11 @@ _PROTOTYPES = {
     'ssmq_transform_create_linear': (ctypes.c_void_p, [ctypes.c_int, ctypes.c_int]),
     'ssmq_transform_create_taylor_gpqd': (ctypes.c_void_p, [ctypes.c_int, ctypes.c_int, ctypes.c_double, c_double_p]),
     'ssmq_taylor_gpqd_variance_planes': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    'ssmq_transform_create_gpqd': (ctypes.c_void_p, [ctypes.c_int, ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_int, c_int32_p, c_double_p,
+                                                     c_double_p, c_double_p, ctypes.c_double]),
+    'ssmq_transform_gpqd_set': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_int32_p, c_double_p, c_double_p, c_double_p, ctypes.c_double]),
+    'ssmq_weights_gpqd': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, c_double_p, c_double_p, ctypes.c_int, c_int32_p, ctypes.c_double,
+                                         ctypes.c_int] + [c_double_p] * 11),
     'ssmq_transform_create_truncated': (ctypes.c_void_p, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_double_p, c_double_p,
                                                           c_double_p, ctypes.c_int, c_double_p, c_double_p]),
     'ssmq_transform_create_mo': (ctypes.c_void_p, [ctypes.c_int] * 3 + [c_double_p] * 5 + [ctypes.c_double, c_double_p]),

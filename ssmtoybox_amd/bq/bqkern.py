@@ -161,6 +161,108 @@ class RBFGauss(Kernel):
         return p[0] ** 2 * np.prod(2 * p[1:] ** -2 + 1.0) ** -0.5
 
 
+GPQD_MAX_DIM = 6
+_GPQD_RANGE = ('GP quadrature with derivative observations supports D <= 6 inputs, 2 <= N <= 2 D + 1 points and a strictly increasing '
+               'which_der within the points')
+
+
+def check_which_der(D, N, which_der):
+    """The index array of the points that carry a derivative observation (None: all), checked against the supported range;
+    NotImplementedError / ValueError before the library is touched."""
+    if not (1 <= int(D) <= GPQD_MAX_DIM and 2 <= int(N) <= 2 * int(D) + 1):
+        raise NotImplementedError('{} (got D = {}, N = {})'.format(_GPQD_RANGE, D, N))
+    wd = np.arange(N, dtype=np.int32) if which_der is None else np.asarray(which_der).reshape(-1)
+    if wd.size and (not np.issubdtype(wd.dtype, np.integer) or wd.min() < 0 or wd.max() >= N or np.any(np.diff(wd) <= 0)):
+        raise ValueError('which_der must be strictly increasing integer indices into the {} points, got {}'.format(N, which_der))
+    return np.ascontiguousarray(wd, dtype=np.int32)
+
+
+def device_gpqd_weights(points, par, which_der=None, jitter=1e-8, scaling=False):
+    """Every quantity of GP quadrature with derivative observations for one parameter row (`ssmq_weights_gpqd`): points (D, N), par
+    [alpha, ell_1 .. ell_D], which_der the points with a derivative observation (None: all).  M = N + Nd D.  Returns a dict: wm (M,),
+    Wc (M, M), Wcc (D, M), model_var, integral_var, K (M, M; joint kernel matrix without jitter), L (its lower factor with jitter),
+    iK (symmetrised inverse), q (M,), Q (M, M), R (D, M) (the joint kernel expectations, scaling=False) and which_der.  `scaling`
+    evaluates K, L and iK with alpha; the weights are the reference's for scaling=False."""
+    x, px = _lib.as_c(points)
+    D, N = x.shape
+    wd = check_which_der(D, N, which_der)
+    par = np.ascontiguousarray(np.atleast_2d(np.asarray(par, dtype=np.float64))[0])
+    if par.shape != (D + 1,):
+        raise ValueError('kernel parameters must have 1 + dim entries')
+    M = N + wd.size * D
+    out = {k: _lib.out_c(s) for k, s in (('wm', (M,)), ('Wc', (M, M)), ('Wcc', (D, M)), ('model_var', (1,)), ('integral_var', (1,)),
+                                         ('K', (M, M)), ('L', (M, M)), ('iK', (M, M)), ('q', (M,)), ('Q', (M, M)), ('R', (D, M)))}
+    rc = _lib.check(_lib.load().ssmq_weights_gpqd(D, N, px, _lib.as_c(par)[1], int(wd.size), wd.ctypes.data_as(_lib.c_int32_p),
+                                                  float(jitter), int(bool(scaling)), *[out[k][1] for k in out]), 'ssmq_weights_gpqd')
+    if rc > 0:
+        raise np.linalg.LinAlgError('Matrix is not positive definite')
+    res = {k: v[0] for k, v in out.items()}
+    res['model_var'], res['integral_var'] = float(res['model_var'][0]), float(res['integral_var'][0])
+    res['which_der'] = wd
+    return res
+
+
+class RBFGaussDer(RBFGauss):
+    """RBF kernel "with derivatives" (research/gpqd/gpqd_base.py: RBFGaussDer): the joint kernel of the integrand's values at all
+    points x (D, N) and of its D partial derivatives at the points `which_der` (None: all), M = N + Nd D rows in the order
+    [values | derivatives at which_der[0] | derivatives at which_der[1] | ..], and its expectations under N(0, I).  Everything
+    comes from one device kernel (`ssmq_weights_gpqd`).  Unlike the reference, EVERY method takes `which_der`: there only
+    `exp_x_dkx` honours the one `bq_weights` passes, so a proper subset fails with mismatched shapes.  Jitter (1e-8) goes on the
+    whole diagonal of the joint matrix."""
+
+    def __init__(self, dim, par, jitter=1e-8):
+        super().__init__(dim, par, jitter)
+
+    def _der(self, par, x, which_der, scaling=False):
+        return device_gpqd_weights(x, par, which_der, self.jitter, scaling)
+
+    def eval(self, par, x1, x2=None, diag=False, scaling=True, which_der=None):
+        """The (M, M) joint kernel matrix of the points x1 (no jitter).  Two different point sets or `diag` are the plain kernel's
+        business: NotImplementedError."""
+        if x2 is not None or diag:
+            raise NotImplementedError('RBFGaussDer.eval: the joint kernel matrix of one point set (x2=None, diag=False); for two point '
+                                      'sets use RBFGauss.eval')
+        return self._der(par, x1, which_der, scaling)['K']
+
+    def eval_chol(self, par, x, scaling=True, which_der=None):
+        """Lower Cholesky factor of K + jitter I, (M, M)."""
+        return self._der(par, x, which_der, scaling)['L']
+
+    def eval_inv_dot(self, par, x, b=None, scaling=True, which_der=None):
+        """sym((K + jitter I)^-1 b), (M, M); b = None: the inverse itself."""
+        iK = self._der(par, x, which_der, scaling)['iK']
+        if b is None:
+            return iK
+        b = np.asarray(b, dtype=np.float64)
+        if b.shape != iK.shape:
+            raise ValueError('eval_inv_dot: the right-hand side has to be (M, M), got {}'.format(b.shape))
+        r = iK.dot(b)
+        return 0.5 * (r + r.T)
+
+    def _scaled(self, par, scaling, power=1):
+        return float(np.atleast_2d(par)[0, 0]) ** (2 * power) if scaling else 1.0
+
+    def exp_x_dkx(self, par, x, scaling=False, which_der=None):
+        """E_x[k_fd(x, x_n)], (Nd D,)."""
+        N = np.shape(x)[1]
+        return self._der(par, x, which_der)['q'][N:] * self._scaled(par, scaling)
+
+    def exp_x_xdkx(self, par, x, scaling=False, which_der=None):
+        """E_x[x k_fd(x, x_m)], (D, Nd D)."""
+        N = np.shape(x)[1]
+        return np.ascontiguousarray(self._der(par, x, which_der)['R'][:, N:]) * self._scaled(par, scaling)
+
+    def exp_x_kxdkx(self, par, x, scaling=False, which_der=None):
+        """E_x[k_ff(x_n, x) k_fd(x, x_m)], (N, Nd D)."""
+        N = np.shape(x)[1]
+        return np.ascontiguousarray(self._der(par, x, which_der)['Q'][:N, N:]) * self._scaled(par, scaling, 2)
+
+    def exp_x_dkxdkx(self, par, x, scaling=False, which_der=None):
+        """E_x[k_df(x_n, x) k_fd(x, x_m)], (Nd D, Nd D)."""
+        N = np.shape(x)[1]
+        return np.ascontiguousarray(self._der(par, x, which_der)['Q'][N:, N:]) * self._scaled(par, scaling, 2)
+
+
 STUDENT_MC_MAX_DIM, STUDENT_MC_MAX_PTS = 16, 128
 _STUDENT_MC_RANGE = ("the 'rbf-student' expectations on the device support D <= 16 inputs, N <= 128 points, "
                      "1 <= num_samples < 2^31 and dof > 0")

@@ -19,7 +19,8 @@ import numpy as np
 from .. import _lib
 from ..mtran import (SphericalRadialTransform, UnscentedTransform, GaussHermiteTransform,
                      FullySymmetricStudentTransform)
-from .bqkern import RBFGauss, RBFStudent, device_gp_weights, device_student_weights
+from .bqkern import (RBFGauss, RBFStudent, RBFGaussDer, device_gp_weights, device_student_weights, device_gpqd_weights,
+                     check_which_der)
 
 
 def n_sum_k(n, k):
@@ -396,6 +397,48 @@ class GaussianProcessModel(Model):
         """bq/bqmod.py:530-535."""
         par = self.kernel.get_parameters(par)
         return float(self._device_weights(par)['integral_var'][0])
+
+
+class GaussianProcessDerModel(GaussianProcessModel):
+    """GP model with derivative observations at the points `which_der` (research/gpqd/gpqd_base.py: GaussianProcessDerModel): a
+    strictly increasing index array into the sigma points, None = all of them, empty = none (the plain GP quadrature weights).
+    `bq_weights` takes any subset - the reference's is consistent for all points only.  D <= 6, 2 <= N <= 2 D + 1."""
+
+    _supported_kernels_ = ['rbf-d']
+
+    def __init__(self, dim, kern_par, point_str, point_par=None, estimate_par=False, which_der=None):
+        super().__init__(dim, kern_par, 'rbf', point_str, point_par, estimate_par)
+        self.which_der = check_which_der(self.dim_in, self.num_pts, which_der)
+        self.kernel = RBFGaussDer(dim, kern_par)
+
+    def bq_weights(self, par, *args):
+        """(wm (M,), Wc (M, M) symmetrised, Wcc (D, M), model_var, integral_var), M = N + Nd D, on the device (`ssmq_weights_gpqd`)."""
+        par = self.kernel.get_parameters(par)
+        w = device_gpqd_weights(self.points, par, self.which_der, self.kernel.jitter)
+        self.q, self.Q, self.R, self.iK = w['q'], w['Q'], w['R'], w['iK']
+        self.model_var, self.integral_var = w['model_var'], w['integral_var']
+        return w['wm'], w['Wc'], w['Wcc'], self.model_var, self.integral_var
+
+    def exp_model_variance(self, par, *args):
+        """alpha^2 (1 - tr(Q~ iK)) with iK the inverse of the SCALED joint kernel matrix, as GaussianProcessModel's."""
+        par = self.kernel.get_parameters(par)
+        iK = self.kernel.eval_inv_dot(par, self.points, which_der=self.which_der)
+        Q = device_gpqd_weights(self.points, par, self.which_der, self.kernel.jitter)['Q']
+        return float(self.kernel.exp_x_kxx(par) * (1 - np.trace(Q.dot(iK))))
+
+    def integral_variance(self, par, *args):
+        par = self.kernel.get_parameters(par)
+        return device_gpqd_weights(self.points, par, self.which_der, self.kernel.jitter)['integral_var']
+
+    def _not_implemented(self, what):
+        raise NotImplementedError('GaussianProcessDerModel.{} is not implemented (nor in the reference: its marginal likelihood and '
+                                  'predictive moments are those of the model without derivatives)'.format(what))
+
+    def optimize(self, *args, **kwargs):
+        self._not_implemented('optimize')
+
+    def predict(self, *args, **kwargs):
+        self._not_implemented('predict')
 
 
 class StudentTProcessModel(GaussianProcessModel):

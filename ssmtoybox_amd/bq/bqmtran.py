@@ -10,11 +10,11 @@ import ctypes
 import numpy as np
 
 from .. import _lib
-from ..mtran import MomentTransform, _DeviceApply, DeviceTransform
+from ..mtran import MomentTransform, _DeviceApply, DeviceTransform, resolve_integrand
 from .._lib import FORM_BQ, EMV_DIAG, EMV_BROADCAST
-from ..ssmod import user_unsupported, is_user_model
+from ..ssmod import user_unsupported, is_user_model, has_device_jacobian
 from .bqmod import (GaussianProcessModel, StudentTProcessModel, BayesSardModel, GaussianProcessMO, StudentTProcessMO,
-                    check_mo_range)
+                    GaussianProcessDerModel, check_mo_range)
 
 
 class BQTransform(_DeviceApply, MomentTransform):
@@ -94,6 +94,115 @@ class GaussianProcessTransform(BQTransform):
         super().__init__(dim_in, dim_out, kern_par, 'gp', kern_str, point_str, point_par, estimate_par)
         self._set_kernel_attributes(kern_attr)
         self.wm, self.Wc, self.Wcc = self.weights(kern_par)
+
+
+class GaussianProcessDerTransform(BQTransform):
+    """GP quadrature with derivative observations at the sigma points (research/gpqd/gpqd_base.py: GaussianProcessDerTransform,
+    the MLSP-2016 moment transform): the GP is conditioned on the integrand's values at all N sigma points and on its Jacobians
+    at the points `which_der` (strictly increasing indices, None = all, empty = none).  With L = chol(cov), x_n = mean + L xi_n
+    the observation vector of output e is
+
+        [f_e(x_1) .. f_e(x_N) | (J(x) L)[e, :] at which_der[0] | (J(x) L)[e, :] at which_der[1] | ..],     M = N + Nd D entries,
+
+    and the moments are BQTransform's on that (E, M) matrix: mean_f = fx wm, cov_f = fx Wc fx' - mean_f mean_f' + model_var I,
+    cov_fx = fx Wcc' L' - (E, D).  Three deliberate departures from the reference: the derivative observation is
+    J L, the derivative in the unit coordinates the GP lives in (the reference takes J, right for cov = I only); row e of the
+    observation matrix holds output e (the reference's reshape is right for one output only); every kernel expectation honours
+    `which_der` (the reference's weights fail on a proper subset).  At one output, cov = I and all derivatives the two agree.
+
+    One launch per batch: `k_apply_gpqd` (dim_in <= 2, observations in registers) or `k_apply_gpqd_lds` (observations in LDS).
+    Supported: dim_in <= 6, 2 <= N <= 2 dim_in + 1 points ('ut', 'sr', 'gh' where it fits), outputs <= max(dim_in, 4); `f` the
+    bound dyn_eval / meas_eval of a built-in model that has a Jacobian and additive noise (UNGM, pendulum, constant velocity and
+    their measurement models) or of a model of your own with `device_code` and `device_jacobian` (compiled at run time).
+    Everything else raises NotImplementedError naming this range, before the library is touched.  `wm`, `Wc`, `Wcc` and
+    `model.model_var` may be replaced after construction; the next call picks them up."""
+
+    _RANGE = ('GaussianProcessDerTransform supports dim_in <= 6, 2 <= N <= 2 dim_in + 1 points, 1 <= outputs <= max(dim_in, 4) and the '
+              'bound dyn_eval / meas_eval of a built-in model with a Jacobian and additive noise (UNGM, pendulum, constant velocity) or '
+              'of a model with device_code and device_jacobian')
+    _BUILTIN = (_lib.F_UNGM_DYN, _lib.F_UNGM_MEAS, _lib.F_PENDULUM_DYN, _lib.F_PENDULUM_MEAS, _lib.F_CV_DYN)
+
+    def __init__(self, dim_in, dim_out, kern_par, point_str='ut', point_par=None, estimate_par=False, which_der=None):
+        if not (1 <= int(dim_in) <= 6 and 1 <= int(dim_out) <= max(int(dim_in), 4)):
+            raise NotImplementedError('{} (got dim_in = {}, dim_out = {})'.format(self._RANGE, dim_in, dim_out))
+        try:
+            self.model = GaussianProcessDerModel(dim_in, kern_par, point_str, point_par, estimate_par, which_der)
+        except NotImplementedError as e:
+            raise NotImplementedError('{} ({})'.format(self._RANGE, e))
+        self.e = int(dim_out)
+        self.I_out = np.eye(dim_out)
+        self._dev = {}
+        self.wm, self.Wc, self.Wcc = self.weights(kern_par)
+
+    def _device_integrand(self, f):
+        """(Integrand, E) of a supported `f`; every refusal is raised here, before the library is touched."""
+        owner = getattr(f, '__self__', None)
+        if is_user_model(owner) and not has_device_jacobian(owner):
+            raise user_unsupported('GaussianProcessDerTransform (model Jacobians: give the model a device_jacobian)')
+        dev = resolve_integrand(f)
+        if dev is None:
+            raise NotImplementedError('not an arbitrary Python callable: ' + self._RANGE)
+        if not getattr(owner, 'noise_additive', True):
+            raise NotImplementedError('not a model with non-additive noise: ' + self._RANGE)
+        integ, E = dev
+        if integ.id < _lib.F_USER_FIRST and integ.id not in self._BUILTIN:
+            raise NotImplementedError('{} has no Jacobian on the device: {}'.format(type(owner).__name__, self._RANGE))
+        if not 1 <= E <= max(self.model.dim_in, 4):
+            raise NotImplementedError('{} (got {} outputs)'.format(self._RANGE, E))
+        return integ, E
+
+    def _handle_for(self, E):
+        D, N = self.model.points.shape
+        wd = self.model.which_der
+        M = N + wd.size * D
+        arrs = [np.ascontiguousarray(a, dtype=np.float64) for a in (self.wm, self.Wc, self.Wcc)]
+        if arrs[0].shape != (M,) or arrs[1].shape != (M, M) or arrs[2].shape != (D, M):
+            raise ValueError('wm / Wc / Wcc must be (M,), (M, M), (D, M) with M = N + Nd D = {}'.format(M))
+        mv = float(self.model.model_var)
+        snap = (mv, wd.tobytes()) + tuple(a.tobytes() for a in arrs)
+        have = self._dev.get(E)
+        if have is not None and have[1] == snap:
+            return have[0]
+        lib = _lib.load()
+        ptr = [a.ctypes.data_as(_lib.c_double_p) for a in arrs]
+        pwd = wd.ctypes.data_as(_lib.c_int32_p)
+        if have is not None:
+            _lib.check(lib.ssmq_transform_gpqd_set(ctypes.c_void_p(have[0]), int(wd.size), pwd, ptr[0], ptr[1], ptr[2], mv),
+                       'ssmq_transform_gpqd_set')
+            h = have[0]
+        else:
+            h = lib.ssmq_transform_create_gpqd(D, int(E), N, _lib.as_c(self.model.points)[1], int(wd.size), pwd, ptr[0], ptr[1], ptr[2], mv)
+            if not h:
+                raise _lib.SsmqError('ssmq_transform_create_gpqd failed: ' + _lib.last_error())
+        self._dev[E] = (h, snap)
+        return h
+
+    def kernel_name(self, f):
+        self._device_integrand(f)
+        return super().kernel_name(f)
+
+    def apply_batch(self, f, mean, cov, time=None, fcn_pars=None, return_status=False):
+        """B transforms in one launch: mean (B, D), cov (B, D, D), time scalar or (B,) -> (B, E), (B, E, E), (B, E, D)."""
+        self._device_integrand(f)
+        if np.ndim(mean) != 2 or np.shape(mean)[1] != self.model.dim_in:
+            raise ValueError('mean must have shape (B, dim_in) with dim_in = {}'.format(self.model.dim_in))
+        return super().apply_batch(f, mean, cov, time=0.0 if time is None else time, fcn_pars=fcn_pars, return_status=return_status)
+
+    def apply_batch_dev(self, f, *args, **kwargs):
+        self._device_integrand(f)
+        return super().apply_batch_dev(f, *args, **kwargs)
+
+    def _fixed_outputs(self):
+        return self.e
+
+    def __del__(self):
+        try:
+            lib = _lib.load()
+            for h, _ in getattr(self, '_dev', {}).values():
+                lib.ssmq_transform_destroy(ctypes.c_void_p(h))
+            self._dev = {}
+        except Exception:
+            pass
 
 
 class BayesSardTransform(BQTransform):

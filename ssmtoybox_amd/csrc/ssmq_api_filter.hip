@@ -151,6 +151,10 @@ int filter_forward_impl(ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, ssmq
     if (trunc && h_dyn->form != SSMQ_FORM_SIGMA) return refuse_trunc("filter whose dynamics transform is not a sigma-point rule");
     if (trunc && user) return refuse_user_integrand("truncated sigma-point transform (k_apply_trunc)");
     if (trunc && (sscale || student_dof != 0.0)) return refuse_trunc("Studentian filter");
+    // GPQ with derivative observations: both transforms of this form, the Gaussian launch loop (forward pass and smoother)
+    const bool gq = is_gpqd(h_dyn) || is_gpqd(h_obs);
+    if (gq && !(is_gpqd(h_dyn) && is_gpqd(h_obs))) return refuse_gpqd("filter with only one GPQ+D transform");
+    if (gq && (sscale || student_dof != 0.0)) return refuse_gpqd("Studentian filter");
     int rc = ensure_device();
     if (rc) return rc;
     if (B == 0) return SSMQ_OK;
@@ -173,7 +177,7 @@ int filter_forward_impl(ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, ssmq
     // Taylor-GPQD: no time-loop kernel reads a Jacobian), each transform of a user member a launch of the kernel compiled for it.
     // Those kernels are compiled and loaded here, before the loop is captured, and a member without a Jacobian is refused here.
     auto jac_form = [](const ssmq_transform *h) { return h->form == SSMQ_FORM_TAYLOR1 || is_taylor_gpqd(h); };
-    const bool user_ekf = user && jac_form(h_dyn) && jac_form(h_obs);
+    const bool user_ekf = user && ((jac_form(h_dyn) && jac_form(h_obs)) || gq);
     if (user && !user_ekf) return (rc = rtc_launch_fused(pass)) < 0 ? rc : SSMQ_OK;
     if (user_ekf) {
         const ssmq_transform *hs2[2] = {h_dyn, h_obs};
@@ -182,7 +186,7 @@ int filter_forward_impl(ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, ssmq
             FInfo fi;
             if ((rc = check_integrand(hs2[i], fs2[i], &fi))) return rc;
             if (is_user_integrand(fs2[i])) {
-                if ((rc = rtc_prepare_jacobian(hs2[i], fs2[i]))) return rc;
+                if ((rc = gq ? rtc_prepare_gpqd(hs2[i], fs2[i]) : rtc_prepare_jacobian(hs2[i], fs2[i]))) return rc;
             } else if (!integrand_has_jacobian(fs2[i]->id)) {
                 set_error("filter_forward: built-in integrand " + std::to_string(fs2[i]->id) + " has no Jacobian (its dyn_fcn_dx / meas_fcn_dx "
                           "returns None in the reference too)");
@@ -213,12 +217,12 @@ int filter_forward_impl(ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, ssmq
     // one fused kernel for the whole time loop when this (models, shapes, form) combination has one (it does not keep
     // the predictive moments, so a pass that has to store them for the smoother takes the launch loop)
     const bool keep_pred = d_pm && d_pP && d_pC;
-    if (!ssmq::sw("SSMQ_NO_FUSED") && !keep_pred && !mo && !user_ekf && !trunc) {
+    if (!ssmq::sw("SSMQ_NO_FUSED") && !keep_pred && !mo && !user_ekf && !trunc && !gq) {
         rc = try_launch_fused(pass);
         if (rc < 0) return rc;
         if (rc == 1) return SSMQ_OK;
     }
-    if (!ssmq::sw("SSMQ_NO_FUSED") && keep_pred && !sscale && student_dof == 0.0 && !trunc) {
+    if (!ssmq::sw("SSMQ_NO_FUSED") && keep_pred && !sscale && student_dof == 0.0 && !trunc && !gq) {
         // smoother: the time loop in one kernel that also leaves the predictive moments of every step in HBM (the extended Kalman
         // filter's k_ekf_loop, or the sigma-point / BQ kernel)
         if (!mo && !user_ekf) {
@@ -301,6 +305,7 @@ static int filter_forward_aug_impl(ssmq_transform *h_dyn, const ssmq_integrand *
     if (is_user_integrand(f_dyn) || is_user_integrand(f_obs)) return refuse_user_integrand("filter with non-additive noise (augmented moments)");
     if (is_mo(h_dyn) || is_mo(h_obs)) return refuse_mo("filter with non-additive noise (augmented moments)");
     if (is_trunc(h_dyn) || is_trunc(h_obs)) return refuse_trunc("filter with non-additive noise (augmented moments)");
+    if (is_gpqd(h_dyn) || is_gpqd(h_obs)) return refuse_gpqd("filter with non-additive noise (augmented moments)");
     if (!h_dyn || !h_obs || !f_dyn || !f_obs || dim_state <= 0 || dq < 0 || dr < 0 || B < 0 || ld < B || T < 0 || !d_y ||
         !d_m0 || !d_P0 || !d_fm || !d_fP || !d_status || (dq > 0 && (!q_mean || !q_cov)) ||
         (dr > 0 && (!r_mean || !r_cov))) {
@@ -453,6 +458,7 @@ extern "C" int ssmq_filter_smooth_aug_dev(ssmq_transform *h_dyn, const ssmq_inte
     SSMQ_HANDLE_LOCK(h_dyn, h_obs);
     if (is_mo(h_dyn) || is_mo(h_obs)) return refuse_mo("ssmq_filter_smooth_aug_dev");
     if (is_trunc(h_dyn) || is_trunc(h_obs)) return refuse_trunc("ssmq_filter_smooth_aug_dev");
+    if (is_gpqd(h_dyn) || is_gpqd(h_obs)) return refuse_gpqd("ssmq_filter_smooth_aug_dev");
     if (!h_dyn || !d_sm || !d_sP || dim_state <= 0 || dq < 0 || B < 0 || T < 0 || ld < B) {
         set_error("filter_smooth_aug: bad argument");
         return SSMQ_E_ARG;
@@ -546,6 +552,7 @@ extern "C" int ssmq_student_filter_forward_dev(ssmq_transform *h_dyn, const ssmq
     SSMQ_HANDLE_LOCK(h_dyn, h_obs);
     if (is_mo(h_dyn) || is_mo(h_obs)) return refuse_mo("ssmq_student_filter_forward_dev");
     if (is_trunc(h_dyn) || is_trunc(h_obs)) return refuse_trunc("ssmq_student_filter_forward_dev");
+    if (is_gpqd(h_dyn) || is_gpqd(h_obs)) return refuse_gpqd("ssmq_student_filter_forward_dev");
     if (!scale || !(dof > 0.0)) {
         set_error("student_filter_forward: scale[T] and dof > 0 are required");
         return SSMQ_E_ARG;
@@ -577,7 +584,9 @@ extern "C" int ssmq_filter_kernel_name_batch(const ssmq_transform *h_dyn, const 
     if (is_trunc(h_dyn)) return refuse_trunc("filter with a truncated DYNAMICS transform");
     if (is_trunc(h_obs) && h_dyn->form != SSMQ_FORM_SIGMA) return refuse_trunc("filter whose dynamics transform is not a sigma-point rule");
     if (is_trunc(h_obs) && user) return refuse_user_integrand("truncated sigma-point transform (k_apply_trunc)");
-    rc = mo || is_trunc(h_obs) || (user && ekf) || (ssmq::sw("SSMQ_NO_FUSED") && !user) ? 0 : try_launch_fused(query);
+    const bool gq = is_gpqd(h_dyn) || is_gpqd(h_obs);      // (both, or filter_forward_impl refuses: the launch loop)
+    if (gq && !(is_gpqd(h_dyn) && is_gpqd(h_obs))) return refuse_gpqd("filter with only one GPQ+D transform");
+    rc = mo || gq || is_trunc(h_obs) || (user && ekf) || (ssmq::sw("SSMQ_NO_FUSED") && !user) ? 0 : try_launch_fused(query);
     if (rc < 0) return rc;
     snprintf(buf, len, "%s", rc == 1 ? name : "hipGraph of 3 T launches (apply dyn | apply obs | k_kalman_update)");
     return SSMQ_OK;

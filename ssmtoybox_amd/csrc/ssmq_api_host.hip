@@ -223,6 +223,7 @@ int ssmq_sigma_points_batch(ssmq_transform *h, int64_t B, const double *mean, co
     }
     if (is_taylor_gpqd(h)) return refuse_taylor_gpqd("ssmq_sigma_points_batch");
     if (is_trunc(h)) return refuse_trunc("ssmq_sigma_points_batch");
+    if (is_gpqd(h)) return refuse_gpqd("ssmq_sigma_points_batch");
     if (!h || B < 0 || !mean || !cov || !x || !chol) return SSMQ_E_ARG;
     int rc = ensure_device();
     if (rc) return rc;
@@ -280,6 +281,7 @@ int ssmq_apply_fx_batch(ssmq_transform *h, int64_t B, const double *chol, const 
     }
     if (is_taylor_gpqd(h)) return refuse_taylor_gpqd("ssmq_apply_fx_batch");
     if (is_trunc(h)) return refuse_trunc("ssmq_apply_fx_batch");
+    if (is_gpqd(h)) return refuse_gpqd("ssmq_apply_fx_batch");
     if (!h || B < 0 || !chol || !fx || !mean_f || !cov_f || !cov_fx) return SSMQ_E_ARG;
     if (h->form == SSMQ_FORM_SIGMA && (!mean || !x)) {
         set_error("apply_fx_batch: the centred form needs mean and x");
@@ -418,6 +420,7 @@ int ssmq_fxwc_batch_dev(ssmq_transform *h, int64_t M, const double *d_fx, int64_
     }
     if (is_taylor_gpqd(h)) return refuse_taylor_gpqd("ssmq_fxwc_batch_dev");
     if (is_trunc(h)) return refuse_trunc("ssmq_fxwc_batch_dev");
+    if (is_gpqd(h)) return refuse_gpqd("ssmq_fxwc_batch_dev");
     if (!h || M < 0 || (M > 0 && (!d_fx || !d_t))) {
         set_error("fxwc_batch: bad argument");
         return SSMQ_E_ARG;

@@ -88,6 +88,8 @@ extern "C" int ssmq_filter_forward_multi_dev(int n_jobs, const ssmq_filter_job *
     for (int i = 0; i < n_jobs; ++i)
         if (is_trunc(jobs[i].h_dyn) || is_trunc(jobs[i].h_obs)) return refuse_trunc("ssmq_filter_forward_multi_dev");
     for (int i = 0; i < n_jobs; ++i)
+        if (is_gpqd(jobs[i].h_dyn) || is_gpqd(jobs[i].h_obs)) return refuse_gpqd("ssmq_filter_forward_multi_dev");
+    for (int i = 0; i < n_jobs; ++i)
         if (is_taylor_gpqd(jobs[i].h_dyn) || is_taylor_gpqd(jobs[i].h_obs)) return refuse_taylor_gpqd("ssmq_filter_forward_multi_dev");
     std::vector<const ssmq_transform *> hs;
     for (int i = 0; i < n_jobs; ++i) {
@@ -455,6 +457,7 @@ extern "C" int ssmq_filter_forward_piped(ssmq_transform *h_dyn, const ssmq_integ
     if (is_user_integrand(f_dyn) || is_user_integrand(f_obs)) return refuse_user_integrand("ssmq_filter_forward_piped");
     if (is_mo(h_dyn) || is_mo(h_obs)) return refuse_mo("ssmq_filter_forward_piped");
     if (is_trunc(h_dyn) || is_trunc(h_obs)) return refuse_trunc("ssmq_filter_forward_piped (no time-block kernel)");
+    if (is_gpqd(h_dyn) || is_gpqd(h_obs)) return refuse_gpqd("ssmq_filter_forward_piped (no time-block kernel)");
     if (is_taylor_gpqd(h_dyn) || is_taylor_gpqd(h_obs)) return refuse_taylor_gpqd("ssmq_filter_forward_piped (no time-block kernel)");
     SSMQ_HANDLE_LOCK(h_dyn, h_obs);
     if (!h_dyn || !h_obs || !f_dyn || !f_obs || B < 0 || T < 0 || !y || !m0 || !P0 || !fm || !fP || !status || n_blocks < 0) {

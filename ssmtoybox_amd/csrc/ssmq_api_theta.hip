@@ -50,6 +50,7 @@ extern "C" int ssmq_gp_theta_step(ssmq_transform *h_dyn, const ssmq_integrand *f
     if (is_user_integrand(f_dyn) || is_user_integrand(f_obs)) return refuse_user_integrand("ssmq_gp_theta_step");
     if (is_mo(h_dyn) || is_mo(h_obs)) return refuse_mo("ssmq_gp_theta_step");
     if (is_trunc(h_dyn) || is_trunc(h_obs)) return refuse_trunc("ssmq_gp_theta_step");
+    if (is_gpqd(h_dyn) || is_gpqd(h_obs)) return refuse_gpqd("ssmq_gp_theta_step");
     if (is_taylor_gpqd(h_dyn) || is_taylor_gpqd(h_obs)) return refuse_taylor_gpqd("ssmq_gp_theta_step");
     SSMQ_HANDLE_LOCK(h_dyn, h_obs);
     return gp_theta_step_impl(h_dyn, f_dyn, h_obs, f_obs, P, par_dyn, par_obs, jitter, mean, cov, shared_state, y, shared_y, time,
@@ -66,6 +67,7 @@ extern "C" int ssmq_gp_theta_step_times(ssmq_transform *h_dyn, const ssmq_integr
     if (is_user_integrand(f_dyn) || is_user_integrand(f_obs)) return refuse_user_integrand("ssmq_gp_theta_step_times");
     if (is_mo(h_dyn) || is_mo(h_obs)) return refuse_mo("ssmq_gp_theta_step_times");
     if (is_trunc(h_dyn) || is_trunc(h_obs)) return refuse_trunc("ssmq_gp_theta_step_times");
+    if (is_gpqd(h_dyn) || is_gpqd(h_obs)) return refuse_gpqd("ssmq_gp_theta_step_times");
     if (is_taylor_gpqd(h_dyn) || is_taylor_gpqd(h_obs)) return refuse_taylor_gpqd("ssmq_gp_theta_step_times");
     SSMQ_HANDLE_LOCK(h_dyn, h_obs);
     if (!times) {

@@ -471,6 +471,24 @@ int apply_dev_impl(ssmq_transform *h, const ssmq_integrand *f, int64_t B, int64_
         a.fp.ttab = ttab;
         return launch_apply_trunc(h, f, a, stream());
     }
+    if (is_gpqd(h)) {
+        // GPQ with derivative observations: one launch (ssmq_apply_gpqd.hip) - for a user integrand, which must have been registered
+        // with its Jacobian, of a kernel compiled for it at run time
+        const bool user = is_user_integrand(f);
+        if (user && !user_integrand_has_jacobian(f->id)) return refuse_user_integrand("GPQ+D transform (k_apply_gpqd) without a Jacobian");
+        const bool dry = dry_run || B <= 0;
+        LinArgs a;
+        memset(&a, 0, sizeof(a));
+        if (!dry) {
+            if (null_args()) return SSMQ_E_ARG;
+            a.mean = d_mean; a.cov = d_cov; a.time = d_time; a.time_stride = d_time ? time_stride : 0; a.cov_add = d_cov_add;
+            a.mean_f = d_mean_f; a.cov_f = d_cov_f; a.cov_fx = d_cov_fx; a.status = d_status; a.B = B; a.ld = ld;
+            a.cov_scale = cov_scale; a.ccov_scale = ccov_scale;
+            fill_fpar(f, &a.fp);
+            if (!user) a.fp.ttab = ttab;
+        }
+        return launch_apply_gpqd(h, fi.din, f, a, stream(), kernel_name, dry);
+    }
     // argument block of the register-resident kernels; fp.ttab stays null (the table route sets it, the user route has no table)
     auto fill_args = [&](ApplyArgs &a) {
         a.mean = d_mean; a.cov = d_cov; a.time = d_time ? d_time : d_mean; a.mean_f = d_mean_f; a.cov_f = d_cov_f;
@@ -739,6 +757,7 @@ int ssmq_transform_update(ssmq_transform *h, const double *xi, const double *wm,
     SSMQ_HANDLE_LOCK(h);
     if (is_mo(h)) return refuse_mo("ssmq_transform_update (use ssmq_transform_update_mo)");
     if (is_trunc(h)) return refuse_trunc("ssmq_transform_update (recreate the handle)");
+    if (is_gpqd(h)) return refuse_gpqd("ssmq_transform_update (use ssmq_transform_gpqd_set)");
     if (h && h->form == SSMQ_FORM_TAYLOR1) {
         set_error("transform_update: the linearisation transform has no constants");
         return SSMQ_E_ARG;
@@ -771,6 +790,7 @@ void ssmq_transform_destroy(ssmq_transform *h) {
     }   // ... and nobody may hold the handle any more: destroying it while another thread uses it is the caller's error
     if (h->d_mo) hipFree(h->d_mo);
     if (h->d_trunc) hipFree(h->d_trunc);
+    if (h->d_gpqd) hipFree(h->d_gpqd);
     if (h->d_small) hipFree(h->d_small);
     if (h->d_wide) hipFree(h->d_wide);
     if (h->d_wc_pad) hipFree(h->d_wc_pad);

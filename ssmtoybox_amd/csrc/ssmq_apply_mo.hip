@@ -353,6 +353,7 @@ int ssmq_transform_update_mo(ssmq_transform *h, const double *xi, const double *
     if (!h) return SSMQ_E_ARG;
     if (is_taylor_gpqd(h)) return refuse_taylor_gpqd("ssmq_transform_update_mo");
     if (is_trunc(h)) return refuse_trunc("ssmq_transform_update_mo");
+    if (is_gpqd(h)) return refuse_gpqd("ssmq_transform_update_mo");
     if (!is_mo(h)) {
         set_error("transform_update_mo: not a multi-output transform");
         return SSMQ_E_ARG;

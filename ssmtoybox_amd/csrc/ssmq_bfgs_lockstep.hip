@@ -201,6 +201,7 @@ extern "C" int ssmq_gp_marginal_laplace_batch(ssmq_transform *h_dyn, const ssmq_
     if (is_user_integrand(f_dyn) || is_user_integrand(f_obs)) return refuse_user_integrand("ssmq_gp_marginal_laplace_batch");
     if (is_mo(h_dyn) || is_mo(h_obs)) return refuse_mo("ssmq_gp_marginal_laplace_batch");
     if (is_trunc(h_dyn) || is_trunc(h_obs)) return refuse_trunc("ssmq_gp_marginal_laplace_batch");
+    if (is_gpqd(h_dyn) || is_gpqd(h_obs)) return refuse_gpqd("ssmq_gp_marginal_laplace_batch");
     if (is_taylor_gpqd(h_dyn) || is_taylor_gpqd(h_obs)) return refuse_taylor_gpqd("ssmq_gp_marginal_laplace_batch");
     SSMQ_HANDLE_LOCK(h_dyn, h_obs);
     if (!h_dyn || !h_obs || !f_dyn || !f_obs || B < 0 || (B > 0 && (!mean || !cov || !y || !prior_mean || !prior_cov || !theta ||

@@ -46,6 +46,11 @@ struct ssmq_transform {
     // (trunc_layout), d_small / d_wide stay null and no host copies are kept (the handle is recreated when its constants change)
     int tr_deff = 0, tr_neff = 0;
     double *d_trunc = nullptr;
+    // GPQ+D form (SSMQ_FORM_GPQD, ssmq_apply_gpqd_kernel.h): N points of which those in gq_mask carry a derivative observation;
+    // d_gpqd is the one constant block (gpqd_layout: the weights expanded to the full layout), xi the host copy of the points,
+    // d_small / d_wide stay null
+    double *d_gpqd = nullptr;
+    uint32_t gq_mask = 0;
     uint32_t generation = 0;   // bumped by every upload of constants (create / update)
     // Threads (include/ssmq.h, conventions): every entry point that takes this handle holds `mu` for its duration; `owner` /
     // `owner_epoch` name the thread context (its stream) that used the handle last - another context waits for that stream
@@ -216,6 +221,20 @@ inline bool is_trunc(const ssmq_transform *h) { return h && h->form == SSMQ_FORM
 int refuse_trunc(const char *what);   // sets the error text, returns SSMQ_E_UNSUPPORTED
 bool trunc_range_ok(int D, int D_eff, int E, int N_eff, int N);   // 1 <= D_eff <= D <= 6, 1 <= E <= 4, 1 <= N_eff, N <= 729
 struct TruncArgs;                     // ssmq_apply_trunc.hip
+// the GPQ+D form (ssmq_apply_gpqd.hip): a block of its own - it runs through ssmq_apply_batch[_dev] and the launch loop of the
+// additive-noise filter and smoother, every other entry point refuses it
+inline bool is_gpqd(const ssmq_transform *h) { return h && h->form == SSMQ_FORM_GPQD; }
+int refuse_gpqd(const char *what);   // sets the error text, returns SSMQ_E_UNSUPPORTED
+bool gpqd_range_ok(int D, int E, int N);   // D <= 6, E <= max(D, 4), 2 <= N <= 2 D + 1
+struct GpqdArgs;                      // ssmq_apply_gpqd_kernel.h
+struct LinArgs;                       // ssmq_jacobian_kernel.h
+// `planes` as for launch_jacobian; a built-in model runs k_apply_gpqd<> / k_apply_gpqd_lds<>, a user integrand registered with a
+// Jacobian the same kernels compiled for it at run time (ssmq_rtc.hip: rtc_launch_gpqd; rtc_prepare_gpqd compiles and loads without
+// launching, for a stream that is about to be captured).  SSMQ_OK (launched, or with dry_run the name set) or < 0.
+int launch_apply_gpqd(const ssmq_transform *h, int din, const ssmq_integrand *f, const LinArgs &planes, hipStream_t s,
+                      const char **name = nullptr, bool dry_run = false);
+int rtc_launch_gpqd(const ssmq_integrand *f, const GpqdArgs &a, bool lds, hipStream_t s, const char **name, bool dry_run);
+int rtc_prepare_gpqd(const ssmq_transform *h, const ssmq_integrand *f);
 // `planes`: the planes, the time argument, cov_add, B, ld and the hooks of one application (a LinArgs, as for launch_jacobian); the
 // rest of the argument block comes from the handle and the integrand.  SSMQ_OK or < 0.
 struct LinArgs;
@@ -458,8 +477,8 @@ inline void key_bytes(std::vector<uint64_t> &key, const void *p, size_t n) {
 inline void key_of_pair(std::vector<uint64_t> &key, const ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, const ssmq_transform *h_obs,
                         const ssmq_integrand *f_obs) {
     for (const ssmq_transform *h : {h_dyn, h_obs}) {
-        for (const void *p : {(const void *)h, (const void *)h->d_small, (const void *)h->d_mo, (const void *)h->d_trunc}) key.push_back((uint64_t)(uintptr_t)p);
-        for (int v : {h->D, h->E, h->N, h->form, h->emv_mode, h->opt_mask, h->np_pad, (int)h->generation}) key.push_back((uint64_t)(uint32_t)v);
+        for (const void *p : {(const void *)h, (const void *)h->d_small, (const void *)h->d_mo, (const void *)h->d_trunc, (const void *)h->d_gpqd}) key.push_back((uint64_t)(uintptr_t)p);
+        for (int v : {h->D, h->E, h->N, h->form, h->emv_mode, h->opt_mask, h->np_pad, (int)h->generation, (int)h->gq_mask}) key.push_back((uint64_t)(uint32_t)v);
         key_bytes(key, &h->tp_nu, 8);
     }
     key_bytes(key, f_dyn, sizeof(ssmq_integrand));
@@ -469,10 +488,10 @@ inline void key_of_pair(std::vector<uint64_t> &key, const ssmq_transform *h_dyn,
 // (ssmq_filter_fused.hip).  A route states what it sets differently next to its launch.
 FusedArgs fused_args(const FilterPass &p);
 // both transforms of one form (sigma-point, BQ or t-process BQ), a measurement index pattern the kernels know, no state index list;
-// the Taylor-GPQD and the truncated sigma-point form are no family by name: no time-loop kernel (fused, strips, quad, wave split,
+// the Taylor-GPQD, the truncated sigma-point and the GPQ+D form are no family by name: no time-loop kernel (fused, strips, quad, wave split,
 // time blocks) reads their parameters
 inline bool same_family(const FilterPass &p) {
-    return !is_taylor_gpqd(p.hd) && !is_taylor_gpqd(p.ho) && !is_trunc(p.hd) && !is_trunc(p.ho) && p.hd->form == p.ho->form && (p.hd->tp_nu > 0.0) == (p.ho->tp_nu > 0.0) && p.sel_obs >= 0 && p.fd->n_idx <= 0;
+    return !is_gpqd(p.hd) && !is_gpqd(p.ho) && !is_taylor_gpqd(p.hd) && !is_taylor_gpqd(p.ho) && !is_trunc(p.hd) && !is_trunc(p.ho) && p.hd->form == p.ho->form && (p.hd->tp_nu > 0.0) == (p.ho->tp_nu > 0.0) && p.sel_obs >= 0 && p.fd->n_idx <= 0;
 }
 // Integrands whose time dependence the fused loops read from a per-step table (time_table() in ssmq_device.h fills it); the kernels'
 // HasTimeTable<> (ssmq_fused.h) is checked against this function id by id in ssmq_filter_shapes.h.

@@ -220,6 +220,7 @@ extern "C" int ssmq_gp_marginal_filter_batch(ssmq_transform *h_dyn, const ssmq_i
     if (is_user_integrand(f_dyn) || is_user_integrand(f_obs)) return refuse_user_integrand("ssmq_gp_marginal_filter_batch");
     if (is_mo(h_dyn) || is_mo(h_obs)) return refuse_mo("ssmq_gp_marginal_filter_batch");
     if (is_trunc(h_dyn) || is_trunc(h_obs)) return refuse_trunc("ssmq_gp_marginal_filter_batch");
+    if (is_gpqd(h_dyn) || is_gpqd(h_obs)) return refuse_gpqd("ssmq_gp_marginal_filter_batch");
     if (is_taylor_gpqd(h_dyn) || is_taylor_gpqd(h_obs)) return refuse_taylor_gpqd("ssmq_gp_marginal_filter_batch");
     SSMQ_HANDLE_LOCK(h_dyn, h_obs);
     if (!h_dyn || !h_obs || !f_dyn || !f_obs || B < 0 || T < 0 || (B > 0 && T > 0 && (!y || !x0_mean || !x0_cov || !prior_mean ||

@@ -32,6 +32,7 @@
 #include "ssmq_filter_shapes.h"
 #include "ssmq_mc_moments.h"
 #include "ssmq_jacobian_kernel.h"
+#include "ssmq_apply_gpqd_kernel.h"
 
 namespace ssmq {
 
@@ -407,7 +408,7 @@ int rtc_launch_fused(const FilterPass &p) {
         return SSMQ_E_UNSUPPORTED;
     }
     if (hd->form != ho->form || (hd->tp_nu > 0.0) != (ho->tp_nu > 0.0) || p.sel_obs != 0 || hd->form == SSMQ_FORM_TAYLOR1 ||
-        is_taylor_gpqd(hd) || is_trunc(hd) || is_trunc(ho)) {
+        is_taylor_gpqd(hd) || is_trunc(hd) || is_trunc(ho) || is_gpqd(hd)) {
         set_error("user integrands: both transforms of one form (sigma-point or BQ), no linearisation, no state index");
         return SSMQ_E_UNSUPPORTED;
     }
@@ -450,7 +451,7 @@ int rtc_launch_apply(const ssmq_transform *h, const ssmq_integrand *f, int sel, 
         set_error(why);
         return SSMQ_E_UNSUPPORTED;
     }
-    if (sel != 0 || h->form == SSMQ_FORM_TAYLOR1 || is_taylor_gpqd(h) || is_trunc(h)) {
+    if (sel != 0 || h->form == SSMQ_FORM_TAYLOR1 || is_taylor_gpqd(h) || is_trunc(h) || is_gpqd(h)) {
         set_error("user integrands: sigma-point or BQ transforms only, no state index");
         return SSMQ_E_UNSUPPORTED;
     }
@@ -540,6 +541,58 @@ int rtc_prepare_jacobian(const ssmq_transform *h, const ssmq_integrand *f) {
     if (rc) return rc;
     hipFunction_t fn;
     return kernel_for(expr, jac_kernel(h->form).arg_type, ids, &fn);
+}
+
+// The GPQ+D kernel of a user integrand that has a Jacobian: k_apply_gpqd<id, D, E, DIN> (observations in registers) or
+// k_apply_gpqd_lds<id, D, E, DIN>, as launch_apply_gpqd chooses for the built-in models
+static int gpqd_expr(int D, int E, bool lds, const ssmq_integrand *f, std::string *expr, std::vector<int> *ids) {
+    int rc = check_user_pair(f, f, ids);
+    if (rc) return rc;
+    UserFn u;
+    if (!user_fn(f->id, &u)) {
+        set_error("integrand id " + std::to_string(f->id) + " is not a registered user integrand");
+        return SSMQ_E_ARG;
+    }
+    if (u.jac.empty()) {
+        set_error("GPQ+D: this model has no Jacobian (a user integrand gets one through ssmq_integrand_define_dx)");
+        return SSMQ_E_UNSUPPORTED;
+    }
+    if (!gpqd_range_ok(D, E, 2)) {
+        set_error("GPQ+D: user integrands run for D <= " + std::to_string(SSMQ_USER_MAX_D) + " and outputs <= max(D, " +
+                  std::to_string(SSMQ_USER_MAX_Y) + ") (got D = " + std::to_string(D) + ", E = " + std::to_string(E) + ")");
+        return SSMQ_E_UNSUPPORTED;
+    }
+    if (u.dout != E || u.din > D) {
+        set_error("GPQ+D: the user integrand's input / output dimensions do not match the transform");
+        return SSMQ_E_ARG;
+    }
+    char b[160];
+    snprintf(b, sizeof(b), "ssmq::%s<%d, %d, %d, %d>", lds ? "k_apply_gpqd_lds" : "k_apply_gpqd", f->id, D, E, u.din);
+    *expr = b;
+    return SSMQ_OK;
+}
+int rtc_launch_gpqd(const ssmq_integrand *f, const GpqdArgs &a0, bool lds, hipStream_t s, const char **name, bool dry_run) {
+    std::string expr;
+    std::vector<int> ids;
+    const int rc = gpqd_expr(a0.D, a0.E, lds, f, &expr, &ids);
+    if (rc) return rc;
+    GpqdArgs a = a0;
+    a.fp.ttab = nullptr;
+    const int ipw = gpqd_lds_items(a.D, a.E);      // grid and block as launch_apply_gpqd
+    return launch_compiled(expr, "ssmq::GpqdArgs", ids, &a, lds ? (unsigned)((a.B + ipw - 1) / ipw) : (unsigned)((a.B + 255) / 256),
+                           lds ? kGpqdLdsBlock : 256, s, name, dry_run, lds ? "k_apply_gpqd_lds" : "k_apply_gpqd");
+}
+int rtc_prepare_gpqd(const ssmq_transform *h, const ssmq_integrand *f) {
+    if (!is_gpqd(h)) {
+        set_error("rtc_prepare_gpqd: not a GPQ+D handle");
+        return SSMQ_E_ARG;
+    }
+    std::string expr;
+    std::vector<int> ids;
+    const int rc = gpqd_expr(h->D, h->E, h->D > kGpqdRegMaxD, f, &expr, &ids);
+    if (rc) return rc;
+    hipFunction_t fn;
+    return kernel_for(expr, "ssmq::GpqdArgs", ids, &fn);
 }
 
 // k_mc_moments<> for a user integrand (ssmq_mc_transform.hip has checked the range and filled `a0`): SSMQ_OK launched, or < 0
@@ -651,6 +704,20 @@ extern "C" int ssmq_rtc_compile_check(int32_t id, int32_t id_obs, int kind, int 
         int rc = jac_expr(jform, D, E, &f, &expr, &ids);
         if (rc) return rc;
         return compile_check_text(expr, jac_kernel(jform).arg_type, ids, arch, log, len);
+    }
+    if (kind == SSMQ_RTC_GPQD) {   // k_apply_gpqd[_lds]<id, D, E, DIN>: N, N_obs, form, tp and opt are not read
+        if (!arch || !*arch) {
+            set_error("ssmq_rtc_compile_check: bad argument");
+            return SSMQ_E_ARG;
+        }
+        ssmq_integrand f;
+        memset(&f, 0, sizeof(f));
+        f.id = id;
+        std::string expr;
+        std::vector<int> ids;
+        int rc = gpqd_expr(D, E, D > kGpqdRegMaxD, &f, &expr, &ids);
+        if (rc) return rc;
+        return compile_check_text(expr, "ssmq::GpqdArgs", ids, arch, log, len);
     }
     if (kind == SSMQ_RTC_MC) {   // k_mc_moments<id, D, E, 0>: N, N_obs, form, tp and opt are not read
         FInfo fm;

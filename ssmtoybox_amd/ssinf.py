@@ -24,7 +24,7 @@ from .mtran import (MomentTransform, LinearizationTransform, TaylorGPQDTransform
                     FullySymmetricStudentTransform, TruncatedUnscentedTransform, TruncatedSphericalRadialTransform,
                     TruncatedGaussHermiteTransform, resolve_integrand)
 from .bq.bqmtran import (GaussianProcessTransform, BayesSardTransform, StudentTProcessTransform,
-                         MultiOutputGaussianProcessTransform)
+                         MultiOutputGaussianProcessTransform, GaussianProcessDerTransform)
 from .ssmod import TransitionModel, MeasurementModel, is_user_model, has_device_jacobian, user_unsupported, check_user_points
 
 
@@ -306,6 +306,9 @@ def run_filters(algs, data, x0_mean=None, x0_cov=None, raise_on_failure=True):
         if isinstance(a, ExtendedKalmanGPQD):
             raise NotImplementedError('run_filters: not implemented for ExtendedKalmanGPQD (its forward pass is a launch loop that '
                                       'ssmq_filter_forward_multi_dev refuses by name)')
+        if isinstance(a, GaussianProcessDerKalman):
+            raise NotImplementedError('run_filters: not implemented for GaussianProcessDerKalman (its forward pass is a launch loop that '
+                                      'ssmq_filter_forward_multi_dev refuses by name)')
         if a.mod_obs.dim_out != Y:
             raise ValueError('run_filters: every filter must take the same measurements')
     d_y = _lib.scratch(8 * T * Y * ld)
@@ -477,6 +480,25 @@ class GaussianProcessKalman(GaussianInference):
     def __init__(self, dyn, obs, kern_par_dyn, kern_par_obs, kernel='rbf', points='ut', point_hyp=None):
         t_dyn = GaussianProcessTransform(dyn.dim_in, dyn.dim_state, kern_par_dyn, kernel, points, point_hyp)
         t_obs = GaussianProcessTransform(obs.dim_in, obs.dim_out, kern_par_obs, kernel, points, point_hyp)
+        super().__init__(dyn, obs, t_dyn, t_obs)
+
+
+class GaussianProcessDerKalman(GaussianInference):
+    """GP quadrature Kalman filter and smoother with derivative observations at the sigma points (the filter of the reference's
+    research/gpqd line of work): both transforms are `GaussianProcessDerTransform`s, kern_par_dyn (1, 1 + dim_in), kern_par_obs
+    (1, 1 + dim_state), which_der_dyn / which_der_obs the points that carry a Jacobian (None: all).  Runs on the captured launch
+    loop (k_apply_gpqd | k_apply_gpqd | k_kalman_update per step; the smoother's variant keeps the predictive moments), routed as
+    ExtendedKalmanGPQD is; additive-noise models only, built-in ones with a Jacobian and models of your own that have a
+    `device_jacobian` (forward pass).  `run_filters` raises NotImplementedError for this class."""
+
+    def __init__(self, dyn, obs, kern_par_dyn, kern_par_obs, points='ut', point_hyp=None, which_der_dyn=None, which_der_obs=None):
+        _need_device_jacobians('GaussianProcessDerKalman', dyn, obs)
+        if not (dyn.noise_additive and obs.noise_additive):
+            raise NotImplementedError('GaussianProcessDerKalman runs for additive-noise models only')
+        t_dyn = GaussianProcessDerTransform(dyn.dim_in, dyn.dim_state, kern_par_dyn, points, point_hyp, which_der=which_der_dyn)
+        t_obs = GaussianProcessDerTransform(obs.dim_state, obs.dim_out, kern_par_obs, points, point_hyp, which_der=which_der_obs)
+        t_dyn._device_integrand(dyn.dyn_eval)          # refused here, before the library is touched
+        t_obs._device_integrand(obs.meas_eval)
         super().__init__(dyn, obs, t_dyn, t_obs)
 
 
