@@ -122,7 +122,10 @@ int ssmq_integrand_define_dx(const char *body, const char *jac_body, int din, in
  * Jacobian (N, N_obs, form, tp, opt ignored); an id without one is SSMQ_E_UNSUPPORTED. */
 /* SSMQ_RTC_GPQD instantiates the GPQ+D kernel of a user id that has a Jacobian: k_apply_gpqd<id, D, E, din> for D <= 2,
  * k_apply_gpqd_lds<id, D, E, din> beyond (D <= 6, E <= max(D, 4); N, N_obs, form, tp, opt ignored). */
-enum ssmq_rtc_kind { SSMQ_RTC_FILTER = 0, SSMQ_RTC_APPLY = 1, SSMQ_RTC_MC = 2, SSMQ_RTC_LINEAR = 3, SSMQ_RTC_TAYLOR_GPQD = 4, SSMQ_RTC_GPQD = 5 };
+/* SSMQ_RTC_INNOVATION instantiates the innovation-score kernel k_innovation<D, E (= Y), N, N_obs, id, id_obs, form, tp, 0, opt>
+ * (arguments as SSMQ_RTC_FILTER). */
+enum ssmq_rtc_kind { SSMQ_RTC_FILTER = 0, SSMQ_RTC_APPLY = 1, SSMQ_RTC_MC = 2, SSMQ_RTC_LINEAR = 3, SSMQ_RTC_TAYLOR_GPQD = 4, SSMQ_RTC_GPQD = 5,
+                     SSMQ_RTC_INNOVATION = 6 };
 int ssmq_rtc_compile_check(int32_t id, int32_t id_obs, int kind, int D, int E, int N, int N_obs, int form, int tp, int opt,
                            const char *arch, char *log, int len);
 /* Process-wide counters of the run-time compiler: programs compiled, kernel lookups served from the cache, compile wall time. */
@@ -936,6 +939,33 @@ int ssmq_filter_kernel_name(const ssmq_transform *h_dyn, const ssmq_integrand *f
  * saturated batches. */
 int ssmq_filter_kernel_name_batch(const ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, const ssmq_transform *h_obs,
                                   const ssmq_integrand *f_obs, int64_t B, char *buf, int len);
+
+/*
+ * Innovation scores of a filter pass, from the measurements and the FILTERED moments alone (no true states): for step k = 0 .. T-1
+ * with (m, P) = (m0, P0) for k = 0, else (fm[k-1], fP[k-1]; the lower triangle of fP is read, as the filters read it),
+ *     m_pr, P_pr = dynamics transform of (m, P) + G Q G';   y_mean, S = measurement transform of (m_pr, P_pr) + R;   e = y_k - y_mean;
+ *     nis[k] = e' S^-1 e (Cholesky of S);   ll[k] = -(Y log 2 pi + log det S + nis[k]) / 2 = log p(y_k | y_1..k-1)
+ * (additive-noise Gaussian recursion, ssinf.py:254-323; both transforms use time index k).  Per trajectory, summed in ascending k:
+ * d_total[b] = sum_k ll[k], d_total[ld + b] = sum_k nis[k] / T.
+ * Buffers: d_y, d_m0, d_P0, d_fm, d_fP, GQG, R as ssmq_filter_forward_dev takes and leaves them; d_nis, d_ll [T][ld]; d_total
+ * [2][ld]; d_status [ld] int32; d_ymean [T][Y][ld] and d_S [T][Y*Y][ld] (both triangles) are optional: NULL = not stored.
+ * Failures: an item whose inputs are NaN (the filter failed earlier) or one of whose Cholesky factorisations fails (input
+ * covariance, predictive covariance, S) is NaN in nis, ll, y_mean and S; d_status[b] = 1 + the first such k, 0 if there is none,
+ * and the totals are NaN from there on.  A trajectory's results do not depend on the batch around it.
+ * One launch of k_innovation<> over all T B items where the fused time loop has an instantiation for the pair (and for a pair
+ * with a user integrand in the range of ssmq_filter_forward_dev, compiled at run time); every other pair the Gaussian launch loop
+ * of ssmq_filter_forward_dev accepts - and every pair under SSMQ_NO_FUSED=1 - runs apply dyn | apply obs | k_innovation_score per
+ * step.  The Studentian recursion has no entry point here; transforms of models that take their noise as an argument (D -> D and
+ * D -> Y is required) return SSMQ_E_UNSUPPORTED before an output is touched.  B == 0: nothing happens; T == 0: status and totals
+ * are zero.  Asynchronous on the library stream.
+ */
+int ssmq_filter_innovations_dev(ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, ssmq_transform *h_obs,
+                                const ssmq_integrand *f_obs, int64_t B, int64_t ld, int T, const double *d_y, const double *d_m0,
+                                const double *d_P0, const double *d_fm, const double *d_fP, const double *GQG, const double *R,
+                                double *d_ymean, double *d_S, double *d_nis, double *d_ll, double *d_total, int32_t *d_status);
+/* Name of the kernel(s) ssmq_filter_innovations_dev would run for this pair (the dry-run twin of ssmq_filter_kernel_name_batch). */
+int ssmq_innovations_kernel_name(const ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, const ssmq_transform *h_obs,
+                                 const ssmq_integrand *f_obs, int64_t B, char *buf, int len);
 
 /*
  * The path's only collective: independent Monte-Carlo trajectories shard across ranks, one process per

@@ -106,6 +106,69 @@ void drop_filter_cache() {
     g_fc.consts_host.clear();
 }
 
+// Which of the launch loop's special forms a pair of an additive-noise Gaussian filter has, after the refusals every entry point
+// of the time loop makes for them (keep: the predictive moments are kept for a smoother; student: Studentian recursion)
+struct PairForms {
+    bool user, mo, trunc, gq;
+};
+static int pair_forms(const ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, const ssmq_transform *h_obs, const ssmq_integrand *f_obs,
+                      bool keep, bool student, PairForms *out) {
+    const bool user = is_user_integrand(f_dyn) || is_user_integrand(f_obs);
+    if (user && keep) return refuse_user_integrand("smoother (predictive moments kept)");
+    // a multi-output transform: the Gaussian forward pass through the launch loop, nothing else
+    const bool mo = is_mo(h_dyn) || is_mo(h_obs);
+    if (mo && user) return refuse_user_integrand("multi-output transform (k_apply_mo)");
+    if (mo && keep) return refuse_mo("smoother (predictive moments kept)");
+    if (mo && student) return refuse_mo("Studentian filter");
+    // a truncated sigma-point transform: the measurement transform of the Gaussian launch loop (forward pass and smoother) next to
+    // a sigma-point dynamics transform, nothing else
+    const bool trunc = is_trunc(h_obs);
+    if (trunc && h_dyn->form != SSMQ_FORM_SIGMA) return refuse_trunc("filter whose dynamics transform is not a sigma-point rule");
+    if (trunc && user) return refuse_user_integrand("truncated sigma-point transform (k_apply_trunc)");
+    if (trunc && student) return refuse_trunc("Studentian filter");
+    // GPQ with derivative observations: both transforms of this form, the Gaussian launch loop (forward pass and smoother)
+    const bool gq = is_gpqd(h_dyn) || is_gpqd(h_obs);
+    if (gq && !(is_gpqd(h_dyn) && is_gpqd(h_obs))) return refuse_gpqd("filter with only one GPQ+D transform");
+    if (gq && student) return refuse_gpqd("Studentian filter");
+    *out = {user, mo, trunc, gq};
+    return SSMQ_OK;
+}
+
+// A pair with a user member whose both transforms read a Jacobian (linearisation, Taylor-GPQD, GPQ+D) runs the launch loop, each
+// transform of a user member a launch of the kernel compiled for it at run time: compiled and loaded here - a stream that is being
+// captured must not meet a compile - and a member without a Jacobian is refused here.
+static int prepare_user_ekf(const ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, const ssmq_transform *h_obs, const ssmq_integrand *f_obs,
+                            bool gq) {
+    const ssmq_transform *hs2[2] = {h_dyn, h_obs};
+    const ssmq_integrand *fs2[2] = {f_dyn, f_obs};
+    for (int i = 0; i < 2; ++i) {
+        FInfo fi;
+        int rc = check_integrand(hs2[i], fs2[i], &fi);
+        if (rc) return rc;
+        if (is_user_integrand(fs2[i])) {
+            if ((rc = gq ? rtc_prepare_gpqd(hs2[i], fs2[i]) : rtc_prepare_jacobian(hs2[i], fs2[i]))) return rc;
+        } else if (!integrand_has_jacobian(fs2[i]->id)) {
+            set_error("filter_forward: built-in integrand " + std::to_string(fs2[i]->id) + " has no Jacobian (its dyn_fcn_dx / meas_fcn_dx "
+                      "returns None in the reference too)");
+            return SSMQ_E_UNSUPPORTED;
+        }
+    }
+    return SSMQ_OK;
+}
+static bool jac_form(const ssmq_transform *h) { return h->form == SSMQ_FORM_TAYLOR1 || is_taylor_gpqd(h); }
+
+// the plane workspace of the launch loops, grow-only (a captured loop points into it: growing drops the graph)
+static int ensure_ws(size_t need) {
+    if (g_fc.ws_bytes >= need) return SSMQ_OK;
+    g_fc.drop_graph();
+    if (g_fc.ws) hipFree(g_fc.ws);
+    g_fc.ws = nullptr;
+    g_fc.ws_bytes = 0;
+    SSMQ_HIP(hipMalloc(&g_fc.ws, need));
+    g_fc.ws_bytes = need;
+    return SSMQ_OK;
+}
+
 int make_filter_pass(const ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, const ssmq_transform *h_obs, const ssmq_integrand *f_obs,
                      int64_t B, int64_t ld, int T, const double *y, const double *m0, const double *P0, double *fm, double *fP,
                      int32_t *status, hipStream_t stream, FilterPass *out) {
@@ -138,23 +201,9 @@ int filter_forward_impl(ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, ssmq
         set_error("filter_forward: additive-noise filter needs dyn (D -> D) and obs (D -> Y) transforms");
         return SSMQ_E_ARG;
     }
-    const bool user = is_user_integrand(f_dyn) || is_user_integrand(f_obs);
-    if (user && (d_pm || d_pP || d_pC)) return refuse_user_integrand("smoother (predictive moments kept)");
-    // a multi-output transform: the Gaussian forward pass through the launch loop, nothing else
-    const bool mo = is_mo(h_dyn) || is_mo(h_obs);
-    if (mo && user) return refuse_user_integrand("multi-output transform (k_apply_mo)");
-    if (mo && (d_pm || d_pP || d_pC)) return refuse_mo("smoother (predictive moments kept)");
-    if (mo && (sscale || student_dof != 0.0)) return refuse_mo("Studentian filter");
-    // a truncated sigma-point transform: the measurement transform of the Gaussian launch loop (forward pass and smoother) next to
-    // a sigma-point dynamics transform, nothing else
-    const bool trunc = is_trunc(h_obs);
-    if (trunc && h_dyn->form != SSMQ_FORM_SIGMA) return refuse_trunc("filter whose dynamics transform is not a sigma-point rule");
-    if (trunc && user) return refuse_user_integrand("truncated sigma-point transform (k_apply_trunc)");
-    if (trunc && (sscale || student_dof != 0.0)) return refuse_trunc("Studentian filter");
-    // GPQ with derivative observations: both transforms of this form, the Gaussian launch loop (forward pass and smoother)
-    const bool gq = is_gpqd(h_dyn) || is_gpqd(h_obs);
-    if (gq && !(is_gpqd(h_dyn) && is_gpqd(h_obs))) return refuse_gpqd("filter with only one GPQ+D transform");
-    if (gq && (sscale || student_dof != 0.0)) return refuse_gpqd("Studentian filter");
+    PairForms pf;
+    if (int rf = pair_forms(h_dyn, f_dyn, h_obs, f_obs, d_pm || d_pP || d_pC, sscale || student_dof != 0.0, &pf)) return rf;
+    const bool user = pf.user, mo = pf.mo, trunc = pf.trunc, gq = pf.gq;
     int rc = ensure_device();
     if (rc) return rc;
     if (B == 0) return SSMQ_OK;
@@ -176,35 +225,13 @@ int filter_forward_impl(ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, ssmq
     // (ssmq_rtc.hip), or an error - and the launch loop for the extended Kalman filters alone (both transforms a linearisation or
     // Taylor-GPQD: no time-loop kernel reads a Jacobian), each transform of a user member a launch of the kernel compiled for it.
     // Those kernels are compiled and loaded here, before the loop is captured, and a member without a Jacobian is refused here.
-    auto jac_form = [](const ssmq_transform *h) { return h->form == SSMQ_FORM_TAYLOR1 || is_taylor_gpqd(h); };
     const bool user_ekf = user && ((jac_form(h_dyn) && jac_form(h_obs)) || gq);
     if (user && !user_ekf) return (rc = rtc_launch_fused(pass)) < 0 ? rc : SSMQ_OK;
-    if (user_ekf) {
-        const ssmq_transform *hs2[2] = {h_dyn, h_obs};
-        const ssmq_integrand *fs2[2] = {f_dyn, f_obs};
-        for (int i = 0; i < 2; ++i) {
-            FInfo fi;
-            if ((rc = check_integrand(hs2[i], fs2[i], &fi))) return rc;
-            if (is_user_integrand(fs2[i])) {
-                if ((rc = gq ? rtc_prepare_gpqd(hs2[i], fs2[i]) : rtc_prepare_jacobian(hs2[i], fs2[i]))) return rc;
-            } else if (!integrand_has_jacobian(fs2[i]->id)) {
-                set_error("filter_forward: built-in integrand " + std::to_string(fs2[i]->id) + " has no Jacobian (its dyn_fcn_dx / meas_fcn_dx "
-                          "returns None in the reference too)");
-                return SSMQ_E_UNSUPPORTED;
-            }
-        }
-    }
+    if (user_ekf && (rc = prepare_user_ekf(h_dyn, f_dyn, h_obs, f_obs, gq))) return rc;
     // workspace carve-up (doubles first, then the two int32 status planes)
     const size_t n_dbl = (size_t)ld * (D + 3 * D * D + Y + Y * Y + Y * D);
     const size_t need = sizeof(double) * n_dbl + 2 * sizeof(int32_t) * (size_t)ld;
-    if (g_fc.ws_bytes < need) {
-        g_fc.drop_graph();
-        if (g_fc.ws) hipFree(g_fc.ws);
-        g_fc.ws = nullptr;
-        g_fc.ws_bytes = 0;
-        SSMQ_HIP(hipMalloc(&g_fc.ws, need));
-        g_fc.ws_bytes = need;
-    }
+    if ((rc = ensure_ws(need))) return rc;
     double *w = (double *)g_fc.ws;
     double *m_pr = w; w += (size_t)ld * D;
     double *P_pr = w; w += (size_t)ld * D * D;
@@ -589,6 +616,115 @@ extern "C" int ssmq_filter_kernel_name_batch(const ssmq_transform *h_dyn, const 
     rc = mo || gq || is_trunc(h_obs) || (user && ekf) || (ssmq::sw("SSMQ_NO_FUSED") && !user) ? 0 : try_launch_fused(query);
     if (rc < 0) return rc;
     snprintf(buf, len, "%s", rc == 1 ? name : "hipGraph of 3 T launches (apply dyn | apply obs | k_kalman_update)");
+    return SSMQ_OK;
+}
+
+// ---- innovation scores of a pass (include/ssmq.h: ssmq_filter_innovations_dev) --------------------------------------------------
+// The checks both entry points share, in the order of filter_forward_impl; the one-launch route is asked for where that function
+// asks for the fused time loop (SSMQ_NO_FUSED switches it off for the table shapes, as there).
+static const char kInnovLoopName[] = "launch loop of 3 T launches (apply dyn | apply obs | k_innovation_score)";
+static int innovations_route(const ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, const ssmq_transform *h_obs,
+                             const ssmq_integrand *f_obs, PairForms *pf, bool *user_ekf, bool *one_launch) {
+    if (is_trunc(h_dyn)) return refuse_trunc("innovation scores with a truncated DYNAMICS transform");
+    if (h_dyn->E != h_dyn->D || h_obs->D != h_dyn->D) {
+        set_error("filter_innovations: additive-noise Gaussian recursion only (dyn D -> D, obs D -> Y): models that take their noise as an "
+                  "argument are not implemented");
+        return SSMQ_E_UNSUPPORTED;
+    }
+    if (int rc = pair_forms(h_dyn, f_dyn, h_obs, f_obs, false, false, pf)) return rc;
+    *user_ekf = pf->user && ((jac_form(h_dyn) && jac_form(h_obs)) || pf->gq);
+    *one_launch = (pf->user && !*user_ekf) || (!ssmq::sw("SSMQ_NO_FUSED") && !pf->user && !pf->mo && !pf->trunc && !pf->gq);
+    return SSMQ_OK;
+}
+
+extern "C" int ssmq_filter_innovations_dev(ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, ssmq_transform *h_obs,
+                                           const ssmq_integrand *f_obs, int64_t B, int64_t ld, int T, const double *d_y,
+                                           const double *d_m0, const double *d_P0, const double *d_fm, const double *d_fP,
+                                           const double *GQG, const double *R, double *d_ymean, double *d_S, double *d_nis,
+                                           double *d_ll, double *d_total, int32_t *d_status) {
+    SSMQ_HANDLE_LOCK(h_dyn, h_obs);
+    if (!h_dyn || !h_obs || !f_dyn || !f_obs || B < 0 || ld < B || T < 0 || !d_y || !d_m0 || !d_P0 || !d_fm || !d_fP || !d_nis ||
+        !d_ll || !d_total || !d_status) {
+        set_error("filter_innovations: bad argument");
+        return SSMQ_E_ARG;
+    }
+    PairForms pf;
+    bool user_ekf = false, one_launch = false;
+    int rc = innovations_route(h_dyn, f_dyn, h_obs, f_obs, &pf, &user_ekf, &one_launch);
+    if (rc) return rc;
+    const int D = h_dyn->D, Y = h_obs->E;
+    if ((rc = ensure_device())) return rc;
+    if (B == 0) return SSMQ_OK;
+    hipStream_t s = stream();
+    if (T == 0) {   // nothing to score: every trajectory is trivially fine, its totals are empty sums
+        SSMQ_HIP(hipMemsetAsync(d_status, 0, sizeof(int32_t) * ld, s));
+        SSMQ_HIP(hipMemsetAsync(d_total, 0, sizeof(double) * 2 * ld, s));
+        return SSMQ_OK;
+    }
+    FilterPass pass;
+    PassConsts pc;
+    // (the pass's fm / fP are the filtered moments here: read, never written)
+    if ((rc = make_filter_pass(h_dyn, f_dyn, h_obs, f_obs, B, ld, T, d_y, d_m0, d_P0, const_cast<double *>(d_fm),
+                               const_cast<double *>(d_fP), d_status, s, &pass)) ||
+        (rc = cached_pass_consts(f_dyn, f_obs, D, Y, T, GQG, R, nullptr, s, &pc)))
+        return rc;
+    const double *cs = (const double *)g_fc.consts, *gqg = cs, *rr = cs + pc.rr, *tvec = cs + pc.steps;
+    wire_pass_consts(pass, cs, pc);
+    const InnovOut out{d_ymean, d_S, d_nis, d_ll};
+    rc = one_launch ? try_launch_innovation(pass, out) : 0;
+    if (rc < 0) return rc;
+    if (rc == 0) {
+        if (pf.user && !user_ekf) {
+            set_error("filter_innovations: no run-time kernel for this pair of user integrands");
+            return SSMQ_E_UNSUPPORTED;
+        }
+        if (user_ekf && (rc = prepare_user_ekf(h_dyn, f_dyn, h_obs, f_obs, pf.gq))) return rc;
+        // the launch loop: per step apply dyn on plane k - 1 | apply obs | k_innovation_score, on the filter's workspace
+        const size_t n_dbl = (size_t)ld * (D + 3 * D * D + Y + Y * Y + Y * D);
+        if ((rc = ensure_ws(sizeof(double) * n_dbl + 2 * sizeof(int32_t) * (size_t)ld))) return rc;
+        double *w = (double *)g_fc.ws;
+        double *m_pr = w; w += (size_t)ld * D;
+        double *P_pr = w; w += (size_t)ld * D * D;
+        double *C_xx = w; w += (size_t)ld * D * D;
+        double *y_mean = w; w += (size_t)ld * Y;
+        double *P_y = w; w += (size_t)ld * Y * Y;
+        double *P_yx = w; w += (size_t)ld * Y * D;
+        w += (size_t)ld * D * D;
+        int32_t *st_a = (int32_t *)w, *st_b = st_a + ld;
+        for (int k = 0; k < T && !rc; ++k) {
+            const double *m_in = k == 0 ? d_m0 : d_fm + (int64_t)(k - 1) * D * ld;
+            const double *P_in = k == 0 ? d_P0 : d_fP + (int64_t)(k - 1) * D * D * ld;
+            rc = apply_dev_impl(h_dyn, f_dyn, B, ld, m_in, P_in, tvec + k, 0, m_pr, P_pr, C_xx, st_a, gqg, nullptr, false, 1.0, 1.0,
+                                pass.ttab_dyn, false);
+            if (!rc)
+                rc = apply_dev_impl(h_obs, f_obs, B, ld, m_pr, P_pr, tvec + k, 0, y_mean, P_y, P_yx, st_b, rr, nullptr, false, 1.0, 1.0,
+                                    pass.ttab_obs, false);
+            if (!rc)
+                rc = launch_innovation_score(D, Y, B, ld, d_y + (int64_t)k * Y * ld, y_mean, P_y, m_in, st_a, st_b,
+                                             d_ymean ? d_ymean + (int64_t)k * Y * ld : nullptr,
+                                             d_S ? d_S + (int64_t)k * Y * Y * ld : nullptr, d_nis + (int64_t)k * ld,
+                                             d_ll + (int64_t)k * ld, s);
+        }
+        if (rc) return rc;
+    }
+    return launch_innovation_total(B, ld, T, d_nis, d_ll, d_total, d_status, s);
+}
+
+extern "C" int ssmq_innovations_kernel_name(const ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, const ssmq_transform *h_obs,
+                                            const ssmq_integrand *f_obs, int64_t B, char *buf, int len) {
+    SSMQ_HANDLE_LOCK(h_dyn, h_obs);
+    if (!h_dyn || !h_obs || !f_dyn || !f_obs || !buf || len <= 0 || B < 0) return SSMQ_E_ARG;
+    PairForms pf;
+    bool user_ekf = false, one_launch = false;
+    int rc = innovations_route(h_dyn, f_dyn, h_obs, f_obs, &pf, &user_ekf, &one_launch);
+    if (rc) return rc;
+    const char *name = nullptr;
+    FilterPass query;
+    if ((rc = make_filter_pass(h_dyn, f_dyn, h_obs, f_obs, B, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &query))) return rc;
+    query.name = &name; query.dry_run = true;
+    rc = one_launch ? try_launch_innovation(query, InnovOut{nullptr, nullptr, nullptr, nullptr}) : 0;
+    if (rc < 0) return rc;
+    snprintf(buf, len, "%s", rc == 1 ? name : kInnovLoopName);
     return SSMQ_OK;
 }
 

@@ -536,6 +536,27 @@ int multi_family_launch(const char *table, int blocks, hipStream_t s);
 int try_launch_range(const FilterPass &p, int kb, int ke, double *hand);
 size_t range_hand_doubles(int D);
 
+// Innovation scores of a pass whose fm / fP hold the FILTERED moments (inputs here; ssmq_innovation.hip, ssmq_filter_innovations_dev):
+// the planes of all T steps, ymean / S null = not stored
+struct InnovOut {
+    double *ymean, *S;                        // [T][Y][ld], [T][Y*Y][ld] or null
+    double *nis, *ll;                         // [T][ld]
+};
+struct InnovArgs;                             // ssmq_innovation_kernel.h
+InnovArgs innov_args(const FilterPass &p, const InnovOut &o);
+// all T B items in one launch of k_innovation<>: 1 launched (dry_run: a kernel exists, its name set), 0 no kernel for this pair,
+// < 0 error; a pair with a user integrand runs the instantiation compiled for it at run time (ssmq_rtc.hip) or is an error
+int try_launch_innovation(const FilterPass &p, const InnovOut &o);
+int rtc_launch_innovation(const FilterPass &p, const InnovOut &o);
+// one step of the launch-loop route: scores from the planes the step's two transforms left (st_a / st_b: their status planes,
+// m_in: the mean the step started from); ymean / S / nis / ll: the planes of this step
+int launch_innovation_score(int D, int Y, int64_t B, int64_t ld, const double *y, const double *y_mean, const double *P_y,
+                            const double *m_in, const int32_t *st_a, const int32_t *st_b, double *ymean, double *S, double *nis,
+                            double *ll, hipStream_t s);
+// total [2][ld]: sum of ll, mean of nis over the steps in ascending order; status [B]: 1 + first step with NaN scores, or 0
+int launch_innovation_total(int64_t B, int64_t ld, int T, const double *nis, const double *ll, double *total, int32_t *status,
+                            hipStream_t s);
+
 // error sums over a batch of filtered trajectories (ssmq_metrics.hip)
 int metrics_values_per_step(int D);
 int metrics_chunks(int64_t B);

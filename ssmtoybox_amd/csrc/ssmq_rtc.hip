@@ -29,6 +29,7 @@
 #include <vector>
 #include "ssmq_host.h"
 #include "ssmq_fused.h"
+#include "ssmq_innovation_kernel.h"
 #include "ssmq_filter_shapes.h"
 #include "ssmq_mc_moments.h"
 #include "ssmq_jacobian_kernel.h"
@@ -335,6 +336,11 @@ std::string fused_expr(int D, int Y, int ND, int NO, int FD, int FO, int form, i
              opt, stu);
     return b;
 }
+std::string innovation_expr(int D, int Y, int ND, int NO, int FD, int FO, int form, int tp, int selo, int opt) {
+    char b[256];
+    snprintf(b, sizeof(b), "ssmq::k_innovation<%d, %d, %d, %d, %d, %d, %d, %d, %d, %d>", D, Y, ND, NO, FD, FO, form, tp, selo, opt);
+    return b;
+}
 std::string apply_expr(int D, int E, int N, int F, int form, int tp, int sel, int opt, bool nts) {
     char b[256];
     snprintf(b, sizeof(b), "ssmq::k_apply_small<%d, %d, %d, %d, %d, %d, %d, %d, %s>", D, E, N, F, form, tp, sel, opt, nts ? "true" : "false");
@@ -389,10 +395,12 @@ static int check_user_pair(const ssmq_integrand *fd, const ssmq_integrand *fo, s
     return SSMQ_OK;
 }
 
-int rtc_launch_fused(const FilterPass &p) {
+// The checks of a pair with a user member that runs ONE kernel instantiated for it (the time loop, the innovation scores): the ids
+// to compile for, both transforms of one form and in the shape range, dimensions that fit
+static int user_pair_shape(const FilterPass &p, std::vector<int> *ids_out) {
     const ssmq_transform *hd = p.hd, *ho = p.ho;
     const ssmq_integrand *fd = p.fd, *fo = p.fo;
-    std::vector<int> ids;
+    std::vector<int> &ids = *ids_out;
     int rc = check_user_pair(fd, fo, &ids);
     if (rc) return rc;
     FInfo id_, io_;
@@ -416,6 +424,16 @@ int rtc_launch_fused(const FilterPass &p) {
         set_error("user integrands: input / output dimensions do not match the transforms");
         return SSMQ_E_ARG;
     }
+    return SSMQ_OK;
+}
+
+int rtc_launch_fused(const FilterPass &p) {
+    const ssmq_transform *hd = p.hd, *ho = p.ho;
+    const ssmq_integrand *fd = p.fd, *fo = p.fo;
+    std::vector<int> ids;
+    int rc = user_pair_shape(p, &ids);
+    if (rc) return rc;
+    const int D = hd->D, Y = ho->E;
     const int tp = hd->tp_nu > 0.0 ? 1 : 0, opt = pick_opt_fused(hd, ho);
     const int stu = (p.sscale != nullptr && p.student_dof > 0.0) ? 1 : 0;
     // scalar state: recursion type fixed at compile time, as the AOT table does (SSMQ_FUSED_ONE_S)
@@ -438,6 +456,33 @@ int rtc_launch_fused(const FilterPass &p) {
     if (is_user_integrand(fd)) a.fd.ttab = nullptr;   // (user integrands evaluate their time dependence themselves)
     if (is_user_integrand(fo)) a.fo.ttab = nullptr;
     rc = launch_compiled(expr, "ssmq::FusedArgs", ids, &a, (unsigned)((a.B + a.lpw - 1) / a.lpw), kSmallBlock, p.s, p.name, false, what);
+    return rc ? rc : 1;
+}
+
+// k_innovation<> (ssmq_innovation_kernel.h) for a pair with a user member: the shapes, the fast-path choice and the time tables
+// of rtc_launch_fused, the grid and the argument block of the AOT launcher (ssmq_innovation.hip)
+int rtc_launch_innovation(const FilterPass &p, const InnovOut &o) {
+    std::vector<int> ids;
+    int rc = user_pair_shape(p, &ids);
+    if (rc) return rc;
+    const ssmq_transform *hd = p.hd, *ho = p.ho;
+    const std::string expr = innovation_expr(hd->D, ho->E, hd->N, ho->N, p.fd->id, p.fo->id, hd->form, hd->tp_nu > 0.0 ? 1 : 0, 0, pick_opt_fused(hd, ho));
+    const char *what = "k_innovation (run-time compiled)";
+    if (p.dry_run) {
+        rc = launch_compiled(expr, "ssmq::InnovArgs", ids, nullptr, 0, kSmallBlock, p.s, p.name, true, what);
+        return rc ? rc : 1;
+    }
+    InnovArgs a = innov_args(p, o);
+    for (const ssmq_integrand *f : {p.fd, p.fo}) {
+        const double *tab = f == p.fd ? a.fd.ttab : a.fo.ttab;
+        if (!is_user_integrand(f) && has_time_table(f->id) && !tab) {
+            set_error("run-time compiled innovation scores: the time table of built-in integrand " + std::to_string(f->id) + " is missing");
+            return SSMQ_E_ARG;
+        }
+    }
+    if (is_user_integrand(p.fd)) a.fd.ttab = nullptr;   // (user integrands evaluate their time dependence themselves)
+    if (is_user_integrand(p.fo)) a.fo.ttab = nullptr;
+    rc = launch_compiled(expr, "ssmq::InnovArgs", ids, &a, (unsigned)a.T * (unsigned)a.nblk, kSmallBlock, p.s, p.name, false, what);
     return rc ? rc : 1;
 }
 
@@ -733,29 +778,31 @@ extern "C" int ssmq_rtc_compile_check(int32_t id, int32_t id_obs, int kind, int 
         form = SSMQ_FORM_SIGMA;
         tp = opt = 0;
     }
-    if (!arch || !*arch || (kind != SSMQ_RTC_FILTER && kind != SSMQ_RTC_APPLY && kind != SSMQ_RTC_MC) || (form != SSMQ_FORM_BQ && form != SSMQ_FORM_SIGMA) ||
+    if (!arch || !*arch || (kind != SSMQ_RTC_FILTER && kind != SSMQ_RTC_APPLY && kind != SSMQ_RTC_MC && kind != SSMQ_RTC_INNOVATION) || (form != SSMQ_FORM_BQ && form != SSMQ_FORM_SIGMA) ||
         tp < 0 || tp > 1 || (opt != 0 && opt != 1 && opt != 2 && opt != 3 && opt != 7)) {
         set_error("ssmq_rtc_compile_check: bad argument");
         return SSMQ_E_ARG;
     }
+    const bool pair = kind == SSMQ_RTC_FILTER || kind == SSMQ_RTC_INNOVATION;      // (id, id_obs): the two models of a filter
     std::string why;
-    if (kind != SSMQ_RTC_MC && (!shape_ok(D, E, N, &why) || (kind == SSMQ_RTC_FILTER && !shape_ok(D, D, N_obs, &why)))) {
+    if (kind != SSMQ_RTC_MC && (!shape_ok(D, E, N, &why) || (pair && !shape_ok(D, D, N_obs, &why)))) {
         set_error(why);
         return SSMQ_E_UNSUPPORTED;
     }
     FInfo fi;
-    if (!integrand_info(id, &fi) || (kind == SSMQ_RTC_FILTER && !integrand_info(id_obs, &fi))) {
+    if (!integrand_info(id, &fi) || (pair && !integrand_info(id_obs, &fi))) {
         set_error("ssmq_rtc_compile_check: unknown integrand id");
         return SSMQ_E_ARG;
     }
     std::vector<int> ids;
     if (is_user_integrand(id)) ids.push_back(id);
-    if (kind == SSMQ_RTC_FILTER && is_user_integrand(id_obs) && id_obs != id) ids.push_back(id_obs);
-    const std::string expr = kind == SSMQ_RTC_FILTER ? fused_expr(D, E, N, N_obs, id, id_obs, form, tp, 0, opt, -1)
-                             : kind == SSMQ_RTC_MC   ? "ssmq::k_mc_moments<" + std::to_string(id) + ", " + std::to_string(D) + ", " + std::to_string(E) + ", 0>"
-                                                     : apply_expr(D, E, N, id, form, tp, 0, opt, false);
-    return compile_check_text(expr, kind == SSMQ_RTC_FILTER ? "ssmq::FusedArgs" : kind == SSMQ_RTC_MC ? "ssmq::McMomArgs" : "ssmq::ApplyArgs", ids,
-                              arch, log, len);
+    if (pair && is_user_integrand(id_obs) && id_obs != id) ids.push_back(id_obs);
+    const std::string expr = kind == SSMQ_RTC_FILTER       ? fused_expr(D, E, N, N_obs, id, id_obs, form, tp, 0, opt, -1)
+                             : kind == SSMQ_RTC_INNOVATION ? innovation_expr(D, E, N, N_obs, id, id_obs, form, tp, 0, opt)
+                             : kind == SSMQ_RTC_MC         ? "ssmq::k_mc_moments<" + std::to_string(id) + ", " + std::to_string(D) + ", " + std::to_string(E) + ", 0>"
+                                                           : apply_expr(D, E, N, id, form, tp, 0, opt, false);
+    return compile_check_text(expr, kind == SSMQ_RTC_FILTER ? "ssmq::FusedArgs" : kind == SSMQ_RTC_INNOVATION ? "ssmq::InnovArgs"
+                                    : kind == SSMQ_RTC_MC   ? "ssmq::McMomArgs" : "ssmq::ApplyArgs", ids, arch, log, len);
 }
 
 extern "C" int ssmq_rtc_stats(int64_t *compiles, int64_t *cache_hits, double *compile_seconds) {

@@ -236,17 +236,7 @@ class GaussianInference:
         # staging block (`ssmq_upload_planes`)
         d_y = _lib.scratch(8 * T * Y * ld)
         _lib.upload_study(data, Y, ld, d_y)
-        m0 = np.broadcast_to(self.x0_mean, (B, D)) if x0_mean is None else np.asarray(x0_mean, dtype=np.float64)
-        P0 = np.broadcast_to(self._initial_cov(), (B, D, D)) if x0_cov is None else np.asarray(x0_cov, dtype=np.float64)
-        mbuf = np.zeros((D, ld))
-        mbuf[:, :B] = m0.T
-        Pbuf = np.zeros((D * D, ld))
-        Pbuf[:, :B] = P0.reshape(B, D * D).T
-        if ld > B:       # padding lanes are never read (b >= B), keep them PD anyway
-            Pbuf[:, B:] = np.eye(D).reshape(-1, 1)
-        d_m0, d_P0 = _lib.scratch(mbuf.nbytes), _lib.scratch(Pbuf.nbytes)
-        d_m0.upload(mbuf)
-        d_P0.upload(Pbuf)
+        d_m0, d_P0 = self._initial_planes(B, ld, x0_mean, x0_cov)
         d_fm, d_fP = _lib.scratch(8 * T * D * ld), _lib.scratch(8 * T * D * D * ld)
         d_st = _lib.scratch(4 * ld)
         f_dyn, e_dyn = resolve_integrand(self.mod_dyn.dyn_eval)
@@ -282,6 +272,125 @@ class GaussianInference:
                 b, int(self.status[b]) - 1))
         self.fi_mean, self.fi_cov = fm, fP
         return self.fi_mean, self.fi_cov
+
+    # ---- innovation scores: what a filter run on measurements alone can be judged by -------------------------------------------
+    def _innovations_refusal(self):
+        """None, or the NotImplementedError of a filter outside the range of the innovation scores (additive-noise Gaussian
+        recursion) - raised before the library is touched."""
+        if not self._additive:
+            return NotImplementedError('innovation scores cover the additive-noise Gaussian recursion; not implemented for models '
+                                       'that take their noise as an argument (non-additive noise)')
+        return None
+
+    def innovations_kernel_name(self, batch=0):
+        """Which kernel(s) `innovations_*` run for this filter: k_innovation<..> (all T B items in one launch) where the fused time
+        loop has an instantiation, and for user models; else the launch loop apply dyn | apply obs | k_innovation_score."""
+        err = self._innovations_refusal()
+        if err is not None:
+            raise err
+        self._check_user_points()
+        f_dyn, e_dyn = resolve_integrand(self.mod_dyn.dyn_eval)
+        f_obs, e_obs = resolve_integrand(self.mod_obs.meas_eval)
+        buf = ctypes.create_string_buffer(512)
+        _lib.check(_lib.load().ssmq_innovations_kernel_name(ctypes.c_void_p(self.tf_dyn._handle_for(e_dyn)), ctypes.byref(f_dyn),
+                                                            ctypes.c_void_p(self.tf_obs._handle_for(e_obs)), ctypes.byref(f_obs),
+                                                            int(batch), buf, 512), 'ssmq_innovations_kernel_name')
+        return buf.value.decode()
+
+    def _launch_innovations(self, lib, B, ld, T, d_y, d_m0, d_P0, d_fm, d_fP, d_ym, d_S, d_nis, d_ll, d_tot, d_st):
+        f_dyn, e_dyn = resolve_integrand(self.mod_dyn.dyn_eval)
+        f_obs, e_obs = resolve_integrand(self.mod_obs.meas_eval)
+        h_dyn, h_obs = self.tf_dyn._handle_for(e_dyn), self.tf_obs._handle_for(e_obs)
+        gqg, pg = _lib.as_c(self.G.dot(self.q_cov).dot(self.G.T))
+        rr, pr = _lib.as_c(self.r_cov)
+        vp = lambda b: ctypes.c_void_p(b.ptr if b is not None else None)       # noqa: E731
+        _lib.check(lib.ssmq_filter_innovations_dev(ctypes.c_void_p(h_dyn), ctypes.byref(f_dyn), ctypes.c_void_p(h_obs), ctypes.byref(f_obs),
+                                                   B, ld, T, vp(d_y), vp(d_m0), vp(d_P0), vp(d_fm), vp(d_fP), pg, pr, vp(d_ym), vp(d_S),
+                                                   vp(d_nis), vp(d_ll), vp(d_tot), vp(d_st)), 'ssmq_filter_innovations_dev')
+
+    def _initial_planes(self, B, ld, x0_mean=None, x0_cov=None):
+        """The initial moments of B trajectories as planes [D][ld], [D*D][ld] (scratch buffers; the caller frees them)."""
+        D = self.mod_dyn.dim_state
+        m0 = np.broadcast_to(self.x0_mean, (B, D)) if x0_mean is None else np.asarray(x0_mean, dtype=np.float64)
+        P0 = np.broadcast_to(self._initial_cov(), (B, D, D)) if x0_cov is None else np.asarray(x0_cov, dtype=np.float64)
+        mbuf = np.zeros((D, ld))
+        mbuf[:, :B] = m0.T
+        Pbuf = np.zeros((D * D, ld))
+        Pbuf[:, :B] = P0.reshape(B, D * D).T
+        if ld > B:       # padding lanes are never read (b >= B), keep them PD anyway
+            Pbuf[:, B:] = np.eye(D).reshape(-1, 1)
+        d_m0, d_P0 = _lib.scratch(mbuf.nbytes), _lib.scratch(Pbuf.nbytes)
+        d_m0.upload(mbuf)
+        d_P0.upload(Pbuf)
+        return d_m0, d_P0
+
+    def innovations_dev(self, d_y, d_fm, d_fP, B, ld, T):
+        """Innovation scores of a pass whose measurements and filtered moments are on the device (what `ssmod.simulate_dev` /
+        `forward_pass_dev` return): DeviceBuffers (d_nis [T][ld], d_ll [T][ld], d_total [2][ld]: sum of the log-likelihoods and mean
+        NIS of every trajectory, d_status [ld] int32: 1 + the first step whose scores are NaN, or 0); the caller frees them.  Every
+        trajectory starts from the model's initial moments, as in `forward_pass_dev`."""
+        err = self._innovations_refusal()
+        if err is not None:
+            raise err
+        self._check_user_points()
+        lib = _lib.load()
+        d_m0, d_P0 = self._initial_planes(B, ld)
+        d_nis, d_ll = _lib.DeviceBuffer(8 * T * ld), _lib.DeviceBuffer(8 * T * ld)
+        d_tot, d_st = _lib.DeviceBuffer(8 * 2 * ld), _lib.DeviceBuffer(4 * ld)
+        self._launch_innovations(lib, B, ld, T, d_y, d_m0, d_P0, d_fm, d_fP, None, None, d_nis, d_ll, d_tot, d_st)
+        _lib.sync()
+        d_m0.free()
+        d_P0.free()
+        return d_nis, d_ll, d_tot, d_st
+
+    def innovations_batch(self, data, x0_mean=None, x0_cov=None, fi_mean=None, fi_cov=None, return_moments=False):
+        """Normalised innovation squared and measurement log-likelihood of every step, data (dim_y, T, B): with (m, P) the initial
+        moments for k = 0, else the filtered moments of step k - 1,
+            y_mean, S = predictive measurement moments of step k;  e = y_k - y_mean;
+            nis[k] = e' S^-1 e;  loglik[k] = log N(y_k | y_mean, S) = log p(y_k | y_1..k-1).
+        fi_mean (D, T, B) / fi_cov (D, D, T, B): the filtered moments of `data` (both or neither); without them
+        `forward_pass_batch(data, x0_mean, x0_cov, raise_on_failure=False)` runs first.  Returns a dict: nis (T, B), loglik (T, B),
+        loglik_total (B,), nis_mean (B,), status (B,) - 1 + the first step whose scores are NaN (the filter failed there or
+        earlier, or a covariance is not positive definite), 0 if none; with return_moments also y_mean (dim_y, T, B) and y_cov
+        (dim_y, dim_y, T, B)."""
+        err = self._innovations_refusal()
+        if err is not None:
+            raise err
+        if (fi_mean is None) != (fi_cov is None):
+            raise ValueError('innovations_batch: give fi_mean and fi_cov, or neither')
+        self._check_user_points()
+        data = np.asarray(data, dtype=np.float64)
+        if fi_mean is None:
+            fi_mean, fi_cov = self.forward_pass_batch(data, x0_mean=x0_mean, x0_cov=x0_cov, raise_on_failure=False)
+        lib = _lib.load()
+        Y, T, B = data.shape
+        D = self.mod_dyn.dim_state
+        ld = (B + 63) // 64 * 64
+        d_y, d_fm, d_fP = _lib.scratch(8 * T * Y * ld), _lib.scratch(8 * T * D * ld), _lib.scratch(8 * T * D * D * ld)
+        _lib.upload_study(data, Y, ld, d_y)
+        _lib.upload_study(np.asarray(fi_mean, dtype=np.float64).reshape(D, T, B), D, ld, d_fm)
+        _lib.upload_study(np.asarray(fi_cov, dtype=np.float64).reshape(D * D, T, B), D * D, ld, d_fP)
+        d_m0, d_P0 = self._initial_planes(B, ld, x0_mean, x0_cov)
+        d_nis, d_ll, d_tot, d_st = _lib.scratch(8 * T * ld), _lib.scratch(8 * T * ld), _lib.scratch(8 * 2 * ld), _lib.scratch(4 * ld)
+        d_ym = _lib.scratch(8 * T * Y * ld) if return_moments else None
+        d_S = _lib.scratch(8 * T * Y * Y * ld) if return_moments else None
+        self._launch_innovations(lib, B, ld, T, d_y, d_m0, d_P0, d_fm, d_fP, d_ym, d_S, d_nis, d_ll, d_tot, d_st)
+        out = {'nis': _lib.download_study(d_nis, (), T, B, ld), 'loglik': _lib.download_study(d_ll, (), T, B, ld)}
+        tot = d_tot.download((2, ld))
+        out['loglik_total'], out['nis_mean'] = tot[0, :B].copy(), tot[1, :B].copy()
+        out['status'] = d_st.download((ld,), dtype=np.int32)[:B]
+        if return_moments:
+            out['y_mean'] = _lib.download_study(d_ym, (Y,), T, B, ld)
+            out['y_cov'] = _lib.download_study(d_S, (Y, Y), T, B, ld)
+        for buf in (d_y, d_fm, d_fP, d_m0, d_P0, d_nis, d_ll, d_tot, d_st, d_ym, d_S):
+            if buf is not None:
+                buf.free()
+        return out
+
+    def innovations(self, data):
+        """`innovations_batch` for one trajectory, data (dim_y, T): nis (T,), loglik (T,), loglik_total, nis_mean, status."""
+        out = self.innovations_batch(np.asarray(data)[..., None])
+        return {k: (v[..., 0] if v.ndim else v) for k, v in out.items()}
 
 
 def run_filters(algs, data, x0_mean=None, x0_cov=None, raise_on_failure=True):
@@ -580,6 +689,10 @@ class StudentianInference(GaussianInference):
     def backward_pass_batch(self):
         raise NotImplementedError('the reference has no Student smoother either (ssinf.py:738-740)')
 
+    def _innovations_refusal(self):
+        return NotImplementedError('innovation scores cover the additive-noise Gaussian recursion; not implemented for the Studentian '
+                                   'recursion (its predictive density is a Student t, not the Gaussian the scores assume)')
+
     def scale_sequence(self, steps):
         """(dof_pr - 2) / dof_pr of every time update (ssinf.py:652-660; dof_fi grows by dim_out per update, :735)."""
         out = np.zeros(steps)
@@ -836,6 +949,10 @@ class MarginalInference(GaussianInference):
         if self.mod_dyn.noise_additive:
             P_pr = P_pr + self.G.dot(self.q_cov).dot(self.G.T)
         return m_pr, P_pr, C[:, :self.mod_dyn.dim_state]
+
+    def _innovations_refusal(self):
+        return NotImplementedError('innovation scores cover the additive-noise Gaussian recursion; not implemented for the marginalised '
+                                   'filter (its predictive density is a mixture over the kernel parameters)')
 
     def forward_pass(self, data, keep_predictive=True):
         """data (dim_y, T) -> (D, T), (D, D, T).  ssinf.py:66-118.  The generic time update of step k only feeds the
