@@ -546,6 +546,10 @@ int ssmq_fxwc_batch_dev(ssmq_transform *h, int64_t M, const double *d_fx, int64_
  * Gaussian measurement update for B trajectories (ssinf.py:297-323): gain = (P_y^-1 P_yx)' by Cholesky,
  * m = m_pr + gain (y - y_mean), P = P_pr - gain P_y gain' (left unsymmetrised as the reference does, :323).
  * SoA planes, pitch ld.  P_yx is (Y, D) as returned by the obs transform.  In-place (m_fi == m_pr etc.) is allowed.
+ * P_y must be symmetric (its lower triangle is factored).  D, Y <= SSMQ_MAX_DIM, else SSMQ_E_UNSUPPORTED and nothing is written.
+ * Asynchronous on the library stream: ssmq_sync() before the results are read.  The call clears d_status[0..B) (lanes B..ld-1 of
+ * every output stay untouched) and then writes 1 to d_status[b], and NaN to every entry of that item's m_fi and P_fi, where P_y is
+ * not positive definite (a pivot that is zero, negative or NaN).
  */
 int ssmq_kalman_update_dev(int D, int Y, int64_t B, int64_t ld, const double *d_m_pr, const double *d_P_pr,
                            const double *d_y_mean, const double *d_P_y, const double *d_P_yx, const double *d_y,
@@ -590,7 +594,9 @@ int ssmq_filter_forward_aug_dev(ssmq_transform *h_dyn, const ssmq_integrand *f_d
 /* The backward pass alone (ssinf.py:120-147, 325-344) over moments the caller kept from its own forward pass (the
  * marginalised filter drives its forward pass from the host): filtered d_fm [T][D][ld], d_fP [T][D*D][ld], predictive
  * d_pm, d_pP (element k = the prediction INTO step k), dynamics cross-covariance d_pC [T][D*D][ld]; outputs d_sm, d_sP;
- * d_status [ld] gets bit 30 set where a predictive covariance is not positive definite.  D <= 7.  Synchronous. */
+ * d_status [ld] gets bit 30 set where a predictive covariance is not positive definite: the bit is OR-ed into the word the caller
+ * passes in, nothing is cleared.  Every d_pP[k] must be symmetric (its lower triangle is read and mirrored); d_fP and d_pC are taken
+ * as they are.  Elements 0 and T - 1 of d_pm, d_pP, d_pC are never read.  D <= 7.  Synchronous. */
 int ssmq_rts_backward_dev(int D, int64_t B, int64_t ld, int T, const double *d_fm, const double *d_fP, const double *d_pm,
                           const double *d_pP, const double *d_pC, double *d_sm, double *d_sP, int32_t *d_status);
 

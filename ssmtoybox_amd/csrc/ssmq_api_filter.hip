@@ -26,6 +26,10 @@ int ssmq_kalman_update_dev(int D, int Y, int64_t B, int64_t ld, const double *d_
     if (D < 1 || Y < 1 || B < 0 || ld < B || !d_m_pr || !d_P_pr || !d_y_mean || !d_P_y || !d_P_yx || !d_y || !d_m_fi ||
         !d_P_fi || !d_status)
         return SSMQ_E_ARG;
+    if (D > SSMQ_MAX_DIM || Y > SSMQ_MAX_DIM) {   // refused before the status words are cleared: a refused call writes nothing
+        set_error("kalman update: D or Y above SSMQ_MAX_DIM");
+        return SSMQ_E_UNSUPPORTED;
+    }
     int rc = ensure_device();
     if (rc) return rc;
     if (B == 0) return SSMQ_OK;
