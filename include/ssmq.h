@@ -124,8 +124,10 @@ int ssmq_integrand_define_dx(const char *body, const char *jac_body, int din, in
  * k_apply_gpqd_lds<id, D, E, din> beyond (D <= 6, E <= max(D, 4); N, N_obs, form, tp, opt ignored). */
 /* SSMQ_RTC_INNOVATION instantiates the innovation-score kernel k_innovation<D, E (= Y), N, N_obs, id, id_obs, form, tp, 0, opt>
  * (arguments as SSMQ_RTC_FILTER). */
+/* SSMQ_RTC_ITERATED instantiates the iterated-pass kernel k_iplf_loop<D, E (= Y), N, N_obs, id, id_obs, form, tp, 0, 0> (arguments as
+ * SSMQ_RTC_FILTER; opt must be 0: the dense kernel is the only one). */
 enum ssmq_rtc_kind { SSMQ_RTC_FILTER = 0, SSMQ_RTC_APPLY = 1, SSMQ_RTC_MC = 2, SSMQ_RTC_LINEAR = 3, SSMQ_RTC_TAYLOR_GPQD = 4, SSMQ_RTC_GPQD = 5,
-                     SSMQ_RTC_INNOVATION = 6 };
+                     SSMQ_RTC_INNOVATION = 6, SSMQ_RTC_ITERATED = 7 };
 int ssmq_rtc_compile_check(int32_t id, int32_t id_obs, int kind, int D, int E, int N, int N_obs, int form, int tp, int opt,
                            const char *arch, char *log, int len);
 /* Process-wide counters of the run-time compiler: programs compiled, kernel lookups served from the cache, compile wall time. */
@@ -972,6 +974,34 @@ int ssmq_filter_innovations_dev(ssmq_transform *h_dyn, const ssmq_integrand *f_d
 /* Name of the kernel(s) ssmq_filter_innovations_dev would run for this pair (the dry-run twin of ssmq_filter_kernel_name_batch). */
 int ssmq_innovations_kernel_name(const ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, const ssmq_transform *h_obs,
                                  const ssmq_integrand *f_obs, int64_t B, char *buf, int len);
+
+/*
+ * Iterated posterior linearisation pass (IPLF, Garcia-Fernandez et al. 2015; with linearisation transforms the iterated EKF) of the
+ * additive-noise Gaussian filters: the time update of ssmq_filter_forward_dev, (m-, P-) = dynamics transform of (m, P) + G Q G', then
+ * with (m_0, P_0) = (m-, P-), for i = 0 .. iterations - 1 (both transforms use time index k at every iteration):
+ *     y^, S_y, C = measurement transform of (m_i, P_i)          A = C P_i^-1     b = y^ - A m_i     Omega = S_y - A P_i A'
+ *     S = A P- A' + Omega + R      K = P- A' S^-1      m_{i+1} = m- + K (y_k - A m- - b)      P_{i+1} = P- - K S K'
+ * and (fm[k], fP[k]) = (m_J, P_J).  iterations = 1 is ssmq_filter_forward_dev up to rounding; 1 <= iterations <= SSMQ_ITERATED_MAX,
+ * else SSMQ_E_ARG.  d_delta [T][ld] or NULL: max_d |m_J[d] - m_{J-1}[d]| / sqrt(P_J[d][d]) of every step (against m- for one
+ * iteration), the convergence diagnostic - there is no stopping rule.  Only P_i and S are factored; P is read through its lower
+ * triangle and both triangles of fP are written from one value.
+ * Buffers as ssmq_filter_forward_dev.  Failures: a step with a failed factorisation or NaN inputs makes the trajectory's outputs
+ * (delta included) NaN from that step on, d_status[b] = 1 + that step.  A trajectory's results do not depend on the batch around it.
+ * One launch of k_iplf_loop<> where the fused time loop has an instantiation for the pair (the dense kernels), and for a pair with a
+ * user integrand in the range of ssmq_filter_forward_dev, compiled at run time; every other pair that ssmq_filter_innovations_dev
+ * accepts - and every pair under SSMQ_NO_FUSED=1 or with flags bit 0 set - runs apply dyn | iterations x (apply obs | k_iplf_update)
+ * per step.  What ssmq_filter_innovations_dev refuses is refused here, SSMQ_E_UNSUPPORTED before an output is touched.
+ * Asynchronous on the library stream.
+ */
+#define SSMQ_ITERATED_MAX 64
+#define SSMQ_ITERATED_LAUNCH_LOOP 1 /* flags bit 0 */
+int ssmq_filter_iterated_dev(ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, ssmq_transform *h_obs, const ssmq_integrand *f_obs,
+                             int64_t B, int64_t ld, int T, int iterations, int flags, const double *d_y, const double *d_m0,
+                             const double *d_P0, const double *GQG, const double *R, double *d_fm, double *d_fP,
+                             double *d_delta /* [T][ld] or NULL */, int32_t *d_status);
+/* Name of the kernel(s) ssmq_filter_iterated_dev would run for this pair, iteration count and flags. */
+int ssmq_iterated_kernel_name(const ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, const ssmq_transform *h_obs,
+                              const ssmq_integrand *f_obs, int64_t B, int iterations, int flags, char *buf, int len);
 
 /*
  * The path's only collective: independent Monte-Carlo trajectories shard across ranks, one process per

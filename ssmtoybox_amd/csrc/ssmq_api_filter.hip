@@ -732,6 +732,78 @@ extern "C" int ssmq_innovations_kernel_name(const ssmq_transform *h_dyn, const s
     return SSMQ_OK;
 }
 
+// ---- iterated posterior linearisation pass (include/ssmq.h: ssmq_filter_iterated_dev) ------------------------------------------------
+// The refusals and the route choice are those of the innovation scores (innovations_route); flag bit 0 forces the launch loop.
+static const char kIplfLoopName[] = "launch loop of (1 + 2 J) T launches (apply dyn | J x (apply obs | k_iplf_update))";
+static bool iterations_ok(int iterations) {
+    if (iterations >= 1 && iterations <= SSMQ_ITERATED_MAX) return true;
+    set_error("filter_iterated: 1 <= iterations <= " + std::to_string(SSMQ_ITERATED_MAX));
+    return false;
+}
+
+extern "C" int ssmq_filter_iterated_dev(ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, ssmq_transform *h_obs,
+                                        const ssmq_integrand *f_obs, int64_t B, int64_t ld, int T, int iterations, int flags,
+                                        const double *d_y, const double *d_m0, const double *d_P0, const double *GQG, const double *R,
+                                        double *d_fm, double *d_fP, double *d_delta, int32_t *d_status) {
+    SSMQ_HANDLE_LOCK(h_dyn, h_obs);
+    if (!h_dyn || !h_obs || !f_dyn || !f_obs || B < 0 || ld < B || T < 0 || !d_y || !d_m0 || !d_P0 || !d_fm || !d_fP || !d_status ||
+        (flags & ~1)) {
+        set_error("filter_iterated: bad argument");
+        return SSMQ_E_ARG;
+    }
+    if (!iterations_ok(iterations)) return SSMQ_E_ARG;
+    PairForms pf;
+    bool user_ekf = false, one_launch = false;
+    int rc = innovations_route(h_dyn, f_dyn, h_obs, f_obs, &pf, &user_ekf, &one_launch);
+    if (rc) return rc;
+    if ((flags & 1) && !pf.user) one_launch = false;      // (a user pair without Jacobians has no launch loop)
+    const int D = h_dyn->D, Y = h_obs->E;
+    if ((rc = ensure_device())) return rc;
+    if (B == 0) return SSMQ_OK;
+    hipStream_t s = stream();
+    if (T == 0) {   // nothing to filter: every trajectory is trivially fine
+        SSMQ_HIP(hipMemsetAsync(d_status, 0, sizeof(int32_t) * ld, s));
+        return SSMQ_OK;
+    }
+    FilterPass pass;
+    PassConsts pc;
+    if ((rc = make_filter_pass(h_dyn, f_dyn, h_obs, f_obs, B, ld, T, d_y, d_m0, d_P0, d_fm, d_fP, d_status, s, &pass)) ||
+        (rc = cached_pass_consts(f_dyn, f_obs, D, Y, T, GQG, R, nullptr, s, &pc)))
+        return rc;
+    const double *cs = (const double *)g_fc.consts;
+    wire_pass_consts(pass, cs, pc);
+    rc = one_launch ? try_launch_iterated(pass, iterations, d_delta) : 0;
+    if (rc < 0) return rc;
+    if (rc == 1) return SSMQ_OK;
+    if (pf.user && !user_ekf) {
+        set_error("filter_iterated: no run-time kernel for this pair of user integrands");
+        return SSMQ_E_UNSUPPORTED;
+    }
+    if (user_ekf && (rc = prepare_user_ekf(h_dyn, f_dyn, h_obs, f_obs, pf.gq))) return rc;
+    if ((rc = ensure_ws(iterated_ws_bytes(D, Y, ld)))) return rc;
+    return iterated_launch_loop(h_dyn, h_obs, pass, iterations, d_delta, cs + pc.steps, g_fc.ws);
+}
+
+extern "C" int ssmq_iterated_kernel_name(const ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, const ssmq_transform *h_obs,
+                                         const ssmq_integrand *f_obs, int64_t B, int iterations, int flags, char *buf, int len) {
+    SSMQ_HANDLE_LOCK(h_dyn, h_obs);
+    if (!h_dyn || !h_obs || !f_dyn || !f_obs || !buf || len <= 0 || B < 0 || (flags & ~1)) return SSMQ_E_ARG;
+    if (!iterations_ok(iterations)) return SSMQ_E_ARG;
+    PairForms pf;
+    bool user_ekf = false, one_launch = false;
+    int rc = innovations_route(h_dyn, f_dyn, h_obs, f_obs, &pf, &user_ekf, &one_launch);
+    if (rc) return rc;
+    if ((flags & 1) && !pf.user) one_launch = false;
+    const char *name = nullptr;
+    FilterPass query;
+    if ((rc = make_filter_pass(h_dyn, f_dyn, h_obs, f_obs, B, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &query))) return rc;
+    query.name = &name; query.dry_run = true;
+    rc = one_launch ? try_launch_iterated(query, iterations, nullptr) : 0;
+    if (rc < 0) return rc;
+    snprintf(buf, len, "%s", rc == 1 ? name : kIplfLoopName);
+    return SSMQ_OK;
+}
+
 static int metrics_impl(int phase, int D, int64_t B, int64_t ld, int T, const double *d_x, const double *d_fm,
                         const double *d_fP, const int32_t *d_status, const double *mse, double *sums) {
     if (D < 1 || D > SSMQ_MAX_DIM || B < 0 || ld < B || T < 0 || !d_x || !d_fm || !d_fP || !sums || (phase == 2 && !mse)) {

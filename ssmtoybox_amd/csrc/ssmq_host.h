@@ -557,6 +557,20 @@ int launch_innovation_score(int D, int Y, int64_t B, int64_t ld, const double *y
 int launch_innovation_total(int64_t B, int64_t ld, int T, const double *nis, const double *ll, double *total, int32_t *status,
                             hipStream_t s);
 
+// Iterated posterior linearisation pass (ssmq_filter_iterated.hip, ssmq_filter_iterated_dev): `iterations` measurement updates per step,
+// each re-linearised around the current posterior; delta [T][ld] or null.  The whole pass in one launch of k_iplf_loop<>: 1 launched
+// (dry_run: a kernel exists, its name set), 0 no kernel for this pair, < 0 error; a pair with a user integrand runs the instantiation
+// compiled for it at run time (ssmq_rtc.hip) or is an error
+struct IplfArgs;                              // ssmq_iterated_kernel.h
+IplfArgs iplf_args(const FilterPass &p, int iterations, double *delta);
+int try_launch_iterated(const FilterPass &p, int iterations, double *delta);
+int rtc_launch_iterated(const FilterPass &p, int iterations, double *delta);
+// ... and the launch loop of every other pair: per step apply dyn, then iterations x (apply obs | k_iplf_update); ws: iterated_ws_bytes()
+// bytes, tvec: device [T] holding 0 .. T-1
+size_t iterated_ws_bytes(int D, int Y, int64_t ld);
+int iterated_launch_loop(ssmq_transform *h_dyn, ssmq_transform *h_obs, const FilterPass &p, int iterations, double *delta,
+                         const double *tvec, void *ws);
+
 // error sums over a batch of filtered trajectories (ssmq_metrics.hip)
 int metrics_values_per_step(int D);
 int metrics_chunks(int64_t B);

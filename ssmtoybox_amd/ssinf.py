@@ -393,6 +393,101 @@ class GaussianInference:
         return {k: (v[..., 0] if v.ndim else v) for k, v in out.items()}
 
 
+    # ---- iterated posterior linearisation (IPLF): J measurement updates per step, each re-linearised around the posterior ------
+    def _iterated_refusal(self, iterations):
+        """Raises what keeps a filter or an iteration count out of the iterated pass - before the library is touched."""
+        err = self._innovations_refusal()
+        if err is not None:
+            raise NotImplementedError(str(err).replace('innovation scores cover', 'the iterated pass covers'))
+        if isinstance(iterations, bool) or int(iterations) != iterations or not 1 <= int(iterations) <= _lib.ITERATED_MAX:
+            raise ValueError('iterations must be an integer in 1 .. {} (got {!r})'.format(_lib.ITERATED_MAX, iterations))
+        return int(iterations)
+
+    def iterated_kernel_name(self, iterations, batch=0, launch_loop=False):
+        """Which kernel(s) `iterated_pass*` run for this filter: k_iplf_loop<..> (the whole pass in one launch) where the fused time
+        loop has an instantiation, and for user models; else the launch loop apply dyn | J x (apply obs | k_iplf_update)."""
+        iterations = self._iterated_refusal(iterations)
+        self._check_user_points()
+        f_dyn, e_dyn = resolve_integrand(self.mod_dyn.dyn_eval)
+        f_obs, e_obs = resolve_integrand(self.mod_obs.meas_eval)
+        buf = ctypes.create_string_buffer(512)
+        _lib.check(_lib.load().ssmq_iterated_kernel_name(ctypes.c_void_p(self.tf_dyn._handle_for(e_dyn)), ctypes.byref(f_dyn),
+                                                         ctypes.c_void_p(self.tf_obs._handle_for(e_obs)), ctypes.byref(f_obs),
+                                                         int(batch), iterations, _lib.ITERATED_LAUNCH_LOOP if launch_loop else 0, buf, 512),
+                   'ssmq_iterated_kernel_name')
+        return buf.value.decode()
+
+    def _launch_iterated(self, lib, B, ld, T, iterations, flags, d_y, d_m0, d_P0, d_fm, d_fP, d_delta, d_st):
+        f_dyn, e_dyn = resolve_integrand(self.mod_dyn.dyn_eval)
+        f_obs, e_obs = resolve_integrand(self.mod_obs.meas_eval)
+        h_dyn, h_obs = self.tf_dyn._handle_for(e_dyn), self.tf_obs._handle_for(e_obs)
+        gqg, pg = _lib.as_c(self.G.dot(self.q_cov).dot(self.G.T))
+        rr, pr = _lib.as_c(self.r_cov)
+        vp = lambda b: ctypes.c_void_p(b.ptr if b is not None else None)       # noqa: E731
+        _lib.check(lib.ssmq_filter_iterated_dev(ctypes.c_void_p(h_dyn), ctypes.byref(f_dyn), ctypes.c_void_p(h_obs), ctypes.byref(f_obs),
+                                                B, ld, T, iterations, flags, vp(d_y), vp(d_m0), vp(d_P0), pg, pr, vp(d_fm), vp(d_fP),
+                                                vp(d_delta), vp(d_st)), 'ssmq_filter_iterated_dev')
+
+    def iterated_pass_dev(self, d_y, B, ld, T, iterations, launch_loop=False):
+        """`forward_pass_dev` with `iterations` re-linearised measurement updates per step: measurements on the device (planes
+        [T][dim_y][ld]), results left there - DeviceBuffers (d_fm [T][D][ld], d_fP [T][D*D][ld], d_delta [T][ld], d_status [ld]);
+        the caller frees them.  Every trajectory starts from the model's initial moments."""
+        iterations = self._iterated_refusal(iterations)
+        self._check_user_points()
+        lib = _lib.load()
+        D = self.mod_dyn.dim_state
+        d_m0, d_P0 = self._initial_planes(B, ld)
+        d_fm, d_fP = _lib.DeviceBuffer(8 * T * D * ld), _lib.DeviceBuffer(8 * T * D * D * ld)
+        d_delta, d_st = _lib.DeviceBuffer(8 * T * ld), _lib.DeviceBuffer(4 * ld)
+        self._launch_iterated(lib, B, ld, T, iterations, _lib.ITERATED_LAUNCH_LOOP if launch_loop else 0, d_y, d_m0, d_P0, d_fm, d_fP,
+                              d_delta, d_st)
+        _lib.sync()
+        d_m0.free()
+        d_P0.free()
+        return d_fm, d_fP, d_delta, d_st
+
+    def iterated_pass_batch(self, data, iterations, x0_mean=None, x0_cov=None, raise_on_failure=True, return_delta=False,
+                            launch_loop=False):
+        """The forward pass with the iterated posterior linearisation update (IPLF; the iterated EKF for `ExtendedKalman`), data
+        (dim_y, T, B): per step the time update of `forward_pass_batch`, then `iterations` measurement updates of the PRIOR, each
+        with the measurement moments taken around the current posterior (m_0, P_0 = the prior):
+            y^, S_y, C = tf_obs(m_i, P_i);  A = C P_i^-1;  b = y^ - A m_i;  Omega = S_y - A P_i A';  S = A P- A' + Omega + R;
+            K = P- A' S^-1;  m_{i+1} = m- + K (y - A m- - b);  P_{i+1} = P- - K S K'.
+        iterations = 1 is the plain filter up to rounding.  Returns and sets fi_mean (D, T, B), fi_cov (D, D, T, B) and `status` as
+        the forward pass does; with return_delta also delta (T, B) = max_d |m_J - m_{J-1}| / sqrt(P_J[d, d]), the convergence
+        diagnostic (the iteration count is fixed: there is no stopping rule).  launch_loop=True forces the launch-loop route."""
+        iterations = self._iterated_refusal(iterations)
+        self._check_user_points()
+        lib = _lib.load()
+        data = np.asarray(data, dtype=np.float64)
+        Y, T, B = data.shape
+        D = self.mod_dyn.dim_state
+        ld = (B + 63) // 64 * 64
+        d_y = _lib.scratch(8 * T * Y * ld)
+        _lib.upload_study(data, Y, ld, d_y)
+        d_m0, d_P0 = self._initial_planes(B, ld, x0_mean, x0_cov)
+        d_fm, d_fP = _lib.scratch(8 * T * D * ld), _lib.scratch(8 * T * D * D * ld)
+        d_delta, d_st = _lib.scratch(8 * T * ld), _lib.scratch(4 * ld)
+        self._launch_iterated(lib, B, ld, T, iterations, _lib.ITERATED_LAUNCH_LOOP if launch_loop else 0, d_y, d_m0, d_P0, d_fm, d_fP,
+                              d_delta, d_st)
+        fm = _lib.download_study(d_fm, (D,), T, B, ld)
+        fP = _lib.download_study(d_fP, (D, D), T, B, ld)
+        delta = _lib.download_study(d_delta, (), T, B, ld)
+        self.status = d_st.download((ld,), dtype=np.int32)[:B]
+        for buf in (d_y, d_m0, d_P0, d_fm, d_fP, d_delta, d_st):
+            buf.free()
+        if raise_on_failure and self.status.any():
+            b = int(np.flatnonzero(self.status)[0])
+            raise np.linalg.LinAlgError('Matrix is not positive definite (trajectory {}, step {})'.format(b, int(self.status[b]) - 1))
+        self.fi_mean, self.fi_cov = fm, fP
+        return (fm, fP, delta) if return_delta else (fm, fP)
+
+    def iterated_pass(self, data, iterations):
+        """`iterated_pass_batch` for one trajectory, data (dim_y, T) -> filtered means (D, T), covariances (D, D, T)."""
+        fm, fP = self.iterated_pass_batch(np.asarray(data)[..., None], iterations)
+        return fm[..., 0], fP[..., 0]
+
+
 def run_filters(algs, data, x0_mean=None, x0_cov=None, raise_on_failure=True):
     """Several filters over the SAME measurements as one device launch - the loop `for alg in algs: alg.forward_pass(y)` of the
     reference's studies (research/bsq/bsq_ungm.py:132-137, research/tpq/tpq_base.py:175-192), for data of shape (dim_y, T, B).
