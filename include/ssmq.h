@@ -126,8 +126,10 @@ int ssmq_integrand_define_dx(const char *body, const char *jac_body, int din, in
  * (arguments as SSMQ_RTC_FILTER). */
 /* SSMQ_RTC_ITERATED instantiates the iterated-pass kernel k_iplf_loop<D, E (= Y), N, N_obs, id, id_obs, form, tp, 0, 0> (arguments as
  * SSMQ_RTC_FILTER; opt must be 0: the dense kernel is the only one). */
+/* SSMQ_RTC_SMOOTHER_ITERATED instantiates the iterated-smoother kernel k_ipls_pass<D, E (= Y), N, N_obs, id, id_obs, form, tp, 0>
+ * (arguments as SSMQ_RTC_FILTER; opt must be 0: the dense transforms are the only ones). */
 enum ssmq_rtc_kind { SSMQ_RTC_FILTER = 0, SSMQ_RTC_APPLY = 1, SSMQ_RTC_MC = 2, SSMQ_RTC_LINEAR = 3, SSMQ_RTC_TAYLOR_GPQD = 4, SSMQ_RTC_GPQD = 5,
-                     SSMQ_RTC_INNOVATION = 6, SSMQ_RTC_ITERATED = 7 };
+                     SSMQ_RTC_INNOVATION = 6, SSMQ_RTC_ITERATED = 7, SSMQ_RTC_SMOOTHER_ITERATED = 8 };
 int ssmq_rtc_compile_check(int32_t id, int32_t id_obs, int kind, int D, int E, int N, int N_obs, int form, int tp, int opt,
                            const char *arch, char *log, int len);
 /* Process-wide counters of the run-time compiler: programs compiled, kernel lookups served from the cache, compile wall time. */
@@ -1002,6 +1004,43 @@ int ssmq_filter_iterated_dev(ssmq_transform *h_dyn, const ssmq_integrand *f_dyn,
 /* Name of the kernel(s) ssmq_filter_iterated_dev would run for this pair, iteration count and flags. */
 int ssmq_iterated_kernel_name(const ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, const ssmq_transform *h_obs,
                               const ssmq_integrand *f_obs, int64_t B, int iterations, int flags, char *buf, int len);
+
+/*
+ * Iterated posterior linearisation smoother (IPLS; Garcia-Fernandez, Svensson, Sarkka, IEEE TAC 2017) of the additive-noise Gaussian
+ * filters, properly indexed: x_{-1} ~ N(m0, P0), step k = 0 .. T-1: x_k = f(x_{k-1}, k) + G q, y_k = h(x_k, k) + r.  One iteration
+ * takes linearisation moments (ml_j, Pl_j), j = -1 .. T-1 (lower triangle read), and runs
+ *   forward, k = 0 .. T-1, (m, P) the filtered moments of step k - 1 ((m0, P0) for k = 0):
+ *     z, S_z, C_f = dynamics transform of (ml_{k-1}, Pl_{k-1})     F = C_f Pl_{k-1}^-1     Lambda = S_z - F Pl_{k-1} F'
+ *     m- = z + F (m - ml_{k-1})     P- = F P F' + Lambda + G Q G'     C_k = P F'
+ *     y^, S_y, C_h = measurement transform of (ml_k, Pl_k)         H = C_h Pl_k^-1         Omega = S_y - H Pl_k H'
+ *     S = H P- H' + Omega + R     K = P- H' S^-1     m_k = m- + K (y_k - y^ - H (m- - ml_k))     P_k = P- - K S K'
+ *   backward, k = T-1 .. 0, from (ms_{T-1}, Ps_{T-1}) = (m_{T-1}, P_{T-1}), the same bits:
+ *     G_k = C_k (P-_k)^-1     ms_{k-1} = m_{k-1} + G_k (ms_k - m-_k)     Ps_{k-1} = P_{k-1} + G_k (Ps_k - P-_k) G_k'
+ * down to the smoothed initial state (d_sm0, d_sP0).  Iteration 1 linearises at d_lin_m / d_lin_P (plane 0: the initial state, plane
+ * 1 + k: step k) or, when both are NULL, at its own running moments - the plain filter step, so that iterations = 1 is
+ * ssmq_filter_forward_dev up to rounding followed by an RTS pass; iteration i > 1 linearises at the smoothed moments of iteration
+ * i - 1.  Outputs: the filtered (d_fm, d_fP) and smoothed (d_sm, d_sP, d_sm0, d_sP0) moments of the LAST iteration, both triangles
+ * written from one value; d_delta [ld] or NULL: max over k = -1 .. T-1 and d of |ms_k[d] - ref_k[d]| / sqrt(Ps_k[d][d]) with ref the
+ * smoothed means of the iteration before (d_lin_m in iteration 1; the filtered means without it) - there is no stopping rule.
+ * 1 <= iterations <= SSMQ_ITERATED_MAX and flags == 0 (reserved), else SSMQ_E_ARG.
+ * Failures: a factorisation that fails (Pl by the transforms, S, P-_k) or a filtered mean that is not finite, in any step of any
+ * iteration, makes EVERY output of the trajectory NaN (delta included); d_status[b] = 1 + that step in the first iteration that
+ * fails (forward sweep first), 0 otherwise.  A trajectory's results do not depend on the batch around it.
+ * One launch of k_ipls_pass<> per iteration, for the pairs the fused time loop has a dense instantiation for and, compiled at run
+ * time, for pairs with a user integrand (sigma-point and BQ forms, 2 .. 2 D + 1 points).  Everything else - other point counts,
+ * linearisation, Taylor-GPQD, GPQ+D, truncated and multi-output transforms, models that take their noise as an argument - is
+ * SSMQ_E_UNSUPPORTED, like every refusal before an output or d_status is touched.  The workspace (the planes the two sweeps share,
+ * two sets of smoothed moments) is allocated per call.  Synchronous.
+ */
+int ssmq_smoother_iterated_dev(ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, ssmq_transform *h_obs, const ssmq_integrand *f_obs,
+                               int64_t B, int64_t ld, int T, const double *d_y, const double *d_m0, const double *d_P0,
+                               const double *GQG, const double *R, int iterations, int flags,
+                               const double *d_lin_m /* [T+1][D][ld] or NULL */, const double *d_lin_P /* [T+1][D*D][ld] or NULL */,
+                               double *d_fm, double *d_fP, double *d_sm, double *d_sP, double *d_sm0 /* [D][ld] */,
+                               double *d_sP0 /* [D*D][ld] */, double *d_delta /* [ld] or NULL */, int32_t *d_status);
+/* Name of the kernel ssmq_smoother_iterated_dev would run for this pair (SSMQ_E_UNSUPPORTED where it has none). */
+int ssmq_smoother_iterated_kernel_name(const ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, const ssmq_transform *h_obs,
+                                       const ssmq_integrand *f_obs, int iterations, char *buf, int len);
 
 /*
  * The path's only collective: independent Monte-Carlo trajectories shard across ranks, one process per

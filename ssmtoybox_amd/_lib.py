@@ -30,6 +30,7 @@ F_CTRS_DYN, F_CV_DYN, F_REENTRY2D_BIAS_DYN, F_SMOOTH10D_DYN = 13, 14, 15, 16
 # user-defined integrands, compiled for the device at run time (include/ssmq.h ssmq_integrand_define)
 F_USER_FIRST, F_USER_SLOTS, USER_BODY_MAX, USER_MAX_D, USER_MAX_Y = 1024, 64, 8192, 6, 4
 RTC_FILTER, RTC_APPLY, RTC_MC, RTC_LINEAR, RTC_TAYLOR_GPQD, RTC_GPQD, RTC_INNOVATION, RTC_ITERATED = 0, 1, 2, 3, 4, 5, 6, 7
+RTC_SMOOTHER_ITERATED = 8
 ITERATED_MAX = 64          # SSMQ_ITERATED_MAX
 ITERATED_LAUNCH_LOOP = 1   # flags bit 0 of ssmq_filter_iterated_dev
 
@@ -260,6 +261,11 @@ _PROTOTYPES = {
                                  [ctypes.c_void_p] * 3 + [c_double_p, c_double_p] + [ctypes.c_void_p] * 4),
     'ssmq_iterated_kernel_name': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Integrand), ctypes.c_void_p, ctypes.POINTER(Integrand),
                                                  ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_char_p, ctypes.c_int]),
+    'ssmq_smoother_iterated_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Integrand), ctypes.c_void_p, ctypes.POINTER(Integrand),
+                                                  ctypes.c_int64, ctypes.c_int64, ctypes.c_int] + [ctypes.c_void_p] * 3 +
+                                   [c_double_p, c_double_p, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 10),
+    'ssmq_smoother_iterated_kernel_name': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Integrand), ctypes.c_void_p,
+                                                          ctypes.POINTER(Integrand), ctypes.c_int, ctypes.c_char_p, ctypes.c_int]),
     'ssmq_rbf_eval': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_int, c_double_p, c_double_p,
                                      ctypes.c_int, ctypes.c_int, ctypes.c_int, c_double_p]),
     'ssmq_rbf_factor': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, c_double_p, c_double_p, ctypes.c_int, ctypes.c_int,

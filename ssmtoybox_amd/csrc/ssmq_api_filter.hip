@@ -804,6 +804,99 @@ extern "C" int ssmq_iterated_kernel_name(const ssmq_transform *h_dyn, const ssmq
     return SSMQ_OK;
 }
 
+// ---- iterated posterior linearisation smoother (include/ssmq.h: ssmq_smoother_iterated_dev) ------------------------------------------
+// The refusals of the innovation scores, then: a pair runs k_ipls_pass<> (a table shape, or a user pair compiled at run time) or is
+// refused - there is no launch-loop route.  Both entry points ask the table by a dry run, before anything is written.
+static int ipls_route(const ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, const ssmq_transform *h_obs, const ssmq_integrand *f_obs,
+                      int iterations, const char **name) {
+    if (iterations < 1 || iterations > SSMQ_ITERATED_MAX) {
+        set_error("smoother_iterated: 1 <= iterations <= " + std::to_string(SSMQ_ITERATED_MAX));
+        return SSMQ_E_ARG;
+    }
+    PairForms pf;
+    bool user_ekf = false, one_launch = false;
+    int rc = innovations_route(h_dyn, f_dyn, h_obs, f_obs, &pf, &user_ekf, &one_launch);
+    if (rc) return rc;
+    FilterPass query;
+    if ((rc = make_filter_pass(h_dyn, f_dyn, h_obs, f_obs, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &query))) return rc;
+    query.name = name; query.dry_run = true;
+    const bool covered = !user_ekf && !pf.mo && !pf.trunc && !pf.gq && !jac_form(h_dyn) && !jac_form(h_obs);
+    rc = covered ? try_launch_ipls(query, IplsPlanes{}) : 0;
+    if (rc < 0) return rc;
+    if (rc == 1) return SSMQ_OK;
+    set_error("smoother_iterated: covers the sigma-point and BQ pairs the fused time loop is instantiated for (unscented and "
+              "spherical-radial point sets of the built-in model pairs) and user models through the run-time compiler; not other point "
+              "counts (Gauss-Hermite), linearisation, Taylor-GPQD, GPQ+D, truncated or multi-output transforms");
+    return SSMQ_E_UNSUPPORTED;
+}
+
+extern "C" int ssmq_smoother_iterated_dev(ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, ssmq_transform *h_obs,
+                                          const ssmq_integrand *f_obs, int64_t B, int64_t ld, int T, const double *d_y, const double *d_m0,
+                                          const double *d_P0, const double *GQG, const double *R, int iterations, int flags,
+                                          const double *d_lin_m, const double *d_lin_P, double *d_fm, double *d_fP, double *d_sm,
+                                          double *d_sP, double *d_sm0, double *d_sP0, double *d_delta, int32_t *d_status) {
+    SSMQ_HANDLE_LOCK(h_dyn, h_obs);
+    if (!h_dyn || !h_obs || !f_dyn || !f_obs || B < 0 || ld < B || T < 0 || !d_y || !d_m0 || !d_P0 || !d_fm || !d_fP || !d_sm || !d_sP ||
+        !d_sm0 || !d_sP0 || !d_status || flags != 0 || (d_lin_m == nullptr) != (d_lin_P == nullptr)) {
+        set_error("smoother_iterated: bad argument (flags is reserved: 0; lin_m and lin_P come together)");
+        return SSMQ_E_ARG;
+    }
+    const char *name = nullptr;
+    int rc = ipls_route(h_dyn, f_dyn, h_obs, f_obs, iterations, &name);
+    if (rc) return rc;
+    const int D = h_dyn->D, Y = h_obs->E;
+    if ((rc = ensure_device())) return rc;
+    if (B == 0) return SSMQ_OK;
+    hipStream_t s = stream();
+    SSMQ_HIP(hipMemsetAsync(d_status, 0, sizeof(int32_t) * ld, s));
+    if (T == 0) {   // nothing to smooth: the initial state is its own smoothed state
+        SSMQ_HIP(hipMemcpyAsync(d_sm0, d_m0, sizeof(double) * D * ld, hipMemcpyDeviceToDevice, s));
+        SSMQ_HIP(hipMemcpyAsync(d_sP0, d_P0, sizeof(double) * D * D * ld, hipMemcpyDeviceToDevice, s));
+        if (d_delta) SSMQ_HIP(hipMemsetAsync(d_delta, 0, sizeof(double) * ld, s));
+        SSMQ_HIP(hipStreamSynchronize(s));
+        return SSMQ_OK;
+    }
+    // the planes the two sweeps share and, for more than one iteration, one or two sets of smoothed moments [T+1][D + D*D][ld]
+    const size_t DP = (size_t)D * (D + 1) / 2, set = (size_t)(T + 1) * (D + D * D) * ld;
+    const int n_sets = iterations == 1 ? 0 : (iterations == 2 ? 1 : 2);
+    DevBuf ws, sets;
+    if ((rc = ws.alloc(sizeof(double) * (size_t)T * (D + DP + (size_t)D * D) * ld)) || (rc = sets.alloc(sizeof(double) * set * n_sets))) return rc;
+    FilterPass pass;
+    PassConsts pc;
+    if ((rc = make_filter_pass(h_dyn, f_dyn, h_obs, f_obs, B, ld, T, d_y, d_m0, d_P0, d_fm, d_fP, d_status, s, &pass)) ||
+        (rc = cached_pass_consts(f_dyn, f_obs, D, Y, T, GQG, R, nullptr, s, &pc)))
+        return rc;
+    wire_pass_consts(pass, (const double *)g_fc.consts, pc);
+    IplsPlanes q;
+    q.pm = ws.d(); q.pP = q.pm + (size_t)T * D * ld; q.pC = q.pP + (size_t)T * DP * ld;
+    q.lin_m = d_lin_m; q.lin_P = d_lin_P;
+    for (int i = 0; i < iterations && !rc; ++i) {
+        const bool last = i == iterations - 1;
+        double *om = last ? nullptr : sets.d() + (size_t)(i & 1) * set, *oP = last ? nullptr : om + (size_t)(T + 1) * D * ld;
+        q.sm0 = last ? d_sm0 : om;  q.sm = last ? d_sm : om + (size_t)D * ld;
+        q.sP0 = last ? d_sP0 : oP;  q.sP = last ? d_sP : oP + (size_t)D * D * ld;
+        q.delta = last ? d_delta : nullptr;
+        rc = try_launch_ipls(pass, q);
+        rc = rc == 1 ? 0 : (rc == 0 ? SSMQ_E_UNSUPPORTED : rc);
+        q.lin_m = om; q.lin_P = oP;
+    }
+    hipError_t e = hipStreamSynchronize(s);      // (the workspace is released when this call returns)
+    if (rc) return rc;
+    SSMQ_HIP(e);
+    return SSMQ_OK;
+}
+
+extern "C" int ssmq_smoother_iterated_kernel_name(const ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, const ssmq_transform *h_obs,
+                                                  const ssmq_integrand *f_obs, int iterations, char *buf, int len) {
+    SSMQ_HANDLE_LOCK(h_dyn, h_obs);
+    if (!h_dyn || !h_obs || !f_dyn || !f_obs || !buf || len <= 0) return SSMQ_E_ARG;
+    const char *name = nullptr;
+    int rc = ipls_route(h_dyn, f_dyn, h_obs, f_obs, iterations, &name);
+    if (rc) return rc;
+    snprintf(buf, len, "%s", name ? name : "k_ipls_pass");
+    return SSMQ_OK;
+}
+
 static int metrics_impl(int phase, int D, int64_t B, int64_t ld, int T, const double *d_x, const double *d_fm,
                         const double *d_fP, const int32_t *d_status, const double *mse, double *sums) {
     if (D < 1 || D > SSMQ_MAX_DIM || B < 0 || ld < B || T < 0 || !d_x || !d_fm || !d_fP || !sums || (phase == 2 && !mse)) {

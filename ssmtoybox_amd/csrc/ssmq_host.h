@@ -571,6 +571,23 @@ size_t iterated_ws_bytes(int D, int Y, int64_t ld);
 int iterated_launch_loop(ssmq_transform *h_dyn, ssmq_transform *h_obs, const FilterPass &p, int iterations, double *delta,
                          const double *tvec, void *ws);
 
+// Iterated posterior linearisation smoother (ssmq_filter_ipls.hip, ssmq_smoother_iterated_dev): ONE iteration - the forward sweep and
+// the backward sweep - is one launch of k_ipls_pass<> (ssmq_ipls_kernel.h).  The planes of an iteration besides those of the pass
+// (p.fm / p.fP: its filtered moments, p.status: read and written): the linearisation moments it reads (both null: the running
+// moments), the workspace the two sweeps share, the smoothed moments it writes, delta [ld] or null.  try_launch_ipls: 1 launched
+// (dry_run: a kernel exists, its name set), 0 no kernel for this pair, < 0 error; a pair with a user integrand runs the
+// instantiation compiled for it at run time (ssmq_rtc.hip) or is an error
+struct IplsPlanes {
+    const double *lin_m, *lin_P;   // [T+1][D][ld], [T+1][D*D][ld]
+    double *pm, *pP, *pC;          // [T][D][ld], [T][D(D+1)/2][ld], [T][D*D][ld]
+    double *sm0, *sP0, *sm, *sP;   // [D][ld], [D*D][ld], [T][D][ld], [T][D*D][ld]
+    double *delta;
+};
+struct IplsArgs;                              // ssmq_ipls_kernel.h
+IplsArgs ipls_args(const FilterPass &p, const IplsPlanes &q);
+int try_launch_ipls(const FilterPass &p, const IplsPlanes &q);
+int rtc_launch_ipls(const FilterPass &p, const IplsPlanes &q);
+
 // error sums over a batch of filtered trajectories (ssmq_metrics.hip)
 int metrics_values_per_step(int D);
 int metrics_chunks(int64_t B);

@@ -487,6 +487,133 @@ class GaussianInference:
         fm, fP = self.iterated_pass_batch(np.asarray(data)[..., None], iterations)
         return fm[..., 0], fP[..., 0]
 
+    # ---- iterated posterior linearisation smoother (IPLS): forward and backward sweep, re-linearised around the smoothed moments ----
+    _IPLS_RANGE = ('the iterated smoother covers the additive-noise Gaussian filters with unscented or spherical-radial point sets '
+                   '(sigma-point, GP and t-process quadrature) on the built-in model pairs of the fused time loop, and user models '
+                   '(device_code) with 2 .. 2 D + 1 points')
+
+    def _ipls_refusal(self, iterations):
+        """Raises what keeps a filter or an iteration count out of the iterated smoother - before the library is touched."""
+        err = self._innovations_refusal()
+        if err is not None:
+            raise NotImplementedError(str(err).replace('innovation scores cover', 'the iterated smoother covers'))
+        from .mtran import TruncatedSigmaPointTransform
+        from .bq.bqmtran import _MultiOutputTransform
+        for tf in (self.tf_dyn, self.tf_obs):
+            for cls, what in ((LinearizationTransform, 'linearisation (the iterated extended Kalman smoother)'), (TaylorGPQDTransform, 'Taylor-GPQD'),
+                              (GaussianProcessDerTransform, 'GPQ+D'), (TruncatedSigmaPointTransform, 'truncated'),
+                              (_MultiOutputTransform, 'multi-output'), (GaussHermiteTransform, 'Gauss-Hermite')):
+                if isinstance(tf, cls):
+                    raise NotImplementedError('{}; not implemented for {} transforms'.format(self._IPLS_RANGE, what))
+        if isinstance(iterations, bool) or int(iterations) != iterations or not 1 <= int(iterations) <= _lib.ITERATED_MAX:
+            raise ValueError('iterations must be an integer in 1 .. {} (got {!r})'.format(_lib.ITERATED_MAX, iterations))
+        return int(iterations)
+
+    def _ipls_handles(self):
+        f_dyn, e_dyn = resolve_integrand(self.mod_dyn.dyn_eval)
+        f_obs, e_obs = resolve_integrand(self.mod_obs.meas_eval)
+        return self.tf_dyn._handle_for(e_dyn), f_dyn, self.tf_obs._handle_for(e_obs), f_obs
+
+    @staticmethod
+    def _ipls_check(rc, what):
+        if rc == -3:             # SSMQ_E_UNSUPPORTED: the pair has no kernel (another point count, ...)
+            raise NotImplementedError(_lib.last_error())
+        _lib.check(rc, what)
+
+    def iterated_smoother_kernel_name(self, iterations):
+        """Which kernel `iterated_smoother*` launches once per iteration for this filter: k_ipls_pass<..>."""
+        iterations = self._ipls_refusal(iterations)
+        self._check_user_points()
+        h_dyn, f_dyn, h_obs, f_obs = self._ipls_handles()
+        buf = ctypes.create_string_buffer(512)
+        self._ipls_check(_lib.load().ssmq_smoother_iterated_kernel_name(ctypes.c_void_p(h_dyn), ctypes.byref(f_dyn), ctypes.c_void_p(h_obs),
+                                                                       ctypes.byref(f_obs), iterations, buf, 512),
+                         'ssmq_smoother_iterated_kernel_name')
+        return buf.value.decode()
+
+    def _launch_ipls(self, lib, B, ld, T, iterations, d_y, d_m0, d_P0, d_lin_m, d_lin_P, outs):
+        h_dyn, f_dyn, h_obs, f_obs = self._ipls_handles()
+        gqg, pg = _lib.as_c(self.G.dot(self.q_cov).dot(self.G.T))
+        rr, pr = _lib.as_c(self.r_cov)
+        vp = lambda b: ctypes.c_void_p(b.ptr if b is not None else None)       # noqa: E731
+        self._ipls_check(lib.ssmq_smoother_iterated_dev(ctypes.c_void_p(h_dyn), ctypes.byref(f_dyn), ctypes.c_void_p(h_obs), ctypes.byref(f_obs),
+                                                        B, ld, T, vp(d_y), vp(d_m0), vp(d_P0), pg, pr, iterations, 0, vp(d_lin_m),
+                                                        vp(d_lin_P), *[vp(b) for b in outs]), 'ssmq_smoother_iterated_dev')
+
+    def iterated_smoother_dev(self, d_y, B, ld, T, iterations):
+        """The iterated smoother on measurements that are already on the device (planes [T][dim_y][ld]), results left there:
+        DeviceBuffers (d_fm [T][D][ld], d_fP [T][D*D][ld], d_sm, d_sP likewise, d_sm0 [D][ld], d_sP0 [D*D][ld], d_delta [ld], d_status
+        [ld] int32); the caller frees them.  Every trajectory starts from the model's initial moments."""
+        iterations = self._ipls_refusal(iterations)
+        self._check_user_points()
+        lib = _lib.load()
+        D = self.mod_dyn.dim_state
+        d_m0, d_P0 = self._initial_planes(B, ld)
+        outs = [_lib.DeviceBuffer(n) for n in (8 * T * D * ld, 8 * T * D * D * ld, 8 * T * D * ld, 8 * T * D * D * ld, 8 * D * ld,
+                                               8 * D * D * ld, 8 * ld, 4 * ld)]
+        self._launch_ipls(lib, B, ld, T, iterations, d_y, d_m0, d_P0, None, None, outs)
+        d_m0.free()
+        d_P0.free()
+        return tuple(outs)
+
+    def iterated_smoother_batch(self, data, iterations=3, x0_mean=None, x0_cov=None, raise_on_failure=True, return_delta=False,
+                                lin_mean=None, lin_cov=None):
+        """The iterated posterior linearisation smoother (IPLS, Garcia-Fernandez, Svensson, Sarkka 2017), data (dim_y, T, B).  With
+        x_{-1} ~ N(x0_mean, x0_cov) and step k = 0 .. T-1 (both transforms of step k use time index k), every iteration linearises
+        the dynamics at (ml_{k-1}, Pl_{k-1}) and the measurement at (ml_k, Pl_k) by statistical linear regression, runs the affine
+        Kalman filter and an RTS pass on the linearised model down to the initial state; iteration i > 1 takes the smoothed moments
+        of iteration i - 1, iteration 1 `lin_mean` (D, T + 1, B) / `lin_cov` (D, D, T + 1, B) (column 0: the initial state) or,
+        without them, its own running moments - so iterations = 1 is the plain filter and a properly indexed RTS smoother (the last
+        smoothed step IS the filtered one; `backward_pass` keeps the reference's index quirk instead).
+        Returns sm (D, T, B), sP (D, D, T, B) and with return_delta also delta (B,) = max_{k,d} |ms_k - ms_k of the iteration
+        before| / sqrt(Ps_k[d, d]) (there is no stopping rule); sets sm_mean, sm_cov, fi_mean, fi_cov (the last iteration's filtered
+        moments), sm_x0_mean (D, B), sm_x0_cov (D, D, B) and status (0, or 1 + the failing step of the first failing iteration: every
+        output of that trajectory is NaN)."""
+        iterations = self._ipls_refusal(iterations)
+        self._check_user_points()
+        if (lin_mean is None) != (lin_cov is None):
+            raise ValueError('lin_mean and lin_cov come together')
+        lib = _lib.load()
+        data = np.asarray(data, dtype=np.float64)
+        Y, T, B = data.shape
+        D = self.mod_dyn.dim_state
+        ld = (B + 63) // 64 * 64
+        d_y = _lib.scratch(8 * T * Y * ld)
+        _lib.upload_study(data, Y, ld, d_y)
+        d_m0, d_P0 = self._initial_planes(B, ld, x0_mean, x0_cov)
+        d_lm = d_lP = None
+        if lin_mean is not None:
+            lin_mean, lin_cov = np.asarray(lin_mean, dtype=np.float64), np.asarray(lin_cov, dtype=np.float64)
+            if lin_mean.shape != (D, T + 1, B) or lin_cov.shape != (D, D, T + 1, B):
+                raise ValueError('lin_mean (D, T + 1, B) and lin_cov (D, D, T + 1, B) expected')
+            d_lm, d_lP = _lib.scratch(8 * (T + 1) * D * ld), _lib.scratch(8 * (T + 1) * D * D * ld)
+            _lib.upload_study(lin_mean, D, ld, d_lm)
+            _lib.upload_study(lin_cov.reshape(D * D, T + 1, B), D * D, ld, d_lP)
+        outs = [_lib.scratch(n) for n in (8 * T * D * ld, 8 * T * D * D * ld, 8 * T * D * ld, 8 * T * D * D * ld, 8 * D * ld, 8 * D * D * ld,
+                                          8 * ld, 4 * ld)]
+        try:
+            self._launch_ipls(lib, B, ld, T, iterations, d_y, d_m0, d_P0, d_lm, d_lP, outs)
+            fm, fP = _lib.download_study(outs[0], (D,), T, B, ld), _lib.download_study(outs[1], (D, D), T, B, ld)
+            sm, sP = _lib.download_study(outs[2], (D,), T, B, ld), _lib.download_study(outs[3], (D, D), T, B, ld)
+            sm0 = outs[4].download((D, ld))[:, :B].copy()
+            sP0 = outs[5].download((D, D, ld))[..., :B].copy()
+            delta = outs[6].download((ld,))[:B].copy()
+            self.status = outs[7].download((ld,), dtype=np.int32)[:B].copy()
+        finally:
+            for buf in [d_y, d_m0, d_P0] + outs + [b for b in (d_lm, d_lP) if b is not None]:
+                buf.free()
+        if raise_on_failure and self.status.any():
+            b = int(np.flatnonzero(self.status)[0])
+            raise np.linalg.LinAlgError('Matrix is not positive definite (trajectory {}, step {})'.format(b, int(self.status[b]) - 1))
+        self.fi_mean, self.fi_cov, self.sm_mean, self.sm_cov = fm, fP, sm, sP
+        self.sm_x0_mean, self.sm_x0_cov = sm0, sP0
+        return (sm, sP, delta) if return_delta else (sm, sP)
+
+    def iterated_smoother(self, data, iterations=3):
+        """`iterated_smoother_batch` for one trajectory, data (dim_y, T) -> smoothed means (D, T), covariances (D, D, T)."""
+        sm, sP = self.iterated_smoother_batch(np.asarray(data)[..., None], iterations)
+        return sm[..., 0], sP[..., 0]
+
 
 def run_filters(algs, data, x0_mean=None, x0_cov=None, raise_on_failure=True):
     """Several filters over the SAME measurements as one device launch - the loop `for alg in algs: alg.forward_pass(y)` of the
