@@ -1043,6 +1043,52 @@ int ssmq_smoother_iterated_kernel_name(const ssmq_transform *h_dyn, const ssmq_i
                                        const ssmq_integrand *f_obs, int iterations, char *buf, int len);
 
 /*
+ * Bootstrap particle filter (sequential Monte Carlo; Gordon, Salmond, Smith 1993) of the additive-noise models: the ground truth the
+ * moment-matching filters are measured against.  N weighted particles per trajectory, in the time convention of
+ * ssmq_filter_forward_dev (both models of step j, 0-based, are evaluated at time j):
+ *     x_{-1,i} = m0_b + chol(P0_b) z                                            initial particles, log w_{-1,i} = -log N
+ *     x_{j,i}  = f(x_{j-1,a(i)}, j) + G (q_mean + L_q z)                        j = 0 .. T-1, a(i) the ancestors chosen after step j-1
+ *     log w_{j,i} = log w_{j-1,a(i)} + log p(y_j | h(x_{j,i}, j))               Gaussian noise: N(y; h + r_mean, R);  Student-t noise:
+ *                                                                               const - (dof + Y) / 2 log(1 + delta^2 / dof), scale R
+ * Per step, in this order: log-sum-exp normalisation with the maximum subtracted; ll[j] = log sum_i w~_{j-1,i} p(y_j | x_{j,i}) with w~ the
+ * normalised weights before the step; fm[j] = sum w~ x; fP[j] = sum w~ (x - fm)(x - fm)' by a second pass around the mean (both
+ * triangles written from one value); ess[j] = 1 / sum w~^2; then systematic resampling - always if ess_threshold >= 1, never if
+ * ess_threshold <= 0, else when ess[j] < ess_threshold N: one uniform u_j, positions p_i = (i + u_j) / N, the CDF the inclusive prefix
+ * sum of w~ with its last entry forced to 1, a(i) the smallest m with cdf[m] > p_i, the weights reset to 1 / N.  Without resampling
+ * a(i) = i.
+ * Random numbers: Philox4x32-10 keyed by `seed`, counter (traj_offset + b lo, hi, step, tag), tag = purpose << 28 | particle << 4 | pair,
+ * normals by Box-Muller, two per counter (pair p gives z[2 p], z[2 p + 1]).  Purpose 8: the initial particles (step 0); 9: the process
+ * noise of step j; 10: the resampling uniform of step j (particle 0, pair 0).  These tags lie above every tag of ssmq_simulate*_dev, so
+ * a filter run with the seed of its data is independent of the data.  Every sum and the prefix sum run in an order fixed by N alone:
+ * a trajectory's bits depend on seed, its global index traj_offset + b, N, ess_threshold and its own inputs - not on B or the device.
+ * Buffers: d_y [T][Y][ld], d_m0 [D][ld], d_P0 [D*D][ld] (lower triangle read) as for ssmq_filter_forward_dev; outputs d_fm [T][D][ld],
+ * d_fP [T][D*D][ld], d_status [ld] in the layout of the Gaussian filters (ssmq_error_sums_dev and ssmq_traj_scores_dev take them
+ * unchanged); d_loglik [T+1][ld], row T the total (summed in ascending j); d_ess [T][ld].  Host arrays: q_mean [dq] (NULL = 0), q_chol
+ * [dq*dq] lower factor, G [D*dq] (NULL = eye(D, dq)); r: SSMQ_RV_GAUSS or SSMQ_RV_STUDENT of dimension Y with n_comp <= 1, chol the lower
+ * factor of R (the scale matrix for Student-t; dof > 0), mean NULL = 0.  Optional outputs, each may be NULL - together the weighted
+ * posterior sample: d_part [T][D][B][N] the particles of step j after propagation; d_logw [T][B][N] their normalised log-weights after
+ * the measurement of step j, before resampling; d_anc [T][B][N] int32 the ancestors chosen after step j (the identity without resampling).
+ * Failures: a step whose largest log-weight is not finite (a NaN measurement, a NaN among the weights, every particle at zero
+ * likelihood) fails the trajectory: d_status[b] = 1 + j, and fm, fP, loglik (the total included) and ess are NaN from step j on (d_logw
+ * NaN and d_anc -1 from step j, d_part NaN from step j + 1); other trajectories are unaffected.
+ * Range: built-in integrands with additive noise, the transition without a state index; 1 <= D <= 6, 1 <= Y <= 4, 1 <= dq <= 6; N a
+ * multiple of 64, 64 <= N <= 4096, (2 D + 1) N <= 13312 (the cloud lives in LDS: 104 KB).  User integrands, SSMQ_F_UNGMNA_*,
+ * SSMQ_F_CTRS_DYN (noise as an argument), SSMQ_RV_MIXTURE noise and larger shapes are SSMQ_E_UNSUPPORTED; an N that is no multiple of
+ * 64 or below 64, T < 1, a NaN ess_threshold, null pointers and mismatched dimensions SSMQ_E_ARG - both before the device, an output or
+ * d_status is touched.  B == 0: nothing happens.  One launch of k_particle_filter<D> (one trajectory per workgroup of 256 threads,
+ * particle i on thread i mod 256, the time loop inside).  Synchronous.
+ */
+int ssmq_particle_filter_dev(const ssmq_integrand *f_dyn, const ssmq_integrand *f_obs, int D, int Y, int dq, int N, int64_t B, int64_t ld,
+                             int T, const double *d_y, const double *d_m0, const double *d_P0, const double *q_mean,
+                             const double *q_chol, const double *G, const ssmq_rv *r, double ess_threshold, uint64_t seed,
+                             uint64_t traj_offset, double *d_fm, double *d_fP, double *d_loglik, double *d_ess, int32_t *d_status,
+                             double *d_part, double *d_logw, int32_t *d_anc);
+/* Name of the kernel ssmq_particle_filter_dev would run, with the LDS it requests: the range check of that call without a device
+ * (the same return codes; T is not part of it). */
+int ssmq_particle_kernel_name(const ssmq_integrand *f_dyn, const ssmq_integrand *f_obs, int D, int Y, int dq, int N, const ssmq_rv *r,
+                              char *buf, int len);
+
+/*
  * The path's only collective: independent Monte-Carlo trajectories shard across ranks, one process per
  * GPU, and only the per-time-step error sums are added at the end (the reference loops `for imc in range(mc)` in one
  * process and averages with numpy: research/tpq/tpq_base.py:154-172, utils.py:113-120).  RCCL over xGMI, opened at run

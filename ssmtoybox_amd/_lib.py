@@ -229,6 +229,12 @@ _PROTOTYPES = {
                                             ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
                                             ctypes.c_int, ctypes.c_double, ctypes.c_uint64, ctypes.c_uint64,
                                             ctypes.c_void_p, ctypes.c_void_p]),
+    'ssmq_particle_filter_dev': (ctypes.c_int, [ctypes.POINTER(Integrand), ctypes.POINTER(Integrand), ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int] + [ctypes.c_void_p] * 3 +
+                                 [c_double_p, c_double_p, c_double_p, ctypes.POINTER(Rv), ctypes.c_double, ctypes.c_uint64, ctypes.c_uint64] +
+                                 [ctypes.c_void_p] * 8),
+    'ssmq_particle_kernel_name': (ctypes.c_int, [ctypes.POINTER(Integrand), ctypes.POINTER(Integrand), ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                 ctypes.c_int, ctypes.POINTER(Rv), ctypes.c_char_p, ctypes.c_int]),
     'ssmq_error_sums_width': (ctypes.c_int, [ctypes.c_int]),
     'ssmq_error_sums_dev': (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p,
                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_double_p]),
@@ -447,6 +453,11 @@ class DeviceBuffer:
     def zero(self):
         check(load().ssmq_memset(ctypes.c_void_p(self.ptr), 0, ctypes.c_size_t(self.nbytes)), 'ssmq_memset')
 
+    def view(self, byte_offset):
+        """The rest of the block from `byte_offset` on as a buffer that owns nothing (e.g. the planes of a study from its second step
+        on); valid while this block is."""
+        return DeviceView(self.ptr + int(byte_offset), self.nbytes - int(byte_offset))
+
     def free(self):
         if self.ptr:
             load().ssmq_free(ctypes.c_void_p(self.ptr))
@@ -457,6 +468,19 @@ class DeviceBuffer:
             self.free()
         except Exception:
             pass
+
+
+class DeviceView(DeviceBuffer):
+    """Part of another buffer's block: free() and deletion leave the block alone."""
+
+    def __init__(self, ptr, nbytes):
+        self.ptr, self.nbytes = ptr, int(nbytes)
+
+    def free(self):
+        self.ptr = None
+
+    def __del__(self):
+        pass
 
 
 class _ScratchPool:

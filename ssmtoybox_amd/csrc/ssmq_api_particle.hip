@@ -1,0 +1,148 @@
+// C entry points of the bootstrap particle filter (include/ssmq.h: ssmq_particle_filter_dev, ssmq_particle_kernel_name): the range
+// check, the host-side constants (noise factors padded to the kernel's strides, the measurement density's log-normaliser) and the
+// launch of k_particle_filter<D> (ssmq_particle.hip).
+#include <cmath>
+#include <cstdio>
+#include "ssmq_particle.h"
+
+namespace ssmq {
+namespace {
+
+// models that take their noise as an argument: no likelihood in closed form
+bool pf_noise_is_argument(int fid) { return fid == SSMQ_F_UNGMNA_DYN || fid == SSMQ_F_UNGMNA_MEAS || fid == SSMQ_F_CTRS_DYN; }
+
+// everything about a call that can be decided without a device: SSMQ_OK, SSMQ_E_ARG or SSMQ_E_UNSUPPORTED (error text set)
+int pf_check(const char *what, const ssmq_integrand *f_dyn, const ssmq_integrand *f_obs, int D, int Y, int dq, int N, const ssmq_rv *r) {
+    char msg[512];
+    if (!f_dyn || !f_obs || !r) {
+        snprintf(msg, sizeof(msg), "%s: null model or noise pointer", what);
+        set_error(msg);
+        return SSMQ_E_ARG;
+    }
+    if (is_user_integrand(f_dyn) || is_user_integrand(f_obs)) return refuse_user_integrand(what);
+    if (N < kPfMinN || N % 64 != 0) {
+        snprintf(msg, sizeof(msg), "%s: N = %d particles - a multiple of 64, at least 64, is needed", what, N);
+        set_error(msg);
+        return SSMQ_E_ARG;
+    }
+    if (D < 1 || Y < 1 || dq < 1) {
+        snprintf(msg, sizeof(msg), "%s: D, Y and dq must be at least 1", what);
+        set_error(msg);
+        return SSMQ_E_ARG;
+    }
+    const char *range = "built-in additive-noise models, 1 <= D <= 6, 1 <= Y <= 4, 1 <= dq <= 6, N a multiple of 64 in 64 .. 4096 with "
+                        "(2 D + 1) N <= 13312 (the cloud lives in LDS), Gaussian or Student-t measurement noise";
+    if (pf_noise_is_argument(f_dyn->id) || pf_noise_is_argument(f_obs->id)) {
+        snprintf(msg, sizeof(msg), "%s: not implemented for models that take their noise as an argument (non-additive noise); range: %s",
+                 what, range);
+        set_error(msg);
+        return SSMQ_E_UNSUPPORTED;
+    }
+    if (r->kind == SSMQ_RV_MIXTURE) {
+        snprintf(msg, sizeof(msg), "%s: not implemented for Gaussian-mixture measurement noise; range: %s", what, range);
+        set_error(msg);
+        return SSMQ_E_UNSUPPORTED;
+    }
+    if (!pf_shape_ok(D, Y, dq, N)) {
+        snprintf(msg, sizeof(msg), "%s: D = %d, Y = %d, dq = %d, N = %d is outside the range: %s", what, D, Y, dq, N, range);
+        set_error(msg);
+        return SSMQ_E_UNSUPPORTED;
+    }
+    if ((r->kind != SSMQ_RV_GAUSS && r->kind != SSMQ_RV_STUDENT) || r->dim != Y || r->n_comp > 1 || !r->chol ||
+        (r->kind == SSMQ_RV_STUDENT && !(r->dof > 0.0))) {
+        snprintf(msg, sizeof(msg), "%s: measurement noise must be SSMQ_RV_GAUSS or SSMQ_RV_STUDENT (dof > 0) of dimension Y with a factor", what);
+        set_error(msg);
+        return SSMQ_E_ARG;
+    }
+    for (int e = 0; e < Y; ++e)
+        if (!(r->chol[e * Y + e] > 0.0)) {
+            snprintf(msg, sizeof(msg), "%s: the factor of R needs a positive diagonal", what);
+            set_error(msg);
+            return SSMQ_E_ARG;
+        }
+    FInfo fid, fio;
+    if (!integrand_info(f_dyn->id, &fid) || fid.dout != D || fid.din != D || f_dyn->n_idx != 0) {
+        snprintf(msg, sizeof(msg), "%s: transition integrand / dimension mismatch (D -> D, no state index)", what);
+        set_error(msg);
+        return SSMQ_E_ARG;
+    }
+    if (!integrand_info(f_obs->id, &fio) || (fio.dout ? fio.dout : Y) != Y || f_obs->n_idx < 0 || f_obs->n_idx > SSMQ_MAX_FIDX ||
+        (f_obs->n_idx == 0 && fio.din > D) || (f_obs->n_idx != 0 && f_obs->n_idx < fio.din)) {
+        snprintf(msg, sizeof(msg), "%s: measurement integrand / dimension mismatch (a state index must name every input the integrand reads)", what);
+        set_error(msg);
+        return SSMQ_E_ARG;
+    }
+    for (int k = 0; k < f_obs->n_idx; ++k)
+        if (f_obs->idx[k] < 0 || f_obs->idx[k] >= D) {
+            snprintf(msg, sizeof(msg), "%s: measurement state index out of range", what);
+            set_error(msg);
+            return SSMQ_E_ARG;
+        }
+    return SSMQ_OK;
+}
+
+}  // namespace
+}  // namespace ssmq
+
+using namespace ssmq;
+
+extern "C" int ssmq_particle_kernel_name(const ssmq_integrand *f_dyn, const ssmq_integrand *f_obs, int D, int Y, int dq, int N,
+                                         const ssmq_rv *r, char *buf, int len) {
+    if (!buf || len < 1) {
+        set_error("ssmq_particle_kernel_name: null buffer");
+        return SSMQ_E_ARG;
+    }
+    int rc = pf_check("ssmq_particle_kernel_name", f_dyn, f_obs, D, Y, dq, N, r);
+    if (rc) return rc;
+    snprintf(buf, (size_t)len, "k_particle_filter<D=%d> (N = %d, %zu B of LDS per trajectory)", D, N, pf_lds_bytes(D, N));
+    return SSMQ_OK;
+}
+
+extern "C" int ssmq_particle_filter_dev(const ssmq_integrand *f_dyn, const ssmq_integrand *f_obs, int D, int Y, int dq, int N, int64_t B,
+                                        int64_t ld, int T, const double *d_y, const double *d_m0, const double *d_P0,
+                                        const double *q_mean, const double *q_chol, const double *G, const ssmq_rv *r,
+                                        double ess_threshold, uint64_t seed, uint64_t traj_offset, double *d_fm, double *d_fP,
+                                        double *d_loglik, double *d_ess, int32_t *d_status, double *d_part, double *d_logw,
+                                        int32_t *d_anc) {
+    int rc = pf_check("ssmq_particle_filter_dev", f_dyn, f_obs, D, Y, dq, N, r);
+    if (rc) return rc;
+    if (T < 1 || B < 0 || ld < B || B > 0x7fffffff || !d_y || !d_m0 || !d_P0 || !q_chol || !d_fm || !d_fP || !d_loglik || !d_ess || !d_status ||
+        ess_threshold != ess_threshold) {
+        set_error("ssmq_particle_filter_dev: bad argument (T >= 1, 0 <= B <= ld, non-null buffers and q_chol, ess_threshold not NaN)");
+        return SSMQ_E_ARG;
+    }
+    PfLaunch h;
+    memset(&h, 0, sizeof(h));
+    h.f_dyn = f_dyn; h.f_obs = f_obs; h.D = D; h.Y = Y; h.dq = dq; h.N = N; h.T = T; h.B = B; h.ld = ld; h.seed = seed;
+    h.traj_offset = traj_offset; h.ess_threshold = ess_threshold;
+    for (int i = 0; i < dq; ++i) {
+        h.qm[i] = q_mean ? q_mean[i] : 0.0;
+        for (int k = 0; k <= i; ++k) h.Lq[i * kPfMaxQ + k] = q_chol[i * dq + k];
+    }
+    for (int d = 0; d < D; ++d)        // default noise gain eye(D, dq)  (ssmod.py:52)
+        for (int k = 0; k < dq; ++k) h.G[d * kPfMaxQ + k] = G ? G[d * dq + k] : (d == k ? 1.0 : 0.0);
+    double logdet = 0.0;
+    for (int e = 0; e < kPfMaxY; ++e) {
+        h.Lr[e * kPfMaxY + e] = 1.0;
+        if (e >= Y) continue;
+        h.rm[e] = r->mean ? r->mean[e] : 0.0;
+        for (int k = 0; k <= e; ++k) h.Lr[e * kPfMaxY + k] = r->chol[e * Y + k];
+        logdet += log(r->chol[e * Y + e]);
+    }
+    h.student = r->kind == SSMQ_RV_STUDENT ? 1 : 0;
+    h.dof = h.student ? r->dof : 0.0;
+    // log-normaliser: Gaussian -Y/2 log(2 pi) - log det L; Student-t lgamma((dof + Y)/2) - lgamma(dof/2) - Y/2 log(dof pi) - log det L
+    h.lognorm = h.student ? lgamma(0.5 * (h.dof + Y)) - lgamma(0.5 * h.dof) - 0.5 * Y * log(h.dof * M_PI) - logdet
+                          : -0.5 * Y * log(2.0 * M_PI) - logdet;
+    h.y = d_y; h.m0 = d_m0; h.P0 = d_P0; h.fm = d_fm; h.fP = d_fP; h.ll = d_loglik; h.ess = d_ess; h.status = d_status;
+    h.part = d_part; h.logw = d_logw; h.anc = d_anc;
+    rc = ensure_device();
+    if (rc) return rc;
+    if (B == 0) return SSMQ_OK;
+    hipStream_t s = stream();
+    rc = launch_particle_filter(h, s);
+    hipError_t e = hipStreamSynchronize(s);
+    if (rc) return rc;
+    SSMQ_HIP(e);
+    return SSMQ_OK;
+}

@@ -28,6 +28,23 @@ from .bq.bqmtran import (GaussianProcessTransform, BayesSardTransform, StudentTP
 from .ssmod import TransitionModel, MeasurementModel, is_user_model, has_device_jacobian, user_unsupported, check_user_points
 
 
+def initial_planes(D, mean, cov, B, ld, x0_mean=None, x0_cov=None):
+    """The initial moments of B trajectories as planes [D][ld], [D*D][ld] (scratch buffers; the caller frees them): the model's
+    (mean, cov) for every trajectory, or the per-trajectory x0_mean (B, D) / x0_cov (B, D, D)."""
+    m0 = np.broadcast_to(mean, (B, D)) if x0_mean is None else np.asarray(x0_mean, dtype=np.float64)
+    P0 = np.broadcast_to(cov, (B, D, D)) if x0_cov is None else np.asarray(x0_cov, dtype=np.float64)
+    mbuf = np.zeros((D, ld))
+    mbuf[:, :B] = m0.T
+    Pbuf = np.zeros((D * D, ld))
+    Pbuf[:, :B] = P0.reshape(B, D * D).T
+    if ld > B:       # padding lanes are never read (b >= B), keep them PD anyway
+        Pbuf[:, B:] = np.eye(D).reshape(-1, 1)
+    d_m0, d_P0 = _lib.scratch(mbuf.nbytes), _lib.scratch(Pbuf.nbytes)
+    d_m0.upload(mbuf)
+    d_P0.upload(Pbuf)
+    return d_m0, d_P0
+
+
 class GaussianInference:
     """Gaussian filter (ssinf.py:215-323)."""
 
@@ -310,19 +327,7 @@ class GaussianInference:
 
     def _initial_planes(self, B, ld, x0_mean=None, x0_cov=None):
         """The initial moments of B trajectories as planes [D][ld], [D*D][ld] (scratch buffers; the caller frees them)."""
-        D = self.mod_dyn.dim_state
-        m0 = np.broadcast_to(self.x0_mean, (B, D)) if x0_mean is None else np.asarray(x0_mean, dtype=np.float64)
-        P0 = np.broadcast_to(self._initial_cov(), (B, D, D)) if x0_cov is None else np.asarray(x0_cov, dtype=np.float64)
-        mbuf = np.zeros((D, ld))
-        mbuf[:, :B] = m0.T
-        Pbuf = np.zeros((D * D, ld))
-        Pbuf[:, :B] = P0.reshape(B, D * D).T
-        if ld > B:       # padding lanes are never read (b >= B), keep them PD anyway
-            Pbuf[:, B:] = np.eye(D).reshape(-1, 1)
-        d_m0, d_P0 = _lib.scratch(mbuf.nbytes), _lib.scratch(Pbuf.nbytes)
-        d_m0.upload(mbuf)
-        d_P0.upload(Pbuf)
-        return d_m0, d_P0
+        return initial_planes(self.mod_dyn.dim_state, self.x0_mean, self._initial_cov(), B, ld, x0_mean, x0_cov)
 
     def innovations_dev(self, d_y, d_fm, d_fP, B, ld, T):
         """Innovation scores of a pass whose measurements and filtered moments are on the device (what `ssmod.simulate_dev` /
@@ -627,6 +632,8 @@ def run_filters(algs, data, x0_mean=None, x0_cov=None, raise_on_failure=True):
     Y, T, B = data.shape
     ld = (B + 63) // 64 * 64
     for a in algs:
+        if isinstance(a, BootstrapParticleFilter):
+            a._refuse('run_filters')
         if not isinstance(a, GaussianInference) or not a._additive:
             raise NotImplementedError('run_filters: additive-noise Gaussian / Studentian filters only')
         if isinstance(a, MultiOutputGaussianProcessKalman):
@@ -1381,3 +1388,227 @@ class MarginalizedGaussianProcessKalman(MarginalInference):
         t_dyn = GaussianProcessTransform(dyn.dim_in, 1, kpar_dyn, kernel, points, point_hyp)
         t_obs = GaussianProcessTransform(obs.dim_state, 1, kpar_obs, kernel, points, point_hyp)
         super().__init__(dyn, obs, t_dyn, t_obs, par_mean, par_cov)
+
+
+class BootstrapParticleFilter:
+    """Bootstrap particle filter (sequential Monte Carlo) on the device - the ground truth the moment-matching filters are measured
+    against (`ssmq_particle_filter_dev`, one launch of k_particle_filter<D>: one trajectory per workgroup, the cloud in LDS).  In the
+    time convention of the Gaussian filters: x_{-1} ~ init_rv, step j = 0 .. T-1: x_j = f(x_{j-1}, j) + G q, y_j = h(x_j, j) + r; the
+    particles are weighted by the measurement density (GaussRV or StudentRV noise) and resampled systematically when the effective
+    sample size falls below ess_threshold * num_particles (>= 1: every step, <= 0: never).  A class of its own, not a
+    GaussianInference: it has no moment transforms.  A trajectory's results depend on `seed`, its global index, num_particles,
+    ess_threshold and its own data alone."""
+
+    RANGE = ('BootstrapParticleFilter covers forward passes (forward_pass, forward_pass_batch, forward_pass_dev) of built-in '
+             'additive-noise models with a GaussRV initial state and process noise and GaussRV or StudentRV measurement noise, '
+             'dim_state <= 6, dim_out <= 4, dim_noise <= 6, num_particles a multiple of 64 in 64 .. 4096 with '
+             '(2 dim_state + 1) num_particles <= 13312')
+
+    def __init__(self, dyn, obs, num_particles=1024, ess_threshold=0.5, seed=0):
+        assert isinstance(dyn, TransitionModel) and isinstance(obs, MeasurementModel)
+        from .ssmod import GaussRV, StudentRV
+        self.mod_dyn, self.mod_obs = dyn, obs
+        self.num_particles, self.ess_threshold, self.seed = int(num_particles), float(ess_threshold), int(seed)
+        if is_user_model(dyn) or is_user_model(obs):
+            raise NotImplementedError('{}; not implemented for user models (device_code)'.format(self.RANGE))
+        if not (dyn.noise_additive and obs.noise_additive):
+            raise NotImplementedError('{}; not implemented for models that take their noise as an argument (non-additive noise)'.format(self.RANGE))
+        if not isinstance(dyn.init_rv, GaussRV) or not isinstance(dyn.noise_rv, GaussRV):
+            raise NotImplementedError('{}; the initial state and the process noise must be GaussRV'.format(self.RANGE))
+        if not isinstance(obs.noise_rv, (GaussRV, StudentRV)):
+            raise NotImplementedError('{}; not implemented for {} measurement noise'.format(self.RANGE, type(obs.noise_rv).__name__))
+        if np.isnan(self.ess_threshold):
+            raise ValueError('ess_threshold must not be NaN')
+        self.x0_mean, self.x0_cov = dyn.init_rv.get_stats()
+        self.G = np.ascontiguousarray(dyn.noise_gain, dtype=np.float64)
+        self._check_range()
+        self.reset()
+
+    def reset(self):
+        self.fi_mean = self.fi_cov = self.status = None
+        self.loglik = self.loglik_total = self.ess = None
+        self.particles = self.log_weights = self.ancestors = None
+        if getattr(self, 'd_loglik', None) is not None or getattr(self, 'd_ess', None) is not None:
+            self.free_dev()
+        self.d_loglik = self.d_ess = None
+        self._data = None
+
+    def _initial_planes(self, B, ld, x0_mean=None, x0_cov=None):
+        return initial_planes(self.mod_dyn.dim_state, self.x0_mean, self.x0_cov, B, ld, x0_mean, x0_cov)
+
+    def _c_args(self):
+        """The model part of the C call (and the arrays it points to, to be kept alive)."""
+        from .ssmod import _rv_desc, _lower_factor
+        f_dyn, _ = self.mod_dyn.device_integrand()
+        f_obs, _ = self.mod_obs.device_integrand()
+        r, keep = _rv_desc(self.mod_obs.noise_rv, 'the measurement noise')
+        qm = np.ascontiguousarray(self.mod_dyn.noise_rv.mean, dtype=np.float64)
+        qL = _lower_factor(self.mod_dyn.noise_rv.cov)
+        return f_dyn, f_obs, r, qm, qL, keep
+
+    def _check_range(self):
+        """The library's range check, without a device: NotImplementedError (the range named) or ValueError before anything runs."""
+        f_dyn, f_obs, r, qm, qL, keep = self._c_args()
+        buf = ctypes.create_string_buffer(256)
+        rc = _lib.load().ssmq_particle_kernel_name(ctypes.byref(f_dyn), ctypes.byref(f_obs), self.mod_dyn.dim_state, self.mod_obs.dim_out,
+                                                   qm.size, self.num_particles, ctypes.byref(r), buf, 256)
+        if rc == -3:             # SSMQ_E_UNSUPPORTED
+            raise NotImplementedError(_lib.last_error())
+        if rc == -1:             # SSMQ_E_ARG
+            raise ValueError(_lib.last_error())
+        _lib.check(rc, 'ssmq_particle_kernel_name')
+        return buf.value.decode()
+
+    def kernel_name(self):
+        """The kernel a forward pass launches, with the LDS it requests per trajectory."""
+        return self._check_range()
+
+    def _launch(self, lib, B, ld, T, traj_offset, d_y, d_m0, d_P0, d_fm, d_fP, d_ll, d_ess, d_st, d_part=None, d_logw=None, d_anc=None):
+        if T < 1:
+            raise ValueError('BootstrapParticleFilter: at least one time step is needed (T = {})'.format(T))
+        f_dyn, f_obs, r, qm, qL, keep = self._c_args()
+        vp = lambda b: ctypes.c_void_p(b.ptr if b is not None else None)       # noqa: E731
+        dp = lambda a: a.ctypes.data_as(_lib.c_double_p)                       # noqa: E731
+        rc = lib.ssmq_particle_filter_dev(ctypes.byref(f_dyn), ctypes.byref(f_obs), self.mod_dyn.dim_state, self.mod_obs.dim_out, qm.size,
+                                          self.num_particles, B, ld, T, vp(d_y), vp(d_m0), vp(d_P0), dp(qm), dp(qL), dp(self.G),
+                                          ctypes.byref(r), self.ess_threshold, ctypes.c_uint64(self.seed), ctypes.c_uint64(int(traj_offset)),
+                                          vp(d_fm), vp(d_fP), vp(d_ll), vp(d_ess), vp(d_st), vp(d_part), vp(d_logw), vp(d_anc))
+        if rc == -3:
+            raise NotImplementedError(_lib.last_error())
+        _lib.check(rc, 'ssmq_particle_filter_dev')
+
+    def forward_pass_dev(self, d_y, B, ld, T, traj_offset=0):
+        """Filter measurements that are already on the device (planes [T][dim_y][ld], e.g. from `ssmod.simulate_dev`) and leave the
+        results there: returns the triple of the Gaussian filters, DeviceBuffers (d_fm [T][D][ld], d_fP [T][D*D][ld], d_status [ld]) for
+        `mcshard.device_error_sums` / `device_traj_scores` / `device_score_bars`; the caller frees them.  The log-likelihood increments
+        [T + 1][ld] (row T: the total) and the effective sample sizes [T][ld] stay on the device as `d_loglik` / `d_ess`: the filter owns
+        these two - the next forward_pass_dev, `reset()` or `free_dev()` frees them.  Every trajectory starts from the model's initial
+        moments; trajectory b draws from the stream of global index traj_offset + b."""
+        lib = _lib.load()
+        D = self.mod_dyn.dim_state
+        self.free_dev()
+        d_m0, d_P0 = self._initial_planes(B, ld)
+        out = [_lib.DeviceBuffer(8 * T * D * ld), _lib.DeviceBuffer(8 * T * D * D * ld), _lib.DeviceBuffer(4 * ld),
+               _lib.DeviceBuffer(8 * (T + 1) * ld), _lib.DeviceBuffer(8 * T * ld)]
+        d_fm, d_fP, d_st, d_ll, d_ess = out
+        try:
+            d_st.zero()
+            self._launch(lib, B, ld, T, traj_offset, d_y, d_m0, d_P0, d_fm, d_fP, d_ll, d_ess, d_st)
+        except BaseException:
+            for buf in out:
+                buf.free()
+            raise
+        finally:
+            d_m0.free()
+            d_P0.free()
+        self.d_loglik, self.d_ess = d_ll, d_ess
+        return d_fm, d_fP, d_st
+
+    def free_dev(self):
+        """Frees the device planes the last forward_pass_dev left with the filter (`d_loglik`, `d_ess`)."""
+        for buf in (self.d_loglik, self.d_ess):
+            if buf is not None:
+                buf.free()
+        self.d_loglik = self.d_ess = None
+
+    def forward_pass_batch(self, data, x0_mean=None, x0_cov=None, raise_on_failure=True, return_particles=False):
+        """data (dim_y, T, B) -> filtered means (D, T, B) and covariances (D, D, T, B): the weighted mean and covariance of the cloud
+        after each measurement.  Optional per-trajectory initial moments x0_mean (B, D), x0_cov (B, D, D).  Sets fi_mean, fi_cov,
+        status (B,) (0, or 1 + the step whose largest log-weight was not finite: NaN from there on), loglik (T, B) - the increments
+        log p(y_j | y_0..j-1) -, loglik_total (B,) and ess (T, B); with return_particles also particles (D, N, T, B) after the
+        propagation of each step, log_weights (N, T, B) after its measurement (normalised, before resampling) and ancestors
+        (N, T, B) chosen after it (the identity where the step did not resample)."""
+        lib = _lib.load()
+        data = np.asarray(data, dtype=np.float64)
+        Y, T, B = data.shape
+        if Y != self.mod_obs.dim_out:
+            raise ValueError('data must have shape (dim_y = {}, T, B)'.format(self.mod_obs.dim_out))
+        if T < 1:
+            raise ValueError('BootstrapParticleFilter: at least one time step is needed (T = {})'.format(T))
+        self._data = data
+        D, N = self.mod_dyn.dim_state, self.num_particles
+        ld = (B + 63) // 64 * 64
+        d_y = _lib.scratch(8 * T * Y * ld)
+        _lib.upload_study(data, Y, ld, d_y)
+        d_m0, d_P0 = self._initial_planes(B, ld, x0_mean, x0_cov)
+        d_fm, d_fP, d_st = _lib.scratch(8 * T * D * ld), _lib.scratch(8 * T * D * D * ld), _lib.scratch(4 * ld)
+        d_ll, d_ess = _lib.scratch(8 * (T + 1) * ld), _lib.scratch(8 * T * ld)
+        d_part = d_logw = d_anc = None
+        if return_particles:
+            d_part, d_logw, d_anc = _lib.scratch(8 * T * D * B * N), _lib.scratch(8 * T * B * N), _lib.scratch(4 * T * B * N)
+        bufs = (d_y, d_m0, d_P0, d_fm, d_fP, d_st, d_ll, d_ess, d_part, d_logw, d_anc)
+        try:
+            d_st.zero()
+            self._launch(lib, B, ld, T, 0, d_y, d_m0, d_P0, d_fm, d_fP, d_ll, d_ess, d_st, d_part, d_logw, d_anc)
+            fm = _lib.download_study(d_fm, (D,), T, B, ld)
+            fP = _lib.download_study(d_fP, (D, D), T, B, ld)
+            self.status = d_st.download((ld,), dtype=np.int32)[:B]
+            ll = d_ll.download((T + 1, ld))
+            self.loglik, self.loglik_total = np.ascontiguousarray(ll[:T, :B]), ll[T, :B].copy()
+            self.ess = np.ascontiguousarray(d_ess.download((T, ld))[:, :B])
+            if return_particles:
+                self.particles = np.ascontiguousarray(d_part.download((T, D, B, N)).transpose(1, 3, 0, 2))
+                self.log_weights = np.ascontiguousarray(d_logw.download((T, B, N)).transpose(2, 0, 1))
+                self.ancestors = np.ascontiguousarray(d_anc.download((T, B, N), dtype=np.int32).transpose(2, 0, 1))
+            else:
+                self.particles = self.log_weights = self.ancestors = None
+        finally:
+            for buf in bufs:
+                if buf is not None:
+                    buf.free()
+        self.fi_mean, self.fi_cov = fm, fP
+        if raise_on_failure and self.status.any():
+            b = int(np.flatnonzero(self.status)[0])
+            raise np.linalg.LinAlgError('Particle filter degenerate: no finite log-weight (trajectory {}, step {})'.format(
+                b, int(self.status[b]) - 1))
+        return self.fi_mean, self.fi_cov
+
+    def forward_pass(self, data):
+        """data (dim_y, T) -> filtered means (D, T), covariances (D, D, T): trajectory 0 of a batch of one."""
+        fm, fP = self.forward_pass_batch(np.asarray(data)[..., None])
+        return fm[..., 0], fP[..., 0]
+
+    def _refuse(self, what):
+        raise NotImplementedError('{}; {} is not implemented for it'.format(self.RANGE, what))
+
+    def backward_pass(self):
+        self._refuse('the RTS smoother (backward_pass)')
+
+    def backward_pass_batch(self):
+        self._refuse('the RTS smoother (backward_pass_batch)')
+
+    def innovations(self, *args, **kwargs):
+        self._refuse('innovations')
+
+    def innovations_batch(self, *args, **kwargs):
+        self._refuse('innovations_batch')
+
+    def innovations_dev(self, *args, **kwargs):
+        self._refuse('innovations_dev')
+
+    def innovations_kernel_name(self, *args, **kwargs):
+        self._refuse('innovations_kernel_name')
+
+    def iterated_pass(self, *args, **kwargs):
+        self._refuse('iterated_pass')
+
+    def iterated_pass_batch(self, *args, **kwargs):
+        self._refuse('iterated_pass_batch')
+
+    def iterated_pass_dev(self, *args, **kwargs):
+        self._refuse('iterated_pass_dev')
+
+    def iterated_kernel_name(self, *args, **kwargs):
+        self._refuse('iterated_kernel_name')
+
+    def iterated_smoother(self, *args, **kwargs):
+        self._refuse('iterated_smoother')
+
+    def iterated_smoother_batch(self, *args, **kwargs):
+        self._refuse('iterated_smoother_batch')
+
+    def iterated_smoother_dev(self, *args, **kwargs):
+        self._refuse('iterated_smoother_dev')
+
+    def iterated_smoother_kernel_name(self, *args, **kwargs):
+        self._refuse('iterated_smoother_kernel_name')
