@@ -805,7 +805,8 @@ int ssmq_error_sums_dev(int D, int64_t B, int64_t ld, int T, const double *d_x, 
  * the GLOBAL per-step MSE matrices mse [T][D*D] (host; regularisation, e.g. + 1e-6 I of research/tpq/tpq_base.py:161,
  * already added).  sums: host [T][2] = lcr sum | n counted (status 0).  A P that is not positive definite goes through
  * the reference's fallback, mat_sqrt = u sqrt(s) of an SVD (utils.py:426-432), i.e. the quadratic form with |P|: a second
- * pass with a Jacobi eigen-decomposition handles those entries.
+ * pass with a Jacobi eigen-decomposition handles those entries.  A singular P is counted in n and its term is +inf (a zero
+ * eigenvalue of |P|), and with it the step's sum.
  */
 int ssmq_lcr_sums_dev(int D, int64_t B, int64_t ld, int T, const double *d_x, const double *d_fm, const double *d_fP,
                       const int32_t *d_status, const double *mse, double *sums);

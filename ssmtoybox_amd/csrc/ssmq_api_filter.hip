@@ -913,12 +913,13 @@ static int metrics_impl(int phase, int D, int64_t B, int64_t ld, int T, const do
         return SSMQ_OK;
     }
     hipStream_t s = stream();
-    DevBuf partial, out, dm;
+    DevBuf partial, out, dm, left;
     if ((rc = partial.alloc(sizeof(double) * (size_t)T * metrics_chunks(B) * NI)) ||
-        (rc = out.alloc(sizeof(double) * (size_t)T * NI)) || (rc = dm.alloc(sizeof(double) * (size_t)T * D * D)))
+        (rc = out.alloc(sizeof(double) * (size_t)T * NI)) || (rc = dm.alloc(sizeof(double) * (size_t)T * D * D)) ||
+        (rc = left.alloc((size_t)T * metrics_chunks(B) * metrics_left_bytes())))
         return rc;
     if (phase == 2) SSMQ_HIP(hipMemcpyAsync(dm.p, mse, sizeof(double) * (size_t)T * D * D, hipMemcpyHostToDevice, s));
-    rc = launch_metrics(phase, D, B, ld, T, d_x, d_fm, d_fP, d_status, dm.d(), partial.d(), out.d(), s);
+    rc = launch_metrics(phase, D, B, ld, T, d_x, d_fm, d_fP, d_status, dm.d(), partial.d(), (uint8_t *)left.p, out.d(), s);
     if (rc) {
         hipStreamSynchronize(s);
         return rc;
@@ -933,7 +934,7 @@ static int metrics_impl(int phase, int D, int64_t B, int64_t ld, int T, const do
     for (int t = 0; t < T && !left_out; ++t)
         left_out = phase == 1 ? h[(size_t)t * NI + i_ok] > h[(size_t)t * NI + i_cnt] : h[(size_t)t * NI + 2] > 0.0;
     if (left_out) {
-        rc = launch_metrics_indef(phase, D, B, ld, T, d_x, d_fm, d_fP, d_status, dm.d(), partial.d(), out.d(), s);
+        rc = launch_metrics_indef(phase, D, B, ld, T, d_x, d_fm, d_fP, d_status, dm.d(), partial.d(), (uint8_t *)left.p, out.d(), s);
         std::vector<double> extra((size_t)T * 2);
         if (!rc) rc = hip_fail(hipMemcpyAsync(extra.data(), out.p, sizeof(double) * extra.size(), hipMemcpyDeviceToHost, s), "hipMemcpyAsync");
         hipError_t e = hipStreamSynchronize(s);

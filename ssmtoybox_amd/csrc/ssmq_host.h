@@ -591,10 +591,11 @@ int rtc_launch_ipls(const FilterPass &p, const IplsPlanes &q);
 // error sums over a batch of filtered trajectories (ssmq_metrics.hip)
 int metrics_values_per_step(int D);
 int metrics_chunks(int64_t B);
+int metrics_left_bytes();      // per (step, chunk): the record of the entries left to the second pass
 int launch_metrics(int phase, int D, int64_t B, int64_t ld, int T, const double *x, const double *fm, const double *fP,
-                   const int32_t *status, const double *mse, double *partial, double *out, hipStream_t s);
+                   const int32_t *status, const double *mse, double *partial, uint8_t *left, double *out, hipStream_t s);
 int launch_metrics_indef(int phase, int D, int64_t B, int64_t ld, int T, const double *x, const double *fm, const double *fP,
-                         const int32_t *status, const double *mse, double *partial, double *out, hipStream_t s);
+                         const int32_t *status, const double *mse, double *partial, uint8_t *left, double *out, hipStream_t s);
 
 // time-averaged scores of every trajectory (ssmq_metrics.hip: k_traj_scores); mse: device [T][D*D] or null
 int launch_traj_scores(int D, int64_t B, int64_t ld, int T, int k0, const double *x, const double *fm, const double *fP,

@@ -86,9 +86,19 @@ struct MetArgs {
     const int32_t *status;         // [ld] or null; nonzero = trajectory excluded (its filter failed)
     const double *mse;             // phase 2: [T][D*D] global MSE matrices (already regularised), device
     double *partial;               // [T][chunks][NV]
+    uint8_t *left;                 // [T][chunks][kMetBlock]: bit r = the thread's r-th entry was left to the second pass
     int64_t B, ld;
     int32_t D, T, chunks;
 };
+
+// The streaming kernels decide once which entries they leave to the second pass (P not positive definite) and record it: one
+// byte per thread and step, bit r for the thread's r-th entry, stored unconditionally (no initialisation pass).  k_indef_sums
+// runs the same (block, thread, r) -> trajectory map and reads its own byte back.  It does not factor P again: a second
+// factorisation - even the same routine, inlined into other code and contracted into other fused operations - can take the
+// other side at a pivot of rounding size, and the entry would be added by both passes or by neither.
+__device__ __forceinline__ void store_left(const MetArgs &a, int t, uint32_t left) {
+    a.left[((int64_t)t * a.chunks + blockIdx.x) * kMetBlock + threadIdx.x] = (uint8_t)left;
+}
 
 // block-wide sums with a compile-time count (accumulators stay in registers)
 template <int NV>
@@ -185,6 +195,7 @@ __global__ __launch_bounds__(kMetBlock) void k_error_sums(MetArgs a) {
     // 32-bit lane index against wave-uniform plane pointers: loads take the (SGPR base + VGPR offset) form and no
     // 64-bit address is kept per plane
     const uint32_t base = blockIdx.x * (uint32_t)(kMetBlock * kMetPerThread) + threadIdx.x;
+    uint32_t left = 0;
     for (int r = 0; r < kMetPerThread; ++r) {
         const uint32_t b = base + (uint32_t)r * kMetBlock;
         if ((int64_t)b >= a.B) break;
@@ -208,7 +219,9 @@ __global__ __launch_bounds__(kMetBlock) void k_error_sums(MetArgs a) {
             for (int j = 0; j <= i; ++j) acc[D + 2 + SSMQ_PK(i, j)] += dx[i] * dx[j];
         acc[D + 2 + TRI] += 1.0;
         if (nll_item<D>(L, dx, acc[D + 1])) acc[D + 3 + TRI] += 1.0;
+        else left |= 1u << r;
     }
+    store_left(a, t, left);
     block_sums_fixed<NA>(acc, sh, a.partial + ((int64_t)t * a.chunks + blockIdx.x) * NA);
 }
 
@@ -222,6 +235,7 @@ __global__ __launch_bounds__(kMetBlock) void k_error_sums_generic(MetArgs a) {
     const double *x = a.x + (int64_t)t * D * a.ld, *fm = a.fm + (int64_t)t * D * a.ld;
     const double *fP = a.fP + (int64_t)t * D * D * a.ld;
     const int64_t base = (int64_t)blockIdx.x * kMetBlock * kMetPerThread;
+    uint32_t left = 0;
     for (int r = 0; r < kMetPerThread; ++r) {
         const int64_t b = base + (int64_t)r * kMetBlock + threadIdx.x;
         if (b >= a.B) break;
@@ -241,7 +255,9 @@ __global__ __launch_bounds__(kMetBlock) void k_error_sums_generic(MetArgs a) {
             }
         acc[D + 2 + TRI] += 1.0;
         if (nll_item_dense(P, dx, D, acc[D + 1])) acc[D + 3 + TRI] += 1.0;
+        else left |= 1u << r;
     }
+    store_left(a, t, left);
     block_sums(acc, NA, sh, a.partial + ((int64_t)t * a.chunks + blockIdx.x) * NA);
 }
 
@@ -262,6 +278,7 @@ __global__ __launch_bounds__(kMetBlock) void k_lcr_sums(MetArgs a) {
         for (int j = 0; j <= i; ++j) M[SSMQ_PK(i, j)] = a.mse[(int64_t)t * D * D + i * D + j];
     const bool m_ok = chol_packed<D>(M);
     const uint32_t base = blockIdx.x * (uint32_t)(kMetBlock * kMetPerThread) + threadIdx.x;
+    uint32_t left = 0;
     for (int r = 0; r < kMetPerThread && m_ok; ++r) {
         const uint32_t b = base + (uint32_t)r * kMetBlock;
         if ((int64_t)b >= a.B) break;
@@ -275,10 +292,12 @@ __global__ __launch_bounds__(kMetBlock) void k_lcr_sums(MetArgs a) {
             for (int j = 0; j <= i; ++j) L[SSMQ_PK(i, j)] = SSMQ_MLOAD(fP[((int64_t)i * D + j) * a.ld + b]);
         if (!lcr_item<D>(L, M, dx, acc[0])) {   // left to k_indef_sums
             acc[2] += 1.0;
+            left |= 1u << r;
             continue;
         }
         acc[1] += 1.0;
     }
+    store_left(a, t, left);
     block_sums_fixed<3>(acc, sh, a.partial + ((int64_t)t * a.chunks + blockIdx.x) * 3);
 }
 
@@ -293,6 +312,7 @@ __global__ __launch_bounds__(kMetBlock) void k_lcr_sums_generic(MetArgs a) {
     for (int i = 0; i < D * D; ++i) M[i] = a.mse[(int64_t)t * D * D + i];
     const bool m_ok = chol_dense<0>(M, D);
     const int64_t base = (int64_t)blockIdx.x * kMetBlock * kMetPerThread;
+    uint32_t left = 0;
     for (int r = 0; r < kMetPerThread && m_ok; ++r) {
         const int64_t b = base + (int64_t)r * kMetBlock + threadIdx.x;
         if (b >= a.B) break;
@@ -303,10 +323,12 @@ __global__ __launch_bounds__(kMetBlock) void k_lcr_sums_generic(MetArgs a) {
             for (int j = 0; j <= i; ++j) P[i * D + j] = fP[((int64_t)i * D + j) * a.ld + b];
         if (!lcr_item_dense(P, M, dx, D, acc[0])) {
             acc[2] += 1.0;
+            left |= 1u << r;
             continue;
         }
         acc[1] += 1.0;
     }
+    store_left(a, t, left);
     block_sums(acc, 3, sh, a.partial + ((int64_t)t * a.chunks + blockIdx.x) * 3);
 }
 
@@ -314,7 +336,8 @@ __global__ __launch_bounds__(kMetBlock) void k_lcr_sums_generic(MetArgs a) {
 // The reference's metrics do not need a positive-definite P: neg_log_likelihood uses inv(P) and sign * logdet of
 // slogdet (utils.py:143-148), log_cred_ratio's mat_sqrt falls back to u sqrt(s) of an SVD (utils.py:426-432), i.e. the
 // quadratic form with |P| = U S U'.  The streaming kernels above go through the Cholesky factor and leave such entries
-// out; when the counts say that some were left out, this kernel makes a second pass that adds exactly those terms:
+// out and record which (store_left); when the counts say that some were left out, this kernel makes a second pass that adds
+// exactly the recorded entries' terms:
 //   phase 1: 0.5 (sign log|det P| + dx' P^-1 dx + D log 2 pi) from an LU factorisation with partial pivoting of the
 //            full matrix;  phase 2: 10 (log10 dx'|P|^-1 dx - log10 dx' M^-1 dx), |P| through a Jacobi
 //            eigen-decomposition of the symmetric part (eigenvalues in absolute value).
@@ -424,20 +447,18 @@ __global__ __launch_bounds__(kMetBlock) void k_indef_sums(MetArgs a, int phase) 
     const double *x = a.x + (int64_t)t * D * a.ld, *fm = a.fm + (int64_t)t * D * a.ld;
     const double *fP = a.fP + (int64_t)t * D * D * a.ld;
     double M[kMetMaxD * kMetMaxD];
-    bool m_ok = true;
-    if (phase == 2) {
+    // bits set: the streaming kernel found the step's MSE matrix positive definite (it runs no entry otherwise) and this P not
+    const uint32_t left = a.left[((int64_t)t * a.chunks + blockIdx.x) * kMetBlock + threadIdx.x];
+    if (phase == 2 && left != 0) {
         for (int i = 0; i < D * D; ++i) M[i] = a.mse[(int64_t)t * D * D + i];
-        m_ok = chol_dense<0>(M, D);
+        chol_dense<0>(M, D);
     }
     const int64_t base = (int64_t)blockIdx.x * kMetBlock * kMetPerThread;
-    for (int r = 0; r < kMetPerThread && m_ok; ++r) {
+    for (int r = 0; r < kMetPerThread; ++r) {
         const int64_t b = base + (int64_t)r * kMetBlock + threadIdx.x;
         if (b >= a.B) break;
-        if (a.status && a.status[b] != 0) continue;
+        if (!((left >> r) & 1u)) continue;          // the streaming kernel has counted it (or it is excluded)
         double dx[kMetMaxD], P[kMetMaxD * kMetMaxD], W[kMetMaxD * kMetMaxD], z[kMetMaxD];
-        for (int i = 0; i < D; ++i)
-            for (int j = 0; j <= i; ++j) W[i * D + j] = fP[((int64_t)i * D + j) * a.ld + b];
-        if (chol_dense<0>(W, D)) continue;          // positive definite: the streaming kernel has counted it
         for (int d = 0; d < D; ++d) dx[d] = x[(int64_t)d * a.ld + b] - fm[(int64_t)d * a.ld + b];
         for (int i = 0; i < D * D; ++i) P[i] = fP[(int64_t)i * a.ld + b];
         if (phase == 1) {
@@ -608,8 +629,8 @@ hipError_t launch_phase(const MetArgs &a, int phase, hipStream_t s) {
 
 // second pass over the entries whose covariance is not positive definite: d_out [T][2] = term sum | count
 int launch_metrics_indef(int phase, int D, int64_t B, int64_t ld, int T, const double *x, const double *fm, const double *fP,
-                         const int32_t *status, const double *mse, double *partial, double *out, hipStream_t s) {
-    MetArgs a{x, fm, fP, status, mse, partial, B, ld, D, T, metrics_chunks(B)};
+                         const int32_t *status, const double *mse, double *partial, uint8_t *left, double *out, hipStream_t s) {
+    MetArgs a{x, fm, fP, status, mse, partial, left, B, ld, D, T, metrics_chunks(B)};
     hipLaunchKernelGGL(k_indef_sums, dim3((unsigned)a.chunks, (unsigned)T), dim3(kMetBlock), sizeof(double) * (kMetBlock / 64) * 2,
                        s, a, phase);
     hipError_t e = hipGetLastError();
@@ -637,12 +658,15 @@ int launch_traj_scores(int D, int64_t B, int64_t ld, int T, int k0, const double
 
 int metrics_values_per_step(int D) { return met_nv(D); }
 
-// d_out [T][NV] device; d_partial scratch of T * chunks * NV doubles (chunks from metrics_chunks)
+// d_out [T][NV] device; d_partial scratch of T * chunks * NV doubles (chunks from metrics_chunks); left: T * chunks *
+// metrics_left_bytes() bytes, written by launch_metrics and read by launch_metrics_indef of the same phase
+int metrics_left_bytes() { return kMetBlock; }
+
 int metrics_chunks(int64_t B) { return (int)((B + (int64_t)kMetBlock * kMetPerThread - 1) / ((int64_t)kMetBlock * kMetPerThread)); }
 
 int launch_metrics(int phase, int D, int64_t B, int64_t ld, int T, const double *x, const double *fm, const double *fP,
-                   const int32_t *status, const double *mse, double *partial, double *out, hipStream_t s) {
-    MetArgs a{x, fm, fP, status, mse, partial, B, ld, D, T, metrics_chunks(B)};
+                   const int32_t *status, const double *mse, double *partial, uint8_t *left, double *out, hipStream_t s) {
+    MetArgs a{x, fm, fP, status, mse, partial, left, B, ld, D, T, metrics_chunks(B)};
     hipError_t e;
     switch (D) {
         case 1: e = launch_phase<1>(a, phase, s); break;
