@@ -153,30 +153,135 @@ __device__ __forceinline__ double exp_nr(double x) {
     return ldexp(p, (int)n);
 }
 
-// In-register lower Cholesky of a packed symmetric matrix, column by column with reciprocal scaling, the operation
+// ---------------------------------------------------------------------------------------------------------------
+// Per-lane packed linear algebra: what a kernel that carries one trajectory per lane ends its step with - factor, the two
+// triangular substitutions, gain, (G M) G'.  Sizes are template arguments: everything unrolled, operands in registers.
+// Operands come through small callables, so a caller keeps its own layout, selects and stores.
+// Callers: kalman_update_item (gain, Studentian delta), ekf_update_reg (gain, sandwich); chol_packed<> everywhere.
+//
+// THE SAME SUMS ARE STILL WRITTEN OUT BY HAND in the places below - change the order of an operation here and they have
+// to follow.  Each was left (or put back) because as a helper call its kernels did not compile to the instructions they
+// had before; the bar for the move was identical code, kernel by kernel:
+//   fused_pass (ssmq_filter_fused_kernel.h)      pair, delta, sandwich tried: the Y = 4 kernels allocate registers differently,
+//                                                and with the fP store in sandwich's callable the scalar kernels' store
+//                                                changes its cache hint
+//   k_filter_fused_aug (ssmq_filter_fused.hip)   pair tried: scheduling and register counts differ; sandwich not tried
+//   k_filter_wsplit (ssmq_filter_wsplit.hip)     pair, delta tried: register allocation differs in all 18; sandwich not tried
+//   k_rts_backward (ssmq_filter.hip)             not tried: its RTS_LD loads sit inside the substitution and the sandwich, and
+//                                                loads in a callable changed the address arithmetic of kalman_update_item
+//   kalman_update_item (ssmq_update.h)           sandwich tried: with the plane loads and stores in the callable every
+//                                                k_kalman_update<> grows 5 - 15 % in instructions
+//   iplf_update (ssmq_iterated_kernel.h),        pairs, gain, sandwich tried: other spill counts at D >= 4, and
+//   ipls_step, ipls_back (ssmq_ipls_kernel.h)    k_ipls_pass<5,4,11,11,11,12,1,0,1> 1.38 ms against 0.95 ms (B = 4096, T = 30)
+//   innovation_score (ssmq_innovation_kernel.h)  factor and forward substitution tried: other register counts, the
+//                                                run-time-size kernel 5 % longer
+//   theta_item_core (ssmq_theta_item.h)          gain, sandwich tried: k_theta_item<2,2,1,5,5> trades 2 SGPRs for 2 spills
+// Separate on purpose, different arithmetic and not a copy: k_filter_quad (pivot reciprocals formed once and multiplied),
+// kalman_update_item_generic and gauss_logpdf_item (dense run-time arrays, IEEE sqrt and division), the double-double
+// kl_chol, the block / LDS routines of ssmq_blockla.h.
+// ---------------------------------------------------------------------------------------------------------------
+// Lower Cholesky of a packed symmetric matrix in place, column by column with reciprocal scaling, the operation
 // order of LAPACK dpotf2 'L' that numpy.linalg.cholesky ends in (bq/bqmtran.py:98).  Returns false at the first
-// non-positive (or NaN) pivot - where the reference raises LinAlgError.
-template <int D>
-__device__ __forceinline__ bool chol_packed(double (&L)[D * (D + 1) / 2]) {
+// non-positive (or NaN) pivot - where the reference raises LinAlgError.  NT > 0: size fixed at compile time, unrolled in
+// full; NT = 0: n_rt <= SSMQ_MAX_DIM at run time (k_iplf_update<0, 0>).
+template <int NT>
+__device__ __forceinline__ bool chol_packed(int n_rt, double *L) {
+    const int n = NT ? NT : n_rt;
+    constexpr int UN = NT ? NT : 1;
     bool ok = true;
-#pragma unroll
-    for (int j = 0; j < D; ++j) {
+#pragma unroll UN
+    for (int j = 0; j < n; ++j) {
         double ajj = L[SSMQ_PK(j, j)];
-#pragma unroll
+#pragma unroll UN
         for (int k = 0; k < j; ++k) ajj -= L[SSMQ_PK(j, k)] * L[SSMQ_PK(j, k)];
         ok = ok && (ajj > 0.0);
         double r;
         sqrt_rsqrt(ajj, ajj, r);
         L[SSMQ_PK(j, j)] = ajj;
-#pragma unroll
-        for (int i = j + 1; i < D; ++i) {
+#pragma unroll UN
+        for (int i = j + 1; i < n; ++i) {
             double s = L[SSMQ_PK(i, j)];
-#pragma unroll
+#pragma unroll UN
             for (int k = 0; k < j; ++k) s -= L[SSMQ_PK(i, k)] * L[SSMQ_PK(j, k)];
             L[SSMQ_PK(i, j)] = s * r;
         }
     }
     return ok;
+}
+template <int D>
+__device__ __forceinline__ bool chol_packed(double (&L)[D * (D + 1) / 2]) {
+    return chol_packed<D>(D, L);
+}
+
+// Forward substitution: v = L^-1 b, b[i] = rhs(i).
+template <int N, class RHS>
+__device__ __forceinline__ void tri_solve_fwd(const double *L, RHS rhs, double *v) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        double s = rhs(i);
+#pragma unroll
+        for (int q = 0; q < i; ++q) s -= L[SSMQ_PK(i, q)] * v[q];
+        v[i] = div_nr(s, L[SSMQ_PK(i, i)]);
+    }
+}
+// Backward substitution: x = L^-T v (x may be v).
+template <int N>
+__device__ __forceinline__ void tri_solve_bwd(const double *L, const double *v, double *x) {
+#pragma unroll
+    for (int i = N - 1; i >= 0; --i) {
+        double s = v[i];
+#pragma unroll
+        for (int q = i + 1; q < N; ++q) s -= L[SSMQ_PK(q, i)] * x[q];
+        x[i] = div_nr(s, L[SSMQ_PK(i, i)]);
+    }
+}
+// x = (L L')^-1 b = b (L L')^-1 for a row b: forward, then backward substitution.
+template <int N, class RHS>
+__device__ __forceinline__ void cho_solve_row(const double *L, RHS rhs, double *x) {
+    tri_solve_fwd<N>(L, rhs, x);
+    tri_solve_bwd<N>(L, x, x);
+}
+
+// Gain G [D][Y] = C' S^-1 from the packed innovation covariance S (factored in place unless Y = 1) and the cross-covariance
+// C(i, d) = cyx(i, d).  A scalar measurement takes one division instead of factor + two substitutions, which would only
+// lengthen the step's dependency chain.  Returns whether S is positive definite.
+template <int D, int Y, class CYX>
+__device__ __forceinline__ bool gain_from_cov(double (&S)[Y * (Y + 1) / 2], CYX cyx, double (&G)[D][Y]) {
+    if constexpr (Y == 1) {
+        const bool ok = S[0] > 0.0;
+#pragma unroll
+        for (int d = 0; d < D; ++d) G[d][0] = div_nr(cyx(0, d), S[0]);
+        return ok;
+    } else {
+        const bool ok = chol_packed<Y>(S);
+#pragma unroll
+        for (int d = 0; d < D; ++d) cho_solve_row<Y>(S, [&](int i) { return cyx(i, d); }, G[d]);
+        return ok;
+    }
+}
+
+// s = sum_j (sum_i G[d][i] M(i, j)) G[d2][j], handed to f(d, d2, s) for every d, d2 < D: the caller forms P +- s with its
+// own operands, selects and stores.
+template <int D, int Y, class MAT, class F>
+__device__ __forceinline__ void sandwich(const double (&G)[D][Y], MAT M, F f) {
+#pragma unroll
+    for (int d = 0; d < D; ++d) {
+        double w[Y];
+#pragma unroll
+        for (int j = 0; j < Y; ++j) {
+            double s = 0.0;
+#pragma unroll
+            for (int i = 0; i < Y; ++i) s += G[d][i] * M(i, j);
+            w[j] = s;
+        }
+#pragma unroll
+        for (int d2 = 0; d2 < D; ++d2) {
+            double s = 0.0;
+#pragma unroll
+            for (int j = 0; j < Y; ++j) s += w[j] * G[d2][j];
+            f(d, d2, s);
+        }
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------------------

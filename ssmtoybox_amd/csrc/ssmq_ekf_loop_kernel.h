@@ -11,8 +11,10 @@
 //   P_yx = H P-,  S = P_yx H' + R,  y- = h(m-)                     (linearize_item again)
 //   gain, m = m- + gain (y - y-),  P = P- - (gain S) gain'         (the update of kalman_update_item<D, Y>, Y = 1 shortcut included)
 // Neither covariance is symmetrised: the launch loop carries the full D x D matrix from kernel to kernel, so do the registers here.
-// The sums and their order are those of linearize_item (ssmq_jacobian_kernel.h) and kalman_update_item (ssmq_update.h); the two
-// routes agree to rounding, not to the bit (the compiler contracts and schedules the two texts separately).
+// The sums and their order are those of linearize_item (ssmq_jacobian_kernel.h); the update is the per-lane linear algebra of
+// ssmq_device.h: gain_from_cov<>, which kalman_update_item (ssmq_update.h) calls too, and sandwich<>, whose sums
+// kalman_update_item writes out around its loads and stores.  The two routes agree to rounding, not to the bit (the compiler
+// contracts and schedules the two kernels separately).
 //
 // The model front end is a template parameter (EkfFrontBuiltin, EkfFrontUser): it gets the state as a register array behind the
 // planes' interface - a LinArgs whose mean plane is that array (ld = 1, item 0) and whose time argument is the step's - so the
@@ -92,8 +94,8 @@ __device__ __forceinline__ void ekf_linearize_reg(const double *J, const double 
         }
 }
 
-// The measurement update of kalman_update_item<D, Y> (Gaussian): m_pr, P_pr (D x D), Py (Y x Y), Pyx (Y x D), dy = y - y_mean in,
-// m, P out (before the status is applied); returns whether Py is positive definite.
+// The measurement update of kalman_update_item<D, Y> (Gaussian) on register operands: m_pr, P_pr (D x D), Py (Y x Y),
+// Pyx (Y x D), dy = y - y_mean in, m, P out (before the status is applied); returns whether Py is positive definite.
 template <int D, int Y>
 __device__ __forceinline__ bool ekf_update_reg(const double *m_pr, const double *P_pr, const double *Py, const double *Pyx, const double *dy,
                                                double *m, double *P) {
@@ -102,35 +104,8 @@ __device__ __forceinline__ bool ekf_update_reg(const double *m_pr, const double 
     for (int i = 0; i < Y; ++i)
 #pragma unroll
         for (int j = 0; j <= i; ++j) S[SSMQ_PK(i, j)] = Py[i * Y + j];
-    bool ok;
     double G[D][Y];
-    if (Y == 1) {
-        ok = S[0] > 0.0;
-#pragma unroll
-        for (int d = 0; d < D; ++d) G[d][0] = div_nr(Pyx[d], S[0]);
-    } else {
-        ok = chol_packed<Y>(S);
-#pragma unroll
-        for (int d = 0; d < D; ++d) {
-            double v[Y];
-#pragma unroll
-            for (int i = 0; i < Y; ++i) {
-                double s = Pyx[i * D + d];
-#pragma unroll
-                for (int k = 0; k < i; ++k) s -= S[SSMQ_PK(i, k)] * v[k];
-                v[i] = div_nr(s, S[SSMQ_PK(i, i)]);
-            }
-#pragma unroll
-            for (int i = Y - 1; i >= 0; --i) {
-                double s = v[i];
-#pragma unroll
-                for (int k = i + 1; k < Y; ++k) s -= S[SSMQ_PK(k, i)] * v[k];
-                v[i] = div_nr(s, S[SSMQ_PK(i, i)]);
-            }
-#pragma unroll
-            for (int i = 0; i < Y; ++i) G[d][i] = v[i];
-        }
-    }
+    const bool ok = gain_from_cov<D, Y>(S, [&](int i, int d) { return Pyx[i * D + d]; }, G);
 #pragma unroll
     for (int d = 0; d < D; ++d) {
         double s = 0.0;
@@ -138,25 +113,9 @@ __device__ __forceinline__ bool ekf_update_reg(const double *m_pr, const double 
         for (int i = 0; i < Y; ++i) s += G[d][i] * dy[i];
         m[d] = m_pr[d] + s;
     }
-    // W = gain P_y (D x Y);  P = P_pr - W gain'
-#pragma unroll
-    for (int d = 0; d < D; ++d) {
-        double w[Y];
-#pragma unroll
-        for (int j = 0; j < Y; ++j) {
-            double s = 0.0;
-#pragma unroll
-            for (int i = 0; i < Y; ++i) s += G[d][i] * Py[i * Y + j];
-            w[j] = s;
-        }
-#pragma unroll
-        for (int d2 = 0; d2 < D; ++d2) {
-            double s = 0.0;
-#pragma unroll
-            for (int j = 0; j < Y; ++j) s += w[j] * G[d2][j];
-            P[d * D + d2] = P_pr[d * D + d2] - s;
-        }
-    }
+    // P = P_pr - (gain P_y) gain'
+    sandwich<D, Y>(G, [&](int i, int j) { return Py[i * Y + j]; },
+                   [&](int d, int d2, double s) { P[d * D + d2] = P_pr[d * D + d2] - s; });
     return ok;
 }
 

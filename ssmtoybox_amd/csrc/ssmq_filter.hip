@@ -170,6 +170,7 @@ __global__ __launch_bounds__(kUpdBlock) void k_rts_backward(const RtsArgs a) {
             }
         allok = chol_packed<D>(S) && allok;
         // gain = (P_pr^-1 C)'  -> G[d][i] = X[i][d], X = P_pr^-1 C, C = cross-covariance (D_out x D_in)
+        // (here and below the sums of cho_solve_row<> and sandwich<> of ssmq_device.h, written out: see the list there)
         double G[D][D];
 #pragma unroll
         for (int d = 0; d < D; ++d) {

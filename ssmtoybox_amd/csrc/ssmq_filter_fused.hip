@@ -242,6 +242,7 @@ __global__ __launch_bounds__(kSmallBlock, (D + DQ >= 5 ? 1 : 2)) void k_filter_f
         augment<D, DR>(pr.mf, pr.cv, rm, rc, mo, Po);
         RegSink<DO, Y> ob;
         ok = moment_transform_core<DO, Y, NO, FO, FORM, TP, SELO, true, 0>(mo, Po, t, a.fo, cpo, ob) && ok;
+        // (the update: the sums of gain_from_cov<> and sandwich<> of ssmq_device.h, written out - see the list there)
         double S[Y * (Y + 1) / 2];
 #pragma unroll
         for (int i = 0; i < Y * (Y + 1) / 2; ++i) S[i] = ob.cv[i];

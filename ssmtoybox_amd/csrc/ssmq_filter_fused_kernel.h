@@ -136,6 +136,7 @@ __device__ __forceinline__ void fused_pass(const FusedArgs &a, uint32_t blk, int
         RegSink<D, Y> ob;
         ok = moment_transform_core<D, Y, NO, FO, FORM, TP, SELO, true, OPT, RegSink<D, Y>>(pr.mf, L2, t, fo, cpo, ob) && ok;
         // ---- measurement update (ssinf.py:321-323) ---------------------------------------------------------------------
+        // (the sums of cho_solve_row<>, tri_solve_fwd<> and sandwich<> of ssmq_device.h, written out: see the list there)
         double S[Y * (Y + 1) / 2];
 #pragma unroll
         for (int i = 0; i < Y * (Y + 1) / 2; ++i) S[i] = ob.cv[i];

@@ -324,6 +324,7 @@ __global__ __launch_bounds__(64 * W, 1) void k_filter_wsplit(const FusedArgs a) 
         RegSink<D, Y> ob;
         ok = transform_split<D, Y, NO, FO, FORM, TP, SELO, true, W>(pr.mf, L2, t, fo, cpo, ob, xa, xb, w) && ok;
         // ---- measurement update (ssinf.py:321-323), replicated in every wave ------------------------------------------------
+        // (the sums of cho_solve_row<>, tri_solve_fwd<> and sandwich<> of ssmq_device.h, written out: see the list there)
         double S[Y * (Y + 1) / 2];
 #pragma unroll
         for (int i = 0; i < Y * (Y + 1) / 2; ++i) S[i] = ob.cv[i];

@@ -26,6 +26,8 @@ struct InnovArgs {
 // e = y - y_mean; S: in = packed lower triangle of the innovation covariance, out = its Cholesky factor (the operation order of
 // chol_packed<>).  nis = |L^-1 e|^2, ll = -(Y log 2 pi + log det S + nis) / 2.  Returns false at a non-positive (or NaN) pivot.
 // YT > 0: Y fixed at compile time, everything in registers; YT = 0: Y = y_rt <= SSMQ_MAX_DIM at run time.
+// The factor and the forward substitution are chol_packed<> and tri_solve_fwd<> (ssmq_device.h) written out, with log det and nis
+// accumulated on the way: as helper calls the kernels came out with other register counts and the run-time-size one 5 % longer.
 template <int YT>
 __device__ __forceinline__ bool innovation_score(int y_rt, const double *e, double *S, double &nis, double &ll) {
     const int Y = YT ? YT : y_rt;

@@ -53,7 +53,8 @@ __device__ __forceinline__ bool ipls_step(bool lin, const double (&m)[D], const 
             RegSink<D, D> pr;      // z, S_z + G Q G', C_f [e][d] = cov(f_e, x_d); the core leaves chol(Pl_{k-1}) in lL0
             ok = moment_transform_core<D, D, ND, FD, FORM, TP, 0, true, 0, RegSink<D, D>>(lm0, lL0, t, fd, cpd, pr);
             double V[D * D], F[D * D], FP[D * D];
-            // V = C_f L^-T (forward substitution per row), F = V L^-1 (backward substitution)
+            // V = C_f L^-T (forward substitution per row), F = V L^-1 (backward substitution): the sums of tri_solve_fwd<> /
+            // tri_solve_bwd<> (ssmq_device.h), written out - see the list there; below also gain_from_cov<> and sandwich<>
 #pragma unroll
             for (int e = 0; e < D; ++e) {
 #pragma unroll
@@ -134,7 +135,7 @@ __device__ __forceinline__ bool ipls_step(bool lin, const double (&m)[D], const 
 #pragma unroll
             for (int d = 0; d < D; ++d) K[d] = div_nr(ob.cx[0][d], S[0]);
         } else {
-            ok = iplf_chol<Y>(Y, S) && ok;
+            ok = chol_packed<Y>(Y, S) && ok;
 #pragma unroll
             for (int d = 0; d < D; ++d) {
 #pragma unroll
@@ -191,8 +192,8 @@ __device__ __forceinline__ bool ipls_back(const double (&mf)[D], const double (&
     double dP[DP], G[D * D];
 #pragma unroll
     for (int i = 0; i < DP; ++i) dP[i] = Ps[i] - Pp[i];
-    const bool ok = iplf_chol<D>(D, Pp);
-    // G = C_k (P-)^-1: per row the two substitutions of iplf_update<>
+    const bool ok = chol_packed<D>(D, Pp);
+    // G = C_k (P-)^-1: per row the sums of cho_solve_row<> (ssmq_device.h), written out: see the list there
 #pragma unroll
     for (int d = 0; d < D; ++d) {
         double v[D];

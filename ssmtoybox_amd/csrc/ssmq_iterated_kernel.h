@@ -27,37 +27,12 @@ struct IplfArgs {
     FPar fd, fo;
 };
 
-// Lower Cholesky of a packed symmetric matrix in the operation order of chol_packed<>.  NT > 0: size fixed at compile time, unrolled
-// in full; NT = 0: n_rt <= SSMQ_MAX_DIM at run time.
-template <int NT>
-__device__ __forceinline__ bool iplf_chol(int n_rt, double *L) {
-    const int n = NT ? NT : n_rt;
-    constexpr int UN = NT ? NT : 1;
-    bool ok = true;
-#pragma unroll UN
-    for (int j = 0; j < n; ++j) {
-        double ajj = L[SSMQ_PK(j, j)];
-#pragma unroll UN
-        for (int k = 0; k < j; ++k) ajj -= L[SSMQ_PK(j, k)] * L[SSMQ_PK(j, k)];
-        ok = ok && (ajj > 0.0);
-        double r;
-        sqrt_rsqrt(ajj, ajj, r);
-        L[SSMQ_PK(j, j)] = ajj;
-#pragma unroll UN
-        for (int i = j + 1; i < n; ++i) {
-            double s = L[SSMQ_PK(i, j)];
-#pragma unroll UN
-            for (int k = 0; k < j; ++k) s -= L[SSMQ_PK(i, k)] * L[SSMQ_PK(j, k)];
-            L[SSMQ_PK(i, j)] = s * r;
-        }
-    }
-    return ok;
-}
-
 // One re-linearised update.  mp, Pp: the prior (Pp packed lower); mi, Li: the iterate, Li = chol(P_i) packed; yh, Sy, C: the
 // measurement moments at the iterate, Sy = S_y + R packed lower, C [Y][D] row-major = cov(h, x); y: the measurement.  Out: mn, Pn
 // (packed lower; may alias nothing above).  Returns false when S is not positive definite (the results are then garbage).
 // DT, YT > 0: dimensions fixed at compile time, everything in registers; 0: d_rt, y_rt <= SSMQ_MAX_DIM at run time.
+// The substitutions and the update are the sums of tri_solve_fwd / tri_solve_bwd / sandwich (ssmq_device.h) written out: as helper
+// calls the D = 5, Y = 4 k_ipls_pass<> came out with other spills and a third slower.
 template <int DT, int YT>
 __device__ __forceinline__ bool iplf_update(int d_rt, int y_rt, const double *mp, const double *Pp, const double *mi, const double *Li,
                                             const double *yh, const double *Sy, const double *C, const double *y, double *mn,
@@ -119,7 +94,7 @@ __device__ __forceinline__ bool iplf_update(int d_rt, int y_rt, const double *mp
 #pragma unroll UD
         for (int d = 0; d < D; ++d) K[d] = div_nr(Tm[d], S[0]);
     } else {
-        ok = iplf_chol<YT>(Y, S);
+        ok = chol_packed<YT>(Y, S);
 #pragma unroll UD
         for (int d = 0; d < D; ++d) {
 #pragma unroll UY
@@ -298,7 +273,7 @@ __global__ __launch_bounds__(kIplfUpdBlock) void k_iplf_update(const IplfUpdArgs
 #pragma unroll UD
         for (int d = 0; d < D; ++d) C[i * D + d] = a.P_yx[((int64_t)i * D + d) * ld + b];
     }
-    bool ok = iplf_chol<DT>(D, Li);
+    bool ok = chol_packed<DT>(D, Li);
     ok = iplf_update<DT, YT>(D, Y, mp, Pp, mi, Li, yh, Sy, C, yk, mn, Pn) && ok;
     int32_t agg = a.status[b];
     int32_t bad = ok ? 0 : 1;

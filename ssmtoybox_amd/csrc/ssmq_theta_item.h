@@ -347,6 +347,7 @@ __device__ __forceinline__ int32_t theta_item_core(int fid_dyn, int fid_obs, con
     double y_mean[Y], P_y[Y][Y], P_yx[Y][D];
     const bool ok_to = bq_transform_item<D, Y, NO, true>(fid_obs, fpo, t, m_pr, P_pr, xio, wo, emv_obs, rr, y_mean, P_y, P_yx);
     // ---- measurement update (kalman_update_item<D, Y>) --------------------------------------------------------------------------
+    // (the sums of gain_from_cov<> and sandwich<> of ssmq_device.h, written out: see the list there)
     double S[Y * (Y + 1) / 2];
 #pragma unroll
     for (int i = 0; i < Y; ++i)

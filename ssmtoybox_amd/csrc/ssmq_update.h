@@ -34,37 +34,15 @@ __device__ __forceinline__ void kalman_update_item(const UpdArgs &a, const uint3
     for (int i = 0; i < Y; ++i)
 #pragma unroll
         for (int j = 0; j < Y; ++j) Py[i][j] = a.P_y[(i * Y + j) * ld + b];
-    bool ok;
-    // X = P_y^-1 P_yx, column by column (forward then backward substitution); gain[d][i] = X[i][d]
-    double G[D][Y];
-    if (Y == 1) {
-        // scalar measurement: one division instead of factor + two substitutions (same shortcut as k_filter_fused)
-        ok = S[0] > 0.0;
+    // gain[d][i] = X[i][d], X = P_y^-1 P_yx (gain_from_cov: a scalar measurement takes one division).  P_yx is staged in
+    // registers on purpose: with the loads inside the callable the compiler forms the plane addresses differently and
+    // every k_kalman_update<> grows by 5 - 15 % in instructions.
+    double G[D][Y], Pyx[Y][D];
 #pragma unroll
-        for (int d = 0; d < D; ++d) G[d][0] = div_nr(a.P_yx[d * ld + b], S[0]);   // (Y == 1: row 0 only)
-    } else {
-        ok = chol_packed<Y>(S);
+    for (int d = 0; d < D; ++d)
 #pragma unroll
-        for (int d = 0; d < D; ++d) {
-            double v[Y];
-#pragma unroll
-            for (int i = 0; i < Y; ++i) {
-                double s = a.P_yx[(i * a.Dx + d) * ld + b];
-#pragma unroll
-                for (int k = 0; k < i; ++k) s -= S[SSMQ_PK(i, k)] * v[k];
-                v[i] = div_nr(s, S[SSMQ_PK(i, i)]);
-            }
-#pragma unroll
-            for (int i = Y - 1; i >= 0; --i) {
-                double s = v[i];
-#pragma unroll
-                for (int k = i + 1; k < Y; ++k) s -= S[SSMQ_PK(k, i)] * v[k];
-                v[i] = div_nr(s, S[SSMQ_PK(i, i)]);
-            }
-#pragma unroll
-            for (int i = 0; i < Y; ++i) G[d][i] = v[i];
-        }
-    }
+        for (int i = 0; i < Y; ++i) Pyx[i][d] = a.P_yx[(i * a.Dx + d) * ld + b];
+    const bool ok = gain_from_cov<D, Y>(S, [&](int i, int d) { return Pyx[i][d]; }, G);
     double dy[Y];
 #pragma unroll
     for (int i = 0; i < Y; ++i) dy[i] = a.y[i * ld + b] - a.y_mean[i * ld + b];
@@ -83,14 +61,9 @@ __device__ __forceinline__ void kalman_update_item(const UpdArgs &a, const uint3
         if (Y == 1) {
             dd = div_nr(dy[0] * dy[0], S[0]);
         } else {
+            tri_solve_fwd<Y>(S, [&](int i) { return dy[i]; }, dl);
 #pragma unroll
-            for (int i = 0; i < Y; ++i) {
-                double s = dy[i];
-#pragma unroll
-                for (int k = 0; k < i; ++k) s -= S[SSMQ_PK(i, k)] * dl[k];
-                dl[i] = div_nr(s, S[SSMQ_PK(i, i)]);
-                dd += dl[i] * dl[i];
-            }
+            for (int i = 0; i < Y; ++i) dd += dl[i] * dl[i];
         }
         sc2 = (a.student_dof + dd) / (a.student_dof + (double)Y);
     }
@@ -102,7 +75,8 @@ __device__ __forceinline__ void kalman_update_item(const UpdArgs &a, const uint3
         const double mp = a.m_pr[d * ld + b];
         a.m_fi[d * ld + b] = good ? mp + s : nan;
     }
-    // W = gain P_y (D x Y);  P = P_pr - W gain'
+    // P = P_pr - (gain P_y) gain': the sums of sandwich<> (ssmq_device.h), written out - with the P_pr loads and the P_fi / smat_out
+    // stores in its callable the plane addresses are formed differently and the kernels grow as above
 #pragma unroll
     for (int d = 0; d < D; ++d) {
         double w[Y];
