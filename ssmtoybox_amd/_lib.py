@@ -381,8 +381,11 @@ def rtc_stats():
     return c.value, h.value, s.value
 
 
-def check(rc, what=''):
-    """Negative return codes are errors; non-negative ones are passed through (0 ok, >0 first non-PD item + 1)."""
+def check(rc, what='', unsupported=False):
+    """Negative return codes are errors; non-negative ones are passed through (0 ok, >0 first non-PD item + 1).  With `unsupported`
+    code -3 (SSMQ_E_UNSUPPORTED: the library has no kernel for this case) is a NotImplementedError that carries its message."""
+    if unsupported and rc == -3:
+        raise NotImplementedError(last_error())
     if rc < 0:
         raise SsmqError('{} failed (code {}): {}'.format(what or 'libssmq call', rc, last_error()))
     return rc
@@ -425,6 +428,21 @@ def as_c(a):
 def out_c(shape):
     a = np.empty(shape, dtype=np.float64)
     return a, a.ctypes.data_as(c_double_p)
+
+
+def dp(a):
+    """A C-contiguous fp64 array as a `const double *` argument (None: a null pointer); the caller keeps the array alive."""
+    return None if a is None else a.ctypes.data_as(c_double_p)
+
+
+def vp(buf):
+    """A device buffer as a `void *` argument (None: a null pointer)."""
+    return ctypes.c_void_p(buf.ptr if buf is not None else None)
+
+
+def padded(B):
+    """The pitch of planes that hold B trajectories: whole waves of 64 lanes."""
+    return (B + 63) // 64 * 64
 
 
 class DeviceBuffer:
@@ -554,6 +572,38 @@ def scratch(nbytes):
     return ScratchBuffer(nbytes)
 
 
+class Staging:
+    """The device buffers of one entry point: `with Staging() as stage:` hands out scratch blocks (`stage.scratch`) and plain
+    DeviceBuffers (`stage.device`) and frees every one of them when the block is left, by an exception or not.  A `*_dev` entry
+    point passes the buffers it returns through `stage.release(...)` as its last statement: those are the caller's from then on."""
+
+    def __init__(self):
+        self.held = []
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+
+    def scratch(self, nbytes):
+        self.held.append(scratch(nbytes))
+        return self.held[-1]
+
+    def device(self, nbytes):
+        self.held.append(DeviceBuffer(nbytes))
+        return self.held[-1]
+
+    def release(self, *bufs):
+        self.held = [b for b in self.held if not any(b is r for r in bufs)]
+        return bufs
+
+    def free(self):
+        held, self.held = self.held, []
+        for buf in held:
+            buf.free()
+
+
 class _PinnedOwner:
     """Owns one block of ssmq_pinned_alloc and presents it through the array interface; the block goes back to the library's pool
     when the last ndarray that views it is collected (np.asarray(owner).base is the owner)."""
@@ -618,7 +668,7 @@ class SoA:
 
     def __init__(self, n_elem, batch, ld=None):
         self.n, self.B = int(n_elem), int(batch)
-        self.ld = int(ld) if ld is not None else (self.B + 63) // 64 * 64
+        self.ld = int(ld) if ld is not None else padded(self.B)
         self.buf = DeviceBuffer(8 * self.n * self.ld)
 
     @property

@@ -11,7 +11,7 @@ Per time step k = 1..T (both transforms use time index k - 1: ssinf.py:104, 276-
 all inside `ssmq_filter_forward_dev` (ssmtoybox_amd/csrc); nothing is computed in NumPy.
 `StudentianInference` (ssinf.py:555-736) runs the same loop with the reference's scale-matrix bookkeeping
 (`ssmq_student_filter_forward_dev`); `backward_pass*` is the RTS smoother (`ssmq_filter_smooth_dev`).  Models that take
-their noise as an argument (UNGMNA, CTRS; ssinf.py:271-295) go through `ssmq_filter_forward_aug_dev` (forward pass only).
+their noise as an argument (UNGMNA, CTRS; ssinf.py:271-295) go through `ssmq_filter_forward_aug_dev` / `ssmq_filter_smooth_aug_dev`.
 `MarginalInference` (ssinf.py:1034-1292) evaluates its theta-conditioned steps on the device (`ssmq_gp_theta_step`); the
 BFGS optimiser stays on the host as in the reference.
 """
@@ -28,9 +28,45 @@ from .bq.bqmtran import (GaussianProcessTransform, BayesSardTransform, StudentTP
 from .ssmod import TransitionModel, MeasurementModel, is_user_model, has_device_jacobian, user_unsupported, check_user_points
 
 
-def initial_planes(D, mean, cov, B, ld, x0_mean=None, x0_cov=None):
-    """The initial moments of B trajectories as planes [D][ld], [D*D][ld] (scratch buffers; the caller frees them): the model's
-    (mean, cov) for every trajectory, or the per-trajectory x0_mean (B, D) / x0_cov (B, D, D)."""
+_NOT_PD = 'Matrix is not positive definite (trajectory {}, step {})'
+
+
+def _raise_failed(status, prefix='', message=_NOT_PD):
+    """The LinAlgError of the first trajectory whose status is not 0 (1 + the step that failed), if there is one."""
+    if status.any():
+        b = int(np.flatnonzero(status)[0])
+        raise np.linalg.LinAlgError(prefix + message.format(b, int(status[b]) - 1))
+
+
+def _iteration_count(iterations):
+    """`iterations` as an int, or the ValueError of a count outside 1 .. ITERATED_MAX."""
+    if isinstance(iterations, bool) or int(iterations) != iterations or not 1 <= int(iterations) <= _lib.ITERATED_MAX:
+        raise ValueError('iterations must be an integer in 1 .. {} (got {!r})'.format(_lib.ITERATED_MAX, iterations))
+    return int(iterations)
+
+
+def initial_planes(stage, D, mean, cov, B, ld, x0_mean=None, x0_cov=None, broadcast_on_device=False):
+    """The initial moments of B trajectories as planes [D][ld], [D*D][ld], buffers of the staging scope `stage`: the model's
+    (mean, cov) for every trajectory, or the per-trajectory x0_mean (B, D) / x0_cov (B, D, D), laid out on the host and uploaded
+    (scratch blocks).  broadcast_on_device: the model's moments only, one 64-lane tile per plane uploaded and doubled on the device
+    until the plane is full (DeviceBuffers; no host array of the size of the batch)."""
+    if broadcast_on_device:
+        assert x0_mean is None and x0_cov is None
+        lib = _lib.load()
+        planes = []
+        for moment, n in ((mean, D), (cov, D * D)):
+            tile = np.ascontiguousarray(np.repeat(np.asarray(moment, dtype=np.float64).reshape(n, 1), 64, axis=1))
+            dev = stage.device(8 * n * ld)
+            for e in range(n):
+                dev.upload(tile[e], byte_offset=8 * e * ld)
+                done = 64
+                while done < ld:
+                    step = min(done, ld - done)
+                    _lib.check(lib.ssmq_memcpy_d2d(dev.at(8 * (e * ld + done)), dev.at(8 * e * ld), ctypes.c_size_t(8 * step)),
+                               'ssmq_memcpy_d2d')
+                    done += step
+            planes.append(dev)
+        return planes
     m0 = np.broadcast_to(mean, (B, D)) if x0_mean is None else np.asarray(x0_mean, dtype=np.float64)
     P0 = np.broadcast_to(cov, (B, D, D)) if x0_cov is None else np.asarray(x0_cov, dtype=np.float64)
     mbuf = np.zeros((D, ld))
@@ -39,7 +75,7 @@ def initial_planes(D, mean, cov, B, ld, x0_mean=None, x0_cov=None):
     Pbuf[:, :B] = P0.reshape(B, D * D).T
     if ld > B:       # padding lanes are never read (b >= B), keep them PD anyway
         Pbuf[:, B:] = np.eye(D).reshape(-1, 1)
-    d_m0, d_P0 = _lib.scratch(mbuf.nbytes), _lib.scratch(Pbuf.nbytes)
+    d_m0, d_P0 = stage.scratch(mbuf.nbytes), stage.scratch(Pbuf.nbytes)
     d_m0.upload(mbuf)
     d_P0.upload(Pbuf)
     return d_m0, d_P0
@@ -78,6 +114,47 @@ class GaussianInference:
     def _additive(self):
         return self.mod_dyn.noise_additive and self.mod_obs.noise_additive
 
+    # ---- what every entry point below is built from: the pair, the noise arguments, a staging scope (`_lib.Staging`), the status
+    # check (`_raise_failed`) ------------------------------------------------------------------------------------------------------
+    _recursion = 'gauss'         # 'student': the Studentian recursion (its own entry point, `scale` / `dof` in a `run_filters` job)
+
+    def _pair(self):
+        """(h_dyn, f_dyn, h_obs, f_obs): the transform handles and integrand descriptors every C entry point starts with (ctypes
+        passes a descriptor by reference where the prototype says so)."""
+        f_dyn, e_dyn = resolve_integrand(self.mod_dyn.dyn_eval)
+        f_obs, e_obs = resolve_integrand(self.mod_obs.meas_eval)
+        return self.tf_dyn._handle_for(e_dyn), f_dyn, self.tf_obs._handle_for(e_obs), f_obs
+
+    def _noise(self):
+        """The additive terms of the recursion as C arrays: G Q G' and R (None for a model that takes its noise as an argument)."""
+        gqg = np.ascontiguousarray(self.G.dot(self.q_cov).dot(self.G.T), dtype=np.float64) if self.mod_dyn.noise_additive else None
+        rr = np.ascontiguousarray(self.r_cov, dtype=np.float64) if self.mod_obs.noise_additive else None
+        return gqg, rr
+
+    def _noise_aug(self):
+        """(q_mean, q_cov, dim_q, r_mean, r_cov, dim_r) of the augmented recursion: the moments of a noise that enters its model
+        function (ssinf.py:271-272, 282-283, 294-295); (None, the term of `_noise`, 0) for an additive one."""
+        def moments(mean, cov):
+            mean = np.ascontiguousarray(np.atleast_1d(mean), dtype=np.float64)
+            return mean, np.ascontiguousarray(np.atleast_2d(cov), dtype=np.float64), int(mean.shape[0])
+        gqg, rr = self._noise()
+        return ((None, gqg, 0) if gqg is not None else moments(self.q_mean, self.q_cov)) + \
+               ((None, rr, 0) if rr is not None else moments(self.r_mean, self.r_cov))
+
+    def _kernel_name(self, fn, *extra, unsupported=False):
+        """`fn(pair..., extra..., buf, 512)` of the library, checked and decoded (unsupported: see `_lib.check`)."""
+        buf = ctypes.create_string_buffer(512)
+        _lib.check(getattr(_lib.load(), fn)(*self._pair(), *extra, buf, 512), fn, unsupported)
+        return buf.value.decode()
+
+    def _initial_planes(self, stage, B, ld, x0_mean=None, x0_cov=None, broadcast_on_device=False):
+        """The initial moments of B trajectories as planes [D][ld], [D*D][ld], buffers of `stage` (`initial_planes`)."""
+        return initial_planes(stage, self.mod_dyn.dim_state, self.x0_mean, self._initial_cov(), B, ld, x0_mean, x0_cov,
+                              broadcast_on_device)
+
+    def _initial_cov(self):
+        return self.x0_cov
+
     def kernel_name(self, batch=0):
         """Which kernel(s) the device filter loop runs for this filter (one fused kernel - k_filter_fused<..> and its schedules,
         k_ekf_loop<D=..,Y=..> for ExtendedKalman on built-in models - or a replayed hipGraph of 3 T launches) on a batch of
@@ -86,67 +163,41 @@ class GaussianInference:
             return ('k_filter_fused_aug (one kernel for the time loop) where instantiated, else a launch loop of 5 T '
                     'launches (k_augment | apply dyn | k_augment | apply obs | k_kalman_update)')
         self._check_user_points()
-        f_dyn, e_dyn = resolve_integrand(self.mod_dyn.dyn_eval)
-        f_obs, e_obs = resolve_integrand(self.mod_obs.meas_eval)
-        buf = ctypes.create_string_buffer(512)
-        _lib.check(_lib.load().ssmq_filter_kernel_name_batch(ctypes.c_void_p(self.tf_dyn._handle_for(e_dyn)),
-                                                             ctypes.byref(f_dyn),
-                                                             ctypes.c_void_p(self.tf_obs._handle_for(e_obs)),
-                                                             ctypes.byref(f_obs), int(batch), buf, 512), 'ssmq_filter_kernel_name_batch')
-        return buf.value.decode()
+        return self._kernel_name('ssmq_filter_kernel_name_batch', int(batch))
 
     def forward_pass(self, data):
         """data (dim_y, T) -> filtered means (D, T), covariances (D, D, T)  (ssinf.py:66-118)."""
         fm, fP = self.forward_pass_batch(np.asarray(data)[..., None])
         return fm[..., 0], fP[..., 0]
 
-    def _launch(self, lib, h_dyn, f_dyn, h_obs, f_obs, B, ld, T, d_y, d_m0, d_P0, d_fm, d_fP, d_st):
+    def _launch(self, lib, B, ld, T, d_y, d_m0, d_P0, d_fm, d_fP, d_st):
         if not self._additive:
-            return self._launch_aug(lib, h_dyn, f_dyn, h_obs, f_obs, B, ld, T, d_y, d_m0, d_P0, d_fm, d_fP, d_st)
-        gqg, pg = _lib.as_c(self.G.dot(self.q_cov).dot(self.G.T))
-        rr, pr = _lib.as_c(self.r_cov)
-        _lib.check(lib.ssmq_filter_forward_dev(ctypes.c_void_p(h_dyn), ctypes.byref(f_dyn), ctypes.c_void_p(h_obs),
-                                               ctypes.byref(f_obs), B, ld, T, ctypes.c_void_p(d_y.ptr),
-                                               ctypes.c_void_p(d_m0.ptr), ctypes.c_void_p(d_P0.ptr), pg, pr,
-                                               ctypes.c_void_p(d_fm.ptr), ctypes.c_void_p(d_fP.ptr),
-                                               ctypes.c_void_p(d_st.ptr)), 'ssmq_filter_forward_dev')
+            return self._launch_aug(lib, B, ld, T, d_y, d_m0, d_P0, d_fm, d_fP, d_st)
+        gqg, rr = self._noise()
+        vp, dp = _lib.vp, _lib.dp
+        _lib.check(lib.ssmq_filter_forward_dev(*self._pair(), B, ld, T, vp(d_y), vp(d_m0), vp(d_P0), dp(gqg), dp(rr), vp(d_fm), vp(d_fP),
+                                               vp(d_st)), 'ssmq_filter_forward_dev')
 
-    def _launch_aug(self, lib, h_dyn, f_dyn, h_obs, f_obs, B, ld, T, d_y, d_m0, d_P0, d_fm, d_fP, d_st, d_sm=None,
-                    d_sP=None):
+    def _launch_smooth(self, lib, B, ld, T, d_y, d_m0, d_P0, d_fm, d_fP, d_sm, d_sP, d_st):
+        """The forward pass and the RTS smoother in one call."""
+        if not self._additive:
+            return self._launch_aug(lib, B, ld, T, d_y, d_m0, d_P0, d_fm, d_fP, d_st, d_sm, d_sP)
+        gqg, rr = self._noise()
+        vp, dp = _lib.vp, _lib.dp
+        _lib.check(lib.ssmq_filter_smooth_dev(*self._pair(), B, ld, T, vp(d_y), vp(d_m0), vp(d_P0), dp(gqg), dp(rr), vp(d_fm), vp(d_fP),
+                                              vp(d_sm), vp(d_sP), vp(d_st)), 'ssmq_filter_smooth_dev')
+
+    def _launch_aug(self, lib, B, ld, T, d_y, d_m0, d_P0, d_fm, d_fP, d_st, d_sm=None, d_sP=None):
         """Noise enters the model functions: augmented moments per transform (ssinf.py:271-272, 282-283, 294-295).
         With d_sm / d_sP the RTS smoother runs as well (`ssmq_filter_smooth_aug_dev`)."""
-        if self.mod_dyn.noise_additive:
-            dq, (qm, pqm) = 0, (None, None)
-            qc, pqc = _lib.as_c(self.G.dot(self.q_cov).dot(self.G.T))
-        else:
-            dq = int(np.atleast_1d(self.q_mean).shape[0])
-            qm, pqm = _lib.as_c(np.atleast_1d(self.q_mean))
-            qc, pqc = _lib.as_c(np.atleast_2d(self.q_cov))
-        if self.mod_obs.noise_additive:
-            dr, (rm, prm) = 0, (None, None)
-            rc, prc = _lib.as_c(self.r_cov)
-        else:
-            dr = int(np.atleast_1d(self.r_mean).shape[0])
-            rm, prm = _lib.as_c(np.atleast_1d(self.r_mean))
-            rc, prc = _lib.as_c(np.atleast_2d(self.r_cov))
+        qm, qc, dq, rm, rc, dr = self._noise_aug()
+        vp, dp = _lib.vp, _lib.dp
+        args = (*self._pair(), self.mod_dyn.dim_state, B, ld, T, vp(d_y), vp(d_m0), vp(d_P0), dp(qm), dp(qc), dq, dp(rm), dp(rc), dr,
+                vp(d_fm), vp(d_fP))
         if d_sm is not None:
-            _lib.check(lib.ssmq_filter_smooth_aug_dev(ctypes.c_void_p(h_dyn), ctypes.byref(f_dyn), ctypes.c_void_p(h_obs),
-                                                      ctypes.byref(f_obs), self.mod_dyn.dim_state, B, ld, T,
-                                                      ctypes.c_void_p(d_y.ptr), ctypes.c_void_p(d_m0.ptr),
-                                                      ctypes.c_void_p(d_P0.ptr), pqm, pqc, dq, prm, prc, dr,
-                                                      ctypes.c_void_p(d_fm.ptr), ctypes.c_void_p(d_fP.ptr),
-                                                      ctypes.c_void_p(d_sm.ptr), ctypes.c_void_p(d_sP.ptr),
-                                                      ctypes.c_void_p(d_st.ptr)), 'ssmq_filter_smooth_aug_dev')
-            return
-        _lib.check(lib.ssmq_filter_forward_aug_dev(ctypes.c_void_p(h_dyn), ctypes.byref(f_dyn), ctypes.c_void_p(h_obs),
-                                                   ctypes.byref(f_obs), self.mod_dyn.dim_state, B, ld, T,
-                                                   ctypes.c_void_p(d_y.ptr), ctypes.c_void_p(d_m0.ptr),
-                                                   ctypes.c_void_p(d_P0.ptr), pqm, pqc, dq, prm, prc, dr,
-                                                   ctypes.c_void_p(d_fm.ptr), ctypes.c_void_p(d_fP.ptr),
-                                                   ctypes.c_void_p(d_st.ptr)), 'ssmq_filter_forward_aug_dev')
-
-    def _initial_cov(self):
-        return self.x0_cov
+            _lib.check(lib.ssmq_filter_smooth_aug_dev(*args, vp(d_sm), vp(d_sP), vp(d_st)), 'ssmq_filter_smooth_aug_dev')
+        else:
+            _lib.check(lib.ssmq_filter_forward_aug_dev(*args, vp(d_st)), 'ssmq_filter_forward_aug_dev')
 
     def backward_pass(self):
         """RTS smoothing of the trajectory given to the last forward_pass (ssinf.py:120-147)."""
@@ -169,41 +220,22 @@ class GaussianInference:
         self._check_user_points()
         lib = _lib.load()
         D = self.mod_dyn.dim_state
-        mrow = np.ascontiguousarray(np.repeat(np.asarray(self.x0_mean, dtype=np.float64).reshape(D, 1), 64, axis=1))
-        Prow = np.ascontiguousarray(np.repeat(np.asarray(self._initial_cov(), dtype=np.float64).reshape(D * D, 1), 64,
-                                              axis=1))
-        d_m0, d_P0 = _lib.DeviceBuffer(8 * D * ld), _lib.DeviceBuffer(8 * D * D * ld)
-        for host, dev, n in ((mrow, d_m0, D), (Prow, d_P0, D * D)):       # one 64-lane tile per plane, doubled on the device
-            for e in range(n):
-                dev.upload(host[e], byte_offset=8 * e * ld)
-                done = 64
-                while done < ld:
-                    step = min(done, ld - done)
-                    _lib.check(lib.ssmq_memcpy_d2d(dev.at(8 * (e * ld + done)), dev.at(8 * e * ld),
-                                                   ctypes.c_size_t(8 * step)), 'ssmq_memcpy_d2d')
-                    done += step
-        d_fm, d_fP = _lib.DeviceBuffer(8 * T * D * ld), _lib.DeviceBuffer(8 * T * D * D * ld)
-        d_st = _lib.DeviceBuffer(4 * ld)
-        f_dyn, e_dyn = resolve_integrand(self.mod_dyn.dyn_eval)
-        f_obs, e_obs = resolve_integrand(self.mod_obs.meas_eval)
-        h_dyn, h_obs = self.tf_dyn._handle_for(e_dyn), self.tf_obs._handle_for(e_obs)
-        self._launch(lib, h_dyn, f_dyn, h_obs, f_obs, B, ld, T, d_y, d_m0, d_P0, d_fm, d_fP, d_st)
-        _lib.sync()
-        d_m0.free()
-        d_P0.free()
-        return d_fm, d_fP, d_st
+        with _lib.Staging() as stage:
+            d_m0, d_P0 = self._initial_planes(stage, B, ld, broadcast_on_device=True)
+            d_fm, d_fP, d_st = stage.device(8 * T * D * ld), stage.device(8 * T * D * D * ld), stage.device(4 * ld)
+            self._launch(lib, B, ld, T, d_y, d_m0, d_P0, d_fm, d_fP, d_st)
+            _lib.sync()
+            return stage.release(d_fm, d_fP, d_st)
 
     def _forward_pass_piped(self, lib, data, x0_mean, x0_cov, raise_on_failure):
         """The forward pass with its transfers overlapped (`ssmq_filter_forward_piped`: time blocks; the measurements of the next
         block go up and the moments of the previous one come down while a block runs).  None when the filter has no time-block
         kernel - the caller then takes the upload / pass / download path.  Results: the same bits either way."""
-        if type(self)._launch is not GaussianInference._launch:        # Studentian recursion: not pipelined
+        if self._recursion != 'gauss':        # Studentian recursion: not pipelined
             return None
         Y, T, B = data.shape
         D = self.mod_dyn.dim_state
-        f_dyn, e_dyn = resolve_integrand(self.mod_dyn.dyn_eval)
-        f_obs, e_obs = resolve_integrand(self.mod_obs.meas_eval)
-        h_dyn, h_obs = self.tf_dyn._handle_for(e_dyn), self.tf_obs._handle_for(e_obs)
+        pair = self._pair()
         flags = 0
         if x0_mean is None and x0_cov is None:
             m0, P0 = np.ascontiguousarray(self.x0_mean, dtype=np.float64), np.ascontiguousarray(self._initial_cov(), dtype=np.float64)
@@ -217,20 +249,17 @@ class GaussianInference:
         else:
             flags |= 1           # SSMQ_PIPED_OUT_PINNED
         st = np.empty(B, dtype=np.int32)
-        gqg, pg = _lib.as_c(self.G.dot(self.q_cov).dot(self.G.T))
-        rr, pr = _lib.as_c(self.r_cov)
+        gqg, rr = self._noise()
         yc = np.ascontiguousarray(data)
-        dp = lambda a: a.ctypes.data_as(_lib.c_double_p)       # noqa: E731
-        rc = lib.ssmq_filter_forward_piped(ctypes.c_void_p(h_dyn), ctypes.byref(f_dyn), ctypes.c_void_p(h_obs), ctypes.byref(f_obs), B, T,
-                                           dp(yc), dp(m0), dp(P0), pg, pr, ctypes.c_void_p(fm.ctypes.data),
+        dp = _lib.dp
+        rc = lib.ssmq_filter_forward_piped(*pair, B, T, dp(yc), dp(m0), dp(P0), dp(gqg), dp(rr), ctypes.c_void_p(fm.ctypes.data),
                                            ctypes.c_void_p(fP.ctypes.data), ctypes.c_void_p(st.ctypes.data), flags, 0)
         if rc == -3:             # SSMQ_E_UNSUPPORTED
             return None
         _lib.check(rc, 'ssmq_filter_forward_piped')
         self.status = st
-        if raise_on_failure and st.any():
-            b = int(np.flatnonzero(st)[0])
-            raise np.linalg.LinAlgError('Matrix is not positive definite (trajectory {}, step {})'.format(b, int(st[b]) - 1))
+        if raise_on_failure:
+            _raise_failed(st)
         self.fi_mean, self.fi_cov = fm, fP
         return fm, fP
 
@@ -244,109 +273,78 @@ class GaussianInference:
         self._data = data
         Y, T, B = data.shape
         D = self.mod_dyn.dim_state
-        ld = (B + 63) // 64 * 64
+        ld = _lib.padded(B)
         if not smooth and self._additive and B > 0 and T > 0:
             done = self._forward_pass_piped(lib, data, x0_mean, x0_cov, raise_on_failure)
             if done is not None:
                 return done
-        # (dim_y, T, B) -> planes [T][Y][ld]: a row permutation, done between the caller's array and the library's pinned
-        # staging block (`ssmq_upload_planes`)
-        d_y = _lib.scratch(8 * T * Y * ld)
-        _lib.upload_study(data, Y, ld, d_y)
-        d_m0, d_P0 = self._initial_planes(B, ld, x0_mean, x0_cov)
-        d_fm, d_fP = _lib.scratch(8 * T * D * ld), _lib.scratch(8 * T * D * D * ld)
-        d_st = _lib.scratch(4 * ld)
-        f_dyn, e_dyn = resolve_integrand(self.mod_dyn.dyn_eval)
-        f_obs, e_obs = resolve_integrand(self.mod_obs.meas_eval)
-        h_dyn, h_obs = self.tf_dyn._handle_for(e_dyn), self.tf_obs._handle_for(e_obs)
-        if smooth:
-            d_sm, d_sP = _lib.scratch(8 * T * D * ld), _lib.scratch(8 * T * D * D * ld)
-            if not self._additive:
-                self._launch_aug(lib, h_dyn, f_dyn, h_obs, f_obs, B, ld, T, d_y, d_m0, d_P0, d_fm, d_fP, d_st, d_sm, d_sP)
+        with _lib.Staging() as stage:
+            # (dim_y, T, B) -> planes [T][Y][ld]: a row permutation, done between the caller's array and the library's pinned
+            # staging block (`ssmq_upload_planes`)
+            d_y = stage.scratch(8 * T * Y * ld)
+            _lib.upload_study(data, Y, ld, d_y)
+            d_m0, d_P0 = self._initial_planes(stage, B, ld, x0_mean, x0_cov)
+            d_fm, d_fP, d_st = stage.scratch(8 * T * D * ld), stage.scratch(8 * T * D * D * ld), stage.scratch(4 * ld)
+            if smooth:
+                d_sm, d_sP = stage.scratch(8 * T * D * ld), stage.scratch(8 * T * D * D * ld)
+                self._launch_smooth(lib, B, ld, T, d_y, d_m0, d_P0, d_fm, d_fP, d_sm, d_sP, d_st)
+                self.sm_mean = _lib.download_study(d_sm, (D,), T, B, ld)
+                self.sm_cov = _lib.download_study(d_sP, (D, D), T, B, ld)
             else:
-                gqg, pg = _lib.as_c(self.G.dot(self.q_cov).dot(self.G.T))
-                rr, pr = _lib.as_c(self.r_cov)
-                _lib.check(lib.ssmq_filter_smooth_dev(ctypes.c_void_p(h_dyn), ctypes.byref(f_dyn), ctypes.c_void_p(h_obs),
-                                                      ctypes.byref(f_obs), B, ld, T, ctypes.c_void_p(d_y.ptr),
-                                                      ctypes.c_void_p(d_m0.ptr), ctypes.c_void_p(d_P0.ptr), pg, pr,
-                                                      ctypes.c_void_p(d_fm.ptr), ctypes.c_void_p(d_fP.ptr),
-                                                      ctypes.c_void_p(d_sm.ptr), ctypes.c_void_p(d_sP.ptr),
-                                                      ctypes.c_void_p(d_st.ptr)), 'ssmq_filter_smooth_dev')
-            self.sm_mean = _lib.download_study(d_sm, (D,), T, B, ld)
-            self.sm_cov = _lib.download_study(d_sP, (D, D), T, B, ld)
-            d_sm.free()
-            d_sP.free()
-        else:
-            self._launch(lib, h_dyn, f_dyn, h_obs, f_obs, B, ld, T, d_y, d_m0, d_P0, d_fm, d_fP, d_st)
-        fm = _lib.download_study(d_fm, (D,), T, B, ld)       # planes [T][D][ld] -> (D, T, B), via pinned staging
-        fP = _lib.download_study(d_fP, (D, D), T, B, ld)
-        self.status = d_st.download((ld,), dtype=np.int32)[:B]
-        for buf in (d_y, d_m0, d_P0, d_fm, d_fP, d_st):
-            buf.free()
-        if raise_on_failure and self.status.any():
-            b = int(np.flatnonzero(self.status)[0])
-            raise np.linalg.LinAlgError('Matrix is not positive definite (trajectory {}, step {})'.format(
-                b, int(self.status[b]) - 1))
+                self._launch(lib, B, ld, T, d_y, d_m0, d_P0, d_fm, d_fP, d_st)
+            fm = _lib.download_study(d_fm, (D,), T, B, ld)       # planes [T][D][ld] -> (D, T, B), via pinned staging
+            fP = _lib.download_study(d_fP, (D, D), T, B, ld)
+            self.status = d_st.download((ld,), dtype=np.int32)[:B]
+        if raise_on_failure:
+            _raise_failed(self.status)
         self.fi_mean, self.fi_cov = fm, fP
         return self.fi_mean, self.fi_cov
 
     # ---- innovation scores: what a filter run on measurements alone can be judged by -------------------------------------------
     def _innovations_refusal(self):
         """None, or the NotImplementedError of a filter outside the range of the innovation scores (additive-noise Gaussian
-        recursion) - raised before the library is touched."""
+        recursion)."""
         if not self._additive:
             return NotImplementedError('innovation scores cover the additive-noise Gaussian recursion; not implemented for models '
                                        'that take their noise as an argument (non-additive noise)')
         return None
 
+    def _additive_gauss_only(self, what='innovation scores cover'):
+        """Raises what keeps a filter out of the passes that cover the range of the innovation scores (`what` names the pass) -
+        before the library is touched."""
+        err = self._innovations_refusal()
+        if err is not None:
+            raise NotImplementedError(str(err).replace('innovation scores cover', what))
+
     def innovations_kernel_name(self, batch=0):
         """Which kernel(s) `innovations_*` run for this filter: k_innovation<..> (all T B items in one launch) where the fused time
         loop has an instantiation, and for user models; else the launch loop apply dyn | apply obs | k_innovation_score."""
-        err = self._innovations_refusal()
-        if err is not None:
-            raise err
+        self._additive_gauss_only()
         self._check_user_points()
-        f_dyn, e_dyn = resolve_integrand(self.mod_dyn.dyn_eval)
-        f_obs, e_obs = resolve_integrand(self.mod_obs.meas_eval)
-        buf = ctypes.create_string_buffer(512)
-        _lib.check(_lib.load().ssmq_innovations_kernel_name(ctypes.c_void_p(self.tf_dyn._handle_for(e_dyn)), ctypes.byref(f_dyn),
-                                                            ctypes.c_void_p(self.tf_obs._handle_for(e_obs)), ctypes.byref(f_obs),
-                                                            int(batch), buf, 512), 'ssmq_innovations_kernel_name')
-        return buf.value.decode()
+        return self._kernel_name('ssmq_innovations_kernel_name', int(batch))
 
     def _launch_innovations(self, lib, B, ld, T, d_y, d_m0, d_P0, d_fm, d_fP, d_ym, d_S, d_nis, d_ll, d_tot, d_st):
-        f_dyn, e_dyn = resolve_integrand(self.mod_dyn.dyn_eval)
-        f_obs, e_obs = resolve_integrand(self.mod_obs.meas_eval)
-        h_dyn, h_obs = self.tf_dyn._handle_for(e_dyn), self.tf_obs._handle_for(e_obs)
-        gqg, pg = _lib.as_c(self.G.dot(self.q_cov).dot(self.G.T))
-        rr, pr = _lib.as_c(self.r_cov)
-        vp = lambda b: ctypes.c_void_p(b.ptr if b is not None else None)       # noqa: E731
-        _lib.check(lib.ssmq_filter_innovations_dev(ctypes.c_void_p(h_dyn), ctypes.byref(f_dyn), ctypes.c_void_p(h_obs), ctypes.byref(f_obs),
-                                                   B, ld, T, vp(d_y), vp(d_m0), vp(d_P0), vp(d_fm), vp(d_fP), pg, pr, vp(d_ym), vp(d_S),
-                                                   vp(d_nis), vp(d_ll), vp(d_tot), vp(d_st)), 'ssmq_filter_innovations_dev')
-
-    def _initial_planes(self, B, ld, x0_mean=None, x0_cov=None):
-        """The initial moments of B trajectories as planes [D][ld], [D*D][ld] (scratch buffers; the caller frees them)."""
-        return initial_planes(self.mod_dyn.dim_state, self.x0_mean, self._initial_cov(), B, ld, x0_mean, x0_cov)
+        gqg, rr = self._noise()
+        vp, dp = _lib.vp, _lib.dp
+        _lib.check(lib.ssmq_filter_innovations_dev(*self._pair(), B, ld, T, vp(d_y), vp(d_m0), vp(d_P0), vp(d_fm), vp(d_fP), dp(gqg),
+                                                   dp(rr), vp(d_ym), vp(d_S), vp(d_nis), vp(d_ll), vp(d_tot), vp(d_st)),
+                   'ssmq_filter_innovations_dev')
 
     def innovations_dev(self, d_y, d_fm, d_fP, B, ld, T):
         """Innovation scores of a pass whose measurements and filtered moments are on the device (what `ssmod.simulate_dev` /
         `forward_pass_dev` return): DeviceBuffers (d_nis [T][ld], d_ll [T][ld], d_total [2][ld]: sum of the log-likelihoods and mean
         NIS of every trajectory, d_status [ld] int32: 1 + the first step whose scores are NaN, or 0); the caller frees them.  Every
         trajectory starts from the model's initial moments, as in `forward_pass_dev`."""
-        err = self._innovations_refusal()
-        if err is not None:
-            raise err
+        self._additive_gauss_only()
         self._check_user_points()
         lib = _lib.load()
-        d_m0, d_P0 = self._initial_planes(B, ld)
-        d_nis, d_ll = _lib.DeviceBuffer(8 * T * ld), _lib.DeviceBuffer(8 * T * ld)
-        d_tot, d_st = _lib.DeviceBuffer(8 * 2 * ld), _lib.DeviceBuffer(4 * ld)
-        self._launch_innovations(lib, B, ld, T, d_y, d_m0, d_P0, d_fm, d_fP, None, None, d_nis, d_ll, d_tot, d_st)
-        _lib.sync()
-        d_m0.free()
-        d_P0.free()
-        return d_nis, d_ll, d_tot, d_st
+        with _lib.Staging() as stage:
+            d_m0, d_P0 = self._initial_planes(stage, B, ld)
+            d_nis, d_ll = stage.device(8 * T * ld), stage.device(8 * T * ld)
+            d_tot, d_st = stage.device(8 * 2 * ld), stage.device(4 * ld)
+            self._launch_innovations(lib, B, ld, T, d_y, d_m0, d_P0, d_fm, d_fP, None, None, d_nis, d_ll, d_tot, d_st)
+            _lib.sync()
+            return stage.release(d_nis, d_ll, d_tot, d_st)
 
     def innovations_batch(self, data, x0_mean=None, x0_cov=None, fi_mean=None, fi_cov=None, return_moments=False):
         """Normalised innovation squared and measurement log-likelihood of every step, data (dim_y, T, B): with (m, P) the initial
@@ -358,9 +356,7 @@ class GaussianInference:
         loglik_total (B,), nis_mean (B,), status (B,) - 1 + the first step whose scores are NaN (the filter failed there or
         earlier, or a covariance is not positive definite), 0 if none; with return_moments also y_mean (dim_y, T, B) and y_cov
         (dim_y, dim_y, T, B)."""
-        err = self._innovations_refusal()
-        if err is not None:
-            raise err
+        self._additive_gauss_only()
         if (fi_mean is None) != (fi_cov is None):
             raise ValueError('innovations_batch: give fi_mean and fi_cov, or neither')
         self._check_user_points()
@@ -370,26 +366,24 @@ class GaussianInference:
         lib = _lib.load()
         Y, T, B = data.shape
         D = self.mod_dyn.dim_state
-        ld = (B + 63) // 64 * 64
-        d_y, d_fm, d_fP = _lib.scratch(8 * T * Y * ld), _lib.scratch(8 * T * D * ld), _lib.scratch(8 * T * D * D * ld)
-        _lib.upload_study(data, Y, ld, d_y)
-        _lib.upload_study(np.asarray(fi_mean, dtype=np.float64).reshape(D, T, B), D, ld, d_fm)
-        _lib.upload_study(np.asarray(fi_cov, dtype=np.float64).reshape(D * D, T, B), D * D, ld, d_fP)
-        d_m0, d_P0 = self._initial_planes(B, ld, x0_mean, x0_cov)
-        d_nis, d_ll, d_tot, d_st = _lib.scratch(8 * T * ld), _lib.scratch(8 * T * ld), _lib.scratch(8 * 2 * ld), _lib.scratch(4 * ld)
-        d_ym = _lib.scratch(8 * T * Y * ld) if return_moments else None
-        d_S = _lib.scratch(8 * T * Y * Y * ld) if return_moments else None
-        self._launch_innovations(lib, B, ld, T, d_y, d_m0, d_P0, d_fm, d_fP, d_ym, d_S, d_nis, d_ll, d_tot, d_st)
-        out = {'nis': _lib.download_study(d_nis, (), T, B, ld), 'loglik': _lib.download_study(d_ll, (), T, B, ld)}
-        tot = d_tot.download((2, ld))
-        out['loglik_total'], out['nis_mean'] = tot[0, :B].copy(), tot[1, :B].copy()
-        out['status'] = d_st.download((ld,), dtype=np.int32)[:B]
-        if return_moments:
-            out['y_mean'] = _lib.download_study(d_ym, (Y,), T, B, ld)
-            out['y_cov'] = _lib.download_study(d_S, (Y, Y), T, B, ld)
-        for buf in (d_y, d_fm, d_fP, d_m0, d_P0, d_nis, d_ll, d_tot, d_st, d_ym, d_S):
-            if buf is not None:
-                buf.free()
+        ld = _lib.padded(B)
+        with _lib.Staging() as stage:
+            d_y, d_fm, d_fP = stage.scratch(8 * T * Y * ld), stage.scratch(8 * T * D * ld), stage.scratch(8 * T * D * D * ld)
+            _lib.upload_study(data, Y, ld, d_y)
+            _lib.upload_study(np.asarray(fi_mean, dtype=np.float64).reshape(D, T, B), D, ld, d_fm)
+            _lib.upload_study(np.asarray(fi_cov, dtype=np.float64).reshape(D * D, T, B), D * D, ld, d_fP)
+            d_m0, d_P0 = self._initial_planes(stage, B, ld, x0_mean, x0_cov)
+            d_nis, d_ll, d_tot, d_st = stage.scratch(8 * T * ld), stage.scratch(8 * T * ld), stage.scratch(8 * 2 * ld), stage.scratch(4 * ld)
+            d_ym = stage.scratch(8 * T * Y * ld) if return_moments else None
+            d_S = stage.scratch(8 * T * Y * Y * ld) if return_moments else None
+            self._launch_innovations(lib, B, ld, T, d_y, d_m0, d_P0, d_fm, d_fP, d_ym, d_S, d_nis, d_ll, d_tot, d_st)
+            out = {'nis': _lib.download_study(d_nis, (), T, B, ld), 'loglik': _lib.download_study(d_ll, (), T, B, ld)}
+            tot = d_tot.download((2, ld))
+            out['loglik_total'], out['nis_mean'] = tot[0, :B].copy(), tot[1, :B].copy()
+            out['status'] = d_st.download((ld,), dtype=np.int32)[:B]
+            if return_moments:
+                out['y_mean'] = _lib.download_study(d_ym, (Y,), T, B, ld)
+                out['y_cov'] = _lib.download_study(d_S, (Y, Y), T, B, ld)
         return out
 
     def innovations(self, data):
@@ -397,41 +391,24 @@ class GaussianInference:
         out = self.innovations_batch(np.asarray(data)[..., None])
         return {k: (v[..., 0] if v.ndim else v) for k, v in out.items()}
 
-
     # ---- iterated posterior linearisation (IPLF): J measurement updates per step, each re-linearised around the posterior ------
     def _iterated_refusal(self, iterations):
         """Raises what keeps a filter or an iteration count out of the iterated pass - before the library is touched."""
-        err = self._innovations_refusal()
-        if err is not None:
-            raise NotImplementedError(str(err).replace('innovation scores cover', 'the iterated pass covers'))
-        if isinstance(iterations, bool) or int(iterations) != iterations or not 1 <= int(iterations) <= _lib.ITERATED_MAX:
-            raise ValueError('iterations must be an integer in 1 .. {} (got {!r})'.format(_lib.ITERATED_MAX, iterations))
-        return int(iterations)
+        self._additive_gauss_only('the iterated pass covers')
+        return _iteration_count(iterations)
 
     def iterated_kernel_name(self, iterations, batch=0, launch_loop=False):
         """Which kernel(s) `iterated_pass*` run for this filter: k_iplf_loop<..> (the whole pass in one launch) where the fused time
         loop has an instantiation, and for user models; else the launch loop apply dyn | J x (apply obs | k_iplf_update)."""
         iterations = self._iterated_refusal(iterations)
         self._check_user_points()
-        f_dyn, e_dyn = resolve_integrand(self.mod_dyn.dyn_eval)
-        f_obs, e_obs = resolve_integrand(self.mod_obs.meas_eval)
-        buf = ctypes.create_string_buffer(512)
-        _lib.check(_lib.load().ssmq_iterated_kernel_name(ctypes.c_void_p(self.tf_dyn._handle_for(e_dyn)), ctypes.byref(f_dyn),
-                                                         ctypes.c_void_p(self.tf_obs._handle_for(e_obs)), ctypes.byref(f_obs),
-                                                         int(batch), iterations, _lib.ITERATED_LAUNCH_LOOP if launch_loop else 0, buf, 512),
-                   'ssmq_iterated_kernel_name')
-        return buf.value.decode()
+        return self._kernel_name('ssmq_iterated_kernel_name', int(batch), iterations, _lib.ITERATED_LAUNCH_LOOP if launch_loop else 0)
 
     def _launch_iterated(self, lib, B, ld, T, iterations, flags, d_y, d_m0, d_P0, d_fm, d_fP, d_delta, d_st):
-        f_dyn, e_dyn = resolve_integrand(self.mod_dyn.dyn_eval)
-        f_obs, e_obs = resolve_integrand(self.mod_obs.meas_eval)
-        h_dyn, h_obs = self.tf_dyn._handle_for(e_dyn), self.tf_obs._handle_for(e_obs)
-        gqg, pg = _lib.as_c(self.G.dot(self.q_cov).dot(self.G.T))
-        rr, pr = _lib.as_c(self.r_cov)
-        vp = lambda b: ctypes.c_void_p(b.ptr if b is not None else None)       # noqa: E731
-        _lib.check(lib.ssmq_filter_iterated_dev(ctypes.c_void_p(h_dyn), ctypes.byref(f_dyn), ctypes.c_void_p(h_obs), ctypes.byref(f_obs),
-                                                B, ld, T, iterations, flags, vp(d_y), vp(d_m0), vp(d_P0), pg, pr, vp(d_fm), vp(d_fP),
-                                                vp(d_delta), vp(d_st)), 'ssmq_filter_iterated_dev')
+        gqg, rr = self._noise()
+        vp, dp = _lib.vp, _lib.dp
+        _lib.check(lib.ssmq_filter_iterated_dev(*self._pair(), B, ld, T, iterations, flags, vp(d_y), vp(d_m0), vp(d_P0), dp(gqg), dp(rr),
+                                                vp(d_fm), vp(d_fP), vp(d_delta), vp(d_st)), 'ssmq_filter_iterated_dev')
 
     def iterated_pass_dev(self, d_y, B, ld, T, iterations, launch_loop=False):
         """`forward_pass_dev` with `iterations` re-linearised measurement updates per step: measurements on the device (planes
@@ -441,15 +418,14 @@ class GaussianInference:
         self._check_user_points()
         lib = _lib.load()
         D = self.mod_dyn.dim_state
-        d_m0, d_P0 = self._initial_planes(B, ld)
-        d_fm, d_fP = _lib.DeviceBuffer(8 * T * D * ld), _lib.DeviceBuffer(8 * T * D * D * ld)
-        d_delta, d_st = _lib.DeviceBuffer(8 * T * ld), _lib.DeviceBuffer(4 * ld)
-        self._launch_iterated(lib, B, ld, T, iterations, _lib.ITERATED_LAUNCH_LOOP if launch_loop else 0, d_y, d_m0, d_P0, d_fm, d_fP,
-                              d_delta, d_st)
-        _lib.sync()
-        d_m0.free()
-        d_P0.free()
-        return d_fm, d_fP, d_delta, d_st
+        with _lib.Staging() as stage:
+            d_m0, d_P0 = self._initial_planes(stage, B, ld)
+            d_fm, d_fP = stage.device(8 * T * D * ld), stage.device(8 * T * D * D * ld)
+            d_delta, d_st = stage.device(8 * T * ld), stage.device(4 * ld)
+            self._launch_iterated(lib, B, ld, T, iterations, _lib.ITERATED_LAUNCH_LOOP if launch_loop else 0, d_y, d_m0, d_P0, d_fm,
+                                  d_fP, d_delta, d_st)
+            _lib.sync()
+            return stage.release(d_fm, d_fP, d_delta, d_st)
 
     def iterated_pass_batch(self, data, iterations, x0_mean=None, x0_cov=None, raise_on_failure=True, return_delta=False,
                             launch_loop=False):
@@ -467,23 +443,21 @@ class GaussianInference:
         data = np.asarray(data, dtype=np.float64)
         Y, T, B = data.shape
         D = self.mod_dyn.dim_state
-        ld = (B + 63) // 64 * 64
-        d_y = _lib.scratch(8 * T * Y * ld)
-        _lib.upload_study(data, Y, ld, d_y)
-        d_m0, d_P0 = self._initial_planes(B, ld, x0_mean, x0_cov)
-        d_fm, d_fP = _lib.scratch(8 * T * D * ld), _lib.scratch(8 * T * D * D * ld)
-        d_delta, d_st = _lib.scratch(8 * T * ld), _lib.scratch(4 * ld)
-        self._launch_iterated(lib, B, ld, T, iterations, _lib.ITERATED_LAUNCH_LOOP if launch_loop else 0, d_y, d_m0, d_P0, d_fm, d_fP,
-                              d_delta, d_st)
-        fm = _lib.download_study(d_fm, (D,), T, B, ld)
-        fP = _lib.download_study(d_fP, (D, D), T, B, ld)
-        delta = _lib.download_study(d_delta, (), T, B, ld)
-        self.status = d_st.download((ld,), dtype=np.int32)[:B]
-        for buf in (d_y, d_m0, d_P0, d_fm, d_fP, d_delta, d_st):
-            buf.free()
-        if raise_on_failure and self.status.any():
-            b = int(np.flatnonzero(self.status)[0])
-            raise np.linalg.LinAlgError('Matrix is not positive definite (trajectory {}, step {})'.format(b, int(self.status[b]) - 1))
+        ld = _lib.padded(B)
+        with _lib.Staging() as stage:
+            d_y = stage.scratch(8 * T * Y * ld)
+            _lib.upload_study(data, Y, ld, d_y)
+            d_m0, d_P0 = self._initial_planes(stage, B, ld, x0_mean, x0_cov)
+            d_fm, d_fP = stage.scratch(8 * T * D * ld), stage.scratch(8 * T * D * D * ld)
+            d_delta, d_st = stage.scratch(8 * T * ld), stage.scratch(4 * ld)
+            self._launch_iterated(lib, B, ld, T, iterations, _lib.ITERATED_LAUNCH_LOOP if launch_loop else 0, d_y, d_m0, d_P0, d_fm,
+                                  d_fP, d_delta, d_st)
+            fm = _lib.download_study(d_fm, (D,), T, B, ld)
+            fP = _lib.download_study(d_fP, (D, D), T, B, ld)
+            delta = _lib.download_study(d_delta, (), T, B, ld)
+            self.status = d_st.download((ld,), dtype=np.int32)[:B]
+        if raise_on_failure:
+            _raise_failed(self.status)
         self.fi_mean, self.fi_cov = fm, fP
         return (fm, fP, delta) if return_delta else (fm, fP)
 
@@ -499,9 +473,7 @@ class GaussianInference:
 
     def _ipls_refusal(self, iterations):
         """Raises what keeps a filter or an iteration count out of the iterated smoother - before the library is touched."""
-        err = self._innovations_refusal()
-        if err is not None:
-            raise NotImplementedError(str(err).replace('innovation scores cover', 'the iterated smoother covers'))
+        self._additive_gauss_only('the iterated smoother covers')
         from .mtran import TruncatedSigmaPointTransform
         from .bq.bqmtran import _MultiOutputTransform
         for tf in (self.tf_dyn, self.tf_obs):
@@ -510,40 +482,27 @@ class GaussianInference:
                               (_MultiOutputTransform, 'multi-output'), (GaussHermiteTransform, 'Gauss-Hermite')):
                 if isinstance(tf, cls):
                     raise NotImplementedError('{}; not implemented for {} transforms'.format(self._IPLS_RANGE, what))
-        if isinstance(iterations, bool) or int(iterations) != iterations or not 1 <= int(iterations) <= _lib.ITERATED_MAX:
-            raise ValueError('iterations must be an integer in 1 .. {} (got {!r})'.format(_lib.ITERATED_MAX, iterations))
-        return int(iterations)
-
-    def _ipls_handles(self):
-        f_dyn, e_dyn = resolve_integrand(self.mod_dyn.dyn_eval)
-        f_obs, e_obs = resolve_integrand(self.mod_obs.meas_eval)
-        return self.tf_dyn._handle_for(e_dyn), f_dyn, self.tf_obs._handle_for(e_obs), f_obs
-
-    @staticmethod
-    def _ipls_check(rc, what):
-        if rc == -3:             # SSMQ_E_UNSUPPORTED: the pair has no kernel (another point count, ...)
-            raise NotImplementedError(_lib.last_error())
-        _lib.check(rc, what)
+        return _iteration_count(iterations)
 
     def iterated_smoother_kernel_name(self, iterations):
         """Which kernel `iterated_smoother*` launches once per iteration for this filter: k_ipls_pass<..>."""
         iterations = self._ipls_refusal(iterations)
         self._check_user_points()
-        h_dyn, f_dyn, h_obs, f_obs = self._ipls_handles()
-        buf = ctypes.create_string_buffer(512)
-        self._ipls_check(_lib.load().ssmq_smoother_iterated_kernel_name(ctypes.c_void_p(h_dyn), ctypes.byref(f_dyn), ctypes.c_void_p(h_obs),
-                                                                       ctypes.byref(f_obs), iterations, buf, 512),
-                         'ssmq_smoother_iterated_kernel_name')
-        return buf.value.decode()
+        return self._kernel_name('ssmq_smoother_iterated_kernel_name', iterations, unsupported=True)
 
     def _launch_ipls(self, lib, B, ld, T, iterations, d_y, d_m0, d_P0, d_lin_m, d_lin_P, outs):
-        h_dyn, f_dyn, h_obs, f_obs = self._ipls_handles()
-        gqg, pg = _lib.as_c(self.G.dot(self.q_cov).dot(self.G.T))
-        rr, pr = _lib.as_c(self.r_cov)
-        vp = lambda b: ctypes.c_void_p(b.ptr if b is not None else None)       # noqa: E731
-        self._ipls_check(lib.ssmq_smoother_iterated_dev(ctypes.c_void_p(h_dyn), ctypes.byref(f_dyn), ctypes.c_void_p(h_obs), ctypes.byref(f_obs),
-                                                        B, ld, T, vp(d_y), vp(d_m0), vp(d_P0), pg, pr, iterations, 0, vp(d_lin_m),
-                                                        vp(d_lin_P), *[vp(b) for b in outs]), 'ssmq_smoother_iterated_dev')
+        gqg, rr = self._noise()
+        vp, dp = _lib.vp, _lib.dp
+        # unsupported: the pair has no kernel (another point count, ...)
+        _lib.check(lib.ssmq_smoother_iterated_dev(*self._pair(), B, ld, T, vp(d_y), vp(d_m0), vp(d_P0), dp(gqg), dp(rr), iterations, 0,
+                                                  vp(d_lin_m), vp(d_lin_P), *[vp(b) for b in outs]), 'ssmq_smoother_iterated_dev',
+                   unsupported=True)
+
+    @staticmethod
+    def _ipls_outputs(alloc, D, T, ld):
+        """The eight outputs of `ssmq_smoother_iterated_dev`: d_fm, d_fP, d_sm, d_sP, d_sm0, d_sP0, d_delta, d_status."""
+        return [alloc(n) for n in (8 * T * D * ld, 8 * T * D * D * ld, 8 * T * D * ld, 8 * T * D * D * ld, 8 * D * ld, 8 * D * D * ld,
+                                   8 * ld, 4 * ld)]
 
     def iterated_smoother_dev(self, d_y, B, ld, T, iterations):
         """The iterated smoother on measurements that are already on the device (planes [T][dim_y][ld]), results left there:
@@ -552,14 +511,11 @@ class GaussianInference:
         iterations = self._ipls_refusal(iterations)
         self._check_user_points()
         lib = _lib.load()
-        D = self.mod_dyn.dim_state
-        d_m0, d_P0 = self._initial_planes(B, ld)
-        outs = [_lib.DeviceBuffer(n) for n in (8 * T * D * ld, 8 * T * D * D * ld, 8 * T * D * ld, 8 * T * D * D * ld, 8 * D * ld,
-                                               8 * D * D * ld, 8 * ld, 4 * ld)]
-        self._launch_ipls(lib, B, ld, T, iterations, d_y, d_m0, d_P0, None, None, outs)
-        d_m0.free()
-        d_P0.free()
-        return tuple(outs)
+        with _lib.Staging() as stage:
+            d_m0, d_P0 = self._initial_planes(stage, B, ld)
+            outs = self._ipls_outputs(stage.device, self.mod_dyn.dim_state, T, ld)
+            self._launch_ipls(lib, B, ld, T, iterations, d_y, d_m0, d_P0, None, None, outs)
+            return stage.release(*outs)
 
     def iterated_smoother_batch(self, data, iterations=3, x0_mean=None, x0_cov=None, raise_on_failure=True, return_delta=False,
                                 lin_mean=None, lin_cov=None):
@@ -582,21 +538,20 @@ class GaussianInference:
         data = np.asarray(data, dtype=np.float64)
         Y, T, B = data.shape
         D = self.mod_dyn.dim_state
-        ld = (B + 63) // 64 * 64
-        d_y = _lib.scratch(8 * T * Y * ld)
-        _lib.upload_study(data, Y, ld, d_y)
-        d_m0, d_P0 = self._initial_planes(B, ld, x0_mean, x0_cov)
-        d_lm = d_lP = None
-        if lin_mean is not None:
-            lin_mean, lin_cov = np.asarray(lin_mean, dtype=np.float64), np.asarray(lin_cov, dtype=np.float64)
-            if lin_mean.shape != (D, T + 1, B) or lin_cov.shape != (D, D, T + 1, B):
-                raise ValueError('lin_mean (D, T + 1, B) and lin_cov (D, D, T + 1, B) expected')
-            d_lm, d_lP = _lib.scratch(8 * (T + 1) * D * ld), _lib.scratch(8 * (T + 1) * D * D * ld)
-            _lib.upload_study(lin_mean, D, ld, d_lm)
-            _lib.upload_study(lin_cov.reshape(D * D, T + 1, B), D * D, ld, d_lP)
-        outs = [_lib.scratch(n) for n in (8 * T * D * ld, 8 * T * D * D * ld, 8 * T * D * ld, 8 * T * D * D * ld, 8 * D * ld, 8 * D * D * ld,
-                                          8 * ld, 4 * ld)]
-        try:
+        ld = _lib.padded(B)
+        with _lib.Staging() as stage:
+            d_y = stage.scratch(8 * T * Y * ld)
+            _lib.upload_study(data, Y, ld, d_y)
+            d_m0, d_P0 = self._initial_planes(stage, B, ld, x0_mean, x0_cov)
+            d_lm = d_lP = None
+            if lin_mean is not None:
+                lin_mean, lin_cov = np.asarray(lin_mean, dtype=np.float64), np.asarray(lin_cov, dtype=np.float64)
+                if lin_mean.shape != (D, T + 1, B) or lin_cov.shape != (D, D, T + 1, B):
+                    raise ValueError('lin_mean (D, T + 1, B) and lin_cov (D, D, T + 1, B) expected')
+                d_lm, d_lP = stage.scratch(8 * (T + 1) * D * ld), stage.scratch(8 * (T + 1) * D * D * ld)
+                _lib.upload_study(lin_mean, D, ld, d_lm)
+                _lib.upload_study(lin_cov.reshape(D * D, T + 1, B), D * D, ld, d_lP)
+            outs = self._ipls_outputs(stage.scratch, D, T, ld)
             self._launch_ipls(lib, B, ld, T, iterations, d_y, d_m0, d_P0, d_lm, d_lP, outs)
             fm, fP = _lib.download_study(outs[0], (D,), T, B, ld), _lib.download_study(outs[1], (D, D), T, B, ld)
             sm, sP = _lib.download_study(outs[2], (D,), T, B, ld), _lib.download_study(outs[3], (D, D), T, B, ld)
@@ -604,12 +559,8 @@ class GaussianInference:
             sP0 = outs[5].download((D, D, ld))[..., :B].copy()
             delta = outs[6].download((ld,))[:B].copy()
             self.status = outs[7].download((ld,), dtype=np.int32)[:B].copy()
-        finally:
-            for buf in [d_y, d_m0, d_P0] + outs + [b for b in (d_lm, d_lP) if b is not None]:
-                buf.free()
-        if raise_on_failure and self.status.any():
-            b = int(np.flatnonzero(self.status)[0])
-            raise np.linalg.LinAlgError('Matrix is not positive definite (trajectory {}, step {})'.format(b, int(self.status[b]) - 1))
+        if raise_on_failure:
+            _raise_failed(self.status)
         self.fi_mean, self.fi_cov, self.sm_mean, self.sm_cov = fm, fP, sm, sP
         self.sm_x0_mean, self.sm_x0_cov = sm0, sP0
         return (sm, sP, delta) if return_delta else (sm, sP)
@@ -630,7 +581,7 @@ def run_filters(algs, data, x0_mean=None, x0_cov=None, raise_on_failure=True):
     lib = _lib.load()
     data = np.asarray(data, dtype=np.float64)
     Y, T, B = data.shape
-    ld = (B + 63) // 64 * 64
+    ld = _lib.padded(B)
     for a in algs:
         if isinstance(a, BootstrapParticleFilter):
             a._refuse('run_filters')
@@ -649,59 +600,41 @@ def run_filters(algs, data, x0_mean=None, x0_cov=None, raise_on_failure=True):
                                       'ssmq_filter_forward_multi_dev refuses by name)')
         if a.mod_obs.dim_out != Y:
             raise ValueError('run_filters: every filter must take the same measurements')
-    d_y = _lib.scratch(8 * T * Y * ld)
-    _lib.upload_study(data, Y, ld, d_y)
-    jobs = (_lib.FilterJob * len(algs))()
-    keep, bufs = [], []
-    for i, a in enumerate(algs):
-        a._data = data
-        D = a.mod_dyn.dim_state
-        m0 = np.broadcast_to(a.x0_mean, (B, D)) if x0_mean is None else np.asarray(x0_mean, dtype=np.float64)
-        P0 = np.broadcast_to(a._initial_cov(), (B, D, D)) if x0_cov is None else np.asarray(x0_cov, dtype=np.float64)
-        mbuf = np.zeros((D, ld))
-        mbuf[:, :B] = m0.T
-        Pbuf = np.zeros((D * D, ld))
-        Pbuf[:, :B] = P0.reshape(B, D * D).T
-        if ld > B:
-            Pbuf[:, B:] = np.eye(D).reshape(-1, 1)
-        d_m0, d_P0 = _lib.scratch(mbuf.nbytes), _lib.scratch(Pbuf.nbytes)
-        d_m0.upload(mbuf)
-        d_P0.upload(Pbuf)
-        d_fm, d_fP, d_st = _lib.scratch(8 * T * D * ld), _lib.scratch(8 * T * D * D * ld), _lib.scratch(4 * ld)
-        bufs.append((d_m0, d_P0, d_fm, d_fP, d_st))
-        f_dyn, e_dyn = resolve_integrand(a.mod_dyn.dyn_eval)
-        f_obs, e_obs = resolve_integrand(a.mod_obs.meas_eval)
-        student = isinstance(a, StudentianInference)
-        gqg, pg = _lib.as_c(a.G.dot(a.q_smat if student else a.q_cov).dot(a.G.T))
-        rr, pr = _lib.as_c(a.r_smat if student else a.r_cov)
-        keep += [f_dyn, f_obs, gqg, rr]
-        j = jobs[i]
-        j.h_dyn, j.f_dyn = a.tf_dyn._handle_for(e_dyn), ctypes.pointer(f_dyn)
-        j.h_obs, j.f_obs = a.tf_obs._handle_for(e_obs), ctypes.pointer(f_obs)
-        j.B, j.ld, j.T = B, ld, T
-        j.d_y, j.d_m0, j.d_P0 = d_y.ptr, d_m0.ptr, d_P0.ptr
-        j.GQG, j.R = pg, pr
-        j.d_fm, j.d_fP, j.d_status = d_fm.ptr, d_fP.ptr, d_st.ptr
-        if student:
-            sc, ps = _lib.as_c(a.scale_sequence(T))
-            keep.append(sc)
-            j.scale, j.dof = ps, float(a.dof)
-    _lib.check(lib.ssmq_filter_forward_multi_dev(len(algs), jobs), 'ssmq_filter_forward_multi_dev')
-    out, failed = [], None
-    for a, (d_m0, d_P0, d_fm, d_fP, d_st) in zip(algs, bufs):
-        D = a.mod_dyn.dim_state
-        a.fi_mean = _lib.download_study(d_fm, (D,), T, B, ld)
-        a.fi_cov = _lib.download_study(d_fP, (D, D), T, B, ld)
-        a.status = d_st.download((ld,), dtype=np.int32)[:B]
-        for buf in (d_m0, d_P0, d_fm, d_fP, d_st):
-            buf.free()
-        if a.status.any() and failed is None:
-            b = int(np.flatnonzero(a.status)[0])
-            failed = '{}: Matrix is not positive definite (trajectory {}, step {})'.format(type(a).__name__, b, int(a.status[b]) - 1)
-        out.append((a.fi_mean, a.fi_cov))
-    d_y.free()
-    if raise_on_failure and failed:
-        raise np.linalg.LinAlgError(failed)
+    with _lib.Staging() as stage:
+        d_y = stage.scratch(8 * T * Y * ld)
+        _lib.upload_study(data, Y, ld, d_y)
+        jobs = (_lib.FilterJob * len(algs))()
+        keep, bufs = [], []
+        for j, a in zip(jobs, algs):
+            a._data = data
+            D = a.mod_dyn.dim_state
+            d_m0, d_P0 = a._initial_planes(stage, B, ld, x0_mean, x0_cov)
+            d_fm, d_fP, d_st = stage.scratch(8 * T * D * ld), stage.scratch(8 * T * D * D * ld), stage.scratch(4 * ld)
+            bufs.append((d_fm, d_fP, d_st))
+            h_dyn, f_dyn, h_obs, f_obs = a._pair()
+            gqg, rr = a._noise()
+            keep += [f_dyn, f_obs, gqg, rr]
+            j.h_dyn, j.f_dyn, j.h_obs, j.f_obs = h_dyn, ctypes.pointer(f_dyn), h_obs, ctypes.pointer(f_obs)
+            j.B, j.ld, j.T = B, ld, T
+            j.d_y, j.d_m0, j.d_P0 = d_y.ptr, d_m0.ptr, d_P0.ptr
+            j.GQG, j.R = _lib.dp(gqg), _lib.dp(rr)
+            j.d_fm, j.d_fP, j.d_status = d_fm.ptr, d_fP.ptr, d_st.ptr
+            if a._recursion == 'student':
+                sc = np.ascontiguousarray(a.scale_sequence(T), dtype=np.float64)
+                keep.append(sc)
+                j.scale, j.dof = _lib.dp(sc), float(a.dof)
+        _lib.check(lib.ssmq_filter_forward_multi_dev(len(algs), jobs), 'ssmq_filter_forward_multi_dev')
+        out, failed = [], None
+        for a, (d_fm, d_fP, d_st) in zip(algs, bufs):
+            D = a.mod_dyn.dim_state
+            a.fi_mean = _lib.download_study(d_fm, (D,), T, B, ld)
+            a.fi_cov = _lib.download_study(d_fP, (D, D), T, B, ld)
+            a.status = d_st.download((ld,), dtype=np.int32)[:B]
+            if a.status.any() and failed is None:
+                failed = a
+            out.append((a.fi_mean, a.fi_cov))
+    if raise_on_failure and failed is not None:
+        _raise_failed(failed.status, prefix=type(failed).__name__ + ': ')
     return out
 
 
@@ -935,15 +868,20 @@ class StudentianInference(GaussianInference):
             dof_fi += self.mod_obs.dim_out
         return out
 
-    def _launch(self, lib, h_dyn, f_dyn, h_obs, f_obs, B, ld, T, d_y, d_m0, d_P0, d_fm, d_fP, d_st):
-        gqg, pg = _lib.as_c(self.G.dot(self.q_smat).dot(self.G.T))
-        rr, pr = _lib.as_c(self.r_smat)
-        sc, ps = _lib.as_c(self.scale_sequence(T))
-        _lib.check(lib.ssmq_student_filter_forward_dev(
-            ctypes.c_void_p(h_dyn), ctypes.byref(f_dyn), ctypes.c_void_p(h_obs), ctypes.byref(f_obs), B, ld, T,
-            ctypes.c_void_p(d_y.ptr), ctypes.c_void_p(d_m0.ptr), ctypes.c_void_p(d_P0.ptr), pg, pr, ps,
-            ctypes.c_double(self.dof), ctypes.c_void_p(d_fm.ptr), ctypes.c_void_p(d_fP.ptr),
-            ctypes.c_void_p(d_st.ptr)), 'ssmq_student_filter_forward_dev')
+    _recursion = 'student'
+
+    def _noise(self):
+        """The scale matrices that stand where the Gaussian recursion has G Q G' and R."""
+        return (np.ascontiguousarray(self.G.dot(self.q_smat).dot(self.G.T), dtype=np.float64),
+                np.ascontiguousarray(self.r_smat, dtype=np.float64))
+
+    def _launch(self, lib, B, ld, T, d_y, d_m0, d_P0, d_fm, d_fP, d_st):
+        gqg, rr = self._noise()
+        sc = np.ascontiguousarray(self.scale_sequence(T), dtype=np.float64)
+        vp, dp = _lib.vp, _lib.dp
+        _lib.check(lib.ssmq_student_filter_forward_dev(*self._pair(), B, ld, T, vp(d_y), vp(d_m0), vp(d_P0), dp(gqg), dp(rr), dp(sc),
+                                                       ctypes.c_double(self.dof), vp(d_fm), vp(d_fP), vp(d_st)),
+                   'ssmq_student_filter_forward_dev')
 
 
 class FullySymmetricStudent(StudentianInference):
@@ -1433,8 +1371,8 @@ class BootstrapParticleFilter:
         self.d_loglik = self.d_ess = None
         self._data = None
 
-    def _initial_planes(self, B, ld, x0_mean=None, x0_cov=None):
-        return initial_planes(self.mod_dyn.dim_state, self.x0_mean, self.x0_cov, B, ld, x0_mean, x0_cov)
+    def _initial_planes(self, stage, B, ld, x0_mean=None, x0_cov=None):
+        return initial_planes(stage, self.mod_dyn.dim_state, self.x0_mean, self.x0_cov, B, ld, x0_mean, x0_cov)
 
     def _c_args(self):
         """The model part of the C call (and the arrays it points to, to be kept alive)."""
@@ -1452,11 +1390,9 @@ class BootstrapParticleFilter:
         buf = ctypes.create_string_buffer(256)
         rc = _lib.load().ssmq_particle_kernel_name(ctypes.byref(f_dyn), ctypes.byref(f_obs), self.mod_dyn.dim_state, self.mod_obs.dim_out,
                                                    qm.size, self.num_particles, ctypes.byref(r), buf, 256)
-        if rc == -3:             # SSMQ_E_UNSUPPORTED
-            raise NotImplementedError(_lib.last_error())
         if rc == -1:             # SSMQ_E_ARG
             raise ValueError(_lib.last_error())
-        _lib.check(rc, 'ssmq_particle_kernel_name')
+        _lib.check(rc, 'ssmq_particle_kernel_name', unsupported=True)
         return buf.value.decode()
 
     def kernel_name(self):
@@ -1467,15 +1403,12 @@ class BootstrapParticleFilter:
         if T < 1:
             raise ValueError('BootstrapParticleFilter: at least one time step is needed (T = {})'.format(T))
         f_dyn, f_obs, r, qm, qL, keep = self._c_args()
-        vp = lambda b: ctypes.c_void_p(b.ptr if b is not None else None)       # noqa: E731
-        dp = lambda a: a.ctypes.data_as(_lib.c_double_p)                       # noqa: E731
-        rc = lib.ssmq_particle_filter_dev(ctypes.byref(f_dyn), ctypes.byref(f_obs), self.mod_dyn.dim_state, self.mod_obs.dim_out, qm.size,
-                                          self.num_particles, B, ld, T, vp(d_y), vp(d_m0), vp(d_P0), dp(qm), dp(qL), dp(self.G),
-                                          ctypes.byref(r), self.ess_threshold, ctypes.c_uint64(self.seed), ctypes.c_uint64(int(traj_offset)),
-                                          vp(d_fm), vp(d_fP), vp(d_ll), vp(d_ess), vp(d_st), vp(d_part), vp(d_logw), vp(d_anc))
-        if rc == -3:
-            raise NotImplementedError(_lib.last_error())
-        _lib.check(rc, 'ssmq_particle_filter_dev')
+        vp, dp = _lib.vp, _lib.dp
+        _lib.check(lib.ssmq_particle_filter_dev(ctypes.byref(f_dyn), ctypes.byref(f_obs), self.mod_dyn.dim_state, self.mod_obs.dim_out,
+                                                qm.size, self.num_particles, B, ld, T, vp(d_y), vp(d_m0), vp(d_P0), dp(qm), dp(qL),
+                                                dp(self.G), ctypes.byref(r), self.ess_threshold, ctypes.c_uint64(self.seed),
+                                                ctypes.c_uint64(int(traj_offset)), vp(d_fm), vp(d_fP), vp(d_ll), vp(d_ess), vp(d_st),
+                                                vp(d_part), vp(d_logw), vp(d_anc)), 'ssmq_particle_filter_dev', unsupported=True)
 
     def forward_pass_dev(self, d_y, B, ld, T, traj_offset=0):
         """Filter measurements that are already on the device (planes [T][dim_y][ld], e.g. from `ssmod.simulate_dev`) and leave the
@@ -1487,28 +1420,21 @@ class BootstrapParticleFilter:
         lib = _lib.load()
         D = self.mod_dyn.dim_state
         self.free_dev()
-        d_m0, d_P0 = self._initial_planes(B, ld)
-        out = [_lib.DeviceBuffer(8 * T * D * ld), _lib.DeviceBuffer(8 * T * D * D * ld), _lib.DeviceBuffer(4 * ld),
-               _lib.DeviceBuffer(8 * (T + 1) * ld), _lib.DeviceBuffer(8 * T * ld)]
-        d_fm, d_fP, d_st, d_ll, d_ess = out
-        try:
+        with _lib.Staging() as stage:
+            d_m0, d_P0 = self._initial_planes(stage, B, ld)
+            d_fm, d_fP, d_st = stage.device(8 * T * D * ld), stage.device(8 * T * D * D * ld), stage.device(4 * ld)
+            d_ll, d_ess = stage.device(8 * (T + 1) * ld), stage.device(8 * T * ld)
             d_st.zero()
             self._launch(lib, B, ld, T, traj_offset, d_y, d_m0, d_P0, d_fm, d_fP, d_ll, d_ess, d_st)
-        except BaseException:
-            for buf in out:
-                buf.free()
-            raise
-        finally:
-            d_m0.free()
-            d_P0.free()
+            stage.release(d_fm, d_fP, d_st, d_ll, d_ess)
         self.d_loglik, self.d_ess = d_ll, d_ess
         return d_fm, d_fP, d_st
 
     def free_dev(self):
         """Frees the device planes the last forward_pass_dev left with the filter (`d_loglik`, `d_ess`)."""
-        for buf in (self.d_loglik, self.d_ess):
-            if buf is not None:
-                buf.free()
+        if self.d_loglik is not None:        # (the two are set together)
+            self.d_loglik.free()
+            self.d_ess.free()
         self.d_loglik = self.d_ess = None
 
     def forward_pass_batch(self, data, x0_mean=None, x0_cov=None, raise_on_failure=True, return_particles=False):
@@ -1527,17 +1453,16 @@ class BootstrapParticleFilter:
             raise ValueError('BootstrapParticleFilter: at least one time step is needed (T = {})'.format(T))
         self._data = data
         D, N = self.mod_dyn.dim_state, self.num_particles
-        ld = (B + 63) // 64 * 64
-        d_y = _lib.scratch(8 * T * Y * ld)
-        _lib.upload_study(data, Y, ld, d_y)
-        d_m0, d_P0 = self._initial_planes(B, ld, x0_mean, x0_cov)
-        d_fm, d_fP, d_st = _lib.scratch(8 * T * D * ld), _lib.scratch(8 * T * D * D * ld), _lib.scratch(4 * ld)
-        d_ll, d_ess = _lib.scratch(8 * (T + 1) * ld), _lib.scratch(8 * T * ld)
-        d_part = d_logw = d_anc = None
-        if return_particles:
-            d_part, d_logw, d_anc = _lib.scratch(8 * T * D * B * N), _lib.scratch(8 * T * B * N), _lib.scratch(4 * T * B * N)
-        bufs = (d_y, d_m0, d_P0, d_fm, d_fP, d_st, d_ll, d_ess, d_part, d_logw, d_anc)
-        try:
+        ld = _lib.padded(B)
+        with _lib.Staging() as stage:
+            d_y = stage.scratch(8 * T * Y * ld)
+            _lib.upload_study(data, Y, ld, d_y)
+            d_m0, d_P0 = self._initial_planes(stage, B, ld, x0_mean, x0_cov)
+            d_fm, d_fP, d_st = stage.scratch(8 * T * D * ld), stage.scratch(8 * T * D * D * ld), stage.scratch(4 * ld)
+            d_ll, d_ess = stage.scratch(8 * (T + 1) * ld), stage.scratch(8 * T * ld)
+            d_part = d_logw = d_anc = None
+            if return_particles:
+                d_part, d_logw, d_anc = stage.scratch(8 * T * D * B * N), stage.scratch(8 * T * B * N), stage.scratch(4 * T * B * N)
             d_st.zero()
             self._launch(lib, B, ld, T, 0, d_y, d_m0, d_P0, d_fm, d_fP, d_ll, d_ess, d_st, d_part, d_logw, d_anc)
             fm = _lib.download_study(d_fm, (D,), T, B, ld)
@@ -1552,15 +1477,9 @@ class BootstrapParticleFilter:
                 self.ancestors = np.ascontiguousarray(d_anc.download((T, B, N), dtype=np.int32).transpose(2, 0, 1))
             else:
                 self.particles = self.log_weights = self.ancestors = None
-        finally:
-            for buf in bufs:
-                if buf is not None:
-                    buf.free()
         self.fi_mean, self.fi_cov = fm, fP
-        if raise_on_failure and self.status.any():
-            b = int(np.flatnonzero(self.status)[0])
-            raise np.linalg.LinAlgError('Particle filter degenerate: no finite log-weight (trajectory {}, step {})'.format(
-                b, int(self.status[b]) - 1))
+        if raise_on_failure:
+            _raise_failed(self.status, message='Particle filter degenerate: no finite log-weight (trajectory {}, step {})')
         return self.fi_mean, self.fi_cov
 
     def forward_pass(self, data):
@@ -1571,44 +1490,17 @@ class BootstrapParticleFilter:
     def _refuse(self, what):
         raise NotImplementedError('{}; {} is not implemented for it'.format(self.RANGE, what))
 
-    def backward_pass(self):
-        self._refuse('the RTS smoother (backward_pass)')
 
-    def backward_pass_batch(self):
-        self._refuse('the RTS smoother (backward_pass_batch)')
+def _refusing(name, what):
+    def method(self, *args, **kwargs):
+        self._refuse(what)
+    method.__name__ = name
+    return method
 
-    def innovations(self, *args, **kwargs):
-        self._refuse('innovations')
 
-    def innovations_batch(self, *args, **kwargs):
-        self._refuse('innovations_batch')
-
-    def innovations_dev(self, *args, **kwargs):
-        self._refuse('innovations_dev')
-
-    def innovations_kernel_name(self, *args, **kwargs):
-        self._refuse('innovations_kernel_name')
-
-    def iterated_pass(self, *args, **kwargs):
-        self._refuse('iterated_pass')
-
-    def iterated_pass_batch(self, *args, **kwargs):
-        self._refuse('iterated_pass_batch')
-
-    def iterated_pass_dev(self, *args, **kwargs):
-        self._refuse('iterated_pass_dev')
-
-    def iterated_kernel_name(self, *args, **kwargs):
-        self._refuse('iterated_kernel_name')
-
-    def iterated_smoother(self, *args, **kwargs):
-        self._refuse('iterated_smoother')
-
-    def iterated_smoother_batch(self, *args, **kwargs):
-        self._refuse('iterated_smoother_batch')
-
-    def iterated_smoother_dev(self, *args, **kwargs):
-        self._refuse('iterated_smoother_dev')
-
-    def iterated_smoother_kernel_name(self, *args, **kwargs):
-        self._refuse('iterated_smoother_kernel_name')
+# what a GaussianInference has and the particle filter refuses: (method, its wording in the NotImplementedError)
+for _name, _what in (('backward_pass', 'the RTS smoother (backward_pass)'), ('backward_pass_batch', 'the RTS smoother (backward_pass_batch)')) + \
+        tuple((n, n) for n in ('innovations', 'innovations_batch', 'innovations_dev', 'innovations_kernel_name', 'iterated_pass',
+                               'iterated_pass_batch', 'iterated_pass_dev', 'iterated_kernel_name', 'iterated_smoother',
+                               'iterated_smoother_batch', 'iterated_smoother_dev', 'iterated_smoother_kernel_name')):
+    setattr(BootstrapParticleFilter, _name, _refusing(_name, _what))

@@ -16,7 +16,6 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 from ssmtoybox_amd import _lib, ssinf, ssmod as sm  # noqa: E402
-from ssmtoybox_amd.mtran import resolve_integrand  # noqa: E402
 
 
 def build(shape):
@@ -59,19 +58,17 @@ def main():
         d_x, d_y, ld = sm.simulate_dev(alg.mod_dyn, alg.mod_obs, T, B, seed=1)
         d_fm, d_fP, d_st = alg.forward_pass_dev(d_y, B, ld, T)
         failed = int(np.count_nonzero(d_st.download((ld,), dtype=np.int32)[:B]))
-        d_m0, d_P0 = alg._initial_planes(B, ld)
+        stage = _lib.Staging()
+        d_m0, d_P0 = alg._initial_planes(stage, B, ld)
         d_nis, d_ll = _lib.DeviceBuffer(8 * T * ld), _lib.DeviceBuffer(8 * T * ld)
         d_tot, d_ist = _lib.DeviceBuffer(16 * ld), _lib.DeviceBuffer(4 * ld)
 
         def forward():
-            alg._launch(lib, h_dyn, f_dyn, h_obs, f_obs, B, ld, T, d_y, d_m0, d_P0, d_fm, d_fP, d_st)
+            alg._launch(lib, B, ld, T, d_y, d_m0, d_P0, d_fm, d_fP, d_st)
 
         def scores():
             alg._launch_innovations(lib, B, ld, T, d_y, d_m0, d_P0, d_fm, d_fP, None, None, d_nis, d_ll, d_tot, d_ist)
 
-        f_dyn, e_dyn = resolve_integrand(alg.mod_dyn.dyn_eval)
-        f_obs, e_obs = resolve_integrand(alg.mod_obs.meas_eval)
-        h_dyn, h_obs = alg.tf_dyn._handle_for(e_dyn), alg.tf_obs._handle_for(e_obs)
         rec = {'shape': shape, 'D': D, 'Y': Y, 'B': B, 'T': T, 'calls': a.calls, 'failed_trajectories': failed,
                'filter_kernel': alg.kernel_name(B), 'innovation_kernel': alg.innovations_kernel_name(B)}
         rec['forward_ms_median'], rec['forward_ms_min'] = (round(v, 4) for v in timed(forward, a.calls))
@@ -86,8 +83,9 @@ def main():
         rec['launch_loop_ms_median'], rec['launch_loop_ms_min'] = (round(v, 4) for v in timed(scores, max(a.calls // 4, 5)))
         del os.environ['SSMQ_NO_FUSED']
         print(json.dumps(rec), flush=True)
-        for buf in (d_x, d_y, d_fm, d_fP, d_st, d_m0, d_P0, d_nis, d_ll, d_tot, d_ist):
+        for buf in (d_x, d_y, d_fm, d_fP, d_st, d_nis, d_ll, d_tot, d_ist):
             buf.free()
+        stage.free()
 
 
 if __name__ == '__main__':

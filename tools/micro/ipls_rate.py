@@ -11,7 +11,6 @@ tools/micro/iterated_rate.py; on the device simulator's reentry data the plain f
 7 steps, and a failed trajectory leaves the sweeps early: `failed_trajectories` is part of the record).
 Prints one JSON line per shape.  Run under a time limit (timeout -k 10 300 python tools/micro/ipls_rate.py)."""
 import argparse
-import ctypes
 import json
 import os
 import sys
@@ -20,7 +19,6 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 from ssmtoybox_amd import _lib, ssmod as sm  # noqa: E402
-from ssmtoybox_amd.mtran import resolve_integrand  # noqa: E402
 from tools.micro.iterated_rate import build, timed  # noqa: E402
 
 
@@ -34,21 +32,13 @@ def main():
         alg, B, T = build(shape)
         D, Y = alg.mod_dyn.dim_state, alg.mod_obs.dim_out
         d_x, d_y, ld = sm.simulate_dev(alg.mod_dyn, alg.mod_obs, T, B, seed=1)
-        d_m0, d_P0 = alg._initial_planes(B, ld)
-        sizes = (8 * T * D * ld, 8 * T * D * D * ld, 8 * T * D * ld, 8 * T * D * D * ld, 8 * D * ld, 8 * D * D * ld, 8 * ld, 4 * ld)
-        outs = [_lib.DeviceBuffer(n) for n in sizes]
+        stage = _lib.Staging()
+        d_m0, d_P0 = alg._initial_planes(stage, B, ld)
+        outs = alg._ipls_outputs(_lib.DeviceBuffer, D, T, ld)
         d_tdelta = _lib.DeviceBuffer(8 * T * ld)
-        f_dyn, e_dyn = resolve_integrand(alg.mod_dyn.dyn_eval)
-        f_obs, e_obs = resolve_integrand(alg.mod_obs.meas_eval)
-        h_dyn, h_obs = alg.tf_dyn._handle_for(e_dyn), alg.tf_obs._handle_for(e_obs)
-        gqg, pg = _lib.as_c(alg.G.dot(alg.q_cov).dot(alg.G.T))
-        rr, pr = _lib.as_c(alg.r_cov)
-        vp = lambda b: ctypes.c_void_p(b.ptr)       # noqa: E731
 
         def rts():
-            _lib.check(lib.ssmq_filter_smooth_dev(ctypes.c_void_p(h_dyn), ctypes.byref(f_dyn), ctypes.c_void_p(h_obs), ctypes.byref(f_obs), B, ld, T,
-                                                  vp(d_y), vp(d_m0), vp(d_P0), pg, pr, vp(outs[0]), vp(outs[1]), vp(outs[2]), vp(outs[3]),
-                                                  vp(outs[7])), 'ssmq_filter_smooth_dev')
+            alg._launch_smooth(lib, B, ld, T, d_y, d_m0, d_P0, outs[0], outs[1], outs[2], outs[3], outs[7])
 
         def iplf():
             alg._launch_iterated(lib, B, ld, T, 1, 0, d_y, d_m0, d_P0, outs[0], outs[1], d_tdelta, outs[7])
@@ -65,8 +55,9 @@ def main():
                                     'failed_trajectories': int(B - np.count_nonzero(ok)),
                                     'delta_median': float(np.median(outs[6].download((ld,))[:B][ok]))}
         print(json.dumps(rec), flush=True)
-        for buf in [d_x, d_y, d_m0, d_P0, d_tdelta] + outs:
+        for buf in [d_x, d_y, d_tdelta] + outs:
             buf.free()
+        stage.free()
 
 
 if __name__ == '__main__':

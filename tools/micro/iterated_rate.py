@@ -16,7 +16,6 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 from ssmtoybox_amd import _lib, ssinf, ssmod as sm  # noqa: E402
-from ssmtoybox_amd.mtran import resolve_integrand  # noqa: E402
 
 
 def build(shape):
@@ -57,15 +56,13 @@ def main():
         alg, B, T = build(shape)
         D, Y = alg.mod_dyn.dim_state, alg.mod_obs.dim_out
         d_x, d_y, ld = sm.simulate_dev(alg.mod_dyn, alg.mod_obs, T, B, seed=1)
-        d_m0, d_P0 = alg._initial_planes(B, ld)
+        stage = _lib.Staging()
+        d_m0, d_P0 = alg._initial_planes(stage, B, ld)
         d_fm, d_fP = _lib.DeviceBuffer(8 * T * D * ld), _lib.DeviceBuffer(8 * T * D * D * ld)
         d_delta, d_st = _lib.DeviceBuffer(8 * T * ld), _lib.DeviceBuffer(4 * ld)
-        f_dyn, e_dyn = resolve_integrand(alg.mod_dyn.dyn_eval)
-        f_obs, e_obs = resolve_integrand(alg.mod_obs.meas_eval)
-        h_dyn, h_obs = alg.tf_dyn._handle_for(e_dyn), alg.tf_obs._handle_for(e_obs)
 
         def forward():
-            alg._launch(lib, h_dyn, f_dyn, h_obs, f_obs, B, ld, T, d_y, d_m0, d_P0, d_fm, d_fP, d_st)
+            alg._launch(lib, B, ld, T, d_y, d_m0, d_P0, d_fm, d_fP, d_st)
 
         rec = {'shape': shape, 'D': D, 'Y': Y, 'B': B, 'T': T, 'calls': a.calls, 'filter_kernel': alg.kernel_name(B),
                'iterated_kernel': alg.iterated_kernel_name(1, B)}
@@ -79,8 +76,9 @@ def main():
                                     'failed_trajectories': int(B - np.count_nonzero(ok)),
                                     'delta_last_step_max': float(np.max(d_delta.download((T, ld))[T - 1, :B][ok]))}
         print(json.dumps(rec), flush=True)
-        for buf in (d_x, d_y, d_fm, d_fP, d_st, d_m0, d_P0, d_delta):
+        for buf in (d_x, d_y, d_fm, d_fP, d_st, d_delta):
             buf.free()
+        stage.free()
 
 
 if __name__ == '__main__':

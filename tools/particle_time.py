@@ -22,7 +22,6 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import ssmtoybox_amd as amd  # noqa: E402
 from ssmtoybox_amd import _lib, ssinf, ssmod as sm  # noqa: E402
-from ssmtoybox_amd.mtran import resolve_integrand  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument('--variant', action='append', default=[])
@@ -86,13 +85,11 @@ for shape, models, B, T, counts in (('UNGM', ungm, 10000, 100, (256, 1024)), ('r
     # every buffer of a pass is allocated once, outside the timed blocks: the figures are the launches alone
     outs = [_lib.DeviceBuffer(8 * T * D * ld), _lib.DeviceBuffer(8 * T * D * D * ld), _lib.DeviceBuffer(8 * (T + 1) * ld),
             _lib.DeviceBuffer(8 * T * ld), _lib.DeviceBuffer(4 * ld)]
-    d_m0, d_P0 = ssinf.initial_planes(D, ukf.x0_mean, ukf.x0_cov, B, ld)
-    f_dyn, e_dyn = resolve_integrand(dyn.dyn_eval)
-    f_obs, e_obs = resolve_integrand(obs.meas_eval)
-    h_dyn, h_obs = ukf.tf_dyn._handle_for(e_dyn), ukf.tf_obs._handle_for(e_obs)
+    stage = _lib.Staging()
+    d_m0, d_P0 = ukf._initial_planes(stage, B, ld)
 
     def run_ukf():
-        ukf._launch(lib, h_dyn, f_dyn, h_obs, f_obs, B, ld, T, d_y, d_m0, d_P0, outs[0], outs[1], outs[4])
+        ukf._launch(lib, B, ld, T, d_y, d_m0, d_P0, outs[0], outs[1], outs[4])
     add('ukf', run_ukf, lib)
     for N in counts:
         for thr in (0.5, 0.0, 1.0):
@@ -117,7 +114,8 @@ for shape, models, B, T, counts in (('UNGM', ungm, 10000, 100, (256, 1024)), ('r
         out['ms_' + k + '_min_max'] = [min(r['ms']), max(r['ms'])]
         print('%s %s: %.3f ms per pass (min %.3f, max %.3f)' % (shape, k, out['ms_' + k], min(r['ms']), max(r['ms'])), flush=True)
     results.append(out)
-    for b in outs + [d_m0, d_P0, d_x, d_y]:
+    for b in outs + [d_x, d_y]:
         b.free()
+    stage.free()
 for r in results:
     print(json.dumps(r), flush=True)
