@@ -1090,6 +1090,63 @@ int ssmq_particle_kernel_name(const ssmq_integrand *f_dyn, const ssmq_integrand 
                               char *buf, int len);
 
 /*
+ * Particle smoothers over the cloud ssmq_particle_filter_dev wrote (d_part, d_logw, d_anc of one call, with its d_fm, d_fP, d_ess and
+ * d_status): the ground truth the Gaussian smoothers are measured against, E[x_k | y_0..T-1] and the covariance.  Per trajectory, in the
+ * filter's time convention: x_k^i the particles of step k after propagation, lw_k^i their normalised log-weights after the measurement
+ * of step k (before resampling), a_k(i) the ancestors chosen after step k.
+ *
+ * SSMQ_PS_MARGINAL - the marginal forward-filter backward-smoother (FFBSm; Doucet, Godsill, Andrieu 2000), for process noise of full
+ * rank: dq == D and Sigma = G Q G' positive definite, Ls = chol(Sigma).  With
+ *     alpha_k^i = Ls^-1 (f(x_k^i, k + 1) + G q_mean),   beta_{k+1}^j = Ls^-1 x_{k+1}^j,   d2_ij = |beta_{k+1}^j - alpha_k^i|^2
+ * (the Gaussian normalising constant cancels), entirely in the log domain:
+ *     ls_{T-1}^i = lw_{T-1}^i
+ *     lv_j       = logsumexp_i ( lw_k^i - d2_ij / 2 )                         for every j of step k + 1
+ *     ls_k^i     = lw_k^i + logsumexp_j ( ls_{k+1}^j - lv_j - d2_ij / 2 )     for every i of step k,  k = T-2 .. 0
+ * and ls_k is then normalised (in exact arithmetic its log-sum-exp is already 0).  Every log-sum-exp is a sweep for the maximum followed
+ * by a sweep for the sum of exp(. - max), both in ascending order of the index summed over.  Terms with a log-weight of -inf contribute
+ * nothing; a lv_j of -inf is skipped (it can only belong to a particle whose own smoothed weight is -inf).  sm[k], sP[k] are the mean
+ * and the covariance (second pass around the mean, both triangles from one value) of the cloud x_k under exp(ls_k), as the filter's;
+ * ess_s[k] = 1 / sum exp(2 ls_k).  O(N^2) transition densities per step and trajectory; deterministic given the forward pass - no
+ * random numbers.
+ *
+ * SSMQ_PS_GENEALOGY - ancestor tracing, for every model the filter covers (singular G Q G' included, where the transition has no
+ * density on the state space and FFBSm does not exist):
+ *     idx_{T-1}(j) = j,   idx_k(j) = a_k(idx_{k+1}(j)),   k = T-2 .. 0
+ * sm[k], sP[k] are the moments of x_k[:, idx_k(j)], j = 0 .. N-1, under the final weights exp(lw_{T-1}^j); ess_s[k] = 1 / sum
+ * exp(2 lw_{T-1}^j) for every k; d_unique[k] is the number of distinct idx_k(j) - the path-degeneracy diagnostic: where it has fallen to
+ * a few, the estimate of step k has collapsed.  A gather, not a scatter-add: the sums run over j in the filter's fixed order.
+ *
+ * Both: step T-1 is the filter's - fm, fP and ess of that step are copied, bit for bit.  The smoothed initial state x_{-1} is not
+ * computed (the filter does not keep its initial cloud).  All sums run in the filter's order, fixed by N alone: a trajectory's bits
+ * depend on its own cloud and N, not on B or on how a batch is split over calls.
+ * Buffers: d_part [T][D][B][N], d_logw [T][B][N], d_anc [T][B][N] int32 (read by SSMQ_PS_GENEALOGY only; may be NULL otherwise), d_fm
+ * [T][D][ld], d_fP [T][D*D][ld], d_ess [T][ld], d_status [ld] as the filter left them; outputs d_sm [T][D][ld], d_sP [T][D*D][ld] in
+ * the layout of the Gaussian smoothers (with d_status the triple ssmq_error_sums_dev and ssmq_traj_scores_dev take), d_ess_s [T][ld].
+ * Optional outputs, each may be NULL: d_logw_s [T][B][N] the normalised smoothed log-weights ls_k (genealogy: the final weights,
+ * repeated); genealogy only: d_lineage [T][B][N] int32 idx_k(j), d_unique [T][ld] int32.  Host arrays: q_mean [dq] (NULL = 0), q_chol
+ * [dq*dq] lower factor of Q, G [D*dq] (NULL = eye(D, dq)) - the filter's; SSMQ_PS_GENEALOGY reads none of the three.
+ * Failures: a trajectory whose d_status is not 0 gets NaN in d_sm, d_sP, d_ess_s and d_logw_s (-1 in d_lineage and d_unique) at every
+ * step; its status stays, other trajectories are untouched.
+ * Range: the filter's (built-in integrand with additive noise, no state index, 1 <= D <= 6, 1 <= dq <= 6, N a multiple of 64 in
+ * 64 .. 4096 with (2 D + 1) N <= 13312).  SSMQ_E_UNSUPPORTED, the reason named: SSMQ_PS_MARGINAL with dq != D or with G Q G' not
+ * positive definite (use SSMQ_PS_GENEALOGY), and what the filter refuses.  SSMQ_E_ARG: a condition number of G Q G' above 1e12, an
+ * unknown method, T < 1, ld < B, null pointers, an N that is no multiple of 64 - all before the device, an output or d_status is
+ * touched.  B == 0: nothing happens.  One launch of k_particle_smooth<D> (LDS: alpha, beta [D][N] and two [N] rows, (2 D + 2) N doubles
+ * and the reduction scratch - at most 128 KB + 768 B) or k_particle_lineage<D>: one trajectory per workgroup of 256 threads, particle i
+ * on thread i mod 256, the loop over k inside.  Synchronous.
+ */
+enum { SSMQ_PS_MARGINAL = 0, SSMQ_PS_GENEALOGY = 1 };
+int ssmq_particle_smoother_dev(const ssmq_integrand *f_dyn, int D, int dq, int N, int64_t B, int64_t ld, int T, const double *q_mean,
+                               const double *q_chol, const double *G, int method, const double *d_part, const double *d_logw,
+                               const int32_t *d_anc, const double *d_fm, const double *d_fP, const double *d_ess,
+                               const int32_t *d_status, double *d_sm, double *d_sP, double *d_ess_s, double *d_logw_s,
+                               int32_t *d_lineage, int32_t *d_unique);
+/* Name of the kernel ssmq_particle_smoother_dev would run, with the LDS it requests: the range check of that call without a device
+ * (the same return codes; B, T and the device buffers are not part of it). */
+int ssmq_particle_smoother_kernel_name(const ssmq_integrand *f_dyn, int D, int dq, int N, const double *q_mean, const double *q_chol,
+                                       const double *G, int method, char *buf, int len);
+
+/*
  * The path's only collective: independent Monte-Carlo trajectories shard across ranks, one process per
  * GPU, and only the per-time-step error sums are added at the end (the reference loops `for imc in range(mc)` in one
  * process and averages with numpy: research/tpq/tpq_base.py:154-172, utils.py:113-120).  RCCL over xGMI, opened at run

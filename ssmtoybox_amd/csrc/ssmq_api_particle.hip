@@ -1,6 +1,9 @@
 // C entry points of the bootstrap particle filter (include/ssmq.h: ssmq_particle_filter_dev, ssmq_particle_kernel_name): the range
 // check, the host-side constants (noise factors padded to the kernel's strides, the measurement density's log-normaliser) and the
-// launch of k_particle_filter<D> (ssmq_particle.hip).
+// launch of k_particle_filter<D> (ssmq_particle.hip).  And of the particle smoothers over its cloud (ssmq_particle_smoother_dev,
+// ssmq_particle_smoother_kernel_name): the range check, the whitening data of the marginal smoother (the inverse factor of G Q G',
+// refused where the transition has no density) and the launch of k_particle_smooth<D> / k_particle_lineage<D>
+// (ssmq_particle_smooth.hip).
 #include <cmath>
 #include <cstdio>
 #include "ssmq_particle.h"
@@ -81,6 +84,153 @@ int pf_check(const char *what, const ssmq_integrand *f_dyn, const ssmq_integrand
     return SSMQ_OK;
 }
 
+// Largest and smallest eigenvalue of the symmetric n x n matrix A (row-major, n <= kPfMaxD) by cyclic Jacobi rotations.
+void ps_eig_range(const double *A, int n, double *lo, double *hi) {
+    double M[kPfMaxD * kPfMaxD];
+    for (int i = 0; i < n * n; ++i) M[i] = A[i];
+    for (int sweep = 0; sweep < 60; ++sweep) {
+        double off = 0.0, diag = 0.0;
+        for (int r = 0; r < n; ++r)
+            for (int c = 0; c < n; ++c) (r == c ? diag : off) += M[r * n + c] * M[r * n + c];
+        if (off <= 1e-60 * diag || off == 0.0) break;
+        for (int p = 0; p < n - 1; ++p)
+            for (int q = p + 1; q < n; ++q) {
+                if (M[p * n + q] == 0.0) continue;
+                const double theta = (M[q * n + q] - M[p * n + p]) / (2.0 * M[p * n + q]);
+                const double tn = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+                const double cs = 1.0 / sqrt(tn * tn + 1.0), sn = tn * cs;
+                for (int k = 0; k < n; ++k) {          // columns p, q
+                    const double kp = M[k * n + p], kq = M[k * n + q];
+                    M[k * n + p] = cs * kp - sn * kq;
+                    M[k * n + q] = sn * kp + cs * kq;
+                }
+                for (int k = 0; k < n; ++k) {          // rows p, q
+                    const double pk = M[p * n + k], qk = M[q * n + k];
+                    M[p * n + k] = cs * pk - sn * qk;
+                    M[q * n + k] = sn * pk + cs * qk;
+                }
+            }
+    }
+    *lo = *hi = M[0];
+    for (int i = 1; i < n; ++i) {
+        *lo = std::min(*lo, M[i * n + i]);
+        *hi = std::max(*hi, M[i * n + i]);
+    }
+}
+
+// everything about a smoother call that can be decided without a device; fills the whitening data of the marginal method
+int ps_check(const char *what, const ssmq_integrand *f_dyn, int D, int dq, int N, const double *q_mean, const double *q_chol,
+             const double *G, int method, PsLaunch *h) {
+    char msg[640];
+    if (!f_dyn) {
+        snprintf(msg, sizeof(msg), "%s: null model pointer", what);
+        set_error(msg);
+        return SSMQ_E_ARG;
+    }
+    if (is_user_integrand(f_dyn)) return refuse_user_integrand(what);
+    if (method != SSMQ_PS_MARGINAL && method != SSMQ_PS_GENEALOGY) {
+        snprintf(msg, sizeof(msg), "%s: unknown method %d (SSMQ_PS_MARGINAL = 0, SSMQ_PS_GENEALOGY = 1)", what, method);
+        set_error(msg);
+        return SSMQ_E_ARG;
+    }
+    if (N < kPfMinN || N % 64 != 0) {
+        snprintf(msg, sizeof(msg), "%s: N = %d particles - a multiple of 64, at least 64, is needed", what, N);
+        set_error(msg);
+        return SSMQ_E_ARG;
+    }
+    if (D < 1 || dq < 1) {
+        snprintf(msg, sizeof(msg), "%s: D and dq must be at least 1", what);
+        set_error(msg);
+        return SSMQ_E_ARG;
+    }
+    const char *range = "the cloud of ssmq_particle_filter_dev: built-in additive-noise models, 1 <= D <= 6, 1 <= dq <= 6, N a multiple of 64 "
+                        "in 64 .. 4096 with (2 D + 1) N <= 13312";
+    if (pf_noise_is_argument(f_dyn->id)) {
+        snprintf(msg, sizeof(msg), "%s: not implemented for models that take their noise as an argument (non-additive noise); range: %s",
+                 what, range);
+        set_error(msg);
+        return SSMQ_E_UNSUPPORTED;
+    }
+    if (!pf_shape_ok(D, 1, dq, N)) {
+        snprintf(msg, sizeof(msg), "%s: D = %d, dq = %d, N = %d is outside the range: %s", what, D, dq, N, range);
+        set_error(msg);
+        return SSMQ_E_UNSUPPORTED;
+    }
+    FInfo fid;
+    if (!integrand_info(f_dyn->id, &fid) || fid.dout != D || fid.din != D || f_dyn->n_idx != 0) {
+        snprintf(msg, sizeof(msg), "%s: transition integrand / dimension mismatch (D -> D, no state index)", what);
+        set_error(msg);
+        return SSMQ_E_ARG;
+    }
+    h->f_dyn = f_dyn; h->D = D; h->N = N; h->method = method;
+    if (method == SSMQ_PS_GENEALOGY) return SSMQ_OK;
+    if (!q_chol) {
+        snprintf(msg, sizeof(msg), "%s: the marginal method needs q_chol", what);
+        set_error(msg);
+        return SSMQ_E_ARG;
+    }
+    const char *hint = "the transition has no density on the state space and the marginal smoother (FFBSm) does not exist; "
+                       "use the genealogy method (method='genealogy')";
+    if (dq != D) {
+        snprintf(msg, sizeof(msg), "%s: dq = %d != D = %d, the process noise G Q G' is singular: %s", what, dq, D, hint);
+        set_error(msg);
+        return SSMQ_E_UNSUPPORTED;
+    }
+    // Sigma = (G Lq)(G Lq)', its Cholesky factor Ls and condition number
+    double GL[kPfMaxD * kPfMaxD], Sg[kPfMaxD * kPfMaxD], Ls[kPfMaxD * kPfMaxD];
+    for (int r = 0; r < D; ++r)
+        for (int c = 0; c < D; ++c) {
+            double s = 0.0;
+            for (int k = c; k < D; ++k) s += (G ? G[r * D + k] : (r == k ? 1.0 : 0.0)) * q_chol[k * D + c];
+            GL[r * D + c] = s;
+        }
+    for (int r = 0; r < D; ++r)
+        for (int c = 0; c < D; ++c) {
+            double s = 0.0;
+            for (int k = 0; k < D; ++k) s += GL[r * D + k] * GL[c * D + k];
+            Sg[r * D + c] = s;
+        }
+    bool pd = true;
+    for (int c = 0; c < D && pd; ++c)
+        for (int r = c; r < D; ++r) {
+            double s = Sg[r * D + c];
+            for (int k = 0; k < c; ++k) s -= Ls[r * D + k] * Ls[c * D + k];
+            if (r == c) {
+                if (!(s > 0.0) || !std::isfinite(s)) { pd = false; break; }
+                Ls[c * D + c] = sqrt(s);
+            } else {
+                Ls[r * D + c] = s / Ls[c * D + c];
+            }
+        }
+    double lo = 0.0, hi = 0.0;
+    if (pd) ps_eig_range(Sg, D, &lo, &hi);
+    if (!pd || !(lo > 0.0)) {
+        snprintf(msg, sizeof(msg), "%s: the process noise G Q G' is not positive definite: %s", what, hint);
+        set_error(msg);
+        return SSMQ_E_UNSUPPORTED;
+    }
+    if (!(hi / lo <= 1e12)) {
+        snprintf(msg, sizeof(msg), "%s: the condition number of G Q G' is %.3g, above 1e12: the whitened distances of the marginal smoother "
+                 "would carry no digits (method='genealogy' does not need them)", what, hi / lo);
+        set_error(msg);
+        return SSMQ_E_ARG;
+    }
+    // Li = Ls^-1 by forward substitution, column by column
+    memset(h->Li, 0, sizeof(h->Li));
+    for (int c = 0; c < D; ++c)
+        for (int r = c; r < D; ++r) {
+            double s = r == c ? 1.0 : 0.0;
+            for (int k = c; k < r; ++k) s -= Ls[r * D + k] * h->Li[k * kPfMaxD + c];
+            h->Li[r * kPfMaxD + c] = s / Ls[r * D + r];
+        }
+    for (int r = 0; r < D; ++r) {
+        double s = 0.0;
+        for (int k = 0; k < D; ++k) s += (G ? G[r * D + k] : (r == k ? 1.0 : 0.0)) * (q_mean ? q_mean[k] : 0.0);
+        h->gq[r] = s;
+    }
+    return SSMQ_OK;
+}
+
 }  // namespace
 }  // namespace ssmq
 
@@ -141,6 +291,51 @@ extern "C" int ssmq_particle_filter_dev(const ssmq_integrand *f_dyn, const ssmq_
     if (B == 0) return SSMQ_OK;
     hipStream_t s = stream();
     rc = launch_particle_filter(h, s);
+    hipError_t e = hipStreamSynchronize(s);
+    if (rc) return rc;
+    SSMQ_HIP(e);
+    return SSMQ_OK;
+}
+
+extern "C" int ssmq_particle_smoother_kernel_name(const ssmq_integrand *f_dyn, int D, int dq, int N, const double *q_mean,
+                                                  const double *q_chol, const double *G, int method, char *buf, int len) {
+    if (!buf || len < 1) {
+        set_error("ssmq_particle_smoother_kernel_name: null buffer");
+        return SSMQ_E_ARG;
+    }
+    PsLaunch h;
+    memset(&h, 0, sizeof(h));
+    int rc = ps_check("ssmq_particle_smoother_kernel_name", f_dyn, D, dq, N, q_mean, q_chol, G, method, &h);
+    if (rc) return rc;
+    snprintf(buf, (size_t)len, "%s<D=%d> (N = %d, %zu B of LDS per trajectory)",
+             method == SSMQ_PS_MARGINAL ? "k_particle_smooth" : "k_particle_lineage", D, N, ps_lds_bytes(method, D, N));
+    return SSMQ_OK;
+}
+
+extern "C" int ssmq_particle_smoother_dev(const ssmq_integrand *f_dyn, int D, int dq, int N, int64_t B, int64_t ld, int T,
+                                          const double *q_mean, const double *q_chol, const double *G, int method, const double *d_part,
+                                          const double *d_logw, const int32_t *d_anc, const double *d_fm, const double *d_fP,
+                                          const double *d_ess, const int32_t *d_status, double *d_sm, double *d_sP, double *d_ess_s,
+                                          double *d_logw_s, int32_t *d_lineage, int32_t *d_unique) {
+    PsLaunch h;
+    memset(&h, 0, sizeof(h));
+    int rc = ps_check("ssmq_particle_smoother_dev", f_dyn, D, dq, N, q_mean, q_chol, G, method, &h);
+    if (rc) return rc;
+    if (T < 1 || B < 0 || ld < B || B > 0x7fffffff || !d_part || !d_logw || !d_fm || !d_fP || !d_ess || !d_status || !d_sm || !d_sP ||
+        !d_ess_s || (method == SSMQ_PS_GENEALOGY && !d_anc)) {
+        set_error("ssmq_particle_smoother_dev: bad argument (T >= 1, 0 <= B <= ld, non-null buffers; d_anc for SSMQ_PS_GENEALOGY)");
+        return SSMQ_E_ARG;
+    }
+    h.T = T; h.B = B; h.ld = ld;
+    h.part = d_part; h.logw = d_logw; h.anc = d_anc; h.fm = d_fm; h.fP = d_fP; h.ess = d_ess; h.status = d_status;
+    h.sm = d_sm; h.sP = d_sP; h.ess_s = d_ess_s; h.logw_s = d_logw_s;
+    h.lineage = method == SSMQ_PS_GENEALOGY ? d_lineage : nullptr;
+    h.unique = method == SSMQ_PS_GENEALOGY ? d_unique : nullptr;
+    rc = ensure_device();
+    if (rc) return rc;
+    if (B == 0) return SSMQ_OK;
+    hipStream_t s = stream();
+    rc = launch_particle_smoother(h, s);
     hipError_t e = hipStreamSynchronize(s);
     if (rc) return rc;
     SSMQ_HIP(e);

@@ -1,5 +1,6 @@
-// Bootstrap particle filter (ssmq_particle.hip: k_particle_filter<D>; ssmq_api_particle.hip: ssmq_particle_filter_dev): what the
-// entry point hands the launcher.  Host arrays are padded to the kernel's fixed strides so that the kernel indexes them statically.
+// Bootstrap particle filter (ssmq_particle.hip: k_particle_filter<D>; ssmq_api_particle.hip: ssmq_particle_filter_dev) and the particle
+// smoothers over its cloud (ssmq_particle_smooth.hip: k_particle_smooth<D>, k_particle_lineage<D>; ssmq_particle_smoother_dev): what
+// the entry points hand the launchers.  Host arrays are padded to the kernels' fixed strides so that the kernels index them statically.
 #pragma once
 #include "ssmq_host.h"
 
@@ -10,6 +11,7 @@ constexpr int kPfMaxD = 6, kPfMaxY = 4, kPfMaxQ = 6;
 constexpr int kPfMinN = 64, kPfMaxN = 4096;
 constexpr int kPfCloudDoubles = 13312; // (2 D + 1) N: two [D][N] particle buffers and the [N] weights / CDF - 104 KB
 constexpr int kPfRedDoubles = 96;      // reduction scratch: 4 wave partials of up to D (D + 1) / 2 = 21 sums, 4 scan totals
+constexpr int kPsCloudDoubles = 16384; // (2 D + 2) N over the filter's range: alpha, beta [D][N], two [N] rows - 128 KB
 
 struct PfLaunch {
     const ssmq_integrand *f_dyn, *f_obs;
@@ -31,5 +33,58 @@ inline bool pf_shape_ok(int D, int Y, int dq, int N) {
 }
 inline size_t pf_lds_bytes(int D, int N) { return sizeof(double) * ((size_t)(2 * D + 1) * N + kPfRedDoubles); }
 int launch_particle_filter(const PfLaunch &h, hipStream_t s);
+
+// The smoothers over the filter's cloud (include/ssmq.h ssmq_particle_smoother_dev states both recursions).
+struct PsLaunch {
+    const ssmq_integrand *f_dyn;
+    int D, N, T, method;                                    // method: SSMQ_PS_MARGINAL or SSMQ_PS_GENEALOGY
+    int64_t B, ld;
+    double Li[kPfMaxD * kPfMaxD], gq[kPfMaxD];              // marginal: inverse of chol(G Q G') (lower, zero-padded), G q_mean
+    const double *part, *logw, *fm, *fP, *ess;
+    const int32_t *anc, *status;
+    double *sm, *sP, *ess_s, *logw_s;
+    int32_t *lineage, *unique;
+};
+
+// marginal: alpha, beta [D][N], the filter's log-weights and the row that carries ls - lv; genealogy: the final weights [N] and two
+// int32 rows [N] (the lineage and the marks of the distinct count) - both with the reduction scratch
+inline size_t ps_lds_bytes(int method, int D, int N) {
+    return sizeof(double) * ((size_t)(method == SSMQ_PS_MARGINAL ? 2 * D + 2 : 2) * N + kPfRedDoubles);
+}
+int launch_particle_smoother(const PsLaunch &h, hipStream_t s);
+
+#ifdef __HIPCC__
+// ---- workgroup reductions of the particle kernels, in the order stated at the top of ssmq_particle.hip ----
+// sums of K values over the workgroup; every thread gets the results
+template <int K>
+__device__ __forceinline__ void pf_block_sum(double (&v)[K], double *red) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int q = 0; q < K; ++q) {
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) v[q] += __shfl_xor(v[q], o);
+    }
+    __syncthreads();                       // the readers of the previous reduction are done with red
+    if (lane == 0) {
+#pragma unroll
+        for (int q = 0; q < K; ++q) red[q * 4 + wave] = v[q];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < K; ++q) v[q] = (red[q * 4] + red[q * 4 + 1]) + (red[q * 4 + 2] + red[q * 4 + 3]);
+}
+
+// maximum that keeps a NaN (so that one NaN log-weight fails the step)
+__device__ __forceinline__ double pf_max(double x, double y) { return (y > x || y != y) ? y : x; }
+__device__ __forceinline__ double pf_block_max(double v, double *red) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v = pf_max(v, __shfl_xor(v, o));
+    __syncthreads();
+    if (lane == 0) red[wave] = v;
+    __syncthreads();
+    return pf_max(pf_max(red[0], red[1]), pf_max(red[2], red[3]));
+}
+#endif
 
 }  // namespace ssmq

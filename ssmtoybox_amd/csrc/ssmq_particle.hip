@@ -61,36 +61,7 @@ __device__ __forceinline__ void pf_normals(const PfArgs &a, uint64_t traj, uint3
     }
 }
 
-// sums of K values over the workgroup in the order stated at the top; every thread gets the results
-template <int K>
-__device__ __forceinline__ void pf_block_sum(double (&v)[K], double *red) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int q = 0; q < K; ++q) {
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) v[q] += __shfl_xor(v[q], o);
-    }
-    __syncthreads();                       // the readers of the previous reduction are done with red
-    if (lane == 0) {
-#pragma unroll
-        for (int q = 0; q < K; ++q) red[q * 4 + wave] = v[q];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < K; ++q) v[q] = (red[q * 4] + red[q * 4 + 1]) + (red[q * 4 + 2] + red[q * 4 + 3]);
-}
-
-// maximum that keeps a NaN (so that one NaN log-weight fails the step)
-__device__ __forceinline__ double pf_max(double x, double y) { return (y > x || y != y) ? y : x; }
-__device__ __forceinline__ double pf_block_max(double v, double *red) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v = pf_max(v, __shfl_xor(v, o));
-    __syncthreads();
-    if (lane == 0) red[wave] = v;
-    __syncthreads();
-    return pf_max(pf_max(red[0], red[1]), pf_max(red[2], red[3]));
-}
+// pf_block_sum / pf_block_max (ssmq_particle.h): the sums and the maximum over the workgroup in the order stated at the top
 
 template <int D>
 __global__ __launch_bounds__(kPfBlock) void k_particle_filter(const PfArgs a) {

@@ -1335,9 +1335,17 @@ class BootstrapParticleFilter:
     particles are weighted by the measurement density (GaussRV or StudentRV noise) and resampled systematically when the effective
     sample size falls below ess_threshold * num_particles (>= 1: every step, <= 0: never).  A class of its own, not a
     GaussianInference: it has no moment transforms.  A trajectory's results depend on `seed`, its global index, num_particles,
-    ess_threshold and its own data alone."""
+    ess_threshold and its own data alone.
 
-    RANGE = ('BootstrapParticleFilter covers forward passes (forward_pass, forward_pass_batch, forward_pass_dev) of built-in '
+    It also answers the smoothing question, E[x_k | y_0..T-1], from the same cloud (`ssmq_particle_smoother_dev`): `smoother`,
+    `smoother_batch`, `smoother_dev` with method='marginal' - the marginal forward-filter backward-smoother (FFBSm), one launch of
+    k_particle_smooth<D>, O(N^2) transition densities per step and trajectory, deterministic given the forward pass; it needs process
+    noise of full rank (G Q G' positive definite) - or method='genealogy' - ancestor tracing (k_particle_lineage<D>), for every model
+    the filter covers, with `unique`, the number of distinct ancestors left at each step, as the diagnostic of its collapse.  The
+    smoothed initial state x_{-1} is not computed: the filter does not keep its initial cloud."""
+
+    RANGE = ('BootstrapParticleFilter covers forward passes (forward_pass, forward_pass_batch, forward_pass_dev) and particle '
+             "smoothers (smoother, smoother_batch, smoother_dev; method='marginal' needs G Q G' positive definite) of built-in "
              'additive-noise models with a GaussRV initial state and process noise and GaussRV or StudentRV measurement noise, '
              'dim_state <= 6, dim_out <= 4, dim_noise <= 6, num_particles a multiple of 64 in 64 .. 4096 with '
              '(2 dim_state + 1) num_particles <= 13312')
@@ -1366,9 +1374,10 @@ class BootstrapParticleFilter:
         self.fi_mean = self.fi_cov = self.status = None
         self.loglik = self.loglik_total = self.ess = None
         self.particles = self.log_weights = self.ancestors = None
-        if getattr(self, 'd_loglik', None) is not None or getattr(self, 'd_ess', None) is not None:
+        self.sm_mean = self.sm_cov = self.ess_smooth = self.smoothed_log_weights = self.lineage = self.unique = None
+        if any(getattr(self, n, None) is not None for n in ('d_loglik', 'd_ess', 'd_ess_smooth')):
             self.free_dev()
-        self.d_loglik = self.d_ess = None
+        self.d_loglik = self.d_ess = self.d_ess_smooth = None
         self._data = None
 
     def _initial_planes(self, stage, B, ld, x0_mean=None, x0_cov=None):
@@ -1431,11 +1440,14 @@ class BootstrapParticleFilter:
         return d_fm, d_fP, d_st
 
     def free_dev(self):
-        """Frees the device planes the last forward_pass_dev left with the filter (`d_loglik`, `d_ess`)."""
+        """Frees the device planes the last forward_pass_dev or smoother_dev left with the filter (`d_loglik`, `d_ess`,
+        `d_ess_smooth`)."""
         if self.d_loglik is not None:        # (the two are set together)
             self.d_loglik.free()
             self.d_ess.free()
-        self.d_loglik = self.d_ess = None
+        if getattr(self, 'd_ess_smooth', None) is not None:
+            self.d_ess_smooth.free()
+        self.d_loglik = self.d_ess = self.d_ess_smooth = None
 
     def forward_pass_batch(self, data, x0_mean=None, x0_cov=None, raise_on_failure=True, return_particles=False):
         """data (dim_y, T, B) -> filtered means (D, T, B) and covariances (D, D, T, B): the weighted mean and covariance of the cloud
@@ -1486,6 +1498,147 @@ class BootstrapParticleFilter:
         """data (dim_y, T) -> filtered means (D, T), covariances (D, D, T): trajectory 0 of a batch of one."""
         fm, fP = self.forward_pass_batch(np.asarray(data)[..., None])
         return fm[..., 0], fP[..., 0]
+
+    # ---- particle smoothers over the cloud of a forward pass -------------------------------------------------------------------------
+    SMOOTHER_METHODS = {'marginal': 0, 'genealogy': 1}        # SSMQ_PS_MARGINAL, SSMQ_PS_GENEALOGY
+
+    def _smoother_check(self, method):
+        """The library's range check of a smoother, without a device: ValueError for an unknown method (or a condition number of
+        G Q G' above 1e12), NotImplementedError where method='marginal' has no transition density to work with."""
+        if method not in self.SMOOTHER_METHODS:
+            raise ValueError("BootstrapParticleFilter: unknown smoother method {!r} ('marginal' or 'genealogy')".format(method))
+        f_dyn, f_obs, r, qm, qL, keep = self._c_args()
+        buf = ctypes.create_string_buffer(256)
+        rc = _lib.load().ssmq_particle_smoother_kernel_name(ctypes.byref(f_dyn), self.mod_dyn.dim_state, qm.size, self.num_particles,
+                                                            _lib.dp(qm), _lib.dp(qL), _lib.dp(self.G), self.SMOOTHER_METHODS[method], buf, 256)
+        if rc == -1:             # SSMQ_E_ARG
+            raise ValueError(_lib.last_error())
+        _lib.check(rc, 'ssmq_particle_smoother_kernel_name', unsupported=True)
+        return buf.value.decode()
+
+    def smoother_kernel_name(self, method='marginal'):
+        """The kernel a smoother of this method launches after the forward pass, with the LDS it requests per trajectory."""
+        return self._smoother_check(method)
+
+    def cloud_block(self, T, B, cloud_bytes=2 ** 30):
+        """Trajectories per block of a smoother pass: the weighted cloud of a block, (8 (D + 1) + 4) T N bytes per trajectory, fits
+        cloud_bytes (at least one trajectory)."""
+        per = (8 * (self.mod_dyn.dim_state + 1) + 4) * int(T) * self.num_particles
+        return int(max(1, min(int(B), int(cloud_bytes) // per)))
+
+    def _smooth_blocks(self, lib, stage, method, B, ld, T, traj_offset, cloud_bytes, d_y, d_m0, d_P0, d, host=None):
+        """Forward pass with the cloud kept, then the smoother, in consecutive blocks of `cloud_block` trajectories: block b0 works on
+        the planes of `d` (fm, fP, ll, ess, st, sm, sP, ess_s, unique - pitch ld) from column b0 on and draws from the streams
+        traj_offset + b0 .., so that nothing depends on the block size.  host: dict of host arrays in the device's layout
+        (particles (T, D, B, N), log_weights, smoothed_log_weights (T, B, N), ancestors, lineage (T, B, N) int32) the clouds are
+        downloaded into, block by block."""
+        D, N, code = self.mod_dyn.dim_state, self.num_particles, self.SMOOTHER_METHODS[method]
+        f_dyn, f_obs, r, qm, qL, keep = self._c_args()
+        vp, dp = _lib.vp, _lib.dp
+        nb = self.cloud_block(T, B, cloud_bytes)
+        d_part, d_logw, d_anc = stage.scratch(8 * T * D * nb * N), stage.scratch(8 * T * nb * N), stage.scratch(4 * T * nb * N)
+        d_lws = stage.scratch(8 * T * nb * N) if host is not None else None
+        d_lin = stage.scratch(4 * T * nb * N) if host is not None and code == 1 else None
+        for b0 in range(0, B, nb):
+            n = min(nb, B - b0)
+            at = lambda name: d[name].view((4 if name in ('st', 'unique') else 8) * b0)          # noqa: E731
+            self._launch(lib, n, ld, T, traj_offset + b0, d_y.view(8 * b0), d_m0.view(8 * b0), d_P0.view(8 * b0), at('fm'), at('fP'),
+                         at('ll'), at('ess'), at('st'), d_part, d_logw, d_anc)
+            _lib.check(lib.ssmq_particle_smoother_dev(ctypes.byref(f_dyn), D, qm.size, N, n, ld, T, dp(qm), dp(qL), dp(self.G), code,
+                                                      vp(d_part), vp(d_logw), vp(d_anc), vp(at('fm')), vp(at('fP')), vp(at('ess')),
+                                                      vp(at('st')), vp(at('sm')), vp(at('sP')), vp(at('ess_s')), vp(d_lws), vp(d_lin),
+                                                      vp(at('unique')) if code == 1 else None),
+                       'ssmq_particle_smoother_dev', unsupported=True)
+            if host is not None:
+                host['particles'][:, :, b0:b0 + n] = d_part.download((T, D, n, N))
+                host['log_weights'][:, b0:b0 + n] = d_logw.download((T, n, N))
+                host['ancestors'][:, b0:b0 + n] = d_anc.download((T, n, N), dtype=np.int32)
+                host['smoothed_log_weights'][:, b0:b0 + n] = d_lws.download((T, n, N))
+                if code == 1:
+                    host['lineage'][:, b0:b0 + n] = d_lin.download((T, n, N), dtype=np.int32)
+
+    def smoother_dev(self, d_y, B, ld, T, method='marginal', traj_offset=0, cloud_bytes=2 ** 30):
+        """Smooth measurements that are already on the device (planes [T][dim_y][ld]) and leave the results there: returns the triple
+        of the Gaussian smoothers, DeviceBuffers (d_sm [T][D][ld], d_sP [T][D*D][ld], d_status [ld]) for `mcshard.device_error_sums` /
+        `device_traj_scores` / `device_score_bars`; the caller frees them.  The forward pass runs first, with the cloud kept on the
+        device: (8 (D + 1) + 4) T B N bytes, processed in consecutive blocks of trajectories whose cloud fits cloud_bytes - the results
+        do not depend on the block size, bit for bit.  `d_ess_smooth` [T][ld], like `d_loglik` and `d_ess` of the forward pass, stays
+        with the filter: the next forward_pass_dev or smoother_dev, `reset()` or `free_dev()` frees them.  Trajectory b draws from the
+        stream of global index traj_offset + b.  The smoothed initial state is not computed."""
+        self._smoother_check(method)
+        if T < 1:
+            raise ValueError('BootstrapParticleFilter: at least one time step is needed (T = {})'.format(T))
+        lib = _lib.load()
+        D = self.mod_dyn.dim_state
+        self.free_dev()
+        with _lib.Staging() as stage:
+            d_m0, d_P0 = self._initial_planes(stage, B, ld)
+            d = dict(fm=stage.scratch(8 * T * D * ld), fP=stage.scratch(8 * T * D * D * ld), ll=stage.device(8 * (T + 1) * ld),
+                     ess=stage.device(8 * T * ld), st=stage.device(4 * ld), sm=stage.device(8 * T * D * ld),
+                     sP=stage.device(8 * T * D * D * ld), ess_s=stage.device(8 * T * ld), unique=stage.scratch(4 * T * ld))
+            d['st'].zero()
+            self._smooth_blocks(lib, stage, method, B, ld, T, traj_offset, cloud_bytes, d_y, d_m0, d_P0, d)
+            stage.release(d['sm'], d['sP'], d['st'], d['ll'], d['ess'], d['ess_s'])
+        self.d_loglik, self.d_ess, self.d_ess_smooth = d['ll'], d['ess'], d['ess_s']
+        return d['sm'], d['sP'], d['st']
+
+    def smoother_batch(self, data, method='marginal', x0_mean=None, x0_cov=None, raise_on_failure=True, return_particles=False,
+                       cloud_bytes=2 ** 30):
+        """data (dim_y, T, B) -> smoothed means (D, T, B) and covariances (D, D, T, B): the moments of the smoothing posterior
+        p(x_k | y_0..T-1) from the particle filter's cloud.  method='marginal': the marginal forward-filter backward-smoother, the
+        cloud of step k re-weighted by exp(ls_k) (needs G Q G' positive definite: NotImplementedError otherwise); method='genealogy':
+        the ancestors of the final particles under the final weights (every model; `unique` (T, B), the number of distinct
+        ancestors, tells where it has collapsed).  Step T-1 is the filter's.  Runs `forward_pass_batch` with the cloud kept on the
+        device, then the smoother, in consecutive blocks of trajectories whose cloud - (8 (D + 1) + 4) T N bytes per trajectory - fits
+        cloud_bytes; the results do not depend on the block size, bit for bit.  Sets sm_mean, sm_cov, ess_smooth (T, B) and
+        everything forward_pass_batch sets; with return_particles also smoothed_log_weights (N, T, B) (genealogy: the final weights,
+        repeated) and for 'genealogy' lineage (N, T, B).  A trajectory the filter failed on is NaN at every step, its status kept.
+        The smoothed initial state x_{-1} is not computed: the filter does not keep its initial cloud."""
+        self._smoother_check(method)
+        lib = _lib.load()
+        data = np.asarray(data, dtype=np.float64)
+        Y, T, B = data.shape
+        if Y != self.mod_obs.dim_out:
+            raise ValueError('data must have shape (dim_y = {}, T, B)'.format(self.mod_obs.dim_out))
+        if T < 1:
+            raise ValueError('BootstrapParticleFilter: at least one time step is needed (T = {})'.format(T))
+        self._data = data
+        D, N = self.mod_dyn.dim_state, self.num_particles
+        ld = _lib.padded(B)
+        host = None
+        if return_particles:
+            host = dict(particles=np.empty((T, D, B, N)), log_weights=np.empty((T, B, N)), smoothed_log_weights=np.empty((T, B, N)),
+                        ancestors=np.empty((T, B, N), dtype=np.int32), lineage=np.empty((T, B, N), dtype=np.int32))
+        with _lib.Staging() as stage:
+            d_y = stage.scratch(8 * T * Y * ld)
+            _lib.upload_study(data, Y, ld, d_y)
+            d_m0, d_P0 = self._initial_planes(stage, B, ld, x0_mean, x0_cov)
+            d = dict(fm=stage.scratch(8 * T * D * ld), fP=stage.scratch(8 * T * D * D * ld), ll=stage.scratch(8 * (T + 1) * ld),
+                     ess=stage.scratch(8 * T * ld), st=stage.scratch(4 * ld), sm=stage.scratch(8 * T * D * ld),
+                     sP=stage.scratch(8 * T * D * D * ld), ess_s=stage.scratch(8 * T * ld), unique=stage.scratch(4 * T * ld))
+            d['st'].zero()
+            self._smooth_blocks(lib, stage, method, B, ld, T, 0, cloud_bytes, d_y, d_m0, d_P0, d, host)
+            self.fi_mean, self.fi_cov = _lib.download_study(d['fm'], (D,), T, B, ld), _lib.download_study(d['fP'], (D, D), T, B, ld)
+            self.sm_mean, self.sm_cov = _lib.download_study(d['sm'], (D,), T, B, ld), _lib.download_study(d['sP'], (D, D), T, B, ld)
+            self.status = d['st'].download((ld,), dtype=np.int32)[:B]
+            ll = d['ll'].download((T + 1, ld))
+            self.loglik, self.loglik_total = np.ascontiguousarray(ll[:T, :B]), ll[T, :B].copy()
+            self.ess = np.ascontiguousarray(d['ess'].download((T, ld))[:, :B])
+            self.ess_smooth = np.ascontiguousarray(d['ess_s'].download((T, ld))[:, :B])
+            self.unique = np.ascontiguousarray(d['unique'].download((T, ld), dtype=np.int32)[:, :B]) if method == 'genealogy' else None
+        self.particles = self.log_weights = self.ancestors = self.smoothed_log_weights = self.lineage = None
+        if return_particles:
+            self.particles = np.ascontiguousarray(host['particles'].transpose(1, 3, 0, 2))
+            for name in ('log_weights', 'ancestors', 'smoothed_log_weights') + (('lineage',) if method == 'genealogy' else ()):
+                setattr(self, name, np.ascontiguousarray(host[name].transpose(2, 0, 1)))
+        if raise_on_failure:
+            _raise_failed(self.status, message='Particle filter degenerate: no finite log-weight (trajectory {}, step {})')
+        return self.sm_mean, self.sm_cov
+
+    def smoother(self, data, method='marginal'):
+        """data (dim_y, T) -> smoothed means (D, T), covariances (D, D, T): trajectory 0 of a batch of one."""
+        sm, sP = self.smoother_batch(np.asarray(data)[..., None], method=method)
+        return sm[..., 0], sP[..., 0]
 
     def _refuse(self, what):
         raise NotImplementedError('{}; {} is not implemented for it'.format(self.RANGE, what))
