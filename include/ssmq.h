@@ -128,8 +128,12 @@ int ssmq_integrand_define_dx(const char *body, const char *jac_body, int din, in
  * SSMQ_RTC_FILTER; opt must be 0: the dense kernel is the only one). */
 /* SSMQ_RTC_SMOOTHER_ITERATED instantiates the iterated-smoother kernel k_ipls_pass<D, E (= Y), N, N_obs, id, id_obs, form, tp, 0>
  * (arguments as SSMQ_RTC_FILTER; opt must be 0: the dense transforms are the only ones). */
+/* SSMQ_RTC_PCRLB_DYN / SSMQ_RTC_PCRLB_OBS instantiate the two kernels of the posterior Cramer-Rao sums (ssmq_pcrlb_sums_dev) for a
+ * user id that has a Jacobian: k_pcrlb_dyn_fn<id, D, din> (a D -> D model: E is not read) and k_pcrlb_obs_fn<id, D, E, din> (N, N_obs, form,
+ * tp, opt ignored); an id without a Jacobian, D > 6 or E > 4 (measurement) is SSMQ_E_UNSUPPORTED. */
 enum ssmq_rtc_kind { SSMQ_RTC_FILTER = 0, SSMQ_RTC_APPLY = 1, SSMQ_RTC_MC = 2, SSMQ_RTC_LINEAR = 3, SSMQ_RTC_TAYLOR_GPQD = 4, SSMQ_RTC_GPQD = 5,
-                     SSMQ_RTC_INNOVATION = 6, SSMQ_RTC_ITERATED = 7, SSMQ_RTC_SMOOTHER_ITERATED = 8 };
+                     SSMQ_RTC_INNOVATION = 6, SSMQ_RTC_ITERATED = 7, SSMQ_RTC_SMOOTHER_ITERATED = 8, SSMQ_RTC_PCRLB_DYN = 9,
+                     SSMQ_RTC_PCRLB_OBS = 10 };
 int ssmq_rtc_compile_check(int32_t id, int32_t id_obs, int kind, int D, int E, int N, int N_obs, int form, int tp, int opt,
                            const char *arch, char *log, int len);
 /* Process-wide counters of the run-time compiler: programs compiled, kernel lookups served from the cache, compile wall time. */
@@ -1145,6 +1149,52 @@ int ssmq_particle_smoother_dev(const ssmq_integrand *f_dyn, int D, int dq, int N
  * (the same return codes; B, T and the device buffers are not part of it). */
 int ssmq_particle_smoother_kernel_name(const ssmq_integrand *f_dyn, int D, int dq, int N, const double *q_mean, const double *q_chol,
                                        const double *G, int method, char *buf, int len);
+
+/*
+ * Posterior Cramer-Rao lower bound (Tichavsky, Muravchik, Nehorai 1998) of the additive-Gaussian-noise models: the floor no filter of
+ * a study can get under, E[(x_j - m_j)(x_j - m_j)'] >= J_j^-1 for every estimator m_j of x_j from y_0 .. y_j.  Input: the true states,
+ * planes p_0 .. p_T as ssmq_simulate*_dev with T + 1 steps writes them (p_0 ~ the initial state, p_{j+1} the state the filters call x_j).
+ * In the filters' time convention (both models of step j at time j), per trajectory
+ *     F_j = df/dx (p_j, j)  (D x D),     H_j = dh/dx (p_{j+1}, j)  (Y x D, placed into the state's columns as the linearisation
+ *     transform places it: through the state index, or - a built-in one-column Jacobian without one - into every column),
+ * and with Qi = (G Q G')^-1, Ri = R^-1, for j = 0 .. T-1:
+ *     D11_j = mean_b F_j' Qi F_j,     D12_j = -(mean_b F_j)' Qi,     D22_j = Qi + mean_b H_j' Ri H_j,
+ *     J_j = D22_j - D12_j' (J_{j-1} + D11_j)^-1 D12_j,     J_{-1} = P0^-1.
+ * Two phases, as the error sums: ssmq_pcrlb_sums_dev adds over this rank's B trajectories, the sums of all ranks are added (one
+ * all-reduce), ssmq_pcrlb_finalize divides by the total count and runs the recursion on the host.
+ *
+ * ssmq_pcrlb_sums_dev: d_x [T+1][D][ld] device planes; q: the process noise, r: the measurement noise - SSMQ_RV_GAUSS with chol the
+ * lower factor of Q [dq*dq] / R [Y*Y] (their means are not read); G [D*dq] (NULL = eye(D, dq)); host arrays.  sums: host [T][S],
+ * S = ssmq_pcrlb_sums_width(D) = D (D + 1) / 2 + D D + D (D + 1) / 2, row j:
+ *     sum_b F_j' Qi F_j, lower triangle packed (entry (i, k), k <= i, at i (i + 1) / 2 + k)  |  sum_b F_j, row-major [D][D]  |
+ *     sum_b H_j' Ri H_j, lower triangle packed.
+ * Sums, not means.  Summation order (fixed: the bits depend on B and the states alone, not on ld, the grid or the device): the
+ * trajectories of a step in groups of 256 consecutive ones; inside a group the 64 lanes of a wave by a butterfly (l ^ 32, 16, .. 1),
+ * then the four waves as (w0 + w1) + (w2 + w3); then the groups in ascending order.  Lanes b >= B contribute exact zeros and their
+ * columns are not read.  A non-finite term is not masked: it makes the sums of its step non-finite, which the finaliser reports.
+ * Kernels: k_pcrlb_dyn<D, D> / k_pcrlb_obs<D, Y> for the built-in models that have a Jacobian, k_pcrlb_dyn_fn / k_pcrlb_obs_fn compiled
+ * at run time for a user integrand registered with one (ssmq_integrand_define_dx) - one kernel per model, so the two kinds pair freely;
+ * one trajectory per lane, one row of partial sums per (step, group) in a workspace; k_pcrlb_rows adds the rows of a step.  No atomics.
+ * Refusals, all before a device is looked for or `sums` is touched.  SSMQ_E_UNSUPPORTED, the range named: a model that takes its noise
+ * as an argument; a model without a Jacobian on the device; Student-t or mixture noise; D > 6 or Y > 4; dq != D or G Q G' not positive
+ * definite.  SSMQ_E_ARG: a condition number of G Q G' above 1e12, a factor of R without a positive diagonal, T < 1, ld < B, B < 0, null
+ * pointers, mismatched dimensions.  B == 0: the sums are zeros.  Synchronous.
+ */
+int ssmq_pcrlb_sums_width(int D);
+int ssmq_pcrlb_sums_dev(const ssmq_integrand *f_dyn, const ssmq_integrand *f_obs, int D, int Y, int dq, int64_t B, int64_t ld, int T,
+                        const double *d_x, const ssmq_rv *q, const double *G, const ssmq_rv *r, double *sums);
+/* Names of the two kernels ssmq_pcrlb_sums_dev would run: the range check of that call without a device (the same return codes; B, ld, T
+ * and d_x are not part of it). */
+int ssmq_pcrlb_kernel_name(const ssmq_integrand *f_dyn, const ssmq_integrand *f_obs, int D, int Y, int dq, const ssmq_rv *q,
+                           const double *G, const ssmq_rv *r, char *buf, int len);
+/* The recursion from the (all-reduced) sums of B_total trajectories, on the host in double; no device.  P0 [D*D] the covariance of the
+ * initial state (lower triangle read), q / G as above (Qi is formed from them again; dq must equal D).  Per step a Cholesky
+ * factorisation of J_{j-1} + D11_j and one of J_j.  Outputs, each may be NULL: info [T][D*D] J_j, bound [T][D*D] J_j^-1 (both symmetric,
+ * both triangles from one value), rmse_bound [T] sqrt(trace J_j^-1).  *status: 0, or 1 + j for the first step j with a non-finite sum
+ * or a non-positive pivot - the outputs of the steps before it stand, those from step j on are NaN; a P0 that is not positive definite
+ * is status 1.  Returns SSMQ_OK also then; SSMQ_E_ARG / SSMQ_E_UNSUPPORTED for the arguments as ssmq_pcrlb_sums_dev. */
+int ssmq_pcrlb_finalize(int D, int T, int64_t B_total, const double *sums, const double *P0, const ssmq_rv *q, const double *G,
+                        double *info, double *bound, double *rmse_bound, int32_t *status);
 
 /*
  * The path's only collective: independent Monte-Carlo trajectories shard across ranks, one process per

@@ -31,6 +31,7 @@ F_CTRS_DYN, F_CV_DYN, F_REENTRY2D_BIAS_DYN, F_SMOOTH10D_DYN = 13, 14, 15, 16
 F_USER_FIRST, F_USER_SLOTS, USER_BODY_MAX, USER_MAX_D, USER_MAX_Y = 1024, 64, 8192, 6, 4
 RTC_FILTER, RTC_APPLY, RTC_MC, RTC_LINEAR, RTC_TAYLOR_GPQD, RTC_GPQD, RTC_INNOVATION, RTC_ITERATED = 0, 1, 2, 3, 4, 5, 6, 7
 RTC_SMOOTHER_ITERATED = 8
+RTC_PCRLB_DYN, RTC_PCRLB_OBS = 9, 10
 ITERATED_MAX = 64          # SSMQ_ITERATED_MAX
 ITERATED_LAUNCH_LOOP = 1   # flags bit 0 of ssmq_filter_iterated_dev
 
@@ -240,6 +241,14 @@ _PROTOTYPES = {
                                    [ctypes.c_void_p] * 13),
     'ssmq_particle_smoother_kernel_name': (ctypes.c_int, [ctypes.POINTER(Integrand), ctypes.c_int, ctypes.c_int, ctypes.c_int, c_double_p,
                                                           c_double_p, c_double_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_int]),
+    'ssmq_pcrlb_sums_width': (ctypes.c_int, [ctypes.c_int]),
+    'ssmq_pcrlb_sums_dev': (ctypes.c_int, [ctypes.POINTER(Integrand), ctypes.POINTER(Integrand), ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                           ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(Rv), c_double_p,
+                                           ctypes.POINTER(Rv), c_double_p]),
+    'ssmq_pcrlb_kernel_name': (ctypes.c_int, [ctypes.POINTER(Integrand), ctypes.POINTER(Integrand), ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                              ctypes.POINTER(Rv), c_double_p, ctypes.POINTER(Rv), ctypes.c_char_p, ctypes.c_int]),
+    'ssmq_pcrlb_finalize': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int64, c_double_p, c_double_p, ctypes.POINTER(Rv), c_double_p,
+                                           c_double_p, c_double_p, c_double_p, c_int32_p]),
     'ssmq_error_sums_width': (ctypes.c_int, [ctypes.c_int]),
     'ssmq_error_sums_dev': (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p,
                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_double_p]),

@@ -84,7 +84,10 @@ int pf_check(const char *what, const ssmq_integrand *f_dyn, const ssmq_integrand
     return SSMQ_OK;
 }
 
-// Largest and smallest eigenvalue of the symmetric n x n matrix A (row-major, n <= kPfMaxD) by cyclic Jacobi rotations.
+}  // namespace
+
+// Largest and smallest eigenvalue of the symmetric n x n matrix A (row-major, n <= kPfMaxD) by cyclic Jacobi rotations.  Also the
+// condition number ssmq_api_pcrlb.hip refuses by (declared in ssmq_pcrlb.h).
 void ps_eig_range(const double *A, int n, double *lo, double *hi) {
     double M[kPfMaxD * kPfMaxD];
     for (int i = 0; i < n * n; ++i) M[i] = A[i];
@@ -117,6 +120,8 @@ void ps_eig_range(const double *A, int n, double *lo, double *hi) {
         *hi = std::max(*hi, M[i * n + i]);
     }
 }
+
+namespace {
 
 // everything about a smoother call that can be decided without a device; fills the whitening data of the marginal method
 int ps_check(const char *what, const ssmq_integrand *f_dyn, int D, int dq, int N, const double *q_mean, const double *q_chol,

@@ -36,6 +36,8 @@
 #include "ssmq_mc_moments.h"
 #include "ssmq_jacobian_kernel.h"
 #include "ssmq_apply_gpqd_kernel.h"
+#include "ssmq_pcrlb.h"
+#include "ssmq_pcrlb_kernel.h"
 
 namespace ssmq {
 
@@ -706,6 +708,46 @@ int rtc_prepare_gpqd(const ssmq_transform *h, const ssmq_integrand *f) {
     return kernel_for(expr, "ssmq::GpqdArgs", ids, &fn);
 }
 
+// The posterior Cramer-Rao kernel of a user integrand that has a Jacobian: k_pcrlb_dyn_fn<id, D, DIN> (a D -> D transition) or
+// k_pcrlb_obs_fn<id, D, E, DIN> (ssmq_pcrlb_kernel.h); D <= 6, a measurement's E <= 4
+static int pcrlb_expr(bool dyn, int D, int E, const ssmq_integrand *f, std::string *expr, std::vector<int> *ids) {
+    const char *kernel = dyn ? "k_pcrlb_dyn_fn" : "k_pcrlb_obs_fn";
+    int rc = check_user_pair(f, f, ids);
+    if (rc) return rc;
+    UserFn u;
+    if (!user_fn(f->id, &u)) {
+        set_error("integrand id " + std::to_string(f->id) + " is not a registered user integrand");
+        return SSMQ_E_ARG;
+    }
+    if (u.jac.empty()) {
+        set_error(std::string(kernel) + ": this model has no Jacobian (a user integrand gets one through ssmq_integrand_define_dx)");
+        return SSMQ_E_UNSUPPORTED;
+    }
+    if (D < 1 || D > kPcrlbMaxD || E < 1 || (dyn ? E != D : E > kPcrlbMaxY)) {
+        set_error(std::string(kernel) + ": user integrands run for D <= " + std::to_string(kPcrlbMaxD) + (dyn ? " and D outputs" : " and outputs <= " +
+                  std::to_string(kPcrlbMaxY)) + " (got D = " + std::to_string(D) + ", E = " + std::to_string(E) + ")");
+        return SSMQ_E_UNSUPPORTED;
+    }
+    if (u.dout != E || u.din > D) {
+        set_error(std::string(kernel) + ": the user integrand's input / output dimensions do not match the model");
+        return SSMQ_E_ARG;
+    }
+    char b[160];
+    if (dyn) snprintf(b, sizeof(b), "ssmq::k_pcrlb_dyn_fn<%d, %d, %d>", f->id, D, u.din);
+    else snprintf(b, sizeof(b), "ssmq::k_pcrlb_obs_fn<%d, %d, %d, %d>", f->id, D, E, u.din);
+    *expr = b;
+    return SSMQ_OK;
+}
+int rtc_launch_pcrlb(bool dyn, const ssmq_integrand *f, const PcrlbArgs &a0, unsigned grid, hipStream_t s, const char **name, bool dry_run) {
+    std::string expr;
+    std::vector<int> ids;
+    const int rc = pcrlb_expr(dyn, a0.lin.D, a0.lin.E, f, &expr, &ids);
+    if (rc) return rc;
+    PcrlbArgs a = a0;
+    a.lin.fp.ttab = nullptr;
+    return launch_compiled(expr, "ssmq::PcrlbArgs", ids, &a, grid, kPcrlbBlock, s, name, dry_run, dyn ? "k_pcrlb_dyn_fn" : "k_pcrlb_obs_fn");
+}
+
 // k_mc_moments<> for a user integrand (ssmq_mc_transform.hip has checked the range and filled `a0`): SSMQ_OK launched, or < 0
 int rtc_launch_mc(const ssmq_integrand *f, int D, int E, const McMomArgs &a0, unsigned grid, hipStream_t s) {
     char b[128];
@@ -829,6 +871,20 @@ extern "C" int ssmq_rtc_compile_check(int32_t id, int32_t id_obs, int kind, int 
         int rc = gpqd_expr(D, E, D > kGpqdRegMaxD, &f, &expr, &ids);
         if (rc) return rc;
         return compile_check_text(expr, "ssmq::GpqdArgs", ids, arch, log, len);
+    }
+    if (kind == SSMQ_RTC_PCRLB_DYN || kind == SSMQ_RTC_PCRLB_OBS) {   // k_pcrlb_dyn_fn<id, D, DIN> / k_pcrlb_obs_fn<id, D, E, DIN>
+        if (!arch || !*arch) {
+            set_error("ssmq_rtc_compile_check: bad argument");
+            return SSMQ_E_ARG;
+        }
+        ssmq_integrand f;
+        memset(&f, 0, sizeof(f));
+        f.id = id;
+        std::string expr;
+        std::vector<int> ids;
+        int rc = pcrlb_expr(kind == SSMQ_RTC_PCRLB_DYN, D, kind == SSMQ_RTC_PCRLB_DYN ? D : E, &f, &expr, &ids);   // (a transition: D outputs)
+        if (rc) return rc;
+        return compile_check_text(expr, "ssmq::PcrlbArgs", ids, arch, log, len);
     }
     if (kind == SSMQ_RTC_MC) {   // k_mc_moments<id, D, E, 0>: N, N_obs, form, tp and opt are not read
         FInfo fm;

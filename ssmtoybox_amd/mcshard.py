@@ -404,6 +404,85 @@ def device_score_bars(D, B, ld, T, d_x, d_fm, d_fP, d_status=None, samples=10000
             for r, nm in enumerate(names)}
 
 
+# ---------------------------------------------------------------------------------------------------------------
+# posterior Cramer-Rao lower bound: the floor of a filter study (include/ssmq.h ssmq_pcrlb_sums_dev / ssmq_pcrlb_finalize)
+# ---------------------------------------------------------------------------------------------------------------
+def _crlb_check(rc, what):
+    """SSMQ_E_ARG is a ValueError, SSMQ_E_UNSUPPORTED a NotImplementedError that names the range, anything else as `_lib.check`."""
+    if rc == -1:
+        raise ValueError(_lib.last_error())
+    return _lib.check(rc, what, unsupported=True)
+
+
+def _crlb_noise(dyn):
+    """(q, G, keep): the process noise as struct ssmq_rv, the noise gain, and the arrays both point to."""
+    from .ssmod import _rv_desc
+    q, keep = _rv_desc(dyn.noise_rv, 'the process noise')
+    G = np.ascontiguousarray(dyn.noise_gain, dtype=np.float64)
+    return q, G, (keep, G)
+
+
+def _crlb_model_args(dyn, obs):
+    """The model part of the C calls: (f_dyn, f_obs, D, Y, dq, q, G, r) and what has to stay alive."""
+    from .ssmod import _rv_desc
+    f_dyn, _ = dyn.device_integrand()
+    f_obs, _ = obs.device_integrand()
+    q, G, keep_q = _crlb_noise(dyn)
+    r, keep_r = _rv_desc(obs.noise_rv, 'the measurement noise')
+    args = (ctypes.byref(f_dyn), ctypes.byref(f_obs), dyn.dim_state, obs.dim_out, int(q.dim), ctypes.byref(q), _lib.dp(G), ctypes.byref(r))
+    return args, (f_dyn, f_obs, q, r, keep_q, keep_r)
+
+
+def crlb_kernel_name(dyn, obs):
+    """The kernels `device_crlb_sums` would run for this pair: the library's range check without a device (NotImplementedError
+    naming the range, or ValueError)."""
+    args, keep = _crlb_model_args(dyn, obs)
+    buf = ctypes.create_string_buffer(512)
+    _crlb_check(_lib.load().ssmq_pcrlb_kernel_name(*args, buf, 512), 'ssmq_pcrlb_kernel_name')
+    return buf.value.decode()
+
+
+def device_crlb_sums(dyn, obs, d_x, B, ld, T):
+    """Phase-1 sums of the posterior Cramer-Rao recursion over this rank's B true trajectories (`ssmq_pcrlb_sums_dev`).
+    d_x: DeviceBuffer planes [T + 1][D][ld], the raw output of `ssmod.simulate_dev(dyn, obs, T + 1, B)` - plane 0 the initial state,
+    plane j + 1 the state the filters call x_j.  Returns an ndarray (T, S), S = D (D + 1) / 2 + D D + D (D + 1) / 2: per step the sums
+    over the trajectories of F' Qi F (lower triangle, packed), F and H' Ri H (lower triangle, packed).  Sums, not means: add the arrays
+    of all ranks (`allreduce_sums` takes the array unchanged), then `finalize_crlb`.  The bits depend on B and the states alone."""
+    lib = _lib.load()
+    args, keep = _crlb_model_args(dyn, obs)
+    D = dyn.dim_state
+    S = lib.ssmq_pcrlb_sums_width(D)
+    sums, ps = _lib.out_c((max(int(T), 0), max(S, 0)))
+    _crlb_check(lib.ssmq_pcrlb_sums_dev(*args[:5], B, ld, T, _lib.vp(d_x), *args[5:], ps), 'ssmq_pcrlb_sums_dev')
+    return sums
+
+
+def finalize_crlb(sums, dyn, B_total):
+    """The recursion J_j = D22_j - D12_j' (J_{j-1} + D11_j)^-1 D12_j, J_{-1} = P0^-1, from the all-reduced sums of B_total trajectories
+    (`ssmq_pcrlb_finalize`; host, no device).  Returns a dict: info (D, D, T) the information matrices J_j, bound (D, D, T) their
+    inverses - the lower bound of every filter's error covariance at step j -, rmse_bound (T,) = sqrt(trace bound), and status: 0, or
+    1 + the first step with a non-finite sum or a matrix that is not positive definite (NaN from that step on)."""
+    from .ssmod import GaussRV
+    if not isinstance(dyn.init_rv, GaussRV):
+        raise NotImplementedError('finalize_crlb: not implemented for a {} initial state; range: additive Gaussian noise, a GaussRV initial '
+                                  'state, dim_state <= 6'.format(type(dyn.init_rv).__name__))
+    sums = np.ascontiguousarray(sums, dtype=np.float64)
+    D = dyn.dim_state
+    if sums.ndim != 2 or sums.shape[0] < 1 or sums.shape[1] != D * (D + 1) + D * D:
+        raise ValueError('finalize_crlb: sums must have shape (T >= 1, {}), got {}'.format(D * (D + 1) + D * D, sums.shape))
+    T = sums.shape[0]
+    P0, pP0 = _lib.as_c(np.atleast_2d(dyn.init_rv.cov))
+    q, G, keep = _crlb_noise(dyn)
+    info, pi = _lib.out_c((T, D, D))
+    bound, pb = _lib.out_c((T, D, D))
+    rmse, pr = _lib.out_c((T,))
+    status = ctypes.c_int32(0)
+    _crlb_check(_lib.load().ssmq_pcrlb_finalize(D, T, int(B_total), _lib.dp(sums), pP0, ctypes.byref(q), _lib.dp(G), pi, pb, pr,
+                                                ctypes.byref(status)), 'ssmq_pcrlb_finalize')
+    return dict(info=np.ascontiguousarray(info.transpose(1, 2, 0)), bound=np.ascontiguousarray(bound.transpose(1, 2, 0)), rmse_bound=rmse,
+                status=int(status.value))
+
+
 def _pack(sums, keys):
     return np.concatenate([np.asarray(sums[k], dtype=np.float64).reshape(-1) for k in keys])
 
@@ -419,8 +498,10 @@ def _unpack(flat, sums, keys):
 
 def allreduce_sums(sums, comm=None):
     """Sum a dict of arrays over all ranks with ONE all-reduce of the packed buffer.  comm: RcclComm / TorchComm /
-    an initialised torch.distributed module / None (single process)."""
+    an initialised torch.distributed module / None (single process).  A bare ndarray (`device_crlb_sums`) is summed as it is."""
     comm = _as_comm(comm)
+    if isinstance(sums, np.ndarray):
+        return np.asarray(comm.allreduce_sum(sums.reshape(-1))).reshape(sums.shape)
     keys = sorted(sums)
     return _unpack(comm.allreduce_sum(_pack(sums, keys)), sums, keys)
 

@@ -1657,3 +1657,30 @@ for _name, _what in (('backward_pass', 'the RTS smoother (backward_pass)'), ('ba
                                'iterated_pass_batch', 'iterated_pass_dev', 'iterated_kernel_name', 'iterated_smoother',
                                'iterated_smoother_batch', 'iterated_smoother_dev', 'iterated_smoother_kernel_name')):
     setattr(BootstrapParticleFilter, _name, _refusing(_name, _what))
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# The floor of a filter study: the posterior Cramer-Rao lower bound (Tichavsky, Muravchik, Nehorai 1998) from the true states
+# ---------------------------------------------------------------------------------------------------------------
+def posterior_crlb_dev(dyn, obs, d_x, B, ld, T):
+    """The bound from true states that are already on the device: d_x planes [T + 1][dim_state][ld], the raw output of
+    `ssmod.simulate_dev(dyn, obs, T + 1, B)` (plane 0 the initial state, plane j + 1 the state the filters call x_j).  One process:
+    `mcshard.device_crlb_sums` then `mcshard.finalize_crlb`, whose dict it returns - info (D, D, T), bound (D, D, T) with
+    E[(x_j - m_j)(x_j - m_j)'] >= bound[:, :, j] for every estimator m_j of x_j from y_0 .. y_j, rmse_bound (T,) = sqrt(trace bound),
+    status.  Additive Gaussian noise, models with a Jacobian on the device (the built-in ones that have one, user models with
+    `device_jacobian`), dim_state <= 6, dim_out <= 4, process noise of full rank; NotImplementedError names the range otherwise."""
+    from . import mcshard
+    return mcshard.finalize_crlb(mcshard.device_crlb_sums(dyn, obs, d_x, B, ld, T), dyn, B)
+
+
+def posterior_crlb(dyn, obs, x):
+    """`posterior_crlb_dev` for true states on the host: x (dim_state, T + 1, B), x[:, 0] the initial states."""
+    x = np.asarray(x, dtype=np.float64)
+    if x.ndim != 3 or x.shape[0] != dyn.dim_state or x.shape[1] < 2:
+        raise ValueError('posterior_crlb: x must have shape (dim_state = {}, T + 1 >= 2, B), got {}'.format(dyn.dim_state, x.shape))
+    D, T1, B = x.shape
+    ld = _lib.padded(B)
+    with _lib.Staging() as stage:
+        d_x = stage.device(8 * T1 * D * ld)
+        _lib.upload_study(x, D, ld, d_x)
+        return posterior_crlb_dev(dyn, obs, d_x, B, ld, T1 - 1)
