@@ -103,11 +103,18 @@ struct CoreParams {
 #define SSMQ_OPT_UT 2
 #define SSMQ_OPT_SYM 4
 
+// Who evaluates the integrand at the N points of a transform.  The default: this lane, all of them, inside moment_transform_core<>.
+// A type with kDealt = true brings the values itself - values(fn, m, L, fx) fills fx[e][n] = f_e(m + L xi_n) - and every sum
+// after them is the same code on the same values (QuadScalarPoints, ssmq_quad.h: the points dealt to the lanes of a quad).
+struct PointsPerLane {
+    static constexpr bool kDealt = false;
+};
+
 // m: mean; L: in = packed lower triangle of cov, out = its Cholesky factor.  Returns false if cov is not PD (results
 // are then garbage; the caller writes NaN).  Sink interface: mean(e, v), cov(e, e2, v) for e2 <= e, ccov(e, d, v).
-template <int D, int E, int N, int F, int FORM, int TP, int SEL, bool NEED_CCOV, int OPT, class Sink>
+template <int D, int E, int N, int F, int FORM, int TP, int SEL, bool NEED_CCOV, int OPT, class Sink, class Points = PointsPerLane>
 __device__ __forceinline__ bool moment_transform_core(const double (&m)[D], double (&L)[D * (D + 1) / 2], double t,
-                                                      const FPar &fp, const CoreParams &cp, Sink &out) {
+                                                      const FPar &fp, const CoreParams &cp, Sink &out, const Points &pts = Points()) {
     constexpr ConstLayout cl = const_layout(D, E, N, FORM);
     using Fun = Fn<F>;
     constexpr int DIN = Fun::DIN;
@@ -128,6 +135,7 @@ __device__ __forceinline__ bool moment_transform_core(const double (&m)[D], doub
     constexpr bool kUT = (OPT & SSMQ_OPT_UT) != 0 && N == 2 * D + 1;
     const double utc = kUT ? c[cl.utc] : 0.0;
     constexpr bool kSYM = (OPT & SSMQ_OPT_SYM) != 0 && kUT && FORM == SSMQ_FORM_BQ && !TP;
+    static_assert(!(Points::kDealt && kSYM), "moment_transform_core: the pair form evaluates its own points");
     double mf[E];
     if constexpr (kSYM) {
         // ---- reflection-symmetric weights (SSMQ_OPT_SYM): ONE pass over the centre point and the D point pairs -----------------
@@ -254,8 +262,9 @@ __device__ __forceinline__ bool moment_transform_core(const double (&m)[D], doub
         sload(xic, c + cl.xi);
         SSMQ_SPIN_T(xic);
     }
+    if constexpr (Points::kDealt) pts.values(fn, m, L, fx);
 #pragma unroll
-    for (int n = 0; n < N; ++n) {
+    for (int n = 0; n < (Points::kDealt ? 0 : N); ++n) {
         SBuf<D> xin;
         if (!kUT && n + 1 < N) sload(xin, c + cl.xi + (n + 1) * D);
         double x[D];

@@ -28,13 +28,7 @@
 namespace ssmq {
 namespace {
 
-template <int CTRL>
-__device__ __forceinline__ double quad_perm(double v) {
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xF, 0xF, true);
-    hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xF, 0xF, true);
-    return __hiloint2double(hi, lo);
-}
+// (quad_perm<>, kQuadTraj: ssmq_quad.h)
 // sum over the four lanes of a quad, the same bits in all four: (v0 + v1) + (v2 + v3) in every lane (addition commutes)
 __device__ __forceinline__ double quad_sum(double v) {
     v += quad_perm<0xB1>(v);      // quad_perm:[1,0,3,2]
@@ -57,8 +51,6 @@ __device__ __forceinline__ void quad_sum_all(double (&v)[NV]) {
 #pragma unroll
     for (int i = 0; i < NV; ++i) v[i] += t[i];
 }
-
-constexpr int kQuadTraj = 16;     // trajectories per wave
 
 // One moment transform in the centred form on unscented points, the N = 2 DI + 1 points dealt to the quad's lanes.
 //   m, L: mean and Cholesky factor (packed lower) of the input, replicated; lds: this trajectory's record (DI x CS doubles);
@@ -346,7 +338,9 @@ const QuadEntry kQuad[] = {
 
 // 1: launched (dry_run: would be); 0: this filter / batch keeps its other routes; < 0: error.
 // Taken when the batch's whole-pass waves would each have a SIMD to themselves and the quad waves still do: ceil(B / 16) <= SIMDs
-// (B <= 16 384 on 256 compute units).  SSMQ_FUSED_QUAD=0 never, =1 for any batch (tests).
+// (B <= 16 384 on 256 compute units).  SSMQ_FUSED_QUAD=0 never, =1 for any batch (tests).  Two families under the one switch:
+//   k_filter_quad       centred form on unscented points, the heavy models of kQuad (results agree with k_filter_fused to rounding)
+//   k_filter_ungm_quad  scalar UNGM in BQ form, 2 / 3 / 5 points (ssmq_filter_ungm_quad.hip; the bits of k_filter_fused)
 int try_launch_quad(const FilterPass &p, int cus) {
     const ssmq_transform *hd = p.hd, *ho = p.ho;
     const char *ev = ssmq::sw("SSMQ_FUSED_QUAD");
@@ -354,12 +348,18 @@ int try_launch_quad(const FilterPass &p, int cus) {
     if (force == 0 || p.sscale || p.student_dof > 0.0 || p.B <= 0) return 0;
     if (!p.dry_run && ctx().no_strips) return 0;       // a job of a multi-filter launch shares the chip: whole-pass kernels only
     if (force != 1 && ssmq::sw("SSMQ_FUSED_WSPLIT")) return 0;          // a forced wave-split mode (0 = the register kernel) is what runs
-    if (!same_family(p) || hd->form != SSMQ_FORM_SIGMA || hd->tp_nu > 0.0) return 0;
+    if (!same_family(p)) return 0;
+    const int64_t waves = (p.B + kQuadTraj - 1) / kQuadTraj;
+    if (force != 1 && waves > 4 * (int64_t)cus) return 0;
+    // the scalar UNGM shapes in BQ form: only the dynamics integrand is dealt to the lanes, same bits as the one-lane kernel.
+    // Up to three quarters of the SIMDs (B <= 12 288): at 1 024 waves its margin over k_filter_fused (33.4 against 33.9 us) is
+    // inside the spread of its own blocks (32.6 - 35.0), at 768 it is not (31.4 against 32.7; profiles/r17_ungm_quad.txt)
+    if (force == 1 || waves <= 3 * (int64_t)cus)
+        if (const int ru = try_launch_ungm_quad(p, waves)) return ru;
+    if (hd->form != SSMQ_FORM_SIGMA || hd->tp_nu > 0.0) return 0;
     if (!(hd->opt_mask & ho->opt_mask & SSMQ_OPT_UT)) return 0;          // unscented-type points [0 | c I | -c I], verified on the host
     if (hd->N != 2 * hd->D + 1 || ho->N != hd->N || ho->D != hd->D || hd->E != hd->D) return 0;
     if ((int64_t)hd->D * hd->D * p.ld * 8 >= ((int64_t)1 << 32)) return 0;      // (the kernel's 32-bit store offsets inside one step's planes)
-    const int64_t waves = (p.B + kQuadTraj - 1) / kQuadTraj;
-    if (force != 1 && waves > 4 * (int64_t)cus) return 0;
     for (const QuadEntry &e : kQuad) {
         if (!(e.fd == p.fd->id && e.fo == p.fo->id && e.D == hd->D && e.Y == ho->E && e.selo == p.sel_obs)) continue;
         if (p.name) *p.name = e.name;

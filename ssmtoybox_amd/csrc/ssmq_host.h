@@ -514,6 +514,7 @@ inline FilterShape shape_of(const FilterPass &p, int opt) {
 // cus: compute units of the device)
 int try_launch_fused(const FilterPass &p);
 int try_launch_quad(const FilterPass &p, int cus);
+int try_launch_ungm_quad(const FilterPass &p, int64_t waves);      // (try_launch_quad's entry for the scalar UNGM shapes: ssmq_filter_ungm_quad.hip)
 int try_launch_wsplit(const FilterPass &p, int cus);
 int try_launch_chunked(const FusedArgs &a0, const FilterShape &shape, int cus, hipStream_t s, bool dry_run, const char **name);
 // ... for models that take their noise as an argument, and for the smoother (p.gqg / p.rr are not read)
