@@ -1151,6 +1151,43 @@ int ssmq_particle_smoother_kernel_name(const ssmq_integrand *f_dyn, int D, int d
                                        const double *G, int method, char *buf, int len);
 
 /*
+ * The particle filter and its smoothers with a heavy-tailed initial state and process noise: the four entry points above, except that
+ * the initial state x0 and the process noise q are described by ssmq_rv, as in ssmq_simulate_rv_dev.  Kinds: SSMQ_RV_GAUSS, or
+ * SSMQ_RV_STUDENT with one component - a draw is v = mean + chol z / sqrt(u), u ~ Gamma(dof / 2, scale 2 / dof), the construction of
+ * ssmq_simulate_rv_dev - in any combination of the two sides.
+ *   x0: only kind and dof are read.  The per-trajectory planes d_m0 / d_P0 keep their role: x_{-1,i} = m0_b + chol(P0_b) z / sqrt(u);
+ *       for a Student-t initial state d_P0 holds the SCALE matrix, not the covariance.
+ *   q:  kind, dim (= dq), n_comp (<= 1), dof, mean [dq] (NULL = 0) and chol [dq*dq], the lower factor of Q (Student-t: of the scale
+ *       matrix) - what q_mean / q_chol are above.
+ * Random numbers: z from the counters of ssmq_particle_filter_dev (purposes 8 and 9); u by Marsaglia-Tsang, one per particle and draw,
+ * attempt t = 0 .. 15 in the low four bits of the tag (the pair field): purpose 11 the normal and 12 the uniform of attempt t for the
+ * initial particle (step 0), 13 the normal and 14 the uniform for the process noise of step j.  No counter is used twice; a side that
+ * is Gaussian draws no u.  A trajectory's bits depend on seed, its global index, N, ess_threshold and its own inputs, as above.
+ * Smoothers: SSMQ_PS_GENEALOGY reads no density and is unchanged.  SSMQ_PS_MARGINAL with Student-t process noise of full rank (dq == D,
+ * G Q G' positive definite, Q the scale matrix): x_{k+1} | x_k is Student-t with location f(x_k, k + 1) + G q_mean, scale G Q G' and
+ * q's dof, so with the whitened d2_ij above  log p = const - (dof + D) / 2 log1p(d2_ij / dof)  takes the place of -d2_ij / 2 in both
+ * log-sum-exps (the constant cancels in the normalisation); everything else is the recursion above.
+ * With SSMQ_RV_GAUSS on both sides the entries launch the kernels of the four entry points above on the same arguments and return
+ * their bits; otherwise k_particle_filter<D, QK=1> / k_particle_smooth<D, QK=1>, the same mapping and LDS.
+ * Range: that of the entry points above, and SSMQ_RV_STUDENT with dof >= 2 (the Gamma sampler needs the shape dof / 2 >= 1):
+ * SSMQ_RV_MIXTURE for x0 or q and 0 < dof < 2 are SSMQ_E_UNSUPPORTED, the range named; a null descriptor, an unknown kind, q->dim != dq,
+ * q->n_comp > 1, a null q->chol, a dof that is not finite and positive SSMQ_E_ARG - before the device or an output is touched.
+ */
+int ssmq_particle_filter_rv_dev(const ssmq_integrand *f_dyn, const ssmq_integrand *f_obs, int D, int Y, int dq, int N, int64_t B,
+                                int64_t ld, int T, const double *d_y, const double *d_m0, const double *d_P0, const ssmq_rv *x0,
+                                const ssmq_rv *q, const double *G, const ssmq_rv *r, double ess_threshold, uint64_t seed,
+                                uint64_t traj_offset, double *d_fm, double *d_fP, double *d_loglik, double *d_ess, int32_t *d_status,
+                                double *d_part, double *d_logw, int32_t *d_anc);
+int ssmq_particle_kernel_name_rv(const ssmq_integrand *f_dyn, const ssmq_integrand *f_obs, int D, int Y, int dq, int N, const ssmq_rv *x0,
+                                 const ssmq_rv *q, const ssmq_rv *r, char *buf, int len);
+int ssmq_particle_smoother_rv_dev(const ssmq_integrand *f_dyn, int D, int dq, int N, int64_t B, int64_t ld, int T, const ssmq_rv *q,
+                                  const double *G, int method, const double *d_part, const double *d_logw, const int32_t *d_anc,
+                                  const double *d_fm, const double *d_fP, const double *d_ess, const int32_t *d_status, double *d_sm,
+                                  double *d_sP, double *d_ess_s, double *d_logw_s, int32_t *d_lineage, int32_t *d_unique);
+int ssmq_particle_smoother_kernel_name_rv(const ssmq_integrand *f_dyn, int D, int dq, int N, const ssmq_rv *q, const double *G, int method,
+                                          char *buf, int len);
+
+/*
  * Posterior Cramer-Rao lower bound (Tichavsky, Muravchik, Nehorai 1998) of the additive-Gaussian-noise models: the floor no filter of
  * a study can get under, E[(x_j - m_j)(x_j - m_j)'] >= J_j^-1 for every estimator m_j of x_j from y_0 .. y_j.  Input: the true states,
  * planes p_0 .. p_T as ssmq_simulate*_dev with T + 1 steps writes them (p_0 ~ the initial state, p_{j+1} the state the filters call x_j).

@@ -241,6 +241,18 @@ _PROTOTYPES = {
                                    [ctypes.c_void_p] * 13),
     'ssmq_particle_smoother_kernel_name': (ctypes.c_int, [ctypes.POINTER(Integrand), ctypes.c_int, ctypes.c_int, ctypes.c_int, c_double_p,
                                                           c_double_p, c_double_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_int]),
+    'ssmq_particle_filter_rv_dev': (ctypes.c_int, [ctypes.POINTER(Integrand), ctypes.POINTER(Integrand), ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                   ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int] + [ctypes.c_void_p] * 3 +
+                                    [ctypes.POINTER(Rv), ctypes.POINTER(Rv), c_double_p, ctypes.POINTER(Rv), ctypes.c_double, ctypes.c_uint64,
+                                     ctypes.c_uint64] + [ctypes.c_void_p] * 8),
+    'ssmq_particle_kernel_name_rv': (ctypes.c_int, [ctypes.POINTER(Integrand), ctypes.POINTER(Integrand), ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                    ctypes.c_int, ctypes.POINTER(Rv), ctypes.POINTER(Rv), ctypes.POINTER(Rv), ctypes.c_char_p,
+                                                    ctypes.c_int]),
+    'ssmq_particle_smoother_rv_dev': (ctypes.c_int, [ctypes.POINTER(Integrand), ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64,
+                                                     ctypes.c_int64, ctypes.c_int, ctypes.POINTER(Rv), c_double_p, ctypes.c_int] +
+                                      [ctypes.c_void_p] * 13),
+    'ssmq_particle_smoother_kernel_name_rv': (ctypes.c_int, [ctypes.POINTER(Integrand), ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                             ctypes.POINTER(Rv), c_double_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_int]),
     'ssmq_pcrlb_sums_width': (ctypes.c_int, [ctypes.c_int]),
     'ssmq_pcrlb_sums_dev': (ctypes.c_int, [ctypes.POINTER(Integrand), ctypes.POINTER(Integrand), ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                            ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(Rv), c_double_p,

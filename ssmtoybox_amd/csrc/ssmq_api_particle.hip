@@ -3,7 +3,8 @@
 // launch of k_particle_filter<D> (ssmq_particle.hip).  And of the particle smoothers over its cloud (ssmq_particle_smoother_dev,
 // ssmq_particle_smoother_kernel_name): the range check, the whitening data of the marginal smoother (the inverse factor of G Q G',
 // refused where the transition has no density) and the launch of k_particle_smooth<D> / k_particle_lineage<D>
-// (ssmq_particle_smooth.hip).
+// (ssmq_particle_smooth.hip).  The *_rv entry points describe the initial state and the process noise by ssmq_rv (Gaussian or
+// Student-t) and share everything else with the four above: all-Gaussian descriptors run the same kernels on the same arguments.
 #include <cmath>
 #include <cstdio>
 #include "ssmq_particle.h"
@@ -83,6 +84,41 @@ int pf_check(const char *what, const ssmq_integrand *f_dyn, const ssmq_integrand
         }
     return SSMQ_OK;
 }
+
+// One side (the initial state or the process noise) of the *_rv entry points: kind and dof, and with dim >= 0 also the dimension, the
+// component count and the factor.  *nu: 0 for Gaussian, the degrees of freedom for Student-t.
+int pf_rv_side(const char *what, const char *side, const ssmq_rv *v, int dim, double *nu) {
+    char msg[512];
+    const char *range = "SSMQ_RV_GAUSS or SSMQ_RV_STUDENT with one component and dof >= 2 (the Gamma sampler of the Student-t draws, "
+                        "Marsaglia-Tsang, needs the shape dof / 2 >= 1) for the initial state and the process noise";
+    if (!v) {
+        snprintf(msg, sizeof(msg), "%s: null descriptor of %s", what, side);
+        set_error(msg);
+        return SSMQ_E_ARG;
+    }
+    if (v->kind == SSMQ_RV_MIXTURE) {
+        snprintf(msg, sizeof(msg), "%s: not implemented for a Gaussian mixture as %s; range: %s", what, side, range);
+        set_error(msg);
+        return SSMQ_E_UNSUPPORTED;
+    }
+    if ((v->kind != SSMQ_RV_GAUSS && v->kind != SSMQ_RV_STUDENT) || (dim >= 0 && (v->dim != dim || v->n_comp > 1 || !v->chol)) ||
+        (v->kind == SSMQ_RV_STUDENT && !(v->dof > 0.0 && std::isfinite(v->dof)))) {
+        snprintf(msg, sizeof(msg), "%s: %s must be SSMQ_RV_GAUSS or SSMQ_RV_STUDENT (finite dof > 0)%s", what, side,
+                 dim >= 0 ? " of dimension dq with one component and a factor" : "");
+        set_error(msg);
+        return SSMQ_E_ARG;
+    }
+    if (v->kind == SSMQ_RV_STUDENT && v->dof < 2.0) {
+        snprintf(msg, sizeof(msg), "%s: dof = %g of %s is below 2; range: %s", what, v->dof, side, range);
+        set_error(msg);
+        return SSMQ_E_UNSUPPORTED;
+    }
+    *nu = v->kind == SSMQ_RV_STUDENT ? v->dof : 0.0;
+    return SSMQ_OK;
+}
+
+const char *pf_kernel_text(int qk) { return qk ? "k_particle_filter<D=%d, QK=1> (N = %d, %zu B of LDS per trajectory)"
+                                                 : "k_particle_filter<D=%d> (N = %d, %zu B of LDS per trajectory)"; }
 
 }  // namespace
 
@@ -249,25 +285,25 @@ extern "C" int ssmq_particle_kernel_name(const ssmq_integrand *f_dyn, const ssmq
     }
     int rc = pf_check("ssmq_particle_kernel_name", f_dyn, f_obs, D, Y, dq, N, r);
     if (rc) return rc;
-    snprintf(buf, (size_t)len, "k_particle_filter<D=%d> (N = %d, %zu B of LDS per trajectory)", D, N, pf_lds_bytes(D, N));
+    snprintf(buf, (size_t)len, pf_kernel_text(0), D, N, pf_lds_bytes(D, N));
     return SSMQ_OK;
 }
 
-extern "C" int ssmq_particle_filter_dev(const ssmq_integrand *f_dyn, const ssmq_integrand *f_obs, int D, int Y, int dq, int N, int64_t B,
-                                        int64_t ld, int T, const double *d_y, const double *d_m0, const double *d_P0,
-                                        const double *q_mean, const double *q_chol, const double *G, const ssmq_rv *r,
-                                        double ess_threshold, uint64_t seed, uint64_t traj_offset, double *d_fm, double *d_fP,
-                                        double *d_loglik, double *d_ess, int32_t *d_status, double *d_part, double *d_logw,
-                                        int32_t *d_anc) {
-    int rc = pf_check("ssmq_particle_filter_dev", f_dyn, f_obs, D, Y, dq, N, r);
-    if (rc) return rc;
+// the pass of both filter entry points after their range checks (nu0, nuq: 0 = Gaussian)
+static int pf_run(const char *what, const ssmq_integrand *f_dyn, const ssmq_integrand *f_obs, int D, int Y, int dq, int N, int64_t B,
+                  int64_t ld, int T, const double *d_y, const double *d_m0, const double *d_P0, const double *q_mean, const double *q_chol,
+                  double nu0, double nuq, const double *G, const ssmq_rv *r, double ess_threshold, uint64_t seed, uint64_t traj_offset,
+                  double *d_fm, double *d_fP, double *d_loglik, double *d_ess, int32_t *d_status, double *d_part, double *d_logw,
+                  int32_t *d_anc) {
+    int rc;
     if (T < 1 || B < 0 || ld < B || B > 0x7fffffff || !d_y || !d_m0 || !d_P0 || !q_chol || !d_fm || !d_fP || !d_loglik || !d_ess || !d_status ||
         ess_threshold != ess_threshold) {
-        set_error("ssmq_particle_filter_dev: bad argument (T >= 1, 0 <= B <= ld, non-null buffers and q_chol, ess_threshold not NaN)");
+        set_error(std::string(what) + ": bad argument (T >= 1, 0 <= B <= ld, non-null buffers and q_chol, ess_threshold not NaN)");
         return SSMQ_E_ARG;
     }
     PfLaunch h;
     memset(&h, 0, sizeof(h));
+    h.nu0 = nu0; h.nuq = nuq;
     h.f_dyn = f_dyn; h.f_obs = f_obs; h.D = D; h.Y = Y; h.dq = dq; h.N = N; h.T = T; h.B = B; h.ld = ld; h.seed = seed;
     h.traj_offset = traj_offset; h.ess_threshold = ess_threshold;
     for (int i = 0; i < dq; ++i) {
@@ -302,6 +338,47 @@ extern "C" int ssmq_particle_filter_dev(const ssmq_integrand *f_dyn, const ssmq_
     return SSMQ_OK;
 }
 
+extern "C" int ssmq_particle_filter_dev(const ssmq_integrand *f_dyn, const ssmq_integrand *f_obs, int D, int Y, int dq, int N, int64_t B,
+                                        int64_t ld, int T, const double *d_y, const double *d_m0, const double *d_P0,
+                                        const double *q_mean, const double *q_chol, const double *G, const ssmq_rv *r,
+                                        double ess_threshold, uint64_t seed, uint64_t traj_offset, double *d_fm, double *d_fP,
+                                        double *d_loglik, double *d_ess, int32_t *d_status, double *d_part, double *d_logw,
+                                        int32_t *d_anc) {
+    int rc = pf_check("ssmq_particle_filter_dev", f_dyn, f_obs, D, Y, dq, N, r);
+    if (rc) return rc;
+    return pf_run("ssmq_particle_filter_dev", f_dyn, f_obs, D, Y, dq, N, B, ld, T, d_y, d_m0, d_P0, q_mean, q_chol, 0.0, 0.0, G, r,
+                  ess_threshold, seed, traj_offset, d_fm, d_fP, d_loglik, d_ess, d_status, d_part, d_logw, d_anc);
+}
+
+extern "C" int ssmq_particle_kernel_name_rv(const ssmq_integrand *f_dyn, const ssmq_integrand *f_obs, int D, int Y, int dq, int N,
+                                            const ssmq_rv *x0, const ssmq_rv *q, const ssmq_rv *r, char *buf, int len) {
+    if (!buf || len < 1) {
+        set_error("ssmq_particle_kernel_name_rv: null buffer");
+        return SSMQ_E_ARG;
+    }
+    double nu0 = 0.0, nuq = 0.0;
+    int rc = pf_check("ssmq_particle_kernel_name_rv", f_dyn, f_obs, D, Y, dq, N, r);
+    if (!rc) rc = pf_rv_side("ssmq_particle_kernel_name_rv", "the initial state", x0, -1, &nu0);
+    if (!rc) rc = pf_rv_side("ssmq_particle_kernel_name_rv", "the process noise", q, dq, &nuq);
+    if (rc) return rc;
+    snprintf(buf, (size_t)len, pf_kernel_text(pf_noise_kind(nu0, nuq)), D, N, pf_lds_bytes(D, N));
+    return SSMQ_OK;
+}
+
+extern "C" int ssmq_particle_filter_rv_dev(const ssmq_integrand *f_dyn, const ssmq_integrand *f_obs, int D, int Y, int dq, int N, int64_t B,
+                                           int64_t ld, int T, const double *d_y, const double *d_m0, const double *d_P0,
+                                           const ssmq_rv *x0, const ssmq_rv *q, const double *G, const ssmq_rv *r, double ess_threshold,
+                                           uint64_t seed, uint64_t traj_offset, double *d_fm, double *d_fP, double *d_loglik,
+                                           double *d_ess, int32_t *d_status, double *d_part, double *d_logw, int32_t *d_anc) {
+    double nu0 = 0.0, nuq = 0.0;
+    int rc = pf_check("ssmq_particle_filter_rv_dev", f_dyn, f_obs, D, Y, dq, N, r);
+    if (!rc) rc = pf_rv_side("ssmq_particle_filter_rv_dev", "the initial state", x0, -1, &nu0);
+    if (!rc) rc = pf_rv_side("ssmq_particle_filter_rv_dev", "the process noise", q, dq, &nuq);
+    if (rc) return rc;
+    return pf_run("ssmq_particle_filter_rv_dev", f_dyn, f_obs, D, Y, dq, N, B, ld, T, d_y, d_m0, d_P0, q->mean, q->chol, nu0, nuq, G, r,
+                  ess_threshold, seed, traj_offset, d_fm, d_fP, d_loglik, d_ess, d_status, d_part, d_logw, d_anc);
+}
+
 extern "C" int ssmq_particle_smoother_kernel_name(const ssmq_integrand *f_dyn, int D, int dq, int N, const double *q_mean,
                                                   const double *q_chol, const double *G, int method, char *buf, int len) {
     if (!buf || len < 1) {
@@ -317,18 +394,14 @@ extern "C" int ssmq_particle_smoother_kernel_name(const ssmq_integrand *f_dyn, i
     return SSMQ_OK;
 }
 
-extern "C" int ssmq_particle_smoother_dev(const ssmq_integrand *f_dyn, int D, int dq, int N, int64_t B, int64_t ld, int T,
-                                          const double *q_mean, const double *q_chol, const double *G, int method, const double *d_part,
-                                          const double *d_logw, const int32_t *d_anc, const double *d_fm, const double *d_fP,
-                                          const double *d_ess, const int32_t *d_status, double *d_sm, double *d_sP, double *d_ess_s,
-                                          double *d_logw_s, int32_t *d_lineage, int32_t *d_unique) {
-    PsLaunch h;
-    memset(&h, 0, sizeof(h));
-    int rc = ps_check("ssmq_particle_smoother_dev", f_dyn, D, dq, N, q_mean, q_chol, G, method, &h);
-    if (rc) return rc;
+// the pass of both smoother entry points after their range checks (h: what ps_check filled, and nuq)
+static int ps_run(const char *what, PsLaunch &h, int method, int64_t B, int64_t ld, int T, const double *d_part, const double *d_logw,
+                  const int32_t *d_anc, const double *d_fm, const double *d_fP, const double *d_ess, const int32_t *d_status, double *d_sm,
+                  double *d_sP, double *d_ess_s, double *d_logw_s, int32_t *d_lineage, int32_t *d_unique) {
+    int rc;
     if (T < 1 || B < 0 || ld < B || B > 0x7fffffff || !d_part || !d_logw || !d_fm || !d_fP || !d_ess || !d_status || !d_sm || !d_sP ||
         !d_ess_s || (method == SSMQ_PS_GENEALOGY && !d_anc)) {
-        set_error("ssmq_particle_smoother_dev: bad argument (T >= 1, 0 <= B <= ld, non-null buffers; d_anc for SSMQ_PS_GENEALOGY)");
+        set_error(std::string(what) + ": bad argument (T >= 1, 0 <= B <= ld, non-null buffers; d_anc for SSMQ_PS_GENEALOGY)");
         return SSMQ_E_ARG;
     }
     h.T = T; h.B = B; h.ld = ld;
@@ -345,4 +418,57 @@ extern "C" int ssmq_particle_smoother_dev(const ssmq_integrand *f_dyn, int D, in
     if (rc) return rc;
     SSMQ_HIP(e);
     return SSMQ_OK;
+}
+
+extern "C" int ssmq_particle_smoother_dev(const ssmq_integrand *f_dyn, int D, int dq, int N, int64_t B, int64_t ld, int T,
+                                          const double *q_mean, const double *q_chol, const double *G, int method, const double *d_part,
+                                          const double *d_logw, const int32_t *d_anc, const double *d_fm, const double *d_fP,
+                                          const double *d_ess, const int32_t *d_status, double *d_sm, double *d_sP, double *d_ess_s,
+                                          double *d_logw_s, int32_t *d_lineage, int32_t *d_unique) {
+    PsLaunch h;
+    memset(&h, 0, sizeof(h));
+    int rc = ps_check("ssmq_particle_smoother_dev", f_dyn, D, dq, N, q_mean, q_chol, G, method, &h);
+    if (rc) return rc;
+    return ps_run("ssmq_particle_smoother_dev", h, method, B, ld, T, d_part, d_logw, d_anc, d_fm, d_fP, d_ess, d_status, d_sm, d_sP, d_ess_s,
+                  d_logw_s, d_lineage, d_unique);
+}
+
+// the range check of both *_rv smoother entry points: ps_check on the descriptor's mean and factor, and its degrees of freedom
+static int ps_check_rv(const char *what, const ssmq_integrand *f_dyn, int D, int dq, int N, const ssmq_rv *q, const double *G, int method,
+                       PsLaunch *h) {
+    double nuq = 0.0;
+    int rc = pf_rv_side(what, "the process noise", q, dq >= 1 ? dq : -1, &nuq);
+    if (!rc) rc = ps_check(what, f_dyn, D, dq, N, q->mean, q->chol, G, method, h);
+    if (rc) return rc;
+    h->nuq = method == SSMQ_PS_MARGINAL ? nuq : 0.0;
+    return SSMQ_OK;
+}
+
+extern "C" int ssmq_particle_smoother_kernel_name_rv(const ssmq_integrand *f_dyn, int D, int dq, int N, const ssmq_rv *q, const double *G,
+                                                     int method, char *buf, int len) {
+    if (!buf || len < 1) {
+        set_error("ssmq_particle_smoother_kernel_name_rv: null buffer");
+        return SSMQ_E_ARG;
+    }
+    PsLaunch h;
+    memset(&h, 0, sizeof(h));
+    int rc = ps_check_rv("ssmq_particle_smoother_kernel_name_rv", f_dyn, D, dq, N, q, G, method, &h);
+    if (rc) return rc;
+    snprintf(buf, (size_t)len, "%s<D=%d%s> (N = %d, %zu B of LDS per trajectory)",
+             method == SSMQ_PS_MARGINAL ? "k_particle_smooth" : "k_particle_lineage", D, h.nuq > 0.0 ? ", QK=1" : "", N,
+             ps_lds_bytes(method, D, N));
+    return SSMQ_OK;
+}
+
+extern "C" int ssmq_particle_smoother_rv_dev(const ssmq_integrand *f_dyn, int D, int dq, int N, int64_t B, int64_t ld, int T,
+                                             const ssmq_rv *q, const double *G, int method, const double *d_part, const double *d_logw,
+                                             const int32_t *d_anc, const double *d_fm, const double *d_fP, const double *d_ess,
+                                             const int32_t *d_status, double *d_sm, double *d_sP, double *d_ess_s, double *d_logw_s,
+                                             int32_t *d_lineage, int32_t *d_unique) {
+    PsLaunch h;
+    memset(&h, 0, sizeof(h));
+    int rc = ps_check_rv("ssmq_particle_smoother_rv_dev", f_dyn, D, dq, N, q, G, method, &h);
+    if (rc) return rc;
+    return ps_run("ssmq_particle_smoother_rv_dev", h, method, B, ld, T, d_part, d_logw, d_anc, d_fm, d_fP, d_ess, d_status, d_sm, d_sP,
+                  d_ess_s, d_logw_s, d_lineage, d_unique);
 }

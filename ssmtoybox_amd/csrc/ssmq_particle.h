@@ -2,6 +2,7 @@
 // smoothers over its cloud (ssmq_particle_smooth.hip: k_particle_smooth<D>, k_particle_lineage<D>; ssmq_particle_smoother_dev): what
 // the entry points hand the launchers.  Host arrays are padded to the kernels' fixed strides so that the kernels index them statically.
 #pragma once
+#include <cmath>
 #include "ssmq_host.h"
 
 namespace ssmq {
@@ -19,6 +20,7 @@ struct PfLaunch {
     int64_t B, ld;
     uint64_t seed, traj_offset;
     double ess_threshold, lognorm, dof;                     // lognorm: the measurement density's log-normaliser
+    double nu0, nuq;                                        // degrees of freedom of a Student-t initial state / process noise, 0 = Gaussian
     double qm[kPfMaxQ], Lq[kPfMaxQ * kPfMaxQ], G[kPfMaxD * kPfMaxQ], rm[kPfMaxY], Lr[kPfMaxY * kPfMaxY];   // zero-padded; Lr: unit diagonal
     const double *y, *m0, *P0;
     double *fm, *fP, *ll, *ess;
@@ -31,6 +33,11 @@ struct PfLaunch {
 inline bool pf_shape_ok(int D, int Y, int dq, int N) {
     return D >= 1 && D <= kPfMaxD && Y >= 1 && Y <= kPfMaxY && dq >= 1 && dq <= kPfMaxQ && N <= kPfMaxN && (2 * D + 1) * N <= kPfCloudDoubles;
 }
+// the degrees of freedom of a Student-t initial state or process noise: 0 (Gaussian) or at least 2, the range of the Gamma sampler
+// (Marsaglia-Tsang, shape nu / 2 >= 1)
+inline bool pf_dof_ok(double nu) { return nu == 0.0 || (nu >= 2.0 && nu < INFINITY); }
+// the kernels' compile-time noise kind QK: 1 where either of the two is Student-t
+inline int pf_noise_kind(double nu0, double nuq) { return (nu0 > 0.0 || nuq > 0.0) ? 1 : 0; }
 inline size_t pf_lds_bytes(int D, int N) { return sizeof(double) * ((size_t)(2 * D + 1) * N + kPfRedDoubles); }
 int launch_particle_filter(const PfLaunch &h, hipStream_t s);
 
@@ -38,6 +45,7 @@ int launch_particle_filter(const PfLaunch &h, hipStream_t s);
 struct PsLaunch {
     const ssmq_integrand *f_dyn;
     int D, N, T, method;                                    // method: SSMQ_PS_MARGINAL or SSMQ_PS_GENEALOGY
+    double nuq;                                             // marginal: degrees of freedom of Student-t process noise, 0 = Gaussian
     int64_t B, ld;
     double Li[kPfMaxD * kPfMaxD], gq[kPfMaxD];              // marginal: inverse of chol(G Q G') (lower, zero-padded), G q_mean
     const double *part, *logw, *fm, *fP, *ess;

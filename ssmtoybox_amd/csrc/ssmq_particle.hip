@@ -20,7 +20,17 @@
 // purpose 8: initial particles (step 0), 9: process noise of step j, 10: the resampling uniform of step j (particle 0, pair 0).  The
 // simulator's tags are purpose << 16 | .. with purpose <= 2, all below 1 << 28.
 //
-// Model dispatch is the run-time eval_integrand of ssmq_device.h, as in k_simulate; the kernel is instantiated over D alone.
+// Noise kind QK (compile time): 0 - Gaussian initial state and process noise, the kernel as it always was; 1 - either of the two may be
+// a multivariate Student-t, v = mean + L z / sqrt(u), u ~ Gamma(nu / 2, scale 2 / nu) (sample_rv of ssmq_simulate.hip), z from the
+// counters above and u by gamma_mt_tags (ssmq_rng.h), one u per particle and draw, its attempt t = 0 .. 15 in the low four bits (the
+// pair field) of
+//     purpose 11: the normal, 12: the uniform of attempt t for the initial particle (step 0)
+//     purpose 13: the normal, 14: the uniform of attempt t for the process noise of step j
+// so no counter is used twice: (step, purpose, particle, low four bits) names one draw, the purposes 8 .. 14 are disjoint, and 0 .. 7 and
+// 15 stay free.  A side that is Gaussian (nu = 0 in the launch) draws no u and takes the factor 1 - decided per launch, the same in every
+// thread.  A rejected attempt diverges inside a wave and nowhere else: the result is a function of the counters alone.
+//
+// Model dispatch is the run-time eval_integrand of ssmq_device.h, as in k_simulate; the kernel is instantiated over D and QK.
 #include <cmath>
 #include "ssmq_particle.h"
 #include "ssmq_rng.h"
@@ -40,9 +50,11 @@ struct PfArgs {
     double *part, *logw;
     int32_t *anc;
     FPar fd, fo;
+    double nu0, nuq;                       // QK = 1: degrees of freedom of the initial state / the process noise, 0 = Gaussian
 };
 
 constexpr uint32_t kPfInit = 8u << 28, kPfNoise = 9u << 28, kPfResample = 10u << 28;
+constexpr uint32_t kPfInitGammaN = 11u << 28, kPfInitGammaU = 12u << 28, kPfNoiseGammaN = 13u << 28, kPfNoiseGammaU = 14u << 28;
 
 // the n <= M leading standard normals of (trajectory, step, purpose, particle); the rest zero
 template <int M>
@@ -61,9 +73,20 @@ __device__ __forceinline__ void pf_normals(const PfArgs &a, uint64_t traj, uint3
     }
 }
 
+// 1 / sqrt(u), u ~ Gamma(nu / 2, scale 2 / nu), of (trajectory, step, particle): the factor on L z of a Student-t draw
+__device__ __forceinline__ double pf_t_factor(const PfArgs &a, uint64_t traj, uint32_t step, uint32_t tag_normal, uint32_t tag_uniform,
+                                              uint32_t particle, double nu) {
+#ifndef SSMQ_PF_NO_RNG
+    const double g = gamma_mt_tags(a.seed, traj, step, tag_normal | (particle << 4), tag_uniform | (particle << 4), 0.5 * nu) * (2.0 / nu);
+    return 1.0 / sqrt(g);
+#else
+    return 1.0;
+#endif
+}
+
 // pf_block_sum / pf_block_max (ssmq_particle.h): the sums and the maximum over the workgroup in the order stated at the top
 
-template <int D>
+template <int D, int QK>
 __global__ __launch_bounds__(kPfBlock) void k_particle_filter(const PfArgs a) {
     extern __shared__ __align__(16) double lds[];
     const int N = a.N, Y = a.Y, T = a.T, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -89,11 +112,16 @@ __global__ __launch_bounds__(kPfBlock) void k_particle_filter(const PfArgs a) {
         for (int i = tid; i < N; i += kPfBlock) {
             double z[D];
             pf_normals<D>(a, traj, 0u, kPfInit, (uint32_t)i, D, z);
+            double sc = 1.0;
+            if constexpr (QK == 1) {
+                if (a.nu0 > 0.0) sc = pf_t_factor(a, traj, 0u, kPfInitGammaN, kPfInitGammaU, (uint32_t)i, a.nu0);
+            }
 #pragma unroll
             for (int d = 0; d < D; ++d) {
                 double s = 0.0;
 #pragma unroll
                 for (int k = 0; k <= d; ++k) s += L[d * D + k] * z[k];
+                if constexpr (QK == 1) s *= sc;
                 xa[d * N + i] = m0[d] + s;
             }
             w[i] = log_unif;
@@ -122,11 +150,16 @@ __global__ __launch_bounds__(kPfBlock) void k_particle_filter(const PfArgs a) {
             for (int d = 0; d < D; ++d) o[d] = 0.9 * xs[d];          // timing variant: no model evaluation
 #endif
             pf_normals<kPfMaxQ>(a, traj, (uint32_t)j, kPfNoise, (uint32_t)i, a.dq, z);
+            double sc = 1.0;
+            if constexpr (QK == 1) {
+                if (a.nuq > 0.0) sc = pf_t_factor(a, traj, (uint32_t)j, kPfNoiseGammaN, kPfNoiseGammaU, (uint32_t)i, a.nuq);
+            }
 #pragma unroll
             for (int r = 0; r < kPfMaxQ; ++r) {
                 double s = 0.0;
 #pragma unroll
                 for (int k = 0; k <= r; ++k) s += a.Lq[r * kPfMaxQ + k] * z[k];
+                if constexpr (QK == 1) s *= sc;
                 q[r] = a.qm[r] + s;
             }
 #pragma unroll
@@ -292,7 +325,7 @@ __global__ __launch_bounds__(kPfBlock) void k_particle_filter(const PfArgs a) {
 }
 
 typedef void (*pf_kernel)(const PfArgs);
-template <int D> constexpr pf_kernel pf_kernel_of() { return k_particle_filter<D>; }
+template <int D, int QK> constexpr pf_kernel pf_kernel_of() { return k_particle_filter<D, QK>; }
 
 }  // namespace
 
@@ -301,26 +334,29 @@ int launch_particle_filter(const PfLaunch &h, hipStream_t s) {
     memset(&a, 0, sizeof(a));
     a.Y = h.Y; a.dq = h.dq; a.N = h.N; a.T = h.T; a.fid_dyn = h.f_dyn->id; a.fid_obs = h.f_obs->id; a.student = h.student;
     a.B = h.B; a.ld = h.ld; a.seed = h.seed; a.traj_offset = h.traj_offset; a.ess_threshold = h.ess_threshold; a.lognorm = h.lognorm;
-    a.dof = h.dof;
+    a.dof = h.dof; a.nu0 = h.nu0; a.nuq = h.nuq;
     memcpy(a.qm, h.qm, sizeof(a.qm)); memcpy(a.Lq, h.Lq, sizeof(a.Lq)); memcpy(a.G, h.G, sizeof(a.G));
     memcpy(a.rm, h.rm, sizeof(a.rm)); memcpy(a.Lr, h.Lr, sizeof(a.Lr));
     a.y = h.y; a.m0 = h.m0; a.P0 = h.P0; a.fm = h.fm; a.fP = h.fP; a.ll = h.ll; a.ess = h.ess; a.status = h.status;
     a.part = h.part; a.logw = h.logw; a.anc = h.anc;
     fill_fpar(h.f_dyn, &a.fd);
     fill_fpar(h.f_obs, &a.fo);
-    static const pf_kernel table[kPfMaxD] = {pf_kernel_of<1>(), pf_kernel_of<2>(), pf_kernel_of<3>(), pf_kernel_of<4>(), pf_kernel_of<5>(),
-                                             pf_kernel_of<6>()};
-    if (!pf_shape_ok(h.D, h.Y, h.dq, h.N) || h.B < 1 || h.B > 0x7fffffff) {
+    static const pf_kernel table[2][kPfMaxD] = {
+        {pf_kernel_of<1, 0>(), pf_kernel_of<2, 0>(), pf_kernel_of<3, 0>(), pf_kernel_of<4, 0>(), pf_kernel_of<5, 0>(), pf_kernel_of<6, 0>()},
+        {pf_kernel_of<1, 1>(), pf_kernel_of<2, 1>(), pf_kernel_of<3, 1>(), pf_kernel_of<4, 1>(), pf_kernel_of<5, 1>(), pf_kernel_of<6, 1>()}};
+    if (!pf_shape_ok(h.D, h.Y, h.dq, h.N) || h.B < 1 || h.B > 0x7fffffff || !pf_dof_ok(h.nu0) || !pf_dof_ok(h.nuq)) {
         set_error("particle filter: shape outside the kernel's range");
         return SSMQ_E_UNSUPPORTED;
     }
     const size_t lds = pf_lds_bytes(h.D, h.N);
     static thread_local unsigned attr_epoch = 0;
-    int rc = set_max_dynamic_lds(attr_epoch, {(const void *)table[0], (const void *)table[1], (const void *)table[2], (const void *)table[3],
-                                              (const void *)table[4], (const void *)table[5]},
+    int rc = set_max_dynamic_lds(attr_epoch, {(const void *)table[0][0], (const void *)table[0][1], (const void *)table[0][2],
+                                              (const void *)table[0][3], (const void *)table[0][4], (const void *)table[0][5],
+                                              (const void *)table[1][0], (const void *)table[1][1], (const void *)table[1][2],
+                                              (const void *)table[1][3], (const void *)table[1][4], (const void *)table[1][5]},
                                  sizeof(double) * (kPfCloudDoubles + kPfRedDoubles));
     if (rc) return rc;
-    hipLaunchKernelGGL(table[h.D - 1], dim3((unsigned)h.B), dim3(kPfBlock), lds, s, a);
+    hipLaunchKernelGGL(table[pf_noise_kind(h.nu0, h.nuq)][h.D - 1], dim3((unsigned)h.B), dim3(kPfBlock), lds, s, a);
     return hip_fail(hipGetLastError(), "k_particle_filter");
 }
 

@@ -15,6 +15,11 @@
 // maximum, sum of exp(ls - max), mean and sum of squared weights, covariance around the mean - through pf_block_max / pf_block_sum, in
 // the order stated at the top of ssmq_particle.hip.  No other sum crosses threads, so a trajectory's bits depend on its cloud and N.
 //
+// Noise kind QK of k_particle_smooth (compile time): 0 - Gaussian process noise, log p(x' | x) = const - d2 / 2, the kernel as it always
+// was; 1 - Student-t process noise of full rank: x' | x is Student-t with location f(x) + G q_mean, scale G Q G' and the noise's nu, so
+// log p = const - (nu + D) / 2 log1p(d2 / nu) with the same whitened d2 (Ls the factor of the scale matrix); the constant cancels in the
+// normalisation.  One more fp64 log1p and division per pair and sweep.
+//
 // k_particle_lineage<D> (ancestor tracing): LDS w [N] doubles (the final weights) | idx [N] | mark [N] int32 | red [96].  idx_k(j) =
 // a_k(idx_{k+1}(j)) is a gather by the owner of j; the moments are sums over j of w[j] x_k[:, idx_k(j)] in the filter's order; the
 // number of distinct idx_k(j) is counted through marks (every writer of a mark writes 1).
@@ -33,6 +38,7 @@ struct PsArgs {
     double *sm, *sP, *ess_s, *logw_s;
     int32_t *lineage, *unique;
     FPar fd;
+    double nuq, hk;                        // QK = 1: the process noise's degrees of freedom nu and (nu + D) / 2
 };
 
 // a failed trajectory: NaN (-1) at every step; uniform over the workgroup, before its first barrier
@@ -89,7 +95,7 @@ __device__ __forceinline__ void ps_whiten(const PsArgs &a, const double *v, doub
     }
 }
 
-template <int D>
+template <int D, int QK>
 __global__ __launch_bounds__(kPfBlock) void k_particle_smooth(const PsArgs a) {
     extern __shared__ __align__(16) double lds[];
     const int N = a.N, T = a.T, tid = threadIdx.x;
@@ -143,7 +149,7 @@ __global__ __launch_bounds__(kPfBlock) void k_particle_smooth(const PsArgs a) {
                     const double df = bj[d] - al[d * N + i];
                     d2 += df * df;
                 }
-                const double v = lw[i] - 0.5 * d2;
+                const double v = QK == 1 ? lw[i] - a.hk * log1p(d2 / a.nuq) : lw[i] - 0.5 * d2;
                 m = v > m ? v : m;
             }
             double lv = -INFINITY;
@@ -156,7 +162,7 @@ __global__ __launch_bounds__(kPfBlock) void k_particle_smooth(const PsArgs a) {
                         const double df = bj[d] - al[d * N + i];
                         d2 += df * df;
                     }
-                    s += exp((lw[i] - 0.5 * d2) - m);
+                    s += QK == 1 ? exp((lw[i] - a.hk * log1p(d2 / a.nuq)) - m) : exp((lw[i] - 0.5 * d2) - m);
                 }
                 lv = m + log(s);
             }
@@ -177,7 +183,7 @@ __global__ __launch_bounds__(kPfBlock) void k_particle_smooth(const PsArgs a) {
                     const double df = be[d * N + j] - ai[d];
                     d2 += df * df;
                 }
-                const double v = rr[j] - 0.5 * d2;
+                const double v = QK == 1 ? rr[j] - a.hk * log1p(d2 / a.nuq) : rr[j] - 0.5 * d2;
                 m = v > m ? v : m;
             }
             double lt = -INFINITY;
@@ -190,7 +196,7 @@ __global__ __launch_bounds__(kPfBlock) void k_particle_smooth(const PsArgs a) {
                         const double df = be[d * N + j] - ai[d];
                         d2 += df * df;
                     }
-                    s += exp((rr[j] - 0.5 * d2) - m);
+                    s += QK == 1 ? exp((rr[j] - a.hk * log1p(d2 / a.nuq)) - m) : exp((rr[j] - 0.5 * d2) - m);
                 }
                 lt = m + log(s);
             }
@@ -311,7 +317,7 @@ __global__ __launch_bounds__(kPfBlock) void k_particle_lineage(const PsArgs a) {
 }
 
 typedef void (*ps_kernel)(const PsArgs);
-template <int D> constexpr ps_kernel ps_smooth_of() { return k_particle_smooth<D>; }
+template <int D, int QK> constexpr ps_kernel ps_smooth_of() { return k_particle_smooth<D, QK>; }
 template <int D> constexpr ps_kernel ps_lineage_of() { return k_particle_lineage<D>; }
 
 }  // namespace
@@ -321,14 +327,16 @@ int launch_particle_smoother(const PsLaunch &h, hipStream_t s) {
     memset(&a, 0, sizeof(a));
     a.N = h.N; a.T = h.T; a.fid_dyn = h.f_dyn->id; a.B = h.B; a.ld = h.ld;
     memcpy(a.Li, h.Li, sizeof(a.Li)); memcpy(a.gq, h.gq, sizeof(a.gq));
+    a.nuq = h.nuq; a.hk = 0.5 * (h.nuq + (double)h.D);
     a.part = h.part; a.logw = h.logw; a.fm = h.fm; a.fP = h.fP; a.ess = h.ess; a.anc = h.anc; a.status = h.status;
     a.sm = h.sm; a.sP = h.sP; a.ess_s = h.ess_s; a.logw_s = h.logw_s; a.lineage = h.lineage; a.unique = h.unique;
     fill_fpar(h.f_dyn, &a.fd);
-    static const ps_kernel table[2][kPfMaxD] = {
-        {ps_smooth_of<1>(), ps_smooth_of<2>(), ps_smooth_of<3>(), ps_smooth_of<4>(), ps_smooth_of<5>(), ps_smooth_of<6>()},
-        {ps_lineage_of<1>(), ps_lineage_of<2>(), ps_lineage_of<3>(), ps_lineage_of<4>(), ps_lineage_of<5>(), ps_lineage_of<6>()}};
+    static const ps_kernel table[3][kPfMaxD] = {
+        {ps_smooth_of<1, 0>(), ps_smooth_of<2, 0>(), ps_smooth_of<3, 0>(), ps_smooth_of<4, 0>(), ps_smooth_of<5, 0>(), ps_smooth_of<6, 0>()},
+        {ps_lineage_of<1>(), ps_lineage_of<2>(), ps_lineage_of<3>(), ps_lineage_of<4>(), ps_lineage_of<5>(), ps_lineage_of<6>()},
+        {ps_smooth_of<1, 1>(), ps_smooth_of<2, 1>(), ps_smooth_of<3, 1>(), ps_smooth_of<4, 1>(), ps_smooth_of<5, 1>(), ps_smooth_of<6, 1>()}};
     if (!pf_shape_ok(h.D, 1, 1, h.N) || h.N < kPfMinN || h.N % 64 != 0 || h.B < 1 || h.B > 0x7fffffff ||
-        (h.method != SSMQ_PS_MARGINAL && h.method != SSMQ_PS_GENEALOGY) || (h.method == SSMQ_PS_GENEALOGY && !h.anc)) {
+        (h.method != SSMQ_PS_MARGINAL && h.method != SSMQ_PS_GENEALOGY) || (h.method == SSMQ_PS_GENEALOGY && !h.anc) || !pf_dof_ok(h.nuq)) {
         set_error("particle smoother: shape or method outside the kernels' range");
         return SSMQ_E_UNSUPPORTED;
     }
@@ -337,12 +345,14 @@ int launch_particle_smoother(const PsLaunch &h, hipStream_t s) {
     int rc = set_max_dynamic_lds(attr_epoch, {(const void *)table[0][0], (const void *)table[0][1], (const void *)table[0][2],
                                               (const void *)table[0][3], (const void *)table[0][4], (const void *)table[0][5],
                                               (const void *)table[1][0], (const void *)table[1][1], (const void *)table[1][2],
-                                              (const void *)table[1][3], (const void *)table[1][4], (const void *)table[1][5]},
+                                              (const void *)table[1][3], (const void *)table[1][4], (const void *)table[1][5],
+                                              (const void *)table[2][0], (const void *)table[2][1], (const void *)table[2][2],
+                                              (const void *)table[2][3], (const void *)table[2][4], (const void *)table[2][5]},
                                  sizeof(double) * (kPsCloudDoubles + kPfRedDoubles));
     if (rc) return rc;
-    const int m = h.method == SSMQ_PS_MARGINAL ? 0 : 1;
+    const int m = h.method == SSMQ_PS_MARGINAL ? (h.nuq > 0.0 ? 2 : 0) : 1;      // the lineage reads no density
     hipLaunchKernelGGL(table[m][h.D - 1], dim3((unsigned)h.B), dim3(kPfBlock), lds, s, a);
-    return hip_fail(hipGetLastError(), m == 0 ? "k_particle_smooth" : "k_particle_lineage");
+    return hip_fail(hipGetLastError(), m == 1 ? "k_particle_lineage" : "k_particle_smooth");
 }
 
 }  // namespace ssmq

@@ -60,4 +60,23 @@ __device__ __forceinline__ double gamma_mt(uint64_t seed, uint64_t traj, uint32_
     return d * v;
 }
 
+// The same sampler for callers whose tags keep other bits than gamma_mt's 0x100 / 0x180 (the particle kernels: tag = purpose << 28 |
+// particle << 4 | pair, where 0x100 is particle 16): the two tag bases are given, their low four bits zero, and attempt t = 0 .. 15
+// draws its normal from tag_normal | t and its uniform from tag_uniform | t.  Same arithmetic, same acceptance test, same fallback.
+__device__ __forceinline__ double gamma_mt_tags(uint64_t seed, uint64_t traj, uint32_t step, uint32_t tag_normal, uint32_t tag_uniform,
+                                                double shape) {
+    const double d = shape - 1.0 / 3.0, c = 1.0 / sqrt(9.0 * d);
+    double v = 1.0;
+    for (uint32_t t = 0; t < 16; ++t) {
+        double x, unused;
+        normal_pair(seed, traj, step, tag_normal | t, &x, &unused);
+        const double u = uniform_one(seed, traj, step, tag_uniform | t);
+        const double w = 1.0 + c * x;
+        v = w * w * w;
+        if (v > 0.0 && log(u) < 0.5 * x * x + d - d * v + d * log(v)) break;
+        v = fabs(v) > 0.0 ? fabs(v) : 1.0;
+    }
+    return d * v;
+}
+
 }  // namespace ssmq

@@ -1337,16 +1337,23 @@ class BootstrapParticleFilter:
     GaussianInference: it has no moment transforms.  A trajectory's results depend on `seed`, its global index, num_particles,
     ess_threshold and its own data alone.
 
+    The initial state and the process noise may each be a GaussRV or a StudentRV (dof >= 2), in any combination: a Student-t draw is
+    mean + L z / sqrt(u), u ~ Gamma(dof / 2, scale 2 / dof), as `ssmod.simulate_dev` draws it (`ssmq_particle_filter_rv_dev`,
+    k_particle_filter<D, QK=1>) - the ground truth of a heavy-tailed study.  For a StudentRV initial state `x0_cov` is the SCALE
+    matrix (default: the random variable's `scale`), not a covariance.  All-Gaussian models run the Gaussian kernels as before.
+
     It also answers the smoothing question, E[x_k | y_0..T-1], from the same cloud (`ssmq_particle_smoother_dev`): `smoother`,
     `smoother_batch`, `smoother_dev` with method='marginal' - the marginal forward-filter backward-smoother (FFBSm), one launch of
     k_particle_smooth<D>, O(N^2) transition densities per step and trajectory, deterministic given the forward pass; it needs process
-    noise of full rank (G Q G' positive definite) - or method='genealogy' - ancestor tracing (k_particle_lineage<D>), for every model
+    noise of full rank (G Q G' positive definite; for StudentRV process noise G Q G' is the scale and the transition density the
+    Student-t's, k_particle_smooth<D, QK=1>) - or method='genealogy' - ancestor tracing (k_particle_lineage<D>), for every model
     the filter covers, with `unique`, the number of distinct ancestors left at each step, as the diagnostic of its collapse.  The
     smoothed initial state x_{-1} is not computed: the filter does not keep its initial cloud."""
 
     RANGE = ('BootstrapParticleFilter covers forward passes (forward_pass, forward_pass_batch, forward_pass_dev) and particle '
              "smoothers (smoother, smoother_batch, smoother_dev; method='marginal' needs G Q G' positive definite) of built-in "
-             'additive-noise models with a GaussRV initial state and process noise and GaussRV or StudentRV measurement noise, '
+             'additive-noise models with a GaussRV or StudentRV (dof >= 2) initial state and process noise and GaussRV or StudentRV '
+             'measurement noise, '
              'dim_state <= 6, dim_out <= 4, dim_noise <= 6, num_particles a multiple of 64 in 64 .. 4096 with '
              '(2 dim_state + 1) num_particles <= 13312')
 
@@ -1359,13 +1366,16 @@ class BootstrapParticleFilter:
             raise NotImplementedError('{}; not implemented for user models (device_code)'.format(self.RANGE))
         if not (dyn.noise_additive and obs.noise_additive):
             raise NotImplementedError('{}; not implemented for models that take their noise as an argument (non-additive noise)'.format(self.RANGE))
-        if not isinstance(dyn.init_rv, GaussRV) or not isinstance(dyn.noise_rv, GaussRV):
-            raise NotImplementedError('{}; the initial state and the process noise must be GaussRV'.format(self.RANGE))
+        for rv, what in ((dyn.init_rv, 'initial state'), (dyn.noise_rv, 'process noise')):
+            if not isinstance(rv, (GaussRV, StudentRV)):
+                raise NotImplementedError('{}; not implemented for a {} {}'.format(self.RANGE, type(rv).__name__, what))
+        # Student-t on either side: the *_rv entry points; all-Gaussian models keep the entry points they always called
+        self._heavy = isinstance(dyn.init_rv, StudentRV) or isinstance(dyn.noise_rv, StudentRV)
         if not isinstance(obs.noise_rv, (GaussRV, StudentRV)):
             raise NotImplementedError('{}; not implemented for {} measurement noise'.format(self.RANGE, type(obs.noise_rv).__name__))
         if np.isnan(self.ess_threshold):
             raise ValueError('ess_threshold must not be NaN')
-        self.x0_mean, self.x0_cov = dyn.init_rv.get_stats()
+        self.x0_mean, self.x0_cov = dyn.init_rv.get_stats()[:2]          # StudentRV: the scale matrix, as the kernel reads the plane
         self.G = np.ascontiguousarray(dyn.noise_gain, dtype=np.float64)
         self._check_range()
         self.reset()
@@ -1390,18 +1400,31 @@ class BootstrapParticleFilter:
         f_obs, _ = self.mod_obs.device_integrand()
         r, keep = _rv_desc(self.mod_obs.noise_rv, 'the measurement noise')
         qm = np.ascontiguousarray(self.mod_dyn.noise_rv.mean, dtype=np.float64)
-        qL = _lower_factor(self.mod_dyn.noise_rv.cov)
+        qL = _lower_factor(self.mod_dyn.noise_rv.get_stats()[1])          # StudentRV: of the scale matrix
         return f_dyn, f_obs, r, qm, qL, keep
+
+    def _rv_args(self):
+        """The descriptors of the initial state and the process noise for the *_rv entry points (and what they point to)."""
+        from .ssmod import _rv_desc
+        x0, keep0 = _rv_desc(self.mod_dyn.init_rv, 'the initial state')
+        q, keepq = _rv_desc(self.mod_dyn.noise_rv, 'the process noise')
+        return x0, q, (keep0, keepq)
 
     def _check_range(self):
         """The library's range check, without a device: NotImplementedError (the range named) or ValueError before anything runs."""
         f_dyn, f_obs, r, qm, qL, keep = self._c_args()
         buf = ctypes.create_string_buffer(256)
-        rc = _lib.load().ssmq_particle_kernel_name(ctypes.byref(f_dyn), ctypes.byref(f_obs), self.mod_dyn.dim_state, self.mod_obs.dim_out,
-                                                   qm.size, self.num_particles, ctypes.byref(r), buf, 256)
+        if self._heavy:
+            x0, q, keep_rv = self._rv_args()
+            rc = _lib.load().ssmq_particle_kernel_name_rv(ctypes.byref(f_dyn), ctypes.byref(f_obs), self.mod_dyn.dim_state,
+                                                          self.mod_obs.dim_out, qm.size, self.num_particles, ctypes.byref(x0),
+                                                          ctypes.byref(q), ctypes.byref(r), buf, 256)
+        else:
+            rc = _lib.load().ssmq_particle_kernel_name(ctypes.byref(f_dyn), ctypes.byref(f_obs), self.mod_dyn.dim_state, self.mod_obs.dim_out,
+                                                       qm.size, self.num_particles, ctypes.byref(r), buf, 256)
         if rc == -1:             # SSMQ_E_ARG
             raise ValueError(_lib.last_error())
-        _lib.check(rc, 'ssmq_particle_kernel_name', unsupported=True)
+        _lib.check(rc, 'ssmq_particle_kernel_name_rv' if self._heavy else 'ssmq_particle_kernel_name', unsupported=True)
         return buf.value.decode()
 
     def kernel_name(self):
@@ -1413,6 +1436,15 @@ class BootstrapParticleFilter:
             raise ValueError('BootstrapParticleFilter: at least one time step is needed (T = {})'.format(T))
         f_dyn, f_obs, r, qm, qL, keep = self._c_args()
         vp, dp = _lib.vp, _lib.dp
+        if self._heavy:
+            x0, q, keep_rv = self._rv_args()
+            _lib.check(lib.ssmq_particle_filter_rv_dev(ctypes.byref(f_dyn), ctypes.byref(f_obs), self.mod_dyn.dim_state, self.mod_obs.dim_out,
+                                                       qm.size, self.num_particles, B, ld, T, vp(d_y), vp(d_m0), vp(d_P0), ctypes.byref(x0),
+                                                       ctypes.byref(q), dp(self.G), ctypes.byref(r), self.ess_threshold,
+                                                       ctypes.c_uint64(self.seed), ctypes.c_uint64(int(traj_offset)), vp(d_fm), vp(d_fP),
+                                                       vp(d_ll), vp(d_ess), vp(d_st), vp(d_part), vp(d_logw), vp(d_anc)),
+                       'ssmq_particle_filter_rv_dev', unsupported=True)
+            return
         _lib.check(lib.ssmq_particle_filter_dev(ctypes.byref(f_dyn), ctypes.byref(f_obs), self.mod_dyn.dim_state, self.mod_obs.dim_out,
                                                 qm.size, self.num_particles, B, ld, T, vp(d_y), vp(d_m0), vp(d_P0), dp(qm), dp(qL),
                                                 dp(self.G), ctypes.byref(r), self.ess_threshold, ctypes.c_uint64(self.seed),
@@ -1509,11 +1541,16 @@ class BootstrapParticleFilter:
             raise ValueError("BootstrapParticleFilter: unknown smoother method {!r} ('marginal' or 'genealogy')".format(method))
         f_dyn, f_obs, r, qm, qL, keep = self._c_args()
         buf = ctypes.create_string_buffer(256)
-        rc = _lib.load().ssmq_particle_smoother_kernel_name(ctypes.byref(f_dyn), self.mod_dyn.dim_state, qm.size, self.num_particles,
-                                                            _lib.dp(qm), _lib.dp(qL), _lib.dp(self.G), self.SMOOTHER_METHODS[method], buf, 256)
+        if self._heavy:
+            x0, q, keep_rv = self._rv_args()
+            rc = _lib.load().ssmq_particle_smoother_kernel_name_rv(ctypes.byref(f_dyn), self.mod_dyn.dim_state, qm.size, self.num_particles,
+                                                                   ctypes.byref(q), _lib.dp(self.G), self.SMOOTHER_METHODS[method], buf, 256)
+        else:
+            rc = _lib.load().ssmq_particle_smoother_kernel_name(ctypes.byref(f_dyn), self.mod_dyn.dim_state, qm.size, self.num_particles,
+                                                                _lib.dp(qm), _lib.dp(qL), _lib.dp(self.G), self.SMOOTHER_METHODS[method], buf, 256)
         if rc == -1:             # SSMQ_E_ARG
             raise ValueError(_lib.last_error())
-        _lib.check(rc, 'ssmq_particle_smoother_kernel_name', unsupported=True)
+        _lib.check(rc, 'ssmq_particle_smoother_kernel_name_rv' if self._heavy else 'ssmq_particle_smoother_kernel_name', unsupported=True)
         return buf.value.decode()
 
     def smoother_kernel_name(self, method='marginal'):
@@ -1535,6 +1572,8 @@ class BootstrapParticleFilter:
         D, N, code = self.mod_dyn.dim_state, self.num_particles, self.SMOOTHER_METHODS[method]
         f_dyn, f_obs, r, qm, qL, keep = self._c_args()
         vp, dp = _lib.vp, _lib.dp
+        if self._heavy:
+            x0, q, keep_rv = self._rv_args()
         nb = self.cloud_block(T, B, cloud_bytes)
         d_part, d_logw, d_anc = stage.scratch(8 * T * D * nb * N), stage.scratch(8 * T * nb * N), stage.scratch(4 * T * nb * N)
         d_lws = stage.scratch(8 * T * nb * N) if host is not None else None
@@ -1544,11 +1583,14 @@ class BootstrapParticleFilter:
             at = lambda name: d[name].view((4 if name in ('st', 'unique') else 8) * b0)          # noqa: E731
             self._launch(lib, n, ld, T, traj_offset + b0, d_y.view(8 * b0), d_m0.view(8 * b0), d_P0.view(8 * b0), at('fm'), at('fP'),
                          at('ll'), at('ess'), at('st'), d_part, d_logw, d_anc)
-            _lib.check(lib.ssmq_particle_smoother_dev(ctypes.byref(f_dyn), D, qm.size, N, n, ld, T, dp(qm), dp(qL), dp(self.G), code,
-                                                      vp(d_part), vp(d_logw), vp(d_anc), vp(at('fm')), vp(at('fP')), vp(at('ess')),
-                                                      vp(at('st')), vp(at('sm')), vp(at('sP')), vp(at('ess_s')), vp(d_lws), vp(d_lin),
-                                                      vp(at('unique')) if code == 1 else None),
-                       'ssmq_particle_smoother_dev', unsupported=True)
+            clouds = (vp(d_part), vp(d_logw), vp(d_anc), vp(at('fm')), vp(at('fP')), vp(at('ess')), vp(at('st')), vp(at('sm')), vp(at('sP')),
+                      vp(at('ess_s')), vp(d_lws), vp(d_lin), vp(at('unique')) if code == 1 else None)
+            if self._heavy:
+                _lib.check(lib.ssmq_particle_smoother_rv_dev(ctypes.byref(f_dyn), D, qm.size, N, n, ld, T, ctypes.byref(q), dp(self.G), code,
+                                                             *clouds), 'ssmq_particle_smoother_rv_dev', unsupported=True)
+            else:
+                _lib.check(lib.ssmq_particle_smoother_dev(ctypes.byref(f_dyn), D, qm.size, N, n, ld, T, dp(qm), dp(qL), dp(self.G), code,
+                                                          *clouds), 'ssmq_particle_smoother_dev', unsupported=True)
             if host is not None:
                 host['particles'][:, :, b0:b0 + n] = d_part.download((T, D, n, N))
                 host['log_weights'][:, b0:b0 + n] = d_logw.download((T, n, N))

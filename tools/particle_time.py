@@ -4,13 +4,16 @@ UnscentedKalman's forward_pass_dev on the same data beside it as the scale: UNGM
 reentry 5-D + radar pair at B = 1e4, T = 50 with N = 1024.  With --variant NAME=PATH (repeatable) the same passes run in another build
 of the library as well, called through the C ABI in the same process - e.g. csrc/ssmq_particle.hip compiled with -DSSMQ_PF_NO_RNG
 (no Philox / Box-Muller) or -DSSMQ_PF_NO_MODEL (no model evaluations), which is how the time is split; ess_threshold = 0 against 1
-gives the cost of the resampling itself.
+gives the cost of the resampling itself.  --heavy adds the Student-t passes (k_particle_filter<D, QK=1>): the UNGM of the README's
+heavy-tailed example (StudentRV initial state, process noise of scale 10 and measurement noise, dof 4) at the UNGM shapes and the
+pendulum with Student-t process noise (dof 3) at B = 1e4, T = 100, N = 1024, each at ess_threshold = 0.5; a variant library that lacks
+the *_rv entry points (a build of an earlier commit) is skipped for them.
 
 hipEvent timing around blocks of passes after a warm-up, every buffer allocated outside the timed blocks; the routes alternate block by
 block and the median over the rounds is reported with the smallest and the largest block.  The variants
 (tools/build_variant.sh NAME "-DSSMQ_PF_NO_RNG" ssmq_particle.hip) run at ess_threshold = 0.5.
 
-    python tools/particle_time.py [--variant NAME=PATH ...] [--rounds N]     ->  one JSON line per shape"""
+    python tools/particle_time.py [--variant NAME=PATH ...] [--rounds N] [--heavy]     ->  one JSON line per shape"""
 import argparse
 import ctypes
 import json
@@ -27,6 +30,8 @@ ap = argparse.ArgumentParser()
 ap.add_argument('--variant', action='append', default=[])
 ap.add_argument('--rounds', type=int, default=5)
 ap.add_argument('--per-block', type=int, default=2)
+ap.add_argument('--heavy', action='store_true')
+ap.add_argument('--shapes', default='', help='comma-separated shape names to run (default: all)')
 opt = ap.parse_args()
 
 amd.set_device(0)
@@ -71,12 +76,34 @@ def reentry():
     return dyn, obs
 
 
+def ungm_t():
+    return (sm.UNGMTransition(sm.StudentRV(1, dof=4.0), sm.StudentRV(1, scale=np.array([[10.0]]), dof=4.0)),
+            sm.UNGMMeasurement(sm.StudentRV(1, dof=4.0), 1))
+
+
+def pendulum_t():
+    dt = 0.01
+    q = 0.01 * np.array([[(dt ** 3) / 3, (dt ** 2) / 2], [(dt ** 2) / 2, dt]])
+    return (sm.Pendulum2DTransition(sm.GaussRV(2, np.array([1.0, 0.0]), 0.05 * np.eye(2)), sm.StudentRV(2, scale=q, dof=3.0), dt=dt),
+            sm.Pendulum2DMeasurement(sm.GaussRV(1, cov=np.array([[0.002]])), 2))
+
+
+SHAPES = [('UNGM', ungm, 10000, 100, (256, 1024)), ('reentry5_radar', reentry, 10000, 50, (1024,))]
+if opt.heavy:
+    SHAPES += [('UNGM_t', ungm_t, 10000, 100, (256, 1024)), ('pendulum_t', pendulum_t, 10000, 100, (1024,))]
+if opt.shapes:
+    SHAPES = [s for s in SHAPES if s[0] in opt.shapes.split(',')]
+
 results = []
-for shape, models, B, T, counts in (('UNGM', ungm, 10000, 100, (256, 1024)), ('reentry5_radar', reentry, 10000, 50, (1024,))):
+for shape, models, B, T, counts in SHAPES:
     dyn, obs = models()
     D = dyn.dim_state
     d_x, d_y, ld = sm.simulate_dev(dyn, obs, T, B, seed=1)
-    ukf = ssinf.UnscentedKalman(dyn, obs)
+    heavy = shape.endswith('_t')
+    # the scale beside it: the UKF, the Studentian filter for the all-Student UNGM, none for a pair that mixes GaussRV and StudentRV
+    from ssmtoybox_amd.ssmod import StudentRV
+    all_t = all(isinstance(rv, StudentRV) for rv in (dyn.init_rv, dyn.noise_rv, obs.noise_rv))
+    ukf = (ssinf.FullySymmetricStudent(dyn, obs, dof=4.0) if all_t else None) if heavy else ssinf.UnscentedKalman(dyn, obs)
     routes = {}
 
     def add(name, fn, l):
@@ -86,15 +113,18 @@ for shape, models, B, T, counts in (('UNGM', ungm, 10000, 100, (256, 1024)), ('r
     outs = [_lib.DeviceBuffer(8 * T * D * ld), _lib.DeviceBuffer(8 * T * D * D * ld), _lib.DeviceBuffer(8 * (T + 1) * ld),
             _lib.DeviceBuffer(8 * T * ld), _lib.DeviceBuffer(4 * ld)]
     stage = _lib.Staging()
-    d_m0, d_P0 = ukf._initial_planes(stage, B, ld)
+    d_m0, d_P0 = ssinf.BootstrapParticleFilter(dyn, obs, num_particles=counts[0])._initial_planes(stage, B, ld)
 
     def run_ukf():
         ukf._launch(lib, B, ld, T, d_y, d_m0, d_P0, outs[0], outs[1], outs[4])
-    add('ukf', run_ukf, lib)
+    if ukf is not None:
+        add('ukf', run_ukf, lib)
     for N in counts:
-        for thr in (0.5, 0.0, 1.0):
+        for thr in ((0.5,) if heavy else (0.5, 0.0, 1.0)):
             pf = ssinf.BootstrapParticleFilter(dyn, obs, num_particles=N, ess_threshold=thr, seed=7)
             for vname, vlib in [('', lib)] + (list(variants.items()) if thr == 0.5 else []):
+                if heavy and not hasattr(vlib, 'ssmq_particle_filter_rv_dev'):
+                    continue
                 def run_pf(pf=pf, vlib=vlib):
                     pf._launch(vlib, B, ld, T, 0, d_y, d_m0, d_P0, outs[0], outs[1], outs[2], outs[3], outs[4])
                 add('pf_N%d_ess%g%s' % (N, thr, '_' + vname if vname else ''), run_pf, vlib)
