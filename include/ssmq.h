@@ -1048,6 +1048,43 @@ int ssmq_smoother_iterated_kernel_name(const ssmq_transform *h_dyn, const ssmq_i
                                        const ssmq_integrand *f_obs, int iterations, char *buf, int len);
 
 /*
+ * Kernel-parameter sweep of a BQ filter by measurement likelihood: the additive-noise Gaussian recursion of ssmq_filter_forward_dev for
+ * P rows of kernel parameters ("theta") on B measurement sequences in ONE launch (k_filter_sweep<>), of which only the scores are kept.
+ * Row p pairs par_dyn[p] with par_obs[p] (not Cartesian).  Per item (p, b), with (m, P) = (x0_mean, x0_cov) and the weights of row p,
+ * for k = 0 .. T-1 (both transforms use time index k):
+ *     m-, P-  = dynamics transform of (m, P) + G Q G';      y^, S, C = measurement transform of (m-, P-) + R;      e = y_k - y^
+ *     nis_k = e' S^-1 e (Cholesky of S);   ll_k = -(Y log 2 pi + log det S + nis_k) / 2 = log p(y_k | y_1..k-1)
+ *     K = C' S^-1;   m = m- + K e;   P = P- - K S K'
+ * - step by step what ssmq_filter_forward_dev followed by ssmq_filter_innovations_dev computes with the dense kernels -, and
+ *     d_loglik_total[p][b] = sum_k ll_k,   d_nis_mean[p][b] = sum_k nis_k / T   (ascending k),   d_loglik_steps[p][k][b] = ll_k.
+ * The filtered moments are never stored.
+ *   kind_dyn / kind_obs        SSMQ_SWEEP_GP (ssmq_weights_gp) or SSMQ_SWEEP_BS (ssmq_weights_bs, with mulind_* [D*NB_*]; NULL / 0 for GP)
+ *   xi_dyn [D*N_dyn], xi_obs [D*N_obs]   unit sigma points, row-major (host);  jitter_*: as the weights entry points take it
+ *   par_dyn, par_obs [P][1+D]  rows [alpha, ell_1 .. ell_D] (host)
+ *   d_y [T][Y][ld] (device);  x0_mean [D], x0_cov [D*D], GQG [D*D], R [Y*Y] (host; NULL GQG / R = zeros)
+ *   d_loglik_total, d_nis_mean [P][ld];  d_loglik_steps [P][T][ld] or NULL;  d_status [P][ld] int32 (device);  theta_status [P] (host)
+ * ld is a multiple of 64 (every wave belongs to one row).  Failures: theta_status[p] = (status of the dynamics weights) + 4 (status of
+ * the measurement weights), as ssmq_weights_gp / ssmq_weights_bs report them; a row with a non-zero value is NaN and has d_status -1.
+ * An item's d_status is otherwise 1 + the first step whose scores are not numbers (a factorisation failed, a measurement is not
+ * finite) - the totals and the remaining steps are then NaN - or 0.  An item's results do not depend on the items around it.
+ * Range: the 'rbf' kernel, the built-in additive-noise model pairs the fused time loop is instantiated for, D <= 6, Y <= 4,
+ * 2 <= N_dyn = N_obs <= 2 D + 1; user-defined integrands, models that take their noise as an argument, other kinds and point counts
+ * beyond 2 D + 1 return SSMQ_E_UNSUPPORTED (bad arguments SSMQ_E_ARG) with the range in ssmq_last_error(), before any output is
+ * touched.  B == 0: only theta_status is written; T == 0: the totals are zero.  Synchronous.
+ */
+#define SSMQ_SWEEP_GP 0
+#define SSMQ_SWEEP_BS 1
+int ssmq_filter_sweep_dev(const ssmq_integrand *f_dyn, const ssmq_integrand *f_obs, int kind_dyn, int kind_obs, const double *xi_dyn,
+                          int N_dyn, const double *xi_obs, int N_obs, const int32_t *mulind_dyn, int NB_dyn, const int32_t *mulind_obs,
+                          int NB_obs, const double *par_dyn, const double *par_obs, int P, double jitter_dyn, double jitter_obs, int D,
+                          int Y, int64_t B, int64_t ld, int T, const double *d_y, const double *x0_mean, const double *x0_cov,
+                          const double *GQG, const double *R, double *d_loglik_total, double *d_nis_mean, double *d_loglik_steps,
+                          int32_t *d_status, int32_t *theta_status);
+/* Name of the kernel ssmq_filter_sweep_dev would run for this pair (the same refusals). */
+int ssmq_filter_sweep_kernel_name(const ssmq_integrand *f_dyn, const ssmq_integrand *f_obs, int kind_dyn, int kind_obs, int N_dyn,
+                                  int N_obs, int D, int Y, char *buf, int len);
+
+/*
  * Bootstrap particle filter (sequential Monte Carlo; Gordon, Salmond, Smith 1993) of the additive-noise models: the ground truth the
  * moment-matching filters are measured against.  N weighted particles per trajectory, in the time convention of
  * ssmq_filter_forward_dev (both models of step j, 0-based, are evaluated at time j):

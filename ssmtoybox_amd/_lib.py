@@ -288,6 +288,16 @@ _PROTOTYPES = {
                                     [c_double_p, c_double_p] + [ctypes.c_void_p] * 6),
     'ssmq_innovations_kernel_name': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Integrand), ctypes.c_void_p,
                                                     ctypes.POINTER(Integrand), ctypes.c_int64, ctypes.c_char_p, ctypes.c_int]),
+    # (f_dyn, f_obs, kind_dyn, kind_obs, xi_dyn, N_dyn, xi_obs, N_obs, mulind_dyn, NB_dyn, mulind_obs, NB_obs, par_dyn, par_obs, P,
+    #  jitter_dyn, jitter_obs, D, Y, B, ld, T, d_y, x0_mean, x0_cov, GQG, R, d_loglik_total, d_nis_mean, d_loglik_steps, d_status,
+    #  theta_status)
+    'ssmq_filter_sweep_dev': (ctypes.c_int, [ctypes.POINTER(Integrand), ctypes.POINTER(Integrand), ctypes.c_int, ctypes.c_int,
+                                             c_double_p, ctypes.c_int, c_double_p, ctypes.c_int, c_int32_p, ctypes.c_int, c_int32_p,
+                                             ctypes.c_int, c_double_p, c_double_p, ctypes.c_int, ctypes.c_double, ctypes.c_double,
+                                             ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p] +
+                              [c_double_p] * 4 + [ctypes.c_void_p] * 4 + [c_int32_p]),
+    'ssmq_filter_sweep_kernel_name': (ctypes.c_int, [ctypes.POINTER(Integrand), ctypes.POINTER(Integrand)] + [ctypes.c_int] * 6 +
+                                      [ctypes.c_char_p, ctypes.c_int]),
     'ssmq_filter_iterated_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Integrand), ctypes.c_void_p, ctypes.POINTER(Integrand),
                                                 ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int] +
                                  [ctypes.c_void_p] * 3 + [c_double_p, c_double_p] + [ctypes.c_void_p] * 4),

@@ -1,0 +1,46 @@
+// Kernel-parameter sweep of a BQ filter (ssmq_filter_sweep_dev): the dispatch table of k_filter_sweep<> (ssmq_filter_sweep_kernel.h) -
+// the dense BQ-form instantiation of every shape the fused time loop is instantiated for (ssmq_filter_shapes.h).
+#include <cstring>
+#include "ssmq_filter_sweep_kernel.h"
+#include "ssmq_filter_shapes.h"
+
+namespace ssmq {
+
+template <int D, int Y, int N, int FD, int FO, int SELO>
+static hipError_t launch_sweep_one(const SweepArgs &a, hipStream_t s) {
+    hipLaunchKernelGGL((k_filter_sweep<D, Y, N, N, FD, FO, SELO>), dim3((unsigned)a.P * (unsigned)a.nblk), dim3(kSmallBlock), 0, s, a);
+    return hipGetLastError();
+}
+
+typedef hipError_t (*sweep_fn)(const SweepArgs &, hipStream_t);
+struct SweepEntry {
+    int fd, fo, D, Y, N, selo;
+    sweep_fn fn;
+    const char *name;
+};
+// a shape of ssmq_filter_shapes.h -> its one dense BQ entry
+#define SSMQ_SWEEP_SHAPE(ONE, FD, FO, D, Y, N, SELO)                        \
+    {FD, FO, D, Y, N, SELO, &launch_sweep_one<D, Y, N, FD, FO, SELO>,       \
+     "k_filter_sweep<D=" #D ",Y=" #Y ",ND=" #N ",NO=" #N "," #FD "," #FO ",SELO=" #SELO ">"}
+
+static const SweepEntry kSweep[] = {
+    SSMQ_SHAPES_UNGM(SSMQ_SWEEP_SHAPE, _),
+    SSMQ_SHAPES_MID(SSMQ_SWEEP_SHAPE, _),
+    SSMQ_SHAPES_HEAVY_UT(SSMQ_SWEEP_SHAPE, _),
+    SSMQ_SHAPES_HEAVY_SR(SSMQ_SWEEP_SHAPE, _),
+};
+
+const char *find_sweep_kernel(int fd, int fo, int D, int Y, int ND, int NO, int selo) {
+    for (const SweepEntry &e : kSweep)
+        if (e.fd == fd && e.fo == fo && e.D == D && e.Y == Y && e.N == ND && e.N == NO && e.selo == selo) return e.name;
+    return nullptr;
+}
+
+// SSMQ_OK launched, SSMQ_E_UNSUPPORTED no instantiation for this shape (the caller has asked find_sweep_kernel first), or a HIP error
+int launch_sweep(int fd, int fo, int D, int Y, int ND, int NO, int selo, const SweepArgs &a, hipStream_t s) {
+    for (const SweepEntry &e : kSweep)
+        if (e.fd == fd && e.fo == fo && e.D == D && e.Y == Y && e.N == ND && e.N == NO && e.selo == selo) return hip_fail(e.fn(a, s), e.name);
+    return SSMQ_E_UNSUPPORTED;
+}
+
+}  // namespace ssmq

@@ -745,7 +745,152 @@ class GaussHermiteKalman(GaussianInference):
                          GaussHermiteTransform(obs.dim_in, degree=deg))
 
 
-class GaussianProcessKalman(GaussianInference):
+def par_grid(alphas, *ells):
+    """The Cartesian grid of kernel-parameter rows [alpha, ell_1 .. ell_D]: alphas and one sequence per input dimension ->
+    (P, 1 + D), the first axis varying slowest."""
+    axes = [np.atleast_1d(np.asarray(a, dtype=np.float64)) for a in (alphas,) + ells]
+    if any(a.ndim != 1 or a.size == 0 for a in axes):
+        raise ValueError('par_grid: every argument is a non-empty one-dimensional sequence')
+    mesh = np.meshgrid(*axes, indexing='ij')
+    return np.ascontiguousarray(np.stack([m.ravel() for m in mesh], axis=1))
+
+
+def fit_table(loglik_total, status, theta_status):
+    """The bookkeeping of `fit_kernel_parameters`: loglik_total, status (P, B), theta_status (P,) -> (index, table).  table[p] sums
+    row p over the trajectories on which EVERY row with theta_status == 0 succeeded (so the rows are comparable; NaN for a row
+    whose weights failed); index is the argmax over the rows with theta_status == 0.  ValueError if no row or no trajectory is
+    left."""
+    ll, st, ts = np.asarray(loglik_total, dtype=np.float64), np.asarray(status), np.asarray(theta_status)
+    rows = ts == 0
+    if not rows.any():
+        raise ValueError('fit_kernel_parameters: the weights of every parameter row failed')
+    keep = ~(st[rows] != 0).any(axis=0)
+    if not keep.any():
+        raise ValueError('fit_kernel_parameters: no trajectory is left on which every parameter row succeeded')
+    table = np.full(ll.shape[0], np.nan)
+    table[rows] = ll[rows][:, keep].sum(axis=1)
+    return int(np.flatnonzero(rows)[np.argmax(table[rows])]), table
+
+
+class _LikelihoodSweep:
+    """Kernel-parameter sweeps by measurement likelihood (`ssmq_filter_sweep_dev`, k_filter_sweep<>): the filter's recursion for P
+    rows of kernel parameters on B measurement sequences in one launch that keeps only the scores.  Row p pairs par_dyn[p] with
+    par_obs[p].  Range: the 'rbf' kernel, built-in additive-noise models with Gaussian noise, D <= 6, Y <= 4, at most 2 D + 1
+    points.  None of these methods touches fi_mean / fi_cov / status or the weights of the object."""
+
+    _sweep_kind = 0          # SSMQ_SWEEP_GP; 1: SSMQ_SWEEP_BS
+
+    def _sweep_setup(self, par_dyn, par_obs):
+        """Every refusal, before the library is loaded; the arguments of the C entry points that do not depend on the data."""
+        from .ssmod import GaussRV
+        what = 'likelihood sweeps cover'
+        if is_user_model(self.mod_dyn) or is_user_model(self.mod_obs):
+            raise user_unsupported('the likelihood sweep (built-in models, D <= 6, Y <= 4, at most 2 D + 1 points)')
+        self._additive_gauss_only(what)
+        for rv in (self.mod_dyn.init_rv, self.mod_dyn.noise_rv, self.mod_obs.noise_rv):
+            if not isinstance(rv, GaussRV):
+                raise NotImplementedError(what + ' Gaussian initial state and noise; not implemented for {}'.format(type(rv).__name__))
+        D, Y = self.mod_dyn.dim_state, self.mod_obs.dim_out
+        for tf in (self.tf_dyn, self.tf_obs):
+            if type(tf.model.kernel).__name__ != 'RBFGauss':
+                raise NotImplementedError(what + " the 'rbf' kernel; not implemented for {}".format(type(tf.model.kernel).__name__))
+            if tf.model.points.shape[0] != D or not 2 <= tf.model.points.shape[1] <= 2 * D + 1:
+                raise NotImplementedError(what + ' 2 .. 2 D + 1 points in the state dimension D <= 6 (Y <= 4); got points {}'.format(
+                    tf.model.points.shape))
+        if D > 6 or Y > 4:
+            raise NotImplementedError(what + ' D <= 6, Y <= 4; got D = {}, Y = {}'.format(D, Y))
+        pd, po = (np.ascontiguousarray(np.atleast_2d(p), dtype=np.float64) for p in (par_dyn, par_obs))
+        if pd.ndim != 2 or po.ndim != 2 or pd.shape[0] != po.shape[0] or pd.shape[0] < 1 or pd.shape[1] != 1 + D or po.shape[1] != 1 + D:
+            raise ValueError('likelihood sweep: par_dyn and par_obs are (P, 1 + D) with the same P >= 1 (row p pairs par_dyn[p] with '
+                             'par_obs[p]); got {} and {}'.format(pd.shape, po.shape))
+        f_dyn, _ = resolve_integrand(self.mod_dyn.dyn_eval)
+        f_obs, _ = resolve_integrand(self.mod_obs.meas_eval)
+        head, keep = [f_dyn, f_obs, self._sweep_kind, self._sweep_kind], [pd, po]
+        mul = []
+        for tf in (self.tf_dyn, self.tf_obs):
+            xi = np.ascontiguousarray(tf.model.points, dtype=np.float64)
+            keep.append(xi)
+            head += [_lib.dp(xi), xi.shape[1]]
+            mi = np.ascontiguousarray(tf.model.mulind, dtype=np.int32) if self._sweep_kind == 1 else None
+            keep.append(mi)
+            mul += [None if mi is None else mi.ctypes.data_as(_lib.c_int32_p), 0 if mi is None else mi.shape[1]]
+        gqg, rr = self._noise()
+        m0, P0 = np.ascontiguousarray(self.x0_mean, dtype=np.float64), np.ascontiguousarray(self._initial_cov(), dtype=np.float64)
+        keep += [gqg, rr, m0, P0]
+        return dict(head=head + mul + [_lib.dp(pd), _lib.dp(po), pd.shape[0], float(self.tf_dyn.model.kernel.jitter),
+                                       float(self.tf_obs.model.kernel.jitter), D, Y],
+                    noise=[_lib.dp(m0), _lib.dp(P0), _lib.dp(gqg), _lib.dp(rr)], P=pd.shape[0], D=D, Y=Y, keep=keep, par=(pd, po))
+
+    def likelihood_sweep_kernel_name(self, P=1):
+        """Which kernel `likelihood_sweep_*` run for this filter (the same for every number of rows P)."""
+        D = self.mod_dyn.dim_state
+        s = self._sweep_setup(np.ones((int(P), 1 + D)), np.ones((int(P), 1 + D)))
+        h = s['head']
+        buf = ctypes.create_string_buffer(512)
+        _lib.check(_lib.load().ssmq_filter_sweep_kernel_name(h[0], h[1], h[2], h[3], h[5], h[7], s['D'], s['Y'], buf, 512),
+                   'ssmq_filter_sweep_kernel_name', True)
+        return buf.value.decode()
+
+    def _sweep_launch(self, stage, s, d_y, B, ld, T, steps, device):
+        alloc = stage.device if device else stage.scratch
+        P = s['P']
+        d_tot, d_nis, d_st = alloc(8 * P * ld), alloc(8 * P * ld), alloc(4 * P * ld)
+        d_ll = alloc(8 * P * T * ld) if steps else None
+        ts = np.zeros(P, dtype=np.int32)
+        vp = _lib.vp
+        _lib.check(_lib.load().ssmq_filter_sweep_dev(*s['head'], B, ld, T, vp(d_y), *s['noise'], vp(d_tot), vp(d_nis), vp(d_ll), vp(d_st),
+                                                     ts.ctypes.data_as(_lib.c_int32_p)), 'ssmq_filter_sweep_dev', True)
+        return d_tot, d_nis, d_ll, d_st, ts
+
+    def likelihood_sweep_dev(self, d_y, B, ld, T, par_dyn, par_obs, steps=False):
+        """The sweep on measurements that are already on the device (planes [T][dim_y][ld], ld a multiple of 64): DeviceBuffers
+        d_loglik_total [P][ld], d_nis_mean [P][ld], d_loglik [P][T][ld] (None without `steps`), d_status [P][ld] int32 - the caller
+        frees them - and theta_status (P,) int32 on the host.  Every trajectory starts from the model's initial moments."""
+        s = self._sweep_setup(par_dyn, par_obs)
+        if ld % 64 or ld < B:
+            raise ValueError('likelihood sweep: ld is a multiple of 64 and at least B')
+        with _lib.Staging() as stage:
+            d_tot, d_nis, d_ll, d_st, ts = self._sweep_launch(stage, s, d_y, B, ld, T, steps, True)
+            stage.release(*[b for b in (d_tot, d_nis, d_ll, d_st) if b is not None])
+        return d_tot, d_nis, d_ll, d_st, ts
+
+    def likelihood_sweep_batch(self, data, par_dyn, par_obs, steps=False):
+        """data (dim_y, T, B), par_dyn / par_obs (P, 1 + D) -> dict: loglik_total (P, B) = sum_k log p(y_k | y_1..k-1) under row p,
+        nis_mean (P, B), status (P, B) int32 (0, 1 + the first step whose scores are not numbers, or -1 for a row whose weights
+        failed; the totals of such an item are NaN), theta_status (P,) int32 (0, or what the weights call reported: dynamics + 4 x
+        measurement), and with `steps` loglik (P, T, B).  Row p is `type(self)(dyn, obs, par_dyn[p:p+1], par_obs[p:p+1])`'s
+        forward_pass_batch followed by innovations_batch, computed by the dense kernels without storing a filtered moment."""
+        s = self._sweep_setup(par_dyn, par_obs)
+        data = np.asarray(data, dtype=np.float64)
+        if data.ndim != 3 or data.shape[0] != s['Y']:
+            raise ValueError('likelihood sweep: data is (dim_y, T, B)')
+        Y, T, B = data.shape
+        if B < 1 or T < 1:
+            raise ValueError('likelihood sweep: data holds at least one step of at least one trajectory')
+        ld, P = _lib.padded(B), s['P']
+        with _lib.Staging() as stage:
+            d_y = stage.scratch(8 * T * Y * ld)
+            _lib.upload_study(data, Y, ld, d_y)
+            d_tot, d_nis, d_ll, d_st, ts = self._sweep_launch(stage, s, d_y, B, ld, T, steps, False)
+            out = {'theta_status': ts}
+            out['loglik_total'] = d_tot.download((P, ld))[:, :B].copy()
+            out['nis_mean'] = d_nis.download((P, ld))[:, :B].copy()
+            out['status'] = d_st.download((P, ld), dtype=np.int32)[:, :B].copy()
+            if steps:
+                out['loglik'] = d_ll.download((P, T, ld))[:, :, :B].copy()
+        return out
+
+    def fit_kernel_parameters(self, data, par_dyn, par_obs):
+        """The row of the grid with the largest measurement likelihood: (index, par_dyn[index], par_obs[index], table) with
+        table[p] the sum of loglik_total[p] over the trajectories on which every row succeeded (`fit_table`).  Construct the
+        filter with the chosen row: `type(alg)(dyn, obs, par_dyn[index:index + 1], par_obs[index:index + 1])`."""
+        out = self.likelihood_sweep_batch(data, par_dyn, par_obs)
+        index, table = fit_table(out['loglik_total'], out['status'], out['theta_status'])
+        pd, po = np.atleast_2d(np.asarray(par_dyn, dtype=np.float64)), np.atleast_2d(np.asarray(par_obs, dtype=np.float64))
+        return index, pd[index].copy(), po[index].copy(), table
+
+
+class GaussianProcessKalman(_LikelihoodSweep, GaussianInference):
     """ssinf.py:423-463."""
 
     def __init__(self, dyn, obs, kern_par_dyn, kern_par_obs, kernel='rbf', points='ut', point_hyp=None):
@@ -800,8 +945,10 @@ class MultiOutputGaussianProcessKalman(GaussianInference):
         return super().forward_pass_batch(data, x0_mean=x0_mean, x0_cov=x0_cov, raise_on_failure=raise_on_failure)
 
 
-class BayesSardKalman(GaussianInference):
+class BayesSardKalman(_LikelihoodSweep, GaussianInference):
     """ssinf.py:466-502."""
+
+    _sweep_kind = 1
 
     def __init__(self, dyn, obs, kern_par_dyn, kern_par_obs, mulind_dyn=2, mulind_obs=2, points='ut', point_hyp=None):
         t_dyn = BayesSardTransform(dyn.dim_in, dyn.dim_state, kern_par_dyn, mulind_dyn, points, point_hyp)
