@@ -1085,6 +1085,62 @@ int ssmq_filter_sweep_kernel_name(const ssmq_integrand *f_dyn, const ssmq_integr
                                   int N_obs, int D, int Y, char *buf, int len);
 
 /*
+ * Student-t measurement likelihood of a Studentian pass: the recursion of ssmq_student_filter_forward_dev for B measurement
+ * sequences in ONE launch (k_filter_score<>), of which only the scores are kept.  Every trajectory starts from (x0_mean, x0_smat).
+ * Per step k = 0 .. T-1, with the weights in the two handles (dense kernels, no fast path) and (m, S) the running mean and scale matrix:
+ *     m-, S-  = scale[k] * (dynamics transform of (m, S)) + GqG;    y^, S_y, S_yx = scale[k] * (measurement transform of (m-, S-)) + r_smat
+ *     e = y_k - y^;   nis_k = Delta^2 = e' S_y^-1 e (Cholesky of S_y)
+ *     ll_k = lgamma((dof + Y) / 2) - lgamma(dof / 2) - Y / 2 log(dof pi) - 1/2 log det S_y - (dof + Y) / 2 log1p(Delta^2 / dof)
+ *     K = S_yx' S_y^-1;   m = m- + K e;   S = (dof + Delta^2) / (dof + Y) * (S- - K S_y K')
+ * The update is the conditional of a joint Student t with `dof` degrees of freedom and these scale blocks; ll_k is the log-density of
+ * the marginal of y_k under the same joint, t_dof(y^, S_y) - so `dof` is the filter's dof, the one in the update factor, not the
+ * dof_pr behind scale[k].  The expected value of nis_k under that density is Y dof / (dof - 2).
+ *   x0_mean [D], x0_smat [D*D], GqG [D*D], r_smat [Y*Y], scale [T]: host arrays as for ssmq_student_filter_forward_dev (NULL GqG / r_smat
+ *   = zeros);  d_y [T][Y][ld] (device);  d_nis, d_loglik [T][ld] or NULL;  d_loglik_total, d_nis_mean [ld];  d_status [ld] int32:
+ *   1 + the first step whose scores are not numbers (a factorisation failed, a measurement is not finite) - the totals and the
+ *   remaining steps are then NaN - or 0.  ld is a multiple of 64.  A trajectory's results do not depend on the trajectories around it.
+ * Range: both handles t-process BQ transforms (tp_nu > 0) or both sigma-point rules, on the built-in additive-noise model pairs of the
+ * fused time loop with D <= 4, Y <= 2 and 2 <= N_dyn = N_obs <= 2 D + 1 points; dof > 2.  User-defined integrands, models that take
+ * their noise as an argument, truncated / multi-output / GPQ+D / Taylor-GPQD / plain GP or Bayes-Sard handles and shapes without an
+ * instantiation return SSMQ_E_UNSUPPORTED (bad arguments SSMQ_E_ARG) with the range in ssmq_last_error(), before any launch.
+ * T == 0: the totals are zero.  Synchronous.
+ */
+int ssmq_student_scores_dev(ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, ssmq_transform *h_obs, const ssmq_integrand *f_obs,
+                            int64_t B, int64_t ld, int T, const double *d_y, const double *x0_mean, const double *x0_smat,
+                            const double *GqG, const double *r_smat, const double *scale, double dof, double *d_nis, double *d_loglik,
+                            double *d_loglik_total, double *d_nis_mean, int32_t *d_status);
+/* Name of the kernel ssmq_student_scores_dev would run for this pair (the same refusals). */
+int ssmq_student_scores_kernel_name(const ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, const ssmq_transform *h_obs,
+                                    const ssmq_integrand *f_obs, char *buf, int len);
+
+/*
+ * Sweep of a t-process filter by measurement likelihood: ssmq_filter_sweep_dev for the filters whose transforms are t-process
+ * quadratures, over P rows of (par_dyn[p], par_obs[p], nu_dyn[p], nu_obs[p], dof[p]) in ONE launch of k_filter_score<>.
+ *   recursion  SSMQ_RECURSION_GAUSS: the Gaussian recursion and score of ssmq_filter_sweep_dev (StudentProcessKalmanSweep); dof and scale
+ *              are not read.  SSMQ_RECURSION_STUDENT: the recursion and Student-t score of ssmq_student_scores_dev
+ *              (StudentProcessStudent) with dof[p] > 2 and the scale table scale[p][0 .. T-1].
+ *   The weights of both transforms come from one theta-batched ssmq_weights_gp call each ('rbf' kernel), with its iK output: the
+ *   model variance of a transform is (nu - 2 + fx iK fx') / (nu - 2 + N) * model_var, added as the whole matrix where the transform
+ *   has more than one output (the t-process filters build their transforms with one output).
+ *   x0_mean [D] is shared; x0_mat [P][D*D], GQG [P][D*D], R [P][Y*Y] are PER ROW (host; NULL GQG / R = zeros): in the Studentian
+ *   recursion they are scale matrices and change with (dof[p] - 2) / dof[p].
+ *   Everything else - xi_*, par_*, jitter_*, d_y, the outputs, d_status and theta_status - as ssmq_filter_sweep_dev.
+ * Range and refusals: as ssmq_student_scores_dev; P <= 65535.  B == 0: only theta_status is written; T == 0: the totals are zero.
+ * Synchronous.
+ */
+#define SSMQ_RECURSION_GAUSS 0
+#define SSMQ_RECURSION_STUDENT 1
+int ssmq_filter_sweep_t_dev(const ssmq_integrand *f_dyn, const ssmq_integrand *f_obs, int recursion, const double *xi_dyn, int N_dyn,
+                            const double *xi_obs, int N_obs, const double *par_dyn, const double *par_obs, const double *nu_dyn,
+                            const double *nu_obs, const double *dof, int P, double jitter_dyn, double jitter_obs, int D, int Y, int64_t B,
+                            int64_t ld, int T, const double *d_y, const double *x0_mean, const double *x0_mat, const double *GQG,
+                            const double *R, const double *scale, double *d_loglik_total, double *d_nis_mean, double *d_loglik_steps,
+                            int32_t *d_status, int32_t *theta_status);
+/* Name of the kernel ssmq_filter_sweep_t_dev would run for this pair and recursion (the same refusals). */
+int ssmq_filter_sweep_t_kernel_name(const ssmq_integrand *f_dyn, const ssmq_integrand *f_obs, int recursion, int N_dyn, int N_obs, int D,
+                                    int Y, char *buf, int len);
+
+/*
  * Bootstrap particle filter (sequential Monte Carlo; Gordon, Salmond, Smith 1993) of the additive-noise models: the ground truth the
  * moment-matching filters are measured against.  N weighted particles per trajectory, in the time convention of
  * ssmq_filter_forward_dev (both models of step j, 0-based, are evaluated at time j):

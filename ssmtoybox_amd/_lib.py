@@ -298,6 +298,21 @@ _PROTOTYPES = {
                               [c_double_p] * 4 + [ctypes.c_void_p] * 4 + [c_int32_p]),
     'ssmq_filter_sweep_kernel_name': (ctypes.c_int, [ctypes.POINTER(Integrand), ctypes.POINTER(Integrand)] + [ctypes.c_int] * 6 +
                                       [ctypes.c_char_p, ctypes.c_int]),
+    # (h_dyn, f_dyn, h_obs, f_obs, B, ld, T, d_y, x0_mean, x0_smat, GqG, r_smat, scale, dof, d_nis, d_loglik, d_loglik_total, d_nis_mean,
+    #  d_status)
+    'ssmq_student_scores_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Integrand), ctypes.c_void_p, ctypes.POINTER(Integrand),
+                                               ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p] + [c_double_p] * 5 +
+                                [ctypes.c_double] + [ctypes.c_void_p] * 5),
+    'ssmq_student_scores_kernel_name': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Integrand), ctypes.c_void_p,
+                                                       ctypes.POINTER(Integrand), ctypes.c_char_p, ctypes.c_int]),
+    # (f_dyn, f_obs, recursion, xi_dyn, N_dyn, xi_obs, N_obs, par_dyn, par_obs, nu_dyn, nu_obs, dof, P, jitter_dyn, jitter_obs, D, Y, B,
+    #  ld, T, d_y, x0_mean, x0_mat, GQG, R, scale, d_loglik_total, d_nis_mean, d_loglik_steps, d_status, theta_status)
+    'ssmq_filter_sweep_t_dev': (ctypes.c_int, [ctypes.POINTER(Integrand), ctypes.POINTER(Integrand), ctypes.c_int, c_double_p, ctypes.c_int,
+                                               c_double_p, ctypes.c_int] + [c_double_p] * 5 +
+                                [ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int64,
+                                 ctypes.c_int, ctypes.c_void_p] + [c_double_p] * 5 + [ctypes.c_void_p] * 4 + [c_int32_p]),
+    'ssmq_filter_sweep_t_kernel_name': (ctypes.c_int, [ctypes.POINTER(Integrand), ctypes.POINTER(Integrand)] + [ctypes.c_int] * 5 +
+                                        [ctypes.c_char_p, ctypes.c_int]),
     'ssmq_filter_iterated_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Integrand), ctypes.c_void_p, ctypes.POINTER(Integrand),
                                                 ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int] +
                                  [ctypes.c_void_p] * 3 + [c_double_p, c_double_p] + [ctypes.c_void_p] * 4),

@@ -59,8 +59,8 @@ static int sweep_weights(int kind, int D, int N, const double *xi, const double 
 
 // Row p's constant block as upload_consts (ssmq_api_transform.hip) lays out the dense part of a BQ handle's: points and Wc
 // transposed, emv = model_var on every entry (the kernels read the diagonal: SSMQ_EMV_DIAG), the rest - t-process inverse, fast-path
-// data, point records: nothing the dense kernels read - zero.
-static void sweep_block(int D, int E, int N, const double *xi, const double *wm, const double *Wc, const double *Wcc, double model_var, double *s) {
+// data, point records: nothing the dense kernels read - zero.  (Also the dense part of the t-process blocks: ssmq_api_score.hip.)
+void sweep_block(int D, int E, int N, const double *xi, const double *wm, const double *Wc, const double *Wcc, double model_var, double *s) {
     const ConstLayout cs = const_layout(D, E, N, SSMQ_FORM_BQ);
     std::fill(s, s + cs.total, 0.0);
     for (int d = 0; d < D; ++d)

@@ -846,7 +846,9 @@ class _LikelihoodSweep:
         """The sweep on measurements that are already on the device (planes [T][dim_y][ld], ld a multiple of 64): DeviceBuffers
         d_loglik_total [P][ld], d_nis_mean [P][ld], d_loglik [P][T][ld] (None without `steps`), d_status [P][ld] int32 - the caller
         frees them - and theta_status (P,) int32 on the host.  Every trajectory starts from the model's initial moments."""
-        s = self._sweep_setup(par_dyn, par_obs)
+        return self._sweep_dev(self._sweep_setup(par_dyn, par_obs), d_y, B, ld, T, steps)
+
+    def _sweep_dev(self, s, d_y, B, ld, T, steps):
         if ld % 64 or ld < B:
             raise ValueError('likelihood sweep: ld is a multiple of 64 and at least B')
         with _lib.Staging() as stage:
@@ -860,7 +862,9 @@ class _LikelihoodSweep:
         failed; the totals of such an item are NaN), theta_status (P,) int32 (0, or what the weights call reported: dynamics + 4 x
         measurement), and with `steps` loglik (P, T, B).  Row p is `type(self)(dyn, obs, par_dyn[p:p+1], par_obs[p:p+1])`'s
         forward_pass_batch followed by innovations_batch, computed by the dense kernels without storing a filtered moment."""
-        s = self._sweep_setup(par_dyn, par_obs)
+        return self._sweep_batch(self._sweep_setup(par_dyn, par_obs), data, steps)
+
+    def _sweep_batch(self, s, data, steps):
         data = np.asarray(data, dtype=np.float64)
         if data.ndim != 3 or data.shape[0] != s['Y']:
             raise ValueError('likelihood sweep: data is (dim_y, T, B)')
@@ -884,7 +888,10 @@ class _LikelihoodSweep:
         """The row of the grid with the largest measurement likelihood: (index, par_dyn[index], par_obs[index], table) with
         table[p] the sum of loglik_total[p] over the trajectories on which every row succeeded (`fit_table`).  Construct the
         filter with the chosen row: `type(alg)(dyn, obs, par_dyn[index:index + 1], par_obs[index:index + 1])`."""
-        out = self.likelihood_sweep_batch(data, par_dyn, par_obs)
+        return self._sweep_fit(self.likelihood_sweep_batch(data, par_dyn, par_obs), par_dyn, par_obs)
+
+    @staticmethod
+    def _sweep_fit(out, par_dyn, par_obs):
         index, table = fit_table(out['loglik_total'], out['status'], out['theta_status'])
         pd, po = np.atleast_2d(np.asarray(par_dyn, dtype=np.float64)), np.atleast_2d(np.asarray(par_obs, dtype=np.float64))
         return index, pd[index].copy(), po[index].copy(), table
@@ -956,14 +963,144 @@ class BayesSardKalman(_LikelihoodSweep, GaussianInference):
         super().__init__(dyn, obs, t_dyn, t_obs)
 
 
+def _per_row(value, P, name, low, low_ok, default):
+    """A sweep argument that is a scalar or (P,): the (P,) float64 array, `default` for None; ValueError for another shape and for a
+    row at or below `low` (below, with low_ok), naming the row."""
+    v = np.asarray(default if value is None else value, dtype=np.float64)
+    if v.ndim > 1 or (v.ndim == 1 and v.shape[0] != P):
+        raise ValueError('likelihood sweep: {} is a scalar or has one entry per parameter row, ({},); got shape {}'.format(name, P, v.shape))
+    v = np.ascontiguousarray(np.broadcast_to(v, (P,)))
+    bad = ~(v >= low) if low_ok else ~(v > low)
+    bad |= ~np.isfinite(v)
+    if bad.any():
+        p = int(np.flatnonzero(bad)[0])
+        raise ValueError('likelihood sweep: {} of row {} is {!r}; it must be a finite number {} {}'.format(
+            name, p, float(v[p]), 'of at least' if low_ok else 'above', low))
+    return v
+
+
+class _TProcessLikelihoodSweep(_LikelihoodSweep):
+    """Likelihood sweeps of the t-process filters (`ssmq_filter_sweep_t_dev`, k_filter_score<>): `_LikelihoodSweep` over rows of
+    (par_dyn[p], par_obs[p], nu[p], dof[p]).  Row p is the filter constructed with par_dyn[p:p+1], par_obs[p:p+1] (and dof[p]) whose
+    two t-process models have `nu` = nu[p] - `tf_dyn.model.nu` / `tf_obs.model.nu`: as in the reference the constructors' `nu` / `dof_tp`
+    never reaches the model, so that is where a filter's nu is set.  Its score is the Gaussian `innovations`
+    for `StudentProcessKalmanSweep` and `student_scores` for `StudentProcessStudent`.  nu and dof are scalars or (P,) and default to the
+    object's values; nu >= 2, dof > 2 (ValueError naming the row - nothing is replaced silently inside a sweep); dof belongs to the
+    Studentian class only.  Range: the 'rbf' kernel, built-in additive-noise models, D <= 4, Y <= 2, 2 .. 2 D + 1 points.  None of
+    these methods touches fi_mean / fi_cov / status or the weights of the object."""
+
+    def _sweep_setup(self, par_dyn, par_obs, nu=None, dof=None):
+        """Every refusal, before the library is loaded; the arguments of the C entry points that do not depend on the data."""
+        from .ssmod import GaussRV
+        what = 'likelihood sweeps of the t-process filters cover'
+        student = self._recursion == 'student'
+        if is_user_model(self.mod_dyn) or is_user_model(self.mod_obs):
+            raise user_unsupported('the likelihood sweep (built-in models, D <= 4, Y <= 2, at most 2 D + 1 points)')
+        if not self._additive:
+            raise NotImplementedError(what + ' additive-noise models; not implemented for models that take their noise as an argument '
+                                      '(non-additive noise)')
+        if not student:
+            for rv in (self.mod_dyn.init_rv, self.mod_dyn.noise_rv, self.mod_obs.noise_rv):
+                if not isinstance(rv, GaussRV):
+                    raise NotImplementedError(what + ' Gaussian initial state and noise for the Gaussian recursion; not implemented for '
+                                              '{}'.format(type(rv).__name__))
+        D, Y = self.mod_dyn.dim_state, self.mod_obs.dim_out
+        for tf in (self.tf_dyn, self.tf_obs):
+            if not isinstance(tf, StudentTProcessTransform):
+                raise NotImplementedError(what + ' t-process transforms; got {}'.format(type(tf).__name__))
+            if type(tf.model.kernel).__name__ != 'RBFGauss':
+                raise NotImplementedError(what + " the 'rbf' kernel; not implemented for {} (the Monte-Carlo weights of 'rbf-student' "
+                                          'are not swept)'.format(type(tf.model.kernel).__name__))
+            if tf.model.points.shape[0] != D or not 2 <= tf.model.points.shape[1] <= 2 * D + 1:
+                raise NotImplementedError(what + ' 2 .. 2 D + 1 points in the state dimension D <= 4 (Y <= 2); got points {}'.format(
+                    tf.model.points.shape))
+        if D > 4 or Y > 2:
+            raise NotImplementedError(what + ' D <= 4, Y <= 2; got D = {}, Y = {}'.format(D, Y))
+        pd, po = (np.ascontiguousarray(np.atleast_2d(p), dtype=np.float64) for p in (par_dyn, par_obs))
+        if pd.ndim != 2 or po.ndim != 2 or pd.shape[0] != po.shape[0] or pd.shape[0] < 1 or pd.shape[1] != 1 + D or po.shape[1] != 1 + D:
+            raise ValueError('likelihood sweep: par_dyn and par_obs are (P, 1 + D) with the same P >= 1 (row p pairs par_dyn[p] with '
+                             'par_obs[p]); got {} and {}'.format(pd.shape, po.shape))
+        P = pd.shape[0]
+        if P > 65535:
+            raise NotImplementedError(what + ' at most 65535 rows; got {}'.format(P))
+        if dof is not None and not student:
+            raise ValueError('likelihood sweep: dof is the Studentian filters\' (StudentProcessStudent); {} has the Gaussian recursion'.format(
+                type(self).__name__))
+        nu_dyn = _per_row(nu, P, 'nu', 2.0, True, self.tf_dyn.model.nu)
+        nu_obs = _per_row(nu, P, 'nu', 2.0, True, self.tf_obs.model.nu)
+        dofs = _per_row(dof, P, 'dof', 2.0, False, self.dof) if student else None
+        # the additive terms and the initial matrix of every row: scale matrices in the Studentian recursion (StudentianInference.__init__)
+        if student:
+            sc = [(float(d) - 2) / float(d) for d in dofs]
+            S0 = np.ascontiguousarray([c * self.x0_cov for c in sc], dtype=np.float64)
+            gqg = np.ascontiguousarray([self.G.dot(c * self.q_cov).dot(self.G.T) for c in sc], dtype=np.float64)
+            rr = np.ascontiguousarray([c * self.r_cov for c in sc], dtype=np.float64)
+        else:
+            g1, r1 = self._noise()
+            S0, gqg, rr = (np.ascontiguousarray(np.broadcast_to(a, (P,) + np.shape(a)), dtype=np.float64) for a in (self.x0_cov, g1, r1))
+        f_dyn, _ = resolve_integrand(self.mod_dyn.dyn_eval)
+        f_obs, _ = resolve_integrand(self.mod_obs.meas_eval)
+        xd, xo = (np.ascontiguousarray(tf.model.points, dtype=np.float64) for tf in (self.tf_dyn, self.tf_obs))
+        m0 = np.ascontiguousarray(self.x0_mean, dtype=np.float64)
+        dp = _lib.dp
+        return dict(head=[f_dyn, f_obs, 1 if student else 0, dp(xd), xd.shape[1], dp(xo), xo.shape[1], dp(pd), dp(po), dp(nu_dyn), dp(nu_obs),
+                          dp(dofs), P, float(self.tf_dyn.model.kernel.jitter), float(self.tf_obs.model.kernel.jitter), D, Y],
+                    noise=[dp(m0), dp(S0), dp(gqg), dp(rr)], P=P, D=D, Y=Y, dof=dofs, par=(pd, po), nu=(nu_dyn, nu_obs),
+                    keep=[pd, po, xd, xo, nu_dyn, nu_obs, dofs, m0, S0, gqg, rr])
+
+    def likelihood_sweep_kernel_name(self, P=1):
+        """Which kernel `likelihood_sweep_*` run for this filter (the same for every number of rows P)."""
+        D = self.mod_dyn.dim_state
+        s = self._sweep_setup(np.ones((int(P), 1 + D)), np.ones((int(P), 1 + D)))
+        h = s['head']
+        buf = ctypes.create_string_buffer(512)
+        _lib.check(_lib.load().ssmq_filter_sweep_t_kernel_name(h[0], h[1], h[2], h[4], h[6], s['D'], s['Y'], buf, 512),
+                   'ssmq_filter_sweep_t_kernel_name', True)
+        return buf.value.decode()
+
+    def _sweep_launch(self, stage, s, d_y, B, ld, T, steps, device):
+        alloc = stage.device if device else stage.scratch
+        P = s['P']
+        d_tot, d_nis, d_st = alloc(8 * P * ld), alloc(8 * P * ld), alloc(4 * P * ld)
+        d_ll = alloc(8 * P * T * ld) if steps else None
+        ts = np.zeros(P, dtype=np.int32)
+        scale = None if s['dof'] is None else np.ascontiguousarray([self._row_scale(float(d), T) for d in s['dof']], dtype=np.float64)
+        vp = _lib.vp
+        _lib.check(_lib.load().ssmq_filter_sweep_t_dev(*s['head'], B, ld, T, vp(d_y), *s['noise'], _lib.dp(scale), vp(d_tot), vp(d_nis), vp(d_ll),
+                                                       vp(d_st), ts.ctypes.data_as(_lib.c_int32_p)), 'ssmq_filter_sweep_t_dev', True)
+        return d_tot, d_nis, d_ll, d_st, ts
+
+    def likelihood_sweep_dev(self, d_y, B, ld, T, par_dyn, par_obs, nu=None, dof=None, steps=False):
+        """`_LikelihoodSweep.likelihood_sweep_dev` over rows of (par_dyn, par_obs, nu, dof)."""
+        return self._sweep_dev(self._sweep_setup(par_dyn, par_obs, nu, dof), d_y, B, ld, T, steps)
+
+    def likelihood_sweep_batch(self, data, par_dyn, par_obs, nu=None, dof=None, steps=False):
+        """data (dim_y, T, B), par_dyn / par_obs (P, 1 + D), nu / dof scalars or (P,) -> the dict of
+        `_LikelihoodSweep.likelihood_sweep_batch`: loglik_total, nis_mean, status (P, B), theta_status (P,), with `steps` loglik
+        (P, T, B).  Row p: see the class."""
+        return self._sweep_batch(self._sweep_setup(par_dyn, par_obs, nu, dof), data, steps)
+
+    def fit_kernel_parameters(self, data, par_dyn, par_obs, nu=None, dof=None):
+        """The row with the largest measurement likelihood: (index, par_dyn[index], par_obs[index], table) (`fit_table`); nu[index] and
+        dof[index] are the caller's to read off."""
+        return self._sweep_fit(self.likelihood_sweep_batch(data, par_dyn, par_obs, nu, dof), par_dyn, par_obs)
+
+
 class StudentProcessKalman(GaussianInference):
     """ssinf.py:505-552.  As in the reference the transforms are built with dim_out = 1 (I_out = eye(1)), so the whole
-    scaled (E, E) model-variance matrix is added for E > 1."""
+    scaled (E, E) model-variance matrix is added for E > 1.  The class itself has no likelihood sweep (tests/test_sweep_host.py pins
+    that); `StudentProcessKalmanSweep` is this filter with one."""
 
     def __init__(self, dyn, obs, kern_par_dyn, kern_par_obs, kernel='rbf', points='ut', point_hyp=None, nu=3.0):
         t_dyn = StudentTProcessTransform(dyn.dim_in, 1, kern_par_dyn, kernel, points, point_hyp, nu=nu)
         t_obs = StudentTProcessTransform(obs.dim_in, 1, kern_par_obs, kernel, points, point_hyp, nu=nu)
         super().__init__(dyn, obs, t_dyn, t_obs)
+
+
+class StudentProcessKalmanSweep(_TProcessLikelihoodSweep, StudentProcessKalman):
+    """`StudentProcessKalman` - the same constructor, the same filter, bit for bit - with `likelihood_sweep_batch` /
+    `likelihood_sweep_dev` / `likelihood_sweep_kernel_name` / `fit_kernel_parameters` over rows of (par_dyn, par_obs, nu): row p is the
+    `StudentProcessKalman` of that row, scored by `forward_pass_batch` then `innovations_batch`."""
 
 
 class StudentianInference(GaussianInference):
@@ -1000,7 +1137,108 @@ class StudentianInference(GaussianInference):
 
     def _innovations_refusal(self):
         return NotImplementedError('innovation scores cover the additive-noise Gaussian recursion; not implemented for the Studentian '
-                                   'recursion (its predictive density is a Student t, not the Gaussian the scores assume)')
+                                   'recursion (its predictive density is a Student t, not the Gaussian the scores assume): see '
+                                   'student_scores')
+
+    # ---- Student-t measurement likelihood: the Studentian filters' counterpart of the innovation scores ---------------------------
+    def _row_scale(self, dof, steps):
+        """`scale_sequence(steps)` of this filter had it been constructed with `dof`."""
+        return self.scale_sequence(steps) if self.fixed_dof else np.full(steps, (dof - 2) / dof)
+
+    def _student_scores_refusal(self):
+        """Raises what keeps a filter out of `student_scores*` - before the library is touched."""
+        what = 'student scores cover'
+        rng = ('fully-symmetric (sigma-point) and t-process transforms with the \'rbf\' kernel on built-in additive-noise models, D <= 4, '
+               'Y <= 2, 2 .. 2 D + 1 points (the same count for both transforms)')
+        if is_user_model(self.mod_dyn) or is_user_model(self.mod_obs):
+            raise user_unsupported('the student scores (' + rng + ')')
+        if not self._additive:
+            raise NotImplementedError(what + ' additive-noise models; not implemented for models that take their noise as an argument '
+                                      '(non-additive noise)')
+        kinds = set()
+        for tf in (self.tf_dyn, self.tf_obs):
+            if isinstance(tf, (TruncatedUnscentedTransform, TruncatedSphericalRadialTransform, TruncatedGaussHermiteTransform)):
+                raise NotImplementedError(what + ' ' + rng + '; not implemented for truncated transforms ({})'.format(type(tf).__name__))
+            if isinstance(tf, StudentTProcessTransform):
+                if type(tf.model.kernel).__name__ != 'RBFGauss':
+                    raise NotImplementedError(what + " the 'rbf' kernel; not implemented for {} (the Monte-Carlo weights of "
+                                              "'rbf-student')".format(type(tf.model.kernel).__name__))
+                kinds.add('tp')
+            elif isinstance(tf, FullySymmetricStudentTransform):
+                kinds.add('fs')
+            else:
+                raise NotImplementedError(what + ' ' + rng + '; got {}'.format(type(tf).__name__))
+        D, Y = self.mod_dyn.dim_state, self.mod_obs.dim_out
+        n = (self.tf_dyn._num_points(), self.tf_obs._num_points())
+        if len(kinds) != 1 or D > 4 or Y > 2 or n[0] != n[1] or not 2 <= n[0] <= 2 * D + 1:
+            raise NotImplementedError(what + ' ' + rng + '; got D = {}, Y = {}, points {}, transforms {} / {}'.format(
+                D, Y, n, type(self.tf_dyn).__name__, type(self.tf_obs).__name__))
+
+    def student_scores_kernel_name(self):
+        """Which kernel `student_scores*` run for this filter: k_filter_score<..,STU=1>."""
+        self._student_scores_refusal()
+        return self._kernel_name('ssmq_student_scores_kernel_name', unsupported=True)
+
+    def _launch_student_scores(self, lib, B, ld, T, d_y, d_nis, d_ll, d_tot, d_nm, d_st):
+        gqg, rr = self._noise()
+        sc = np.ascontiguousarray(self.scale_sequence(T), dtype=np.float64)
+        m0, S0 = np.ascontiguousarray(self.x0_mean, dtype=np.float64), np.ascontiguousarray(self._initial_cov(), dtype=np.float64)
+        vp, dp = _lib.vp, _lib.dp
+        _lib.check(lib.ssmq_student_scores_dev(*self._pair(), B, ld, T, vp(d_y), dp(m0), dp(S0), dp(gqg), dp(rr), dp(sc),
+                                               ctypes.c_double(self.dof), vp(d_nis), vp(d_ll), vp(d_tot), vp(d_nm), vp(d_st)),
+                   'ssmq_student_scores_dev', True)
+
+    def student_scores_dev(self, d_y, B, ld, T):
+        """Student scores of measurements that are already on the device (planes [T][dim_y][ld], ld a multiple of 64, e.g. from
+        `ssmod.simulate_dev`): DeviceBuffers (d_nis [T][ld], d_loglik [T][ld], d_loglik_total [ld], d_nis_mean [ld], d_status [ld]
+        int32); the caller frees them.  Every trajectory starts from the model's initial moments."""
+        self._student_scores_refusal()
+        if ld % 64 or ld < B:
+            raise ValueError('student scores: ld is a multiple of 64 and at least B')
+        lib = _lib.load()
+        with _lib.Staging() as stage:
+            d_nis, d_ll = stage.device(8 * T * ld), stage.device(8 * T * ld)
+            d_tot, d_nm, d_st = stage.device(8 * ld), stage.device(8 * ld), stage.device(4 * ld)
+            self._launch_student_scores(lib, B, ld, T, d_y, d_nis, d_ll, d_tot, d_nm, d_st)
+            return stage.release(d_nis, d_ll, d_tot, d_nm, d_st)
+
+    def student_scores_batch(self, data):
+        """One-step-ahead Student-t measurement likelihood of every step, data (dim_y, T, B), computed by one scoring pass that stores
+        no filtered moment.  With (m, S) the running mean and scale matrix, y_mean, S_y = sc_k P_y + r_smat the predictive measurement
+        mean and scale matrix of step k and e = y_k - y_mean,
+            nis[k] = Delta^2 = e' S_y^-1 e                     (expected value under the density below: dim_y dof / (dof - 2))
+            loglik[k] = log t_dof(y_k | y_mean, S_y) = lgamma((dof + Y) / 2) - lgamma(dof / 2) - Y / 2 log(dof pi) - log det S_y / 2
+                        - (dof + Y) / 2 log1p(Delta^2 / dof).
+        The filter's update, with its factor (dof + Delta^2) / (dof + dim_y), is the conditional of a joint Student t with `dof`
+        degrees of freedom; this is the marginal of y_k under the same joint - so dof is the filter's `dof`, not the dof_pr of
+        `scale_sequence`.  Returns a dict: nis (T, B), loglik (T, B), loglik_total (B,), nis_mean (B,), status (B,) - 1 + the first
+        step whose scores are not numbers (the totals and the remaining steps are then NaN), 0 if none.  Touches neither fi_mean /
+        fi_cov / status nor the weights."""
+        self._student_scores_refusal()
+        data = np.asarray(data, dtype=np.float64)
+        if data.ndim != 3 or data.shape[0] != self.mod_obs.dim_out:
+            raise ValueError('student scores: data is (dim_y, T, B)')
+        Y, T, B = data.shape
+        if B < 1 or T < 1:
+            raise ValueError('student scores: data holds at least one step of at least one trajectory')
+        lib = _lib.load()
+        ld = _lib.padded(B)
+        with _lib.Staging() as stage:
+            d_y = stage.scratch(8 * T * Y * ld)
+            _lib.upload_study(data, Y, ld, d_y)
+            d_nis, d_ll = stage.scratch(8 * T * ld), stage.scratch(8 * T * ld)
+            d_tot, d_nm, d_st = stage.scratch(8 * ld), stage.scratch(8 * ld), stage.scratch(4 * ld)
+            self._launch_student_scores(lib, B, ld, T, d_y, d_nis, d_ll, d_tot, d_nm, d_st)
+            out = {'nis': _lib.download_study(d_nis, (), T, B, ld), 'loglik': _lib.download_study(d_ll, (), T, B, ld)}
+            out['loglik_total'] = d_tot.download((ld,))[:B].copy()
+            out['nis_mean'] = d_nm.download((ld,))[:B].copy()
+            out['status'] = d_st.download((ld,), dtype=np.int32)[:B].copy()
+        return out
+
+    def student_scores(self, data):
+        """`student_scores_batch` for one trajectory, data (dim_y, T): nis (T,), loglik (T,), loglik_total, nis_mean, status."""
+        out = self.student_scores_batch(np.asarray(data)[..., None])
+        return {k: (v[..., 0] if v.ndim else v) for k, v in out.items()}
 
     def scale_sequence(self, steps):
         """(dof_pr - 2) / dof_pr of every time update (ssinf.py:652-660; dof_fi grows by dim_out per update, :735)."""
@@ -1042,7 +1280,7 @@ class FullySymmetricStudent(StudentianInference):
         super().__init__(dyn, obs, t_dyn, t_obs, dof, fixed_dof)
 
 
-class StudentProcessStudent(StudentianInference):
+class StudentProcessStudent(_TProcessLikelihoodSweep, StudentianInference):
     """Student-t process quadrature Student filter, the TPQSF (ssinf.py:793-857).  kernel='rbf' (the default) builds both
     transforms with the Gaussian-expectation RBF kernel, as this class always has; kernel='rbf-student' builds the
     reference's filter: the weights of both transforms come from the 'rbf-student' kernel, the RBF kernel with Monte-Carlo
