@@ -112,15 +112,18 @@ class GaussianProcessDerTransform(BQTransform):
 
     One launch per batch: `k_apply_gpqd` (dim_in <= 2, observations in registers) or `k_apply_gpqd_lds` (observations in LDS).
     Supported: dim_in <= 6, 2 <= N <= 2 dim_in + 1 points ('ut', 'sr', 'gh' where it fits), outputs <= max(dim_in, 4); `f` the
-    bound dyn_eval / meas_eval of a built-in model that has a Jacobian and additive noise (UNGM, pendulum, constant velocity and
-    their measurement models) or of a model of your own with `device_code` and `device_jacobian` (compiled at run time).
+    bound dyn_eval / meas_eval of a built-in model that has a Jacobian and additive noise (UNGM, pendulum, constant velocity,
+    coordinated turn and the UNGM, pendulum, radar and bearing measurement models) or of a model of your own with `device_code`
+    and `device_jacobian` (compiled at run time).
     Everything else raises NotImplementedError naming this range, before the library is touched.  `wm`, `Wc`, `Wcc` and
     `model.model_var` may be replaced after construction; the next call picks them up."""
 
     _RANGE = ('GaussianProcessDerTransform supports dim_in <= 6, 2 <= N <= 2 dim_in + 1 points, 1 <= outputs <= max(dim_in, 4) and the '
-              'bound dyn_eval / meas_eval of a built-in model with a Jacobian and additive noise (UNGM, pendulum, constant velocity) or '
+              'bound dyn_eval / meas_eval of a built-in model with a Jacobian and additive noise (UNGM, pendulum, constant velocity, '
+              'coordinated turn, radar, bearings) or '
               'of a model with device_code and device_jacobian')
-    _BUILTIN = (_lib.F_UNGM_DYN, _lib.F_UNGM_MEAS, _lib.F_PENDULUM_DYN, _lib.F_PENDULUM_MEAS, _lib.F_CV_DYN)
+    _BUILTIN = (_lib.F_UNGM_DYN, _lib.F_UNGM_MEAS, _lib.F_PENDULUM_DYN, _lib.F_PENDULUM_MEAS, _lib.F_CV_DYN, _lib.F_CT_DYN,
+                _lib.F_RADAR2D_MEAS, _lib.F_BEARING_MEAS)
 
     def __init__(self, dim_in, dim_out, kern_par, point_str='ut', point_par=None, estimate_par=False, which_der=None):
         if not (1 <= int(dim_in) <= 6 and 1 <= int(dim_out) <= max(int(dim_in), 4)):

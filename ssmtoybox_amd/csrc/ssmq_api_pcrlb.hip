@@ -174,11 +174,7 @@ int pcrlb_check(const char *what, const ssmq_integrand *f_dyn, const ssmq_integr
             set_error(msg);
             return SSMQ_E_ARG;
         }
-    if (!is_user_integrand(f_obs) && f_obs->n_idx == 0 && fio.din != D && fio.din != 1) {
-        snprintf(msg, sizeof(msg), "%s: a Jacobian of 1 < din < D columns without a state index has no placement (numpy raises there)", what);
-        set_error(msg);
-        return SSMQ_E_UNSUPPORTED;
-    }
+    // (a built-in Jacobian of 1 < din < D columns without a state index lands in the leading din columns: jac_front_builtin)
     if ((!is_user_integrand(f_dyn) && !pcrlb_builtin_dyn_shape(D)) || (!is_user_integrand(f_obs) && !pcrlb_builtin_obs_shape(D, Y))) {
         snprintf(msg, sizeof(msg), "%s: no kernel for this built-in shape (D = %d, Y = %d); range: %s", what, D, Y, kRange);
         set_error(msg);

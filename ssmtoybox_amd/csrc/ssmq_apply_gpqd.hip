@@ -104,14 +104,17 @@ int launch_apply_gpqd(const ssmq_transform *h, int din, const ssmq_integrand *f,
     if (is_user_integrand(f)) return rtc_launch_gpqd(f, a, lds, s, name, dry_run);      // (makes the checks of that route)
     if (name) *name = lds ? "k_apply_gpqd_lds" : "k_apply_gpqd";
     if (!integrand_has_jacobian(f->id) || f->id == SSMQ_F_UNGMNA_DYN || f->id == SSMQ_F_UNGMNA_MEAS) {
-        set_error("GPQ+D: built-in models with a Jacobian and additive noise only (UNGM, pendulum, constant velocity)");
+        set_error("GPQ+D: built-in models with a Jacobian and additive noise only (UNGM, pendulum, constant velocity, coordinated turn, "
+                  "radar, bearings)");
         return SSMQ_E_UNSUPPORTED;
     }
-    if (f->n_idx == 0 && din != D && din != 1) {
-        set_error("GPQ+D: a Jacobian of 1 < din < D columns without a state index has no placement");
+    // (a Jacobian of 1 < din < D columns without a state index lands in the leading din columns, as jac_front_builtin places it)
+    if (!jacobian_fits(f->id, D, E)) {
+        set_error("GPQ+D: this model's Jacobian does not fit the shape (D, E) = (" + std::to_string(D) + ", " + std::to_string(E) + ")");
         return SSMQ_E_UNSUPPORTED;
     }
-    const bool have = (D == 1 && E == 1) || (D == 2 && (E == 1 || E == 2)) || (D == 4 && E == 4);
+    const bool have = (D == 1 && E == 1) || (D == 2 && (E == 1 || E == 2)) || (D == 4 && (E == 2 || E == 4)) ||
+                      (D == 5 && (E == 2 || E == 4 || E == 5));
     if (!have) {
         set_error("GPQ+D: no kernel for a built-in model of this shape (D, E) = (" + std::to_string(D) + ", " + std::to_string(E) + ")");
         return SSMQ_E_UNSUPPORTED;
@@ -120,7 +123,11 @@ int launch_apply_gpqd(const ssmq_transform *h, int din, const ssmq_integrand *f,
     if (D == 1) launch_reg<1, 1>(a, s);
     else if (D == 2 && E == 1) launch_reg<2, 1>(a, s);
     else if (D == 2) launch_reg<2, 2>(a, s);
-    else launch_lds<4, 4>(a, s);
+    else if (D == 4 && E == 2) launch_lds<4, 2>(a, s);
+    else if (D == 4) launch_lds<4, 4>(a, s);
+    else if (E == 2) launch_lds<5, 2>(a, s);
+    else if (E == 4) launch_lds<5, 4>(a, s);
+    else launch_lds<5, 5>(a, s);
     return hip_fail(hipGetLastError(), lds ? "k_apply_gpqd_lds" : "k_apply_gpqd");
 }
 

@@ -54,23 +54,32 @@ __host__ __device__ constexpr inline int gpqd_lds_items(int D, int E) {
     return E * gpqd_layout(D).mx * 16 * 8 <= 65536 ? 16 : 8;
 }
 
-// the built-in models that have a Jacobian and additive noise (ssmq_device.h: jac_integrand)
+// the built-in models that have a Jacobian and additive noise (ssmq_device.h: jac_integrand); a tracking model's case is compiled
+// wherever its Jacobian's is (jacobian_fits: the launcher refuses the other pairs), so no shape gets a Jacobian without values
+template <int D, int E>
 __device__ __forceinline__ void gpqd_eval_builtin(int id, const double *xs, double t, const FPar &fp, double *o) {
-#define SSMQ_CASE(F)                            \
-    case F: {                                   \
-        Fn<F> fn;                               \
-        fn.init(t, fp);                         \
-        fn.template eval<SSMQ_MAX_FIDX>(xs, o); \
-    } break;
+#define SSMQ_CASE_IF(F, COND)                       \
+    case F:                                         \
+        if constexpr (COND) {                       \
+            Fn<F> fn;                               \
+            fn.init(t, fp);                         \
+            fn.template eval<SSMQ_MAX_FIDX>(xs, o); \
+        }                                           \
+        break;
+#define SSMQ_CASE(F) SSMQ_CASE_IF(F, true)
     switch (id) {
         SSMQ_CASE(SSMQ_F_UNGM_DYN)
         SSMQ_CASE(SSMQ_F_UNGM_MEAS)
         SSMQ_CASE(SSMQ_F_PENDULUM_DYN)
         SSMQ_CASE(SSMQ_F_PENDULUM_MEAS)
         SSMQ_CASE(SSMQ_F_CV_DYN)
+        SSMQ_CASE_IF(SSMQ_F_CT_DYN, D >= 5 && E >= 5)
+        SSMQ_CASE_IF(SSMQ_F_RADAR2D_MEAS, D >= 2 && E >= 2)
+        SSMQ_CASE_IF(SSMQ_F_BEARING_MEAS, D >= 2)
         default: break;
     }
 #undef SSMQ_CASE
+#undef SSMQ_CASE_IF
 }
 
 // f(x) in o[E] and, if der, J(x) L in JL[E * D] (else untouched) at the point x[D]; L packed lower
@@ -102,13 +111,13 @@ __device__ __forceinline__ void gpqd_point(const GpqdArgs &a, const double *x, c
         }
 #pragma unroll
         for (int e = 0; e < SSMQ_MAX_DIM; ++e) oo[e] = 0.0;
-        gpqd_eval_builtin(a.fid, xs, t, a.fp, oo);
+        gpqd_eval_builtin<D, E>(a.fid, xs, t, a.fp, oo);
 #pragma unroll
         for (int e = 0; e < E; ++e) o[e] = oo[e];
         if (der) {
 #pragma unroll
             for (int i = 0; i < E * D; ++i) Js[i] = 0.0;
-            jac_integrand(a.fid, xs, t, a.fp, Js, D);
+            jac_integrand<E, D, false>(a.fid, xs, t, a.fp, Js, D, E);
             // placement into the columns of the full state, as jac_front_builtin (state index, broadcast of a one-column Jacobian)
 #pragma unroll
             for (int e = 0; e < E; ++e)

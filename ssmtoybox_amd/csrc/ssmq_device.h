@@ -566,12 +566,82 @@ __device__ __forceinline__ void eval_integrand(int id, const double *xs, double 
 }
 
 // Jacobian of integrand `id` at xs with respect to its own inputs (the leading DIN of them): J[e * ldj + k] = d out_e / d xs_k.
-// Only the models whose dyn_fcn_dx / meas_fcn_dx the reference implements (ssmod.py:271-272, 305-306, 363-365, 848-852,
-// 1063-1064, 1088-1089, 1117-1118; every other model's returns None there and its ExtendedKalman raises).  Formulas as written
-// in the reference - including ConstantVelocity's, which returns the TRANSPOSE of its transition matrix (ssmod.py:848-852).
-// Returns false for an integrand without one.
-__device__ __forceinline__ bool jac_integrand(int id, const double *xs, double t, const FPar &fp, double *J, int ldj) {
+// Seven models whose dyn_fcn_dx / meas_fcn_dx the reference implements (ssmod.py:271-272, 305-306, 363-365, 848-852, 1063-1064,
+// 1088-1089, 1117-1118), formulas as written there - including ConstantVelocity's, which returns the TRANSPOSE of its transition
+// matrix (ssmod.py:848-852) - and the three tracking models whose methods are `pass` in the reference: coordinated turn, radar,
+// bearings.  The reentry models, ConstantTurnRateSpeed and Smooth10D have none: false.
+//
+// EB, KB: the rows and the pitch the caller's J can hold (its compile-time shape; SSMQ_MAX_DIM at the run-time sizes) - a case that
+// does not fit them is not compiled into that instantiation (a <1, 1> body has a J of one element) and returns false; the
+// launchers refuse such a pair beforehand (jacobian_fits).  RT: the run-time-size body (E known at run time only); false: a
+// register-resident body, instantiated with EB = E.  E: the outputs of the transform, the bearings' sensor count.
+//
+// The three tracking Jacobians are written with the expressions of their Fn<>::eval, so that a front end that evaluates both
+// forms sincos, the square root and the quotients once.  Not guarded, as the model functions are not: omega = 0 exactly (0 / 0,
+// as in the reference's dyn_fcn) and a target exactly at a sensor (1 / 0).  c_om and d_om cancel for small theta = omega dt
+// (theta b - a = -theta^3 / 3 + ..): absolute error eps (|theta b| + |a|) / omega^2, relative eps / theta^2 - 8e-12 at the
+// reference's 3 deg / s and dt = 0.1, left as it is.
+template <int EB, int KB, bool RT>
+__device__ __forceinline__ bool jac_integrand(int id, const double *xs, double t, const FPar &fp, double *J, int ldj, int E) {
     switch (id) {
+        case SSMQ_F_CT_DYN:
+            if constexpr (EB >= 5 && KB >= 5) {
+                // state [x, vx, y, vy, om]; theta = om dt, a = sin theta, b = cos theta, c = a / om, d = (1 - b) / om,
+                // c_om = dc / dom = (theta b - a) / om^2 = (dt b - c) / om,  d_om = dd / dom = (theta a - (1 - b)) / om^2 = (dt a - d) / om
+                const double dt = fp.p[0], om = xs[4];
+                double a, b;
+                sincos_nr(om * dt, &a, &b);
+                const double c = a / om, d = (1.0 - b) / om;
+                const double iom = div_nr(1.0, om);
+                const double c_om = (dt * b - c) * iom, d_om = (dt * a - d) * iom;
+                J[0] = 1.0; J[1] = c; J[3] = -d; J[4] = xs[1] * c_om - xs[3] * d_om;
+                J[ldj + 1] = b; J[ldj + 3] = -a; J[ldj + 4] = -dt * (a * xs[1] + b * xs[3]);
+                J[2 * ldj + 1] = d; J[2 * ldj + 2] = 1.0; J[2 * ldj + 3] = c; J[2 * ldj + 4] = xs[1] * d_om + xs[3] * c_om;
+                J[3 * ldj + 1] = a; J[3 * ldj + 3] = b; J[3 * ldj + 4] = dt * (b * xs[1] - a * xs[3]);
+                J[4 * ldj + 4] = 1.0;
+                return true;
+            } else {
+                return false;
+            }
+        case SSMQ_F_RADAR2D_MEAS:
+            if constexpr (EB >= 2 && KB >= 2) {
+                Fn<SSMQ_F_RADAR2D_MEAS> fn;
+                fn.init(t, fp);
+                const double dx = xs[0] - fn.lx, dy = xs[1] - fn.ly;
+                const double r2 = dx * dx + dy * dy;
+                double rg, irg;
+                sqrt_rsqrt(r2, rg, irg);
+                const double ir2 = irg * irg;
+                J[0] = dx * irg; J[1] = dy * irg;
+                J[ldj] = -dy * ir2; J[ldj + 1] = dx * ir2;
+                return true;
+            } else {
+                return false;
+            }
+        case SSMQ_F_BEARING_MEAS:
+            if constexpr (KB >= 2) {
+                // one (x, y) pair of constants per sensor.  A register-resident body is instantiated with EB = E = the sensor count:
+                // the loop bound is the only bound (as Fn<SSMQ_F_BEARING_MEAS>::eval); the run-time sizes test E and n_par.
+                constexpr int SB = EB < SSMQ_MAX_FPAR / 2 ? EB : SSMQ_MAX_FPAR / 2;
+                if constexpr (RT) {
+#pragma unroll 1
+                    for (int s = 0; s < SB && s < E && 2 * s < fp.n_par; ++s) {
+                        const double dx = xs[0] - fp.p[2 * s], dy = xs[1] - fp.p[2 * s + 1];
+                        const double ir2 = div_nr(1.0, dx * dx + dy * dy);
+                        J[s * ldj] = -dy * ir2; J[s * ldj + 1] = dx * ir2;
+                    }
+                } else {
+#pragma unroll
+                    for (int s = 0; s < SB; ++s) {
+                        const double dx = xs[0] - fp.p[2 * s], dy = xs[1] - fp.p[2 * s + 1];
+                        const double ir2 = div_nr(1.0, dx * dx + dy * dy);
+                        J[s * ldj] = -dy * ir2; J[s * ldj + 1] = dx * ir2;
+                    }
+                }
+                return true;
+            } else {
+                return false;
+            }
         case SSMQ_F_UNGM_DYN: {
             const double x2 = xs[0] * xs[0], d = 1.0 + x2;
             J[0] = 0.5 + div_nr(25.0 * (1.0 - x2), d * d);
@@ -617,9 +687,17 @@ __device__ __forceinline__ bool jac_integrand(int id, const double *xs, double t
         default: return false;
     }
 }
+// whether the case of a model that has a Jacobian is compiled into a body of D inputs and E outputs (the tests of jac_integrand)
+__host__ __device__ inline bool jacobian_fits(int id, int D, int E) {
+    if (id == SSMQ_F_CT_DYN) return D >= 5 && E >= 5;
+    if (id == SSMQ_F_RADAR2D_MEAS) return D >= 2 && E >= 2;
+    if (id == SSMQ_F_BEARING_MEAS) return D >= 2 && E >= 1 && E <= SSMQ_MAX_FPAR / 2;
+    return true;
+}
 __host__ __device__ inline bool integrand_has_jacobian(int id) {
     return id == SSMQ_F_UNGM_DYN || id == SSMQ_F_UNGMNA_DYN || id == SSMQ_F_PENDULUM_DYN || id == SSMQ_F_CV_DYN ||
-           id == SSMQ_F_UNGM_MEAS || id == SSMQ_F_UNGMNA_MEAS || id == SSMQ_F_PENDULUM_MEAS;
+           id == SSMQ_F_UNGM_MEAS || id == SSMQ_F_UNGMNA_MEAS || id == SSMQ_F_PENDULUM_MEAS ||
+           id == SSMQ_F_CT_DYN || id == SSMQ_F_RADAR2D_MEAS || id == SSMQ_F_BEARING_MEAS;
 }
 
 // Host: the time-dependent constant of integrand `id` for times 0..T-1 (what Fn<id>::init would compute), or false if the

@@ -25,7 +25,8 @@ struct EkfEntry {
 };
 #define SSMQ_EKF(D, Y) \
     {D, Y, {&launch_ekf<D, Y, false>, &launch_ekf<D, Y, true>}, {"k_ekf_loop<D=" #D ",Y=" #Y ">", "k_ekf_loop_keep<D=" #D ",Y=" #Y ">"}}
-static const EkfEntry kEkf[] = {SSMQ_EKF(1, 1), SSMQ_EKF(2, 1), SSMQ_EKF(2, 2), SSMQ_EKF(4, 1), SSMQ_EKF(4, 2), SSMQ_EKF(4, 4)};
+static const EkfEntry kEkf[] = {SSMQ_EKF(1, 1), SSMQ_EKF(2, 1), SSMQ_EKF(2, 2), SSMQ_EKF(4, 1), SSMQ_EKF(4, 2), SSMQ_EKF(4, 4),
+                                 SSMQ_EKF(5, 2), SSMQ_EKF(5, 4)};
 
 // 1 launched (dry_run: a kernel exists, its name set), 0 this pass keeps the launch loop, < 0 error
 int try_launch_ekf_loop(const FilterPass &p, double *pm, double *pP, double *pC) {
@@ -39,12 +40,14 @@ int try_launch_ekf_loop(const FilterPass &p, double *pm, double *pP, double *pC)
     const ssmq_transform *hs[2] = {p.hd, p.ho};
     const ssmq_integrand *fs[2] = {p.fd, p.fo};
     for (int i = 0; i < 2; ++i) {
-        if (!integrand_info(fs[i]->id, &fi[i]) || fi[i].dout != hs[i]->E || fs[i]->n_idx < 0 || fs[i]->n_idx > SSMQ_MAX_FIDX) return 0;
+        if (!integrand_info(fs[i]->id, &fi[i])) return 0;
+        if (fs[i]->id == SSMQ_F_BEARING_MEAS) fi[i].dout = fs[i]->n_par / 2;      // (one output per sensor: check_integrand)
+        if (fi[i].dout != hs[i]->E || fs[i]->n_idx < 0 || fs[i]->n_idx > SSMQ_MAX_FIDX) return 0;
         if (fs[i]->n_idx > 0) {
             if (fs[i]->n_idx < fi[i].din) return 0;
             for (int k = 0; k < fs[i]->n_idx; ++k)
                 if (fs[i]->idx[k] < 0 || fs[i]->idx[k] >= D) return 0;
-        } else if (fi[i].din != D && fi[i].din != 1) {
+        } else if (fi[i].din > D) {
             return 0;
         }
     }

@@ -79,7 +79,7 @@ __device__ __forceinline__ void jac_front_builtin(const LinArgs &a, const int64_
     const int pj = DT > 0 ? DM : din;
 #pragma unroll
     for (int i = 0; i < E * pj; ++i) Js[i] = 0.0;
-    jac_integrand(a.fid, xs, t, a.fp, Js, pj);
+    jac_integrand<EM, DM, DT == 0>(a.fid, xs, t, a.fp, Js, pj, E);
 #pragma unroll
     for (int e = 0; e < E; ++e)
 #pragma unroll

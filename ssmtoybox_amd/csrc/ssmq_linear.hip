@@ -1,7 +1,8 @@
 // The linearisation and the Taylor-GPQD transform for the built-in models: the instantiations of k_linearize<DT, ET> and
 // k_taylor_gpqd<DT, ET> (ssmq_jacobian_kernel.h, where the transforms are described) and the one launcher of both forms.  The
 // Jacobian is the model's own (ssmq_device.h: jac_integrand - the seven models whose dyn_fcn_dx / meas_fcn_dx the reference
-// implements); a user model's kernels are compiled for it at run time (ssmq_rtc.hip).
+// implements and the three tracking models: coordinated turn, radar, bearings); a user model's kernels are compiled for it at run
+// time (ssmq_rtc.hip).
 #include "ssmq_device.h"
 #include "ssmq_host.h"
 #include "ssmq_math.h"
@@ -22,8 +23,9 @@ static void launch_shape(const TaylorGpqdArgs &a, hipStream_t s) {
     if constexpr (LIN) hipLaunchKernelGGL((k_linearize<DT, ET>), grid, block, 0, s, static_cast<const LinArgs &>(a));
     else hipLaunchKernelGGL((k_taylor_gpqd<DT, ET>), grid, block, 0, s, a);
 }
-// register-resident bodies for the (D, E) pairs of the seven models (0.6-0.7 of HBM), the run-time-size body for the rest
-// (0.13-0.21) - and for every shape under the form's switch (tools/alt_paths.sh, tests)
+// register-resident bodies for the (D, E) pairs of the models that have a Jacobian (0.6-0.7 of HBM) - constant velocity or the
+// coordinated turn with radar or four bearings among them - the run-time-size body for the rest (0.13-0.21; other sensor counts) -
+// and for every shape under the form's switch (tools/alt_paths.sh, tests)
 template <bool LIN>
 static void launch_ladder(const TaylorGpqdArgs &a, hipStream_t s) {
     const int D = a.D, E = a.E;
@@ -31,8 +33,19 @@ static void launch_ladder(const TaylorGpqdArgs &a, hipStream_t s) {
     else if (D == 1 && E == 1) launch_shape<LIN, 1, 1>(a, s);
     else if (D == 2 && E == 1) launch_shape<LIN, 2, 1>(a, s);
     else if (D == 2 && E == 2) launch_shape<LIN, 2, 2>(a, s);
+    else if (D == 4 && E == 2) launch_shape<LIN, 4, 2>(a, s);
     else if (D == 4 && E == 4) launch_shape<LIN, 4, 4>(a, s);
-    else launch_shape<LIN, 0, 0>(a, s);
+    else if (D == 5 && (E == 2 || E == 4 || E == 5)) {
+        // the linearisation only: the D = 5 bodies of k_taylor_gpqd index a Cholesky factor in scratch memory and
+        // are not instantiated - those shapes keep the run-time-size body there
+        if constexpr (LIN) {
+            if (E == 2) launch_shape<LIN, 5, 2>(a, s);
+            else if (E == 4) launch_shape<LIN, 5, 4>(a, s);
+            else launch_shape<LIN, 5, 5>(a, s);
+        } else {
+            launch_shape<LIN, 0, 0>(a, s);
+        }
+    } else launch_shape<LIN, 0, 0>(a, s);
 }
 
 // h: a linearisation or a Taylor-GPQD handle (D, E, and for the latter alpha, ell and the optional variance planes); din: the
@@ -54,8 +67,10 @@ int launch_jacobian(const ssmq_transform *h, int din, const ssmq_integrand *f, c
         set_error(what + ": this model has no Jacobian (its dyn_fcn_dx / meas_fcn_dx returns None in the reference too)");
         return SSMQ_E_UNSUPPORTED;
     }
-    if (f->n_idx == 0 && din != D && din != 1) {
-        set_error(what + ": a Jacobian of 1 < din < D columns without a state index has no placement (numpy raises there)");
+    // (a Jacobian of 1 < din < D columns without a state index lands in the leading din columns, the rest zero: how a user model's
+    // is placed and how meas_eval reads its inputs; din == 1 < D is the pendulum's broadcast)
+    if (!jacobian_fits(f->id, D, E)) {
+        set_error(what + ": this model's Jacobian does not fit the shape (D, E) = (" + std::to_string(D) + ", " + std::to_string(E) + ")");
         return SSMQ_E_UNSUPPORTED;
     }
     if (lin) launch_ladder<true>(a, s);

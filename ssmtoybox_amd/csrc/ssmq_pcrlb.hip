@@ -1,15 +1,18 @@
 // Posterior Cramer-Rao sums for the built-in models: the instantiations of k_pcrlb_dyn<D, D> / k_pcrlb_obs<D, Y>
 // (ssmq_pcrlb_kernel.h, where mapping and summation order are described) for the models that have a Jacobian (ssmq_device.h:
-// jac_integrand) - transitions of D = 1 (UNGM), 2 (pendulum), 4 (constant velocity), measurements with one output (UNGM, pendulum) on
-// any state of D <= 6, reached through a state index or the reference's one-column broadcast - and the launcher of both kernels of a
-// pair; a user model's kernel is compiled for it at run time (ssmq_rtc.hip: rtc_launch_pcrlb).
+// jac_integrand) - transitions of D = 1 (UNGM), 2 (pendulum), 4 (constant velocity), 5 (coordinated turn), measurements with one
+// output (UNGM, pendulum) on any state of D <= 6, reached through a state index or the reference's one-column broadcast, radar on
+// D = 4, 5 and four bearings on D = 5 - and the launcher of both kernels of a pair; a user model's kernel is compiled for it at
+// run time (ssmq_rtc.hip: rtc_launch_pcrlb).
 #include "ssmq_pcrlb.h"
 #include "ssmq_pcrlb_kernel.h"
 
 namespace ssmq {
 
-bool pcrlb_builtin_dyn_shape(int D) { return D == 1 || D == 2 || D == 4; }
-bool pcrlb_builtin_obs_shape(int D, int Y) { return D >= 1 && D <= kPcrlbMaxD && Y == 1; }
+bool pcrlb_builtin_dyn_shape(int D) { return D == 1 || D == 2 || D == 4 || D == 5; }
+bool pcrlb_builtin_obs_shape(int D, int Y) {
+    return (D >= 1 && D <= kPcrlbMaxD && Y == 1) || ((D == 4 || D == 5) && Y == 2) || (D == 5 && Y == 4);
+}
 
 namespace {
 
@@ -33,9 +36,9 @@ template <int D>
 void launch_dyn(const PcrlbArgs &a, unsigned grid, hipStream_t s) {
     hipLaunchKernelGGL((k_pcrlb_dyn<D, D>), dim3(grid), dim3(kPcrlbBlock), 0, s, a);
 }
-template <int D>
+template <int D, int Y = 1>
 void launch_obs(const PcrlbArgs &a, unsigned grid, hipStream_t s) {
-    hipLaunchKernelGGL((k_pcrlb_obs<D, 1>), dim3(grid), dim3(kPcrlbBlock), 0, s, a);
+    hipLaunchKernelGGL((k_pcrlb_obs<D, Y>), dim3(grid), dim3(kPcrlbBlock), 0, s, a);
 }
 
 // the argument block of one model's kernel; E: its outputs, W: Qi / Ri [E][E]
@@ -74,6 +77,7 @@ int launch_pcrlb(const PcrlbLaunch &h, hipStream_t s, const char **name_dyn, con
             if (D == 1) launch_dyn<1>(a, grid, s);
             else if (D == 2) launch_dyn<2>(a, grid, s);
             else if (D == 4) launch_dyn<4>(a, grid, s);
+            else if (D == 5) launch_dyn<5>(a, grid, s);
             else {
                 set_error("k_pcrlb_dyn: no instantiation for this built-in shape");
                 return SSMQ_E_UNSUPPORTED;
@@ -89,11 +93,14 @@ int launch_pcrlb(const PcrlbLaunch &h, hipStream_t s, const char **name_dyn, con
     } else {
         if (name_obs) *name_obs = "k_pcrlb_obs";
         if (!dry_run) {
-            if (Y != 1) {
+            if (!pcrlb_builtin_obs_shape(D, Y)) {
                 set_error("k_pcrlb_obs: no instantiation for this built-in shape");
                 return SSMQ_E_UNSUPPORTED;
             }
-            switch (D) {
+            if (Y == 2 && D == 4) launch_obs<4, 2>(a, grid, s);
+            else if (Y == 2) launch_obs<5, 2>(a, grid, s);
+            else if (Y == 4) launch_obs<5, 4>(a, grid, s);
+            else switch (D) {
                 case 1: launch_obs<1>(a, grid, s); break;
                 case 2: launch_obs<2>(a, grid, s); break;
                 case 3: launch_obs<3>(a, grid, s); break;

@@ -199,11 +199,12 @@ class _DeviceApply:
 class LinearizationTransform(_DeviceApply, MomentTransform):
     """First-order Taylor (linearisation) transform of the extended Kalman filter (mtran.py:49-59):
     mean_f = f(mean), J = f(mean, dx=True), cov_fx = J cov, cov_f = cov_fx J' - one launch of `k_linearize`
-    (csrc/ssmq_linear.hip) for a batch.  `f` must be the bound dyn_eval / meas_eval of a model whose Jacobian the reference
-    implements (UNGM, UNGM with non-additive noise, pendulum, constant velocity: ssmod.py dyn_fcn_dx / meas_fcn_dx); for the
-    others the reference's Jacobian is None and its apply() raises - here `SsmqError` (SSMQ_E_UNSUPPORTED).  A model of your own
-    (`device_code`) runs if it also has a `device_jacobian`: `k_linearize_fn`, compiled for the model and its shape at run time
-    (dim <= 6), its Jacobian in the leading columns of the (E, dim) matrix."""
+    (csrc/ssmq_linear.hip) for a batch.  `f` must be the bound dyn_eval / meas_eval of a built-in model with a Jacobian: those
+    the reference implements (UNGM, UNGM with non-additive noise, pendulum, constant velocity: ssmod.py dyn_fcn_dx / meas_fcn_dx)
+    and the coordinated turn, radar and bearing models; for the others (reentry, ConstantTurnRateSpeed, Smooth10D) - `SsmqError`
+    (SSMQ_E_UNSUPPORTED).  A measurement Jacobian narrower than the state without a state_index fills the leading columns.
+    A model of your own (`device_code`) runs if it also has a `device_jacobian`: `k_linearize_fn`, compiled for the model and
+    its shape at run time (dim <= 6), its Jacobian in the leading columns of the (E, dim) matrix."""
 
     def __init__(self, dim):
         self.dim = dim

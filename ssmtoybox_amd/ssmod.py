@@ -280,7 +280,8 @@ class TransitionModel:
         return self.dyn_fcn(xq[:self.dim_state], xq[-self.dim_noise:], time)
 
     def dyn_fcn_dx(self, x, q, time):
-        """Jacobian of the dynamics (ssmod.py:105-127): implemented by UNGM, UNGM-NA, pendulum and constant velocity only."""
+        """Jacobian of the dynamics (ssmod.py:105-127): UNGM, UNGM-NA, pendulum and constant velocity as in the reference, and the
+        coordinated turn (the reference's method is `pass`).  The reentry models, ConstantTurnRateSpeed and Smooth10D have none."""
         return None
 
     def check_jacobian(self, points, time=0, rel_step=1e-5):
@@ -429,6 +430,19 @@ class CoordinatedTurnTransition(TransitionModel):
         return np.array([x[0] + c * x[1] - d * x[3], b * x[1] - a * x[3], d * x[1] + x[2] + c * x[3],
                          a * x[1] + b * x[3], x[4]]) + q
 
+    def dyn_fcn_dx(self, x, q, *args):
+        """The NumPy twin of the device Jacobian (csrc/ssmq_device.h: jac_integrand).  c_om = dc / dom and
+        d_om = dd / dom cancel for small om dt (relative error eps / (om dt)^2); om = 0 exactly is 0 / 0, as in dyn_fcn."""
+        om, dt = x[4], self.dt
+        a, b = np.sin(om * dt), np.cos(om * dt)
+        c, d = a / om, (1 - b) / om
+        c_om, d_om = (dt * b - c) / om, (dt * a - d) / om
+        return np.array([[1, c, 0, -d, x[1] * c_om - x[3] * d_om],
+                         [0, b, 0, -a, -dt * (a * x[1] + b * x[3])],
+                         [0, d, 1, c, x[1] * d_om + x[3] * c_om],
+                         [0, a, 0, b, dt * (b * x[1] - a * x[3])],
+                         [0, 0, 0, 0, 1.0]])
+
 
 class ConstantTurnRateSpeed(TransitionModel):
     """ssmod.py:699-780 (non-additive noise: input [x(5), q(2)])."""
@@ -566,7 +580,13 @@ class MeasurementModel:
                 xr = xr[self.state_index]
             if self.noise_additive:
                 out = np.zeros((self.dim_out, self.dim_state))
-                out[:, self.state_index] = self.meas_fcn_dx(xr, self.zero_r, time)
+                jac = self.meas_fcn_dx(xr, self.zero_r, time)
+                if self.state_index is None and np.ndim(jac) == 2 and np.shape(jac)[1] > 1:
+                    # a Jacobian of several columns without a state index (radar on the position-first state): the leading
+                    # columns, where meas_fcn reads its inputs and a user model's Jacobian lands; `out[:, None] = jac` raises there
+                    out[:, :np.shape(jac)[1]] = jac
+                else:
+                    out[:, self.state_index] = jac
                 return out
             x, r = xr[:self.dim_substate], xr[-self.dim_noise:]
             out = np.zeros((self.dim_out, self.dim_state + self.dim_noise))
@@ -584,7 +604,8 @@ class MeasurementModel:
         return self.meas_fcn(x, r, time)
 
     def meas_fcn_dx(self, x, r, time):
-        """Jacobian of the measurement function (ssmod.py:937-958): UNGM, UNGM-NA and pendulum only."""
+        """Jacobian of the measurement function (ssmod.py:937-958): UNGM, UNGM-NA and pendulum as in the reference, and the
+        radar and bearing measurements (the reference's methods are `pass`).  RangeMeasurement has none."""
         return None
 
     def check_jacobian(self, points, time=0, rel_step=1e-5):
@@ -651,6 +672,12 @@ class BearingMeasurement(MeasurementModel):
     def meas_fcn(self, x, r, time):
         return np.arctan2(x[1] - self.sensor_pos[:, 1], x[0] - self.sensor_pos[:, 0]) + r
 
+    def meas_fcn_dx(self, x, r, time):
+        """Row s: [-dy_s, dx_s] / r_s^2 (the twin of csrc/ssmq_device.h: jac_integrand); a target exactly at a sensor is 1 / 0."""
+        dx, dy = x[0] - self.sensor_pos[:, 0], x[1] - self.sensor_pos[:, 1]
+        ir2 = 1.0 / (dx * dx + dy * dy)
+        return np.stack((-dy * ir2, dx * ir2), axis=1)
+
 
 class Radar2DMeasurement(MeasurementModel):
     """ssmod.py:1201-1255 (range and bearing from the radar location)."""
@@ -666,3 +693,10 @@ class Radar2DMeasurement(MeasurementModel):
     def meas_fcn(self, x, r, time):
         dx, dy = x[0] - self.radar_loc[0], x[1] - self.radar_loc[1]
         return np.array([np.sqrt(dx ** 2 + dy ** 2), np.arctan2(dy, dx)]) + r
+
+    def meas_fcn_dx(self, x, r, time):
+        """[[dx, dy] / r, [-dy, dx] / r^2] (the twin of csrc/ssmq_device.h: jac_integrand); a target exactly at the radar is 1 / 0."""
+        dx, dy = x[0] - self.radar_loc[0], x[1] - self.radar_loc[1]
+        r2 = dx * dx + dy * dy
+        ir = 1.0 / np.sqrt(r2)
+        return np.array([[dx * ir, dy * ir], [-dy / r2, dx / r2]])

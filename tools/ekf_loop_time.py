@@ -116,7 +116,7 @@ for shape, models, B, T in (('UNGM', ungm_models, 10000, 100), ('pendulum', pend
     if shape == 'UNGM':
         par = np.array([[1.0, 3.0]])
         gpq = ssinf.GaussianProcessKalman(dyn, obs, par, par, 'rbf', 'ut')
-        assert 'k_filter_fused' in gpq.kernel_name(B), gpq.kernel_name(B)
+        assert 'k_filter_' in gpq.kernel_name(B), gpq.kernel_name(B)      # (k_filter_fused, since 3.41 k_filter_ungm_quad)
         routes['gpq_kalman_fused'] = route(lib, gpq.tf_dyn._handle_for(e_dyn), gpq.tf_obs._handle_for(e_obs), None)
     for r in routes.values():          # warm-up: code objects, the captured loop, clocks
         r['run'](3)
