@@ -1141,6 +1141,39 @@ int ssmq_filter_sweep_t_kernel_name(const ssmq_integrand *f_dyn, const ssmq_inte
                                     int Y, char *buf, int len);
 
 /*
+ * Noise sweep of a Gaussian filter by measurement likelihood: the sibling of ssmq_filter_sweep_dev that keeps the weights - the two
+ * transform handles, as ssmq_filter_forward_dev takes them - shared and varies the process-noise term G Q G', the measurement-noise
+ * covariance R and the initial moments per row, for P rows on B measurement sequences in ONE launch (k_noise_sweep<>), of which only
+ * the scores are kept.  Per item (p, b), with (m, P) = row p of x0 and the recursion of ssmq_filter_sweep_dev,
+ *     m-, P- = dynamics transform of (m, P) + gqg[p];   y^, S, C = measurement transform of (m-, P-) + rr[p];   nis_k, ll_k;   update
+ * - step by step what ssmq_filter_forward_dev followed by ssmq_filter_innovations_dev computes with the dense kernels for a filter
+ * whose noise covariances and initial moments are those of row p -, and
+ *     d_loglik_total[p][b] = sum_k ll_k,   d_nis_mean[p][b] = sum_k nis_k / T   (ascending k),   d_loglik[p][k][b] = ll_k.
+ * The filtered moments are never stored.
+ *   recursion      SSMQ_RECURSION_GAUSS; SSMQ_RECURSION_STUDENT (a Studentian pass) is refused
+ *   d_y [T][Y][ld] (device), ld a multiple of 64 (every wave belongs to one row)
+ *   gqg [P or 1][D*D], rr [P or 1][Y*Y], x0 [P or 1][D + D*D] = m0 | P0 (lower triangle read): host arrays, each with its own row stride
+ *   in doubles - the row size, or 0 for ONE row shared by all P (NULL gqg / rr = zeros).  Every entry is finite; whether a row is
+ *   positive definite is not checked: an indefinite row fails in its first factorisation and shows up in d_status.
+ *   d_loglik_total, d_nis_mean [P][ld];  d_loglik [P][T][ld] or NULL;  d_status [P][ld] int32 (device): 1 + the first step whose scores
+ *   are not numbers - the totals and the remaining steps of that item are then NaN - or 0.  An item's results do not depend on the
+ *   items around it.
+ * Range: both handles sigma-point rules, both GP / Bayes-Sard transforms or both t-process BQ transforms, on the built-in
+ * additive-noise model pairs and point counts the fused time loop is instantiated for (D <= 6, Y <= 4, N_dyn = N_obs).  User-defined
+ * integrands, handles of two different forms, linearisation / Taylor-GPQD / GPQ+D / truncated / multi-output handles, a Studentian pass,
+ * models that take their noise as an argument and shapes without an instantiation return SSMQ_E_UNSUPPORTED; null or ill-sized
+ * arguments, a stride that is neither 0 nor the row size, a non-finite entry of a row array and P < 1 return SSMQ_E_ARG - both with the
+ * range in ssmq_last_error(), before any output is touched.  T == 0: the totals are zero.  Synchronous.
+ */
+int ssmq_filter_noise_sweep_dev(ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, ssmq_transform *h_obs, const ssmq_integrand *f_obs,
+                                int recursion, int64_t B, int64_t ld, int T, const double *d_y, int P, const double *gqg,
+                                int64_t gqg_stride, const double *rr, int64_t rr_stride, const double *x0, int64_t x0_stride,
+                                double *d_loglik_total, double *d_nis_mean, double *d_loglik, int32_t *d_status);
+/* Name of the kernel ssmq_filter_noise_sweep_dev would run for this pair (the same range check; no launch). */
+int ssmq_filter_noise_sweep_kernel_name(const ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, const ssmq_transform *h_obs,
+                                        const ssmq_integrand *f_obs, int recursion, char *buf, int len);
+
+/*
  * Bootstrap particle filter (sequential Monte Carlo; Gordon, Salmond, Smith 1993) of the additive-noise models: the ground truth the
  * moment-matching filters are measured against.  N weighted particles per trajectory, in the time convention of
  * ssmq_filter_forward_dev (both models of step j, 0-based, are evaluated at time j):

@@ -313,6 +313,13 @@ _PROTOTYPES = {
                                  ctypes.c_int, ctypes.c_void_p] + [c_double_p] * 5 + [ctypes.c_void_p] * 4 + [c_int32_p]),
     'ssmq_filter_sweep_t_kernel_name': (ctypes.c_int, [ctypes.POINTER(Integrand), ctypes.POINTER(Integrand)] + [ctypes.c_int] * 5 +
                                         [ctypes.c_char_p, ctypes.c_int]),
+    # (h_dyn, f_dyn, h_obs, f_obs, recursion, B, ld, T, d_y, P, gqg, gqg_stride, rr, rr_stride, x0, x0_stride, d_loglik_total, d_nis_mean,
+    #  d_loglik, d_status)
+    'ssmq_filter_noise_sweep_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Integrand), ctypes.c_void_p, ctypes.POINTER(Integrand),
+                                                   ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_int] +
+                                    [c_double_p, ctypes.c_int64] * 3 + [ctypes.c_void_p] * 4),
+    'ssmq_filter_noise_sweep_kernel_name': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Integrand), ctypes.c_void_p,
+                                                           ctypes.POINTER(Integrand), ctypes.c_int, ctypes.c_char_p, ctypes.c_int]),
     'ssmq_filter_iterated_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Integrand), ctypes.c_void_p, ctypes.POINTER(Integrand),
                                                 ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int] +
                                  [ctypes.c_void_p] * 3 + [c_double_p, c_double_p] + [ctypes.c_void_p] * 4),

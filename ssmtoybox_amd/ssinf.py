@@ -81,6 +81,40 @@ def initial_planes(stage, D, mean, cov, B, ld, x0_mean=None, x0_cov=None, broadc
     return d_m0, d_P0
 
 
+_NOISE_SWEEP_RANGE = ('noise sweeps cover UnscentedKalman, CubatureKalman, GaussHermiteKalman, GaussianProcessKalman, BayesSardKalman and '
+                      'StudentProcessKalman on the built-in additive-noise model pairs of the fused time loop, Gaussian noise and a '
+                      'Gaussian initial state, D <= 6, Y <= 4 and the point counts that loop is instantiated for')
+
+
+def noise_grid(cov, scales):
+    """Rows of a noise sweep that are multiples of one covariance: cov (n, n) and scales (P,) -> (P, n, n) = scales[:, None, None] *
+    cov."""
+    cov, scales = np.atleast_2d(np.asarray(cov, dtype=np.float64)), np.asarray(scales, dtype=np.float64)
+    if cov.ndim != 2 or cov.shape[0] != cov.shape[1] or scales.ndim != 1 or scales.size == 0:
+        raise ValueError('noise_grid: cov is a square matrix and scales a non-empty one-dimensional sequence')
+    return np.ascontiguousarray(scales[:, None, None] * cov)
+
+
+def _cov_rows(value, own, name):
+    """A covariance argument of a noise sweep - None (the model's own), one matrix (shared by all rows) or a stack (P, n, n) - as
+    ((rows, n, n) float64, whether it is a stack); ValueError for another shape and for a row that is not finite or not symmetric,
+    naming the row."""
+    own = np.atleast_2d(np.asarray(own, dtype=np.float64))
+    a = own if value is None else np.asarray(value, dtype=np.float64)
+    n = own.shape[0]
+    stacked = a.ndim == 3
+    if a.shape[-2:] != (n, n) or a.ndim not in (2, 3) or a.shape[0] < 1:
+        raise ValueError('noise sweep: {} is None, one ({n}, {n}) matrix or a stack (P, {n}, {n}) with P >= 1; got shape {}'.format(
+            name, a.shape, n=n))
+    a = a.reshape((-1, n, n))
+    for p, row in enumerate(a):
+        if not np.isfinite(row).all():
+            raise ValueError('noise sweep: row {} of {} is not finite'.format(p, name))
+        if not np.array_equal(row, row.T):
+            raise ValueError('noise sweep: row {} of {} is not symmetric'.format(p, name))
+    return a, stacked
+
+
 class GaussianInference:
     """Gaussian filter (ssinf.py:215-323)."""
 
@@ -390,6 +424,125 @@ class GaussianInference:
         """`innovations_batch` for one trajectory, data (dim_y, T): nis (T,), loglik (T,), loglik_total, nis_mean, status."""
         out = self.innovations_batch(np.asarray(data)[..., None])
         return {k: (v[..., 0] if v.ndim else v) for k, v in out.items()}
+
+    # ---- noise sweeps: Q, R and P0 per row by measurement likelihood, the weights shared (`ssmq_filter_noise_sweep_dev`) ----------
+    def _noise_sweep_setup(self, q_cov, r_cov, x0_cov):
+        """The refusals of the noise sweeps that need no library - the class, the models, the noise, the kind of transform, D and Y -
+        and the row arrays of the C entry point: G Q_p G', R_p and m0 | P0_p, each (rows, size) with rows = P for a stack and 1 for a
+        shared matrix (stride 0).  Whether the pair of models and the point counts have a kernel is the table's to say: the C entry
+        point answers that (NotImplementedError as well, after the library is loaded)."""
+        from .ssmod import GaussRV
+        what = _NOISE_SWEEP_RANGE
+        if self._recursion != 'gauss':
+            raise NotImplementedError(what + '; not implemented for the Studentian recursion ({})'.format(type(self).__name__))
+        if isinstance(self, MarginalInference):
+            raise NotImplementedError(what + '; not implemented for the marginalised filters ({})'.format(type(self).__name__))
+        if is_user_model(self.mod_dyn) or is_user_model(self.mod_obs):
+            raise NotImplementedError(what + '; not implemented for user models (device_code)')
+        if not self._additive:
+            raise NotImplementedError(what + '; not implemented for models that take their noise as an argument (non-additive noise)')
+        for rv in (self.mod_dyn.init_rv, self.mod_dyn.noise_rv, self.mod_obs.noise_rv):
+            if not isinstance(rv, GaussRV):
+                raise NotImplementedError(what + '; not implemented for {}'.format(type(rv).__name__))
+        families = ((UnscentedTransform, SphericalRadialTransform, GaussHermiteTransform), (GaussianProcessTransform, BayesSardTransform),
+                    (StudentTProcessTransform,))
+        family = [[type(tf) in fam for fam in families] for tf in (self.tf_dyn, self.tf_obs)]
+        if not any(family[0]) or family[0] != family[1]:
+            raise NotImplementedError(what + '; not implemented for the pair of transforms {} / {} (the extended, Taylor-GPQD, GPQ+D, '
+                                      'truncated, multi-output, Monte-Carlo and fully-symmetric Student transforms have no sweep, and both '
+                                      'transforms are of one form)'.format(type(self.tf_dyn).__name__, type(self.tf_obs).__name__))
+        D, Y = self.mod_dyn.dim_state, self.mod_obs.dim_out
+        if D > 6 or Y > 4:
+            raise NotImplementedError(what + '; got D = {}, Y = {}'.format(D, Y))
+        q, qs = _cov_rows(q_cov, self.q_cov, 'q_cov')
+        r, rs = _cov_rows(r_cov, self.r_cov, 'r_cov')
+        x, xs = _cov_rows(x0_cov, self._initial_cov(), 'x0_cov')
+        stacks = [a.shape[0] for a, s in ((q, qs), (r, rs), (x, xs)) if s]
+        if not stacks or len(set(stacks)) != 1:
+            raise ValueError('noise sweep: at least one of q_cov, r_cov, x0_cov is a stack (P, n, n), and all stacks have the same P; got '
+                             'leading axes {}'.format(stacks))
+        G = self.G
+        # row p: the very expression of `_noise`, so that a row can have the bits of the two-call path
+        gqg = np.ascontiguousarray([np.ascontiguousarray(G.dot(qp).dot(G.T), dtype=np.float64).ravel() for qp in q], dtype=np.float64)
+        rr = np.ascontiguousarray([np.ascontiguousarray(rp, dtype=np.float64).ravel() for rp in r], dtype=np.float64)
+        m0 = np.ascontiguousarray(self.x0_mean, dtype=np.float64).ravel()
+        x0 = np.ascontiguousarray([np.concatenate((m0, np.ascontiguousarray(xp, dtype=np.float64).ravel())) for xp in x], dtype=np.float64)
+        return dict(P=stacks[0], D=D, Y=Y, gqg=gqg, rr=rr, x0=x0, q=q, r=r)
+
+    def noise_sweep_kernel_name(self, P=1):
+        """Which kernel `noise_sweep_*` run for this filter (the same for every number of rows P)."""
+        self._noise_sweep_setup(noise_grid(self.q_cov, np.ones(int(P))), None, None)
+        return self._kernel_name('ssmq_filter_noise_sweep_kernel_name', 0, unsupported=True)
+
+    def _noise_sweep_launch(self, stage, s, d_y, B, ld, T, steps, device):
+        alloc = stage.device if device else stage.scratch
+        P = s['P']
+        d_tot, d_nis, d_st = alloc(8 * P * ld), alloc(8 * P * ld), alloc(4 * P * ld)
+        d_ll = alloc(8 * P * T * ld) if steps else None
+        vp, dp = _lib.vp, _lib.dp
+        rows = []
+        for a in (s['gqg'], s['rr'], s['x0']):
+            rows += [dp(a), a.shape[1] if a.shape[0] > 1 else 0]
+        _lib.check(_lib.load().ssmq_filter_noise_sweep_dev(*self._pair(), 0, B, ld, T, vp(d_y), P, *rows, vp(d_tot), vp(d_nis), vp(d_ll),
+                                                           vp(d_st)), 'ssmq_filter_noise_sweep_dev', True)
+        return d_tot, d_nis, d_ll, d_st
+
+    def noise_sweep_dev(self, d_y, B, ld, T, q_cov=None, r_cov=None, x0_cov=None, steps=False):
+        """`noise_sweep_batch` on measurements that are already on the device (planes [T][dim_y][ld], ld a multiple of 64):
+        DeviceBuffers d_loglik_total [P][ld], d_nis_mean [P][ld], d_loglik [P][T][ld] (None without `steps`), d_status [P][ld] int32;
+        the caller frees them.  Every trajectory of row p starts from (x0_mean, x0_cov[p])."""
+        s = self._noise_sweep_setup(q_cov, r_cov, x0_cov)
+        if ld % 64 or ld < B:
+            raise ValueError('noise sweep: ld is a multiple of 64 and at least B')
+        with _lib.Staging() as stage:
+            bufs = self._noise_sweep_launch(stage, s, d_y, B, ld, T, steps, True)
+            stage.release(*[b for b in bufs if b is not None])
+        return bufs
+
+    def noise_sweep_batch(self, data, q_cov=None, r_cov=None, x0_cov=None, steps=False):
+        """The measurement likelihood of `data` (dim_y, T, B) under P rows of noise covariances, in one kernel launch that stores no
+        filtered moment (k_noise_sweep<>).  Each of q_cov (process noise, the dimension of `noise_rv`), r_cov (measurement noise) and
+        x0_cov (initial state) is None - the model's own -, one matrix shared by all rows, or a stack (P, n, n); at least one is a
+        stack and all stacks have the same P (ValueError otherwise, and for a row that is not finite or not symmetric, naming the
+        row).  Positive definiteness is not checked here: an indefinite row fails on the device and shows in `status`.
+
+        Row p is `type(self)` on the same models with noise_rv.cov = q_cov[p], r_cov[p] and initial covariance x0_cov[p], and the
+        weights this object has now; its scores are that filter's forward_pass_batch followed by innovations_batch, computed by the
+        dense kernels.  Returns a dict: loglik_total (P, B) = sum_k log p(y_k | y_1..k-1) under row p, nis_mean (P, B), status (P, B)
+        int32 (0, or 1 + the first step whose scores are not numbers; the totals of such an item are NaN), and with `steps` loglik
+        (P, T, B).  Touches neither fi_mean / fi_cov / status nor the weights.  Range: see `_NOISE_SWEEP_RANGE`.  A filter class, a
+        kind of model, noise or transform, or a D or Y outside it raises NotImplementedError before the library is loaded; a built-in
+        additive-noise pair of models or a point count for which the fused time loop has no instantiation passes those checks and is
+        refused by the library's table - NotImplementedError too, but after the library is loaded."""
+        return self._noise_sweep_run(self._noise_sweep_setup(q_cov, r_cov, x0_cov), data, steps)
+
+    def _noise_sweep_run(self, s, data, steps):
+        data = np.asarray(data, dtype=np.float64)
+        if data.ndim != 3 or data.shape[0] != s['Y']:
+            raise ValueError('noise sweep: data is (dim_y, T, B)')
+        Y, T, B = data.shape
+        if B < 1 or T < 1:
+            raise ValueError('noise sweep: data holds at least one step of at least one trajectory')
+        ld, P = _lib.padded(B), s['P']
+        with _lib.Staging() as stage:
+            d_y = stage.scratch(8 * T * Y * ld)
+            _lib.upload_study(data, Y, ld, d_y)
+            d_tot, d_nis, d_ll, d_st = self._noise_sweep_launch(stage, s, d_y, B, ld, T, steps, False)
+            out = {'loglik_total': d_tot.download((P, ld))[:, :B].copy(), 'nis_mean': d_nis.download((P, ld))[:, :B].copy(),
+                   'status': d_st.download((P, ld), dtype=np.int32)[:, :B].copy()}
+            if steps:
+                out['loglik'] = d_ll.download((P, T, ld))[:, :, :B].copy()
+        return out
+
+    def fit_noise_covariances(self, data, q_cov=None, r_cov=None, x0_cov=None):
+        """The row of `noise_sweep_batch` with the largest measurement likelihood: (index, q_cov[index], r_cov[index], table) with
+        table[p] the sum of loglik_total[p] over the trajectories on which every row succeeded (`fit_table`); an argument that is
+        shared (or None: the model's own) is returned as it is."""
+        s = self._noise_sweep_setup(q_cov, r_cov, x0_cov)
+        out = self._noise_sweep_run(s, data, False)
+        index, table = fit_table(out['loglik_total'], out['status'], np.zeros(s['P'], dtype=np.int32))
+        q, r = (rows[index if len(rows) > 1 else 0].copy() for rows in (s['q'], s['r']))      # (one row: shared by all)
+        return index, q, r, table
 
     # ---- iterated posterior linearisation (IPLF): J measurement updates per step, each re-linearised around the posterior ------
     def _iterated_refusal(self, iterations):
