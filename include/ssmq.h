@@ -954,6 +954,10 @@ int ssmq_filter_kernel_name(const ssmq_transform *h_dyn, const ssmq_integrand *f
  * saturated batches. */
 int ssmq_filter_kernel_name_batch(const ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, const ssmq_transform *h_obs,
                                   const ssmq_integrand *f_obs, int64_t B, char *buf, int len);
+/* ... and for planes of pitch ld and T steps (0, 0: not given - the answer for the batch alone): routes whose kernels address a
+ * pass with 32-bit offsets are bounded by its size (k_filter_ungm_quad: 8 ld T < 2^31).  Nothing is allocated or launched. */
+int ssmq_filter_kernel_name_shape(const ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, const ssmq_transform *h_obs,
+                                  const ssmq_integrand *f_obs, int64_t B, int64_t ld, int T, char *buf, int len);
 
 /*
  * Innovation scores of a filter pass, from the measurements and the FILTERED moments alone (no true states): for step k = 0 .. T-1

@@ -283,6 +283,9 @@ _PROTOTYPES = {
                                                ctypes.POINTER(Integrand), ctypes.c_char_p, ctypes.c_int]),
     'ssmq_filter_kernel_name_batch': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Integrand), ctypes.c_void_p,
                                                      ctypes.POINTER(Integrand), ctypes.c_int64, ctypes.c_char_p, ctypes.c_int]),
+    'ssmq_filter_kernel_name_shape': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Integrand), ctypes.c_void_p,
+                                                     ctypes.POINTER(Integrand), ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
+                                                     ctypes.c_char_p, ctypes.c_int]),
     'ssmq_filter_innovations_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Integrand), ctypes.c_void_p, ctypes.POINTER(Integrand),
                                                    ctypes.c_int64, ctypes.c_int64, ctypes.c_int] + [ctypes.c_void_p] * 5 +
                                     [c_double_p, c_double_p] + [ctypes.c_void_p] * 6),

@@ -599,11 +599,16 @@ extern "C" int ssmq_filter_kernel_name(const ssmq_transform *h_dyn, const ssmq_i
 
 extern "C" int ssmq_filter_kernel_name_batch(const ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, const ssmq_transform *h_obs,
                                              const ssmq_integrand *f_obs, int64_t B, char *buf, int len) {
+    return ssmq_filter_kernel_name_shape(h_dyn, f_dyn, h_obs, f_obs, B, 0, 0, buf, len);
+}
+
+extern "C" int ssmq_filter_kernel_name_shape(const ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, const ssmq_transform *h_obs,
+                                             const ssmq_integrand *f_obs, int64_t B, int64_t ld, int T, char *buf, int len) {
     SSMQ_HANDLE_LOCK(h_dyn, h_obs);
-    if (!h_dyn || !h_obs || !f_dyn || !f_obs || !buf || len <= 0 || B < 0) return SSMQ_E_ARG;
+    if (!h_dyn || !h_obs || !f_dyn || !f_obs || !buf || len <= 0 || B < 0 || ld < 0 || T < 0 || (ld > 0 && ld < B)) return SSMQ_E_ARG;
     const char *name = nullptr;
     FilterPass query;
-    int rc = make_filter_pass(h_dyn, f_dyn, h_obs, f_obs, B, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &query);
+    int rc = make_filter_pass(h_dyn, f_dyn, h_obs, f_obs, B, ld, T, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &query);
     if (rc) return rc;
     query.name = &name; query.dry_run = true;
     const bool mo = is_mo(h_dyn) || is_mo(h_obs);       // no fused time loop takes the multi-output form

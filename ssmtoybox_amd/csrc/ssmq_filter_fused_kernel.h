@@ -34,13 +34,11 @@ namespace ssmq {
 // One pass over the steps k_begin ... k_end - 1 of the wave's trajectories (block `blk` of a.lpw trajectories).  The whole filter is
 // the pass (0, T, first, last); CHUNKED passes (ssmq_filter_chunked.hip) start from the state - mean, lower triangle of the
 // covariance, status word: what the registers held, bit for bit - that the previous pass of the block left in a.hand.
-// QUAD (scalar shapes, whole passes; ssmq_filter_ungm_quad.hip): a trajectory sits on the four lanes of a quad, block `blk` is
-// kQuadTraj trajectories.  Only the evaluations of the dynamics integrand are dealt to the lanes (QuadScalarPoints); the state,
-// the inputs and everything else of a step are replicated, and all four lanes store the (same) results.
-template <int D, int Y, int ND, int NO, int FD, int FO, int FORM, int TP, int SELO, int OPT, int STU, bool CHUNKED, bool QUAD = false>
+// (The scalar UNGM pass with a trajectory on the four lanes of a quad has its own loop around the same step:
+// ssmq_filter_ungm_quad.hip.)
+template <int D, int Y, int ND, int NO, int FD, int FO, int FORM, int TP, int SELO, int OPT, int STU, bool CHUNKED>
 __device__ __forceinline__ void fused_pass(const FusedArgs &a, uint32_t blk, int k_begin, int k_end, bool first, bool last) {
-    static_assert(!QUAD || (D == 1 && !CHUNKED), "fused_pass: the quad form is for whole passes of scalar states");
-    const uint32_t b = QUAD ? blk * kQuadTraj + (threadIdx.x >> 2) : blk * a.lpw + threadIdx.x;
+    const uint32_t b = blk * a.lpw + threadIdx.x;
     if ((int64_t)b >= a.B) return;
     const int64_t ld = a.ld;
     double m[D], Pl[D * (D + 1) / 2];
@@ -90,8 +88,6 @@ __device__ __forceinline__ void fused_pass(const FusedArgs &a, uint32_t blk, int
     if constexpr (kTTd) { tdn = ttd[k_begin]; fd.use_tval = 1; }
     if constexpr (kTTo) { ton = tto[k_begin]; fo.use_tval = 1; }
     if (stu_scale) scn = ssc[k_begin];
-    QuadScalarPoints<ND> qpts;                // QUAD: the points of the dynamics transform this lane evaluates
-    if constexpr (QUAD) qpts.init(cpd.c + const_layout(D, D, ND, FORM).xi, (int)(threadIdx.x & 3));
     // Everything requested so far has to have ARRIVED before the loop is entered: hipcc's wait-count insertion merges the
     // loop-entry state into the loop header, and a vector load still pending there (m0, P0: used by the first step
     // only) leaves an s_waitcnt vmcnt(n) in the body that - memory operations retire in order - makes EVERY iteration
@@ -135,9 +131,7 @@ __device__ __forceinline__ void fused_pass(const FusedArgs &a, uint32_t blk, int
         }
         // ---- time update: predictive state moments, + G Q G' (ssinf.py:276-279) ----------------------------------
         RegSinkNoCross<D, D> pr;
-        bool ok;
-        if constexpr (QUAD) ok = moment_transform_core<D, D, ND, FD, FORM, TP, 0, false, OPT>(m, Pl, t, fd, cpd, pr, qpts);
-        else ok = moment_transform_core<D, D, ND, FD, FORM, TP, 0, false, OPT, RegSinkNoCross<D, D>>(m, Pl, t, fd, cpd, pr);
+        bool ok = moment_transform_core<D, D, ND, FD, FORM, TP, 0, false, OPT, RegSinkNoCross<D, D>>(m, Pl, t, fd, cpd, pr);
         // ---- predictive measurement moments, + R (ssinf.py:287-291) ------------------------------------------------
         double L2[D * (D + 1) / 2];
 #pragma unroll

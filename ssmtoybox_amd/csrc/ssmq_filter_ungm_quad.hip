@@ -4,19 +4,137 @@
 // is the dynamics integrand x / 2 + 25 x / (1 + x^2) + 8 cos(1.2 k): ten instructions and a reciprocal per point.  Here lane q of a
 // quad evaluates it at point q alone and the N values are broadcast to the quad (`v_mov_b32_dpp quad_perm:[n,n,n,n]`, two per
 // double); from there every lane runs the sums, the measurement transform and the update of the one-lane kernel on a replicated
-// state - fused_pass<..., QUAD = true> (ssmq_filter_fused_kernel.h), QuadScalarPoints (ssmq_quad.h).  No partial sums, no
-// all-reduce: every value comes from the same operations in the same order as in k_filter_fused<1, 1, N, N, ..., OPT = 0, STU = 0>,
-// so the results are the same bits (tests/test_ungm_quad_gpu.py).  All four lanes issue the step's two stores - same address, same
-// bits: a store block predicated on the lane would end each step in a branch.  16 trajectories per wave: four times the waves of
-// the one-lane kernel, taken while they still have a SIMD each (try_launch_quad).
+// state - QuadScalarPoints (ssmq_quad.h).  No partial sums, no all-reduce: every value comes from the same operations in the same
+// order as in k_filter_fused<1, 1, N, N, ..., OPT = 0, STU = 0>, so the results are the same bits (tests/test_ungm_quad_gpu.py,
+// tests/test_ungm_quad_scaffold_gpu.py).  All four lanes issue the step's two stores - same address, same bits: a store block
+// predicated on the lane would end each step in a branch.  16 trajectories per wave: four times the waves of the one-lane kernel,
+// taken while they still have a SIMD each (try_launch_quad).
+//
+// The kernel has its OWN TIME LOOP (UngmQuadPass below), not fused_pass<>: on a wave that pays one issue slot per instruction the
+// step bookkeeping of the generic loop - a 64-bit plane offset multiplied out of the clamped step index, three 64-bit vector
+// addresses rebuilt per step, the copy of the prefetched measurement - was a fifth of what the arithmetic costs.  D = Y = 1: y[k],
+// fm[k] and fP[k] are planes of one pitch, so ONE 32-bit lane byte offset `vo` (8 b, + 8 ld per step) addresses all three against
+// uniform bases (`global_load / global_store v, s[base:base+1]`; the measurement one plane ahead through the base y + 8 ld), and the
+// time table is read at a scalar byte offset (+ 8 per step).  The last step is peeled - it requests nothing ahead, so no index is
+// clamped - and the steps before it run two per trip with the measurement alternating between two registers.
 #include "ssmq_filter_fused_kernel.h"
 
 namespace ssmq {
 namespace {
 
+typedef const __attribute__((address_space(4))) char *cbyte_p;
+
+// The pass of one quad's trajectory.  step<AHEAD>() is the step of fused_pass<1, 1, N, N, UNGM_DYN, UNGM_MEAS, FORM_BQ, TP = 0,
+// SELO = 0, OPT = 0, STU = 0> - the same calls and the same update lines on the same operands in the same order - around the
+// addressing described above.
+template <int N>
+struct UngmQuadPass {
+    CoreParams cpd, cpo;
+    FPar fd, fo;
+    QuadScalarPoints<N> qpts;
+    const char *ynx;      // uniform: the measurement plane AFTER the one `vo` points into
+    char *fm, *fP;        // uniform
+    cbyte_p tt;           // uniform: the dynamics' time table
+    uint32_t pitch;       // 8 ld
+    uint32_t vo;          // lane: byte offset of this trajectory in the current step's planes
+    uint32_t to;          // uniform: byte offset of the NEXT step's time-table entry
+    double m[1], Pl[1];
+    double tdn;           // the time-table entry of the step about to run
+    int32_t agg;          // number of steps completed without a NaN
+
+    // One step on the measurement ycur.  AHEAD: requests the next step's measurement into ynext and its time-table entry, and has
+    // the measurement ARRIVE before the step's stores are issued (the one vmcnt wait of a step: behind the stores it would wait
+    // for their acknowledgement as well).
+    template <bool AHEAD>
+    __device__ __forceinline__ void step(int k, const double ycur, double &ynext) {
+        const double t = (double)k;   // (unused: the integrands take their time constant from tval)
+        fd.tval = tdn;
+        if constexpr (AHEAD) {
+            ynext = *(const double *)(ynx + vo);
+        }
+        // ---- time update: predictive state moments, + G Q G' ----------------------------------------------------------------
+        RegSinkNoCross<1, 1> pr;
+        bool ok = moment_transform_core<1, 1, N, SSMQ_F_UNGM_DYN, SSMQ_FORM_BQ, 0, 0, false, 0>(m, Pl, t, fd, cpd, pr, qpts);
+        if constexpr (AHEAD) {
+            // the next entry of the time table is requested BEHIND the integrand that consumed this step's: scalar loads return
+            // out of order, so the wait in front of that use is for all of them, a request just made included
+            __builtin_amdgcn_sched_barrier(0);
+            tdn = *(cdouble_p)(tt + to);
+            to += 8;
+        }
+        // ---- predictive measurement moments, + R ------------------------------------------------------------------------------
+        double L2[1] = {pr.cv[0]};
+        RegSink<1, 1> ob;
+        ok = moment_transform_core<1, 1, N, SSMQ_F_UNGM_MEAS, SSMQ_FORM_BQ, 0, 0, true, 0, RegSink<1, 1>>(pr.mf, L2, t, fo, cpo, ob) && ok;
+        // ---- measurement update: the scalar lines of fused_pass (see there for the NaN that carries a failure) ----------------
+        double S = ob.cv[0];
+        int hi = __double2hiint(S);
+        hi = (S > 0.0) ? hi : 0x7ff80000;
+        S = __hiloint2double(hi, __double2loint(S));
+        const double G = div_nr(ob.cx[0][0], S);
+        double s = 0.0;
+        s += G * (ycur - ob.mf[0]);
+        m[0] = pr.mf[0] + s;
+        double w = 0.0;
+        w += G * ob.cv[0];
+        double s2 = 0.0;
+        s2 += w * G;
+        double p = pr.cv[0] - s2;
+        // (tied to the step's results: on its own the pin - and with it the wait - moves up to the request)
+        if constexpr (AHEAD) asm volatile("" : "+v"(ynext), "+v"(m[0]), "+v"(p));
+        SSMQ_STORE(*(double *)(fm + vo), m[0]);
+        SSMQ_STORE(*(double *)(fP + vo), p);
+        agg += (p == p) ? 1 : 0;
+        Pl[0] = p;
+        vo += pitch;
+    }
+};
+
 template <int N>
 __global__ __launch_bounds__(kSmallBlock, 2) void k_filter_ungm_quad(const FusedArgs a) {
-    fused_pass<1, 1, N, N, SSMQ_F_UNGM_DYN, SSMQ_F_UNGM_MEAS, SSMQ_FORM_BQ, 0, 0, 0, 0, false, true>(a, blockIdx.x, 0, a.T, true, true);
+    const uint32_t b = blockIdx.x * kQuadTraj + (threadIdx.x >> 2);
+    const int T = a.T;
+    // (host, try_launch_ungm_quad: T >= 1 and 8 ld T < 2^31, so B <= ld fits 32 bits with room to spare)
+    if (b >= (uint32_t)a.B || T < 1) return;
+    UngmQuadPass<N> u;
+    u.cpd = CoreParams{(cdouble_p)a.c_dyn, (cdouble_p)a.gqg, a.emv_dyn, a.nu_dyn, 1.0, 1.0};
+    u.cpo = CoreParams{(cdouble_p)a.c_obs, (cdouble_p)a.rr, a.emv_obs, a.nu_obs, 1.0, 1.0};
+    u.fd = a.fd;
+    u.fo = a.fo;
+    u.fd.use_tval = 1;
+    u.pitch = 8u * (uint32_t)a.ld;
+    u.vo = 8u * b;
+    u.to = 8;
+    u.ynx = (const char *)a.y + u.pitch;
+    u.fm = (char *)a.fm;
+    u.fP = (char *)a.fP;
+    u.tt = (cbyte_p)a.fd.ttab;                    // host: non-null
+    u.m[0] = *(const double *)((const char *)a.m0 + u.vo);
+    u.Pl[0] = *(const double *)((const char *)a.P0 + u.vo);
+    u.agg = 0;
+    double ya = *(const double *)((const char *)a.y + u.vo), yb;
+    u.tdn = *(cdouble_p)u.tt;
+    u.qpts.init(u.cpd.c + const_layout(1, 1, N, SSMQ_FORM_BQ).xi, (int)(threadIdx.x & 3));
+    // everything requested so far has ARRIVED before the loop is entered (fused_pass: a load pending at the loop header leaves a
+    // vmcnt(n > 0) in the body that waits for the previous step's stores)
+    pin_v(u.m[0]);
+    pin_v(u.Pl[0]);
+    pin_v(ya);
+    // T - 1 steps that request their successor's inputs - two per trip, the measurement alternating between ya and yb (no copy),
+    // and an odd one after them - then the last step, which requests nothing.  The time-table offset counts the trips: from 8 by
+    // 16 to 8 + 16 ((T - 1) / 2), which is 8 T for odd T and 8 (T - 1) for even T
+    int k = 0;
+#pragma unroll 1
+    for (const uint32_t to_end = 8u * (uint32_t)((T - 1) | 1); u.to != to_end; k += 2) {
+        u.template step<true>(k, ya, yb);
+        u.template step<true>(k + 1, yb, ya);
+    }
+    if (!(T & 1)) {
+        u.template step<true>(k++, ya, yb);
+        ya = yb;
+    }
+    u.template step<false>(k, ya, yb);
+    *(int32_t *)((char *)a.status + 4u * b) = (u.agg == T) ? 0 : u.agg + 1;
 }
 
 typedef void (*ungm_quad_kernel)(const FusedArgs);
@@ -37,6 +155,10 @@ int try_launch_ungm_quad(const FilterPass &p, int64_t waves) {
     if (p.fd->id != SSMQ_F_UNGM_DYN || p.fo->id != SSMQ_F_UNGM_MEAS || hd->D != 1 || hd->E != 1 || ho->D != 1 || ho->E != 1) return 0;
     if (hd->form != SSMQ_FORM_BQ || hd->tp_nu > 0.0 || ho->N != hd->N || p.sel_obs != 0) return 0;
     if (!p.ttab_dyn && !p.dry_run) return 0;          // the kernels read the time table
+    // the kernels' byte offsets into y, fm and fP are 32-bit: passes of 8 ld T >= 2^31 bytes a plane set keep k_filter_fused (a name
+    // query that gives no pitch and no step count - ld = T = 0 - is about the batch alone)
+    if (p.ld >= ((int64_t)1 << 28) || 8 * p.ld * p.T >= ((int64_t)1 << 31)) return 0;
+    if (p.T < 1 && !p.dry_run) return 0;
     for (const UngmQuadEntry &e : kUngmQuad) {
         if (e.N != hd->N) continue;
         if (p.name) *p.name = e.name;

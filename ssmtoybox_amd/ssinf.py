@@ -189,14 +189,17 @@ class GaussianInference:
     def _initial_cov(self):
         return self.x0_cov
 
-    def kernel_name(self, batch=0):
+    def kernel_name(self, batch=0, ld=0, T=0):
         """Which kernel(s) the device filter loop runs for this filter (one fused kernel - k_filter_fused<..> and its schedules,
         k_ekf_loop<D=..,Y=..> for ExtendedKalman on built-in models - or a replayed hipGraph of 3 T launches) on a batch of
-        `batch` trajectories (0: a batch that fills the device; small batches of some systems run k_filter_wsplit)."""
+        `batch` trajectories (0: a batch that fills the device; small batches of some systems run k_filter_wsplit), in planes
+        of pitch `ld` over `T` steps (0, 0: not given; k_filter_ungm_quad takes passes of 8 ld T < 2^31 bytes only)."""
         if not self._additive:
             return ('k_filter_fused_aug (one kernel for the time loop) where instantiated, else a launch loop of 5 T '
                     'launches (k_augment | apply dyn | k_augment | apply obs | k_kalman_update)')
         self._check_user_points()
+        if ld or T:
+            return self._kernel_name('ssmq_filter_kernel_name_shape', int(batch), int(ld), int(T))
         return self._kernel_name('ssmq_filter_kernel_name_batch', int(batch))
 
     def forward_pass(self, data):
