@@ -16,13 +16,38 @@
 // fm[k] and fP[k] are planes of one pitch, so ONE 32-bit lane byte offset `vo` (8 b, + 8 ld per step) addresses all three against
 // uniform bases (`global_load / global_store v, s[base:base+1]`; the measurement one plane ahead through the base y + 8 ld), and the
 // time table is read at a scalar byte offset (+ 8 per step).  The last step is peeled - it requests nothing ahead, so no index is
-// clamped - and the steps before it run two per trip with the measurement alternating between two registers.
+// clamped - and the steps before it run two per trip with the measurement alternating between two registers.  The loop keeps no
+// failure count: the status word is made behind it, from the last covariance and - on a failed trajectory - from the covariances
+// the pass stored (first_nan_step).
 #include "ssmq_filter_fused_kernel.h"
 
 namespace ssmq {
 namespace {
 
 typedef const __attribute__((address_space(4))) char *cbyte_p;
+
+// The first step k whose stored fP[k] is NaN, for a trajectory whose LAST one is (the cold tail of a failed trajectory; o: its
+// byte offset in step 0's plane).  The planes are read back behind the wave's own stores (vmcnt(0)) - a wave's 16 trajectories
+// are one 128-byte line of a plane, which no other wave writes or holds - with the pass's 32-bit offsets, by loads that go past
+// the vector L1 (agent scope), kChunk requested back to back before the first is looked at.
+__device__ __forceinline__ int32_t first_nan_step(const char *fP, uint32_t o, const uint32_t pitch, const int T) {
+    constexpr int kChunk = 8;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const int32_t last = T - 1;
+    const uint32_t o_last = o + (uint32_t)last * pitch;
+    int32_t first = last;
+    for (int32_t k0 = 0; k0 < last && first == last; k0 += kChunk) {
+        double v[kChunk];
+#pragma unroll
+        for (int j = 0; j < kChunk; ++j) {     // (behind the last step: the last step's, a NaN that changes nothing)
+            v[j] = __hip_atomic_load((const double *)(fP + (k0 + j < last ? o : o_last)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            o += pitch;
+        }
+#pragma unroll
+        for (int j = kChunk - 1; j >= 0; --j) first = (v[j] != v[j] && k0 + j < first) ? k0 + j : first;
+    }
+    return first;
+}
 
 // The pass of one quad's trajectory.  step<AHEAD>() is the step of fused_pass<1, 1, N, N, UNGM_DYN, UNGM_MEAS, FORM_BQ, TP = 0,
 // SELO = 0, OPT = 0, STU = 0> - the same calls and the same update lines on the same operands in the same order - around the
@@ -40,7 +65,6 @@ struct UngmQuadPass {
     uint32_t to;          // uniform: byte offset of the NEXT step's time-table entry
     double m[1], Pl[1];
     double tdn;           // the time-table entry of the step about to run
-    int32_t agg;          // number of steps completed without a NaN
 
     // One step on the measurement ycur.  AHEAD: requests the next step's measurement into ynext and its time-table entry, and has
     // the measurement ARRIVE before the step's stores are issued (the one vmcnt wait of a step: behind the stores it would wait
@@ -49,6 +73,12 @@ struct UngmQuadPass {
     __device__ __forceinline__ void step(int k, const double ycur, double &ynext) {
         const double t = (double)k;   // (unused: the integrands take their time constant from tval)
         fd.tval = tdn;
+        // the next step's offset, formed HERE and not behind the stores: the top of a step is one dependent chain (v_rsq, the
+        // Newton steps, the integrand), and the hazard-aware scheduler puts this one independent add into the wait state behind
+        // v_rsq_f64 that is an s_nop otherwise.  (N = 5: the second live offset costs more moves of constants than the slot.)
+        constexpr bool kEarly = N <= 3;
+        uint32_t vn = 0;
+        if constexpr (kEarly) vn = vo + pitch;
         if constexpr (AHEAD) {
             ynext = *(const double *)(ynx + vo);
         }
@@ -84,9 +114,8 @@ struct UngmQuadPass {
         if constexpr (AHEAD) asm volatile("" : "+v"(ynext), "+v"(m[0]), "+v"(p));
         SSMQ_STORE(*(double *)(fm + vo), m[0]);
         SSMQ_STORE(*(double *)(fP + vo), p);
-        agg += (p == p) ? 1 : 0;
         Pl[0] = p;
-        vo += pitch;
+        vo = kEarly ? vn : vo + pitch;
     }
 };
 
@@ -111,7 +140,6 @@ __global__ __launch_bounds__(kSmallBlock, 2) void k_filter_ungm_quad(const Fused
     u.tt = (cbyte_p)a.fd.ttab;                    // host: non-null
     u.m[0] = *(const double *)((const char *)a.m0 + u.vo);
     u.Pl[0] = *(const double *)((const char *)a.P0 + u.vo);
-    u.agg = 0;
     double ya = *(const double *)((const char *)a.y + u.vo), yb;
     u.tdn = *(cdouble_p)u.tt;
     u.qpts.init(u.cpd.c + const_layout(1, 1, N, SSMQ_FORM_BQ).xi, (int)(threadIdx.x & 3));
@@ -134,7 +162,12 @@ __global__ __launch_bounds__(kSmallBlock, 2) void k_filter_ungm_quad(const Fused
         ya = yb;
     }
     u.template step<false>(k, ya, yb);
-    *(int32_t *)((char *)a.status + 4u * b) = (u.agg == T) ? 0 : u.agg + 1;
+    // status: 0, or 1 + the first step whose covariance is NaN.  Nothing in the loop counts: a NaN in p STAYS - Pl NaN -> v_rsq
+    // NaN -> every point, sum and S of the next step NaN, and the poison select keeps a NaN S - so the last p tells whether the
+    // trajectory failed, and where is read back from what it stored.
+    int32_t status = 0;
+    if (!(u.Pl[0] == u.Pl[0])) status = 1 + first_nan_step((const char *)a.fP, 8u * b, u.pitch, T);
+    *(int32_t *)((char *)a.status + 4u * b) = status;
 }
 
 typedef void (*ungm_quad_kernel)(const FusedArgs);
