@@ -131,9 +131,11 @@ int ssmq_integrand_define_dx(const char *body, const char *jac_body, int din, in
 /* SSMQ_RTC_PCRLB_DYN / SSMQ_RTC_PCRLB_OBS instantiate the two kernels of the posterior Cramer-Rao sums (ssmq_pcrlb_sums_dev) for a
  * user id that has a Jacobian: k_pcrlb_dyn_fn<id, D, din> (a D -> D model: E is not read) and k_pcrlb_obs_fn<id, D, E, din> (N, N_obs, form,
  * tp, opt ignored); an id without a Jacobian, D > 6 or E > 4 (measurement) is SSMQ_E_UNSUPPORTED. */
+/* SSMQ_RTC_IMM instantiates the IMM kernel k_imm_loop<D, E (= Y), N, N_obs, id, id_obs, SELO, form, tp> of two built-in integrands
+ * (ssmq_filter_imm_dev); `opt` carries SELO (0: the measurement reads the leading states, 1: states 0, 2, 4, ...). */
 enum ssmq_rtc_kind { SSMQ_RTC_FILTER = 0, SSMQ_RTC_APPLY = 1, SSMQ_RTC_MC = 2, SSMQ_RTC_LINEAR = 3, SSMQ_RTC_TAYLOR_GPQD = 4, SSMQ_RTC_GPQD = 5,
                      SSMQ_RTC_INNOVATION = 6, SSMQ_RTC_ITERATED = 7, SSMQ_RTC_SMOOTHER_ITERATED = 8, SSMQ_RTC_PCRLB_DYN = 9,
-                     SSMQ_RTC_PCRLB_OBS = 10 };
+                     SSMQ_RTC_PCRLB_OBS = 10, SSMQ_RTC_IMM = 11 };
 int ssmq_rtc_compile_check(int32_t id, int32_t id_obs, int kind, int D, int E, int N, int N_obs, int form, int tp, int opt,
                            const char *arch, char *log, int len);
 /* Process-wide counters of the run-time compiler: programs compiled, kernel lookups served from the cache, compile wall time. */
@@ -1176,6 +1178,35 @@ int ssmq_filter_noise_sweep_dev(ssmq_transform *h_dyn, const ssmq_integrand *f_d
 /* Name of the kernel ssmq_filter_noise_sweep_dev would run for this pair (the same range check; no launch). */
 int ssmq_filter_noise_sweep_kernel_name(const ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, const ssmq_transform *h_obs,
                                         const ssmq_integrand *f_obs, int recursion, char *buf, int len);
+
+/*
+ * Interacting multiple-model (IMM) filter over noise modes (Blom & Bar-Shalom 1988), the whole pass in ONE launch (k_imm_loop<>): M
+ * mode-matched filters of the two transform handles - mode j is the filter with the rows gqg[j], rr[j], x0[j], as a row of
+ * ssmq_filter_noise_sweep_dev - exchange moments every step through the Markov mixing probabilities and are weighted by the per-step
+ * measurement likelihood.  Everything fp64, the time convention of ssmq_filter_forward_dev.  Per trajectory and step k, every sum over
+ * modes in ascending mode index, with mu = mu0 before step 0:
+ *     c_j = sum_i pi[i][j] mu_i;   w_ij = pi[i][j] mu_i / c_j   (c_j == 0: w_ij = delta_ij, a mode nobody can reach keeps its moments)
+ *     m0_j = sum_i w_ij m_i;       P0_j = sum_i w_ij (P_i + (m_i - m0_j)(m_i - m0_j)')
+ *     (m_j, P_j, ll_j) = the step of ssmq_filter_noise_sweep_dev for row j from (m0_j, P0_j)
+ *     a_j = log c_j + ll_j (-inf when c_j == 0);   amax = max_j a_j;   loglik[k] = amax + log sum_j exp(a_j - amax);
+ *     mu_j = exp(a_j - loglik[k]);   fm[k] = sum_j mu_j m_j;   fP[k] = sum_j mu_j (P_j + (m_j - fm)(m_j - fm)')
+ *   pi [M][M] (host): pi[i][j] the probability of going from mode i to mode j; mu0 [M] (host): the initial mode probabilities.  Every
+ *   entry finite and non-negative, every row of pi and mu0 summing to 1 within 1e-12 (else SSMQ_E_ARG, the row named), 1 <= M <= 8.
+ *   d_y, gqg, rr, x0 and their strides: as ssmq_filter_noise_sweep_dev, with M for P.
+ *   d_fm [T][D][ld], d_fP [T][D*D][ld] (both triangles from the one value), d_mode_prob [T][M][ld], d_loglik [T][ld],
+ *   d_loglik_total [ld] (ascending k), d_status [ld] int32 (device).  A trajectory fails as a whole: the first step at which a mode's
+ *   scores or a mixed quantity is not a finite number sets status = 1 + k; from that step on every output of the trajectory, and its
+ *   total, is NaN.  A trajectory's results do not depend on the batch around it.
+ * Range and refusals: those of ssmq_filter_noise_sweep_dev (SSMQ_E_UNSUPPORTED / SSMQ_E_ARG with the range in ssmq_last_error(), before
+ * any output is touched).  T == 0: the totals are zero.  Synchronous.
+ */
+int ssmq_filter_imm_dev(ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, ssmq_transform *h_obs, const ssmq_integrand *f_obs, int recursion,
+                        int64_t B, int64_t ld, int T, const double *d_y, int M, const double *gqg, int64_t gqg_stride, const double *rr,
+                        int64_t rr_stride, const double *x0, int64_t x0_stride, const double *pi, const double *mu0, double *d_fm, double *d_fP,
+                        double *d_mode_prob, double *d_loglik, double *d_loglik_total, int32_t *d_status);
+/* Name of the kernel ssmq_filter_imm_dev would run for this pair (the same range check; no launch). */
+int ssmq_filter_imm_kernel_name(const ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, const ssmq_transform *h_obs,
+                                const ssmq_integrand *f_obs, int recursion, char *buf, int len);
 
 /*
  * Bootstrap particle filter (sequential Monte Carlo; Gordon, Salmond, Smith 1993) of the additive-noise models: the ground truth the

@@ -32,6 +32,7 @@ F_USER_FIRST, F_USER_SLOTS, USER_BODY_MAX, USER_MAX_D, USER_MAX_Y = 1024, 64, 81
 RTC_FILTER, RTC_APPLY, RTC_MC, RTC_LINEAR, RTC_TAYLOR_GPQD, RTC_GPQD, RTC_INNOVATION, RTC_ITERATED = 0, 1, 2, 3, 4, 5, 6, 7
 RTC_SMOOTHER_ITERATED = 8
 RTC_PCRLB_DYN, RTC_PCRLB_OBS = 9, 10
+RTC_IMM = 11
 ITERATED_MAX = 64          # SSMQ_ITERATED_MAX
 ITERATED_LAUNCH_LOOP = 1   # flags bit 0 of ssmq_filter_iterated_dev
 
@@ -323,6 +324,13 @@ _PROTOTYPES = {
                                     [c_double_p, ctypes.c_int64] * 3 + [ctypes.c_void_p] * 4),
     'ssmq_filter_noise_sweep_kernel_name': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Integrand), ctypes.c_void_p,
                                                            ctypes.POINTER(Integrand), ctypes.c_int, ctypes.c_char_p, ctypes.c_int]),
+    # (h_dyn, f_dyn, h_obs, f_obs, recursion, B, ld, T, d_y, M, gqg, gqg_stride, rr, rr_stride, x0, x0_stride, pi, mu0, d_fm, d_fP,
+    #  d_mode_prob, d_loglik, d_loglik_total, d_status)
+    'ssmq_filter_imm_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Integrand), ctypes.c_void_p, ctypes.POINTER(Integrand), ctypes.c_int,
+                                           ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_int] +
+                            [c_double_p, ctypes.c_int64] * 3 + [c_double_p, c_double_p] + [ctypes.c_void_p] * 6),
+    'ssmq_filter_imm_kernel_name': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Integrand), ctypes.c_void_p, ctypes.POINTER(Integrand),
+                                                   ctypes.c_int, ctypes.c_char_p, ctypes.c_int]),
     'ssmq_filter_iterated_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Integrand), ctypes.c_void_p, ctypes.POINTER(Integrand),
                                                 ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int] +
                                  [ctypes.c_void_p] * 3 + [c_double_p, c_double_p] + [ctypes.c_void_p] * 4),

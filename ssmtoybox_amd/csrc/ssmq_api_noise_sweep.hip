@@ -22,8 +22,9 @@ static int noise_refuse(int code, const std::string &why) {
     return code;
 }
 
-// What both entry points check, in this order, before anything else happens; *shape: the key of the kernel's table.
-static int noise_sweep_route(const ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, const ssmq_transform *h_obs, const ssmq_integrand *f_obs,
+// What both entry points check, in this order, before anything else happens; *shape: the key of the kernel's table.  (Also the
+// route of the IMM filter over noise modes, ssmq_api_imm.hip: the same range.)
+int noise_sweep_route(const ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, const ssmq_transform *h_obs, const ssmq_integrand *f_obs,
                              int recursion, FilterShape *shape, const char **name) {
     if (!h_dyn || !h_obs || !f_dyn || !f_obs) return noise_refuse(SSMQ_E_ARG, "filter_noise_sweep: bad argument");
     if (recursion != SSMQ_RECURSION_GAUSS && recursion != SSMQ_RECURSION_STUDENT) return noise_refuse(SSMQ_E_ARG, "filter_noise_sweep: bad recursion");
@@ -56,8 +57,8 @@ static int noise_sweep_route(const ssmq_transform *h_dyn, const ssmq_integrand *
 }
 
 // One row array: `rows` rows of n doubles (stride 0: one row; else stride == n and P rows), every entry finite.  Null is allowed
-// where `optional` (zeros).
-static int noise_rows_ok(const char *what, const double *a, int64_t stride, int n, int P, bool optional) {
+// where `optional` (zeros).  (Also the mode rows of ssmq_api_imm.hip.)
+int noise_rows_ok(const char *what, const double *a, int64_t stride, int n, int P, bool optional) {
     if (!a) return optional ? SSMQ_OK : noise_refuse(SSMQ_E_ARG, std::string("filter_noise_sweep: ") + what + " is null");
     if (stride != 0 && stride != n)
         return noise_refuse(SSMQ_E_ARG, std::string("filter_noise_sweep: the row stride of ") + what + " is 0 (shared) or the row size " + std::to_string(n));

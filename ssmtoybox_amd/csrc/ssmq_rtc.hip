@@ -886,6 +886,18 @@ extern "C" int ssmq_rtc_compile_check(int32_t id, int32_t id_obs, int kind, int 
         if (rc) return rc;
         return compile_check_text(expr, "ssmq::PcrlbArgs", ids, arch, log, len);
     }
+    if (kind == SSMQ_RTC_IMM) {   // k_imm_loop<D, E (= Y), N, N_obs, id, id_obs, opt (= SELO), form, tp>: built-in integrands
+        FInfo fd, fo;
+        if (!arch || !*arch || is_user_integrand(id) || is_user_integrand(id_obs) || !integrand_info(id, &fd) || !integrand_info(id_obs, &fo) || D < 1 ||
+            D > 6 || E < 1 || E > 4 || N < 2 || N_obs < 2 || (form != SSMQ_FORM_BQ && form != SSMQ_FORM_SIGMA) || tp < 0 || tp > 1 ||
+            (form == SSMQ_FORM_SIGMA && tp) || (opt != 0 && opt != 1)) {
+            set_error("ssmq_rtc_compile_check: bad argument");
+            return SSMQ_E_ARG;
+        }
+        char b[256];
+        snprintf(b, sizeof(b), "ssmq::k_imm_loop<%d, %d, %d, %d, %d, %d, %d, %d, %d>", D, E, N, N_obs, id, id_obs, opt, form, tp);
+        return compile_check_text(b, "ssmq::ImmArgs", {}, arch, log, len);
+    }
     if (kind == SSMQ_RTC_MC) {   // k_mc_moments<id, D, E, 0>: N, N_obs, form, tp and opt are not read
         FInfo fm;
         if (!arch || !*arch || !integrand_info(id, &fm)) {

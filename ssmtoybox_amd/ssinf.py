@@ -95,6 +95,46 @@ def noise_grid(cov, scales):
     return np.ascontiguousarray(scales[:, None, None] * cov)
 
 
+def mode_transition(M, stay):
+    """The transition matrix of M modes that keep their mode with probability `stay` and go to each of the others with equal
+    probability: (M, M), `stay` on the diagonal and (1 - stay) / (M - 1) off it (M = 1: [[1]])."""
+    M = int(M)
+    if M < 1 or not 0.0 <= float(stay) <= 1.0:
+        raise ValueError('mode_transition: M >= 1 and 0 <= stay <= 1')
+    if M == 1:
+        return np.ones((1, 1))
+    pi = np.full((M, M), (1.0 - float(stay)) / (M - 1))
+    np.fill_diagonal(pi, float(stay))
+    return pi
+
+
+IMM_MAX_MODES = 8
+
+
+def _mode_probabilities(pi, mu0):
+    """(pi (M, M), mu0 (M,)) of an IMM pass as C arrays, checked as the library checks them: 1 <= M <= IMM_MAX_MODES
+    (NotImplementedError beyond), entries finite and non-negative, every row of pi and mu0 summing to 1 within 1e-12 (ValueError
+    naming the row).  mu0 None: uniform."""
+    pi = np.ascontiguousarray(pi, dtype=np.float64)
+    if pi.ndim != 2 or pi.shape[0] != pi.shape[1] or pi.shape[0] < 1:
+        raise ValueError('IMM: pi is a square (M, M) matrix with M >= 1; got shape {}'.format(pi.shape))
+    M = pi.shape[0]
+    if M > IMM_MAX_MODES:
+        raise NotImplementedError('IMM: 1 <= M <= {} modes; got M = {}'.format(IMM_MAX_MODES, M))
+    mu0 = np.full(M, 1.0 / M) if mu0 is None else np.ascontiguousarray(mu0, dtype=np.float64)
+    if mu0.shape != (M,):
+        raise ValueError('IMM: mu0 is None (uniform) or has shape ({},); got {}'.format(M, mu0.shape))
+    for name, row in [('row {} of pi'.format(i), pi[i]) for i in range(M)] + [('mu0', mu0)]:
+        if not np.isfinite(row).all() or (row < 0).any():
+            raise ValueError('IMM: {} has an entry that is not finite or is negative'.format(name))
+        total = 0.0
+        for v in row:
+            total += float(v)
+        if not abs(total - 1.0) <= 1e-12:
+            raise ValueError('IMM: {} does not sum to 1 within 1e-12 (sum {!r})'.format(name, total))
+    return pi, mu0
+
+
 def _cov_rows(value, own, name):
     """A covariance argument of a noise sweep - None (the model's own), one matrix (shared by all rows) or a stack (P, n, n) - as
     ((rows, n, n) float64, whether it is a stack); ValueError for another shape and for a row that is not finite or not symmetric,
@@ -546,6 +586,108 @@ class GaussianInference:
         index, table = fit_table(out['loglik_total'], out['status'], np.zeros(s['P'], dtype=np.int32))
         q, r = (rows[index if len(rows) > 1 else 0].copy() for rows in (s['q'], s['r']))      # (one row: shared by all)
         return index, q, r, table
+
+    # ---- interacting multiple-model filter over noise modes: M rows of a noise sweep coupled every step (`ssmq_filter_imm_dev`) ---
+    def _imm_setup(self, pi, mu0, q_cov, r_cov, x0_cov, x0_mean):
+        """The refusals of the IMM pass that need no library - those of the noise sweeps (`_noise_sweep_setup`, naming the range),
+        then the mode count and the probabilities (`_mode_probabilities`) - and the arrays of the C entry point.  The modes are the
+        rows of a noise sweep: at least one of q_cov, r_cov, x0_cov is a stack (M, n, n), or M = 1 and none is."""
+        pi_shape = np.shape(pi)
+        M = pi_shape[0] if len(pi_shape) == 2 else 0
+        stacked = any(a is not None and np.ndim(a) == 3 for a in (q_cov, r_cov, x0_cov))
+        if not stacked and M == 1:     # one mode, nothing varied: a stack of one row of the model's own process noise
+            q_cov = np.atleast_2d(np.asarray(self.q_cov if q_cov is None else q_cov, dtype=np.float64))[None]
+        try:
+            s = self._noise_sweep_setup(q_cov, r_cov, x0_cov)
+        except NotImplementedError as e:
+            raise NotImplementedError('IMM over noise modes has the range of the noise sweeps: ' + str(e)) from None
+        pi, mu0 = _mode_probabilities(pi, mu0)
+        if s['P'] != pi.shape[0]:
+            raise ValueError('IMM: the stacks of q_cov / r_cov / x0_cov have {} rows and pi has M = {}'.format(s['P'], pi.shape[0]))
+        if x0_mean is not None:
+            x0_mean = np.asarray(x0_mean, dtype=np.float64)
+            D = s['D']
+            if x0_mean.shape not in ((D,), (s['P'], D)) or not np.isfinite(x0_mean).all():
+                raise ValueError('IMM: x0_mean is None, one finite ({0},) vector or a stack (M, {0})'.format(D))
+            rows = np.broadcast_to(s['x0'], (s['P'] if x0_mean.ndim == 2 else s['x0'].shape[0], D + D * D)).copy()
+            rows[:, :D] = x0_mean
+            s['x0'] = np.ascontiguousarray(rows)
+        s.update(M=pi.shape[0], pi=pi, mu0=mu0)
+        return s
+
+    def imm_kernel_name(self, M=1):
+        """Which kernel `imm_pass*` run for this filter (the same for every number of modes M)."""
+        self._imm_setup(mode_transition(int(M), 0.9), None, noise_grid(self.q_cov, np.ones(int(M))), None, None, None)
+        return self._kernel_name('ssmq_filter_imm_kernel_name', 0, unsupported=True)
+
+    def _imm_launch(self, stage, s, d_y, B, ld, T, device):
+        alloc = stage.device if device else stage.scratch
+        D, M = s['D'], s['M']
+        d_fm, d_fP, d_mp = alloc(8 * T * D * ld), alloc(8 * T * D * D * ld), alloc(8 * T * M * ld)
+        d_ll, d_tot, d_st = alloc(8 * T * ld), alloc(8 * ld), alloc(4 * ld)
+        vp, dp = _lib.vp, _lib.dp
+        rows = []
+        for a in (s['gqg'], s['rr'], s['x0']):
+            rows += [dp(a), a.shape[1] if a.shape[0] > 1 else 0]
+        _lib.check(_lib.load().ssmq_filter_imm_dev(*self._pair(), 0, B, ld, T, vp(d_y), M, *rows, dp(s['pi']), dp(s['mu0']), vp(d_fm), vp(d_fP),
+                                                   vp(d_mp), vp(d_ll), vp(d_tot), vp(d_st)), 'ssmq_filter_imm_dev', True)
+        return d_fm, d_fP, d_mp, d_ll, d_tot, d_st
+
+    def imm_pass_dev(self, d_y, B, ld, T, pi, mu0=None, q_cov=None, r_cov=None, x0_cov=None, x0_mean=None):
+        """`imm_pass_batch` on measurements that are already on the device (planes [T][dim_y][ld], ld a multiple of 64):
+        DeviceBuffers d_fm [T][D][ld], d_fP [T][D*D][ld], d_mode_prob [T][M][ld], d_loglik [T][ld], d_loglik_total [ld], d_status [ld]
+        int32; the caller frees them."""
+        s = self._imm_setup(pi, mu0, q_cov, r_cov, x0_cov, x0_mean)
+        if ld % 64 or ld < B:
+            raise ValueError('IMM: ld is a multiple of 64 and at least B')
+        with _lib.Staging() as stage:
+            bufs = self._imm_launch(stage, s, d_y, B, ld, T, True)
+            stage.release(*bufs)
+        return bufs
+
+    def imm_pass_batch(self, data, pi, mu0=None, q_cov=None, r_cov=None, x0_cov=None, x0_mean=None, raise_on_failure=True):
+        """Interacting multiple-model filter (Blom & Bar-Shalom 1988) over M noise modes of this filter on `data` (dim_y, T, B), the
+        whole pass in one kernel launch (k_imm_loop<>).  Mode j is `type(self)` on the same models and weights with noise_rv.cov =
+        q_cov[j], r_cov[j], initial covariance x0_cov[j] and initial mean x0_mean[j]: each of q_cov / r_cov / x0_cov is None - the
+        model's own -, one matrix shared by all modes, or a stack (M, n, n), as in `noise_sweep_batch`; at least one is a stack, or
+        M = 1.  x0_mean: None, (D,) or (M, D).  pi (M, M): pi[i][j] the probability of going from mode i to mode j (`mode_transition`);
+        mu0 (M,): the initial mode probabilities, None = uniform.  Rows of pi and mu0 sum to 1 within 1e-12 (ValueError naming the
+        row); 1 <= M <= 8.
+
+        Every step the modes' moments are mixed by the Markov probabilities, each mode runs its filter step, the modes are weighted
+        by their measurement likelihood, and the combined moments are stored (the steps: include/ssmq.h, ssmq_filter_imm_dev).
+        Returns a dict: mean (D, T, B), cov (D, D, T, B), mode_prob (M, T, B), loglik (T, B) = log p(y_k | y_1..k-1), loglik_total (B,),
+        status (B,) int32 - 1 + the first step at which a mode's scores or a mixed quantity is not a finite number (every output of
+        that trajectory is NaN from there on), or 0.  Sets fi_mean / fi_cov / status as `forward_pass_batch` does and raises
+        LinAlgError for a failed trajectory unless raise_on_failure is False.  Touches neither the weights nor the noise of the
+        object.  Range: that of the noise sweeps (`_NOISE_SWEEP_RANGE`; NotImplementedError before the library is loaded)."""
+        s = self._imm_setup(pi, mu0, q_cov, r_cov, x0_cov, x0_mean)
+        data = np.asarray(data, dtype=np.float64)
+        if data.ndim != 3 or data.shape[0] != s['Y']:
+            raise ValueError('IMM: data is (dim_y, T, B)')
+        Y, T, B = data.shape
+        if B < 1 or T < 1:
+            raise ValueError('IMM: data holds at least one step of at least one trajectory')
+        ld, D, M = _lib.padded(B), s['D'], s['M']
+        with _lib.Staging() as stage:
+            d_y = stage.scratch(8 * T * Y * ld)
+            _lib.upload_study(data, Y, ld, d_y)
+            d_fm, d_fP, d_mp, d_ll, d_tot, d_st = self._imm_launch(stage, s, d_y, B, ld, T, False)
+            out = {'mean': _lib.download_study(d_fm, (D,), T, B, ld), 'cov': _lib.download_study(d_fP, (D, D), T, B, ld),
+                   'mode_prob': _lib.download_study(d_mp, (M,), T, B, ld), 'loglik': _lib.download_study(d_ll, (), T, B, ld),
+                   'loglik_total': d_tot.download((ld,))[:B].copy(), 'status': d_st.download((ld,), dtype=np.int32)[:B].copy()}
+        self._data = data
+        self.status = out['status']
+        if raise_on_failure:
+            _raise_failed(self.status, message='a mode\'s scores or a mixed moment is not a finite number (trajectory {}, step {})')
+        self.fi_mean, self.fi_cov = out['mean'], out['cov']
+        return out
+
+    def imm_pass(self, data, pi, **kwargs):
+        """`imm_pass_batch` for one trajectory, data (dim_y, T): mean (D, T), cov (D, D, T), mode_prob (M, T), loglik (T,),
+        loglik_total, status."""
+        out = self.imm_pass_batch(np.asarray(data)[..., None], pi, **kwargs)
+        return {k: (v[..., 0] if v.ndim else v) for k, v in out.items()}
 
     # ---- iterated posterior linearisation (IPLF): J measurement updates per step, each re-linearised around the posterior ------
     def _iterated_refusal(self, iterations):
