@@ -111,8 +111,9 @@ extern "C" int ssmq_filter_imm_dev(ssmq_transform *h_dyn, const ssmq_integrand *
     std::copy(pi, pi + (size_t)M * M, host.begin() + o_pi);
     std::copy(mu0, mu0 + M, host.begin() + o_mu);
     const bool ttd = time_table(f_dyn->id, T, host.data() + o_tt), tto = time_table(f_obs->id, T, host.data() + o_tt + T);
-    double *dev = nullptr;
-    SSMQ_HIP(hipMalloc((void **)&dev, sizeof(double) * host.size()));
+    DeviceImage img;
+    if ((rc = img.alloc(host.size()))) return rc;
+    double *const dev = img.dev;
     ImmArgs a;
     memset(&a, 0, sizeof(a));
     a.y = d_y; a.c_dyn = h_dyn->d_small; a.c_obs = h_obs->d_small;
@@ -125,9 +126,8 @@ extern "C" int ssmq_filter_imm_dev(ssmq_transform *h_dyn, const ssmq_integrand *
     fill_fpar(f_obs, &a.fo);
     a.fd.ttab = ttd ? dev + o_tt : nullptr;
     a.fo.ttab = tto ? dev + o_tt + T : nullptr;
-    rc = hip_fail(hipMemcpyAsync(dev, host.data(), sizeof(double) * host.size(), hipMemcpyHostToDevice, s), "filter_imm: upload");
+    rc = img.upload(host, "filter_imm: upload");
     if (!rc) rc = launch_imm(shape, a, s);
     const int rs = hip_fail(hipStreamSynchronize(s), "filter_imm");
-    hipFree(dev);
     return rc ? rc : rs;
 }

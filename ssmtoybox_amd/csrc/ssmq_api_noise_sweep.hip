@@ -28,27 +28,24 @@ int noise_sweep_route(const ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, 
                              int recursion, FilterShape *shape, const char **name) {
     if (!h_dyn || !h_obs || !f_dyn || !f_obs) return noise_refuse(SSMQ_E_ARG, "filter_noise_sweep: bad argument");
     if (recursion != SSMQ_RECURSION_GAUSS && recursion != SSMQ_RECURSION_STUDENT) return noise_refuse(SSMQ_E_ARG, "filter_noise_sweep: bad recursion");
-    if (is_user_integrand(f_dyn) || is_user_integrand(f_obs))
-        return noise_refuse(SSMQ_E_UNSUPPORTED, "filter_noise_sweep: user-defined models (device_code) are not implemented");
-    if (recursion == SSMQ_RECURSION_STUDENT) return noise_refuse(SSMQ_E_UNSUPPORTED, "filter_noise_sweep: the Studentian recursion is not implemented");
-    for (const ssmq_transform *h : {h_dyn, h_obs}) {
-        if (is_mo(h)) return noise_refuse(SSMQ_E_UNSUPPORTED, "filter_noise_sweep: multi-output transforms are not implemented");
-        if (is_trunc(h)) return noise_refuse(SSMQ_E_UNSUPPORTED, "filter_noise_sweep: truncated sigma-point transforms are not implemented");
-        if (is_gpqd(h)) return noise_refuse(SSMQ_E_UNSUPPORTED, "filter_noise_sweep: GPQ+D transforms are not implemented");
-        if (is_taylor_gpqd(h) || h->form == SSMQ_FORM_TAYLOR1)
-            return noise_refuse(SSMQ_E_UNSUPPORTED, "filter_noise_sweep: linearisation and Taylor-GPQD transforms are not implemented");
-    }
-    if (h_dyn->form != h_obs->form || (h_dyn->tp_nu > 0.0) != (h_obs->tp_nu > 0.0) || (h_dyn->form != SSMQ_FORM_BQ && h_dyn->form != SSMQ_FORM_SIGMA))
-        return noise_refuse(SSMQ_E_UNSUPPORTED, "filter_noise_sweep: the two transforms are of different forms");
     const int D = h_dyn->D, Y = h_obs->E;
-    if (h_dyn->E != D || h_obs->D != D) return noise_refuse(SSMQ_E_ARG, "filter_noise_sweep: needs dyn (D -> D) and obs (D -> Y) transforms");
-    FInfo fid, fio;
-    if (!integrand_info(f_dyn->id, &fid) || !integrand_info(f_obs->id, &fio)) return noise_refuse(SSMQ_E_ARG, "filter_noise_sweep: unknown integrand id");
-    if (f_dyn->id == SSMQ_F_UNGMNA_DYN || f_dyn->id == SSMQ_F_CTRS_DYN || f_obs->id == SSMQ_F_UNGMNA_MEAS || fid.din != D || fid.dout != D ||
-        f_dyn->n_idx > 0)
-        return noise_refuse(SSMQ_E_UNSUPPORTED, "filter_noise_sweep: models that take their noise as an argument (non-additive noise) are not implemented");
+    auto handles = [&]() {
+        if (recursion == SSMQ_RECURSION_STUDENT) return noise_refuse(SSMQ_E_UNSUPPORTED, "filter_noise_sweep: the Studentian recursion is not implemented");
+        for (const ssmq_transform *h : {h_dyn, h_obs}) {
+            if (is_mo(h)) return noise_refuse(SSMQ_E_UNSUPPORTED, "filter_noise_sweep: multi-output transforms are not implemented");
+            if (is_trunc(h)) return noise_refuse(SSMQ_E_UNSUPPORTED, "filter_noise_sweep: truncated sigma-point transforms are not implemented");
+            if (is_gpqd(h)) return noise_refuse(SSMQ_E_UNSUPPORTED, "filter_noise_sweep: GPQ+D transforms are not implemented");
+            if (is_taylor_gpqd(h) || h->form == SSMQ_FORM_TAYLOR1)
+                return noise_refuse(SSMQ_E_UNSUPPORTED, "filter_noise_sweep: linearisation and Taylor-GPQD transforms are not implemented");
+        }
+        if (h_dyn->form != h_obs->form || (h_dyn->tp_nu > 0.0) != (h_obs->tp_nu > 0.0) || (h_dyn->form != SSMQ_FORM_BQ && h_dyn->form != SSMQ_FORM_SIGMA))
+            return noise_refuse(SSMQ_E_UNSUPPORTED, "filter_noise_sweep: the two transforms are of different forms");
+        if (h_dyn->E != D || h_obs->D != D) return noise_refuse(SSMQ_E_ARG, "filter_noise_sweep: needs dyn (D -> D) and obs (D -> Y) transforms");
+        return (int)SSMQ_OK;
+    };
+    int selo = 0;
+    if (int rc = additive_pair_route(noise_refuse, "filter_noise_sweep", f_dyn, f_obs, D, handles, &selo)) return rc;
     if (D > 6 || Y > 4) return noise_refuse(SSMQ_E_UNSUPPORTED, "filter_noise_sweep: dimension out of range");
-    const int selo = sel_pattern(f_obs, fio.din);
     *shape = {f_dyn->id, f_obs->id, D, Y, h_dyn->N, h_obs->N, h_dyn->form, h_dyn->tp_nu > 0.0 ? 1 : 0, selo, 0};
     const char *kn = selo < 0 || !h_dyn->d_small || !h_obs->d_small ? nullptr : find_noise_sweep_kernel(*shape);
     if (!kn) return noise_refuse(SSMQ_E_UNSUPPORTED, "filter_noise_sweep: no kernel for this pair of models and point sets");
@@ -103,14 +100,7 @@ extern "C" int ssmq_filter_noise_sweep_dev(ssmq_transform *h_dyn, const ssmq_int
         return rc;
     if ((rc = ensure_device())) return rc;
     if (B == 0) return SSMQ_OK;
-    hipStream_t s = stream();
-    const size_t items = (size_t)P * ld;
-    if (T == 0) {   // nothing to score (as ssmq_filter_innovations_dev): empty sums
-        SSMQ_HIP(hipMemsetAsync(d_loglik_total, 0, sizeof(double) * items, s));
-        SSMQ_HIP(hipMemsetAsync(d_nis_mean, 0, sizeof(double) * items, s));
-        SSMQ_HIP(hipMemsetAsync(d_status, 0, sizeof(int32_t) * items, s));
-        return hip_fail(hipStreamSynchronize(s), "filter_noise_sweep");
-    }
+    if (T == 0) return score_empty("filter_noise_sweep", P, ld, nullptr, d_loglik_total, d_nis_mean, d_status);
     // ---- one host image: gqg rows | rr rows | x0 rows | ttab_dyn [T] | ttab_obs [T]; a null array is one row of zeros -----------
     const size_t rows_q = gqg && gqg_stride ? P : 1, rows_r = rr && rr_stride ? P : 1, rows_x = x0_stride ? P : 1;
     const size_t o_r = (rows_q * nq + 1) / 2 * 2, o_x = o_r + (rows_r * nr + 1) / 2 * 2, o_tt = o_x + (rows_x * nx + 1) / 2 * 2;
@@ -119,8 +109,10 @@ extern "C" int ssmq_filter_noise_sweep_dev(ssmq_transform *h_dyn, const ssmq_int
     if (rr) std::copy(rr, rr + rows_r * nr, host.begin() + o_r);
     std::copy(x0, x0 + rows_x * nx, host.begin() + o_x);
     const bool ttd = time_table(f_dyn->id, T, host.data() + o_tt), tto = time_table(f_obs->id, T, host.data() + o_tt + T);
-    double *dev = nullptr;
-    SSMQ_HIP(hipMalloc((void **)&dev, sizeof(double) * host.size()));
+    DeviceImage img;
+    if ((rc = img.alloc(host.size()))) return rc;
+    double *const dev = img.dev;
+    hipStream_t s = stream();
     NoiseSweepArgs a;
     memset(&a, 0, sizeof(a));
     a.y = d_y; a.c_dyn = h_dyn->d_small; a.c_obs = h_obs->d_small;
@@ -133,9 +125,8 @@ extern "C" int ssmq_filter_noise_sweep_dev(ssmq_transform *h_dyn, const ssmq_int
     fill_fpar(f_obs, &a.fo);
     a.fd.ttab = ttd ? dev + o_tt : nullptr;
     a.fo.ttab = tto ? dev + o_tt + T : nullptr;
-    rc = hip_fail(hipMemcpyAsync(dev, host.data(), sizeof(double) * host.size(), hipMemcpyHostToDevice, s), "filter_noise_sweep: upload");
+    rc = img.upload(host, "filter_noise_sweep: upload");
     if (!rc) rc = launch_noise_sweep(shape, a, s);
     const int rs = hip_fail(hipStreamSynchronize(s), "filter_noise_sweep");
-    hipFree(dev);
     return rc ? rc : rs;
 }

@@ -10,8 +10,8 @@
 
 namespace ssmq {
 
-const char *find_score_kernel(int fd, int fo, int D, int Y, int ND, int NO, int selo, int form, int tp, int stu);
-int launch_score(int fd, int fo, int D, int Y, int ND, int NO, int selo, int form, int tp, int stu, const ScoreArgs &a, hipStream_t s);
+const char *find_score_kernel(const ScoreShape &shape);
+int launch_score(const ScoreShape &shape, const ScoreArgs &a, hipStream_t s);
 // row p's dense constant block (ssmq_api_sweep.hip)
 void sweep_block(int D, int E, int N, const double *xi, const double *wm, const double *Wc, const double *Wcc, double model_var, double *s);
 
@@ -25,22 +25,17 @@ static int score_refuse(int code, const std::string &why) {
     return code;
 }
 
-// What every entry point checks first, in this order; *selo: the measurement model's index pattern.
+// What every entry point checks first, in this order; *shape: the key of the kernel's table.
 static int score_route(const char *who, const ssmq_integrand *f_dyn, const ssmq_integrand *f_obs, int N_dyn, int N_obs, int D, int Y, int form,
-                       int tp, int stu, int *selo, const char **name) {
+                       int tp, int stu, ScoreShape *shape, const char **name) {
     const std::string w(who);
     if (!f_dyn || !f_obs || D < 1 || Y < 1 || N_dyn < 1 || N_obs < 1) return score_refuse(SSMQ_E_ARG, w + ": bad argument");
-    if (is_user_integrand(f_dyn) || is_user_integrand(f_obs))
-        return score_refuse(SSMQ_E_UNSUPPORTED, w + ": user-defined models (device_code) are not implemented");
-    FInfo fid, fio;
-    if (!integrand_info(f_dyn->id, &fid) || !integrand_info(f_obs->id, &fio)) return score_refuse(SSMQ_E_ARG, w + ": unknown integrand id");
-    if (f_dyn->id == SSMQ_F_UNGMNA_DYN || f_dyn->id == SSMQ_F_CTRS_DYN || f_obs->id == SSMQ_F_UNGMNA_MEAS || fid.din != D || fid.dout != D ||
-        f_dyn->n_idx > 0)
-        return score_refuse(SSMQ_E_UNSUPPORTED, w + ": models that take their noise as an argument (non-additive noise) are not implemented");
+    int selo = 0;
+    if (int rc = additive_pair_route(score_refuse, w, f_dyn, f_obs, D, [] { return (int)SSMQ_OK; }, &selo)) return rc;
     if (D > 4 || Y > 2) return score_refuse(SSMQ_E_UNSUPPORTED, w + ": dimension out of range");
     if (N_dyn > 2 * D + 1 || N_obs > 2 * D + 1 || N_dyn < 2 || N_obs < 2) return score_refuse(SSMQ_E_UNSUPPORTED, w + ": point count out of range");
-    *selo = sel_pattern(f_obs, fio.din);
-    const char *kn = *selo < 0 ? nullptr : find_score_kernel(f_dyn->id, f_obs->id, D, Y, N_dyn, N_obs, *selo, form, tp, stu);
+    *shape = {{f_dyn->id, f_obs->id, D, Y, N_dyn, N_obs, form, tp, selo, 0}, stu};
+    const char *kn = selo < 0 ? nullptr : find_score_kernel(*shape);
     if (!kn) return score_refuse(SSMQ_E_UNSUPPORTED, w + ": no kernel for this pair of models, point sets, form and recursion");
     if (name) *name = kn;
     return SSMQ_OK;
@@ -83,8 +78,8 @@ static void score_row(double *r, int D, int Y, int T, double nu_dyn, double nu_o
     for (int k = 0; k < T; ++k) q[k] = scale ? scale[k] : 1.0;
 }
 
-// T == 0: nothing to score - empty sums; a failed row is still a failed row (theta_status: host [P] or null)
-static int score_empty(const char *who, int P, int64_t ld, const int32_t *theta_status, double *d_ll_total, double *d_nis_mean, int32_t *d_status) {
+// T == 0 (ssmq_host.h): also the empty pass of ssmq_filter_sweep_dev and ssmq_filter_noise_sweep_dev
+int score_empty(const char *who, int P, int64_t ld, const int32_t *theta_status, double *d_ll_total, double *d_nis_mean, int32_t *d_status) {
     hipStream_t s = stream();
     const size_t items = (size_t)P * ld;
     SSMQ_HIP(hipMemsetAsync(d_ll_total, 0, sizeof(double) * items, s));
@@ -104,7 +99,8 @@ static int score_empty(const char *who, int P, int64_t ld, const int32_t *theta_
 struct ScoreCall {
     const char *who;
     const ssmq_integrand *fd, *fo;
-    int D, Y, ND, NO, selo, form, tp, stu, emv_dyn, emv_obs, P, T;
+    ScoreShape shape;
+    int emv_dyn, emv_obs, P, T;
     int64_t B, ld;
     const double *d_y, *d_c_dyn, *d_c_obs;
     const int32_t *theta_status;
@@ -112,8 +108,8 @@ struct ScoreCall {
     int32_t *status;
 };
 static int score_launch(const ScoreCall &c, const std::vector<double> &consts, const std::vector<double> &rows) {
-    const int D = c.D, Y = c.Y, T = c.T, P = c.P;
-    const size_t nd = const_layout(D, D, c.ND, c.form).total, no = const_layout(D, Y, c.NO, c.form).total;
+    const int D = c.shape.D, Y = c.shape.Y, T = c.T, P = c.P;
+    const size_t nd = const_layout(D, D, c.shape.ND, c.shape.form).total, no = const_layout(D, Y, c.shape.NO, c.shape.form).total;
     const size_t rs = score_row_doubles(D, Y, T), ntt = ((size_t)2 * T + 7) / 8 * 8;
     const size_t o_rows = consts.size(), o_tt = o_rows + rows.size(), n_dbl = o_tt + ntt;
     std::vector<double> host(n_dbl + ((size_t)P + 1) / 2, 0.0);
@@ -122,8 +118,9 @@ static int score_launch(const ScoreCall &c, const std::vector<double> &consts, c
     const bool ttd = time_table(c.fd->id, T, host.data() + o_tt), tto = time_table(c.fo->id, T, host.data() + o_tt + T);
     if (c.theta_status) memcpy(host.data() + n_dbl, c.theta_status, sizeof(int32_t) * P);
     hipStream_t s = stream();
-    double *dev = nullptr;
-    SSMQ_HIP(hipMalloc((void **)&dev, sizeof(double) * host.size()));
+    DeviceImage img;
+    if (int rc = img.alloc(host.size())) return rc;
+    double *const dev = img.dev;
     ScoreArgs a;
     memset(&a, 0, sizeof(a));
     a.y = c.d_y;
@@ -138,10 +135,9 @@ static int score_launch(const ScoreCall &c, const std::vector<double> &consts, c
     fill_fpar(c.fo, &a.fo);
     a.fd.ttab = ttd ? dev + o_tt : nullptr;
     a.fo.ttab = tto ? dev + o_tt + T : nullptr;
-    int rc = hip_fail(hipMemcpyAsync(dev, host.data(), sizeof(double) * host.size(), hipMemcpyHostToDevice, s), c.who);
-    if (!rc) rc = launch_score(c.fd->id, c.fo->id, D, Y, c.ND, c.NO, c.selo, c.form, c.tp, c.stu, a, s);
+    int rc = img.upload(host, c.who);
+    if (!rc) rc = launch_score(c.shape, a, s);
     const int rs2 = hip_fail(hipStreamSynchronize(s), c.who);
-    hipFree(dev);
     return rc ? rc : rs2;
 }
 
@@ -153,10 +149,11 @@ extern "C" int ssmq_student_scores_kernel_name(const ssmq_transform *h_dyn, cons
                                                const ssmq_integrand *f_obs, char *buf, int len) {
     if (!buf || len <= 0) return score_refuse(SSMQ_E_ARG, "student_scores: bad argument");
     SSMQ_HANDLE_LOCK(h_dyn, h_obs);
-    int form = 0, tp = 0, selo = 0;
+    int form = 0, tp = 0;
+    ScoreShape shape;
     const char *name = nullptr;
     if (int rc = score_handles("student_scores", h_dyn, h_obs, &form, &tp)) return rc;
-    if (int rc = score_route("student_scores", f_dyn, f_obs, h_dyn->N, h_obs->N, h_dyn->D, h_obs->E, form, tp, 1, &selo, &name)) return rc;
+    if (int rc = score_route("student_scores", f_dyn, f_obs, h_dyn->N, h_obs->N, h_dyn->D, h_obs->E, form, tp, 1, &shape, &name)) return rc;
     snprintf(buf, len, "%s", name);
     return SSMQ_OK;
 }
@@ -166,10 +163,11 @@ extern "C" int ssmq_student_scores_dev(ssmq_transform *h_dyn, const ssmq_integra
                                        const double *GqG, const double *r_smat, const double *scale, double dof, double *d_nis,
                                        double *d_loglik, double *d_loglik_total, double *d_nis_mean, int32_t *d_status) {
     SSMQ_HANDLE_LOCK(h_dyn, h_obs);
-    int form = 0, tp = 0, selo = 0;
+    int form = 0, tp = 0;
+    ScoreShape shape;
     if (int rc = score_handles("student_scores", h_dyn, h_obs, &form, &tp)) return rc;
     const int D = h_dyn->D, Y = h_obs->E;
-    if (int rc = score_route("student_scores", f_dyn, f_obs, h_dyn->N, h_obs->N, D, Y, form, tp, 1, &selo, nullptr)) return rc;
+    if (int rc = score_route("student_scores", f_dyn, f_obs, h_dyn->N, h_obs->N, D, Y, form, tp, 1, &shape, nullptr)) return rc;
     if (B < 0 || ld < B || ld % kSmallBlock != 0 || T < 0 || !d_y || !x0_mean || !x0_smat || (T > 0 && !scale) || !(dof > 2.0) || !std::isfinite(dof) ||
         !d_loglik_total || !d_nis_mean || !d_status)
         return score_refuse(SSMQ_E_ARG, "student_scores: bad argument (ld a multiple of 64 and >= B, scale [T], dof > 2)");
@@ -178,7 +176,7 @@ extern "C" int ssmq_student_scores_dev(ssmq_transform *h_dyn, const ssmq_integra
     if (T == 0) return score_empty("student_scores", 1, ld, nullptr, d_loglik_total, d_nis_mean, d_status);
     std::vector<double> rows(score_row_doubles(D, Y, T));
     score_row(rows.data(), D, Y, T, h_dyn->tp_nu, h_obs->tp_nu, dof, GqG, r_smat, x0_mean, x0_smat, scale);
-    ScoreCall c{"student_scores", f_dyn, f_obs, D, Y, h_dyn->N, h_obs->N, selo, form, tp, 1, h_dyn->emv_mode, h_obs->emv_mode, 1, T, B, ld, d_y,
+    ScoreCall c{"student_scores", f_dyn, f_obs, shape, h_dyn->emv_mode, h_obs->emv_mode, 1, T, B, ld, d_y,
                 h_dyn->d_small, h_obs->d_small, nullptr, d_loglik_total, d_nis_mean, d_loglik, d_nis, d_status};
     return score_launch(c, std::vector<double>(), rows);
 }
@@ -187,9 +185,9 @@ extern "C" int ssmq_filter_sweep_t_kernel_name(const ssmq_integrand *f_dyn, cons
                                                int D, int Y, char *buf, int len) {
     if (!buf || len <= 0 || (recursion != SSMQ_RECURSION_GAUSS && recursion != SSMQ_RECURSION_STUDENT))
         return score_refuse(SSMQ_E_ARG, "filter_sweep_t: bad argument");
-    int selo = 0;
+    ScoreShape shape;
     const char *name = nullptr;
-    if (int rc = score_route("filter_sweep_t", f_dyn, f_obs, N_dyn, N_obs, D, Y, SSMQ_FORM_BQ, 1, recursion, &selo, &name)) return rc;
+    if (int rc = score_route("filter_sweep_t", f_dyn, f_obs, N_dyn, N_obs, D, Y, SSMQ_FORM_BQ, 1, recursion, &shape, &name)) return rc;
     snprintf(buf, len, "%s", name);
     return SSMQ_OK;
 }
@@ -202,8 +200,8 @@ extern "C" int ssmq_filter_sweep_t_dev(const ssmq_integrand *f_dyn, const ssmq_i
                                        double *d_loglik_steps, int32_t *d_status, int32_t *theta_status) {
     if (recursion != SSMQ_RECURSION_GAUSS && recursion != SSMQ_RECURSION_STUDENT) return score_refuse(SSMQ_E_ARG, "filter_sweep_t: bad recursion");
     const bool stu = recursion == SSMQ_RECURSION_STUDENT;
-    int selo = 0;
-    if (int rc = score_route("filter_sweep_t", f_dyn, f_obs, N_dyn, N_obs, D, Y, SSMQ_FORM_BQ, 1, recursion, &selo, nullptr)) return rc;
+    ScoreShape shape;
+    if (int rc = score_route("filter_sweep_t", f_dyn, f_obs, N_dyn, N_obs, D, Y, SSMQ_FORM_BQ, 1, recursion, &shape, nullptr)) return rc;
     if (!xi_dyn || !xi_obs || !par_dyn || !par_obs || !nu_dyn || !nu_obs || P < 1 || B < 0 || ld < B || ld % kSmallBlock != 0 || T < 0 || !d_y ||
         !x0_mean || !x0_mat || !d_loglik_total || !d_nis_mean || !d_status || !theta_status || (stu && (!dof || (T > 0 && !scale))))
         return score_refuse(SSMQ_E_ARG, "filter_sweep_t: bad argument (P >= 1, ld a multiple of 64 and >= B; Studentian recursion: dof [P], scale [P][T])");
@@ -248,7 +246,7 @@ extern "C" int ssmq_filter_sweep_t_dev(const ssmq_integrand *f_dyn, const ssmq_i
                   R ? R + (size_t)p * Y * Y : nullptr, x0_mean, x0_mat + (size_t)p * D * D, stu ? scale + (size_t)p * T : nullptr);
     }
     // the model variance of a t-process transform built with one output (the t-process filters of ssinf.py): the whole matrix for E > 1
-    ScoreCall c{"filter_sweep_t", f_dyn, f_obs, D, Y, N_dyn, N_obs, selo, SSMQ_FORM_BQ, 1, stu ? 1 : 0, D == 1 ? SSMQ_EMV_DIAG : SSMQ_EMV_BROADCAST,
+    ScoreCall c{"filter_sweep_t", f_dyn, f_obs, shape, D == 1 ? SSMQ_EMV_DIAG : SSMQ_EMV_BROADCAST,
                 Y == 1 ? SSMQ_EMV_DIAG : SSMQ_EMV_BROADCAST, P, T, B, ld, d_y, nullptr, nullptr, theta_status, d_loglik_total, d_nis_mean,
                 d_loglik_steps, nullptr, d_status};
     return score_launch(c, consts, rows);

@@ -8,8 +8,8 @@
 
 namespace ssmq {
 
-const char *find_sweep_kernel(int fd, int fo, int D, int Y, int ND, int NO, int selo);
-int launch_sweep(int fd, int fo, int D, int Y, int ND, int NO, int selo, const SweepArgs &a, hipStream_t s);
+const char *find_sweep_kernel(const FilterShape &shape);
+int launch_sweep(const FilterShape &shape, const SweepArgs &a, hipStream_t s);
 
 static const char kSweepRange[] =
     "filter_sweep: GP (kind 0) and Bayes-Sard (kind 1) transforms with the 'rbf' kernel on the built-in additive-noise model pairs of "
@@ -20,25 +20,23 @@ static int sweep_refuse(int code, const std::string &why) {
     return code;
 }
 
-// What both entry points check, in this order, before anything else happens; *selo: the measurement model's index pattern.
+// What both entry points check, in this order, before anything else happens; *shape: the key of the kernel's table.
 static int sweep_route(const ssmq_integrand *f_dyn, const ssmq_integrand *f_obs, int kind_dyn, int kind_obs, int N_dyn, int N_obs, int D, int Y,
-                       int *selo, const char **name) {
+                       FilterShape *shape, const char **name) {
     if (!f_dyn || !f_obs || D < 1 || Y < 1 || N_dyn < 1 || N_obs < 1) return sweep_refuse(SSMQ_E_ARG, "filter_sweep: bad argument");
-    if (is_user_integrand(f_dyn) || is_user_integrand(f_obs))
-        return sweep_refuse(SSMQ_E_UNSUPPORTED, "filter_sweep: user-defined models (device_code) are not implemented");
-    for (int kind : {kind_dyn, kind_obs})
-        if (kind != SSMQ_SWEEP_GP && kind != SSMQ_SWEEP_BS)
-            return sweep_refuse(SSMQ_E_UNSUPPORTED, "filter_sweep: the t-process and multi-output models are not implemented");
-    FInfo fid, fio;
-    if (!integrand_info(f_dyn->id, &fid) || !integrand_info(f_obs->id, &fio)) return sweep_refuse(SSMQ_E_ARG, "filter_sweep: unknown integrand id");
-    if (f_dyn->id == SSMQ_F_UNGMNA_DYN || f_dyn->id == SSMQ_F_CTRS_DYN || f_obs->id == SSMQ_F_UNGMNA_MEAS || fid.din != D || fid.dout != D ||
-        f_dyn->n_idx > 0)
-        return sweep_refuse(SSMQ_E_UNSUPPORTED, "filter_sweep: models that take their noise as an argument (non-additive noise) are not implemented");
+    auto kinds = [&]() {
+        for (int kind : {kind_dyn, kind_obs})
+            if (kind != SSMQ_SWEEP_GP && kind != SSMQ_SWEEP_BS)
+                return sweep_refuse(SSMQ_E_UNSUPPORTED, "filter_sweep: the t-process and multi-output models are not implemented");
+        return (int)SSMQ_OK;
+    };
+    int selo = 0;
+    if (int rc = additive_pair_route(sweep_refuse, "filter_sweep", f_dyn, f_obs, D, kinds, &selo)) return rc;
     if (D > 6 || Y > 4) return sweep_refuse(SSMQ_E_UNSUPPORTED, "filter_sweep: dimension out of range");
     if (N_dyn > 2 * D + 1 || N_obs > 2 * D + 1 || N_dyn < 2 || N_obs < 2)
         return sweep_refuse(SSMQ_E_UNSUPPORTED, "filter_sweep: point count out of range");
-    *selo = sel_pattern(f_obs, fio.din);
-    const char *kn = *selo < 0 ? nullptr : find_sweep_kernel(f_dyn->id, f_obs->id, D, Y, N_dyn, N_obs, *selo);
+    *shape = {f_dyn->id, f_obs->id, D, Y, N_dyn, N_obs, SSMQ_FORM_BQ, 0, selo, 0};
+    const char *kn = selo < 0 ? nullptr : find_sweep_kernel(*shape);
     if (!kn) return sweep_refuse(SSMQ_E_UNSUPPORTED, "filter_sweep: no kernel for this pair of models and point sets");
     if (name) *name = kn;
     return SSMQ_OK;
@@ -81,9 +79,9 @@ using namespace ssmq;
 extern "C" int ssmq_filter_sweep_kernel_name(const ssmq_integrand *f_dyn, const ssmq_integrand *f_obs, int kind_dyn, int kind_obs, int N_dyn,
                                              int N_obs, int D, int Y, char *buf, int len) {
     if (!buf || len <= 0) return sweep_refuse(SSMQ_E_ARG, "filter_sweep: bad argument");
-    int selo = 0;
+    FilterShape shape;
     const char *name = nullptr;
-    if (int rc = sweep_route(f_dyn, f_obs, kind_dyn, kind_obs, N_dyn, N_obs, D, Y, &selo, &name)) return rc;
+    if (int rc = sweep_route(f_dyn, f_obs, kind_dyn, kind_obs, N_dyn, N_obs, D, Y, &shape, &name)) return rc;
     snprintf(buf, len, "%s", name);
     return SSMQ_OK;
 }
@@ -94,8 +92,8 @@ extern "C" int ssmq_filter_sweep_dev(const ssmq_integrand *f_dyn, const ssmq_int
                                      int Y, int64_t B, int64_t ld, int T, const double *d_y, const double *x0_mean, const double *x0_cov,
                                      const double *GQG, const double *R, double *d_loglik_total, double *d_nis_mean, double *d_loglik_steps,
                                      int32_t *d_status, int32_t *theta_status) {
-    int selo = 0;
-    if (int rc = sweep_route(f_dyn, f_obs, kind_dyn, kind_obs, N_dyn, N_obs, D, Y, &selo, nullptr)) return rc;
+    FilterShape shape;
+    if (int rc = sweep_route(f_dyn, f_obs, kind_dyn, kind_obs, N_dyn, N_obs, D, Y, &shape, nullptr)) return rc;
     if (!xi_dyn || !xi_obs || !par_dyn || !par_obs || P < 1 || B < 0 || ld < B || ld % kSmallBlock != 0 || T < 0 || !d_y || !x0_mean || !x0_cov ||
         !d_loglik_total || !d_nis_mean || !d_status || !theta_status || (kind_dyn == SSMQ_SWEEP_BS && (!mulind_dyn || NB_dyn < 1 || NB_dyn > N_dyn)) ||
         (kind_obs == SSMQ_SWEEP_BS && (!mulind_obs || NB_obs < 1 || NB_obs > N_obs)))
@@ -111,20 +109,7 @@ extern "C" int ssmq_filter_sweep_dev(const ssmq_integrand *f_dyn, const ssmq_int
         return rc;
     for (int p = 0; p < P; ++p) theta_status[p] = st[0][p] + 4 * st[1][p];
     if (B == 0) return SSMQ_OK;
-    hipStream_t s = stream();
-    const size_t items = (size_t)P * ld;
-    if (T == 0) {   // nothing to score (as ssmq_filter_innovations_dev): empty sums; a failed row is still a failed row
-        SSMQ_HIP(hipMemsetAsync(d_loglik_total, 0, sizeof(double) * items, s));
-        SSMQ_HIP(hipMemsetAsync(d_nis_mean, 0, sizeof(double) * items, s));
-        SSMQ_HIP(hipMemsetAsync(d_status, 0, sizeof(int32_t) * items, s));
-        for (int p = 0; p < P; ++p)
-            if (theta_status[p]) {
-                SSMQ_HIP(hipMemsetAsync(d_loglik_total + (size_t)p * ld, 0xff, sizeof(double) * ld, s));    // (all bits set: a NaN; -1)
-                SSMQ_HIP(hipMemsetAsync(d_nis_mean + (size_t)p * ld, 0xff, sizeof(double) * ld, s));
-                SSMQ_HIP(hipMemsetAsync(d_status + (size_t)p * ld, 0xff, sizeof(int32_t) * ld, s));
-            }
-        return hip_fail(hipStreamSynchronize(s), "filter_sweep");
-    }
+    if (T == 0) return score_empty("filter_sweep", P, ld, theta_status, d_loglik_total, d_nis_mean, d_status);
     // ---- one host image: c_dyn [P][block] | c_obs [P][block] | pass constants | m0 | P0 | theta_status ----------------------
     const size_t nd = const_layout(D, D, N_dyn, SSMQ_FORM_BQ).total, no = const_layout(D, Y, N_obs, SSMQ_FORM_BQ).total;
     const size_t npc = pass_consts_doubles(D, Y, T), nx0 = ((size_t)D + (size_t)D * D + 7) / 8 * 8;
@@ -141,8 +126,10 @@ extern "C" int ssmq_filter_sweep_dev(const ssmq_integrand *f_dyn, const ssmq_int
     std::copy(x0_mean, x0_mean + D, hx0);
     std::copy(x0_cov, x0_cov + (size_t)D * D, hx0 + D);
     memcpy(host.data() + n_dbl, theta_status, sizeof(int32_t) * P);
-    double *dev = nullptr;
-    SSMQ_HIP(hipMalloc((void **)&dev, sizeof(double) * host.size()));
+    DeviceImage img;
+    if ((rc = img.alloc(host.size()))) return rc;
+    double *const dev = img.dev;
+    hipStream_t s = stream();
     SweepArgs a;
     memset(&a, 0, sizeof(a));
     a.y = d_y; a.c_dyn = dev; a.c_obs = dev + P * nd; a.gqg = dev + P * nd + P * no; a.rr = a.gqg + pc.rr; a.x0 = a.gqg + npc;
@@ -154,9 +141,8 @@ extern "C" int ssmq_filter_sweep_dev(const ssmq_integrand *f_dyn, const ssmq_int
     fill_fpar(f_obs, &a.fo);
     a.fd.ttab = pc.has_ttab_dyn ? a.gqg + pc.ttab_dyn : nullptr;
     a.fo.ttab = pc.has_ttab_obs ? a.gqg + pc.ttab_obs : nullptr;
-    rc = hip_fail(hipMemcpyAsync(dev, host.data(), sizeof(double) * host.size(), hipMemcpyHostToDevice, s), "filter_sweep: upload");
-    if (!rc) rc = launch_sweep(f_dyn->id, f_obs->id, D, Y, N_dyn, N_obs, selo, a, s);
+    rc = img.upload(host, "filter_sweep: upload");
+    if (!rc) rc = launch_sweep(shape, a, s);
     const int rs = hip_fail(hipStreamSynchronize(s), "filter_sweep");
-    hipFree(dev);
     return rc ? rc : rs;
 }

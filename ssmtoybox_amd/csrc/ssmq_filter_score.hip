@@ -17,12 +17,12 @@ static hipError_t launch_score_one(const ScoreArgs &a, hipStream_t s) {
 
 typedef hipError_t (*score_fn)(const ScoreArgs &, hipStream_t);
 struct ScoreEntry {
-    int fd, fo, D, Y, N, selo, form, tp, stu;
+    ScoreShape shape;
     score_fn fn;
     const char *name;
 };
-#define SSMQ_SCORE_ONE(FD, FO, D, Y, N, SELO, FORM, TP, STU)                                        \
-    {FD, FO, D, Y, N, SELO, FORM, TP, STU, &launch_score_one<D, Y, N, FD, FO, FORM, TP, SELO, STU>, \
+#define SSMQ_SCORE_ONE(FD, FO, D, Y, N, SELO, FORM, TP, STU)                                               \
+    {{{FD, FO, D, Y, N, N, FORM, TP, SELO, 0}, STU}, &launch_score_one<D, Y, N, FD, FO, FORM, TP, SELO, STU>, \
      "k_filter_score<D=" #D ",Y=" #Y ",ND=" #N ",NO=" #N "," #FD "," #FO "," #FORM ",TP=" #TP ",SELO=" #SELO ",STU=" #STU ">"}
 // a shape of ssmq_filter_shapes.h -> its three entries
 #define SSMQ_SCORE_SHAPE(ONE, FD, FO, D, Y, N, SELO)              \
@@ -34,23 +34,17 @@ static const ScoreEntry kScore[] = {
     SSMQ_SHAPES_UNGM(SSMQ_SCORE_SHAPE, _),
     SSMQ_SHAPES_MID(SSMQ_SCORE_SHAPE, _),
 };
+static_assert(sizeof(kScore) / sizeof(kScore[0]) == 27, "k_filter_score: three instantiations of nine shapes");
 
-static const ScoreEntry *find_score(int fd, int fo, int D, int Y, int ND, int NO, int selo, int form, int tp, int stu) {
-    for (const ScoreEntry &e : kScore)
-        if (e.fd == fd && e.fo == fo && e.D == D && e.Y == Y && e.N == ND && e.N == NO && e.selo == selo && e.form == form && e.tp == tp &&
-            e.stu == stu)
-            return &e;
-    return nullptr;
-}
-
-const char *find_score_kernel(int fd, int fo, int D, int Y, int ND, int NO, int selo, int form, int tp, int stu) {
-    const ScoreEntry *e = find_score(fd, fo, D, Y, ND, NO, selo, form, tp, stu);
+// shape.opt is 0: the dense kernel of the form
+const char *find_score_kernel(const ScoreShape &shape) {
+    const ScoreEntry *e = find_entry(kScore, shape);
     return e ? e->name : nullptr;
 }
 
 // SSMQ_OK launched, SSMQ_E_UNSUPPORTED no instantiation for this shape (the caller has asked find_score_kernel first), or a HIP error
-int launch_score(int fd, int fo, int D, int Y, int ND, int NO, int selo, int form, int tp, int stu, const ScoreArgs &a, hipStream_t s) {
-    const ScoreEntry *e = find_score(fd, fo, D, Y, ND, NO, selo, form, tp, stu);
+int launch_score(const ScoreShape &shape, const ScoreArgs &a, hipStream_t s) {
+    const ScoreEntry *e = find_entry(kScore, shape);
     return e ? hip_fail(e->fn(a, s), e->name) : SSMQ_E_UNSUPPORTED;
 }
 

@@ -1,6 +1,6 @@
 // The model shapes the time-loop kernels are instantiated for, once, and the rules by which a pass picks among the instantiations
-// of a shape.  Host only: included by the three table files (ssmq_filter_fused.hip, ssmq_filter_chunked.hip, ssmq_filter_piped.hip)
-// and by the run-time compiler's host code, never embedded in the text it compiles.
+// of a shape.  Host only: included by the table files (ssmq_filter_fused.hip, ssmq_filter_chunked.hip, ssmq_filter_piped.hip, those of
+// the scoring kernels, ...) and by the run-time compiler's host code, never embedded in the text it compiles.
 #pragma once
 #include <array>
 #include <utility>
@@ -55,6 +55,15 @@ inline std::array<int, 3> opt_preference(const ssmq_transform *hd, const ssmq_tr
     const int both = hd->opt_mask & ho->opt_mask;
     const bool plain = !(hd->tp_nu > 0.0 || hd->form == SSMQ_FORM_SIGMA);
     return {(plain && (both & 7) == 7) ? 7 : -1, both & (plain ? 3 : SSMQ_OPT_UT), 0};
+}
+
+// The entry of a dispatch table for a key: entries carry the key as `shape` (a FilterShape, or a type that extends it), null = no
+// instantiation.
+template <class Entry, size_t N, class Key>
+const Entry *find_entry(const Entry (&table)[N], const Key &shape) {
+    for (const Entry &e : table)
+        if (e.shape == shape) return &e;
+    return nullptr;
 }
 
 // has_time_table() is what the host goes by, HasTimeTable<> what the kernels are compiled with: the same set of integrands

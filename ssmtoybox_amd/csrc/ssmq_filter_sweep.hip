@@ -14,13 +14,13 @@ static hipError_t launch_sweep_one(const SweepArgs &a, hipStream_t s) {
 
 typedef hipError_t (*sweep_fn)(const SweepArgs &, hipStream_t);
 struct SweepEntry {
-    int fd, fo, D, Y, N, selo;
+    FilterShape shape;
     sweep_fn fn;
     const char *name;
 };
-// a shape of ssmq_filter_shapes.h -> its one dense BQ entry
-#define SSMQ_SWEEP_SHAPE(ONE, FD, FO, D, Y, N, SELO)                        \
-    {FD, FO, D, Y, N, SELO, &launch_sweep_one<D, Y, N, FD, FO, SELO>,       \
+// a shape of ssmq_filter_shapes.h -> its one entry: the dense kernel of the BQ form
+#define SSMQ_SWEEP_SHAPE(ONE, FD, FO, D, Y, N, SELO)                                           \
+    {{FD, FO, D, Y, N, N, SSMQ_FORM_BQ, 0, SELO, 0}, &launch_sweep_one<D, Y, N, FD, FO, SELO>, \
      "k_filter_sweep<D=" #D ",Y=" #Y ",ND=" #N ",NO=" #N "," #FD "," #FO ",SELO=" #SELO ">"}
 
 static const SweepEntry kSweep[] = {
@@ -29,18 +29,18 @@ static const SweepEntry kSweep[] = {
     SSMQ_SHAPES_HEAVY_UT(SSMQ_SWEEP_SHAPE, _),
     SSMQ_SHAPES_HEAVY_SR(SSMQ_SWEEP_SHAPE, _),
 };
+static_assert(sizeof(kSweep) / sizeof(kSweep[0]) == 15, "k_filter_sweep: the BQ form of fifteen shapes");
 
-const char *find_sweep_kernel(int fd, int fo, int D, int Y, int ND, int NO, int selo) {
-    for (const SweepEntry &e : kSweep)
-        if (e.fd == fd && e.fo == fo && e.D == D && e.Y == Y && e.N == ND && e.N == NO && e.selo == selo) return e.name;
-    return nullptr;
+// shape: BQ form, tp 0, opt 0
+const char *find_sweep_kernel(const FilterShape &shape) {
+    const SweepEntry *e = find_entry(kSweep, shape);
+    return e ? e->name : nullptr;
 }
 
 // SSMQ_OK launched, SSMQ_E_UNSUPPORTED no instantiation for this shape (the caller has asked find_sweep_kernel first), or a HIP error
-int launch_sweep(int fd, int fo, int D, int Y, int ND, int NO, int selo, const SweepArgs &a, hipStream_t s) {
-    for (const SweepEntry &e : kSweep)
-        if (e.fd == fd && e.fo == fo && e.D == D && e.Y == Y && e.N == ND && e.N == NO && e.selo == selo) return hip_fail(e.fn(a, s), e.name);
-    return SSMQ_E_UNSUPPORTED;
+int launch_sweep(const FilterShape &shape, const SweepArgs &a, hipStream_t s) {
+    const SweepEntry *e = find_entry(kSweep, shape);
+    return e ? hip_fail(e->fn(a, s), e->name) : SSMQ_E_UNSUPPORTED;
 }
 
 }  // namespace ssmq

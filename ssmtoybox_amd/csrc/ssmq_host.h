@@ -504,6 +504,11 @@ struct FilterShape {
                selo == o.selo && opt == o.opt;
     }
 };
+// ... of k_filter_score<> (ssmq_filter_score.hip): the shape and the recursion (stu 1: Studentian)
+struct ScoreShape : FilterShape {
+    int stu;
+    bool operator==(const ScoreShape &o) const { return FilterShape::operator==(o) && stu == o.stu; }
+};
 // ... and the key of a pass (same_family) with fast path `opt`
 inline FilterShape shape_of(const FilterPass &p, int opt) {
     return {p.fd->id, p.fo->id, p.hd->D, p.ho->E, p.hd->N, p.ho->N, p.hd->form, p.hd->tp_nu > 0.0 ? 1 : 0, p.sel_obs, opt};
@@ -543,7 +548,7 @@ struct InnovOut {
     double *ymean, *S;                        // [T][Y][ld], [T][Y*Y][ld] or null
     double *nis, *ll;                         // [T][ld]
 };
-struct InnovArgs;                             // ssmq_innovation_kernel.h
+struct InnovArgs;                             // ssmq_innovation_kernel.h (k_innovation<>: ssmq_score_step.h)
 InnovArgs innov_args(const FilterPass &p, const InnovOut &o);
 // all T B items in one launch of k_innovation<>: 1 launched (dry_run: a kernel exists, its name set), 0 no kernel for this pair,
 // < 0 error; a pair with a user integrand runs the instantiation compiled for it at run time (ssmq_rtc.hip) or is an error
@@ -557,6 +562,46 @@ int launch_innovation_score(int D, int Y, int64_t B, int64_t ld, const double *y
 // total [2][ld]: sum of ll, mean of nis over the steps in ascending order; status [B]: 1 + first step with NaN scores, or 0
 int launch_innovation_total(int64_t B, int64_t ld, int T, const double *nis, const double *ll, double *total, int32_t *status,
                             hipStream_t s);
+
+// The likelihood-scoring entry points (ssmq_api_sweep.hip, ssmq_api_score.hip, ssmq_api_noise_sweep.hip, ssmq_api_imm.hip).
+// The model checks their routes share, in the order every one of them makes them: no user-defined integrand; own() - the entry
+// point's checks that come next (nonzero: its refusal, already reported); known integrand ids; additive noise, D -> D dynamics
+// without an index list.  refuse(code, text) is the entry point's refusal, w the name it reports under.  *selo: sel_pattern() of the
+// measurement integrand (< 0: no kernel reads that pattern).
+template <class Refuse, class Own>
+int additive_pair_route(Refuse refuse, const std::string &w, const ssmq_integrand *f_dyn, const ssmq_integrand *f_obs, int D, Own own, int *selo) {
+    if (is_user_integrand(f_dyn) || is_user_integrand(f_obs))
+        return refuse(SSMQ_E_UNSUPPORTED, w + ": user-defined models (device_code) are not implemented");
+    if (int rc = own()) return rc;
+    FInfo fid, fio;
+    if (!integrand_info(f_dyn->id, &fid) || !integrand_info(f_obs->id, &fio)) return refuse(SSMQ_E_ARG, w + ": unknown integrand id");
+    if (f_dyn->id == SSMQ_F_UNGMNA_DYN || f_dyn->id == SSMQ_F_CTRS_DYN || f_obs->id == SSMQ_F_UNGMNA_MEAS || fid.din != D || fid.dout != D ||
+        f_dyn->n_idx > 0)
+        return refuse(SSMQ_E_UNSUPPORTED, w + ": models that take their noise as an argument (non-additive noise) are not implemented");
+    *selo = sel_pattern(f_obs, fio.din);
+    return SSMQ_OK;
+}
+// T == 0, the row entry points: nothing to score - empty sums, status 0; a failed row is still a failed row (theta_status: host [P]
+// or null; NaN, -1).  Synchronous.  (ssmq_api_score.hip)
+int score_empty(const char *who, int P, int64_t ld, const int32_t *theta_status, double *d_ll_total, double *d_nis_mean, int32_t *d_status);
+// A host image on the device for the length of one call: uploaded asynchronously on stream(), so the launch that follows on that
+// stream reads the copy; freed when the scope ends, on every path - the caller synchronises the stream before that.
+struct DeviceImage {
+    double *dev = nullptr;
+    DeviceImage() = default;
+    DeviceImage(const DeviceImage &) = delete;
+    DeviceImage &operator=(const DeviceImage &) = delete;
+    ~DeviceImage() {
+        if (dev) hipFree(dev);
+    }
+    int alloc(size_t doubles) {
+        SSMQ_HIP(hipMalloc((void **)&dev, sizeof(double) * doubles));
+        return SSMQ_OK;
+    }
+    int upload(const std::vector<double> &host, const char *what) {
+        return hip_fail(hipMemcpyAsync(dev, host.data(), sizeof(double) * host.size(), hipMemcpyHostToDevice, stream()), what);
+    }
+};
 
 // Iterated posterior linearisation pass (ssmq_filter_iterated.hip, ssmq_filter_iterated_dev): `iterations` measurement updates per step,
 // each re-linearised around the current posterior; delta [T][ld] or null.  The whole pass in one launch of k_iplf_loop<>: 1 launched

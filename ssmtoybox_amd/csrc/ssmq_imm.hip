@@ -41,18 +41,16 @@ static_assert(imm_lds_bytes(6, kImmMaxModes) <= 160 * 1024 - 64, "k_imm_loop: th
 
 // shape.opt is 0: the dense kernel of the form
 const char *find_imm_kernel(const FilterShape &shape) {
-    for (const ImmEntry &e : kImm)
-        if (e.shape == shape) return e.name;
-    return nullptr;
+    const ImmEntry *e = find_entry(kImm, shape);
+    return e ? e->name : nullptr;
 }
 
 // SSMQ_OK launched, SSMQ_E_UNSUPPORTED no instantiation for this shape (the caller has asked find_imm_kernel first), or a HIP error.
 // a.M is 1 .. kImmMaxModes, a.B >= 1 and a.ld a multiple of 64: the caller has checked.
 int launch_imm(const FilterShape &shape, const ImmArgs &a, hipStream_t s) {
     if (a.M < 1 || a.M > kImmMaxModes || a.B < 1 || a.ld % kSmallBlock != 0 || a.ld < a.B) return SSMQ_E_ARG;
-    for (const ImmEntry &e : kImm)
-        if (e.shape == shape) return e.fn(a, s);
-    return SSMQ_E_UNSUPPORTED;
+    const ImmEntry *e = find_entry(kImm, shape);
+    return e ? e->fn(a, s) : SSMQ_E_UNSUPPORTED;
 }
 
 }  // namespace ssmq

@@ -4,8 +4,8 @@
 // per-step measurement likelihood.  Per trajectory and step k, every sum over modes ascending in the mode index:
 //     c_j = sum_i Pi[i][j] mu_i;   w_ij = Pi[i][j] mu_i / c_j   (c_j == 0: w_ij = delta_ij - a mode nobody can reach keeps its moments)
 //     m0_j = sum_i w_ij m_i;       P0_j = sum_i w_ij (P_i + (m_i - m0_j)(m_i - m0_j)')
-//     mode j's filter step from (m0_j, P0_j): the step of k_noise_sweep<> - both transforms, innovation_score<> -> ll_j, gain_from_cov<>,
-//                                             sandwich<> - nothing of it restated
+//     mode j's filter step from (m0_j, P0_j): predict_and_score<> -> ll_j, then kalman_update_lower<> (ssmq_score_step.h: the step of
+//                                             the row kernels, the one k_noise_sweep<> runs)
 //     a_j = log c_j + ll_j (-inf: c_j == 0);  amax = max_j a_j;  loglik[k] = amax + log sum_j exp(a_j - amax);  mu_j = exp(a_j - loglik[k])
 //     fm[k] = sum_j mu_j m_j;      fP[k] = sum_j mu_j (P_j + (m_j - fm)(m_j - fm)')   (both triangles from the one value)
 //
@@ -32,7 +32,7 @@
 //     (no index and no branch around a barrier depends on it).
 // Nothing a trajectory computes depends on the lanes around it.
 #pragma once
-#include "ssmq_innovation_kernel.h"
+#include "ssmq_score_step.h"
 
 namespace ssmq {
 
@@ -126,12 +126,7 @@ __global__ __launch_bounds__(kSmallBlock * kImmMaxModes) void k_imm_loop(const I
     const cdouble_p pi = (cdouble_p)a.pi, mu0 = (cdouble_p)a.mu0;
     double *const own = lds + (size_t)j * NW * kSmallBlock + lane;           // slot j, this lane's column
     double m[D], Pl[PK];
-#pragma unroll
-    for (int d = 0; d < D; ++d) m[d] = x0[d];
-#pragma unroll
-    for (int r = 0; r < D; ++r)
-#pragma unroll
-        for (int q = 0; q <= r; ++q) Pl[SSMQ_PK(r, q)] = x0[D + r * D + q];
+    load_x0<D>(x0, m, Pl);
     // ---- the initial moments meet: mixing of step 0 with mu = mu0 ------------------------------------------------------------------
 #pragma unroll
     for (int d = 0; d < D; ++d) own[d * kSmallBlock] = m[d];
@@ -148,42 +143,15 @@ __global__ __launch_bounds__(kSmallBlock * kImmMaxModes) void k_imm_loop(const I
 #pragma unroll 1
     for (int k = 0; k < a.T; ++k) {
         double yk[Y];
-#pragma unroll
-        for (int i = 0; i < Y; ++i) yk[i] = a.y[((int64_t)k * Y + i) * ld + b];
+        step_inputs<Y, FD, FO>(a.y, k, ld, b, yk, fd, fo);
         const double t = (double)k;   // both transforms of step k + 1 use time index k (ssinf.py:104, 276-288)
-        if constexpr (HasTimeTable<FD>::value) { fd.tval = ((cdouble_p)a.fd.ttab)[k]; fd.use_tval = 1; }   // host: non-null
-        if constexpr (HasTimeTable<FO>::value) { fo.tval = ((cdouble_p)a.fo.ttab)[k]; fo.use_tval = 1; }
-        bool ok = mix_ok;
-        // ---- mode j's step from the mixed moments, as k_noise_sweep<> runs it -------------------------------------------------------
+        // ---- mode j's step from the mixed moments: the two halves of ssmq_score_step.h (no break, no return, no barrier in them) ------
         RegSinkNoCross<D, D> pr;
-        ok = moment_transform_core<D, D, ND, FD, FORM, TP, 0, false, 0, RegSinkNoCross<D, D>>(m, Pl, t, fd, cpd, pr) && ok;
-        double L2[PK];
-#pragma unroll
-        for (int i = 0; i < PK; ++i) L2[i] = pr.cv[i];
         RegSink<D, Y> ob;
-        ok = moment_transform_core<D, Y, NO, FO, FORM, TP, SELO, true, 0, RegSink<D, Y>>(pr.mf, L2, t, fo, cpo, ob) && ok;
-        double e[Y], S[Y * (Y + 1) / 2], nis, ll;
-#pragma unroll
-        for (int i = 0; i < Y; ++i) e[i] = yk[i] - ob.mf[i];
-#pragma unroll
-        for (int i = 0; i < Y * (Y + 1) / 2; ++i) S[i] = ob.cv[i];
-        ok = innovation_score<Y>(Y, e, S, nis, ll) && ok;
+        double S[Y * (Y + 1) / 2], nis, ll;
+        bool ok = predict_and_score<D, Y, ND, NO, FD, FO, FORM, TP, SELO, 0>(m, Pl, t, fd, fo, cpd, cpo, yk, pr, ob, S, nis, ll) && mix_ok;
         ok = ok && imm_finite(nis) && imm_finite(ll);
-#pragma unroll
-        for (int i = 0; i < Y * (Y + 1) / 2; ++i) S[i] = ob.cv[i];
-        double G[D][Y];
-        gain_from_cov<D, Y>(S, [&](int i, int d) { return ob.cx[i][d]; }, G);
-#pragma unroll
-        for (int d = 0; d < D; ++d) {
-            double s = 0.0;
-#pragma unroll
-            for (int i = 0; i < Y; ++i) s += G[d][i] * (yk[i] - ob.mf[i]);
-            m[d] = pr.mf[d] + s;
-        }
-        sandwich<D, Y>(G, [&](int i, int q) { return ob.cv[i >= q ? SSMQ_PK(i, q) : SSMQ_PK(q, i)]; },
-                       [&](int d, int d2, double s) {
-                           if (d2 <= d) Pl[SSMQ_PK(d, d2)] = pr.cv[SSMQ_PK(d, d2)] - s;   // the lower triangle: what the mixing reads
-                       });
+        kalman_update_lower<D, Y, 0>(pr, ob, yk, 1.0, m, Pl);   // the lower triangle: what the mixing reads
         // ---- the modes meet: updated moments and a_j (NaN: the poison flag) ---------------------------------------------------------
         const double aj = !ok ? nan : (cj != 0.0 ? log(cj) + ll : -__builtin_inf());
 #pragma unroll

@@ -1,9 +1,9 @@
-// Innovation scores of a filter pass (ssmq_filter_innovations_dev): the dispatch table of k_innovation<> (ssmq_innovation_kernel.h) -
+// Innovation scores of a filter pass (ssmq_filter_innovations_dev): the dispatch table of k_innovation<> (ssmq_score_step.h) -
 // every shape the fused time loop is instantiated for, one recursion-free launch over all T B items -, the scoring half on its
 // own for the launch-loop route (k_innovation_score: reads the y_mean / P_y planes one step's transforms left) and the totals of
 // every trajectory (k_innovation_total: ascending k, one lane per trajectory - a trajectory's bits do not depend on the batch).
 #include <cstring>
-#include "ssmq_innovation_kernel.h"
+#include "ssmq_score_step.h"
 #include "ssmq_filter_shapes.h"
 
 namespace ssmq {

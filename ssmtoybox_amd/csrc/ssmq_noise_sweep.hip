@@ -34,16 +34,14 @@ static_assert(sizeof(kNoiseSweep) / sizeof(kNoiseSweep[0]) == 45, "k_noise_sweep
 
 // shape.opt is 0: the dense kernel of the form
 const char *find_noise_sweep_kernel(const FilterShape &shape) {
-    for (const NoiseSweepEntry &e : kNoiseSweep)
-        if (e.shape == shape) return e.name;
-    return nullptr;
+    const NoiseSweepEntry *e = find_entry(kNoiseSweep, shape);
+    return e ? e->name : nullptr;
 }
 
 // SSMQ_OK launched, SSMQ_E_UNSUPPORTED no instantiation for this shape (the caller has asked find_noise_sweep_kernel first), or a HIP error
 int launch_noise_sweep(const FilterShape &shape, const NoiseSweepArgs &a, hipStream_t s) {
-    for (const NoiseSweepEntry &e : kNoiseSweep)
-        if (e.shape == shape) return hip_fail(e.fn(a, s), e.name);
-    return SSMQ_E_UNSUPPORTED;
+    const NoiseSweepEntry *e = find_entry(kNoiseSweep, shape);
+    return e ? hip_fail(e->fn(a, s), e->name) : SSMQ_E_UNSUPPORTED;
 }
 
 }  // namespace ssmq

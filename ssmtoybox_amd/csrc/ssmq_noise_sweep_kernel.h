@@ -1,7 +1,6 @@
-// Noise sweep of a Gaussian filter by measurement likelihood: k_noise_sweep<> is the sibling of k_filter_sweep<>
-// (ssmq_filter_sweep_kernel.h) that keeps the WEIGHTS shared and varies what every filter has - the process-noise term G Q G', the
-// measurement-noise covariance R and the initial moments - per row.  It runs the additive-noise Gaussian recursion of P rows on B
-// measurement sequences in ONE launch and keeps of every item (p, b) only
+// Noise sweep of a Gaussian filter by measurement likelihood: k_noise_sweep<> keeps the WEIGHTS shared and varies what every filter
+// has - the process-noise term G Q G', the measurement-noise covariance R and the initial moments - per row.  It runs the
+// additive-noise Gaussian recursion of P rows on B measurement sequences in ONE launch and keeps of every item (p, b) only
 //     loglik_total = sum_k log N(y_k; y^_k, S_k),   nis_mean = sum_k e_k' S_k^-1 e_k / T,   status
 // (and, on request, the per-step log-likelihoods).  No filtered moment is stored.
 //
@@ -15,11 +14,18 @@
 // Arithmetic: a step is what k_filter_sweep<> does, for every form of the fused time loop (FORM / TP: sigma-point, BQ, t-process BQ;
 // tp_nu reaches CoreParams as fused_args() / fused_pass<> pass it) - the two moment_transform_core<> calls with the template
 // arguments of the dense kernel of the form (OPT = 0), innovation_score<> (ssmq_innovation_kernel.h) on the predictive measurement
-// moments, then the measurement update as gain_from_cov<> and sandwich<> (ssmq_device.h) define it.  Nothing of it is restated here.
+// moments, then the measurement update as gain_from_cov<> and sandwich<> (ssmq_device.h) define it.
 //
 // Failures: per lane, the rule of k_filter_sweep<>.  The first step j whose scores are not finite numbers (a factorisation failed -
 // an indefinite Q, R or P0 row shows up here -, an input is not finite) sets status = 1 + j, the lane leaves the loop and its
 // totals (and the remaining steps) are NaN.
+//
+// OWN COPY OF THE STEP, on purpose: this kernel does what score_rows_lane<> (ssmq_score_step.h) does for k_filter_sweep<> and
+// k_filter_score<>, statement for statement, but keeps the statements here.  Routed through the shared function the outputs were
+// bit-identical, yet six five-state instantiations gained 24 .. 48 bytes of scratch and three of them measured slower than before
+// (reentry t-process N = 10: 0.191 / 0.194 ms against 0.181 / 0.182; coordinated turn GP N = 10 and 11: 1 %; profiles/README.md,
+// r20).  A change to the step in ssmq_score_step.h has to be made here as well; tests/test_noise_sweep_gpu.py and
+// tests/test_imm_gpu.py tie the two bit for bit (row = two-call path, IMM with one mode = row).
 #pragma once
 #include "ssmq_innovation_kernel.h"
 

@@ -473,7 +473,7 @@ int rtc_launch_fused(const FilterPass &p) {
     return rc ? rc : 1;
 }
 
-// k_innovation<> (ssmq_innovation_kernel.h) for a pair with a user member: the shapes, the fast-path choice and the time tables
+// k_innovation<> (ssmq_score_step.h) for a pair with a user member: the shapes, the fast-path choice and the time tables
 // of rtc_launch_fused, the grid and the argument block of the AOT launcher (ssmq_innovation.hip)
 int rtc_launch_innovation(const FilterPass &p, const InnovOut &o) {
     std::vector<int> ids;
