@@ -49,6 +49,50 @@ __device__ __forceinline__ int32_t first_nan_step(const char *fP, uint32_t o, co
     return first;
 }
 
+// The transform constants a step reads, REQUESTED ONCE at the top of the kernel and held in scalar registers for the whole pass:
+// the dynamics' wm, Wc, emv and G Q G' (its points are dealt - QuadScalarPoints - and it forms no cross-covariance), the
+// measurement's xi, wm, Wcc, Wc, emv and R.  moment_transform_core<> reads them as c[cl...] off the same uniform pointers; a
+// constant-address-space load of an address already loaded HERE, above every branch of the kernel, is this value, so the loop
+// and both peeled steps run on these registers and request nothing but their time-table entry.  Left to itself the compiler
+// hoisted the loads into the loop's pre-header only - behind the waits for the initial state, a scalar-cache round trip of its
+// own in front of the first step - and, the pre-header not being on the path of a pass of one or two steps, loaded everything
+// again in each peeled step, with its waits inside the step's dependent chain.  hold() is where the values have to BE in
+// registers: once behind the requests, once behind the loop (which keeps them live across it).
+// N = 5 (37 + 46 constants) does not fit the scalar file and moves constants through lanes as it is: kHeld is false there and the
+// kernel is what it was.
+template <int N>
+struct UngmQuadConsts {
+    static constexpr bool kHeld = N <= 3;
+    SBuf<N> wm_d, xi_o, wm_o, wcc_o;
+    SBuf<N * N> wc_d, wc_o;
+    SBuf<1> emv_d, add_d, emv_o, add_o;
+    __device__ __forceinline__ void request(const CoreParams &cpd, const CoreParams &cpo) {
+        constexpr ConstLayout cl = const_layout(1, 1, N, SSMQ_FORM_BQ);
+        sload(wm_d, cpd.c + cl.wm);
+        sload(wc_d, cpd.c + cl.Wc);
+        sload(emv_d, cpd.c + cl.emv);
+        sload(add_d, cpd.cadd);
+        sload(xi_o, cpo.c + cl.xi);
+        sload(wm_o, cpo.c + cl.wm);
+        sload(wcc_o, cpo.c + cl.Wcc);
+        sload(wc_o, cpo.c + cl.Wc);
+        sload(emv_o, cpo.c + cl.emv);
+        sload(add_o, cpo.cadd);
+    }
+    __device__ __forceinline__ void hold() const {
+        spin(wm_d);
+        spin(wc_d);
+        spin(emv_d);
+        spin(add_d);
+        spin(xi_o);
+        spin(wm_o);
+        spin(wcc_o);
+        spin(wc_o);
+        spin(emv_o);
+        spin(add_o);
+    }
+};
+
 // The pass of one quad's trajectory.  step<AHEAD>() is the step of fused_pass<1, 1, N, N, UNGM_DYN, UNGM_MEAS, FORM_BQ, TP = 0,
 // SELO = 0, OPT = 0, STU = 0> - the same calls and the same update lines on the same operands in the same order - around the
 // addressing described above.
@@ -123,6 +167,12 @@ template <int N>
 __global__ __launch_bounds__(kSmallBlock, 2) void k_filter_ungm_quad(const FusedArgs a) {
     const uint32_t b = blockIdx.x * kQuadTraj + (threadIdx.x >> 2);
     const int T = a.T;
+    // every argument field the kernel reads, requested in ONE batch in front of the early-out (whose operands arrive with the
+    // rest): one round trip to the argument segment where there were three dependent ones - B and T; the pointers behind the
+    // branch; ld, the time table and the outputs behind the first loads
+    if constexpr (UngmQuadConsts<N>::kHeld)
+        asm volatile("" ::"s"(a.y), "s"(a.m0), "s"(a.P0), "s"(a.fm), "s"(a.fP), "s"(a.status), "s"(a.c_dyn), "s"(a.c_obs), "s"(a.gqg),
+                     "s"(a.rr), "s"((uint32_t)a.B), "s"((uint32_t)a.ld), "s"(T), "s"(a.fd.ttab));
     // (host, try_launch_ungm_quad: T >= 1 and 8 ld T < 2^31, so B <= ld fits 32 bits with room to spare)
     if (b >= (uint32_t)a.B || T < 1) return;
     UngmQuadPass<N> u;
@@ -142,7 +192,15 @@ __global__ __launch_bounds__(kSmallBlock, 2) void k_filter_ungm_quad(const Fused
     u.Pl[0] = *(const double *)((const char *)a.P0 + u.vo);
     double ya = *(const double *)((const char *)a.y + u.vo), yb;
     u.tdn = *(cdouble_p)u.tt;
+    // ... and, in the same flight as the initial state, the first time-table entry and the lane's points, every constant of a step
+    // (requested in FRONT of qpts.init, whose pin is a wait: behind it they would be a round trip of their own)
+    UngmQuadConsts<N> cst;
+    if constexpr (cst.kHeld) cst.request(u.cpd, u.cpo);
     u.qpts.init(u.cpd.c + const_layout(1, 1, N, SSMQ_FORM_BQ).xi, (int)(threadIdx.x & 3));
+    if constexpr (cst.kHeld) {
+        cst.hold();
+        asm volatile("" ::"s"(u.tdn));
+    }
     // everything requested so far has ARRIVED before the loop is entered (fused_pass: a load pending at the loop header leaves a
     // vmcnt(n > 0) in the body that waits for the previous step's stores)
     pin_v(u.m[0]);
@@ -157,6 +215,7 @@ __global__ __launch_bounds__(kSmallBlock, 2) void k_filter_ungm_quad(const Fused
         u.template step<true>(k, ya, yb);
         u.template step<true>(k + 1, yb, ya);
     }
+    if constexpr (cst.kHeld) cst.hold();
     if (!(T & 1)) {
         u.template step<true>(k++, ya, yb);
         ya = yb;
