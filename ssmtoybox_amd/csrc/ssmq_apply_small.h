@@ -106,9 +106,17 @@ struct CoreParams {
 // Who evaluates the integrand at the N points of a transform.  The default: this lane, all of them, inside moment_transform_core<>.
 // A type with kDealt = true brings the values itself - values(fn, m, L, fx) fills fx[e][n] = f_e(m + L xi_n) - and every sum
 // after them is the same code on the same values (QuadScalarPoints, ssmq_quad.h: the points dealt to the lanes of a quad).
-struct PointsPerLane {
+// kCentre (PointsPerLaneCentre): the caller KNOWS that the first unit point is +0.0 in every coordinate (the host read the handle's
+// xi block), and point 0 is evaluated at m itself instead of at fma(+0.0, L, m): one instruction per coordinate less on the
+// dependent chain.  The two differ only where L is not finite (there every other point is NaN, and so are all three results) and
+// in the sign of a zero mean (-0.0 stays -0.0), which is why only k_filter_ungm_quad sets it (ssmq_filter_ungm_quad.hip).
+template <bool CENTRE>
+struct PointsPerLaneT {
     static constexpr bool kDealt = false;
+    static constexpr bool kCentre = CENTRE;
 };
+typedef PointsPerLaneT<false> PointsPerLane;
+typedef PointsPerLaneT<true> PointsPerLaneCentre;
 
 // m: mean; L: in = packed lower triangle of cov, out = its Cholesky factor.  Returns false if cov is not PD (results
 // are then garbage; the caller writes NaN).  Sink interface: mean(e, v), cov(e, e2, v) for e2 <= e, ccov(e, d, v).
@@ -274,6 +282,9 @@ __device__ __forceinline__ bool moment_transform_core(const double (&m)[D], doub
             const double sc = (n == 0) ? 0.0 : ((n - 1) < D ? utc : -utc);
 #pragma unroll
             for (int d = 0; d < D; ++d) x[d] = (n != 0 && d >= k) ? m[d] + L[SSMQ_PK(d >= k ? d : k, k)] * sc : m[d];
+        } else if (Points::kCentre && n == 0) {
+#pragma unroll
+            for (int d = 0; d < D; ++d) x[d] = m[d];
         } else {
 #pragma unroll
             for (int d = 0; d < D; ++d) {

@@ -95,8 +95,9 @@ struct UngmQuadConsts {
 
 // The pass of one quad's trajectory.  step<AHEAD>() is the step of fused_pass<1, 1, N, N, UNGM_DYN, UNGM_MEAS, FORM_BQ, TP = 0,
 // SELO = 0, OPT = 0, STU = 0> - the same calls and the same update lines on the same operands in the same order - around the
-// addressing described above.
-template <int N>
+// addressing described above.  CENTRE: the measurement transform's first unit point is +0.0 (the host looked) and its point 0 is
+// evaluated at the predictive mean itself (PointsPerLaneCentre, ssmq_apply_small.h) - the dynamics' points are dealt and gain nothing.
+template <int N, bool CENTRE>
 struct UngmQuadPass {
     CoreParams cpd, cpo;
     FPar fd, fo;
@@ -131,7 +132,9 @@ struct UngmQuadPass {
         bool ok = moment_transform_core<1, 1, N, SSMQ_F_UNGM_DYN, SSMQ_FORM_BQ, 0, 0, false, 0>(m, Pl, t, fd, cpd, pr, qpts);
         if constexpr (AHEAD) {
             // the next entry of the time table is requested BEHIND the integrand that consumed this step's: scalar loads return
-            // out of order, so the wait in front of that use is for all of them, a request just made included
+            // out of order, so the wait in front of that use is for all of them, a request just made included.  (One 128-bit
+            // request per loop trip for both of its entries - half a load, a wait and an add less per step - was built and
+            // measured 1.2 % SLOWER: profiles/r22_ungm_quad_centre.txt.)
             __builtin_amdgcn_sched_barrier(0);
             tdn = *(cdouble_p)(tt + to);
             to += 8;
@@ -139,7 +142,8 @@ struct UngmQuadPass {
         // ---- predictive measurement moments, + R ------------------------------------------------------------------------------
         double L2[1] = {pr.cv[0]};
         RegSink<1, 1> ob;
-        ok = moment_transform_core<1, 1, N, SSMQ_F_UNGM_MEAS, SSMQ_FORM_BQ, 0, 0, true, 0, RegSink<1, 1>>(pr.mf, L2, t, fo, cpo, ob) && ok;
+        ok = moment_transform_core<1, 1, N, SSMQ_F_UNGM_MEAS, SSMQ_FORM_BQ, 0, 0, true, 0, RegSink<1, 1>>(pr.mf, L2, t, fo, cpo, ob,
+                                                                                                          PointsPerLaneT<CENTRE>()) && ok;
         // ---- measurement update: the scalar lines of fused_pass (see there for the NaN that carries a failure) ----------------
         double S = ob.cv[0];
         int hi = __double2hiint(S);
@@ -163,7 +167,7 @@ struct UngmQuadPass {
     }
 };
 
-template <int N>
+template <int N, bool CENTRE>
 __global__ __launch_bounds__(kSmallBlock, 2) void k_filter_ungm_quad(const FusedArgs a) {
     const uint32_t b = blockIdx.x * kQuadTraj + (threadIdx.x >> 2);
     const int T = a.T;
@@ -175,7 +179,7 @@ __global__ __launch_bounds__(kSmallBlock, 2) void k_filter_ungm_quad(const Fused
                      "s"(a.rr), "s"((uint32_t)a.B), "s"((uint32_t)a.ld), "s"(T), "s"(a.fd.ttab));
     // (host, try_launch_ungm_quad: T >= 1 and 8 ld T < 2^31, so B <= ld fits 32 bits with room to spare)
     if (b >= (uint32_t)a.B || T < 1) return;
-    UngmQuadPass<N> u;
+    UngmQuadPass<N, CENTRE> u;
     u.cpd = CoreParams{(cdouble_p)a.c_dyn, (cdouble_p)a.gqg, a.emv_dyn, a.nu_dyn, 1.0, 1.0};
     u.cpo = CoreParams{(cdouble_p)a.c_obs, (cdouble_p)a.rr, a.emv_obs, a.nu_obs, 1.0, 1.0};
     u.fd = a.fd;
@@ -229,14 +233,25 @@ __global__ __launch_bounds__(kSmallBlock, 2) void k_filter_ungm_quad(const Fused
     *(int32_t *)((char *)a.status + 4u * b) = status;
 }
 
+// k: the kernel for any points; k_centre: the one for a measurement transform whose first unit point is +0.0, or null.  N = 2, the
+// 'sr' points, has no centre.  N = 5 keeps its body: without the centre's fma it is the same 579 instructions a trip - 3.5 VALU per
+// step fewer, but 2 SALU moves of constants and 1.5 s_nop (4 wait states) more.  One name for both: they are the same pass.
 typedef void (*ungm_quad_kernel)(const FusedArgs);
 struct UngmQuadEntry {
     int N;
-    ungm_quad_kernel k;
+    ungm_quad_kernel k, k_centre;
     const char *name;
 };
-#define SSMQ_UQ(N) {N, &k_filter_ungm_quad<N>, "k_filter_ungm_quad<N=" #N ",SSMQ_FORM_BQ,TP=0>"}
-const UngmQuadEntry kUngmQuad[] = {SSMQ_UQ(2), SSMQ_UQ(3), SSMQ_UQ(5)};
+#define SSMQ_UQ_C(N) &k_filter_ungm_quad<N, true>
+#define SSMQ_UQ(N, C) {N, &k_filter_ungm_quad<N, false>, C, "k_filter_ungm_quad<N=" #N ",SSMQ_FORM_BQ,TP=0>"}
+const UngmQuadEntry kUngmQuad[] = {SSMQ_UQ(2, nullptr), SSMQ_UQ(3, SSMQ_UQ_C(3)), SSMQ_UQ(5, nullptr)};
+
+// the bits of +0.0, not a comparison: -0.0 == 0.0 too, and a handle with that point keeps the body that multiplies by it
+bool is_plus_zero(double v) {
+    uint64_t u;
+    memcpy(&u, &v, sizeof u);
+    return u == 0;
+}
 
 }  // namespace
 
@@ -257,7 +272,9 @@ int try_launch_ungm_quad(const FilterPass &p, int64_t waves) {
         if (p.dry_run) return 1;
         FusedArgs a = fused_args(p);
         a.lpw = kQuadTraj;
-        hipLaunchKernelGGL(e.k, dim3((unsigned)waves), dim3(kSmallBlock), 0, p.s, a);
+        // the handle's own points, as uploaded (D = 1: xi[0] is the first): a centre of exactly +0.0 takes the body without its fma
+        const bool centre = e.k_centre && !ho->xi.empty() && is_plus_zero(ho->xi[0]);
+        hipLaunchKernelGGL(centre ? e.k_centre : e.k, dim3((unsigned)waves), dim3(kSmallBlock), 0, p.s, a);
         const int rc = hip_fail(hipGetLastError(), e.name);
         return rc ? rc : 1;
     }

@@ -34,6 +34,7 @@ __device__ __forceinline__ double quad_bcast(int q, double v) {
 template <int N>
 struct QuadScalarPoints {
     static constexpr bool kDealt = true;
+    static constexpr bool kCentre = false;
     static constexpr int S = (N + 3) / 4;
     double xi[S];       // this lane's unit points; where 4 s + q >= N the first point (evaluated like the others, never read)
     // once, before a time loop.  xi_all: the transform's N unit points (const_layout: xi), q: the lane's place in its quad
