@@ -133,9 +133,11 @@ int ssmq_integrand_define_dx(const char *body, const char *jac_body, int din, in
  * tp, opt ignored); an id without a Jacobian, D > 6 or E > 4 (measurement) is SSMQ_E_UNSUPPORTED. */
 /* SSMQ_RTC_IMM instantiates the IMM kernel k_imm_loop<D, E (= Y), N, N_obs, id, id_obs, SELO, form, tp> of two built-in integrands
  * (ssmq_filter_imm_dev); `opt` carries SELO (0: the measurement reads the leading states, 1: states 0, 2, 4, ...). */
+/* SSMQ_RTC_ROBUST instantiates the outlier-robust kernel k_robust_loop<D, E (= Y), N, N_obs, id, id_obs, form, tp, 0, 0> (arguments as
+ * SSMQ_RTC_FILTER; opt must be 0: the dense kernel is the only one). */
 enum ssmq_rtc_kind { SSMQ_RTC_FILTER = 0, SSMQ_RTC_APPLY = 1, SSMQ_RTC_MC = 2, SSMQ_RTC_LINEAR = 3, SSMQ_RTC_TAYLOR_GPQD = 4, SSMQ_RTC_GPQD = 5,
                      SSMQ_RTC_INNOVATION = 6, SSMQ_RTC_ITERATED = 7, SSMQ_RTC_SMOOTHER_ITERATED = 8, SSMQ_RTC_PCRLB_DYN = 9,
-                     SSMQ_RTC_PCRLB_OBS = 10, SSMQ_RTC_IMM = 11 };
+                     SSMQ_RTC_PCRLB_OBS = 10, SSMQ_RTC_IMM = 11, SSMQ_RTC_ROBUST = 12 };
 int ssmq_rtc_compile_check(int32_t id, int32_t id_obs, int kind, int D, int E, int N, int N_obs, int form, int tp, int opt,
                            const char *arch, char *log, int len);
 /* Process-wide counters of the run-time compiler: programs compiled, kernel lookups served from the cache, compile wall time. */
@@ -1015,6 +1017,38 @@ int ssmq_filter_iterated_dev(ssmq_transform *h_dyn, const ssmq_integrand *f_dyn,
 /* Name of the kernel(s) ssmq_filter_iterated_dev would run for this pair, iteration count and flags. */
 int ssmq_iterated_kernel_name(const ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, const ssmq_transform *h_obs,
                               const ssmq_integrand *f_obs, int64_t B, int iterations, int flags, char *buf, int len);
+
+/*
+ * Outlier-robust pass of the additive-noise Gaussian filters (Agamennoni, Nieto, Nebot 2012; Piche, Sarkka, Hartikainen 2012): the
+ * measurement noise is Student-t, r_k | lambda_k ~ N(0, R / lambda_k), lambda_k ~ Gamma(dof / 2, rate dof / 2), R its SCALE matrix.
+ * Per step the time update of ssmq_filter_forward_dev, ONE measurement transform at the prior,
+ *     y^, P_h (no noise), C = measurement transform of (m-, P-)          e = y_k - y^          lambda_0 = 1,
+ * the variational fixed point in measurement space, i = 0 .. iterations - 2,
+ *     S_i = P_h + R / lambda_i      r^ = (R / lambda_i) S_i^-1 e      Psi = r^ r^' + P_h - P_h S_i^-1 P_h
+ *     gamma = sum_ab (R^-1)[a][b] Psi[a][b]      lambda_{i+1} = (dof + Y) / (dof + gamma)
+ * and one state update with the last weight: S = P_h + R / lambda, K = C' S^-1, m = m- + K e, P = P- - K S K' (both triangles of fP
+ * from one value).  d_lam [T][ld]: the weight the update used (the outlier indicator: 1 for an unsurprising measurement, towards 0
+ * for an outlier); d_delta [T][ld]: |lambda_{J-1} - lambda_{J-2}| / lambda_{J-1}, 0 for iterations = 1 - there is no stopping rule.
+ * iterations = 1 is ssmq_filter_forward_dev up to rounding.  1 <= iterations <= SSMQ_ITERATED_MAX, dof a positive finite number
+ * (1e300: every weight is exactly 1), R symmetric positive definite (its inverse is taken on the host by Cholesky), flags: bit 0
+ * alone - else SSMQ_E_ARG.  Buffers as ssmq_filter_forward_dev.
+ * Failures: a factorisation that fails (P by the transforms, S_i, S), a weight that is not a positive finite number or an updated mean
+ * that is not finite (a NaN measurement) makes the trajectory's outputs (lam and delta included) NaN from that step on,
+ * d_status[b] = 1 + that step.  A trajectory's results do not depend on the batch around it.
+ * One launch of k_robust_loop<> where the fused time loop has an instantiation for the pair (the dense kernels), and for a pair with a
+ * user integrand in the range of ssmq_filter_forward_dev, compiled at run time; every other pair that ssmq_filter_innovations_dev
+ * accepts - and every pair under SSMQ_NO_FUSED=1 or with flags bit 0 set - runs apply dyn | apply obs | k_robust_update per step.  What
+ * ssmq_filter_innovations_dev refuses is refused here; every refusal comes before an output is touched.  Asynchronous on the library
+ * stream.
+ */
+#define SSMQ_ROBUST_LAUNCH_LOOP 1 /* flags bit 0 */
+int ssmq_filter_robust_dev(ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, ssmq_transform *h_obs, const ssmq_integrand *f_obs,
+                           int64_t B, int64_t ld, int T, int iterations, int flags, const double *d_y, const double *d_m0,
+                           const double *d_P0, const double *GQG, const double *R /* scale, [Y*Y] */, double dof, double *d_fm,
+                           double *d_fP, double *d_lam /* [T][ld] */, double *d_delta /* [T][ld] */, int32_t *d_status);
+/* Name of the kernel(s) ssmq_filter_robust_dev would run for this pair, iteration count and flags. */
+int ssmq_robust_kernel_name(const ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, const ssmq_transform *h_obs,
+                            const ssmq_integrand *f_obs, int64_t B, int iterations, int flags, char *buf, int len);
 
 /*
  * Iterated posterior linearisation smoother (IPLS; Garcia-Fernandez, Svensson, Sarkka, IEEE TAC 2017) of the additive-noise Gaussian

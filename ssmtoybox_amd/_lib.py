@@ -33,8 +33,10 @@ RTC_FILTER, RTC_APPLY, RTC_MC, RTC_LINEAR, RTC_TAYLOR_GPQD, RTC_GPQD, RTC_INNOVA
 RTC_SMOOTHER_ITERATED = 8
 RTC_PCRLB_DYN, RTC_PCRLB_OBS = 9, 10
 RTC_IMM = 11
+RTC_ROBUST = 12
 ITERATED_MAX = 64          # SSMQ_ITERATED_MAX
 ITERATED_LAUNCH_LOOP = 1   # flags bit 0 of ssmq_filter_iterated_dev
+ROBUST_LAUNCH_LOOP = 1     # flags bit 0 of ssmq_filter_robust_dev
 
 
 class SsmqError(RuntimeError):
@@ -336,6 +338,12 @@ _PROTOTYPES = {
                                  [ctypes.c_void_p] * 3 + [c_double_p, c_double_p] + [ctypes.c_void_p] * 4),
     'ssmq_iterated_kernel_name': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Integrand), ctypes.c_void_p, ctypes.POINTER(Integrand),
                                                  ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_char_p, ctypes.c_int]),
+    # (pair, B, ld, T, iterations, flags, d_y, d_m0, d_P0, GQG, R, dof, d_fm, d_fP, d_lam, d_delta, d_status)
+    'ssmq_filter_robust_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Integrand), ctypes.c_void_p, ctypes.POINTER(Integrand),
+                                              ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int] +
+                               [ctypes.c_void_p] * 3 + [c_double_p, c_double_p, ctypes.c_double] + [ctypes.c_void_p] * 5),
+    'ssmq_robust_kernel_name': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Integrand), ctypes.c_void_p, ctypes.POINTER(Integrand),
+                                               ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_char_p, ctypes.c_int]),
     'ssmq_smoother_iterated_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Integrand), ctypes.c_void_p, ctypes.POINTER(Integrand),
                                                   ctypes.c_int64, ctypes.c_int64, ctypes.c_int] + [ctypes.c_void_p] * 3 +
                                    [c_double_p, c_double_p, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 10),

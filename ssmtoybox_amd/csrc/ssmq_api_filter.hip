@@ -2,6 +2,7 @@
 // (FilterCache), the filter for models that take their noise as an argument, both smoothers, the Student filter, the error sums
 // over filtered trajectories and the simulator.
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <vector>
 #include "ssmq_host.h"
@@ -49,6 +50,9 @@ struct FilterCache {
     void *consts = nullptr;           // the pass's constants (PassConsts layout, ssmq_host.h) of every single-filter route, grow-only ...
     size_t consts_bytes = 0;
     std::vector<double> consts_host;  // ... and what the block holds
+    void *robust = nullptr;           // R | R^-1 of the outlier-robust pass, [Y*Y] each, grow-only ...
+    size_t robust_bytes = 0;
+    std::vector<double> robust_host;  // ... and what the block holds
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
     std::vector<uint64_t> key;
@@ -105,9 +109,11 @@ void drop_filter_cache() {
     g_fc.drop_graph();
     if (g_fc.ws) hipFree(g_fc.ws);
     if (g_fc.consts) hipFree(g_fc.consts);
-    g_fc.ws = g_fc.consts = nullptr;
-    g_fc.ws_bytes = g_fc.consts_bytes = 0;
+    if (g_fc.robust) hipFree(g_fc.robust);
+    g_fc.ws = g_fc.consts = g_fc.robust = nullptr;
+    g_fc.ws_bytes = g_fc.consts_bytes = g_fc.robust_bytes = 0;
     g_fc.consts_host.clear();
+    g_fc.robust_host.clear();
 }
 
 // Which of the launch loop's special forms a pair of an additive-noise Gaussian filter has, after the refusals every entry point
@@ -806,6 +812,157 @@ extern "C" int ssmq_iterated_kernel_name(const ssmq_transform *h_dyn, const ssmq
     rc = one_launch ? try_launch_iterated(query, iterations, nullptr) : 0;
     if (rc < 0) return rc;
     snprintf(buf, len, "%s", rc == 1 ? name : kIplfLoopName);
+    return SSMQ_OK;
+}
+
+// ---- outlier-robust pass (include/ssmq.h: ssmq_filter_robust_dev) ---------------------------------------------------------------------
+// The refusals and the route choice are those of the innovation scores (innovations_route); flag bit 0 forces the launch loop.
+static const char kRobustLoopName[] = "launch loop of 3 T launches (apply dyn | apply obs | k_robust_update)";
+
+// R | R^-1 as the host image of the context's block: false when R is not finite, not symmetric or not positive definite.  The
+// inverse by Cholesky, R = L L': column j of R^-1 from L z = e_j, L' x = z; symmetrised by its lower triangle (the kernels read that).
+static bool robust_consts(int Y, const double *R, std::vector<double> *out) {
+    std::vector<double> L((size_t)Y * Y, 0.0), h(2 * (size_t)Y * Y, 0.0), v(Y);
+    for (int i = 0; i < Y; ++i)
+        for (int j = 0; j < Y; ++j)
+            if (!std::isfinite(R[i * Y + j]) || R[i * Y + j] != R[j * Y + i]) return false;
+    for (int j = 0; j < Y; ++j) {
+        double ajj = R[j * Y + j];
+        for (int k = 0; k < j; ++k) ajj -= L[j * Y + k] * L[j * Y + k];
+        if (!(ajj > 0.0)) return false;
+        L[j * Y + j] = std::sqrt(ajj);
+        for (int i = j + 1; i < Y; ++i) {
+            double s = R[i * Y + j];
+            for (int k = 0; k < j; ++k) s -= L[i * Y + k] * L[j * Y + k];
+            L[i * Y + j] = s / L[j * Y + j];
+        }
+    }
+    for (int j = 0; j < Y; ++j) {
+        for (int i = 0; i < Y; ++i) {
+            double s = i == j ? 1.0 : 0.0;
+            for (int k = 0; k < i; ++k) s -= L[i * Y + k] * v[k];
+            v[i] = s / L[i * Y + i];
+        }
+        for (int i = Y - 1; i >= 0; --i) {
+            double s = v[i];
+            for (int k = i + 1; k < Y; ++k) s -= L[k * Y + i] * v[k];
+            v[i] = s / L[i * Y + i];
+        }
+        for (int i = j; i < Y; ++i) h[(size_t)Y * Y + i * Y + j] = h[(size_t)Y * Y + j * Y + i] = v[i];
+    }
+    std::copy(R, R + (size_t)Y * Y, h.begin());
+    for (double x : h)
+        if (!std::isfinite(x)) return false;
+    out->swap(h);
+    return true;
+}
+
+// ... uploaded when it differs from what the block holds (as cached_pass_consts)
+static int cached_robust_consts(std::vector<double> &h, hipStream_t s) {
+    FilterCache &c = g_fc;
+    if (h == c.robust_host) return SSMQ_OK;
+    const size_t need = sizeof(double) * h.size();
+    c.robust_host.clear();
+    if (c.robust_bytes < need) {
+        if (c.robust) {
+            SSMQ_HIP(hipStreamSynchronize(s));
+            hipFree(c.robust);
+        }
+        c.robust = nullptr;
+        c.robust_bytes = 0;
+        SSMQ_HIP(hipMalloc(&c.robust, need));
+        c.robust_bytes = need;
+    }
+    SSMQ_HIP(hipMemcpyAsync(c.robust, h.data(), need, hipMemcpyHostToDevice, s));
+    SSMQ_HIP(hipStreamSynchronize(s));
+    c.robust_host.swap(h);
+    return SSMQ_OK;
+}
+
+// the argument checks both entry points share, after the null checks; R may be null for the name query
+static int robust_arg_checks(int iterations, int flags, double dof) {
+    if (flags & ~SSMQ_ROBUST_LAUNCH_LOOP) {
+        set_error("filter_robust: flags: bit 0 alone");
+        return SSMQ_E_ARG;
+    }
+    if (iterations < 1 || iterations > SSMQ_ITERATED_MAX) {
+        set_error("filter_robust: 1 <= iterations <= " + std::to_string(SSMQ_ITERATED_MAX));
+        return SSMQ_E_ARG;
+    }
+    if (!(dof > 0.0) || !std::isfinite(dof)) {
+        set_error("filter_robust: dof must be a positive finite number");
+        return SSMQ_E_ARG;
+    }
+    return SSMQ_OK;
+}
+
+extern "C" int ssmq_filter_robust_dev(ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, ssmq_transform *h_obs, const ssmq_integrand *f_obs,
+                                      int64_t B, int64_t ld, int T, int iterations, int flags, const double *d_y, const double *d_m0,
+                                      const double *d_P0, const double *GQG, const double *R, double dof, double *d_fm, double *d_fP,
+                                      double *d_lam, double *d_delta, int32_t *d_status) {
+    SSMQ_HANDLE_LOCK(h_dyn, h_obs);
+    if (!h_dyn || !h_obs || !f_dyn || !f_obs || B < 0 || ld < B || T < 0 || !d_y || !d_m0 || !d_P0 || !R || !d_fm || !d_fP || !d_lam ||
+        !d_delta || !d_status) {
+        set_error("filter_robust: bad argument");
+        return SSMQ_E_ARG;
+    }
+    int rc = robust_arg_checks(iterations, flags, dof);
+    if (rc) return rc;
+    PairForms pf;
+    bool user_ekf = false, one_launch = false;
+    if ((rc = innovations_route(h_dyn, f_dyn, h_obs, f_obs, &pf, &user_ekf, &one_launch))) return rc;
+    if ((flags & SSMQ_ROBUST_LAUNCH_LOOP) && !pf.user) one_launch = false;      // (a user pair without Jacobians has no launch loop)
+    const int D = h_dyn->D, Y = h_obs->E;
+    std::vector<double> rh;
+    if (!robust_consts(Y, R, &rh)) {
+        set_error("filter_robust: R must be a finite symmetric positive definite matrix");
+        return SSMQ_E_ARG;
+    }
+    if ((rc = ensure_device())) return rc;
+    if (B == 0) return SSMQ_OK;
+    hipStream_t s = stream();
+    if (T == 0) {   // nothing to filter: every trajectory is trivially fine
+        SSMQ_HIP(hipMemsetAsync(d_status, 0, sizeof(int32_t) * ld, s));
+        return SSMQ_OK;
+    }
+    FilterPass pass;
+    PassConsts pc;
+    // (the pass's constants without R: its rr block is the zeros the measurement transform adds)
+    if ((rc = make_filter_pass(h_dyn, f_dyn, h_obs, f_obs, B, ld, T, d_y, d_m0, d_P0, d_fm, d_fP, d_status, s, &pass)) ||
+        (rc = cached_pass_consts(f_dyn, f_obs, D, Y, T, GQG, nullptr, nullptr, s, &pc)) || (rc = cached_robust_consts(rh, s)))
+        return rc;
+    const double *cs = (const double *)g_fc.consts, *rb = (const double *)g_fc.robust;
+    wire_pass_consts(pass, cs, pc);
+    const RobustPass rp{iterations, dof, rb, rb + (size_t)Y * Y, d_lam, d_delta};
+    rc = one_launch ? try_launch_robust(pass, rp) : 0;
+    if (rc < 0) return rc;
+    if (rc == 1) return SSMQ_OK;
+    if (pf.user && !user_ekf) {
+        set_error("filter_robust: no run-time kernel for this pair of user integrands");
+        return SSMQ_E_UNSUPPORTED;
+    }
+    if (user_ekf && (rc = prepare_user_ekf(h_dyn, f_dyn, h_obs, f_obs, pf.gq))) return rc;
+    if ((rc = ensure_ws(robust_ws_bytes(D, Y, ld)))) return rc;
+    return robust_launch_loop(h_dyn, h_obs, pass, rp, cs + pc.steps, g_fc.ws);
+}
+
+extern "C" int ssmq_robust_kernel_name(const ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, const ssmq_transform *h_obs,
+                                       const ssmq_integrand *f_obs, int64_t B, int iterations, int flags, char *buf, int len) {
+    SSMQ_HANDLE_LOCK(h_dyn, h_obs);
+    if (!h_dyn || !h_obs || !f_dyn || !f_obs || !buf || len <= 0 || B < 0) return SSMQ_E_ARG;
+    int rc = robust_arg_checks(iterations, flags, 1.0);
+    if (rc) return rc;
+    PairForms pf;
+    bool user_ekf = false, one_launch = false;
+    if ((rc = innovations_route(h_dyn, f_dyn, h_obs, f_obs, &pf, &user_ekf, &one_launch))) return rc;
+    if ((flags & SSMQ_ROBUST_LAUNCH_LOOP) && !pf.user) one_launch = false;
+    const char *name = nullptr;
+    FilterPass query;
+    if ((rc = make_filter_pass(h_dyn, f_dyn, h_obs, f_obs, B, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &query))) return rc;
+    query.name = &name; query.dry_run = true;
+    rc = one_launch ? try_launch_robust(query, RobustPass{iterations, 1.0, nullptr, nullptr, nullptr, nullptr}) : 0;
+    if (rc < 0) return rc;
+    snprintf(buf, len, "%s", rc == 1 ? name : kRobustLoopName);
     return SSMQ_OK;
 }
 

@@ -617,6 +617,23 @@ size_t iterated_ws_bytes(int D, int Y, int64_t ld);
 int iterated_launch_loop(ssmq_transform *h_dyn, ssmq_transform *h_obs, const FilterPass &p, int iterations, double *delta,
                          const double *tvec, void *ws);
 
+// Outlier-robust pass (ssmq_filter_robust.hip, ssmq_filter_robust_dev): the measurement update under Student-t noise of scale R and
+// `dof` degrees of freedom, `iterations` - 1 rounds of its fixed point per step.  The pass is built WITHOUT R (p.rr: zeros - the
+// measurement transform adds no noise); R and its inverse travel here, device [Y*Y] each.  try_launch_robust / rtc_launch_robust /
+// robust_launch_loop: as their iterated twins above.
+struct RobustPass {
+    int iterations;
+    double dof;
+    const double *rr, *ir;
+    double *lam, *delta;                      // [T][ld] each
+};
+struct RobustArgs;                            // ssmq_robust_kernel.h
+RobustArgs robust_args(const FilterPass &p, const RobustPass &r);
+int try_launch_robust(const FilterPass &p, const RobustPass &r);
+int rtc_launch_robust(const FilterPass &p, const RobustPass &r);
+size_t robust_ws_bytes(int D, int Y, int64_t ld);
+int robust_launch_loop(ssmq_transform *h_dyn, ssmq_transform *h_obs, const FilterPass &p, const RobustPass &r, const double *tvec, void *ws);
+
 // Iterated posterior linearisation smoother (ssmq_filter_ipls.hip, ssmq_smoother_iterated_dev): ONE iteration - the forward sweep and
 // the backward sweep - is one launch of k_ipls_pass<> (ssmq_ipls_kernel.h).  The planes of an iteration besides those of the pass
 // (p.fm / p.fP: its filtered moments, p.status: read and written): the linearisation moments it reads (both null: the running

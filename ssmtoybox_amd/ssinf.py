@@ -164,7 +164,8 @@ class GaussianInference:
         self.mod_dyn, self.mod_obs, self.tf_dyn, self.tf_obs = mod_dyn, mod_obs, tf_dyn, tf_obs
         self.x0_mean, self.x0_cov = mod_dyn.init_rv.get_stats()
         self.q_mean, self.q_cov = mod_dyn.noise_rv.get_stats()
-        self.r_mean, self.r_cov = mod_obs.noise_rv.get_stats()
+        # (a StudentRV measurement noise hands back its dof as well: its SCALE matrix stands in for R - what `robust_pass*` are for)
+        self.r_mean, self.r_cov = mod_obs.noise_rv.get_stats()[:2]
         self.G = mod_dyn.noise_gain
         self.fi_mean = self.fi_cov = None
         self.sm_mean = self.sm_cov = None
@@ -763,6 +764,113 @@ class GaussianInference:
         """`iterated_pass_batch` for one trajectory, data (dim_y, T) -> filtered means (D, T), covariances (D, D, T)."""
         fm, fP = self.iterated_pass_batch(np.asarray(data)[..., None], iterations)
         return fm[..., 0], fP[..., 0]
+
+    # ---- outlier-robust measurement update: Student-t measurement noise, the weight lambda_k found by a fixed point per step -----
+    def _robust_refusal(self, dof, iterations, r_scale):
+        """(dof, iterations, R) of a robust pass, or what keeps a filter or an argument out of it - before the library is touched.
+        r_scale=None: the scale of a `StudentRV` measurement noise, the covariance of a `GaussRV`; dof=None: the `StudentRV`'s."""
+        self._additive_gauss_only('the robust pass covers')
+        from .ssmod import StudentRV
+        iterations = _iteration_count(iterations)
+        rv = self.mod_obs.noise_rv
+        if dof is None:
+            if not isinstance(rv, StudentRV):
+                raise ValueError('robust pass: the measurement noise is not a StudentRV, so `dof` must be given')
+            dof = rv.dof
+        dof = float(dof)
+        if not (dof > 0.0 and np.isfinite(dof)):
+            raise ValueError('robust pass: dof must be a positive finite number (got {!r})'.format(dof))
+        if r_scale is None:
+            r_scale = rv.scale if isinstance(rv, StudentRV) else rv.cov
+        Y = self.mod_obs.dim_out
+        R = np.ascontiguousarray(np.atleast_2d(np.asarray(r_scale, dtype=np.float64)))
+        if R.shape != (Y, Y) or not np.isfinite(R).all() or not np.array_equal(R, R.T):
+            raise ValueError('robust pass: r_scale must be a finite symmetric ({0}, {0}) matrix'.format(Y))
+        try:
+            np.linalg.cholesky(R)
+        except np.linalg.LinAlgError:
+            raise ValueError('robust pass: r_scale is not positive definite') from None
+        return dof, iterations, R
+
+    def robust_kernel_name(self, iterations, batch=0, launch_loop=False):
+        """Which kernel(s) `robust_pass*` run for this filter: k_robust_loop<..> (the whole pass in one launch) where the fused time
+        loop has an instantiation, and for user models; else the launch loop apply dyn | apply obs | k_robust_update."""
+        self._additive_gauss_only('the robust pass covers')
+        iterations = _iteration_count(iterations)
+        self._check_user_points()
+        return self._kernel_name('ssmq_robust_kernel_name', int(batch), iterations, _lib.ROBUST_LAUNCH_LOOP if launch_loop else 0)
+
+    def _launch_robust(self, lib, B, ld, T, dof, iterations, R, flags, d_y, d_m0, d_P0, d_fm, d_fP, d_lam, d_delta, d_st):
+        gqg, _ = self._noise()
+        vp, dp = _lib.vp, _lib.dp
+        _lib.check(lib.ssmq_filter_robust_dev(*self._pair(), B, ld, T, iterations, flags, vp(d_y), vp(d_m0), vp(d_P0), dp(gqg), dp(R), dof,
+                                              vp(d_fm), vp(d_fP), vp(d_lam), vp(d_delta), vp(d_st)), 'ssmq_filter_robust_dev')
+
+    def robust_pass_dev(self, d_y, B, ld, T, dof=None, iterations=5, r_scale=None, launch_loop=False):
+        """`forward_pass_dev` with the outlier-robust measurement update: measurements on the device (planes [T][dim_y][ld]), results
+        left there - DeviceBuffers (d_fm [T][D][ld], d_fP [T][D*D][ld], d_lam [T][ld], d_delta [T][ld], d_status [ld]); the caller
+        frees them.  Every trajectory starts from the model's initial moments."""
+        dof, iterations, R = self._robust_refusal(dof, iterations, r_scale)
+        self._check_user_points()
+        lib = _lib.load()
+        D = self.mod_dyn.dim_state
+        with _lib.Staging() as stage:
+            d_m0, d_P0 = self._initial_planes(stage, B, ld)
+            d_fm, d_fP = stage.device(8 * T * D * ld), stage.device(8 * T * D * D * ld)
+            d_lam, d_delta, d_st = stage.device(8 * T * ld), stage.device(8 * T * ld), stage.device(4 * ld)
+            self._launch_robust(lib, B, ld, T, dof, iterations, R, _lib.ROBUST_LAUNCH_LOOP if launch_loop else 0, d_y, d_m0, d_P0, d_fm,
+                                d_fP, d_lam, d_delta, d_st)
+            _lib.sync()
+            return stage.release(d_fm, d_fP, d_lam, d_delta, d_st)
+
+    def robust_pass_batch(self, data, dof=None, iterations=5, r_scale=None, x0_mean=None, x0_cov=None, raise_on_failure=True,
+                          return_weights=False, launch_loop=False):
+        """The forward pass with the variational outlier-robust measurement update (Agamennoni et al. 2012; Piche, Sarkka,
+        Hartikainen 2012), data (dim_y, T, B).  The measurement noise is Student-t with scale matrix `r_scale` and `dof` degrees of
+        freedom, r_k | lambda_k ~ N(0, R / lambda_k), lambda_k ~ Gamma(dof / 2, dof / 2).  Per step the time update of
+        `forward_pass_batch`, one measurement transform at the prior (y^, P_h without noise, C; e = y_k - y^, lambda_0 = 1), then
+        `iterations` - 1 rounds of the fixed point in measurement space
+            S_i = P_h + R / lambda_i;  r^ = (R / lambda_i) S_i^-1 e;  Psi = r^ r^' + P_h - P_h S_i^-1 P_h;
+            lambda_{i+1} = (dof + dim_y) / (dof + trace(R^-1 Psi))
+        and one state update with the last weight: S = P_h + R / lambda, K = C' S^-1, m = m- + K e, P = P- - K S K'.
+        iterations = 1 is the plain filter with R = r_scale, up to rounding.  r_scale=None: the scale of a `StudentRV` measurement
+        noise, the covariance of a `GaussRV`; dof=None: the `StudentRV`'s (a ValueError for a `GaussRV`).  Returns and sets fi_mean
+        (D, T, B), fi_cov (D, D, T, B) and `status` as the forward pass does; with return_weights also lam (T, B), the weight every
+        update used - the outlier indicator, near 1 for an unsurprising measurement, towards 0 for an outlier - and delta (T, B) =
+        |lambda_{J-1} - lambda_{J-2}| / lambda_{J-1}, the convergence diagnostic (the iteration count is fixed: there is no stopping
+        rule).  Neither the weights of the transforms nor the noise of the filter are touched.  launch_loop=True forces the
+        launch-loop route."""
+        dof, iterations, R = self._robust_refusal(dof, iterations, r_scale)
+        self._check_user_points()
+        lib = _lib.load()
+        data = np.asarray(data, dtype=np.float64)
+        Y, T, B = data.shape
+        D = self.mod_dyn.dim_state
+        ld = _lib.padded(B)
+        with _lib.Staging() as stage:
+            d_y = stage.scratch(8 * T * Y * ld)
+            _lib.upload_study(data, Y, ld, d_y)
+            d_m0, d_P0 = self._initial_planes(stage, B, ld, x0_mean, x0_cov)
+            d_fm, d_fP = stage.scratch(8 * T * D * ld), stage.scratch(8 * T * D * D * ld)
+            d_lam, d_delta, d_st = stage.scratch(8 * T * ld), stage.scratch(8 * T * ld), stage.scratch(4 * ld)
+            self._launch_robust(lib, B, ld, T, dof, iterations, R, _lib.ROBUST_LAUNCH_LOOP if launch_loop else 0, d_y, d_m0, d_P0, d_fm,
+                                d_fP, d_lam, d_delta, d_st)
+            fm = _lib.download_study(d_fm, (D,), T, B, ld)
+            fP = _lib.download_study(d_fP, (D, D), T, B, ld)
+            lam = _lib.download_study(d_lam, (), T, B, ld)
+            delta = _lib.download_study(d_delta, (), T, B, ld)
+            self.status = d_st.download((ld,), dtype=np.int32)[:B]
+        if raise_on_failure:
+            _raise_failed(self.status)
+        self.fi_mean, self.fi_cov = fm, fP
+        return (fm, fP, lam, delta) if return_weights else (fm, fP)
+
+    def robust_pass(self, data, dof=None, iterations=5, r_scale=None, return_weights=False):
+        """`robust_pass_batch` for one trajectory, data (dim_y, T) -> filtered means (D, T), covariances (D, D, T); with
+        return_weights also lam (T,) and delta (T,)."""
+        out = self.robust_pass_batch(np.asarray(data)[..., None], dof=dof, iterations=iterations, r_scale=r_scale,
+                                     return_weights=return_weights)
+        return tuple(v[..., 0] for v in out)
 
     # ---- iterated posterior linearisation smoother (IPLS): forward and backward sweep, re-linearised around the smoothed moments ----
     _IPLS_RANGE = ('the iterated smoother covers the additive-noise Gaussian filters with unscented or spherical-radial point sets '
@@ -2380,7 +2488,8 @@ def _refusing(name, what):
 for _name, _what in (('backward_pass', 'the RTS smoother (backward_pass)'), ('backward_pass_batch', 'the RTS smoother (backward_pass_batch)')) + \
         tuple((n, n) for n in ('innovations', 'innovations_batch', 'innovations_dev', 'innovations_kernel_name', 'iterated_pass',
                                'iterated_pass_batch', 'iterated_pass_dev', 'iterated_kernel_name', 'iterated_smoother',
-                               'iterated_smoother_batch', 'iterated_smoother_dev', 'iterated_smoother_kernel_name')):
+                               'iterated_smoother_batch', 'iterated_smoother_dev', 'iterated_smoother_kernel_name', 'robust_pass',
+                               'robust_pass_batch', 'robust_pass_dev', 'robust_kernel_name')):
     setattr(BootstrapParticleFilter, _name, _refusing(_name, _what))
 
 
