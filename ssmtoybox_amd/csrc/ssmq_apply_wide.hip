@@ -228,11 +228,16 @@ __global__ __launch_bounds__(BLOCK) void k_apply_wide(const WideArgs a) {
                 sT[idx] = s;
             }
             __syncthreads();
-            for (int idx = lane; idx < E * E; idx += BLOCK) {
-                const int e = idx / E, e2 = idx % E;
+            // (fx iK) fx' is symmetric as well: lower triangle, mirrored - with SSMQ_EMV_BROADCAST it scales the off-diagonal
+            // entries of the model variance, and cov_f is symmetric to the last bit
+            for (int idx = lane; idx < E * (E + 1) / 2; idx += BLOCK) {
+                int e = 0;
+                while ((e + 1) * (e + 2) / 2 <= idx) ++e;
+                const int e2 = idx - e * (e + 1) / 2;
                 double s = 0.0;
                 for (int j = 0; j < N; ++j) s += sT[e * N + j] * sfx[e2 * N + j];
-                sS[idx] = s;
+                sS[e * E + e2] = s;
+                sS[e2 * E + e] = s;
             }
             __syncthreads();
         }
@@ -263,13 +268,17 @@ __global__ __launch_bounds__(BLOCK) void k_apply_wide(const WideArgs a) {
         // ---- classical centred form (mtran.py:141-149), Wc = diag(wc) -------------------------------------------
         for (int idx = lane; idx < E * N; idx += BLOCK) sfx[idx] -= smf[idx / N];
         __syncthreads();
-        for (int idx = lane; idx < E * E; idx += BLOCK) {
-            const int e = idx / E, e2 = idx % E;
+        // (e, e2) and (e2, e) round differently as written ((fx_e wc) fx_e2): lower triangle, mirrored, as the BQ form
+        for (int idx = lane; idx < E * (E + 1) / 2; idx += BLOCK) {
+            int e = 0;
+            while ((e + 1) * (e + 2) / 2 <= idx) ++e;
+            const int e2 = idx - e * (e + 1) / 2;
             double s = 0.0;
             for (int n = 0; n < N; ++n) s += (sfx[e * N + n] * c[cl.Wc + n]) * sfx[e2 * N + n];
             s *= a.cov_scale;
-            if (a.cov_add) s += a.cov_add[idx];
-            OUT_ADDR(a.cov_f, idx, a.bs_cf) = ok ? s : nan;
+            const double lo = a.cov_add ? s + a.cov_add[e * E + e2] : s, up = a.cov_add ? s + a.cov_add[e2 * E + e] : s;
+            OUT_ADDR(a.cov_f, e * E + e2, a.bs_cf) = ok ? lo : nan;
+            if (e2 != e) OUT_ADDR(a.cov_f, e2 * E + e, a.bs_cf) = ok ? up : nan;
         }
         for (int idx = lane; idx < E * D; idx += BLOCK) {
             const int e = idx / D, d = idx % D;
@@ -595,14 +604,7 @@ __device__ __forceinline__ bool apply_wave_body(const WideArgs &a, int64_t B, in
             SSMQ_WAVE_SYNC();
             times_matrix(cl.iK);
             SSMQ_WAVE_SYNC();
-            if (active) {
-                for (int idx = gl; idx < E * E; idx += G) {
-                    const int e = idx / E, e2 = idx % E;
-                    double sacc = 0.0;
-                    for (int j = 0; j < N; ++j) sacc += sA[e * N + j] * sfx[e2 * N + j];
-                    sS[idx] = sacc;
-                }
-            }
+            lower_products(sS);                         // (symmetric to the last bit: it scales the model variance of SSMQ_EMV_BROADCAST)
         }
         SSMQ_WAVE_SYNC();
         if (active) {
@@ -641,13 +643,17 @@ __device__ __forceinline__ bool apply_wave_body(const WideArgs &a, int64_t B, in
             for (int idx = gl; idx < E * N; idx += G) sfx[idx] -= smf[idx / N];
         SSMQ_WAVE_SYNC();
         if (active) {
-            for (int idx = gl; idx < E * E; idx += G) {
-                const int e = idx / E, e2 = idx % E;
+            // (e, e2) and (e2, e) round differently as written ((fx_e wc) fx_e2): lower triangle, mirrored, as the BQ form
+            for (int idx = gl; idx < E * (E + 1) / 2; idx += G) {
+                int e = 0;
+                while ((e + 1) * (e + 2) / 2 <= idx) ++e;
+                const int e2 = idx - e * (e + 1) / 2;
                 double sacc = 0.0;
                 for (int n = 0; n < N; ++n) sacc += (sfx[e * N + n] * c[cl.Wc + n]) * sfx[e2 * N + n];
                 sacc *= a.cov_scale;
-                if (a.cov_add) sacc += a.cov_add[idx];
-                OUT_ADDR(a.cov_f, idx, a.bs_cf) = ok ? sacc : nan;
+                const double lo = a.cov_add ? sacc + a.cov_add[e * E + e2] : sacc, up = a.cov_add ? sacc + a.cov_add[e2 * E + e] : sacc;
+                OUT_ADDR(a.cov_f, e * E + e2, a.bs_cf) = ok ? lo : nan;
+                if (e2 != e) OUT_ADDR(a.cov_f, e2 * E + e, a.bs_cf) = ok ? up : nan;
             }
             for (int idx = gl; idx < E * D; idx += G) {
                 const int e = idx / D, d = idx % D;

@@ -86,7 +86,7 @@ MODELS = {
 }
 DIN = {orc.F_UNGM_DYN: 1, orc.F_UNGM_MEAS: 1, orc.F_UNGMNA_DYN: 2, orc.F_UNGMNA_MEAS: 2, orc.F_PENDULUM_DYN: 2, orc.F_PENDULUM_MEAS: 1,
        orc.F_REENTRY1D_DYN: 3, orc.F_RANGE_MEAS: 1, orc.F_REENTRY2D_DYN: 5, orc.F_REENTRY2D_BIAS_DYN: 6, orc.F_RADAR2D_MEAS: 2,
-       orc.F_CT_DYN: 5, orc.F_BEARING_MEAS: 2, orc.F_CV_DYN: 4, orc.F_CTRS_DYN: 7}
+       orc.F_CT_DYN: 5, orc.F_BEARING_MEAS: 2, orc.F_CV_DYN: 4, orc.F_CTRS_DYN: 7, orc.F_SMOOTH10D_DYN: 10}
 
 
 # ---- the dispatch tables -------------------------------------------------------------------------------------------------------
@@ -386,6 +386,10 @@ def integrand_hp(fid, x, t, p=()):
         dt = p[0]
         return ([x[0] + dt * x[1], x[1], x[2] + dt * x[3], x[3]],
                 [a(x[0]) + a(dt * x[1]), a(x[1]), a(x[2]) + a(dt * x[3]), a(x[3])])
+    if fid == orc.F_SMOOTH10D_DYN:                # (no row of the small tables: the generic kernels' cases, tests/_apply_generic_oracle.py)
+        sn, cs = [mp.sin(x[i]) for i in range(5)], [mp.cos(x[i]) for i in range(5)]
+        lo, hi = [sn[i] + x[5 + i] ** 2 for i in range(5)], [x[5 + i] * cs[i] for i in range(5)]
+        return lo + hi, [a(sn[i]) + x[5 + i] ** 2 for i in range(5)] + [a(v) for v in hi]
     raise ValueError(fid)
 
 
