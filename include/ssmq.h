@@ -135,9 +135,10 @@ int ssmq_integrand_define_dx(const char *body, const char *jac_body, int din, in
  * (ssmq_filter_imm_dev); `opt` carries SELO (0: the measurement reads the leading states, 1: states 0, 2, 4, ...). */
 /* SSMQ_RTC_ROBUST instantiates the outlier-robust kernel k_robust_loop<D, E (= Y), N, N_obs, id, id_obs, form, tp, 0, 0> (arguments as
  * SSMQ_RTC_FILTER; opt must be 0: the dense kernel is the only one). */
+/* SSMQ_RTC_MASKED instantiates the masked-pass kernel k_masked_loop<..> with the same arguments (opt must be 0). */
 enum ssmq_rtc_kind { SSMQ_RTC_FILTER = 0, SSMQ_RTC_APPLY = 1, SSMQ_RTC_MC = 2, SSMQ_RTC_LINEAR = 3, SSMQ_RTC_TAYLOR_GPQD = 4, SSMQ_RTC_GPQD = 5,
                      SSMQ_RTC_INNOVATION = 6, SSMQ_RTC_ITERATED = 7, SSMQ_RTC_SMOOTHER_ITERATED = 8, SSMQ_RTC_PCRLB_DYN = 9,
-                     SSMQ_RTC_PCRLB_OBS = 10, SSMQ_RTC_IMM = 11, SSMQ_RTC_ROBUST = 12 };
+                     SSMQ_RTC_PCRLB_OBS = 10, SSMQ_RTC_IMM = 11, SSMQ_RTC_ROBUST = 12, SSMQ_RTC_MASKED = 13 };
 int ssmq_rtc_compile_check(int32_t id, int32_t id_obs, int kind, int D, int E, int N, int N_obs, int form, int tp, int opt,
                            const char *arch, char *log, int len);
 /* Process-wide counters of the run-time compiler: programs compiled, kernel lookups served from the cache, compile wall time. */
@@ -1049,6 +1050,54 @@ int ssmq_filter_robust_dev(ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, s
 /* Name of the kernel(s) ssmq_filter_robust_dev would run for this pair, iteration count and flags. */
 int ssmq_robust_kernel_name(const ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, const ssmq_transform *h_obs,
                             const ssmq_integrand *f_obs, int64_t B, int iterations, int flags, char *buf, int len);
+
+/*
+ * Masked pass of the additive-noise Gaussian filters: missing components of y_k and a chi-square gate in front of the update.
+ * d_mask [T][ld], uint32: bit i of mask[k][b] set = component i of y_k was observed (bits at or above Y are ignored); NULL: component
+ * i is observed iff y_k[i] is not a NaN.  Per step the time update of ssmq_filter_forward_dev, ONE measurement transform at the prior
+ * - at every step, whatever the mask -
+ *     y^, P_h (no noise), C = measurement transform of (m-, P-)          S = P_h + R          e = y_k - y^
+ * and with o = popcount(mask) and the subscript o selecting the observed rows and columns
+ *     d2 = e_o' S_oo^-1 e_o          ll = -(o log 2 pi + log det S_oo + d2) / 2          (both 0 for o = 0)
+ *     take = (o > 0) and not (d2 > gate[o])
+ *     take:  K = C_o' S_oo^-1,  m = m- + K e_o,  P = P- - K S_oo K'          else:  m = m-,  P = P-  (bit for bit the prior)
+ * (both triangles of fP from one value).  The observed rows are not compressed: the unobserved components are decoupled in place by
+ * selects (e_i = 0, S_ii = 1, S_ij = S_ji = 0, C_i. = 0) and the Y x Y update runs; every term they contribute is an exact zero.  The
+ * value under a cleared bit is never an operand: it may be anything, NaN and Inf included.
+ * gate: HOST [Y + 1], entry o = the threshold for o observed components (the chi-square quantile with o degrees of freedom, say),
+ * entry 0 ignored, +inf = no gate for that o; NULL: no gate.  An entry 1 .. Y that is NaN or <= 0, an R that is not finite and
+ * symmetric, flags other than bit 0: SSMQ_E_ARG.
+ * d_used [T][ld], uint32: the mask the update applied - 0 when nothing was offered or the gate rejected; d_nis [T][ld] = d2 and
+ * d_loglik [T][ld] = ll: the scores of the OFFERED components, whether or not the gate then rejected them.  Other buffers as
+ * ssmq_filter_forward_dev.
+ * Failures: a factorisation that fails (P by the transforms - the measurement transform's counts at a fully masked step too, so the
+ * status does not depend on the mask - or S_oo) or a mean that is not finite (an OBSERVED component that is NaN; a NaN d2 does not
+ * gate, so the update runs and fails) makes the trajectory's outputs NaN and d_used 0 from that step on, d_status[b] = 1 + that step.
+ * A trajectory's results do not depend on the batch around it.
+ * One launch of k_masked_loop<> where the fused time loop has an instantiation for the pair (the dense kernels), and for a pair with a
+ * user integrand in the range of ssmq_filter_forward_dev, compiled at run time; every other pair that ssmq_filter_innovations_dev
+ * accepts - and every pair under SSMQ_NO_FUSED=1 or with flags bit 0 set - runs apply dyn | apply obs | k_masked_update per step.  What
+ * ssmq_filter_innovations_dev refuses is refused here; every refusal comes before an output is touched.  Asynchronous on the library
+ * stream.
+ */
+#define SSMQ_MASKED_LAUNCH_LOOP 1 /* flags bit 0 */
+int ssmq_filter_masked_dev(ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, ssmq_transform *h_obs, const ssmq_integrand *f_obs,
+                           int64_t B, int64_t ld, int T, int flags, const double *d_y, const uint32_t *d_mask /* [T][ld] or NULL */,
+                           const double *d_m0, const double *d_P0, const double *GQG, const double *R /* [Y*Y] */,
+                           const double *gate /* host [Y+1] or NULL */, double *d_fm, double *d_fP, uint32_t *d_used /* [T][ld] */,
+                           double *d_nis /* [T][ld] */, double *d_loglik /* [T][ld] */, int32_t *d_status);
+/* Name of the kernel(s) ssmq_filter_masked_dev would run for this pair and flags. */
+int ssmq_masked_kernel_name(const ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, const ssmq_transform *h_obs,
+                            const ssmq_integrand *f_obs, int64_t B, int flags, char *buf, int len);
+/*
+ * Detection masks for ssmq_filter_masked_dev, drawn on the device: bit i of d_mask[k][b] (uint32 [T][ld]) is set iff u < p_detect[i]
+ * (host [Y], each in [0, 1]; 1 <= Y <= SSMQ_MAX_DIM), u a 53-bit uniform in (0, 1) from Philox4x32-10 keyed by `seed`, counter
+ * (traj_offset + b lo, hi, k, 15 << 28 | i), its first two output words.  per_component = 0: one draw per (k, b) with i = 0 against
+ * p_detect[0], and all Y bits go together (a scan is detected or it is not).  The bits depend on (seed, traj_offset + b, k, i) alone.
+ * Asynchronous on the library stream.
+ */
+int ssmq_detection_mask_dev(int64_t B, int64_t ld, int T, int Y, const double *p_detect, uint64_t seed, uint64_t traj_offset,
+                            int per_component, uint32_t *d_mask);
 
 /*
  * Iterated posterior linearisation smoother (IPLS; Garcia-Fernandez, Svensson, Sarkka, IEEE TAC 2017) of the additive-noise Gaussian

@@ -34,9 +34,11 @@ RTC_SMOOTHER_ITERATED = 8
 RTC_PCRLB_DYN, RTC_PCRLB_OBS = 9, 10
 RTC_IMM = 11
 RTC_ROBUST = 12
+RTC_MASKED = 13
 ITERATED_MAX = 64          # SSMQ_ITERATED_MAX
 ITERATED_LAUNCH_LOOP = 1   # flags bit 0 of ssmq_filter_iterated_dev
 ROBUST_LAUNCH_LOOP = 1     # flags bit 0 of ssmq_filter_robust_dev
+MASKED_LAUNCH_LOOP = 1     # flags bit 0 of ssmq_filter_masked_dev
 
 
 class SsmqError(RuntimeError):
@@ -344,6 +346,15 @@ _PROTOTYPES = {
                                [ctypes.c_void_p] * 3 + [c_double_p, c_double_p, ctypes.c_double] + [ctypes.c_void_p] * 5),
     'ssmq_robust_kernel_name': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Integrand), ctypes.c_void_p, ctypes.POINTER(Integrand),
                                                ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_char_p, ctypes.c_int]),
+    # (pair, B, ld, T, flags, d_y, d_mask, d_m0, d_P0, GQG, R, gate, d_fm, d_fP, d_used, d_nis, d_loglik, d_status)
+    'ssmq_filter_masked_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Integrand), ctypes.c_void_p, ctypes.POINTER(Integrand),
+                                              ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 4 +
+                               [c_double_p] * 3 + [ctypes.c_void_p] * 6),
+    'ssmq_masked_kernel_name': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Integrand), ctypes.c_void_p, ctypes.POINTER(Integrand),
+                                               ctypes.c_int64, ctypes.c_int, ctypes.c_char_p, ctypes.c_int]),
+    # (B, ld, T, Y, p_detect, seed, traj_offset, per_component, d_mask)
+    'ssmq_detection_mask_dev': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_uint64,
+                                               ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p]),
     'ssmq_smoother_iterated_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Integrand), ctypes.c_void_p, ctypes.POINTER(Integrand),
                                                   ctypes.c_int64, ctypes.c_int64, ctypes.c_int] + [ctypes.c_void_p] * 3 +
                                    [c_double_p, c_double_p, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 10),

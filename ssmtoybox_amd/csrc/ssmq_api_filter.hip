@@ -966,6 +966,125 @@ extern "C" int ssmq_robust_kernel_name(const ssmq_transform *h_dyn, const ssmq_i
     return SSMQ_OK;
 }
 
+// ---- masked pass (include/ssmq.h: ssmq_filter_masked_dev) -------------------------------------------------------------------------------
+// The refusals and the route choice are those of the innovation scores (innovations_route); flag bit 0 forces the launch loop.
+static const char kMaskedLoopName[] = "launch loop of 3 T launches (apply dyn | apply obs | k_masked_update)";
+
+// R | gate as the host image of a device block ([Y*Y] | [Y+1]; gate null: +inf everywhere): false, with the error set, when R is
+// not finite or not symmetric or a gate entry 1 .. Y is not a positive number or +inf
+static bool masked_consts(int Y, const double *R, const double *gate, std::vector<double> *out) {
+    std::vector<double> h((size_t)Y * Y + Y + 1, HUGE_VAL);
+    for (int i = 0; i < Y; ++i)
+        for (int j = 0; j < Y; ++j) {
+            if (!std::isfinite(R[i * Y + j]) || R[i * Y + j] != R[j * Y + i]) {
+                set_error("filter_masked: R must be a finite symmetric matrix");
+                return false;
+            }
+            h[(size_t)i * Y + j] = R[i * Y + j];
+        }
+    for (int o = 1; gate && o <= Y; ++o) {
+        if (!(gate[o] > 0.0)) {   // (NaN included)
+            set_error("filter_masked: gate entries 1 .. Y must be positive numbers or +inf");
+            return false;
+        }
+        h[(size_t)Y * Y + o] = gate[o];
+    }
+    out->swap(h);
+    return true;
+}
+
+static int masked_flag_check(int flags) {
+    if (flags & ~SSMQ_MASKED_LAUNCH_LOOP) {
+        set_error("filter_masked: flags: bit 0 alone");
+        return SSMQ_E_ARG;
+    }
+    return SSMQ_OK;
+}
+
+extern "C" int ssmq_filter_masked_dev(ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, ssmq_transform *h_obs, const ssmq_integrand *f_obs,
+                                      int64_t B, int64_t ld, int T, int flags, const double *d_y, const uint32_t *d_mask, const double *d_m0,
+                                      const double *d_P0, const double *GQG, const double *R, const double *gate, double *d_fm, double *d_fP,
+                                      uint32_t *d_used, double *d_nis, double *d_loglik, int32_t *d_status) {
+    SSMQ_HANDLE_LOCK(h_dyn, h_obs);
+    if (!h_dyn || !h_obs || !f_dyn || !f_obs || B < 0 || ld < B || T < 0 || !d_y || !d_m0 || !d_P0 || !R || !d_fm || !d_fP || !d_used ||
+        !d_nis || !d_loglik || !d_status) {
+        set_error("filter_masked: bad argument");
+        return SSMQ_E_ARG;
+    }
+    int rc = masked_flag_check(flags);
+    if (rc) return rc;
+    PairForms pf;
+    bool user_ekf = false, one_launch = false;
+    if ((rc = innovations_route(h_dyn, f_dyn, h_obs, f_obs, &pf, &user_ekf, &one_launch))) return rc;
+    if ((flags & SSMQ_MASKED_LAUNCH_LOOP) && !pf.user) one_launch = false;      // (a user pair without Jacobians has no launch loop)
+    const int D = h_dyn->D, Y = h_obs->E;
+    std::vector<double> mh;
+    if (!masked_consts(Y, R, gate, &mh)) return SSMQ_E_ARG;
+    if ((rc = ensure_device())) return rc;
+    if (B == 0) return SSMQ_OK;
+    hipStream_t s = stream();
+    if (T == 0) {   // nothing to filter: every trajectory is trivially fine
+        SSMQ_HIP(hipMemsetAsync(d_status, 0, sizeof(int32_t) * ld, s));
+        return SSMQ_OK;
+    }
+    FilterPass pass;
+    PassConsts pc;
+    // (the pass's constants without R: its rr block is the zeros the measurement transform adds; R | gate in the block the robust
+    // pass keeps its R | R^-1 in - one image at a time, uploaded when it differs from what the block holds)
+    if ((rc = make_filter_pass(h_dyn, f_dyn, h_obs, f_obs, B, ld, T, d_y, d_m0, d_P0, d_fm, d_fP, d_status, s, &pass)) ||
+        (rc = cached_pass_consts(f_dyn, f_obs, D, Y, T, GQG, nullptr, nullptr, s, &pc)) || (rc = cached_robust_consts(mh, s)))
+        return rc;
+    const double *cs = (const double *)g_fc.consts, *rb = (const double *)g_fc.robust;
+    wire_pass_consts(pass, cs, pc);
+    const MaskedPass mp{d_mask, rb, rb + (size_t)Y * Y, d_used, d_nis, d_loglik};
+    rc = one_launch ? try_launch_masked(pass, mp) : 0;
+    if (rc < 0) return rc;
+    if (rc == 1) return SSMQ_OK;
+    if (pf.user && !user_ekf) {
+        set_error("filter_masked: no run-time kernel for this pair of user integrands");
+        return SSMQ_E_UNSUPPORTED;
+    }
+    if (user_ekf && (rc = prepare_user_ekf(h_dyn, f_dyn, h_obs, f_obs, pf.gq))) return rc;
+    if ((rc = ensure_ws(robust_ws_bytes(D, Y, ld)))) return rc;
+    return masked_launch_loop(h_dyn, h_obs, pass, mp, cs + pc.steps, g_fc.ws);
+}
+
+extern "C" int ssmq_masked_kernel_name(const ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, const ssmq_transform *h_obs,
+                                       const ssmq_integrand *f_obs, int64_t B, int flags, char *buf, int len) {
+    SSMQ_HANDLE_LOCK(h_dyn, h_obs);
+    if (!h_dyn || !h_obs || !f_dyn || !f_obs || !buf || len <= 0 || B < 0) return SSMQ_E_ARG;
+    int rc = masked_flag_check(flags);
+    if (rc) return rc;
+    PairForms pf;
+    bool user_ekf = false, one_launch = false;
+    if ((rc = innovations_route(h_dyn, f_dyn, h_obs, f_obs, &pf, &user_ekf, &one_launch))) return rc;
+    if ((flags & SSMQ_MASKED_LAUNCH_LOOP) && !pf.user) one_launch = false;
+    const char *name = nullptr;
+    FilterPass query;
+    if ((rc = make_filter_pass(h_dyn, f_dyn, h_obs, f_obs, B, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &query))) return rc;
+    query.name = &name; query.dry_run = true;
+    rc = one_launch ? try_launch_masked(query, MaskedPass{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}) : 0;
+    if (rc < 0) return rc;
+    snprintf(buf, len, "%s", rc == 1 ? name : kMaskedLoopName);
+    return SSMQ_OK;
+}
+
+extern "C" int ssmq_detection_mask_dev(int64_t B, int64_t ld, int T, int Y, const double *p_detect, uint64_t seed, uint64_t traj_offset,
+                                       int per_component, uint32_t *d_mask) {
+    if (B < 0 || ld < B || T < 0 || Y < 1 || Y > SSMQ_MAX_DIM || !p_detect || !d_mask) {
+        set_error("detection_mask: bad argument (1 <= Y <= " + std::to_string(SSMQ_MAX_DIM) + ")");
+        return SSMQ_E_ARG;
+    }
+    for (int i = 0; i < (per_component ? Y : 1); ++i)
+        if (!(p_detect[i] >= 0.0 && p_detect[i] <= 1.0)) {
+            set_error("detection_mask: p_detect must lie in [0, 1]");
+            return SSMQ_E_ARG;
+        }
+    if (int rc = ensure_device()) return rc;
+    if (B == 0 || T == 0) return SSMQ_OK;
+    return launch_detection_mask(B, ld, T, Y, p_detect, seed, traj_offset, per_component ? 1 : 0, d_mask, stream());
+}
+
 // ---- iterated posterior linearisation smoother (include/ssmq.h: ssmq_smoother_iterated_dev) ------------------------------------------
 // The refusals of the innovation scores, then: a pair runs k_ipls_pass<> (a table shape, or a user pair compiled at run time) or is
 // refused - there is no launch-loop route.  Both entry points ask the table by a dry run, before anything is written.

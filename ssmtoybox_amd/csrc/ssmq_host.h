@@ -634,6 +634,24 @@ int rtc_launch_robust(const FilterPass &p, const RobustPass &r);
 size_t robust_ws_bytes(int D, int Y, int64_t ld);
 int robust_launch_loop(ssmq_transform *h_dyn, ssmq_transform *h_obs, const FilterPass &p, const RobustPass &r, const double *tvec, void *ws);
 
+// Masked pass (ssmq_filter_masked.hip, ssmq_filter_masked_dev): the measurement update over the components a bit mask marks as
+// observed, behind a chi-square gate.  The pass is built WITHOUT R, as the robust pass; R [Y*Y] and the gate table [Y+1] travel here
+// (device).  try_launch_masked / rtc_launch_masked / masked_launch_loop: as their robust twins above (ws: robust_ws_bytes()).
+struct MaskedPass {
+    const uint32_t *mask;                     // [T][ld] or null: NaN = missing
+    const double *rr, *gate;
+    uint32_t *used;                           // [T][ld]
+    double *nis, *ll;                         // [T][ld] each
+};
+struct MaskedArgs;                            // ssmq_masked_kernel.h
+MaskedArgs masked_args(const FilterPass &p, const MaskedPass &r);
+int try_launch_masked(const FilterPass &p, const MaskedPass &r);
+int rtc_launch_masked(const FilterPass &p, const MaskedPass &r);
+int masked_launch_loop(ssmq_transform *h_dyn, ssmq_transform *h_obs, const FilterPass &p, const MaskedPass &r, const double *tvec, void *ws);
+// k_detection_mask (ssmq_filter_masked.hip): p_detect host [Y], Y <= SSMQ_MAX_DIM
+int launch_detection_mask(int64_t B, int64_t ld, int T, int Y, const double *p_detect, uint64_t seed, uint64_t traj_offset, int per_component,
+                          uint32_t *d_mask, hipStream_t s);
+
 // Iterated posterior linearisation smoother (ssmq_filter_ipls.hip, ssmq_smoother_iterated_dev): ONE iteration - the forward sweep and
 // the backward sweep - is one launch of k_ipls_pass<> (ssmq_ipls_kernel.h).  The planes of an iteration besides those of the pass
 // (p.fm / p.fP: its filtered moments, p.status: read and written): the linearisation moments it reads (both null: the running

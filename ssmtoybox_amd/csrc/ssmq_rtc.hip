@@ -32,6 +32,7 @@
 #include "ssmq_innovation_kernel.h"
 #include "ssmq_iterated_kernel.h"
 #include "ssmq_robust_kernel.h"
+#include "ssmq_masked_kernel.h"
 #include "ssmq_ipls_kernel.h"
 #include "ssmq_filter_shapes.h"
 #include "ssmq_mc_moments.h"
@@ -356,6 +357,11 @@ std::string robust_expr(int D, int Y, int ND, int NO, int FD, int FO, int form, 
     snprintf(b, sizeof(b), "ssmq::k_robust_loop<%d, %d, %d, %d, %d, %d, %d, %d, %d, 0>", D, Y, ND, NO, FD, FO, form, tp, selo);
     return b;
 }
+std::string masked_expr(int D, int Y, int ND, int NO, int FD, int FO, int form, int tp, int selo) {
+    char b[256];
+    snprintf(b, sizeof(b), "ssmq::k_masked_loop<%d, %d, %d, %d, %d, %d, %d, %d, %d, 0>", D, Y, ND, NO, FD, FO, form, tp, selo);
+    return b;
+}
 std::string ipls_expr(int D, int Y, int ND, int NO, int FD, int FO, int form, int tp, int selo) {
     char b[256];
     snprintf(b, sizeof(b), "ssmq::k_ipls_pass<%d, %d, %d, %d, %d, %d, %d, %d, %d>", D, Y, ND, NO, FD, FO, form, tp, selo);
@@ -557,6 +563,32 @@ int rtc_launch_robust(const FilterPass &p, const RobustPass &r) {
     if (is_user_integrand(p.fd)) a.fd.ttab = nullptr;   // (user integrands evaluate their time dependence themselves)
     if (is_user_integrand(p.fo)) a.fo.ttab = nullptr;
     rc = launch_compiled(expr, "ssmq::RobustArgs", ids, &a, (unsigned)((a.B + kSmallBlock - 1) / kSmallBlock), kSmallBlock, p.s, p.name, false, what);
+    return rc ? rc : 1;
+}
+
+// k_masked_loop<> (ssmq_masked_kernel.h) for a pair with a user member: as rtc_launch_robust
+int rtc_launch_masked(const FilterPass &p, const MaskedPass &r) {
+    std::vector<int> ids;
+    int rc = user_pair_shape(p, &ids);
+    if (rc) return rc;
+    const ssmq_transform *hd = p.hd, *ho = p.ho;
+    const std::string expr = masked_expr(hd->D, ho->E, hd->N, ho->N, p.fd->id, p.fo->id, hd->form, hd->tp_nu > 0.0 ? 1 : 0, 0);
+    const char *what = "k_masked_loop (run-time compiled)";
+    if (p.dry_run) {
+        rc = launch_compiled(expr, "ssmq::MaskedArgs", ids, nullptr, 0, kSmallBlock, p.s, p.name, true, what);
+        return rc ? rc : 1;
+    }
+    MaskedArgs a = masked_args(p, r);
+    for (const ssmq_integrand *f : {p.fd, p.fo}) {
+        const double *tab = f == p.fd ? a.fd.ttab : a.fo.ttab;
+        if (!is_user_integrand(f) && has_time_table(f->id) && !tab) {
+            set_error("run-time compiled masked pass: the time table of built-in integrand " + std::to_string(f->id) + " is missing");
+            return SSMQ_E_ARG;
+        }
+    }
+    if (is_user_integrand(p.fd)) a.fd.ttab = nullptr;   // (user integrands evaluate their time dependence themselves)
+    if (is_user_integrand(p.fo)) a.fo.ttab = nullptr;
+    rc = launch_compiled(expr, "ssmq::MaskedArgs", ids, &a, (unsigned)((a.B + kSmallBlock - 1) / kSmallBlock), kSmallBlock, p.s, p.name, false, what);
     return rc ? rc : 1;
 }
 
@@ -946,14 +978,14 @@ extern "C" int ssmq_rtc_compile_check(int32_t id, int32_t id_obs, int kind, int 
         tp = opt = 0;
     }
     if (!arch || !*arch || (kind != SSMQ_RTC_FILTER && kind != SSMQ_RTC_APPLY && kind != SSMQ_RTC_MC && kind != SSMQ_RTC_INNOVATION && kind != SSMQ_RTC_ITERATED &&
-                            kind != SSMQ_RTC_SMOOTHER_ITERATED && kind != SSMQ_RTC_ROBUST) ||
-        ((kind == SSMQ_RTC_ITERATED || kind == SSMQ_RTC_SMOOTHER_ITERATED || kind == SSMQ_RTC_ROBUST) && opt != 0) || (form != SSMQ_FORM_BQ && form != SSMQ_FORM_SIGMA) ||
+                            kind != SSMQ_RTC_SMOOTHER_ITERATED && kind != SSMQ_RTC_ROBUST && kind != SSMQ_RTC_MASKED) ||
+        ((kind == SSMQ_RTC_ITERATED || kind == SSMQ_RTC_SMOOTHER_ITERATED || kind == SSMQ_RTC_ROBUST || kind == SSMQ_RTC_MASKED) && opt != 0) || (form != SSMQ_FORM_BQ && form != SSMQ_FORM_SIGMA) ||
         tp < 0 || tp > 1 || (opt != 0 && opt != 1 && opt != 2 && opt != 3 && opt != 7)) {
         set_error("ssmq_rtc_compile_check: bad argument");
         return SSMQ_E_ARG;
     }
     const bool pair = kind == SSMQ_RTC_FILTER || kind == SSMQ_RTC_INNOVATION || kind == SSMQ_RTC_ITERATED || kind == SSMQ_RTC_SMOOTHER_ITERATED ||
-                      kind == SSMQ_RTC_ROBUST;      // (id, id_obs): the two models of a filter
+                      kind == SSMQ_RTC_ROBUST || kind == SSMQ_RTC_MASKED;      // (id, id_obs): the two models of a filter
     std::string why;
     if (kind != SSMQ_RTC_MC && (!shape_ok(D, E, N, &why) || (pair && !shape_ok(D, D, N_obs, &why)))) {
         set_error(why);
@@ -972,12 +1004,14 @@ extern "C" int ssmq_rtc_compile_check(int32_t id, int32_t id_obs, int kind, int 
                              : kind == SSMQ_RTC_ITERATED   ? iterated_expr(D, E, N, N_obs, id, id_obs, form, tp, 0)
                              : kind == SSMQ_RTC_SMOOTHER_ITERATED ? ipls_expr(D, E, N, N_obs, id, id_obs, form, tp, 0)
                              : kind == SSMQ_RTC_ROBUST     ? robust_expr(D, E, N, N_obs, id, id_obs, form, tp, 0)
+                             : kind == SSMQ_RTC_MASKED     ? masked_expr(D, E, N, N_obs, id, id_obs, form, tp, 0)
                              : kind == SSMQ_RTC_MC         ? "ssmq::k_mc_moments<" + std::to_string(id) + ", " + std::to_string(D) + ", " + std::to_string(E) + ", 0>"
                                                            : apply_expr(D, E, N, id, form, tp, 0, opt, false);
     return compile_check_text(expr, kind == SSMQ_RTC_FILTER ? "ssmq::FusedArgs" : kind == SSMQ_RTC_INNOVATION ? "ssmq::InnovArgs"
                                     : kind == SSMQ_RTC_ITERATED ? "ssmq::IplfArgs"
                                     : kind == SSMQ_RTC_SMOOTHER_ITERATED ? "ssmq::IplsArgs"
                                     : kind == SSMQ_RTC_ROBUST ? "ssmq::RobustArgs"
+                                    : kind == SSMQ_RTC_MASKED ? "ssmq::MaskedArgs"
                                     : kind == SSMQ_RTC_MC   ? "ssmq::McMomArgs" : "ssmq::ApplyArgs", ids, arch, log, len);
 }
 

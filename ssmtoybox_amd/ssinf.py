@@ -95,6 +95,16 @@ def noise_grid(cov, scales):
     return np.ascontiguousarray(scales[:, None, None] * cov)
 
 
+def gate_thresholds(dim_y, prob):
+    """The gate table of `masked_pass*` from a gate probability: the chi-square quantiles chi2.ppf(prob, o) for o = 1 .. dim_y
+    observed components (SciPy), so that a measurement that fits the filter's model passes the gate with probability `prob`."""
+    from scipy.stats import chi2
+    prob = float(prob)
+    if not 0.0 < prob <= 1.0:
+        raise ValueError('gate_thresholds: prob must lie in (0, 1] (got {!r})'.format(prob))
+    return chi2.ppf(prob, np.arange(1, int(dim_y) + 1))
+
+
 def mode_transition(M, stay):
     """The transition matrix of M modes that keep their mode with probability `stay` and go to each of the others with equal
     probability: (M, M), `stay` on the diagonal and (1 - stay) / (M - 1) off it (M = 1: [[1]])."""
@@ -871,6 +881,125 @@ class GaussianInference:
         out = self.robust_pass_batch(np.asarray(data)[..., None], dof=dof, iterations=iterations, r_scale=r_scale,
                                      return_weights=return_weights)
         return tuple(v[..., 0] for v in out)
+
+    # ---- missing and gated measurements: a bit mask of the observed components per step, a chi-square gate in front of the update ----
+    def _masked_refusal(self, gate):
+        """The gate table [dim_y + 1] of a masked pass (None: no gate), or what keeps a filter or a gate out of it - before the library
+        is touched.  gate: None, a scalar (the threshold for every number of observed components) or a sequence of dim_y thresholds
+        (for o = 1 .. dim_y observed components; `gate_thresholds`); every threshold a positive number or +inf."""
+        self._additive_gauss_only('the masked pass covers')
+        if gate is None:
+            return None
+        Y = self.mod_obs.dim_out
+        g = np.asarray(gate, dtype=np.float64)
+        if g.ndim == 0:
+            g = np.full(Y, float(g))
+        if g.shape != (Y,) or not np.all(g > 0.0):
+            raise ValueError('masked pass: gate must be a positive number (or +inf) or {} of them, for o = 1 .. {} observed components'
+                             .format(Y, Y))
+        return np.ascontiguousarray(np.concatenate(([np.inf], g)))
+
+    def _mask_words(self, mask, Y, T, B):
+        """mask (dim_y, T, B) bool or (T, B) unsigned integers -> (T, B) uint32 words, bit i = component i observed."""
+        m = np.asarray(mask)
+        if m.dtype == np.bool_ and m.shape == (Y, T, B):
+            return (m.astype(np.uint32) << np.arange(Y, dtype=np.uint32)[:, None, None]).sum(axis=0, dtype=np.uint32)
+        if m.dtype.kind == 'u' and m.shape == (T, B):
+            return np.ascontiguousarray(m & np.asarray((1 << Y) - 1, dtype=m.dtype), dtype=np.uint32)
+        raise ValueError('masked pass: mask must be a bool array of shape {} or an unsigned-integer array of shape {} (got {} {})'
+                         .format((Y, T, B), (T, B), m.dtype, m.shape))
+
+    def masked_kernel_name(self, batch=0, launch_loop=False):
+        """Which kernel(s) `masked_pass*` run for this filter: k_masked_loop<..> (the whole pass in one launch) where the fused time
+        loop has an instantiation, and for user models; else the launch loop apply dyn | apply obs | k_masked_update."""
+        self._additive_gauss_only('the masked pass covers')
+        self._check_user_points()
+        return self._kernel_name('ssmq_masked_kernel_name', int(batch), _lib.MASKED_LAUNCH_LOOP if launch_loop else 0)
+
+    def _launch_masked(self, lib, B, ld, T, flags, gate, d_y, d_mask, d_m0, d_P0, d_fm, d_fP, d_used, d_nis, d_ll, d_st):
+        gqg, rr = self._noise()
+        vp, dp = _lib.vp, _lib.dp
+        _lib.check(lib.ssmq_filter_masked_dev(*self._pair(), B, ld, T, flags, vp(d_y), vp(d_mask), vp(d_m0), vp(d_P0), dp(gqg), dp(rr),
+                                              dp(gate), vp(d_fm), vp(d_fP), vp(d_used), vp(d_nis), vp(d_ll), vp(d_st)),
+                   'ssmq_filter_masked_dev')
+
+    def masked_pass_dev(self, d_y, B, ld, T, d_mask=None, gate=None, launch_loop=False):
+        """`forward_pass_dev` with missing and gated measurements: measurements on the device (planes [T][dim_y][ld]), d_mask a
+        DeviceBuffer of uint32 words [T][ld] (bit i: component i observed; what `ssmod.detection_mask_dev` returns) or None: NaN =
+        missing.  Results left on the device - DeviceBuffers (d_fm [T][D][ld], d_fP [T][D*D][ld], d_used [T][ld] uint32, d_nis [T][ld],
+        d_loglik [T][ld], d_status [ld] int32); the caller frees them.  Every trajectory starts from the model's initial moments."""
+        gate = self._masked_refusal(gate)
+        self._check_user_points()
+        lib = _lib.load()
+        D = self.mod_dyn.dim_state
+        with _lib.Staging() as stage:
+            d_m0, d_P0 = self._initial_planes(stage, B, ld)
+            d_fm, d_fP = stage.device(8 * T * D * ld), stage.device(8 * T * D * D * ld)
+            d_used, d_nis, d_ll, d_st = stage.device(4 * T * ld), stage.device(8 * T * ld), stage.device(8 * T * ld), stage.device(4 * ld)
+            self._launch_masked(lib, B, ld, T, _lib.MASKED_LAUNCH_LOOP if launch_loop else 0, gate, d_y, d_mask, d_m0, d_P0, d_fm, d_fP,
+                                d_used, d_nis, d_ll, d_st)
+            _lib.sync()
+            return stage.release(d_fm, d_fP, d_used, d_nis, d_ll, d_st)
+
+    def masked_pass_batch(self, data, mask=None, gate=None, x0_mean=None, x0_cov=None, raise_on_failure=True, return_scores=False,
+                          launch_loop=False):
+        """The forward pass when not every component of y_k arrived, data (dim_y, T, B).  mask (dim_y, T, B) bool, or (T, B) unsigned
+        integers (bit i: component i of y_k was observed); None: a NaN in `data` means not observed.  With o the number of observed
+        components of a step and the subscript o their rows and columns, after the time update of `forward_pass_batch` and one
+        measurement transform at the prior (y^, P_h without noise, C):
+            S = P_h + R;  e = y_k - y^;  d2 = e_o' S_oo^-1 e_o;  ll = -(o log 2 pi + log det S_oo + d2) / 2     (both 0 for o = 0)
+            take = (o > 0) and not (d2 > gate[o])
+            take: K = C_o' S_oo^-1, m = m- + K e_o, P = P- - K S_oo K';  else m = m-, P = P- (bit for bit the prior).
+        The value under a cleared mask bit is never read.  gate: None, one threshold for every o, or dim_y thresholds for o = 1 ..
+        dim_y (`gate_thresholds`).  Returns and sets fi_mean (D, T, B), fi_cov (D, D, T, B) and `status` as the forward pass does;
+        with return_scores a dict: fm, fP, used (dim_y, T, B) bool - the components the update applied, none where nothing was offered
+        or the gate rejected -, nis (T, B) = d2 and loglik (T, B) = ll of the OFFERED components (rejected or not), loglik_total (B,),
+        n_used (B,): the number of components used over the pass, and status.  A trajectory with an observed NaN component, or whose
+        factorisation fails, is NaN from that step on (status = 1 + step).  Neither the weights of the transforms nor the noise of
+        the filter are touched.  launch_loop=True forces the launch-loop route."""
+        gate = self._masked_refusal(gate)
+        data = np.asarray(data, dtype=np.float64)
+        Y, T, B = data.shape
+        words = None if mask is None else self._mask_words(mask, Y, T, B)
+        self._check_user_points()
+        lib = _lib.load()
+        D = self.mod_dyn.dim_state
+        ld = _lib.padded(B)
+        with _lib.Staging() as stage:
+            d_y = stage.scratch(8 * T * Y * ld)
+            _lib.upload_study(data, Y, ld, d_y)
+            d_mask = None
+            if words is not None:
+                planes = np.zeros((T, ld), dtype=np.uint32)
+                planes[:, :B] = words
+                d_mask = stage.scratch(4 * T * ld)
+                d_mask.upload(planes)
+            d_m0, d_P0 = self._initial_planes(stage, B, ld, x0_mean, x0_cov)
+            d_fm, d_fP = stage.scratch(8 * T * D * ld), stage.scratch(8 * T * D * D * ld)
+            d_used, d_nis, d_ll, d_st = stage.scratch(4 * T * ld), stage.scratch(8 * T * ld), stage.scratch(8 * T * ld), stage.scratch(4 * ld)
+            self._launch_masked(lib, B, ld, T, _lib.MASKED_LAUNCH_LOOP if launch_loop else 0, gate, d_y, d_mask, d_m0, d_P0, d_fm, d_fP,
+                                d_used, d_nis, d_ll, d_st)
+            fm = _lib.download_study(d_fm, (D,), T, B, ld)
+            fP = _lib.download_study(d_fP, (D, D), T, B, ld)
+            if return_scores:
+                uw = d_used.download((T, ld), dtype=np.uint32)[:, :B]
+                nis = _lib.download_study(d_nis, (), T, B, ld)
+                ll = _lib.download_study(d_ll, (), T, B, ld)
+            self.status = d_st.download((ld,), dtype=np.int32)[:B]
+        if raise_on_failure:
+            _raise_failed(self.status)
+        self.fi_mean, self.fi_cov = fm, fP
+        if not return_scores:
+            return fm, fP
+        used = ((uw[None, :, :] >> np.arange(Y, dtype=np.uint32)[:, None, None]) & 1).astype(bool)
+        return {'fm': fm, 'fP': fP, 'used': used, 'nis': nis, 'loglik': ll, 'loglik_total': ll.sum(axis=0),
+                'n_used': used.sum(axis=(0, 1)), 'status': self.status}
+
+    def masked_pass(self, data, mask=None, gate=None):
+        """`masked_pass_batch` for one trajectory, data (dim_y, T), mask (dim_y, T) bool or (T,) unsigned integers -> filtered means
+        (D, T), covariances (D, D, T)."""
+        fm, fP = self.masked_pass_batch(np.asarray(data)[..., None], None if mask is None else np.asarray(mask)[..., None], gate)
+        return fm[..., 0], fP[..., 0]
 
     # ---- iterated posterior linearisation smoother (IPLS): forward and backward sweep, re-linearised around the smoothed moments ----
     _IPLS_RANGE = ('the iterated smoother covers the additive-noise Gaussian filters with unscented or spherical-radial point sets '
@@ -2489,7 +2618,8 @@ for _name, _what in (('backward_pass', 'the RTS smoother (backward_pass)'), ('ba
         tuple((n, n) for n in ('innovations', 'innovations_batch', 'innovations_dev', 'innovations_kernel_name', 'iterated_pass',
                                'iterated_pass_batch', 'iterated_pass_dev', 'iterated_kernel_name', 'iterated_smoother',
                                'iterated_smoother_batch', 'iterated_smoother_dev', 'iterated_smoother_kernel_name', 'robust_pass',
-                               'robust_pass_batch', 'robust_pass_dev', 'robust_kernel_name')):
+                               'robust_pass_batch', 'robust_pass_dev', 'robust_kernel_name', 'masked_pass', 'masked_pass_batch',
+                               'masked_pass_dev', 'masked_kernel_name')):
     setattr(BootstrapParticleFilter, _name, _refusing(_name, _what))
 
 

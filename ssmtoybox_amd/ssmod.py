@@ -209,6 +209,22 @@ def simulate_dev(dyn, obs, steps, mc_sims, seed=0, traj_offset=0, continuous_dt=
     return d_x, d_y, ld
 
 
+def detection_mask_dev(B, ld, T, dim_y, p_detect, seed=0, traj_offset=0, per_component=True):
+    """Detection masks for `GaussianInference.masked_pass_dev` drawn on the device: a DeviceBuffer of uint32 words [T][ld] (the caller
+    frees it), bit i of word (k, b) set iff u < p_detect[i] with u uniform in (0, 1) from Philox4x32-10 - a pure function of (seed,
+    traj_offset + b, k, i), so a sharded study draws the bits of the single-device one.  p_detect: one probability for all components
+    or dim_y of them.  per_component=False: one draw per (k, b) against p_detect[0], all dim_y bits together (a scan is detected or it
+    is not)."""
+    p = np.ascontiguousarray(np.broadcast_to(np.asarray(p_detect, dtype=np.float64), (int(dim_y),)))
+    if not np.all((p >= 0.0) & (p <= 1.0)):
+        raise ValueError('detection_mask_dev: p_detect must lie in [0, 1]')
+    lib = _lib.load()
+    d_mask = _lib.DeviceBuffer(4 * T * ld)
+    _lib.check(lib.ssmq_detection_mask_dev(B, ld, T, int(dim_y), _lib.dp(p), int(seed), int(traj_offset), 1 if per_component else 0,
+                                           ctypes.c_void_p(d_mask.ptr)), 'ssmq_detection_mask_dev')
+    return d_mask
+
+
 class TransitionModel:
     """x_{k+1} = f(x_k, q_k, k)   (ssmod.py:10-244)."""
     dim_state = None
