@@ -743,83 +743,14 @@ extern "C" int ssmq_innovations_kernel_name(const ssmq_transform *h_dyn, const s
     return SSMQ_OK;
 }
 
-// ---- iterated posterior linearisation pass (include/ssmq.h: ssmq_filter_iterated_dev) ------------------------------------------------
-// The refusals and the route choice are those of the innovation scores (innovations_route); flag bit 0 forces the launch loop.
+// ---- the measurement-update variants: iterated posterior linearisation, outlier-robust, masked (include/ssmq.h) ------------------------
+// The refusals and the route choice are those of the innovation scores (innovations_route); flag bit 0 forces the launch loop.  Each
+// entry point keeps its null checks, its argument checks and its constants; what follows them is update_pass_dev / update_kernel_name.
 static const char kIplfLoopName[] = "launch loop of (1 + 2 J) T launches (apply dyn | J x (apply obs | k_iplf_update))";
-static bool iterations_ok(int iterations) {
-    if (iterations >= 1 && iterations <= SSMQ_ITERATED_MAX) return true;
-    set_error("filter_iterated: 1 <= iterations <= " + std::to_string(SSMQ_ITERATED_MAX));
-    return false;
-}
-
-extern "C" int ssmq_filter_iterated_dev(ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, ssmq_transform *h_obs,
-                                        const ssmq_integrand *f_obs, int64_t B, int64_t ld, int T, int iterations, int flags,
-                                        const double *d_y, const double *d_m0, const double *d_P0, const double *GQG, const double *R,
-                                        double *d_fm, double *d_fP, double *d_delta, int32_t *d_status) {
-    SSMQ_HANDLE_LOCK(h_dyn, h_obs);
-    if (!h_dyn || !h_obs || !f_dyn || !f_obs || B < 0 || ld < B || T < 0 || !d_y || !d_m0 || !d_P0 || !d_fm || !d_fP || !d_status ||
-        (flags & ~1)) {
-        set_error("filter_iterated: bad argument");
-        return SSMQ_E_ARG;
-    }
-    if (!iterations_ok(iterations)) return SSMQ_E_ARG;
-    PairForms pf;
-    bool user_ekf = false, one_launch = false;
-    int rc = innovations_route(h_dyn, f_dyn, h_obs, f_obs, &pf, &user_ekf, &one_launch);
-    if (rc) return rc;
-    if ((flags & 1) && !pf.user) one_launch = false;      // (a user pair without Jacobians has no launch loop)
-    const int D = h_dyn->D, Y = h_obs->E;
-    if ((rc = ensure_device())) return rc;
-    if (B == 0) return SSMQ_OK;
-    hipStream_t s = stream();
-    if (T == 0) {   // nothing to filter: every trajectory is trivially fine
-        SSMQ_HIP(hipMemsetAsync(d_status, 0, sizeof(int32_t) * ld, s));
-        return SSMQ_OK;
-    }
-    FilterPass pass;
-    PassConsts pc;
-    if ((rc = make_filter_pass(h_dyn, f_dyn, h_obs, f_obs, B, ld, T, d_y, d_m0, d_P0, d_fm, d_fP, d_status, s, &pass)) ||
-        (rc = cached_pass_consts(f_dyn, f_obs, D, Y, T, GQG, R, nullptr, s, &pc)))
-        return rc;
-    const double *cs = (const double *)g_fc.consts;
-    wire_pass_consts(pass, cs, pc);
-    rc = one_launch ? try_launch_iterated(pass, iterations, d_delta) : 0;
-    if (rc < 0) return rc;
-    if (rc == 1) return SSMQ_OK;
-    if (pf.user && !user_ekf) {
-        set_error("filter_iterated: no run-time kernel for this pair of user integrands");
-        return SSMQ_E_UNSUPPORTED;
-    }
-    if (user_ekf && (rc = prepare_user_ekf(h_dyn, f_dyn, h_obs, f_obs, pf.gq))) return rc;
-    if ((rc = ensure_ws(iterated_ws_bytes(D, Y, ld)))) return rc;
-    return iterated_launch_loop(h_dyn, h_obs, pass, iterations, d_delta, cs + pc.steps, g_fc.ws);
-}
-
-extern "C" int ssmq_iterated_kernel_name(const ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, const ssmq_transform *h_obs,
-                                         const ssmq_integrand *f_obs, int64_t B, int iterations, int flags, char *buf, int len) {
-    SSMQ_HANDLE_LOCK(h_dyn, h_obs);
-    if (!h_dyn || !h_obs || !f_dyn || !f_obs || !buf || len <= 0 || B < 0 || (flags & ~1)) return SSMQ_E_ARG;
-    if (!iterations_ok(iterations)) return SSMQ_E_ARG;
-    PairForms pf;
-    bool user_ekf = false, one_launch = false;
-    int rc = innovations_route(h_dyn, f_dyn, h_obs, f_obs, &pf, &user_ekf, &one_launch);
-    if (rc) return rc;
-    if ((flags & 1) && !pf.user) one_launch = false;
-    const char *name = nullptr;
-    FilterPass query;
-    if ((rc = make_filter_pass(h_dyn, f_dyn, h_obs, f_obs, B, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &query))) return rc;
-    query.name = &name; query.dry_run = true;
-    rc = one_launch ? try_launch_iterated(query, iterations, nullptr) : 0;
-    if (rc < 0) return rc;
-    snprintf(buf, len, "%s", rc == 1 ? name : kIplfLoopName);
-    return SSMQ_OK;
-}
-
-// ---- outlier-robust pass (include/ssmq.h: ssmq_filter_robust_dev) ---------------------------------------------------------------------
-// The refusals and the route choice are those of the innovation scores (innovations_route); flag bit 0 forces the launch loop.
 static const char kRobustLoopName[] = "launch loop of 3 T launches (apply dyn | apply obs | k_robust_update)";
+static const char kMaskedLoopName[] = "launch loop of 3 T launches (apply dyn | apply obs | k_masked_update)";
 
-// R | R^-1 as the host image of the context's block: false when R is not finite, not symmetric or not positive definite.  The
+// R | R^-1 as the host image of the variants' block of the context: false when R is not finite, not symmetric or not positive definite.  The
 // inverse by Cholesky, R = L L': column j of R^-1 from L z = e_j, L' x = z; symmetrised by its lower triangle (the kernels read that).
 static bool robust_consts(int Y, const double *R, std::vector<double> *out) {
     std::vector<double> L((size_t)Y * Y, 0.0), h(2 * (size_t)Y * Y, 0.0), v(Y);
@@ -879,6 +810,123 @@ static int cached_robust_consts(std::vector<double> &h, hipStream_t s) {
     return SSMQ_OK;
 }
 
+// The pass after the entry point's own checks.  PassIO: the planes and sizes every entry point takes.  UpdateVariant: what differs -
+// who: the prefix of its errors; R_pass: what the measurement transform adds (R, or null: zeros); consts(Y, &host): the variant's own
+// device block (R | R^-1, R | gate; left empty: none) or an error, checked where the entry points always checked it - after the
+// route, before the device; try_launch(pass, block), loop(pass, block, tvec, ws): the variant's two routes, block = that block on
+// the device (the iterated pass has none and ignores it).
+struct PassIO {
+    int64_t B, ld;
+    int T;
+    const double *d_y, *d_m0, *d_P0, *GQG;
+    double *d_fm, *d_fP;
+    int32_t *d_status;
+};
+template <class Consts, class Try, class Loop>
+struct UpdateVariant {
+    const char *who;
+    const double *R_pass;
+    Consts consts;       // int(int Y, std::vector<double> *host)
+    Try try_launch;      // int(const FilterPass &pass, const double *block)
+    Loop loop;           // int(const FilterPass &pass, const double *block, const double *tvec, void *ws)
+};
+template <class Consts, class Try, class Loop>
+static UpdateVariant<Consts, Try, Loop> update_variant(const char *who, const double *R_pass, Consts consts, Try try_launch, Loop loop) {
+    return {who, R_pass, consts, try_launch, loop};
+}
+template <class Variant>
+static int update_pass_dev(ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, ssmq_transform *h_obs, const ssmq_integrand *f_obs,
+                           const PassIO &io, bool force_loop, const Variant &v) {
+    const int64_t B = io.B, ld = io.ld;
+    const int T = io.T;
+    PairForms pf;
+    bool user_ekf = false, one_launch = false;
+    int rc = innovations_route(h_dyn, f_dyn, h_obs, f_obs, &pf, &user_ekf, &one_launch);
+    if (rc) return rc;
+    if (force_loop && !pf.user) one_launch = false;      // (a user pair without Jacobians has no launch loop)
+    const int D = h_dyn->D, Y = h_obs->E;
+    std::vector<double> host;
+    if ((rc = v.consts(Y, &host))) return rc;
+    if ((rc = ensure_device())) return rc;
+    if (B == 0) return SSMQ_OK;
+    hipStream_t s = stream();
+    if (T == 0) {   // nothing to filter: every trajectory is trivially fine
+        SSMQ_HIP(hipMemsetAsync(io.d_status, 0, sizeof(int32_t) * ld, s));
+        return SSMQ_OK;
+    }
+    FilterPass pass;
+    PassConsts pc;
+    // (one image of the variants' block at a time, uploaded when it differs from what the block holds)
+    if ((rc = make_filter_pass(h_dyn, f_dyn, h_obs, f_obs, B, ld, T, io.d_y, io.d_m0, io.d_P0, io.d_fm, io.d_fP, io.d_status, s, &pass)) ||
+        (rc = cached_pass_consts(f_dyn, f_obs, D, Y, T, io.GQG, v.R_pass, nullptr, s, &pc)) || (!host.empty() && (rc = cached_robust_consts(host, s))))
+        return rc;
+    const double *cs = (const double *)g_fc.consts, *block = (const double *)g_fc.robust;
+    wire_pass_consts(pass, cs, pc);
+    rc = one_launch ? v.try_launch(pass, block) : 0;
+    if (rc < 0) return rc;
+    if (rc == 1) return SSMQ_OK;
+    if (pf.user && !user_ekf) {
+        set_error(std::string(v.who) + ": no run-time kernel for this pair of user integrands");
+        return SSMQ_E_UNSUPPORTED;
+    }
+    if (user_ekf && (rc = prepare_user_ekf(h_dyn, f_dyn, h_obs, f_obs, pf.gq))) return rc;
+    if ((rc = ensure_ws(update_ws_bytes(D, Y, ld)))) return rc;
+    return v.loop(pass, block, cs + pc.steps, g_fc.ws);
+}
+
+// The name of what update_pass_dev would run: try_launch(query) on a dry-run pass, else the launch loop's
+template <class Try>
+static int update_kernel_name(const ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, const ssmq_transform *h_obs, const ssmq_integrand *f_obs,
+                              int64_t B, bool force_loop, const char *loop_name, char *buf, int len, Try try_launch) {
+    PairForms pf;
+    bool user_ekf = false, one_launch = false;
+    int rc = innovations_route(h_dyn, f_dyn, h_obs, f_obs, &pf, &user_ekf, &one_launch);
+    if (rc) return rc;
+    if (force_loop && !pf.user) one_launch = false;
+    const char *name = nullptr;
+    FilterPass query;
+    if ((rc = make_filter_pass(h_dyn, f_dyn, h_obs, f_obs, B, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &query))) return rc;
+    query.name = &name; query.dry_run = true;
+    rc = one_launch ? try_launch(query) : 0;
+    if (rc < 0) return rc;
+    snprintf(buf, len, "%s", rc == 1 ? name : loop_name);
+    return SSMQ_OK;
+}
+
+static bool iterations_ok(int iterations) {
+    if (iterations >= 1 && iterations <= SSMQ_ITERATED_MAX) return true;
+    set_error("filter_iterated: 1 <= iterations <= " + std::to_string(SSMQ_ITERATED_MAX));
+    return false;
+}
+
+extern "C" int ssmq_filter_iterated_dev(ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, ssmq_transform *h_obs,
+                                        const ssmq_integrand *f_obs, int64_t B, int64_t ld, int T, int iterations, int flags,
+                                        const double *d_y, const double *d_m0, const double *d_P0, const double *GQG, const double *R,
+                                        double *d_fm, double *d_fP, double *d_delta, int32_t *d_status) {
+    SSMQ_HANDLE_LOCK(h_dyn, h_obs);
+    if (!h_dyn || !h_obs || !f_dyn || !f_obs || B < 0 || ld < B || T < 0 || !d_y || !d_m0 || !d_P0 || !d_fm || !d_fP || !d_status ||
+        (flags & ~1)) {
+        set_error("filter_iterated: bad argument");
+        return SSMQ_E_ARG;
+    }
+    if (!iterations_ok(iterations)) return SSMQ_E_ARG;
+    const IplfPass ip{iterations, d_delta};
+    auto consts = [](int, std::vector<double> *) { return SSMQ_OK; };
+    auto try_launch = [&](const FilterPass &pass, const double *) { return try_launch_iterated(pass, ip); };
+    auto loop = [&](const FilterPass &pass, const double *, const double *tvec, void *ws) { return iterated_launch_loop(h_dyn, h_obs, pass, ip, tvec, ws); };
+    return update_pass_dev(h_dyn, f_dyn, h_obs, f_obs, PassIO{B, ld, T, d_y, d_m0, d_P0, GQG, d_fm, d_fP, d_status}, flags & 1,
+                           update_variant("filter_iterated", R, consts, try_launch, loop));
+}
+
+extern "C" int ssmq_iterated_kernel_name(const ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, const ssmq_transform *h_obs,
+                                         const ssmq_integrand *f_obs, int64_t B, int iterations, int flags, char *buf, int len) {
+    SSMQ_HANDLE_LOCK(h_dyn, h_obs);
+    if (!h_dyn || !h_obs || !f_dyn || !f_obs || !buf || len <= 0 || B < 0 || (flags & ~1)) return SSMQ_E_ARG;
+    if (!iterations_ok(iterations)) return SSMQ_E_ARG;
+    return update_kernel_name(h_dyn, f_dyn, h_obs, f_obs, B, flags & 1, kIplfLoopName, buf, len,
+                              [&](const FilterPass &q) { return try_launch_iterated(q, IplfPass{iterations, nullptr}); });
+}
+
 // the argument checks both entry points share, after the null checks; R may be null for the name query
 static int robust_arg_checks(int iterations, int flags, double dof) {
     if (flags & ~SSMQ_ROBUST_LAUNCH_LOOP) {
@@ -908,42 +956,18 @@ extern "C" int ssmq_filter_robust_dev(ssmq_transform *h_dyn, const ssmq_integran
     }
     int rc = robust_arg_checks(iterations, flags, dof);
     if (rc) return rc;
-    PairForms pf;
-    bool user_ekf = false, one_launch = false;
-    if ((rc = innovations_route(h_dyn, f_dyn, h_obs, f_obs, &pf, &user_ekf, &one_launch))) return rc;
-    if ((flags & SSMQ_ROBUST_LAUNCH_LOOP) && !pf.user) one_launch = false;      // (a user pair without Jacobians has no launch loop)
-    const int D = h_dyn->D, Y = h_obs->E;
-    std::vector<double> rh;
-    if (!robust_consts(Y, R, &rh)) {
+    const size_t YY = (size_t)h_obs->E * h_obs->E;
+    // (the pass's constants without R: its rr block is the zeros the measurement transform adds)
+    auto rp = [&](const double *rb) { return RobustPass{iterations, dof, rb, rb + YY, d_lam, d_delta}; };
+    auto consts = [&](int Y, std::vector<double> *h) {
+        if (robust_consts(Y, R, h)) return SSMQ_OK;
         set_error("filter_robust: R must be a finite symmetric positive definite matrix");
         return SSMQ_E_ARG;
-    }
-    if ((rc = ensure_device())) return rc;
-    if (B == 0) return SSMQ_OK;
-    hipStream_t s = stream();
-    if (T == 0) {   // nothing to filter: every trajectory is trivially fine
-        SSMQ_HIP(hipMemsetAsync(d_status, 0, sizeof(int32_t) * ld, s));
-        return SSMQ_OK;
-    }
-    FilterPass pass;
-    PassConsts pc;
-    // (the pass's constants without R: its rr block is the zeros the measurement transform adds)
-    if ((rc = make_filter_pass(h_dyn, f_dyn, h_obs, f_obs, B, ld, T, d_y, d_m0, d_P0, d_fm, d_fP, d_status, s, &pass)) ||
-        (rc = cached_pass_consts(f_dyn, f_obs, D, Y, T, GQG, nullptr, nullptr, s, &pc)) || (rc = cached_robust_consts(rh, s)))
-        return rc;
-    const double *cs = (const double *)g_fc.consts, *rb = (const double *)g_fc.robust;
-    wire_pass_consts(pass, cs, pc);
-    const RobustPass rp{iterations, dof, rb, rb + (size_t)Y * Y, d_lam, d_delta};
-    rc = one_launch ? try_launch_robust(pass, rp) : 0;
-    if (rc < 0) return rc;
-    if (rc == 1) return SSMQ_OK;
-    if (pf.user && !user_ekf) {
-        set_error("filter_robust: no run-time kernel for this pair of user integrands");
-        return SSMQ_E_UNSUPPORTED;
-    }
-    if (user_ekf && (rc = prepare_user_ekf(h_dyn, f_dyn, h_obs, f_obs, pf.gq))) return rc;
-    if ((rc = ensure_ws(robust_ws_bytes(D, Y, ld)))) return rc;
-    return robust_launch_loop(h_dyn, h_obs, pass, rp, cs + pc.steps, g_fc.ws);
+    };
+    auto try_launch = [&](const FilterPass &pass, const double *rb) { return try_launch_robust(pass, rp(rb)); };
+    auto loop = [&](const FilterPass &pass, const double *rb, const double *tvec, void *ws) { return robust_launch_loop(h_dyn, h_obs, pass, rp(rb), tvec, ws); };
+    return update_pass_dev(h_dyn, f_dyn, h_obs, f_obs, PassIO{B, ld, T, d_y, d_m0, d_P0, GQG, d_fm, d_fP, d_status}, flags & SSMQ_ROBUST_LAUNCH_LOOP,
+                           update_variant("filter_robust", nullptr, consts, try_launch, loop));
 }
 
 extern "C" int ssmq_robust_kernel_name(const ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, const ssmq_transform *h_obs,
@@ -952,23 +976,10 @@ extern "C" int ssmq_robust_kernel_name(const ssmq_transform *h_dyn, const ssmq_i
     if (!h_dyn || !h_obs || !f_dyn || !f_obs || !buf || len <= 0 || B < 0) return SSMQ_E_ARG;
     int rc = robust_arg_checks(iterations, flags, 1.0);
     if (rc) return rc;
-    PairForms pf;
-    bool user_ekf = false, one_launch = false;
-    if ((rc = innovations_route(h_dyn, f_dyn, h_obs, f_obs, &pf, &user_ekf, &one_launch))) return rc;
-    if ((flags & SSMQ_ROBUST_LAUNCH_LOOP) && !pf.user) one_launch = false;
-    const char *name = nullptr;
-    FilterPass query;
-    if ((rc = make_filter_pass(h_dyn, f_dyn, h_obs, f_obs, B, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &query))) return rc;
-    query.name = &name; query.dry_run = true;
-    rc = one_launch ? try_launch_robust(query, RobustPass{iterations, 1.0, nullptr, nullptr, nullptr, nullptr}) : 0;
-    if (rc < 0) return rc;
-    snprintf(buf, len, "%s", rc == 1 ? name : kRobustLoopName);
-    return SSMQ_OK;
+    return update_kernel_name(h_dyn, f_dyn, h_obs, f_obs, B, flags & SSMQ_ROBUST_LAUNCH_LOOP, kRobustLoopName, buf, len, [&](const FilterPass &q) {
+        return try_launch_robust(q, RobustPass{iterations, 1.0, nullptr, nullptr, nullptr, nullptr});
+    });
 }
-
-// ---- masked pass (include/ssmq.h: ssmq_filter_masked_dev) -------------------------------------------------------------------------------
-// The refusals and the route choice are those of the innovation scores (innovations_route); flag bit 0 forces the launch loop.
-static const char kMaskedLoopName[] = "launch loop of 3 T launches (apply dyn | apply obs | k_masked_update)";
 
 // R | gate as the host image of a device block ([Y*Y] | [Y+1]; gate null: +inf everywhere): false, with the error set, when R is
 // not finite or not symmetric or a gate entry 1 .. Y is not a positive number or +inf
@@ -1013,40 +1024,14 @@ extern "C" int ssmq_filter_masked_dev(ssmq_transform *h_dyn, const ssmq_integran
     }
     int rc = masked_flag_check(flags);
     if (rc) return rc;
-    PairForms pf;
-    bool user_ekf = false, one_launch = false;
-    if ((rc = innovations_route(h_dyn, f_dyn, h_obs, f_obs, &pf, &user_ekf, &one_launch))) return rc;
-    if ((flags & SSMQ_MASKED_LAUNCH_LOOP) && !pf.user) one_launch = false;      // (a user pair without Jacobians has no launch loop)
-    const int D = h_dyn->D, Y = h_obs->E;
-    std::vector<double> mh;
-    if (!masked_consts(Y, R, gate, &mh)) return SSMQ_E_ARG;
-    if ((rc = ensure_device())) return rc;
-    if (B == 0) return SSMQ_OK;
-    hipStream_t s = stream();
-    if (T == 0) {   // nothing to filter: every trajectory is trivially fine
-        SSMQ_HIP(hipMemsetAsync(d_status, 0, sizeof(int32_t) * ld, s));
-        return SSMQ_OK;
-    }
-    FilterPass pass;
-    PassConsts pc;
-    // (the pass's constants without R: its rr block is the zeros the measurement transform adds; R | gate in the block the robust
-    // pass keeps its R | R^-1 in - one image at a time, uploaded when it differs from what the block holds)
-    if ((rc = make_filter_pass(h_dyn, f_dyn, h_obs, f_obs, B, ld, T, d_y, d_m0, d_P0, d_fm, d_fP, d_status, s, &pass)) ||
-        (rc = cached_pass_consts(f_dyn, f_obs, D, Y, T, GQG, nullptr, nullptr, s, &pc)) || (rc = cached_robust_consts(mh, s)))
-        return rc;
-    const double *cs = (const double *)g_fc.consts, *rb = (const double *)g_fc.robust;
-    wire_pass_consts(pass, cs, pc);
-    const MaskedPass mp{d_mask, rb, rb + (size_t)Y * Y, d_used, d_nis, d_loglik};
-    rc = one_launch ? try_launch_masked(pass, mp) : 0;
-    if (rc < 0) return rc;
-    if (rc == 1) return SSMQ_OK;
-    if (pf.user && !user_ekf) {
-        set_error("filter_masked: no run-time kernel for this pair of user integrands");
-        return SSMQ_E_UNSUPPORTED;
-    }
-    if (user_ekf && (rc = prepare_user_ekf(h_dyn, f_dyn, h_obs, f_obs, pf.gq))) return rc;
-    if ((rc = ensure_ws(robust_ws_bytes(D, Y, ld)))) return rc;
-    return masked_launch_loop(h_dyn, h_obs, pass, mp, cs + pc.steps, g_fc.ws);
+    const size_t YY = (size_t)h_obs->E * h_obs->E;
+    // (the pass's constants without R, as the robust pass; R | gate in the variants' block)
+    auto mp = [&](const double *rb) { return MaskedPass{d_mask, rb, rb + YY, d_used, d_nis, d_loglik}; };
+    auto consts = [&](int Y, std::vector<double> *h) { return masked_consts(Y, R, gate, h) ? SSMQ_OK : SSMQ_E_ARG; };
+    auto try_launch = [&](const FilterPass &pass, const double *rb) { return try_launch_masked(pass, mp(rb)); };
+    auto loop = [&](const FilterPass &pass, const double *rb, const double *tvec, void *ws) { return masked_launch_loop(h_dyn, h_obs, pass, mp(rb), tvec, ws); };
+    return update_pass_dev(h_dyn, f_dyn, h_obs, f_obs, PassIO{B, ld, T, d_y, d_m0, d_P0, GQG, d_fm, d_fP, d_status}, flags & SSMQ_MASKED_LAUNCH_LOOP,
+                           update_variant("filter_masked", nullptr, consts, try_launch, loop));
 }
 
 extern "C" int ssmq_masked_kernel_name(const ssmq_transform *h_dyn, const ssmq_integrand *f_dyn, const ssmq_transform *h_obs,
@@ -1055,18 +1040,9 @@ extern "C" int ssmq_masked_kernel_name(const ssmq_transform *h_dyn, const ssmq_i
     if (!h_dyn || !h_obs || !f_dyn || !f_obs || !buf || len <= 0 || B < 0) return SSMQ_E_ARG;
     int rc = masked_flag_check(flags);
     if (rc) return rc;
-    PairForms pf;
-    bool user_ekf = false, one_launch = false;
-    if ((rc = innovations_route(h_dyn, f_dyn, h_obs, f_obs, &pf, &user_ekf, &one_launch))) return rc;
-    if ((flags & SSMQ_MASKED_LAUNCH_LOOP) && !pf.user) one_launch = false;
-    const char *name = nullptr;
-    FilterPass query;
-    if ((rc = make_filter_pass(h_dyn, f_dyn, h_obs, f_obs, B, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &query))) return rc;
-    query.name = &name; query.dry_run = true;
-    rc = one_launch ? try_launch_masked(query, MaskedPass{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}) : 0;
-    if (rc < 0) return rc;
-    snprintf(buf, len, "%s", rc == 1 ? name : kMaskedLoopName);
-    return SSMQ_OK;
+    return update_kernel_name(h_dyn, f_dyn, h_obs, f_obs, B, flags & SSMQ_MASKED_LAUNCH_LOOP, kMaskedLoopName, buf, len, [&](const FilterPass &q) {
+        return try_launch_masked(q, MaskedPass{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr});
+    });
 }
 
 extern "C" int ssmq_detection_mask_dev(int64_t B, int64_t ld, int T, int Y, const double *p_detect, uint64_t seed, uint64_t traj_offset,

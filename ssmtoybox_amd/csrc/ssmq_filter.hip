@@ -4,6 +4,7 @@
 // only its lower triangle (LAPACK 'L').  SoA planes, pitch ld.
 #include "ssmq_host.h"
 #include "ssmq_update.h"
+#include "ssmq_filter_shapes.h"
 
 namespace ssmq {
 
@@ -35,20 +36,8 @@ int launch_kalman_update_ex(int D, int Y, int64_t B, int64_t ld, const double *m
                             int step, hipStream_t s, double student_dof, double *smat_out, int Dx) {
     UpdArgs a{m_pr, P_pr, y_mean, P_y, P_yx, y, m_fi, P_fi, status, st_a, st_b, B, ld, step, D, Y, student_dof, smat_out,
               Dx > 0 ? Dx : D};
-#define SSMQ_UPD(d, y_)                  \
-    if (D == d && Y == y_) {             \
-        launch_upd<d, y_>(a, s);         \
-        return hip_fail(hipGetLastError(), "k_kalman_update"); \
-    }
-    SSMQ_UPD(1, 1)
-    SSMQ_UPD(2, 1)
-    SSMQ_UPD(2, 2)
-    SSMQ_UPD(3, 1)
-    SSMQ_UPD(4, 2)
-    SSMQ_UPD(5, 2)
-    SSMQ_UPD(5, 4)
-    SSMQ_UPD(6, 2)
-#undef SSMQ_UPD
+    if (for_update_pair(D, Y, [&](auto d, auto y) { launch_upd<decltype(d)::value, decltype(y)::value>(a, s); }))
+        return hip_fail(hipGetLastError(), "k_kalman_update");
     if (D > SSMQ_MAX_DIM || Y > SSMQ_MAX_DIM) {
         set_error("kalman update: D or Y above SSMQ_MAX_DIM");
         return SSMQ_E_UNSUPPORTED;
@@ -63,6 +52,47 @@ int launch_kalman_update(int D, int Y, int64_t B, int64_t ld, const double *m_pr
                          double *P_fi, int32_t *status, hipStream_t s) {
     return launch_kalman_update_ex(D, Y, B, ld, m_pr, P_pr, y_mean, P_y, P_yx, y, m_fi, P_fi, status, nullptr, nullptr,
                                    0, s, 0.0, nullptr, 0);
+}
+
+// ---- what the measurement-update variants share on the host (ssmq_host.h) ----------------------------------------------------------
+// the planes of the launch loop: m_pr | P_pr | C_xx | y_mean | P_y | P_yx | m_it | P_it | two status planes
+size_t update_ws_bytes(int D, int Y, int64_t ld) {
+    return sizeof(double) * (size_t)ld * (2 * D + 3 * D * D + Y + Y * Y + Y * D) + 2 * sizeof(int32_t) * (size_t)ld;
+}
+
+int update_launch_loop(ssmq_transform *h_dyn, ssmq_transform *h_obs, const FilterPass &p, int napply, const double *tvec, void *ws,
+                       const std::function<int(const ItemPlanes &c, bool last)> &item) {
+    const int D = h_dyn->D, Y = h_obs->E;
+    const int64_t B = p.B, ld = p.ld;
+    double *w = (double *)ws;
+    double *m_pr = w; w += (size_t)ld * D;
+    double *P_pr = w; w += (size_t)ld * D * D;
+    double *C_xx = w; w += (size_t)ld * D * D;
+    double *y_mean = w; w += (size_t)ld * Y;
+    double *P_y = w; w += (size_t)ld * Y * Y;
+    double *P_yx = w; w += (size_t)ld * Y * D;
+    double *m_it = w; w += (size_t)ld * D;
+    double *P_it = w; w += (size_t)ld * D * D;
+    int32_t *st_a = (int32_t *)w, *st_b = st_a + ld;
+    int rc = hip_fail(hipMemsetAsync(p.status, 0, sizeof(int32_t) * ld, p.s), "hipMemsetAsync");
+    for (int k = 0; k < p.T && !rc; ++k) {
+        const double *m_in = k == 0 ? p.m0 : p.fm + (int64_t)(k - 1) * D * ld;
+        const double *P_in = k == 0 ? p.P0 : p.fP + (int64_t)(k - 1) * D * D * ld;
+        rc = apply_dev_impl(h_dyn, p.fd, B, ld, m_in, P_in, tvec + k, 0, m_pr, P_pr, C_xx, st_a, p.gqg, nullptr, false, 1.0, 1.0,
+                            p.ttab_dyn, false);
+        for (int i = 0; i < napply && !rc; ++i) {
+            const bool last = i == napply - 1;
+            const double *m_at = i == 0 ? m_pr : m_it, *P_at = i == 0 ? P_pr : P_it;
+            // (p.rr: what the pass was built with - R, or zeros: P_y is then P_h)
+            rc = apply_dev_impl(h_obs, p.fo, B, ld, m_at, P_at, tvec + k, 0, y_mean, P_y, P_yx, st_b, p.rr, nullptr, false, 1.0, 1.0,
+                                p.ttab_obs, false);
+            if (rc) break;
+            const ItemPlanes c{m_pr, P_pr, m_at, P_at, y_mean, P_y, P_yx, p.y + (int64_t)k * Y * ld, last ? p.fm + (int64_t)k * D * ld : m_it,
+                               last ? p.fP + (int64_t)k * D * D * ld : P_it, p.status, st_a, st_b, B, ld, k, D, Y};
+            rc = item(c, last);
+        }
+    }
+    return rc;
 }
 
 

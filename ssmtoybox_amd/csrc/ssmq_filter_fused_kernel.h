@@ -31,6 +31,11 @@ namespace ssmq {
 #define SSMQ_FUSED_OCC_D5_SIGMA 1   // waves per SIMD for the centred D = 5 kernels: 276 registers unconstrained; held to 256
                                     // (2 waves) 20 of them spill and the UKF pass is 2-3 % slower (round 3, tools/build_variant.sh)
 #endif
+// Launch bounds of a whole-pass kernel, one trajectory per lane (k_iplf_loop<>, k_robust_loop<>, k_masked_loop<>, k_ipls_pass<>):
+// those of k_filter_fused<> of the same shape
+#define SSMQ_PASS_LAUNCH_BOUNDS(D, FORM)                                        \
+    __launch_bounds__(kSmallBlock, (SSMQ_FUSED_FORCE_OCC ? SSMQ_FUSED_FORCE_OCC \
+                                    : ((D) >= 6 ? 1 : (((D) >= 5 && (FORM) == SSMQ_FORM_SIGMA) ? SSMQ_FUSED_OCC_D5_SIGMA : 2))))
 // One pass over the steps k_begin ... k_end - 1 of the wave's trajectories (block `blk` of a.lpw trajectories).  The whole filter is
 // the pass (0, T, first, last); CHUNKED passes (ssmq_filter_chunked.hip) start from the state - mean, lower triangle of the
 // covariance, status word: what the registers held, bit for bit - that the previous pass of the block left in a.hand.

@@ -50,7 +50,10 @@ IplsArgs ipls_args(const FilterPass &p, const IplsPlanes &q) {
 
 // One iteration.  1: launched (dry run: a kernel exists, its name set), 0: no kernel for this pair, < 0: error
 int try_launch_ipls(const FilterPass &p, const IplsPlanes &q) {
-    if (is_user_integrand(p.fd) || is_user_integrand(p.fo)) return rtc_launch_ipls(p, q);
+    if (is_user_integrand(p.fd) || is_user_integrand(p.fo)) {
+        IplsArgs a = ipls_args(p, q);
+        return rtc_launch_pass(p, SSMQ_RTC_SMOOTHER_ITERATED, &a, &a.fd, &a.fo, a.B);
+    }
     if (!same_family(p)) return 0;
     for (const IplsEntry &e : kIpls) {
         if (!(e.shape == shape_of(p, 0))) continue;

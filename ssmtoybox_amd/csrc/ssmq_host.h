@@ -6,6 +6,7 @@
 #include <initializer_list>
 #include <mutex>
 #include <string>
+#include <functional>
 #include <vector>
 #include "ssmq_device.h"
 #include "ssmq_wide.h"
@@ -603,51 +604,58 @@ struct DeviceImage {
     }
 };
 
-// Iterated posterior linearisation pass (ssmq_filter_iterated.hip, ssmq_filter_iterated_dev): `iterations` measurement updates per step,
-// each re-linearised around the current posterior; delta [T][ld] or null.  The whole pass in one launch of k_iplf_loop<>: 1 launched
-// (dry_run: a kernel exists, its name set), 0 no kernel for this pair, < 0 error; a pair with a user integrand runs the instantiation
-// compiled for it at run time (ssmq_rtc.hip) or is an error
-struct IplfArgs;                              // ssmq_iterated_kernel.h
-IplfArgs iplf_args(const FilterPass &p, int iterations, double *delta);
-int try_launch_iterated(const FilterPass &p, int iterations, double *delta);
-int rtc_launch_iterated(const FilterPass &p, int iterations, double *delta);
-// ... and the launch loop of every other pair: per step apply dyn, then iterations x (apply obs | k_iplf_update); ws: iterated_ws_bytes()
-// bytes, tvec: device [T] holding 0 .. T-1
-size_t iterated_ws_bytes(int D, int Y, int64_t ld);
-int iterated_launch_loop(ssmq_transform *h_dyn, ssmq_transform *h_obs, const FilterPass &p, int iterations, double *delta,
-                         const double *tvec, void *ws);
-
-// Outlier-robust pass (ssmq_filter_robust.hip, ssmq_filter_robust_dev): the measurement update under Student-t noise of scale R and
-// `dof` degrees of freedom, `iterations` - 1 rounds of its fixed point per step.  The pass is built WITHOUT R (p.rr: zeros - the
-// measurement transform adds no noise); R and its inverse travel here, device [Y*Y] each.  try_launch_robust / rtc_launch_robust /
-// robust_launch_loop: as their iterated twins above.
+// The measurement-update variants of the additive-noise Gaussian filters - the iterated posterior linearisation pass
+// (ssmq_filter_iterated.hip: `iterations` updates per step, each re-linearised around the current posterior), the outlier-robust pass
+// (ssmq_filter_robust.hip: Student-t noise of scale R and `dof` degrees of freedom, `iterations` - 1 rounds of its fixed point per
+// step) and the masked pass (ssmq_filter_masked.hip: the components a bit mask marks as observed, behind a chi-square gate).  The
+// robust and the masked pass are built WITHOUT R (p.rr: zeros - the measurement transform adds no noise); R | R^-1 and R | gate travel
+// in their own structs, device pointers.  try_launch_*: the whole pass in one launch of k_*_loop<>: 1 launched (dry_run: a kernel
+// exists, its name set), 0 no kernel for this pair, < 0 error; a pair with a user integrand runs the instantiation compiled for it at
+// run time (rtc_launch_pass) or is an error.  *_launch_loop: every other pair, through update_launch_loop.
+struct IplfPass {
+    int iterations;
+    double *delta;                            // [T][ld] or null
+};
 struct RobustPass {
     int iterations;
     double dof;
-    const double *rr, *ir;
+    const double *rr, *ir;                    // [Y*Y] each
     double *lam, *delta;                      // [T][ld] each
 };
-struct RobustArgs;                            // ssmq_robust_kernel.h
-RobustArgs robust_args(const FilterPass &p, const RobustPass &r);
-int try_launch_robust(const FilterPass &p, const RobustPass &r);
-int rtc_launch_robust(const FilterPass &p, const RobustPass &r);
-size_t robust_ws_bytes(int D, int Y, int64_t ld);
-int robust_launch_loop(ssmq_transform *h_dyn, ssmq_transform *h_obs, const FilterPass &p, const RobustPass &r, const double *tvec, void *ws);
-
-// Masked pass (ssmq_filter_masked.hip, ssmq_filter_masked_dev): the measurement update over the components a bit mask marks as
-// observed, behind a chi-square gate.  The pass is built WITHOUT R, as the robust pass; R [Y*Y] and the gate table [Y+1] travel here
-// (device).  try_launch_masked / rtc_launch_masked / masked_launch_loop: as their robust twins above (ws: robust_ws_bytes()).
 struct MaskedPass {
     const uint32_t *mask;                     // [T][ld] or null: NaN = missing
-    const double *rr, *gate;
+    const double *rr, *gate;                  // [Y*Y], [Y+1]
     uint32_t *used;                           // [T][ld]
     double *nis, *ll;                         // [T][ld] each
 };
-struct MaskedArgs;                            // ssmq_masked_kernel.h
-MaskedArgs masked_args(const FilterPass &p, const MaskedPass &r);
+int try_launch_iterated(const FilterPass &p, const IplfPass &r);
+int try_launch_robust(const FilterPass &p, const RobustPass &r);
 int try_launch_masked(const FilterPass &p, const MaskedPass &r);
-int rtc_launch_masked(const FilterPass &p, const MaskedPass &r);
+int iterated_launch_loop(ssmq_transform *h_dyn, ssmq_transform *h_obs, const FilterPass &p, const IplfPass &r, const double *tvec, void *ws);
+int robust_launch_loop(ssmq_transform *h_dyn, ssmq_transform *h_obs, const FilterPass &p, const RobustPass &r, const double *tvec, void *ws);
 int masked_launch_loop(ssmq_transform *h_dyn, ssmq_transform *h_obs, const FilterPass &p, const MaskedPass &r, const double *tvec, void *ws);
+// What the three share.  The launch loop (ssmq_filter.hip): per step apply dyn, then `napply` x (apply obs | item).  The first
+// application of the measurement transform is at the prior, every later one at the iterate planes the item before it wrote; the last
+// item writes plane k of p.fm / p.fP.  item(c, last): fills its per-item arguments from c (launch_item_update, ssmq_filter_shapes.h)
+// and launches its kernel.  ws: update_ws_bytes() bytes, tvec: device [T] holding 0 .. T-1 (the pass's constants).  Plain launches
+// on p.s, no graph.
+struct ItemPlanes {
+    const double *m_pr, *P_pr;        // the prior of the step
+    const double *m_at, *P_at;        // where the measurement transform was applied: the prior, or the iterate
+    const double *y_mean, *P_y, *P_yx, *y;
+    double *m_out, *P_out;
+    int32_t *status;
+    const int32_t *st_dyn, *st_obs;
+    int64_t B, ld;
+    int32_t step, D, Y;
+};
+size_t update_ws_bytes(int D, int Y, int64_t ld);
+int update_launch_loop(ssmq_transform *h_dyn, ssmq_transform *h_obs, const FilterPass &p, int napply, const double *tvec, void *ws,
+                       const std::function<int(const ItemPlanes &c, bool last)> &item);
+// A whole-pass kernel for a pair with a user member, compiled at run time (ssmq_rtc.hip): kind SSMQ_RTC_ITERATED, _ROBUST, _MASKED or
+// _SMOOTHER_ITERATED; args: the kernel's argument block (fd, fo: its FPar members, B: its batch), the grid ceil(B / 64) of the AOT
+// launchers.  Returns as try_launch_*.
+int rtc_launch_pass(const FilterPass &p, int kind, void *args, FPar *fd, FPar *fo, int64_t B);
 // k_detection_mask (ssmq_filter_masked.hip): p_detect host [Y], Y <= SSMQ_MAX_DIM
 int launch_detection_mask(int64_t B, int64_t ld, int T, int Y, const double *p_detect, uint64_t seed, uint64_t traj_offset, int per_component,
                           uint32_t *d_mask, hipStream_t s);
@@ -667,7 +675,6 @@ struct IplsPlanes {
 struct IplsArgs;                              // ssmq_ipls_kernel.h
 IplsArgs ipls_args(const FilterPass &p, const IplsPlanes &q);
 int try_launch_ipls(const FilterPass &p, const IplsPlanes &q);
-int rtc_launch_ipls(const FilterPass &p, const IplsPlanes &q);
 
 // error sums over a batch of filtered trajectories (ssmq_metrics.hip)
 int metrics_values_per_step(int D);

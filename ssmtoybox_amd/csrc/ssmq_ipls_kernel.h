@@ -239,8 +239,7 @@ __device__ __forceinline__ bool ipls_back(const double (&mf)[D], const double (&
 // One iteration: the forward sweep, then the backward sweep, one trajectory per lane, grid of ceil(B / 64) blocks.  Launch bounds:
 // those of k_iplf_loop<> of the same shape.  A lane that fails - or failed in an earlier iteration - writes NaN to every output.
 template <int D, int Y, int ND, int NO, int FD, int FO, int FORM, int TP, int SELO>
-__global__ __launch_bounds__(kSmallBlock, (SSMQ_FUSED_FORCE_OCC ? SSMQ_FUSED_FORCE_OCC
-                                           : (D >= 6 ? 1 : ((D >= 5 && FORM == SSMQ_FORM_SIGMA) ? SSMQ_FUSED_OCC_D5_SIGMA : 2)))) void k_ipls_pass(const IplsArgs a) {
+__global__ SSMQ_PASS_LAUNCH_BOUNDS(D, FORM) void k_ipls_pass(const IplsArgs a) {
     const uint32_t b = blockIdx.x * kSmallBlock + threadIdx.x;
     if ((int64_t)b >= a.B) return;
     const int64_t ld = a.ld;

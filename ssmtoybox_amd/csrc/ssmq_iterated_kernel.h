@@ -20,7 +20,8 @@ struct IplfArgs {
     double *fm, *fP;            // [T][D][ld], [T][D*D][ld]
     double *delta;              // [T][ld] or null: max_d |m_J - m_{J-1}| / sqrt(P_J[d][d]) of every step
     int32_t *status;            // [B]: 0 or 1 + first failing step
-    const double *c_dyn, *c_obs, *gqg, *rr;
+    const double *c_dyn, *c_obs, *gqg;
+    const double *radd;         // [Y*Y]: what the measurement transform adds to its covariance (here R, at every iterate)
     int64_t B, ld;
     int32_t T, iters, emv_dyn, emv_obs;
     double nu_dyn, nu_obs;
@@ -156,10 +157,9 @@ __device__ __forceinline__ double iplf_delta(int d_rt, const double *mn, const d
     return worst;
 }
 
-// The whole pass: one trajectory per lane, grid of ceil(B / 64) blocks.  Launch bounds: those of k_filter_fused<> of the same shape.
+// The whole pass: one trajectory per lane, grid of ceil(B / 64) blocks.
 template <int D, int Y, int ND, int NO, int FD, int FO, int FORM, int TP, int SELO, int OPT>
-__global__ __launch_bounds__(kSmallBlock, (SSMQ_FUSED_FORCE_OCC ? SSMQ_FUSED_FORCE_OCC
-                                           : (D >= 6 ? 1 : ((D >= 5 && FORM == SSMQ_FORM_SIGMA) ? SSMQ_FUSED_OCC_D5_SIGMA : 2)))) void k_iplf_loop(const IplfArgs a) {
+__global__ SSMQ_PASS_LAUNCH_BOUNDS(D, FORM) void k_iplf_loop(const IplfArgs a) {
     const uint32_t b = blockIdx.x * kSmallBlock + threadIdx.x;
     if ((int64_t)b >= a.B) return;
     const int64_t ld = a.ld;
@@ -172,7 +172,7 @@ __global__ __launch_bounds__(kSmallBlock, (SSMQ_FUSED_FORCE_OCC ? SSMQ_FUSED_FOR
 #pragma unroll
         for (int j = 0; j <= i; ++j) Pl[SSMQ_PK(i, j)] = a.P0[(i * D + j) * ld + b];
     const CoreParams cpd{(cdouble_p)a.c_dyn, (cdouble_p)a.gqg, a.emv_dyn, a.nu_dyn, 1.0, 1.0};
-    const CoreParams cpo{(cdouble_p)a.c_obs, (cdouble_p)a.rr, a.emv_obs, a.nu_obs, 1.0, 1.0};
+    const CoreParams cpo{(cdouble_p)a.c_obs, (cdouble_p)a.radd, a.emv_obs, a.nu_obs, 1.0, 1.0};
     FPar fd = a.fd, fo = a.fo;
     const double nan = __builtin_nan("");
     int32_t agg = 0;       // 1 + first failing step

@@ -22,7 +22,7 @@ struct RobustArgs {
     double *lam, *delta;        // [T][ld] each: the weight the update used, |lambda_{J-1} - lambda_{J-2}| / lambda_{J-1}
     int32_t *status;            // [B]: 0 or 1 + first failing step
     const double *c_dyn, *c_obs, *gqg;
-    const double *zero;         // [Y*Y] zeros: what the measurement transform adds to its covariance (P_h carries no noise)
+    const double *radd;         // [Y*Y]: what the measurement transform adds to its covariance (here zeros: P_h carries no noise)
     const double *rr, *ir;      // [Y*Y] each: the scale matrix R and its inverse (lower triangles read)
     int64_t B, ld;
     int32_t T, iters, emv_dyn, emv_obs;
@@ -173,10 +173,9 @@ __device__ __forceinline__ bool robust_update(int d_rt, int y_rt, int iters, dou
     return ok;
 }
 
-// The whole pass: one trajectory per lane, grid of ceil(B / 64) blocks.  Launch bounds: those of k_filter_fused<> of the same shape.
+// The whole pass: one trajectory per lane, grid of ceil(B / 64) blocks.
 template <int D, int Y, int ND, int NO, int FD, int FO, int FORM, int TP, int SELO, int OPT = 0>
-__global__ __launch_bounds__(kSmallBlock, (SSMQ_FUSED_FORCE_OCC ? SSMQ_FUSED_FORCE_OCC
-                                           : (D >= 6 ? 1 : ((D >= 5 && FORM == SSMQ_FORM_SIGMA) ? SSMQ_FUSED_OCC_D5_SIGMA : 2)))) void k_robust_loop(const RobustArgs a) {
+__global__ SSMQ_PASS_LAUNCH_BOUNDS(D, FORM) void k_robust_loop(const RobustArgs a) {
     const uint32_t b = blockIdx.x * kSmallBlock + threadIdx.x;
     if ((int64_t)b >= a.B) return;
     const int64_t ld = a.ld;
@@ -189,7 +188,7 @@ __global__ __launch_bounds__(kSmallBlock, (SSMQ_FUSED_FORCE_OCC ? SSMQ_FUSED_FOR
 #pragma unroll
         for (int j = 0; j <= i; ++j) Pl[SSMQ_PK(i, j)] = a.P0[(i * D + j) * ld + b];
     const CoreParams cpd{(cdouble_p)a.c_dyn, (cdouble_p)a.gqg, a.emv_dyn, a.nu_dyn, 1.0, 1.0};
-    const CoreParams cpo{(cdouble_p)a.c_obs, (cdouble_p)a.zero, a.emv_obs, a.nu_obs, 1.0, 1.0};
+    const CoreParams cpo{(cdouble_p)a.c_obs, (cdouble_p)a.radd, a.emv_obs, a.nu_obs, 1.0, 1.0};
     FPar fd = a.fd, fo = a.fo;
     const double nan = __builtin_nan("");
     int32_t agg = 0;       // 1 + first failing step

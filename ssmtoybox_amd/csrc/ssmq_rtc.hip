@@ -347,24 +347,26 @@ std::string innovation_expr(int D, int Y, int ND, int NO, int FD, int FO, int fo
     snprintf(b, sizeof(b), "ssmq::k_innovation<%d, %d, %d, %d, %d, %d, %d, %d, %d, %d>", D, Y, ND, NO, FD, FO, form, tp, selo, opt);
     return b;
 }
-std::string iterated_expr(int D, int Y, int ND, int NO, int FD, int FO, int form, int tp, int selo) {
-    char b[256];
-    snprintf(b, sizeof(b), "ssmq::k_iplf_loop<%d, %d, %d, %d, %d, %d, %d, %d, %d, 0>", D, Y, ND, NO, FD, FO, form, tp, selo);
-    return b;
+// The whole-pass kernels of the measurement-update variants and of the iterated smoother: kind, kernel, the format of its template
+// id (D, Y, ND, NO, FD, FO, FORM, TP, SELO; the three passes: the dense kernel, OPT 0), its argument type, what errors call the pass
+struct PassKernel {
+    int kind;
+    const char *kernel, *expr_fmt, *args_type, *pass;
+};
+static const PassKernel kPassKernels[] = {
+    {SSMQ_RTC_ITERATED, "k_iplf_loop", "ssmq::k_iplf_loop<%d, %d, %d, %d, %d, %d, %d, %d, %d, 0>", "ssmq::IplfArgs", "iterated pass"},
+    {SSMQ_RTC_ROBUST, "k_robust_loop", "ssmq::k_robust_loop<%d, %d, %d, %d, %d, %d, %d, %d, %d, 0>", "ssmq::RobustArgs", "robust pass"},
+    {SSMQ_RTC_MASKED, "k_masked_loop", "ssmq::k_masked_loop<%d, %d, %d, %d, %d, %d, %d, %d, %d, 0>", "ssmq::MaskedArgs", "masked pass"},
+    {SSMQ_RTC_SMOOTHER_ITERATED, "k_ipls_pass", "ssmq::k_ipls_pass<%d, %d, %d, %d, %d, %d, %d, %d, %d>", "ssmq::IplsArgs", "iterated smoother"},
+};
+static const PassKernel *pass_kernel(int kind) {
+    for (const PassKernel &k : kPassKernels)
+        if (k.kind == kind) return &k;
+    return nullptr;
 }
-std::string robust_expr(int D, int Y, int ND, int NO, int FD, int FO, int form, int tp, int selo) {
+static std::string pass_expr(const PassKernel &k, int D, int Y, int ND, int NO, int FD, int FO, int form, int tp, int selo) {
     char b[256];
-    snprintf(b, sizeof(b), "ssmq::k_robust_loop<%d, %d, %d, %d, %d, %d, %d, %d, %d, 0>", D, Y, ND, NO, FD, FO, form, tp, selo);
-    return b;
-}
-std::string masked_expr(int D, int Y, int ND, int NO, int FD, int FO, int form, int tp, int selo) {
-    char b[256];
-    snprintf(b, sizeof(b), "ssmq::k_masked_loop<%d, %d, %d, %d, %d, %d, %d, %d, %d, 0>", D, Y, ND, NO, FD, FO, form, tp, selo);
-    return b;
-}
-std::string ipls_expr(int D, int Y, int ND, int NO, int FD, int FO, int form, int tp, int selo) {
-    char b[256];
-    snprintf(b, sizeof(b), "ssmq::k_ipls_pass<%d, %d, %d, %d, %d, %d, %d, %d, %d>", D, Y, ND, NO, FD, FO, form, tp, selo);
+    snprintf(b, sizeof(b), k.expr_fmt, D, Y, ND, NO, FD, FO, form, tp, selo);
     return b;
 }
 std::string apply_expr(int D, int E, int N, int F, int form, int tp, int sel, int opt, bool nts) {
@@ -512,110 +514,35 @@ int rtc_launch_innovation(const FilterPass &p, const InnovOut &o) {
     return rc ? rc : 1;
 }
 
-// k_iplf_loop<> (ssmq_iterated_kernel.h) for a pair with a user member: the shape checks and the time tables of
-// rtc_launch_innovation, the dense kernel (OPT 0), the grid and the argument block of the AOT launcher (ssmq_filter_iterated.hip)
-int rtc_launch_iterated(const FilterPass &p, int iterations, double *delta) {
+// A whole-pass kernel of kPassKernels for a pair with a user member: the shape checks and the time tables of rtc_launch_innovation,
+// the grid of the AOT launchers; the caller built the argument block as for them
+int rtc_launch_pass(const FilterPass &p, int kind, void *args, FPar *fd, FPar *fo, int64_t B) {
+    const PassKernel *found = pass_kernel(kind);
+    if (!found) {
+        set_error("rtc_launch_pass: not a whole-pass kernel kind");
+        return SSMQ_E_ARG;
+    }
+    const PassKernel &pk = *found;
     std::vector<int> ids;
     int rc = user_pair_shape(p, &ids);
     if (rc) return rc;
     const ssmq_transform *hd = p.hd, *ho = p.ho;
-    const std::string expr = iterated_expr(hd->D, ho->E, hd->N, ho->N, p.fd->id, p.fo->id, hd->form, hd->tp_nu > 0.0 ? 1 : 0, 0);
-    const char *what = "k_iplf_loop (run-time compiled)";
+    const std::string expr = pass_expr(pk, hd->D, ho->E, hd->N, ho->N, p.fd->id, p.fo->id, hd->form, hd->tp_nu > 0.0 ? 1 : 0, 0);
+    const std::string what = std::string(pk.kernel) + " (run-time compiled)";
     if (p.dry_run) {
-        rc = launch_compiled(expr, "ssmq::IplfArgs", ids, nullptr, 0, kSmallBlock, p.s, p.name, true, what);
+        rc = launch_compiled(expr, pk.args_type, ids, nullptr, 0, kSmallBlock, p.s, p.name, true, what.c_str());
         return rc ? rc : 1;
     }
-    IplfArgs a = iplf_args(p, iterations, delta);
     for (const ssmq_integrand *f : {p.fd, p.fo}) {
-        const double *tab = f == p.fd ? a.fd.ttab : a.fo.ttab;
+        const double *tab = f == p.fd ? fd->ttab : fo->ttab;
         if (!is_user_integrand(f) && has_time_table(f->id) && !tab) {
-            set_error("run-time compiled iterated pass: the time table of built-in integrand " + std::to_string(f->id) + " is missing");
+            set_error(std::string("run-time compiled ") + pk.pass + ": the time table of built-in integrand " + std::to_string(f->id) + " is missing");
             return SSMQ_E_ARG;
         }
     }
-    if (is_user_integrand(p.fd)) a.fd.ttab = nullptr;   // (user integrands evaluate their time dependence themselves)
-    if (is_user_integrand(p.fo)) a.fo.ttab = nullptr;
-    rc = launch_compiled(expr, "ssmq::IplfArgs", ids, &a, (unsigned)((a.B + kSmallBlock - 1) / kSmallBlock), kSmallBlock, p.s, p.name, false, what);
-    return rc ? rc : 1;
-}
-
-// k_robust_loop<> (ssmq_robust_kernel.h) for a pair with a user member: the checks of rtc_launch_iterated, the grid and the argument
-// block of the AOT launcher (ssmq_filter_robust.hip)
-int rtc_launch_robust(const FilterPass &p, const RobustPass &r) {
-    std::vector<int> ids;
-    int rc = user_pair_shape(p, &ids);
-    if (rc) return rc;
-    const ssmq_transform *hd = p.hd, *ho = p.ho;
-    const std::string expr = robust_expr(hd->D, ho->E, hd->N, ho->N, p.fd->id, p.fo->id, hd->form, hd->tp_nu > 0.0 ? 1 : 0, 0);
-    const char *what = "k_robust_loop (run-time compiled)";
-    if (p.dry_run) {
-        rc = launch_compiled(expr, "ssmq::RobustArgs", ids, nullptr, 0, kSmallBlock, p.s, p.name, true, what);
-        return rc ? rc : 1;
-    }
-    RobustArgs a = robust_args(p, r);
-    for (const ssmq_integrand *f : {p.fd, p.fo}) {
-        const double *tab = f == p.fd ? a.fd.ttab : a.fo.ttab;
-        if (!is_user_integrand(f) && has_time_table(f->id) && !tab) {
-            set_error("run-time compiled robust pass: the time table of built-in integrand " + std::to_string(f->id) + " is missing");
-            return SSMQ_E_ARG;
-        }
-    }
-    if (is_user_integrand(p.fd)) a.fd.ttab = nullptr;   // (user integrands evaluate their time dependence themselves)
-    if (is_user_integrand(p.fo)) a.fo.ttab = nullptr;
-    rc = launch_compiled(expr, "ssmq::RobustArgs", ids, &a, (unsigned)((a.B + kSmallBlock - 1) / kSmallBlock), kSmallBlock, p.s, p.name, false, what);
-    return rc ? rc : 1;
-}
-
-// k_masked_loop<> (ssmq_masked_kernel.h) for a pair with a user member: as rtc_launch_robust
-int rtc_launch_masked(const FilterPass &p, const MaskedPass &r) {
-    std::vector<int> ids;
-    int rc = user_pair_shape(p, &ids);
-    if (rc) return rc;
-    const ssmq_transform *hd = p.hd, *ho = p.ho;
-    const std::string expr = masked_expr(hd->D, ho->E, hd->N, ho->N, p.fd->id, p.fo->id, hd->form, hd->tp_nu > 0.0 ? 1 : 0, 0);
-    const char *what = "k_masked_loop (run-time compiled)";
-    if (p.dry_run) {
-        rc = launch_compiled(expr, "ssmq::MaskedArgs", ids, nullptr, 0, kSmallBlock, p.s, p.name, true, what);
-        return rc ? rc : 1;
-    }
-    MaskedArgs a = masked_args(p, r);
-    for (const ssmq_integrand *f : {p.fd, p.fo}) {
-        const double *tab = f == p.fd ? a.fd.ttab : a.fo.ttab;
-        if (!is_user_integrand(f) && has_time_table(f->id) && !tab) {
-            set_error("run-time compiled masked pass: the time table of built-in integrand " + std::to_string(f->id) + " is missing");
-            return SSMQ_E_ARG;
-        }
-    }
-    if (is_user_integrand(p.fd)) a.fd.ttab = nullptr;   // (user integrands evaluate their time dependence themselves)
-    if (is_user_integrand(p.fo)) a.fo.ttab = nullptr;
-    rc = launch_compiled(expr, "ssmq::MaskedArgs", ids, &a, (unsigned)((a.B + kSmallBlock - 1) / kSmallBlock), kSmallBlock, p.s, p.name, false, what);
-    return rc ? rc : 1;
-}
-
-// k_ipls_pass<> (ssmq_ipls_kernel.h), one iteration of the smoother, for a pair with a user member: the checks of
-// rtc_launch_iterated, the grid and the argument block of the AOT launcher (ssmq_filter_ipls.hip)
-int rtc_launch_ipls(const FilterPass &p, const IplsPlanes &q) {
-    std::vector<int> ids;
-    int rc = user_pair_shape(p, &ids);
-    if (rc) return rc;
-    const ssmq_transform *hd = p.hd, *ho = p.ho;
-    const std::string expr = ipls_expr(hd->D, ho->E, hd->N, ho->N, p.fd->id, p.fo->id, hd->form, hd->tp_nu > 0.0 ? 1 : 0, 0);
-    const char *what = "k_ipls_pass (run-time compiled)";
-    if (p.dry_run) {
-        rc = launch_compiled(expr, "ssmq::IplsArgs", ids, nullptr, 0, kSmallBlock, p.s, p.name, true, what);
-        return rc ? rc : 1;
-    }
-    IplsArgs a = ipls_args(p, q);
-    for (const ssmq_integrand *f : {p.fd, p.fo}) {
-        const double *tab = f == p.fd ? a.fd.ttab : a.fo.ttab;
-        if (!is_user_integrand(f) && has_time_table(f->id) && !tab) {
-            set_error("run-time compiled iterated smoother: the time table of built-in integrand " + std::to_string(f->id) + " is missing");
-            return SSMQ_E_ARG;
-        }
-    }
-    if (is_user_integrand(p.fd)) a.fd.ttab = nullptr;   // (user integrands evaluate their time dependence themselves)
-    if (is_user_integrand(p.fo)) a.fo.ttab = nullptr;
-    rc = launch_compiled(expr, "ssmq::IplsArgs", ids, &a, (unsigned)((a.B + kSmallBlock - 1) / kSmallBlock), kSmallBlock, p.s, p.name, false, what);
+    if (is_user_integrand(p.fd)) fd->ttab = nullptr;   // (user integrands evaluate their time dependence themselves)
+    if (is_user_integrand(p.fo)) fo->ttab = nullptr;
+    rc = launch_compiled(expr, pk.args_type, ids, args, (unsigned)((B + kSmallBlock - 1) / kSmallBlock), kSmallBlock, p.s, p.name, false, what.c_str());
     return rc ? rc : 1;
 }
 
@@ -977,15 +904,14 @@ extern "C" int ssmq_rtc_compile_check(int32_t id, int32_t id_obs, int kind, int 
         form = SSMQ_FORM_SIGMA;
         tp = opt = 0;
     }
-    if (!arch || !*arch || (kind != SSMQ_RTC_FILTER && kind != SSMQ_RTC_APPLY && kind != SSMQ_RTC_MC && kind != SSMQ_RTC_INNOVATION && kind != SSMQ_RTC_ITERATED &&
-                            kind != SSMQ_RTC_SMOOTHER_ITERATED && kind != SSMQ_RTC_ROBUST && kind != SSMQ_RTC_MASKED) ||
-        ((kind == SSMQ_RTC_ITERATED || kind == SSMQ_RTC_SMOOTHER_ITERATED || kind == SSMQ_RTC_ROBUST || kind == SSMQ_RTC_MASKED) && opt != 0) || (form != SSMQ_FORM_BQ && form != SSMQ_FORM_SIGMA) ||
+    const PassKernel *pk = pass_kernel(kind);   // the whole-pass kernels of the update variants and the smoother: dense alone
+    if (!arch || !*arch || (kind != SSMQ_RTC_FILTER && kind != SSMQ_RTC_APPLY && kind != SSMQ_RTC_MC && kind != SSMQ_RTC_INNOVATION && !pk) ||
+        (pk && opt != 0) || (form != SSMQ_FORM_BQ && form != SSMQ_FORM_SIGMA) ||
         tp < 0 || tp > 1 || (opt != 0 && opt != 1 && opt != 2 && opt != 3 && opt != 7)) {
         set_error("ssmq_rtc_compile_check: bad argument");
         return SSMQ_E_ARG;
     }
-    const bool pair = kind == SSMQ_RTC_FILTER || kind == SSMQ_RTC_INNOVATION || kind == SSMQ_RTC_ITERATED || kind == SSMQ_RTC_SMOOTHER_ITERATED ||
-                      kind == SSMQ_RTC_ROBUST || kind == SSMQ_RTC_MASKED;      // (id, id_obs): the two models of a filter
+    const bool pair = kind == SSMQ_RTC_FILTER || kind == SSMQ_RTC_INNOVATION || pk;      // (id, id_obs): the two models of a filter
     std::string why;
     if (kind != SSMQ_RTC_MC && (!shape_ok(D, E, N, &why) || (pair && !shape_ok(D, D, N_obs, &why)))) {
         set_error(why);
@@ -1001,17 +927,11 @@ extern "C" int ssmq_rtc_compile_check(int32_t id, int32_t id_obs, int kind, int 
     if (pair && is_user_integrand(id_obs) && id_obs != id) ids.push_back(id_obs);
     const std::string expr = kind == SSMQ_RTC_FILTER       ? fused_expr(D, E, N, N_obs, id, id_obs, form, tp, 0, opt, -1)
                              : kind == SSMQ_RTC_INNOVATION ? innovation_expr(D, E, N, N_obs, id, id_obs, form, tp, 0, opt)
-                             : kind == SSMQ_RTC_ITERATED   ? iterated_expr(D, E, N, N_obs, id, id_obs, form, tp, 0)
-                             : kind == SSMQ_RTC_SMOOTHER_ITERATED ? ipls_expr(D, E, N, N_obs, id, id_obs, form, tp, 0)
-                             : kind == SSMQ_RTC_ROBUST     ? robust_expr(D, E, N, N_obs, id, id_obs, form, tp, 0)
-                             : kind == SSMQ_RTC_MASKED     ? masked_expr(D, E, N, N_obs, id, id_obs, form, tp, 0)
+                             : pk                          ? pass_expr(*pk, D, E, N, N_obs, id, id_obs, form, tp, 0)
                              : kind == SSMQ_RTC_MC         ? "ssmq::k_mc_moments<" + std::to_string(id) + ", " + std::to_string(D) + ", " + std::to_string(E) + ", 0>"
                                                            : apply_expr(D, E, N, id, form, tp, 0, opt, false);
     return compile_check_text(expr, kind == SSMQ_RTC_FILTER ? "ssmq::FusedArgs" : kind == SSMQ_RTC_INNOVATION ? "ssmq::InnovArgs"
-                                    : kind == SSMQ_RTC_ITERATED ? "ssmq::IplfArgs"
-                                    : kind == SSMQ_RTC_SMOOTHER_ITERATED ? "ssmq::IplsArgs"
-                                    : kind == SSMQ_RTC_ROBUST ? "ssmq::RobustArgs"
-                                    : kind == SSMQ_RTC_MASKED ? "ssmq::MaskedArgs"
+                                    : pk ? pk->args_type
                                     : kind == SSMQ_RTC_MC   ? "ssmq::McMomArgs" : "ssmq::ApplyArgs", ids, arch, log, len);
 }
 
